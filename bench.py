@@ -21,16 +21,23 @@ reduction, RCCL all-reduce across ranks when N>1, divide).  Workloads (SURVEY 8(
        partitions exceed 8 and go through Murty-200 (murty_jobs_kernel, the dominant kernel of this workload: latency-bound
        assignment searches, its "roofline" line is there for the record).  Re-seeded.
 
-  python bench.py --gpus N --steps K --warmup W [--workload c2a|c2b|c3|c4|c5]
+  python bench.py --gpus N --steps K --warmup W [--workload c2a|c2b|c3|c4|c5] [--dump-outputs DIR] [--full]
   N>1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 Particles shard across ranks with no data-path collective except the 2-double all-reduce (weak scaling).  Rank 0 prints
-ONE JSON line.  roofline.achieved = SURVEY 8(d)'s bytes_step / the fused step kernel's average HIP-event duration inside the
-timed region; roofline.traffic = HBM bytes per launch from rocprofv3 PMC passes (FETCH_SIZE, WRITE_SIZE) of this same
-workload, collected live by two short child runs (N = 1, rank 0; --no-pmc skips them); roofline.valu_issue_frac (what binds) from a
-third, SQ-counter pass; roofline.flop_frac = SURVEY 8(d)'s algorithmic fp64 flops / kernel time / 78.6 TFLOP/s.  cpu_baseline = the
-oracle's restatement timed on the host cores (two labelled figures), boundary = what an update costs through the reference-side
-binding and under the unmodified reference driver, config.distributed = world size / backend / PCI bus ids / the collective's form.
+ONE JSON line.  A plain run sets up, warms up, times the K steps and prints the line (ms_per_step = wall milliseconds of one
+timed step).  roofline.achieved = SURVEY 8(d)'s bytes_step / the fused step kernel's average HIP-event duration inside the
+timed region; roofline.flop_frac = SURVEY 8(d)'s algorithmic fp64 flops / kernel time / 78.6 TFLOP/s.
+
+--full adds what takes runs of its own: roofline.traffic = HBM bytes per launch from rocprofv3 PMC passes (FETCH_SIZE,
+WRITE_SIZE) of this same workload, collected live by two short child runs (N = 1, rank 0; --no-pmc skips them);
+roofline.valu_issue_frac (what binds) from a third, SQ-counter pass; the stand-alone phase kernels and the likelihood sweep
+(an untimed phase-by-phase pass); cpu_baseline = the oracle's restatement timed on the host cores (two labelled figures);
+boundary = what an update costs through the reference-side binding and under the unmodified reference driver; with N > 1 the
+same shard without the collective and one global resampling step with migration.  config.distributed = world size /
+backend / PCI bus ids / the collective's form.
+
+--dump-outputs DIR writes what the last timed step computed, as a caller of the path receives it (see dump_outputs).
 """
 import os
 import argparse
@@ -363,6 +370,35 @@ def live_issue(kernel_prefix, child_args, timeout_s=240, also=None):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+DUMP_MAX_PARTICLES = 512       # mixtures of at most this many particles (a fixed, seeded sample): <= 512 x cap x 13 doubles
+
+
+def dump_outputs(f, out_dir, suffix=""):
+    """What the last timed step left in the filter, as a caller of the path receives it: the particle weights and every
+    particle's mixture size (all particles), and the Gaussian mixtures (rfsgpu_export_gm: weight, weight before the update,
+    mean, covariance) of a fixed sample of the particles, concatenated in particle order (gm_sizes[gm_particles] delimits
+    them).  float64 throughout; the sample depends on the particle count only, so that two builds compare file for file."""
+    os.makedirs(out_dir, exist_ok=True)
+    n = f.n
+    w = np.asarray(f.get_weights(), dtype=np.float64)
+    sizes = np.asarray(f.gm_sizes()).astype(np.float64)
+    if n <= DUMP_MAX_PARTICLES:
+        idx = np.arange(n)
+    else:
+        idx = np.sort(np.random.default_rng(20240601).choice(n, DUMP_MAX_PARTICLES, replace=False))
+    gw, gwp, gm, gc = [], [], [], []
+    for i in idx:
+        a, b, m, c = f.export_gm(int(i))
+        gw.append(a); gwp.append(b); gm.append(m); gc.append(c)
+    arrays = dict(weights=w, gm_sizes=sizes, gm_particles=idx.astype(np.float64),
+                  gm_weight=np.concatenate(gw), gm_weight_prev=np.concatenate(gwp),
+                  gm_mean=np.concatenate(gm), gm_cov=np.concatenate(gc))
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + suffix + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+    return sorted(arrays)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
 def boundary_cost(pkg, sc, wl, n_local, CAP, scen, local_rank):
     """What RBPHDFilter::update costs THROUGH the drop-in boundary (VERDICT r3 item 7), beside the stream-ordered step the headline
     times.  (a) The call sequence of integration/RBPHDFilter_rfsgpu.hpp::update (:213-235 there; reference include/RBPHDFilter.hpp:
@@ -487,9 +523,12 @@ def main():
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--workload", choices=sorted(WORKLOADS), default=None, help="default: c2a (configs[1]'s shape per GPU) at every --gpus N; c3 = configs[2]'s shard (--workload c3 --gpus 8 is configs[2])")
     ap.add_argument("--particles", type=int, default=None, help="particles per GPU (default: the workload's)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-boundary", action="store_true", help="skip the 'boundary' leg (synchronous binding sequence + the unmodified reference driver)")
-    ap.add_argument("--no-pmc", action="store_true", help="skip the two rocprofv3 PMC child runs (roofline.traffic = null)")
+    ap.add_argument("--full", action="store_true", help="also measure what takes runs of its own: rocprofv3 PMC / SQ passes, the stand-alone "
+                    "phase pass, cpu_baseline, boundary, and with N > 1 the single-shard reference and the resampling step with migration")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed as DIR/<name>.npy (float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-boundary", action="store_true", help="with --full: skip the 'boundary' leg (synchronous binding sequence + the unmodified reference driver)")
+    ap.add_argument("--no-pmc", action="store_true", help="with --full: skip the rocprofv3 PMC child runs (roofline.traffic = null)")
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--cpu-child", type=int, default=0, help=argparse.SUPPRESS)
     args = ap.parse_args()
@@ -820,10 +859,12 @@ def main():
     wsum = float(f.get_weights().sum())
     assert np.isfinite(wsum) and (multi or abs(wsum - 1.0) < 1e-6), "weights did not normalise"
     fused = kern_ms[1] == 0.0 and kern_ms[2] == 0.0
+    if args.dump_outputs:            # the last timed step's outputs, before anything below touches the filter's state
+        dump_outputs(f, args.dump_outputs, "_rank%d" % rank if world > 1 else "")
 
     # weak-scaling reference on the SAME workload: this rank's shard alone, without the collective (N > 1 only)
     solo = None
-    if multi and wl["reseed"]:
+    if args.full and multi and wl["reseed"]:
         ring_refill()
         torch.cuda.synchronize()
         t1 = time.perf_counter()
@@ -841,7 +882,7 @@ def main():
     # per-phase breakdown (and the likelihood-sweep rate the north star asks for): the three stand-alone kernels, HIP events,
     # untimed pass after the region
     phase_ms = kern_ms
-    if fused and wl["reseed"]:
+    if args.full and fused and wl["reseed"]:
         acc = np.zeros(3)
         reps = 20
         f.set_phase_timing(True)      # (update() as three launches, each with its own event pair)
@@ -855,11 +896,12 @@ def main():
 
     if rank == 0:
         per_kernel = {}
+        phases = args.full or not fused       # a fused step has per-phase figures only from the untimed phase pass of --full
         for k, name in enumerate(kernels):
-            if phase_ms[k] > 0:
+            if phases and phase_ms[k] > 0:
                 per_kernel[name] = dict(ms=round(float(phase_ms[k]), 5), design_bytes=int(dbytes[name]),
                                         design_GBps=round(dbytes[name] / (phase_ms[k] * 1e-3) / 1e9, 2))
-        sweep_ms = float(phase_ms[0]) if phase_ms[0] > 0 and not (fused and not wl["reseed"]) else None
+        sweep_ms = float(phase_ms[0]) if phases and phase_ms[0] > 0 and not (fused and not wl["reseed"]) else None
         sweep = None
         if sweep_ms:
             g = bytes_sweep / (sweep_ms * 1e-3) / 1e9
@@ -871,8 +913,10 @@ def main():
         dom_ms = post_ms if murty_dominant else (float(kern_ms[0]) if fused else float(kern_ms.sum()))
         achieved = bytes_step / (dom_ms * 1e-3) / 1e9
         design_total = int(sum(dbytes.values()))
-        traffic, traffic_note = None, "skipped (--no-pmc)" if args.no_pmc else None
-        if not args.no_pmc and not multi and fused:
+        pmc = args.full and not args.no_pmc
+        skipped = "skipped (--no-pmc)" if args.full else "not collected (a run of its own: --full)"
+        traffic, traffic_note = None, None if pmc else skipped
+        if pmc and not multi and fused:
             child = ["--workload", wname, "--no-pmc", "--no-cpu-baseline"] + (["--particles", str(n_local)] if args.particles else [])
             tr, err = live_traffic(dom_name, child)
             if tr is None:
@@ -882,17 +926,17 @@ def main():
                 traffic_note = (f"rocprofv3 --kernel-trace --pmc FETCH_SIZE / --pmc WRITE_SIZE, two child runs of this workload in this invocation: "
                                 f"avg over {tr['launches']} launches, FETCH_SIZE {tr['fetch_size_kib']} KiB, WRITE_SIZE {tr['write_size_kib']} KiB, "
                                 f"bytes = (2*FETCH + WRITE)*1024 (gfx950 correction, MI355X_MICROARCH.md)")
-        elif not args.no_pmc:
+        elif pmc:
             traffic_note = "collected at --gpus 1 only"
-        issue, issue_note = None, "skipped (--no-pmc)" if args.no_pmc else None
-        if not args.no_pmc and not multi and fused:
+        issue, issue_note = None, None if pmc else skipped
+        if pmc and not multi and fused:
             issue, err = live_issue(dom_name, child, also=("vp_update_map_kernel" if vp else "phd_update_map_block_kernel"))
             if issue is None:
                 issue_note = "SQ counter collection failed: " + str(err)
             else:
                 issue_note = ("rocprofv3 --kernel-trace --pmc " + " ".join(SQ_COUNTERS) + ", one child run of this workload in this invocation; "
                               "valu_issue_frac = 4 * SQ_ACTIVE_INST_VALU / (1024 SIMDs * SQ_BUSY_CYCLES / 32 SEs)")
-        elif not args.no_pmc:
+        elif pmc:
             issue_note = "collected at --gpus 1 only"
         sweep_issue = None
         if issue and issue.get("also"):
@@ -984,15 +1028,16 @@ def main():
             collective=(None if not multi else ("inline" if not deferred else ("events" if mode["events"] else "sequence_numbers"))),
             collective_fell_back=(bool(mode["fell_back"]) if deferred else False),
             collective_probe=(probe_note if deferred else None))
+        out["config"]["full"] = bool(args.full)
         if per_step:
             d = np.diff(np.array([t0] + per_step)) * 1e3
             out["config"]["ms_per_step_median"] = round(float(np.median(d)), 5)
             out["config"]["ms_per_step_p90"] = round(float(np.percentile(d, 90)), 5)
         if solo is not None:
             out["config"]["same_workload_single_shard_steps_per_s"] = round(solo, 3)
-        if not args.no_cpu_baseline and not multi:      # (rank 0 at N = 1 only)
+        if args.full and not args.no_cpu_baseline and not multi:      # (rank 0 at N = 1 only)
             out["cpu_baseline"] = cpu_baseline(wname, n_local, args.particles)
-        if not args.no_boundary and not multi and not vp and wl["reseed"]:
+        if args.full and not args.no_boundary and not multi and not vp and wl["reseed"]:
             try:
                 out["boundary"] = boundary_cost(pkg, sc, wl, n_local, CAP, scen, local_rank)
             except Exception as e:   # noqa: BLE001  (a side figure must not cost the line)
@@ -1009,7 +1054,7 @@ def main():
     # One global resampling step with cross-shard migration (N > 1), timed on its own -- LAST, and under a watchdog: it is a side
     # figure, and neither an exception in it nor a collective that never completes may cost the line above.
     migr = None
-    if multi and wl["reseed"]:
+    if args.full and multi and wl["reseed"]:
         import threading
         dist.barrier()
         finished = threading.Event()

@@ -1959,6 +1959,52 @@ def test_bench_two_ranks_on_one_gpu():
     assert d["roofline"]["frac"] > 0
 
 
+def test_bench_plain_run_dumps_the_last_timed_step(pkg, sc, tmp_path):
+    """A plain bench.py run (no --full) times exactly --steps steps, reports none of the side figures, and --dump-outputs writes
+    what the last timed step computed: the same weights and mixtures a direct rfsgpu_step_async on the same seeded state gives."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = str(tmp_path / "dump")
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "7", "--warmup", "2", "--particles", "256",
+           "--dump-outputs", out]
+    r = subprocess.run(cmd, capture_output=True, text=True, cwd=root, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert d["steps"] == 7 and d["warmup"] == 2 and d["unit"] == "steps/s" and d["higher_is_better"] is True and d["dtype"] == "f64"
+    assert abs(d["value"] - 1e3 / d["ms_per_step"]) < 1e-2 * d["value"]
+    assert d["config"]["full"] is False and "cpu_baseline" not in d and "boundary" not in d
+    assert d["roofline"]["traffic"] is None and d["roofline"]["valu_issue"] is None
+    got = {f[:-4]: np.load(os.path.join(out, f)) for f in os.listdir(out)}
+    assert set(got) == {"weights", "gm_sizes", "gm_particles", "gm_weight", "gm_weight_prev", "gm_mean", "gm_cov"}
+    assert all(a.dtype == np.float64 for a in got.values())
+    assert sum(a.nbytes for a in got.values()) <= 64 << 20
+    np.testing.assert_array_equal(got["gm_particles"], np.arange(256))
+    assert got["gm_weight"].shape[0] == got["gm_mean"].shape[0] == got["gm_cov"].shape[0] == int(got["gm_sizes"].sum())
+    # the same seeded input through the launch bench.py times
+    sys.path.insert(0, root)
+    import bench
+    wl = bench.WORKLOADS["c2a"]
+    scen = bench.make_scen(sc, wl, 256)
+    dev = pkg.RBPHDFilter(256, gm_capacity=wl["cap"])
+    sc.load_scenario(dev, scen)
+    dev.step_async(scen["Z"], normalize=True)
+    dev.synchronize()
+    np.testing.assert_allclose(got["weights"], dev.get_weights(), rtol=1e-12, atol=0)
+    np.testing.assert_array_equal(got["gm_sizes"], dev.gm_sizes())
+    o = np.concatenate([[0], np.cumsum(dev.gm_sizes())])
+    for i in (0, 100, 255):
+        w, wp, m, c = dev.export_gm(i)
+        np.testing.assert_allclose(got["gm_weight"][o[i]:o[i + 1]], w, rtol=1e-12, atol=0)
+        np.testing.assert_allclose(got["gm_mean"][o[i]:o[i + 1]], m, rtol=1e-12, atol=1e-300)
+        np.testing.assert_allclose(got["gm_cov"][o[i]:o[i + 1]], c, rtol=1e-12, atol=1e-300)
+    dev.close()
+
+
 def test_full_size_c2(pkg, ob, sc):
     """configs[1]: 2000 particles x 200 GM landmarks x 30 measurements."""
     _full_size_check(pkg, ob, sc, sc.make_scenario(2000, 200, 30, seed=12345), cap=384, fused=(2, 1, 5, 1))   # phd_step_fused_kernel<2, true, 5>

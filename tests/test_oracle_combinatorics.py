@@ -13,7 +13,6 @@ import math
 import os
 
 import numpy as np
-import pytest
 from scipy.optimize import linear_sum_assignment
 
 GOLD = os.path.join(os.path.dirname(__file__), "golden")
@@ -43,16 +42,25 @@ def test_mat_perm_random_vs_bruteforce(ob):
             assert np.isclose(got[b], brute_perm(A[b]), rtol=1e-10, atol=1e-12)
 
 
+def _live_fixture(name):
+    """The reference's answers on the live tests' own inputs (tests/golden/make_live_reference_fixtures.py), for where oracle/_ref
+    is not built."""
+    with open(os.path.join(GOLD, "reference_live_cases.json")) as fh:
+        return json.load(fh)[name]
+
+
 def test_permlex_matches_reference_build(ob):
     ref = ob.load_ref()
-    if ref is None:
-        pytest.skip("oracle/_ref not built (no /root/reference here)")
+    gold = None
+    if ref is None:     # the reference class's own output for the same (nM, nZ), stored by make_combinatorics_fixtures.py
+        with open(os.path.join(GOLD, "permlex.json")) as fh:
+            gold = json.load(fh)
     for nM in range(0, 5):
         for nZ in range(0, 5):
             if nM + nZ == 0:
                 continue
             a = ob.permlex_all(nM, nZ)
-            b = ob.permlex_all(nM, nZ, lib=ref, sym="rfsref_permlex_all")
+            b = ob.permlex_all(nM, nZ, lib=ref, sym="rfsref_permlex_all") if ref is not None else np.array(gold[f"{nM}x{nZ}"])
             assert a.shape == b.shape and np.array_equal(a, b), (nM, nZ)
 
 
@@ -86,14 +94,21 @@ def test_hungarian_vs_scipy(ob):
             assert np.allclose(Cafter, Cm, rtol=0, atol=1e-12)
 
 
+def murty_plain_tables():
+    rng = np.random.default_rng(2)
+    return [rng.uniform(-3, 0, (n, n)) for n in (2, 3, 4, 5, 6)]
+
+
 def test_murty_plain_vs_reference_bruteforce(ob):
     ref = ob.load_ref()
-    if ref is None:
-        pytest.skip("oracle/_ref not built")
-    rng = np.random.default_rng(2)
-    for n in (2, 3, 4, 5, 6):
-        Cm = rng.uniform(-3, 0, (n, n))
-        want, _ = ob.ref_bruteforce(Cm)
+    gold = None if ref is not None else _live_fixture("murty_plain")
+    for t, Cm in enumerate(murty_plain_tables()):
+        n = Cm.shape[0]
+        if ref is not None:
+            want, _ = ob.ref_bruteforce(Cm)
+        else:
+            assert np.array_equal(np.array(gold[t]["C"]), Cm)
+            want = np.array(gold[t]["scores"])
         k = min(200, math.factorial(n))
         got, assign = ob.murty(Cm, kmax=k)
         assert got.size == k
@@ -134,12 +149,9 @@ def test_murty_with_the_real_assignment_block_vs_golden_fixture(ob):
         assert np.all(np.diff(got) <= 0)                # ranked: never increasing (the premise of the device's early end of the loop)
 
 
-def test_murty_with_the_real_assignment_block_vs_reference_bruteforce_live(ob):
-    """The same comparison against the reference class executed here (fresh tables, incl. dimension 9 with > 200 distinct assignments)."""
-    ref = ob.load_ref()
-    if ref is None:
-        pytest.skip("oracle/_ref not built")
+def extended_live_tables():
     rng = np.random.default_rng(77)
+    out = []
     for nR, nC in ((4, 4), (5, 4), (4, 5), (3, 6)):
         n = nR + nC
         Cm = np.full((n, n), -1000.0)
@@ -149,8 +161,24 @@ def test_murty_with_the_real_assignment_block_vs_reference_bruteforce_live(ob):
         Cm[np.arange(nR), nC + np.arange(nR)] = np.log(1.0 - rng.uniform(0.5, 0.99, nR))
         Cm[nR + np.arange(nC), np.arange(nC)] = np.log(rng.uniform(1e-3, 1e-1, nC))
         Cm[nR:, nC:] = 0.0
-        s, _ = ob.ref_bruteforce(Cm, kmax=math.factorial(n))
-        keep = [s[i] for i in range(len(s)) if s[i] >= -1000.0 and (i == 0 or s[i] != s[i - 1])]
+        out.append((nR, nC, Cm))
+    return out
+
+
+def test_murty_with_the_real_assignment_block_vs_reference_bruteforce_live(ob):
+    """The same comparison against the reference class executed here (fresh tables, incl. dimension 9 with > 200 distinct assignments);
+    where oracle/_ref is not built, against the reference's answers on these same tables (tests/golden/reference_live_cases.json)."""
+    ref = ob.load_ref()
+    gold = None if ref is not None else _live_fixture("extended")
+    for t, (nR, nC, Cm) in enumerate(extended_live_tables()):
+        n = nR + nC
+        if ref is not None:
+            s, _ = ob.ref_bruteforce(Cm, kmax=math.factorial(n))
+            keep = [s[i] for i in range(len(s)) if s[i] >= -1000.0 and (i == 0 or s[i] != s[i - 1])]
+        else:
+            case = gold[t]
+            assert (case["nR"], case["nC"]) == (nR, nC) and np.array_equal(np.array(case["C"]), Cm)
+            keep = case["scores"] + [None] * (case["n_distinct"] - len(case["scores"]))     # (only the first 200 are compared)
         got, _ = ob.murty(Cm, nR, nC, kmax=200)
         got = got[got >= -1000.0]
         assert got.size == min(len(keep), 200)
