@@ -60,7 +60,8 @@ extern "C" {
 /* Maximum measurements per update() (one 64-bit association mask per landmark). */
 /* Hard limits of the device path (the reference has none; all are refused LOUDLY -- an error status, never a silent
  * truncation -- and all are far above BASELINE.json's configurations): RFSGPU_MAX_Z measurements per update,
- * RFSGPU_MAX_EVAL evaluation points, Murty extended dimension nR + nC <= 64, gm_capacity <= 2048 Gaussians per particle,
+ * RFSGPU_MAX_EVAL evaluation points, Murty extended dimension nR + nC <= 64 (a partition's search that outgrows the
+ * 1 + 200 x 32 node pool -- possible only with more than 32 rows -- is refused with its own message, not truncated), gm_capacity <= 2048 Gaussians per particle,
  * RFSGPU_MAX_CANDIDATES birth candidates per particle on the RB-PHD path (64 landmark candidates on the FastSLAM path). */
 #define RFSGPU_MAX_Z 64
 /* Maximum evaluation points for the multi-feature particle weight. */

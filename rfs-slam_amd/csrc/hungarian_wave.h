@@ -90,6 +90,7 @@ __device__ __forceinline__ bool hungarian_wave(double *C, int ld, int n, int &xy
         if (v >= m) { m = v; yy = j; }
       }
     lx = in ? m : 0.0;
+    if (__ballot(in && m < 0.0) != 0ull) return false;   // a row without a non-NaN cell (see the start below)
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");   // the rows written above are read by columns from here on
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
@@ -122,6 +123,10 @@ __device__ __forceinline__ bool hungarian_wave(double *C, int ld, int n, int &xy
     const double v = in ? Ccol[x * ld] : -1.0;                  // every real cell is >= 0 now
     const double m = wave_max_f64(v);
     const unsigned long long eq = __ballot(in && v == m);
+    // no lane equals the maximum: every cell of row x is NaN (the maxima pass over NaN).  No cell of the row is ever tight, and
+    // the reference's solver fails with 'Cannot find alternating path' (include/HungarianMethod.hpp:505-522): so does this --
+    // before the row is given a column index from an empty ballot.
+    if (eq == 0ull) return false;
     const int yy = 63 - __builtin_clzll(eq);                     // `>=` keeps the LAST maximum
     if (lane == x) { lx = m; xy = yy; }
     const int x_t = __builtin_amdgcn_readlane(yx, yy);

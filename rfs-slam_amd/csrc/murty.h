@@ -422,7 +422,7 @@ __device__ __forceinline__ void murty_solve_child(double *myTile, const double *
 // wave 0 pops, and after a barrier pushes the children in partition order and looks at the next score, exactly as the
 // one-wave form does.  What happens with the scores is the caller's: onRoot(score) and onTop(score, node) run on wave 0's
 // lane 0 and return true to stop (onTop is called for the 2nd, 3rd, ... best, at most maxK - 1 times).
-// ctl: [0] parent [1] its partition [2] nodes so far [3] heap length [4] stop [5] ok.
+// ctl: [0] parent [1] its partition [2] nodes so far [3] heap length [4] stop [5] ok [6] the root has no assignment [7] the node pool is full.
 template <int W, int LDSN, class FRoot, class FTop>
 __device__ __forceinline__ void murty_kbest_block(double *C, int n, int partitionMax, int realNC, int maxNodes, int maxK, MurtyArena &A, bool &ok,
                                                   double *myTile, int *ctl, double *sScore, unsigned char *sPushed, const int wave, FRoot onRoot,
@@ -441,7 +441,7 @@ __device__ __forceinline__ void murty_kbest_block(double *C, int n, int partitio
     double s = 0;
     const bool okr = murty_root_wave(C, n, A, a0, s, nullptr);
     if (lane == 0) {
-      ctl[2] = 1; ctl[3] = okr ? 1 : 0; ctl[5] = okr ? 1 : 0;
+      ctl[2] = 1; ctl[3] = okr ? 1 : 0; ctl[5] = okr ? 1 : 0; ctl[6] = okr ? 0 : 1; ctl[7] = 0;
       ctl[4] = (!okr || onRoot(s)) ? 1 : 0;
     }
   }
@@ -487,7 +487,7 @@ __device__ __forceinline__ void murty_kbest_block(double *C, int n, int partitio
     if (wave == 0 && lane == 0) {
       int stop = 0;
       if (poolFull) {
-        ctl[5] = 0;
+        ctl[5] = 0; ctl[7] = 1;
         stop = 1;
       } else {
         int hl = ctl[3];
@@ -595,7 +595,7 @@ __device__ __forceinline__ void murty_kbest_async(double *C, int n, int partitio
     if (lane == 0) {
       if (okr) { H.lid[0] = 0; H.lsc[0] = s; }      // (murty_root_wave pushed node 0 onto the arena's heap: position 0 lives in LDS here)
       if constexpr (SMALL) A.nodeExcl[0] = (unsigned short)(1u << a0);
-      ctl[2] = 1; ctl[3] = okr ? 1 : 0; ctl[5] = okr ? 1 : 0;
+      ctl[2] = 1; ctl[3] = okr ? 1 : 0; ctl[5] = okr ? 1 : 0; ctl[6] = okr ? 0 : 1; ctl[7] = 0;
       ctl[4] = (!okr || onRoot(s)) ? 1 : 0;
     }
   }
@@ -661,7 +661,10 @@ __device__ __forceinline__ void murty_kbest_async(double *C, int n, int partitio
     int postedL = 0;          // lane v in 1..NS: tasks posted to mailbox v so far
     MqTop top;                // (ARGQ) the best three open nodes, found after the last push
     int qLen = __builtin_amdgcn_readfirstlane(ctl[3]);
-    if constexpr (ARGQ) mq_top3(H, qLen, top);
+    // (ARGQ, defensive) an open node whose score is NaN or -inf is never the scan's best (mq_top3 compares with >): with only
+    // such a root the first pop would be mq_remove(-1), so the search ends here -- the reference's rank == -1.  (After a push,
+    // onTop(-DBL_MAX) already stops.)  hungarian_wave never takes a NaN cell, so no tested table reaches it.
+    if constexpr (ARGQ) { mq_top3(H, qLen, top); if (top.id[0] < 0 && lane == 0) ctl[4] = 1; }
     for (int k = 1; k < maxK && __builtin_amdgcn_readfirstlane(ctl[4]) == 0; k++) {
       if constexpr (ARGQ) {
         const int parent = top.id[0];
@@ -848,7 +851,7 @@ __device__ __forceinline__ void murty_kbest_async(double *C, int n, int partitio
       if constexpr (ARGQ) {
         int stop = 0;
         if (poolFull) {
-          if (lane == 0) ctl[5] = 0;
+          if (lane == 0) { ctl[5] = 0; ctl[7] = 1; }
           stop = 1;
         } else {
           for (int c = 0; c < cnt; c++)
@@ -874,7 +877,7 @@ __device__ __forceinline__ void murty_kbest_async(double *C, int n, int partitio
       if (lane == 0) {
         int stop = 0;
         if (poolFull) {
-          ctl[5] = 0;
+          ctl[5] = 0; ctl[7] = 1;
           stop = 1;
         } else {
           int hl = ctl[3];
@@ -955,6 +958,7 @@ __device__ __forceinline__ double murty_partition_sum_block(double *C, int n, in
 #define MURTY_LIB_EXP 0
 #endif
   auto term_of = [](double s) { return MURTY_LIB_EXP ? exp(s) : rfs_exp(s); };
+  // (a NaN score is not below BIG_NEG: the reference adds exp(NaN) and goes on (RBPHDFilter.hpp:953-956), so does this -- the sum is NaN)
   auto onRoot = [&](double s) { if (s < BIG_NEG) return true; *sSum = term_of(s); return false; };
   auto onTop = [&](double st, int) {
     if (st < BIG_NEG) return true;
@@ -962,18 +966,23 @@ __device__ __forceinline__ double murty_partition_sum_block(double *C, int n, in
     *sSum = sum;
     return earlyStop && t < sum * 0x1p-56;
   };
+  bool searched = false;
   if constexpr (W >= 2) {
     if (spec) {
       const MurtyHeap H{heapId, heapSc, A.heap, A.nodeScore};
-      if (sC && n <= HQ_N) {
+      if (sC && n <= HQ_N)
         murty_kbest_async<W, MURTY_LDS_N, true>(C, n, partitionMax, realNC, MURTY_MAX_NODES, MURTY_KBEST, A, ok, myTile, ctl, sScore, sPushed, wave, spec, sC, H, onRoot, onTop);
-        return *sSum;
-      }
-      murty_kbest_async<W, MURTY_LDS_N, false>(C, n, partitionMax, realNC, MURTY_MAX_NODES, MURTY_KBEST, A, ok, myTile, ctl, sScore, sPushed, wave, spec, nullptr, H, onRoot, onTop);
-      return *sSum;
+      else
+        murty_kbest_async<W, MURTY_LDS_N, false>(C, n, partitionMax, realNC, MURTY_MAX_NODES, MURTY_KBEST, A, ok, myTile, ctl, sScore, sPushed, wave, spec, nullptr, H, onRoot, onTop);
+      searched = true;
     }
   }
-  murty_kbest_block<W, MURTY_LDS_N>(C, n, partitionMax, realNC, MURTY_MAX_NODES, MURTY_KBEST, A, ok, myTile, ctl, sScore, sPushed, wave, onRoot, onTop);
+  if (!searched)
+    murty_kbest_block<W, MURTY_LDS_N>(C, n, partitionMax, realNC, MURTY_MAX_NODES, MURTY_KBEST, A, ok, myTile, ctl, sScore, sPushed, wave, onRoot, onTop);
+  // No assignment at the root (log(1 - Pd) = -inf at Pd = 1, a row without a finite cell: the reference's solver fails, include/
+  // HungarianMethod.hpp:505-522): findNextBest's rank == -1 on the first call, and RBPHDFilter.hpp:953-955 adds nothing -- the
+  // partition's likelihood is 0, not an error.  What is left of !ok is a full node pool (ctl[7]).
+  if (!ok && __builtin_amdgcn_readfirstlane(ctl[6]) != 0) ok = true;
   return *sSum;
 }
 
@@ -1291,7 +1300,7 @@ void murty_jobs_kernel(MurtyQueue Q, MurtyScratch MS, int *err, double *weight, 
       bool ok;
       v = murty_partition_sum_block<W>(Q.mats + (size_t)j * MURTY_MAXN * MURTY_MAXN, n, J.nR, J.nC, A, ok, sTile[wave], sCtl, &sSum, sScore,
                                                      sPushed, wave, spec, jobC, sHeapId, sHeapSc);
-      if (!ok && threadIdx.x == 0) atomicOr(err, ERRBIT_MURTY);
+      if (!ok && threadIdx.x == 0) atomicOr(err, ERRBIT_MURTY_POOL);   // (the search outgrew MURTY_MAX_NODES: refused, not truncated)
     }
     if (threadIdx.x == 0) Q.results[j] = v;
 #ifdef RFS_PROFILE

@@ -230,6 +230,7 @@ static int check_device_errors(rfsgpu_filter *f) {
   };
   add(ERRBIT_CAPACITY, RFSGPU_ERR_CAPACITY, "a particle's Gaussian mixture outgrew gm_capacity (raise it in rfsgpu_create)");
   add(ERRBIT_MURTY, RFSGPU_ERR_UNSUPPORTED, "Murty job queue overflow, a partition larger than MURTY_MAXN, or a FastSLAM association component beyond the in-kernel solver");
+  add(ERRBIT_MURTY_POOL, RFSGPU_ERR_UNSUPPORTED, "a Murty-200 partition's search outgrew the node pool (MURTY_MAX_NODES = 1 + 200 expansions x 32 children; a partition with more than 32 rows can need more)");
   add(ERRBIT_EVALPTS, RFSGPU_ERR_UNSUPPORTED, "more than RFSGPU_MAX_EVAL evaluation points requested");
   add(ERRBIT_BIRTHLIST, RFSGPU_ERR_UNSUPPORTED, "a particle's birth-candidate / landmark-candidate list outgrew RFSGPU_MAX_CANDIDATES");
   add(ERRBIT_COLLECTIVE, RFSGPU_ERR_UNSUPPORTED, "collective hand-over timed out: the sequence number of the weight all-reduce was not published within 0.5 s (rfsgpu_step_async_trailing / rfsgpu_collective_gate / _publish)");
