@@ -626,6 +626,46 @@ int rfsgpu_fastslam_set_resample_occured(rfsgpu_filter *f, int flag);
 /* parent[k] = the slot particle k was copied from by the last rfsgpu_fastslam_update (k itself when it was not a copy). */
 int rfsgpu_particle_parents(rfsgpu_filter *f, int *parent, int max_n);
 
+/* ---- [batch] many independent 2-D RB-PHD filters in one handle (outside the STABLE CORE) -------------------------------------
+ * A batch handle holds n_filters independent range-bearing filters of n_per_filter particles each, stepped together: one cycle is
+ * one fused step launch + one post launch for all of them.  Particle slots are global -- filter b owns slots
+ * [b * n_per_filter, (b + 1) * n_per_filter) -- so the per-slot calls work unchanged (rfsgpu_set_poses, rfsgpu_get_weights,
+ * rfsgpu_gm_size(s), rfsgpu_get_landmark, rfsgpu_export_gm, rfsgpu_get_unused, particle ids).  Each filter has its own configuration,
+ * measurement set, weights, normalisation, resampling and resampleOccured_; each equals a separate handle given the same inputs.
+ * The whole-handle setters (rfsgpu_set_filter_config, _set_model_rngbrg, _set_kf_config, _set_lmk_process_noise) set every filter.
+ * Not on a batch handle (RFSGPU_ERR_UNSUPPORTED, with a rfsgpu_last_error message): the Victoria Park model and
+ * rfsgpu_set_laser_scan, FastSLAM, rfsgpu_update* and the phase calls, rfsgpu_step_async*, rfsgpu_cycle_async, rfsgpu_predict_map*,
+ * the collective calls, rfsgpu_resample_apply[_n], rfsgpu_weight_sums[_async], rfsgpu_normalize_weights[_parts] (one total for all
+ * filters: rfsgpu_batch_weight_sums and the cycle's normalize instead), rfsgpu_import_birth_candidates, birth inheritance modes other
+ * than RFSGPU_INHERIT_REFERENCE, and configurations with birthGaussianMeasurementCountThreshold != 1 (the births are immediate).
+ * rfsgpu_resample_occured returns -1 on a batch (rfsgpu_batch_resample_occured has the per-filter flags).
+ * Groups (rfsgpu_group_*) create their own handles and are not batches.  Limits per filter: RFSGPU_MAX_Z, RFSGPU_MAX_EVAL,
+ * gm_capacity.  Shared by the whole batch: the Murty-200 job queue (4 jobs per particle of the batch, at most 8192 -- fewer in all
+ * than the same filters get as separate handles, so a dense sweep can overflow it where the handles would not) and the device error
+ * word: rfsgpu_last_error names a filter that exceeded gm_capacity (the lowest such filter) or asks for more than RFSGPU_MAX_EVAL
+ * evaluation points; a Murty error is not attributed. */
+int rfsgpu_create_batch(rfsgpu_filter **out, int model, int n_filters, int n_per_filter, int device_id, int gm_capacity);
+int rfsgpu_n_filters(const rfsgpu_filter *f);    /* 1 for an ordinary handle */
+/* Filter `filter`'s configuration; a NULL pointer leaves that part as it is.  lmk_Q: the 2x2 landmark process noise, row-major. */
+int rfsgpu_batch_configure(rfsgpu_filter *f, int filter, const rfsgpu_filter_config *cfg, const rfsgpu_rngbrg_config *model,
+                           const rfsgpu_kf_config *kf, const double *lmk_Q);
+/* rfsgpu_cycle_async for every filter at once (predict as there; x [N][3], x_cov [9] or [N][9] by cov_stride, or NULL).
+ * z: [n_filters][RFSGPU_MAX_Z][2], n_z: [n_filters].  A filter with n_z == 0 is not updated this cycle (its predict part runs, its
+ * weights are summed and divided as asked).  normalize != 0: each filter's weights are divided by their own sum. */
+int rfsgpu_batch_cycle_async(rfsgpu_filter *f, int predict, const double *x, const double *x_cov, int cov_stride,
+                             const double *z, const int *n_z, int normalize);
+/* {sum w, sum w^2} of each filter's current weights: out [n_filters][2].  Synchronising. */
+int rfsgpu_batch_weight_sums(rfsgpu_filter *f, double *out);
+/* Resample the filters with resampled[b] != 0: slot k takes slot src_slot[k] (global slots; a source lies in k's own block and keeps
+ * itself, else RFSGPU_ERR_INVALID); their weights become 1.  Other filters' entries of src_slot are not read. */
+int rfsgpu_batch_resample_apply(rfsgpu_filter *f, const int *src_slot, const unsigned char *resampled);
+/* resampleOccured_ of each filter: out [n_filters]. */
+int rfsgpu_batch_resample_occured(const rfsgpu_filter *f, unsigned char *out);
+#ifdef RFSGPU_ENABLE_BENCH_API
+/* [test] 1 once a step of this handle (batch or not) has queued Murty-200 partitions, else 0.  Synchronising. */
+int rfsgpu_murty_seen(rfsgpu_filter *f);
+#endif
+
 #ifdef __cplusplus
 }
 #endif

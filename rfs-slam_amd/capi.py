@@ -124,6 +124,7 @@ ABI_SYMBOLS = [
     "group_get_poses", "group_set_weights", "group_get_weights", "group_predict_map", "group_update", "group_normalize",
     "group_resample", "group_apply_plan", "group_migration_stats", "group_gm_size", "group_get_landmark", "group_synchronize", "group_set_birth_inheritance", "group_get_particle_ids",
     "group_update_io", "group_update_deferred", "group_set_model_victoriapark", "group_set_laser_scan", "group_set_phase_timing", "group_get_timing", "group_collective",
+    "create_batch", "n_filters", "batch_configure", "batch_cycle_async", "batch_weight_sums", "batch_resample_apply", "batch_resample_occured", "murty_seen",
 ]
 
 _dp = np.ctypeslib.ndpointer(dtype=np.float64, flags="C_CONTIGUOUS")
@@ -583,6 +584,91 @@ class CFilter:
 
     def synchronize(self):
         self._call("synchronize")
+
+
+class CBatch(CFilter):
+    """A filter batch behind the C ABI ([batch] in include/rfsgpu.h): n_filters independent 2-D filters of n_per_filter particles in one
+    handle, filter b in the global slots [b * n_per_filter, (b + 1) * n_per_filter).  Every per-slot method of CFilter works on it."""
+
+    def __init__(self, lib, prefix, n_filters, n_per_filter, model=MODEL_RNGBRG_2D, device_id=0, gm_capacity=512):
+        self._lib, self._p = lib, prefix
+        self.model = model
+        self.device_id = device_id
+        self.dm = self.dz = 2
+        self._borrowed = False
+        self._h = C.c_void_p()
+        fn = self._fn("create_batch")
+        fn.restype = C.c_int
+        rc = fn(C.byref(self._h), C.c_int(model), C.c_int(int(n_filters)), C.c_int(int(n_per_filter)), C.c_int(device_id), C.c_int(gm_capacity))
+        if rc != OK:
+            self._h = C.c_void_p()
+            raise EngineError(rc, "create_batch failed: " + ("the Victoria Park model has no batch form" if rc == ERR_UNSUPPORTED and model == MODEL_VICTORIAPARK_3D
+                                                             else "no gfx950 device / bad arguments"))
+        self.n_filters = int(n_filters)
+        self.n_per_filter = int(n_per_filter)
+
+    def block(self, b):
+        """The global slots of filter b."""
+        return slice(b * self.n_per_filter, (b + 1) * self.n_per_filter)
+
+    def batch_configure(self, b, cfg=None, R=None, Pd=None, clutter=None, rmax=None, rmin=None, rbuf=None, kf=None, Q=None):
+        """Filter b's configuration: cfg a FilterConfig; the range-bearing model (R, Pd, clutter, rmax, rmin, rbuf: all or none);
+        kf = (range_thr, bearing_thr); Q the 2x2 landmark process noise.  What is None stays."""
+        m = None
+        if R is not None:
+            m = RngBrgConfig()
+            R = _f64(R, (4,))
+            for k in range(4):
+                m.R[k] = R[k]
+            m.probabilityOfDetection, m.uniformClutterIntensity = Pd, clutter
+            m.rangeLimMax, m.rangeLimMin, m.rangeLimBuffer = rmax, rmin, rbuf
+        k = None if kf is None else KFConfig(*kf)
+        q = None if Q is None else _f64(Q, (4,))
+        self._call("batch_configure", C.c_int(int(b)), C.c_void_p(None) if cfg is None else C.byref(cfg), C.c_void_p(None) if m is None else C.byref(m),
+                   C.c_void_p(None) if k is None else C.byref(k), C.c_void_p(None) if q is None else self._ptr(q))
+
+    def batch_cycle_async(self, predict, Zs, poses=None, pose_cov=None, normalize=True):
+        """rfsgpu_batch_cycle_async: Zs = one measurement array per filter ([n_z, 2], possibly empty); predict None / False / True as
+        rfsgpu_cycle_async."""
+        assert len(Zs) == self.n_filters
+        z = np.zeros((self.n_filters, MAX_Z, 2))
+        nz = np.zeros(self.n_filters, dtype=np.int32)
+        for b, Z in enumerate(Zs):
+            Z = _f64(Z).reshape(-1, 2) if np.size(Z) else np.zeros((0, 2))
+            nz[b] = Z.shape[0]
+            z[b, : min(Z.shape[0], MAX_Z)] = Z[:MAX_Z]
+        x = None if poses is None else _f64(poses, (self.n, 3))
+        stride = 0
+        cv = None
+        if pose_cov is not None:
+            cv = _f64(pose_cov)
+            assert cv.size in (9, 9 * self.n)
+            stride = 0 if cv.size == 9 else 9
+        self._call("batch_cycle_async", C.c_int(-1 if predict is None else (1 if predict else 0)), C.c_void_p(None) if x is None else self._ptr(x),
+                   C.c_void_p(None) if cv is None else self._ptr(cv), C.c_int(stride), self._ptr(z), self._ptr(nz), C.c_int(1 if normalize else 0))
+
+    def batch_weight_sums(self):
+        out = np.empty((self.n_filters, 2))
+        self._call("batch_weight_sums", self._ptr(out))
+        return out
+
+    def batch_resample_apply(self, src_slot, resampled):
+        s = np.ascontiguousarray(src_slot, dtype=np.int32)
+        r = np.ascontiguousarray(resampled, dtype=np.uint8)
+        assert s.size == self.n and r.size == self.n_filters
+        self._call("batch_resample_apply", self._ptr(s), self._ptr(r))
+
+    def batch_resample_occured(self):
+        out = np.zeros(self.n_filters, dtype=np.uint8)
+        fn = self._fn("batch_resample_occured")
+        fn.restype = C.c_int
+        fn(self._h, self._ptr(out))
+        return out.astype(bool)
+
+    def n_filters_abi(self):
+        fn = self._fn("n_filters")
+        fn.restype = C.c_int
+        return int(fn(self._h))
 
 
 def mat_perm(lib, prefix, A, device_id=0):

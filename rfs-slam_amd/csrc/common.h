@@ -63,6 +63,29 @@ struct ZArg {
   double v[RFSGPU_MAX_Z * 3];
 };
 
+// ---- filter batches (rfsgpu_create_batch) --------------------------------------------------------------------------------
+// A batch handle holds n_filters independent filters of nPer particles each; filter b owns slots [b * nPer, (b + 1) * nPer).  The
+// BATCH instantiations of the step kernel take what a single handle passes as kernel arguments -- Params, the measurement set and its
+// count, the eval-point cap, the weighting switch, the previous set for the births -- from these device tables instead, per workgroup,
+// for the filter of the particle it owns.  The host writes them once per cycle (rfsgpu_batch_cycle_async).
+struct BatchFilter {
+  int nZ;        // this cycle's measurements (0: no update for this filter, RBPHDFilter.hpp:450-452 -- its predict head still runs)
+  int nZprev;    // the previous update's (its births)
+  int evalCap;   // eval_cap() of the filter's configuration
+  int useW;      // !useClusterProcess
+  int zOff;      // where its set starts in BatchArg::z (doubles)
+  int pad[3];
+};
+struct BatchArg {
+  const BatchFilter *filt;   // [nF]
+  const Params *params;      // [nF]
+  const double *z;           // this cycle's sets, packed (2 doubles per measurement)
+  double *zPrev;             // [nF][RFSGPU_MAX_Z * 2] each filter's last non-empty set: the next predict's births (written by the post kernel)
+  double *sums;              // [nF][2] {sum w, sum w^2} per filter (post kernel)
+  int *errFilter;            // [1] lowest filter seen at gm_capacity with the capacity bit up (INT_MAX: none)
+  int nF, nPer;
+};
+
 struct Buffers {
   double *slab[2];
   int *count;

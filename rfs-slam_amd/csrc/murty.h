@@ -13,6 +13,7 @@
 // particle's weight in partition order.  Node pool, heap and root table live in HBM (per-job arena), sub-problem tables
 // in an LDS tile.  (The one-thread form of the solver that round 1 still carried for FastSLAM's small blocks is gone: every caller uses hungarian_wave.)
 #pragma once
+#include <type_traits>
 #include "common.h"
 #include "weighting.h"
 #include "hungarian_wave.h"
@@ -1236,19 +1237,65 @@ __global__ __launch_bounds__(1024) void murty_order_kernel(MurtyQueue Q) {
 // (the compiler's own register count, no scratch): what a filter WITHOUT Murty work launches as its post kernel
 // step after step -- the capped instance needs scratch memory set up for every wave it dispatches and costs 0.2 us more per
 // step for nothing.  Both do the same thing with whatever the queue holds.
-template <int W, int WAVES_PER_EU>
+// A batch's post work for filter b, by one workgroup (rfsgpu_create_batch): the filter's {sum w, sum w^2} and, when asked, the division --
+// what the filter's own handle does at the end of a cycle.  An updated filter: step_post_tail on its block of weights.  A filter without an
+// update this cycle: the reduction of weight_sums_kernel + normalize_kernel (what rfsgpu_cycle_async issues for an empty set); for blocks of
+// at most blockDim.x particles both give the handle's bits (the extra lanes and waves add zeros).
+__device__ __forceinline__ void batch_post_tail(double *weight, const BatchArg &A, const int b, const int normalize) {
+  double *w = weight + (size_t)b * A.nPer;
+  const int N = A.nPer;
+  if (A.filt[b].nZ > 0) {
+    step_post_tail(w, N, A.sums + 2 * b, normalize);
+  } else {
+    __shared__ double s0[16], s1[16];
+    __shared__ double sDiv;
+    double a = 0, c = 0;
+    for (int k = threadIdx.x; k < N; k += blockDim.x) { const double v = w[k]; a += v; c += v * v; }
+    a = wave_sum(a); c = wave_sum(c);
+    if ((threadIdx.x & 63) == 0) { s0[threadIdx.x >> 6] = a; s1[threadIdx.x >> 6] = c; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      double x = 0, y = 0;
+      for (int k = 0; k < (int)(blockDim.x >> 6); k++) { x += s0[k]; y += s1[k]; }
+      A.sums[2 * b] = x; A.sums[2 * b + 1] = y;
+      sDiv = x;
+    }
+    __syncthreads();
+    if (normalize) {
+      const double d = sDiv;
+      for (int k = threadIdx.x; k < N; k += blockDim.x) w[k] = w[k] / d;
+    }
+  }
+  __syncthreads();   // (the next filter's pass reuses the shared words)
+}
+
+// BATCH: the post kernel of a batch cycle -- the measurement sets written back per filter, the sums / division per filter; the Murty
+// jobs themselves need nothing per filter (they carry global particle indices).  ZArg and dZ / nZdoubles are then unused.
+template <int W, int WAVES_PER_EU, bool BATCH = false>
 __global__ __launch_bounds__(64 * W) __attribute__((amdgpu_waves_per_eu(WAVES_PER_EU > 0 ? WAVES_PER_EU : 1, WAVES_PER_EU > 0 ? WAVES_PER_EU : 8)))
 void murty_jobs_kernel(MurtyQueue Q, MurtyScratch MS, int *err, double *weight, int N, double *sums,
-                                                                         int normalize, ZArg zarg, double *dZ, int nZdoubles, int *hostSeen, int ordered, StepOut SO,
+                                                                         int normalize, typename std::conditional<BATCH, BatchArg, ZArg>::type zarg, double *dZ, int nZdoubles, int *hostSeen, int ordered, StepOut SO,
                                                                          StepOrderArg SOrd) {
   // (a fused step carries the measurement set in its kernel arguments; the device copy the next predict reads is written here)
-  if (blockIdx.x == 0 && dZ)
-    for (int t = threadIdx.x; t < nZdoubles; t += blockDim.x) dZ[t] = zarg.v[t];
+  if constexpr (BATCH) {
+    for (int b = blockIdx.x; b < zarg.nF; b += gridDim.x) {     // (block-uniform)
+      const int n2 = 2 * zarg.filt[b].nZ;
+      const double *zs = zarg.z + zarg.filt[b].zOff;
+      for (int t = threadIdx.x; t < n2; t += blockDim.x) zarg.zPrev[(size_t)b * (RFSGPU_MAX_Z * 2) + t] = zs[t];
+    }
+  } else {
+    if (blockIdx.x == 0 && dZ)
+      for (int t = threadIdx.x; t < nZdoubles; t += blockDim.x) dZ[t] = zarg.v[t];
+  }
   if (SOrd.cost && blockIdx.x >= 1 && blockIdx.x <= STEP_ORDER_CLASSES)     // (every launch has >= 64 workgroups; block-uniform)
     step_cost_order_class(SOrd, (int)blockIdx.x - 1);
   const int nJobs = min(*Q.count, Q.maxJobs);
   if (nJobs == 0) {
-    if (blockIdx.x == 0) { step_post_tail(weight, N, sums, normalize, SO.preDiv, SO.collSeq, SO.collNeed, SO.collPost, err); step_post_out(weight, N, err, SO); }
+    if constexpr (BATCH) {
+      for (int b = blockIdx.x; b < zarg.nF; b += gridDim.x) batch_post_tail(weight, zarg, b, normalize);
+    } else {
+      if (blockIdx.x == 0) { step_post_tail(weight, N, sums, normalize, SO.preDiv, SO.collSeq, SO.collNeed, SO.collPost, err); step_post_out(weight, N, err, SO); }
+    }
     return;
   }
   __shared__ double sTile[W][MURTY_LDS_N * MURTY_LDS_N];
@@ -1386,8 +1433,12 @@ void murty_jobs_kernel(MurtyQueue Q, MurtyScratch MS, int *err, double *weight, 
 #ifdef RFS_PROFILE
   if (threadIdx.x == 0) printf("murty tail (last workgroup %d): factors into the weights %lld ticks of 10 ns, ends at tick %lld\n", (int)blockIdx.x, (long long)wall_clock64() - dbgTail0, (long long)wall_clock64());
 #endif
-  step_post_tail(weight, N, sums, normalize, SO.preDiv, SO.collSeq, SO.collNeed, SO.collPost, err);
-  step_post_out(weight, N, err, SO);
+  if constexpr (BATCH) {
+    for (int b = 0; b < zarg.nF; b++) batch_post_tail(weight, zarg, b, normalize);
+  } else {
+    step_post_tail(weight, N, sums, normalize, SO.preDiv, SO.collSeq, SO.collNeed, SO.collPost, err);
+    step_post_out(weight, N, err, SO);
+  }
 }
 
 // Start of a step: measurement set -> device buffer (read by every kernel of the step and by the next predict), Murty
@@ -1445,5 +1496,22 @@ static inline int murty_launch(MurtyQueue &Q, MurtyScratch &MS, Buffers &B, hipS
   else
     murty_jobs_kernel<MURTY_JOB_WAVES, MURTY_WAVES_PER_EU><<<blocks, 64 * MURTY_JOB_WAVES, 0, stream>>>(Q, MS, B.err, B.weight, B.N, sums, normalize,
                                                                                                       za ? *za : none, za ? B.Z : nullptr, nZdoubles, hostSeen, ordered, SO, sord);
+  return hipGetLastError() == hipSuccess ? 0 : 1;
+}
+// The post launch of a batch cycle (rfsgpu_batch_cycle_async): murty_launch's choice of instance, the BATCH kernel.
+static inline int murty_launch_batch(MurtyQueue &Q, MurtyScratch &MS, Buffers &B, hipStream_t stream, const BatchArg &A, int normalize, int *hostSeen,
+                                     const StepOrderArg &SOrd) {
+  int blocks = std::min(MURTY_JOB_BLOCKS, Q.maxJobs);
+  if (hostSeen && *hostSeen == 0) blocks = std::min(blocks, MURTY_FIRST_BLOCKS);
+  const int ordered = (Q.order && (!hostSeen || *hostSeen != 0)) ? 1 : 0;
+  const StepOrderArg sord = blocks > STEP_ORDER_CLASSES ? SOrd : StepOrderArg{nullptr, nullptr, 0, nullptr, 0};
+  const StepOut none{nullptr, nullptr, 0, nullptr, nullptr, 0, 0};
+  if (ordered) murty_order_kernel<<<1, 1024, 0, stream>>>(Q);
+  if (hostSeen && *hostSeen == 0)
+    murty_jobs_kernel<MURTY_LIGHT_WAVES, 0, true><<<blocks, 64 * MURTY_LIGHT_WAVES, 0, stream>>>(Q, MS, B.err, B.weight, B.N, A.sums, normalize, A, nullptr, 0,
+                                                                                               hostSeen, ordered, none, sord);
+  else
+    murty_jobs_kernel<MURTY_JOB_WAVES, MURTY_WAVES_PER_EU, true><<<blocks, 64 * MURTY_JOB_WAVES, 0, stream>>>(Q, MS, B.err, B.weight, B.N, A.sums, normalize, A,
+                                                                                                            nullptr, 0, hostSeen, ordered, none, sord);
   return hipGetLastError() == hipSuccess ? 0 : 1;
 }

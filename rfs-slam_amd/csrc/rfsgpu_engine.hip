@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <climits>
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -146,6 +147,28 @@ struct rfsgpu_filter {
   std::string err;
   int maxLds = 0;
   int wpbUpdate = 4, wpbWeight = 4, wpbMerge = 4, wpbPrune = 4;
+  // filter batch (rfsgpu_create_batch): nF independent filters of nPer particles, filter b in slots [b * nPer, (b + 1) * nPer)
+  bool batch = false;
+  int nF = 1, nPer = 0;
+  std::vector<rfsgpu_filter_config> bCfg;
+  std::vector<rfsgpu_rngbrg_config> bRb;
+  std::vector<rfsgpu_kf_config> bKf;
+  std::vector<double> bQ;             // [nF][9]
+  std::vector<int> bNZ;               // measurements of each filter's last update (its next births)
+  std::vector<char> bResampled;       // RBPHDFilter::resampleOccured_ per filter
+  bool bParamsDirty = true;           // the device Params table is behind the host configuration
+  int bHandleWide[3] = {-1, -1, -1};  // the handle-wide Params fields the table was built with (pose covariance stride, partition mode, dense intensity)
+  BatchFilter *dBFilt = nullptr;      // [nF]
+  Params *dBParams = nullptr;         // [nF]
+  double *dBZ = nullptr;              // [nF][RFSGPU_MAX_Z * 2] this cycle's sets, packed
+  double *dBZPrev = nullptr;          // [nF][RFSGPU_MAX_Z * 2]
+  double *dBSums = nullptr;           // [nF][2]
+  int *dBErrFilter = nullptr;         // [1] BatchArg::errFilter
+  unsigned long long *dBMaskTmp = nullptr;   // [N] birth inheritance: the masks before the walk
+  int *dBInhSrc = nullptr;            // [N]
+  unsigned char *hBStage[4] = {nullptr, nullptr, nullptr, nullptr};   // pinned ring of the per-cycle tables
+  hipEvent_t evBStage[4] = {};
+  int bStageNext = 0;
 };
 
 #define HIPCHK(call)                                                                       \
@@ -165,6 +188,11 @@ static int fail(rfsgpu_filter *f, int code, const char *msg) {
   return code;
 }
 
+static void batch_set_all(rfsgpu_filter *f);
+#define REFUSE_ON_BATCH(f, what)                                                                                                   \
+  if ((f)->batch) return fail(f, RFSGPU_ERR_UNSUPPORTED, what " is not available on a filter batch (rfsgpu_create_batch): use the rfsgpu_batch_* calls")
+
+static std::string batch_error_note(rfsgpu_filter *f, int e);
 static void rebuild_params(rfsgpu_filter *f) {
   Params &P = f->P;
   P.denseIntensity = f->denseIntensity ? 1 : 0;
@@ -234,6 +262,7 @@ static int check_device_errors(rfsgpu_filter *f) {
   add(ERRBIT_EVALPTS, RFSGPU_ERR_UNSUPPORTED, "more than RFSGPU_MAX_EVAL evaluation points requested");
   add(ERRBIT_BIRTHLIST, RFSGPU_ERR_UNSUPPORTED, "a particle's birth-candidate / landmark-candidate list outgrew RFSGPU_MAX_CANDIDATES");
   add(ERRBIT_COLLECTIVE, RFSGPU_ERR_UNSUPPORTED, "collective hand-over timed out: the sequence number of the weight all-reduce was not published within 0.5 s (rfsgpu_step_async_trailing / rfsgpu_collective_gate / _publish)");
+  if (code != RFSGPU_OK && f->batch) msg += batch_error_note(f, e);
   if (code != RFSGPU_OK) { f->err = msg; return code; }
   return fail(f, RFSGPU_ERR_HIP, "unknown device error flag");
 }
@@ -386,6 +415,8 @@ void rfsgpu_destroy(rfsgpu_filter *f) {
   hipFree(f->inhTmp.unused); hipFree(f->inhTmp.count); hipFree(f->inhTmp.sup); hipFree(f->inhTmp.chk); hipFree(f->inhTmp.mean); hipFree(f->inhTmp.cov);  // (hipFree(nullptr) is a no-op)
   hipFree(B.scan); hipFree(B.candMean); hipFree(B.candCov); hipFree(B.candSup); hipFree(B.candChk); hipFree(B.candCount);
   murty_free(f->Q, f->MS);
+  hipFree(f->dBFilt); hipFree(f->dBParams); hipFree(f->dBZ); hipFree(f->dBZPrev); hipFree(f->dBSums); hipFree(f->dBErrFilter); hipFree(f->dBMaskTmp); hipFree(f->dBInhSrc);
+  for (int k = 0; k < 4; k++) { if (f->hBStage[k]) hipHostFree(f->hBStage[k]); if (f->evBStage[k]) hipEventDestroy(f->evBStage[k]); }
   if (f->hErr) hipHostFree(f->hErr);
   if (f->hJobCount) hipHostFree(f->hJobCount);
   if (f->hSums) hipHostFree(f->hSums);
@@ -406,6 +437,7 @@ int rfsgpu_set_filter_config(rfsgpu_filter *f, const rfsgpu_filter_config *c) {
   if (!c) return RFSGPU_ERR_INVALID;
   f->cfg = *c;
   rebuild_params(f);
+  if (f->batch) batch_set_all(f);
   return RFSGPU_OK;
 }
 int rfsgpu_set_partition_mode(rfsgpu_filter *f, int mode) {
@@ -454,10 +486,12 @@ int rfsgpu_set_model_rngbrg(rfsgpu_filter *f, const rfsgpu_rngbrg_config *c) {
   if (f->model != RFSGPU_MODEL_RNGBRG_2D) return fail(f, RFSGPU_ERR_INVALID, "set_model_rngbrg on a handle created for another model");
   f->rb = *c;
   rebuild_params(f);
+  if (f->batch) batch_set_all(f);
   return RFSGPU_OK;
 }
 int rfsgpu_set_model_victoriapark(rfsgpu_filter *f, const rfsgpu_vp_config *c) {
   CHECK_HANDLE(f);
+  REFUSE_ON_BATCH(f, "the Victoria Park model");
   if (!c) return RFSGPU_ERR_INVALID;
   if (f->model != RFSGPU_MODEL_VICTORIAPARK_3D) return fail(f, RFSGPU_ERR_INVALID, "set_model_victoriapark on a handle created for another model");
   if (c->nPd < 1 || c->nPd > RFSGPU_VP_MAX_PD) return fail(f, RFSGPU_ERR_INVALID, "Pd table size out of range");
@@ -469,6 +503,7 @@ int rfsgpu_set_model_victoriapark(rfsgpu_filter *f, const rfsgpu_vp_config *c) {
 // intensity are a 361-term host sum; the raw scan goes to the device for the occlusion-based Pd.
 int rfsgpu_set_laser_scan(rfsgpu_filter *f, const double *scan, int n) {
   CHECK_HANDLE(f);
+  REFUSE_ON_BATCH(f, "rfsgpu_set_laser_scan");
   if (f->model != RFSGPU_MODEL_VICTORIAPARK_3D) return fail(f, RFSGPU_ERR_INVALID, "set_laser_scan needs the Victoria Park model");
   if (!scan || n < 2 || n > RFSGPU_VP_MAX_SCAN) return fail(f, RFSGPU_ERR_INVALID, "laser scan size out of range");
   double area = 0;
@@ -507,6 +542,7 @@ int rfsgpu_set_kf_config(rfsgpu_filter *f, const rfsgpu_kf_config *c) {
   if (!c) return RFSGPU_ERR_INVALID;
   f->kf = *c;
   rebuild_params(f);
+  if (f->batch) batch_set_all(f);
   return RFSGPU_OK;
 }
 int rfsgpu_set_lmk_process_noise(rfsgpu_filter *f, const double *Q) {
@@ -514,6 +550,7 @@ int rfsgpu_set_lmk_process_noise(rfsgpu_filter *f, const double *Q) {
   if (!Q) return RFSGPU_ERR_INVALID;
   memcpy(f->Qlm, Q, (size_t)f->D * f->D * sizeof(double));
   rebuild_params(f);
+  if (f->batch) batch_set_all(f);
   return RFSGPU_OK;
 }
 
@@ -728,6 +765,7 @@ int rfsgpu_export_birth_candidates(rfsgpu_filter *f, int slot, int max_n, int *n
 }
 int rfsgpu_import_birth_candidates(rfsgpu_filter *f, int slot, int n, const double *mean, const double *cov, const int *n_support, const int *n_checks) {
   CHECK_HANDLE(f);
+  REFUSE_ON_BATCH(f, "rfsgpu_import_birth_candidates");
   if (slot < 0 || slot >= f->N || n < 0 || n > RFSGPU_MAX_CANDIDATES) return fail(f, RFSGPU_ERR_INVALID, "import_birth_candidates: bad arguments");
   hipSetDevice(f->device);
   if (n > 0) f->candUsed = true;
@@ -903,6 +941,7 @@ static int stage_measurements(rfsgpu_filter *f, const double *z, int n_z) {
 
 int rfsgpu_update_map(rfsgpu_filter *f, const double *z, int n_z) {
   CHECK_HANDLE(f);
+  REFUSE_ON_BATCH(f, "rfsgpu_update_map");
   long long t0 = now_ns();
   int rc = stage_measurements(f, z, n_z);
   if (rc != RFSGPU_OK) return rc;
@@ -917,6 +956,7 @@ int rfsgpu_update_map(rfsgpu_filter *f, const double *z, int n_z) {
 }
 int rfsgpu_importance_weighting(rfsgpu_filter *f) {
   CHECK_HANDLE(f);
+  REFUSE_ON_BATCH(f, "rfsgpu_importance_weighting");
   long long t0 = now_ns();
   hipSetDevice(f->device);
   HIPCHK(hipEventRecord(f->ev[EV_UM1], f->stream));
@@ -930,6 +970,7 @@ int rfsgpu_importance_weighting(rfsgpu_filter *f) {
 }
 int rfsgpu_merge(rfsgpu_filter *f) {
   CHECK_HANDLE(f);
+  REFUSE_ON_BATCH(f, "rfsgpu_merge");
   f->holes = true;
   long long t0 = now_ns();
   hipSetDevice(f->device);
@@ -944,6 +985,7 @@ int rfsgpu_merge(rfsgpu_filter *f) {
 }
 int rfsgpu_prune(rfsgpu_filter *f) {
   CHECK_HANDLE(f);
+  REFUSE_ON_BATCH(f, "rfsgpu_prune");
   f->holes = false;
   long long t0 = now_ns();
   hipSetDevice(f->device);
@@ -965,6 +1007,7 @@ static int update_async_impl(rfsgpu_filter *f, const double *z, int n_z, bool wi
                              hipEvent_t waitBeforePost = nullptr);
 int rfsgpu_update(rfsgpu_filter *f, const double *z, int n_z) {
   CHECK_HANDLE(f);
+  REFUSE_ON_BATCH(f, "rfsgpu_update");
   f->holes = false;
   if (n_z == 0) return RFSGPU_OK;  // :450-452
   // 2-D model: ONE fused launch (+ the post kernel) unless the caller asked for phase-resolved timing (rfsgpu_set_phase_timing):
@@ -1224,10 +1267,12 @@ static int update_async_impl(rfsgpu_filter *f, const double *z, int n_z, bool wi
 }
 int rfsgpu_update_async(rfsgpu_filter *f, const double *z, int n_z) {
   CHECK_HANDLE(f);
+  REFUSE_ON_BATCH(f, "rfsgpu_update_async");
   return update_async_impl(f, z, n_z, false, 0);
 }
 int rfsgpu_step_async(rfsgpu_filter *f, const double *z, int n_z, int normalize) {
   CHECK_HANDLE(f);
+  REFUSE_ON_BATCH(f, "rfsgpu_step_async");
   if (n_z == 0) {  // no update (:450-452), but the weights are still summed / normalised as the caller asked
     int rc = rfsgpu_weight_sums_async(f);
     if (rc != RFSGPU_OK) return rc;
@@ -1243,6 +1288,7 @@ int rfsgpu_step_async(rfsgpu_filter *f, const double *z, int n_z, int normalize)
 // and the post kernel: the collective of step k runs beside the step kernel of step k + 1 instead of in front of it.
 int rfsgpu_step_async_deferred(rfsgpu_filter *f, const double *z, int n_z, const void *prev_total_dev, void *wait_event) {
   CHECK_HANDLE(f);
+  REFUSE_ON_BATCH(f, "rfsgpu_step_async_deferred");
   hipSetDevice(f->device);
   if (n_z == 0 || !f->fuseSteps || f->phaseTiming) {        // no fused step: the same arithmetic with the stand-alone kernels, in stream order
     if (wait_event) HIPCHK(hipStreamWaitEvent(f->stream, (hipEvent_t)wait_event, 0));
@@ -1261,6 +1307,7 @@ int rfsgpu_step_async_deferred(rfsgpu_filter *f, const double *z, int n_z, const
 // before it divides by total_dev).  have_prev == 0: the first step of a run (or the first after a flush): nothing to divide by.
 int rfsgpu_step_async_trailing(rfsgpu_filter *f, const double *z, int n_z, const void *total_dev, int have_prev) {
   CHECK_HANDLE(f);
+  REFUSE_ON_BATCH(f, "rfsgpu_step_async_trailing");
   hipSetDevice(f->device);
   if (!total_dev) return fail(f, RFSGPU_ERR_INVALID, "step_async_trailing: null total buffer");
   const int k = ++f->collStep;
@@ -1282,6 +1329,7 @@ int rfsgpu_step_async_trailing(rfsgpu_filter *f, const double *z, int n_z, const
 // rfsgpu_step_async_trailing call has written this shard's sums.
 int rfsgpu_collective_gate(rfsgpu_filter *f, void *hip_stream) {
   CHECK_HANDLE(f);
+  REFUSE_ON_BATCH(f, "rfsgpu_collective_gate");
   hipSetDevice(f->device);
   coll_gate_kernel<<<1, 64, 0, (hipStream_t)hip_stream>>>(f->dCollSeq, f->collStep, f->B.err);
   HIPCHK(hipGetLastError());
@@ -1290,6 +1338,7 @@ int rfsgpu_collective_gate(rfsgpu_filter *f, void *hip_stream) {
 // [multi] on the same stream, behind the collective: the total of the last step is in place.
 int rfsgpu_collective_publish(rfsgpu_filter *f, void *hip_stream) {
   CHECK_HANDLE(f);
+  REFUSE_ON_BATCH(f, "rfsgpu_collective_publish");
   hipSetDevice(f->device);
   coll_publish_kernel<<<1, 1, 0, (hipStream_t)hip_stream>>>(f->dCollSeq + 1, f->collStep);   // word [1]: "the total of step k is in place"
   HIPCHK(hipGetLastError());
@@ -1305,6 +1354,7 @@ int rfsgpu_collective_publish(rfsgpu_filter *f, void *hip_stream) {
 // a spinning kernel for that long -- past the bound the probe must answer 0 and the hosts must take the event form.
 int rfsgpu_collective_probe(rfsgpu_filter *f, void *hip_stream, int *side_by_side) {
   CHECK_HANDLE(f);
+  REFUSE_ON_BATCH(f, "rfsgpu_collective_probe");
   if (!side_by_side) return fail(f, RFSGPU_ERR_INVALID, "collective_probe: null result pointer");
   hipSetDevice(f->device);
   const int k = ++f->collProbeSeq;
@@ -1477,6 +1527,7 @@ static int cycle_impl(rfsgpu_filter *f, int predict, const double *x, const doub
 int rfsgpu_cycle_async(rfsgpu_filter *f, int predict, const double *x, const double *x_cov, int cov_stride, const double *w_in, const double *z, int n_z,
                        int normalize) {
   CHECK_HANDLE(f);
+  REFUSE_ON_BATCH(f, "rfsgpu_cycle_async");
   return cycle_impl(f, predict, x, x_cov, cov_stride, w_in, z, n_z, true, normalize);
 }
 // The synchronous form for a host that stands where RBPHDFilter::update stands (:444-541): everything the update consumes goes in,
@@ -1540,6 +1591,7 @@ static int update_io_end(rfsgpu_filter *f, double *w_out) {
 int rfsgpu_update_io(rfsgpu_filter *f, int predict, const double *x, const double *x_cov, int cov_stride, const double *w_in, const double *z, int n_z,
                      double *w_out) {
   CHECK_HANDLE(f);
+  REFUSE_ON_BATCH(f, "rfsgpu_update_io");
   long long t0 = now_ns();
   int rc = update_io_begin(f, predict, x, x_cov, cov_stride, w_in, z, n_z, w_out != nullptr);
   if (rc != RFSGPU_OK) return rc;
@@ -1647,6 +1699,7 @@ static int predict_launch(rfsgpu_filter *f, int add_birth) {
 // One level of the level-ordered birth step, for hosts that move the per-slot birth lists between shards themselves (rfsgpu.h).
 int rfsgpu_predict_map_level(rfsgpu_filter *f, int add_birth, const int *level_of_slot, int level, int do_static) {
   CHECK_HANDLE(f);
+  REFUSE_ON_BATCH(f, "rfsgpu_predict_map_level");
   if (!level_of_slot) return fail(f, RFSGPU_ERR_INVALID, "predict_map_level: null level array");
   f->externalAck = true;
   hipSetDevice(f->device);
@@ -1665,6 +1718,7 @@ int rfsgpu_predict_map_level(rfsgpu_filter *f, int add_birth, const int *level_o
 
 int rfsgpu_predict_map(rfsgpu_filter *f, int add_birth) {
   CHECK_HANDLE(f);
+  REFUSE_ON_BATCH(f, "rfsgpu_predict_map");
   if (add_birth && f->resampleOccured && f->inheritMode == RFSGPU_INHERIT_EXTERNAL && !f->externalAck)
     return fail(f, RFSGPU_ERR_INVALID, "predict_map with births after a resampling in RFSGPU_INHERIT_EXTERNAL mode, but the host has not applied the "
                 "inheritance rule (rfsgpu_set_unused_masks, rfsgpu_predict_map_level, or rfsgpu_set_birth_inheritance(EXTERNAL) again to acknowledge): "
@@ -1684,6 +1738,7 @@ int rfsgpu_predict_map(rfsgpu_filter *f, int add_birth) {
 // RBPHDFilter::predict's map part without the error-word readback: stream-ordered, errors surface at the next synchronising call.
 int rfsgpu_predict_map_async(rfsgpu_filter *f, int add_birth) {
   CHECK_HANDLE(f);
+  REFUSE_ON_BATCH(f, "rfsgpu_predict_map_async");
   if (add_birth && f->resampleOccured && f->inheritMode == RFSGPU_INHERIT_EXTERNAL && !f->externalAck)
     return fail(f, RFSGPU_ERR_INVALID, "predict_map with births after a resampling in RFSGPU_INHERIT_EXTERNAL mode, but the host has not applied the "
                 "inheritance rule (rfsgpu_set_unused_masks, rfsgpu_predict_map_level, or rfsgpu_set_birth_inheritance(EXTERNAL) again to acknowledge): "
@@ -1845,6 +1900,7 @@ int rfsgpu_landmarks_in_fov(rfsgpu_filter *f, int slot, int *n_out) {
 
 int rfsgpu_weight_sums_async(rfsgpu_filter *f) {
   CHECK_HANDLE(f);
+  REFUSE_ON_BATCH(f, "rfsgpu_weight_sums_async");
   hipSetDevice(f->device);
   weight_sums_kernel<<<1, 1024, 0, f->stream>>>(f->B.weight, f->N, f->dSums);
   HIPCHK(hipGetLastError());
@@ -1853,6 +1909,7 @@ int rfsgpu_weight_sums_async(rfsgpu_filter *f) {
 void *rfsgpu_weight_sums_device_ptr(rfsgpu_filter *f) { return f ? (void *)f->dSums : nullptr; }
 int rfsgpu_weight_sums(rfsgpu_filter *f, double *out) {
   CHECK_HANDLE(f);
+  REFUSE_ON_BATCH(f, "rfsgpu_weight_sums (use rfsgpu_batch_weight_sums)");
   int rc = rfsgpu_weight_sums_async(f);
   if (rc != RFSGPU_OK) return rc;
   HIPCHK(hipMemcpyAsync(f->hSums, f->dSums, 2 * sizeof(double), hipMemcpyDeviceToHost, f->stream));
@@ -1864,6 +1921,7 @@ int rfsgpu_weight_sums(rfsgpu_filter *f, double *out) {
 int rfsgpu_normalize_weights(rfsgpu_filter *f, double sum, const void *sum_dev) { return rfsgpu_normalize_weights_parts(f, sum, sum_dev, 1); }
 int rfsgpu_normalize_weights_parts(rfsgpu_filter *f, double sum, const void *sum_dev, int n_parts) {
   CHECK_HANDLE(f);
+  REFUSE_ON_BATCH(f, "rfsgpu_normalize_weights");
   if (n_parts < 1) return RFSGPU_ERR_INVALID;
   hipSetDevice(f->device);
   long long t0 = now_ns();
@@ -1882,6 +1940,7 @@ int rfsgpu_max_particles(const rfsgpu_filter *f) { return f ? f->Ncap : -1; }
 int rfsgpu_resample_apply(rfsgpu_filter *f, const int *src_slot) { return f ? rfsgpu_resample_apply_n(f, src_slot, f->N) : RFSGPU_ERR_INVALID; }
 int rfsgpu_resample_apply_n(rfsgpu_filter *f, const int *src_slot, int n_out) {
   CHECK_HANDLE(f);
+  REFUSE_ON_BATCH(f, "rfsgpu_resample_apply");
   if (!src_slot || n_out < 1 || n_out > f->N) return RFSGPU_ERR_INVALID;
   const int nIn = f->N;
   for (int k = 0; k < n_out; k++) {
@@ -1940,6 +1999,7 @@ int rfsgpu_resample_apply_n(rfsgpu_filter *f, const int *src_slot, int n_out) {
 int rfsgpu_set_birth_inheritance(rfsgpu_filter *f, int mode) {
   CHECK_HANDLE(f);
   if (mode != RFSGPU_INHERIT_REFERENCE && mode != RFSGPU_INHERIT_EAGER && mode != RFSGPU_INHERIT_EXTERNAL) return fail(f, RFSGPU_ERR_INVALID, "set_birth_inheritance: unknown mode");
+  if (f->batch && mode != RFSGPU_INHERIT_REFERENCE) return fail(f, RFSGPU_ERR_UNSUPPORTED, "a filter batch keeps the reference birth inheritance (RFSGPU_INHERIT_REFERENCE) only");
   f->inheritMode = mode;
   f->externalAck = true;    // (EXTERNAL: the caller asserts that it owns the rule from here on, incl. for the coming predict)
   return RFSGPU_OK;
@@ -1957,7 +2017,7 @@ int rfsgpu_set_particle_ids(rfsgpu_filter *f, const int *id, const int *parent_i
   for (int k = 0; k < f->N; k++) { if (id) f->pid[k] = id[k]; if (parent_id) f->ppid[k] = parent_id[k]; }
   return RFSGPU_OK;
 }
-int rfsgpu_resample_occured(const rfsgpu_filter *f) { return f ? (f->resampleOccured ? 1 : 0) : -1; }
+int rfsgpu_resample_occured(const rfsgpu_filter *f) { return (f && !f->batch) ? (f->resampleOccured ? 1 : 0) : -1; }   // (a batch: rfsgpu_batch_resample_occured)
 int rfsgpu_get_unused_masks(rfsgpu_filter *f, unsigned long long *masks) {
   CHECK_HANDLE(f);
   if (!masks) return RFSGPU_ERR_INVALID;
@@ -2232,6 +2292,7 @@ void rfsgpu_default_fastslam_config(rfsgpu_fastslam_config *c) {  // constructor
 }
 int rfsgpu_set_fastslam_config(rfsgpu_filter *f, const rfsgpu_fastslam_config *cfg) {
   CHECK_HANDLE(f);
+  REFUSE_ON_BATCH(f, "FastSLAM");
   if (!cfg) return RFSGPU_ERR_INVALID;
   f->fs = *cfg;
   return RFSGPU_OK;
@@ -2352,6 +2413,7 @@ int rfsgpu_particle_parents(rfsgpu_filter *f, int *parent, int max_n) {
 }
 int rfsgpu_fastslam_update(rfsgpu_filter *f, const double *z, int n_z) {
   CHECK_HANDLE(f);
+  REFUSE_ON_BATCH(f, "FastSLAM");
   f->holes = false;
   f->fastSlamHandle = true;
   if (n_z == 0) return RFSGPU_OK;  // :401-402
@@ -2425,6 +2487,392 @@ int rfsgpu_mat_perm(const double *A, int n, int batch, double *out, int device_i
   hipFree(dA);
   hipFree(dO);
   return rc;
+}
+
+// ---- filter batches (rfsgpu_create_batch; step_fused.h BatchArg) --------------------------------------------------------------
+// n_filters independent 2-D filters in one handle: slot s belongs to filter s / n_per_filter.  One batch cycle is one fused step launch
+// (the BATCH instantiation: each workgroup takes its filter's Params / measurement set / counts from device tables) + one post launch
+// (the BATCH instantiation of the post kernel: per-filter write-back of the set, sums and division).  Per-slot calls work unchanged.
+__global__ void batch_inherit_kernel(unsigned long long *mask, const unsigned long long *before, const int *src, int n) {
+  const int k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= n) return;
+  const int s = src[k];
+  if (s != k) mask[k] = s < 0 ? 0ull : before[s];
+}
+__global__ void batch_reset_weights_kernel(double *w, int n, int nPer, const int *flag) {
+  const int k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k < n && flag[k / nPer]) w[k] = 1.0;
+}
+__global__ __launch_bounds__(256) void batch_weight_sums_kernel(double *w, int nPer, double *sums) {
+  step_post_tail(w + (size_t)blockIdx.x * nPer, nPer, sums + 2 * blockIdx.x, 0);
+}
+
+// Which filter of a batch raised the error word e (the stream is drained): gm_capacity -- the filter the step kernel found at the
+// capacity (BatchArg::errFilter, reset here); too many evaluation points -- a filter whose configuration asks for more than
+// RFSGPU_MAX_EVAL; the Murty bits come from the post kernel, which the filters share.
+static std::string batch_error_note(rfsgpu_filter *f, int e) {
+  std::string note;
+  auto add = [&](const std::string &t) { note += note.empty() ? " (filter batch: " + t : "; " + t; };
+  if (e & ERRBIT_CAPACITY) {
+    int b = INT_MAX;
+    const int none = INT_MAX;
+    if (hipMemcpy(&b, f->dBErrFilter, sizeof(int), hipMemcpyDeviceToHost) == hipSuccess)
+      hipMemcpy(f->dBErrFilter, &none, sizeof(int), hipMemcpyHostToDevice);
+    add(b >= 0 && b < f->nF ? "gm_capacity exceeded in filter " + std::to_string(b) : std::string("gm_capacity exceeded, filter not identified"));
+  }
+  if (e & ERRBIT_EVALPTS) {
+    int b = -1;
+    for (int q = 0; q < f->nF && b < 0; q++) {
+      const int c = f->bCfg[q].importanceWeightingEvalPointCount;
+      if (c < 0 || c > RFSGPU_MAX_EVAL) b = q;
+    }
+    add(b >= 0 ? "evaluation points beyond RFSGPU_MAX_EVAL in filter " + std::to_string(b) : std::string("evaluation points beyond RFSGPU_MAX_EVAL"));
+  }
+  if (e & (ERRBIT_MURTY | ERRBIT_MURTY_POOL)) add("raised by the Murty-200 post kernel, which all filters share");
+  return note.empty() ? note : note + ")";
+}
+static void batch_set_all(rfsgpu_filter *f) {
+  for (int b = 0; b < f->nF; b++) {
+    f->bCfg[b] = f->cfg; f->bRb[b] = f->rb; f->bKf[b] = f->kf;
+    memcpy(&f->bQ[(size_t)9 * b], f->Qlm, 9 * sizeof(double));
+  }
+  f->bParamsDirty = true;
+}
+// Params of filter b: the handle's own rule (rebuild_params) on the filter's configuration; the handle-wide fields (pose covariance
+// stride, partition mode, dense intensity) are the handle's.
+static Params batch_params(rfsgpu_filter *f, int b) {
+  const rfsgpu_filter_config cfg = f->cfg;
+  const rfsgpu_rngbrg_config rb = f->rb;
+  const rfsgpu_kf_config kf = f->kf;
+  double Q[9];
+  memcpy(Q, f->Qlm, sizeof Q);
+  const Params keep = f->P;
+  f->cfg = f->bCfg[b]; f->rb = f->bRb[b]; f->kf = f->bKf[b];
+  memcpy(f->Qlm, &f->bQ[(size_t)9 * b], sizeof Q);
+  rebuild_params(f);
+  const Params out = f->P;
+  f->cfg = cfg; f->rb = rb; f->kf = kf;
+  memcpy(f->Qlm, Q, sizeof Q);
+  f->P = keep;
+  return out;
+}
+static size_t batch_stage_bytes(const rfsgpu_filter *f) {
+  return (size_t)f->nF * (sizeof(BatchFilter) + sizeof(Params) + RFSGPU_MAX_Z * 2 * sizeof(double) + sizeof(int)) + (size_t)f->N * sizeof(int);
+}
+// One slot of the batch's pinned ring (as stage_slot): waits until the copies issued from it four cycles ago are done.
+static int batch_stage(rfsgpu_filter *f, unsigned char **h, int *k_out) {
+  const int k = f->bStageNext;
+  f->bStageNext = (k + 1) & 3;
+  const bool fresh = !f->hBStage[k] || !f->evBStage[k];
+  if (!f->hBStage[k]) HIPCHK(hipHostMalloc(&f->hBStage[k], batch_stage_bytes(f)));
+  if (!f->evBStage[k]) HIPCHK(hipEventCreateWithFlags(&f->evBStage[k], hipEventDisableTiming));
+  if (fresh) HIPCHK(hipStreamSynchronize(f->stream));
+  else HIPCHK(hipEventSynchronize(f->evBStage[k]));
+  *h = f->hBStage[k];
+  *k_out = k;
+  return RFSGPU_OK;
+}
+static int batch_check(rfsgpu_filter *f, int filter) {
+  if (!f->batch) return fail(f, RFSGPU_ERR_INVALID, "not a filter batch (rfsgpu_create_batch)");
+  if (filter < -1 || filter >= f->nF) return fail(f, RFSGPU_ERR_INVALID, "batch: filter index out of range");
+  return RFSGPU_OK;
+}
+
+int rfsgpu_create_batch(rfsgpu_filter **out, int model, int n_filters, int n_per_filter, int device_id, int gm_capacity) {
+  if (!out) return RFSGPU_ERR_INVALID;
+  *out = nullptr;
+  if (model == RFSGPU_MODEL_VICTORIAPARK_3D) return RFSGPU_ERR_UNSUPPORTED;    // (2-D range-bearing filters only)
+  if (model != RFSGPU_MODEL_RNGBRG_2D || n_filters < 1 || n_per_filter < 1 || (long long)n_filters * n_per_filter > (1 << 24)) return RFSGPU_ERR_INVALID;
+  rfsgpu_filter *f = nullptr;
+  int rc = rfsgpu_create(&f, model, n_filters * n_per_filter, device_id, gm_capacity);
+  if (rc != RFSGPU_OK) return rc;
+  f->batch = true;
+  f->nF = n_filters;
+  f->nPer = n_per_filter;
+  f->bCfg.resize(n_filters); f->bRb.resize(n_filters); f->bKf.resize(n_filters); f->bQ.assign((size_t)9 * n_filters, 0.0);
+  f->bNZ.assign(n_filters, 0);
+  f->bResampled.assign(n_filters, 0);
+  batch_set_all(f);
+  bool ok = true;
+  ok &= hipMalloc(&f->dBFilt, (size_t)n_filters * sizeof(BatchFilter)) == hipSuccess;
+  ok &= hipMalloc(&f->dBParams, (size_t)n_filters * sizeof(Params)) == hipSuccess;
+  ok &= hipMalloc(&f->dBZ, (size_t)n_filters * RFSGPU_MAX_Z * 2 * sizeof(double)) == hipSuccess;
+  ok &= hipMalloc(&f->dBZPrev, (size_t)n_filters * RFSGPU_MAX_Z * 2 * sizeof(double)) == hipSuccess;
+  ok &= hipMalloc(&f->dBSums, (size_t)n_filters * 2 * sizeof(double)) == hipSuccess;
+  ok &= hipMalloc(&f->dBErrFilter, sizeof(int)) == hipSuccess;
+  if (ok) { const int none = INT_MAX; ok &= hipMemcpy(f->dBErrFilter, &none, sizeof(int), hipMemcpyHostToDevice) == hipSuccess; }
+  ok &= hipMalloc(&f->dBMaskTmp, (size_t)f->Ncap * sizeof(unsigned long long)) == hipSuccess;
+  ok &= hipMalloc(&f->dBInhSrc, (size_t)f->Ncap * sizeof(int)) == hipSuccess;
+  if (ok) ok &= hipMemset(f->dBZPrev, 0, (size_t)n_filters * RFSGPU_MAX_Z * 2 * sizeof(double)) == hipSuccess;
+  if (ok) ok &= hipMemset(f->dBSums, 0, (size_t)n_filters * 2 * sizeof(double)) == hipSuccess;
+  if (!ok) { rfsgpu_destroy(f); return RFSGPU_ERR_HIP; }
+  *out = f;
+  return RFSGPU_OK;
+}
+int rfsgpu_n_filters(const rfsgpu_filter *f) { return f ? (f->batch ? f->nF : 1) : -1; }
+int rfsgpu_batch_configure(rfsgpu_filter *f, int filter, const rfsgpu_filter_config *cfg, const rfsgpu_rngbrg_config *model, const rfsgpu_kf_config *kf,
+                           const double *lmk_Q) {
+  CHECK_HANDLE(f);
+  int rc = batch_check(f, filter);
+  if (rc != RFSGPU_OK) return rc;
+  if (filter < 0) return fail(f, RFSGPU_ERR_INVALID, "batch_configure: filter index out of range");
+  if (cfg && cfg->birthGaussianMeasurementCountThreshold != 1u)
+    return fail(f, RFSGPU_ERR_UNSUPPORTED, "batch_configure: a filter batch takes immediate births only (birthGaussianMeasurementCountThreshold 1)");
+  if (cfg) f->bCfg[filter] = *cfg;
+  if (model) f->bRb[filter] = *model;
+  if (kf) f->bKf[filter] = *kf;
+  if (lmk_Q) memcpy(&f->bQ[(size_t)9 * filter], lmk_Q, 4 * sizeof(double));
+  f->bParamsDirty = true;
+  return RFSGPU_OK;
+}
+
+// One predict + update cycle of every filter (rfsgpu_cycle_async per filter, in one launch chain).  z: [n_filters][RFSGPU_MAX_Z][2],
+// n_z: [n_filters]; a filter with n_z 0 is not updated (its predict part runs; its weights are summed / divided as asked).
+int rfsgpu_batch_cycle_async(rfsgpu_filter *f, int predict, const double *x, const double *x_cov, int cov_stride, const double *z, const int *n_z,
+                             int normalize) {
+  CHECK_HANDLE(f);
+  int rc = batch_check(f, -1);
+  if (rc != RFSGPU_OK) return rc;
+  if (predict < -1 || predict > 1) return fail(f, RFSGPU_ERR_INVALID, "batch_cycle: predict is RFSGPU_CYCLE_NO_PREDICT (-1), 0 (static step only) or 1 (births + static step)");
+  if (x_cov && cov_stride != 0 && cov_stride != 9) return fail(f, RFSGPU_ERR_INVALID, "batch_cycle: cov_stride must be 0 or 9");
+  if (!n_z) return fail(f, RFSGPU_ERR_INVALID, "batch_cycle: null measurement counts");
+  const int nF = f->nF, nPer = f->nPer;
+  int nZmax = 0, ecMax = 1;
+  for (int b = 0; b < nF; b++) {
+    if (n_z[b] < 0 || n_z[b] > RFSGPU_MAX_Z) {
+      f->err = "batch_cycle: filter " + std::to_string(b) + " has " + std::to_string(n_z[b]) + " measurements (0 ... RFSGPU_MAX_Z)";
+      return RFSGPU_ERR_INVALID;
+    }
+    if (n_z[b] > 0 && !z) return fail(f, RFSGPU_ERR_INVALID, "batch_cycle: null measurement buffer");
+    if (f->bCfg[b].birthGaussianMeasurementCountThreshold != 1u)
+      return fail(f, RFSGPU_ERR_UNSUPPORTED, "batch_cycle: a filter batch takes immediate births only (birthGaussianMeasurementCountThreshold 1)");
+    nZmax = std::max(nZmax, n_z[b]);
+  }
+  hipSetDevice(f->device);
+  long long t0 = now_ns();
+  // pose covariance stride: handle-wide, as rfsgpu_cycle_async sets it
+  if (x) {
+    const int stride = x_cov ? cov_stride : 0;
+    if (f->P.poseCovStride != stride) { f->P.poseCovStride = stride; f->bParamsDirty = true; }
+  }
+  // the reference's lazy birth-state copy after a resampling (birth.h): with immediate births only the unused-measurement mask moves.
+  // A slot copies from a HIGHER slot what that slot held before this predict, and from a LOWER slot what that one holds after its own
+  // birth step: nothing once that filter has had an update (its births consume the whole mask), else what it inherited in turn.
+  ensure_ids(f);
+  std::vector<int> src;
+  if (predict == 1) {
+    for (int b = 0; b < nF; b++) {
+      if (!f->bResampled[b]) continue;
+      const int lo = b * nPer, hi = lo + nPer;
+      for (int k = lo; k < hi; k++) {
+        int p = f->ppid[k];
+        if (p < lo || p >= hi) p = k;
+        if (p == k && src.empty()) continue;
+        if (src.empty()) { src.resize(f->N); for (int q = 0; q < f->N; q++) src[q] = q; }
+        // (a lower slot's birth step -- predict_map_particle, immediate births -- empties its mask only when the filter has had an
+        //  update; before that the lower slot still holds what it inherited)
+        src[k] = p > k ? p : (p == k ? k : (f->bNZ[b] > 0 ? -1 : src[p]));
+      }
+    }
+  }
+  // per-cycle tables into a slot of the pinned ring, then to the device
+  unsigned char *h = nullptr;
+  int kb = 0;
+  if ((rc = batch_stage(f, &h, &kb)) != RFSGPU_OK) return rc;
+  BatchFilter *hf = reinterpret_cast<BatchFilter *>(h);
+  Params *hp = reinterpret_cast<Params *>(h + (size_t)nF * sizeof(BatchFilter));
+  double *hz = reinterpret_cast<double *>(h + (size_t)nF * (sizeof(BatchFilter) + sizeof(Params)));
+  int *hsrc = reinterpret_cast<int *>(hz + (size_t)nF * RFSGPU_MAX_Z * 2);
+  int zOff = 0;
+  for (int b = 0; b < nF; b++) {
+    BatchFilter &F = hf[b];
+    memset(&F, 0, sizeof F);
+    F.nZ = n_z[b];
+    F.nZprev = f->bNZ[b];
+    int c = f->bCfg[b].importanceWeightingEvalPointCount;
+    if (c < 0 || c > RFSGPU_MAX_EVAL) c = RFSGPU_MAX_EVAL;
+    if (c < 1) c = 1;
+    F.evalCap = c;
+    ecMax = std::max(ecMax, c);
+    F.useW = f->bCfg[b].useClusterProcess ? 0 : 1;
+    F.zOff = zOff;
+    if (n_z[b] > 0) memcpy(hz + zOff, z + (size_t)b * RFSGPU_MAX_Z * 2, (size_t)n_z[b] * 2 * sizeof(double));
+    zOff += 2 * n_z[b];
+  }
+  HIPCHK(hipMemcpyAsync(f->dBFilt, hf, (size_t)nF * sizeof(BatchFilter), hipMemcpyHostToDevice, f->stream));
+  if (zOff) HIPCHK(hipMemcpyAsync(f->dBZ, hz, (size_t)zOff * sizeof(double), hipMemcpyHostToDevice, f->stream));
+  {
+    const int hw[3] = {f->P.poseCovStride, f->P.exactPartitions, f->P.denseIntensity};
+    for (int q = 0; q < 3; q++)
+      if (hw[q] != f->bHandleWide[q]) { f->bHandleWide[q] = hw[q]; f->bParamsDirty = true; }
+  }
+  if (f->bParamsDirty) {
+    for (int b = 0; b < nF; b++) hp[b] = batch_params(f, b);
+    HIPCHK(hipMemcpyAsync(f->dBParams, hp, (size_t)nF * sizeof(Params), hipMemcpyHostToDevice, f->stream));
+    f->bParamsDirty = false;
+  }
+  if (!src.empty()) {
+    memcpy(hsrc, src.data(), (size_t)f->N * sizeof(int));
+    HIPCHK(hipMemcpyAsync(f->dBInhSrc, hsrc, (size_t)f->N * sizeof(int), hipMemcpyHostToDevice, f->stream));
+    HIPCHK(hipMemcpyAsync(f->dBMaskTmp, f->B.unusedMask, (size_t)f->N * sizeof(unsigned long long), hipMemcpyDeviceToDevice, f->stream));
+    batch_inherit_kernel<<<(f->N + 255) / 256, 256, 0, f->stream>>>(f->B.unusedMask, f->dBMaskTmp, f->dBInhSrc, f->N);
+  }
+  HIPCHK(hipEventRecord(f->evBStage[kb], f->stream));
+  // the host's new poses / covariances, pulled by the step kernel from a slot of the staging ring (rfsgpu_cycle_async's form)
+  StepPredict sp = NO_HEAD;
+  sp.mode = predict < 0 ? 0 : (predict ? 2 : 1);
+  sp.birthPose = f->B.pose;
+  int ks = -1;
+  if (x) {
+    double *hx = nullptr;
+    if ((rc = stage_slot(f, &hx, &ks)) != RFSGPU_OK) return rc;
+    const bool pullCov = x_cov && cov_stride == 9;
+    sp.inPacked = hx;
+    sp.inMask = 1 | (pullCov ? 2 : 0);
+    for (int i = 0; i < f->N; i++) {
+      double *d = hx + (size_t)13 * i;
+      d[0] = x[3 * i]; d[1] = x[3 * i + 1]; d[2] = x[3 * i + 2];
+      if (pullCov) memcpy(d + 3, x_cov + (size_t)9 * i, 9 * sizeof(double));
+    }
+    double *hc = hx + (size_t)f->Ncap * 13;
+    if (x_cov) {
+      if (!pullCov) {
+        memcpy(hc, x_cov, 9 * sizeof(double));
+        HIPCHK(hipMemcpyAsync(f->B.poseCov, hc, 9 * sizeof(double), hipMemcpyHostToDevice, f->stream));
+      }
+      f->poseCovZero = false;
+    } else if (!f->poseCovZero) {
+      memset(hc, 0, 9 * sizeof(double));
+      HIPCHK(hipMemcpyAsync(f->B.poseCov, hc, 9 * sizeof(double), hipMemcpyHostToDevice, f->stream));
+      f->poseCovZero = true;
+    }
+  }
+  BatchArg A{f->dBFilt, f->dBParams, f->dBZ, f->dBZPrev, f->dBSums, f->dBErrFilter, nF, nPer};
+  // waves per particle and phase priorities: the single handle's rule (update_async_impl) for the whole launch, LDS sized for the
+  // batch's largest evalCap and set (every filter's own layout lies inside it)
+  const size_t b2 = step_fused_lds_total(f->cap, ecMax, nZmax, 2);
+  const int perCU2 = (int)std::min<size_t>(8, b2 ? (size_t)(160 * 1024) / b2 : 8);
+  int wpp = ((long long)perCU2 * f->nCU >= f->N || perCU2 >= 8) ? 2 : 3;
+  {
+    const size_t b3 = step_fused_lds_total(f->cap, ecMax, nZmax, 3);
+    const int perCU3 = (int)std::min<size_t>(16 / 3, b3 ? (size_t)(160 * 1024) / b3 : 16 / 3);
+    if ((long long)perCU3 * f->nCU >= f->N) wpp = 3;
+  }
+  if (f->stepWppOverride == 2 || f->stepWppOverride == 3) wpp = f->stepWppOverride;
+  const size_t lds = step_fused_lds_total(f->cap, ecMax, nZmax, wpp);
+  const int perCU = (int)std::min<size_t>(16 / wpp, lds ? (size_t)(160 * 1024) / lds : 16);
+  const int phasePrio = (long long)perCU * f->nCU >= f->N ? 1 : 0;
+  f->lastStepVariant[0] = wpp; f->lastStepVariant[1] = phasePrio; f->lastStepVariant[2] = 5; f->lastStepVariant[3] = sp.mode ? 2 : (sp.inMask ? 3 : 1);
+  if ((rc = vp_order_buffers(f)) != RFSGPU_OK) return rc;
+  const StepLaunchOrder sloOn{f->vpOrderMode ? f->vpCost : nullptr, f->vpOrderMode ? f->vpOrder : nullptr}, sloOff{nullptr, nullptr};
+  static const ZArg noZ{};
+  (void)noZ;
+#define BATCH_LAUNCH(WPPV, PRIO)                                                                                                      \
+  do {                                                                                                                                \
+    if (sp.mode || sp.inMask) {                                                                                                       \
+      if ((rc = set_lds(f, (phd_step_fused_kernel<WPPV, PRIO, 5, true, true>), lds)) != RFSGPU_OK) return rc;                        \
+      phd_step_fused_kernel<WPPV, PRIO, 5, true, true><<<f->N, WPPV * 64, lds, f->stream>>>(f->B, f->P, f->cur, 0, 1, 1, f->Q, A, sp, PRIO ? sloOff : sloOn);   \
+    } else {                                                                                                                          \
+      if ((rc = set_lds(f, (phd_step_fused_kernel<WPPV, PRIO, 5, false, true>), lds)) != RFSGPU_OK) return rc;                       \
+      phd_step_fused_kernel<WPPV, PRIO, 5, false, true><<<f->N, WPPV * 64, lds, f->stream>>>(f->B, f->P, f->cur, 0, 1, 1, f->Q, A, sp, PRIO ? sloOff : sloOn); \
+    }                                                                                                                                 \
+  } while (0)
+  if (wpp == 2) { if (phasePrio) BATCH_LAUNCH(2, true); else BATCH_LAUNCH(2, false); }
+  else { if (phasePrio) BATCH_LAUNCH(3, true); else BATCH_LAUNCH(3, false); }
+#undef BATCH_LAUNCH
+  HIPCHK(hipGetLastError());
+  const bool sortCosts = !phasePrio && f->vpOrderMode == 2;
+  const StepOrderArg sord{sortCosts ? f->vpCost : nullptr, f->vpOrder, f->N, f->vpCost + f->Ncap, f->vpParity};
+  if (sortCosts) f->vpParity ^= 1;
+  if (murty_launch_batch(f->Q, f->MS, f->B, f->stream, A, normalize, f->hJobCount, sord) != 0) return fail(f, RFSGPU_ERR_HIP, "batch post kernel launch failed");
+  if (ks >= 0) HIPCHK(hipEventRecord(f->evStage[ks], f->stream));   // the pinned input slot is free once the step kernel has read it
+  f->cur ^= 1;   // (filters without an update had their mixture moved to the new slab by the step kernel)
+  for (int b = 0; b < nF; b++)
+    if (n_z[b] > 0) { f->bNZ[b] = n_z[b]; f->bResampled[b] = 0; }
+  f->holes = false;
+  f->timing.mapUpdate_cpu += now_ns() - t0;
+  return RFSGPU_OK;
+}
+// {sum w, sum w^2} of every filter's current weights, [n_filters][2] (synchronising).
+int rfsgpu_batch_weight_sums(rfsgpu_filter *f, double *out) {
+  CHECK_HANDLE(f);
+  int rc = batch_check(f, -1);
+  if (rc != RFSGPU_OK) return rc;
+  if (!out) return fail(f, RFSGPU_ERR_INVALID, "batch_weight_sums: null output");
+  hipSetDevice(f->device);
+  batch_weight_sums_kernel<<<f->nF, 256, 0, f->stream>>>(f->B.weight, f->nPer, f->dBSums);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(out, f->dBSums, (size_t)f->nF * 2 * sizeof(double), hipMemcpyDeviceToHost, f->stream));
+  HIPCHK(hipStreamSynchronize(f->stream));
+  return RFSGPU_OK;
+}
+// Resampling of the filters whose flag is set: slot k takes slot src_slot[k] (global slots, a source in k's own block that keeps
+// itself); their weights become 1 and their resampleOccured_ is set.  The other filters' entries of src_slot are not read.
+int rfsgpu_batch_resample_apply(rfsgpu_filter *f, const int *src_slot, const unsigned char *resampled) {
+  CHECK_HANDLE(f);
+  int rc = batch_check(f, -1);
+  if (rc != RFSGPU_OK) return rc;
+  if (!src_slot || !resampled) return fail(f, RFSGPU_ERR_INVALID, "batch_resample_apply: null argument");
+  const int nF = f->nF, nPer = f->nPer;
+  bool any = false;
+  for (int b = 0; b < nF; b++) {
+    if (!resampled[b]) continue;
+    any = true;
+    const int lo = b * nPer, hi = lo + nPer;
+    for (int k = lo; k < hi; k++) {
+      const int s = src_slot[k];
+      if (s < lo || s >= hi) {
+        f->err = "batch_resample_apply: filter " + std::to_string(b) + ": source slot " + std::to_string(s) + " of slot " + std::to_string(k) + " lies outside the filter's block";
+        return RFSGPU_ERR_INVALID;
+      }
+      if (src_slot[s] != s) {
+        f->err = "batch_resample_apply: filter " + std::to_string(b) + ": a source slot must keep itself";
+        return RFSGPU_ERR_INVALID;
+      }
+    }
+  }
+  if (!any) return RFSGPU_OK;
+  ensure_ids(f);
+  hipSetDevice(f->device);
+  long long t0 = now_ns();
+  double *hs;
+  int ks;
+  if ((rc = stage_slot(f, &hs, &ks)) != RFSGPU_OK) return rc;
+  int *hsrc = reinterpret_cast<int *>(hs);
+  int *hflag = hsrc + f->N;
+  for (int b = 0; b < nF; b++) {
+    hflag[b] = resampled[b] ? 1 : 0;
+    const int lo = b * nPer, hi = lo + nPer;
+    for (int k = lo; k < hi; k++) {
+      const int s = resampled[b] ? src_slot[k] : k;
+      hsrc[k] = s;
+      if (!resampled[b]) continue;
+      if (s != k) { f->pid[k] = f->pid[s]; f->ppid[k] = f->pid[s]; }
+      else f->ppid[k] = f->pid[k];
+    }
+    if (resampled[b]) f->bResampled[b] = 1;
+  }
+  resample_gather_kernel<<<f->N, 256, 0, f->stream>>>(f->B, f->cur, hsrc, f->P.poseCovStride, 1);
+  batch_reset_weights_kernel<<<(f->N + 255) / 256, 256, 0, f->stream>>>(f->B.weight, f->N, nPer, hflag);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipEventRecord(f->evStage[ks], f->stream));
+  const long long dtn = now_ns() - t0;
+  f->timing.particleResample_wall += dtn;
+  f->timing.particleResample_cpu += dtn;
+  return RFSGPU_OK;
+}
+// [test] 1 once a step of this handle has queued Murty-200 partitions (the post kernel's pinned flag, see murty_launch)
+int rfsgpu_murty_seen(rfsgpu_filter *f) {
+  CHECK_HANDLE(f);
+  hipSetDevice(f->device);
+  HIPCHK(hipStreamSynchronize(f->stream));
+  return *f->hJobCount ? 1 : 0;
+}
+// resampleOccured_ of every filter, [n_filters]
+int rfsgpu_batch_resample_occured(const rfsgpu_filter *f, unsigned char *out) {
+  if (!f || !f->batch || !out) return RFSGPU_ERR_INVALID;
+  for (int b = 0; b < f->nF; b++) out[b] = f->bResampled[b] ? 1 : 0;
+  return RFSGPU_OK;
 }
 
 }  // extern "C"

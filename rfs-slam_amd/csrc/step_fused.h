@@ -15,6 +15,8 @@
 #include "weighting.h"
 #include "merge_prune.h"
 
+#include <type_traits>
+
 #ifndef STEP_WPP
 #define STEP_WPP 2
 #endif
@@ -66,10 +68,24 @@ __host__ __device__ inline size_t step_fused_lds_total(int cap, int evalCap, int
 // PRED: the instantiation with the predict at its head (a template parameter, not a run-time branch: the births' sin / cos bring
 // 60 B of scratch per lane into the kernel, and the plain step -- configs[1]'s headline -- lost 10 us to it when both shared one body;
 // the head as a real call with its own register allocation: C2b 0.112 -> 0.208 ms per cycle, profiles/r05a_*).
-template <int WPP, bool PHASE_PRIO, int GL = 5, bool PRED = false>
+// A batch shares the device error word.  Which filter overflowed gm_capacity: the births of the predict head and the map update clamp an
+// overflowing mixture at the capacity, so a workgroup whose particle stands at the capacity while the capacity bit is up enters its filter
+// in BatchArg::errFilter (the lowest such filter wins; the host names it, check_device_errors).
+__device__ __forceinline__ void batch_note_capacity(const Buffers &B, const BatchArg &A, const int i, const int bf, const int tid) {
+  if (tid != 0) return;
+  const int n = __hip_atomic_load(B.count + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+  if (n < B.cap) return;
+  if (__hip_atomic_load(B.err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & ERRBIT_CAPACITY) atomicMin(A.errFilter, bf);
+}
+
+// BATCH (rfsgpu_create_batch): the workgroup's filter is particle / nPer (the particle, not the launch slot: the cost-ordered launch
+// maps slots to particles first), and its Params, measurement set, nZ, evalCap and weighting switch come from the BatchArg tables in
+// place of the arguments of the same names (which it ignores).  Everything else is the single filter's code path: same device functions
+// on the same values.  The other instantiations compile as before (every difference is behind `if constexpr`).
+template <int WPP, bool PHASE_PRIO, int GL = 5, bool PRED = false, bool BATCH = false>
 __global__ __launch_bounds__(WPP * 64) __attribute__((amdgpu_waves_per_eu(STEP_WAVES_PER_EU)))
-void phd_step_fused_kernel(Buffers B, Params P, int cur, int nZ, int evalCap, int useWeighting, MurtyQueue Q, ZArg zarg, StepPredict SP,
-                           StepLaunchOrder SLO) {
+void phd_step_fused_kernel(Buffers B, Params Parg, int cur, int nZarg, int evalCapArg, int useWeightingArg, MurtyQueue Q,
+                           typename std::conditional<BATCH, BatchArg, ZArg>::type zarg, StepPredict SP, StepLaunchOrder SLO) {
   extern __shared__ __align__(16) unsigned char smem_raw[];
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -79,6 +95,16 @@ void phd_step_fused_kernel(Buffers B, Params P, int cur, int nZ, int evalCap, in
     if (SLO.order) i = SLO.order[blockIdx.x];      // (workgroup-uniform: a scalar load)
     if (SLO.cost) tStart = wall_clock64();
   }
+  int bf = 0;   // the particle's filter
+  if constexpr (BATCH) bf = __builtin_amdgcn_readfirstlane(i / zarg.nPer);
+  const Params &P = [&]() -> const Params & { if constexpr (BATCH) return zarg.params[bf]; else return Parg; }();
+  int nZ = nZarg, evalCap = evalCapArg, useWeighting = useWeightingArg;
+  if constexpr (BATCH) {
+    const BatchFilter &F = zarg.filt[bf];
+    nZ = __builtin_amdgcn_readfirstlane(F.nZ);
+    evalCap = __builtin_amdgcn_readfirstlane(F.evalCap);
+    useWeighting = __builtin_amdgcn_readfirstlane(F.useW);
+  }
   // Round 5: the map part of the PREDICT that precedes this update (RBPHDFilter::predict, include/RBPHDFilter.hpp:415-442 -- birth
   // Gaussians from the previous update's unused measurements at the poses that update used, then Sigma += Q on every Gaussian,
   // include/ProcessModel.hpp:195-208) runs at the head of the step, by the workgroup that owns the particle: one launch chain per
@@ -86,7 +112,13 @@ void phd_step_fused_kernel(Buffers B, Params P, int cur, int nZ, int evalCap, in
   // function is the stand-alone predict kernel's (merge_prune.h, predict_map_particle): same bits.  B.Z still holds the PREVIOUS
   // measurement set here (this step's post kernel writes the new one).
   if constexpr (PRED) {
-    if (SP.mode) predict_map_particle<WPP * 64>(B, P, cur, i, tid, SP.mode > 1, SP.nZprev, SP.birthPose, true);
+    if constexpr (BATCH) {     // the filter's own previous set and count
+      Buffers Bp = B;
+      Bp.Z = zarg.zPrev + (size_t)bf * (RFSGPU_MAX_Z * 2);
+      if (SP.mode) predict_map_particle<WPP * 64>(Bp, P, cur, i, tid, SP.mode > 1, __builtin_amdgcn_readfirstlane(zarg.filt[bf].nZprev), SP.birthPose, true);
+    } else {
+      if (SP.mode) predict_map_particle<WPP * 64>(B, P, cur, i, tid, SP.mode > 1, SP.nZprev, SP.birthPose, true);
+    }
     // the host's inputs for THIS update, after the births have read the old pose (same wave, program order)
     if (SP.inMask && tid < 13) {
       const double v = SP.inPacked[13 * i + tid];
@@ -97,6 +129,7 @@ void phd_step_fused_kernel(Buffers B, Params P, int cur, int nZ, int evalCap, in
     __threadfence_block();
     __syncthreads();
     __builtin_amdgcn_s_dcache_inv();   // count / pose / covariance are read through the scalar cache below: drop what the head's own loads left there
+    if constexpr (BATCH) batch_note_capacity(B, zarg, i, bf, tid);
   }
   // Issue priority falls from phase to phase (s_setprio 2/3 -> 1 -> 0): the SIMD arbiter otherwise always prefers its oldest waves, so the
   // last workgroups to arrive on a CU crawl through the map update while the first ones race ahead, and the launch lasts as
@@ -108,7 +141,25 @@ void phd_step_fused_kernel(Buffers B, Params P, int cur, int nZ, int evalCap, in
   // the prune 0 (set inside gm_merge_particle) -- r02: one more level inside the merge bought another 1 % (126.7 -> 125.3 us).
   // The measurement set arrives in the kernel-argument block (no staging launch); the step's post kernel leaves it in the
   // device buffer that later kernels read (the next predict's births).  (Writing it from here cost 112 B/lane of scratch.)
-  stage_measurements_lds(smem_raw, [&](int t) { return zarg.v[t]; }, nZ, tid, WPP * 64);
+  if constexpr (BATCH) {
+    if (nZ == 0) {
+      // no update for this filter this cycle: its mixture moves to the slab the others' merge writes (the batch flips `cur` as one)
+      const int n = B.count[i];
+      for (int pl = 0; pl < PL_COUNT; pl++) {
+        const double *src = plane(B.slab[cur], B.cap, i, pl);
+        double *dst = plane(B.slab[cur ^ 1], B.cap, i, pl);
+        for (int m = tid; m < n; m += WPP * 64) dst[m] = src[m];
+      }
+      if constexpr (!PHASE_PRIO) {
+        if (SLO.cost && threadIdx.x == 0) SLO.cost[i] = 0.f;
+      }
+      return;
+    }
+    const double *zs = zarg.z + zarg.filt[bf].zOff;
+    stage_measurements_lds(smem_raw, [&](int t) { return zs[t]; }, nZ, tid, WPP * 64);
+  } else {
+    stage_measurements_lds(smem_raw, [&](int t) { return zarg.v[t]; }, nZ, tid, WPP * 64);
+  }
   __syncthreads();
 #ifdef RFS_PROFILE
   long long *fd = B.dbg ? B.dbg + 64 + 4 * (size_t)B.N + 4 * (size_t)i : nullptr;
@@ -121,6 +172,7 @@ void phd_step_fused_kernel(Buffers B, Params P, int cur, int nZ, int evalCap, in
   else phd_update_map_block<WPP>(B, P, cur, nZ, i, tid, smem_raw, smem_raw + RFS_Z_LDS_BYTES, PHASE_PRIO);
   __threadfence_block();  // the slab / count written by wave 0 -> the whole workgroup
   __syncthreads();
+  if constexpr (BATCH) batch_note_capacity(B, zarg, i, bf, tid);
   RFS_CUT(8);
 #ifdef RFS_PROFILE
   if (fd && tid == 0) fd[1] = (long long)wall_clock64();

@@ -397,3 +397,72 @@ def _systematic_resample_plan_shrink(w, u01, n):
         src[nxt] = idx
         nxt += 1
     return src
+
+
+class FilterBatch(capi.CBatch):
+    """n_filters independent 2-D RB-PHD filters stepped together (rfsgpu_create_batch): one fused launch + one post launch per cycle for
+    all of them.  Filter b owns the global slots [b * n_per_filter, (b + 1) * n_per_filter); each filter has its own configuration,
+    measurement set, weights, normalisation and resampling, and equals a separate RBPHDFilter given the same inputs."""
+
+    def __init__(self, n_filters, n_per_filter, device_id=0, gm_capacity=512, model=capi.MODEL_RNGBRG_2D):
+        super().__init__(load_library(), "rfsgpu_", n_filters, n_per_filter, model=model, device_id=device_id, gm_capacity=gm_capacity)
+        self.configs = [self.default_filter_config() for _ in range(n_filters)]
+        self.nUpdatesSinceResample = np.zeros(n_filters, dtype=np.int64)
+        self.nMeasurementsSinceResample = np.zeros(n_filters, dtype=np.int64)
+
+    def configure(self, b, cfg=None, **model):
+        """Filter b's configuration (see CBatch.batch_configure); cfg also becomes self.configs[b] (the resampling thresholds)."""
+        if cfg is not None:
+            self.configs[b] = cfg
+        self.batch_configure(b, cfg=cfg, **model)
+
+    def cycle_async(self, predict, Zs, poses=None, pose_cov=None, normalize=True):
+        """One predict + update cycle of every filter (rfsgpu_batch_cycle_async)."""
+        self.batch_cycle_async(predict, Zs, poses=poses, pose_cov=pose_cov, normalize=normalize)
+
+    def weight_sums_per_filter(self):
+        """{sum w, sum w^2} of each filter: [n_filters, 2]."""
+        return self.batch_weight_sums()
+
+    def normalize_per_filter(self):
+        """Divide each filter's weights by their own sum (ParticleFilter::normalizeWeights per filter)."""
+        w = self.get_weights()
+        for b in range(self.n_filters):
+            blk = self.block(b)
+            w[blk] = w[blk] / np.sum(w[blk])
+        self.set_weights(w)
+
+    def update_and_resample(self, n_z, u01, eff_n):
+        """The tail of RBPHDFilter::update after a batch cycle with normalize (:444-539), per filter, as RBPHDFilter.update_and_resample
+        does it for one handle: every cycle counts as an update (nUpdatesSinceResample_ grows before the empty-set return, :448-452), a
+        filter without measurements stops there; otherwise ParticleFilter::resample's minimum-update / minimum-measurement gate and
+        N_eff test, and the systematic plan (systematic_resample_plan) with that filter's draw.  u01: a callable u01(b) -> [0, 1),
+        called only for a filter whose N_eff test fires (as Sim2dRun draws), or an array of draws.  One rfsgpu_batch_resample_apply for
+        the filters that fire.  n_z: the cycle's measurement counts; eff_n: the N_eff threshold per filter.
+        Returns (fired [n_filters] bool, plan [N] global source slots)."""
+        nF, nP = self.n_filters, self.n_per_filter
+        n_z = np.asarray(n_z)
+        w = self.get_weights()
+        fired = np.zeros(nF, dtype=bool)
+        plan = np.arange(self.n, dtype=np.int32)
+        for b in range(nF):
+            self.nUpdatesSinceResample[b] += 1
+            if n_z[b] == 0:
+                continue
+            self.nMeasurementsSinceResample[b] += int(n_z[b])
+            c = self.configs[b]
+            if self.nUpdatesSinceResample[b] < c.minUpdatesBeforeResample or self.nMeasurementsSinceResample[b] < c.minMeasurementsBeforeResample:
+                continue
+            wb = w[self.block(b)]
+            neff = 1.0 / float(np.sum(wb * wb))
+            if neff > eff_n[b] and neff / nP > eff_n[b] / nP:
+                continue
+            u = float(u01(b)) if callable(u01) else float(u01[b])
+            plan[self.block(b)] = b * nP + systematic_resample_plan(wb, u)
+            fired[b] = True
+            self.nUpdatesSinceResample[b] = 0
+            self.nMeasurementsSinceResample[b] = 0
+        if fired.any():
+            self.batch_resample_apply(plan, fired)
+        return fired, plan
+

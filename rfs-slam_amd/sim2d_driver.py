@@ -14,6 +14,7 @@ methods of capi.CFilter.
 """
 import numpy as np
 
+from . import capi
 from .engine import systematic_resample_plan
 
 # values of the shipped cfg/rbphdslam2dSim.xml (tests/golden/rbphdslam2dSim_c1.xml)
@@ -190,6 +191,121 @@ class Sim2dRun:
 
     def run(self, k_from=1, k_to=None, on_step=None):
         for k in range(k_from, int(k_to or self.data["K"])):
+            fired = self.step(k)
+            if on_step is not None:
+                on_step(k, self, fired)
+        return self
+
+
+def configure_batch_filter(batch, b, P=C1_SIM):
+    """setupRBPHDFilter for filter b of a FilterBatch (what configure() does for a handle)."""
+    dt = P["dt"]
+    cfg = batch.default_filter_config()
+    cfg.birthGaussianWeight = P["birth_w"]
+    cfg.minUpdatesBeforeResample = P["min_updates"]
+    cfg.newGaussianCreateInnovMDThreshold = P["new_gaussian_md"]
+    cfg.importanceWeightingMeasurementLikelihoodMDThreshold = P["weighting_md"]
+    cfg.importanceWeightingEvalPointCount = P["n_eval"]
+    cfg.importanceWeightingEvalPointGuassianWeight = P["min_weight"]
+    cfg.gaussianMergingThreshold = P["merge_thr"]
+    cfg.gaussianMergingCovarianceInflationFactor = P["merge_infl"]
+    cfg.gaussianPruningThreshold = P["prune_thr"]
+    cfg.useClusterProcess = P["use_cluster"]
+    R = np.diag([P["varzr"], P["varzb"]]) * P["z_noise_inflation"]
+    batch.configure(b, cfg, R=R, Pd=P["Pd"], clutter=P["clutter"], rmax=P["rmax"], rmin=P["rmin"], rbuf=P["rbuf"], kf=(P["kf_range"], P["kf_bearing"]),
+                    Q=np.diag([P["varlmx"], P["varlmy"]]) * dt * dt)
+    return cfg
+
+
+class Sim2dBatchRun:
+    """run() :540-643 for MANY independent filters, each with its own realisation (`datas[b]`, its own generate(traj_seed=...)), its
+    own configuration dict `Ps[b]` and its own host RNG stream (`seeds[b]`: process noise, resampling draws).  `target` is either a
+    FilterBatch (every filter's cycle in one batch launch chain) or a list of ordinary handles, one per filter (cycled one after
+    another): the same per-filter randomness drives both, so that the two can be compared.  Per cycle and filter: predict (births +
+    static step) with the new poses, the update with the step's measurements (none: no update), normalisation, and
+    ParticleFilter::resample's gate / N_eff test / systematic plan (FilterBatch.update_and_resample; the same rule per handle).  As in
+    Sim2dRun, every cycle counts as an update for the gate (empty ones included), a filter draws its process noise every step and its
+    resampling draw only when its N_eff test fires: a one-filter run takes the draws Sim2dRun takes with the same seed."""
+
+    def __init__(self, target, datas, Ps, seeds):
+        self.batch = target if isinstance(target, capi.CBatch) else None
+        self.handles = None if self.batch is not None else list(target)
+        self.nF = len(datas)
+        self.n = self.batch.n_per_filter if self.batch is not None else self.handles[0].n
+        assert len(Ps) == self.nF and len(seeds) == self.nF
+        assert self.batch is None or self.batch.n_filters == self.nF
+        assert self.handles is None or len(self.handles) == self.nF
+        self.datas, self.Ps = list(datas), list(Ps)
+        self.rngs = [np.random.default_rng(s) for s in seeds]
+        self.x = [np.zeros((self.n, 3)) for _ in range(self.nF)]
+        self.cov = [np.zeros((3, 3)) for _ in range(self.nF)]
+        self.Q = [np.diag([P["vardx"], P["vardy"], P["vardz"]]) * P["p_noise_inflation"] * P["dt"] ** 2 for P in self.Ps]
+        self.eff_n = np.array([float(P["eff_n"]) for P in self.Ps])
+        if self.batch is not None:
+            self.cfgs = [configure_batch_filter(self.batch, b, P) for b, P in enumerate(self.Ps)]
+        else:
+            self.cfgs = [configure(f, P) for f, P in zip(self.handles, self.Ps)]
+        self.n_updates_since = np.zeros(self.nF, dtype=np.int64)
+        self.n_meas_since = np.zeros(self.nF, dtype=np.int64)
+        self.last_n_z = np.zeros(self.nF, dtype=np.int64)
+        self.last_fired = np.zeros(self.nF, dtype=bool)
+        self.last_plans = [np.arange(self.n) for _ in range(self.nF)]
+        self.n_resamples = np.zeros(self.nF, dtype=np.int64)
+        self.resample_steps = [[] for _ in range(self.nF)]    # the steps k at which each filter resampled
+
+    def step(self, k):
+        Zs = []
+        for b in range(self.nF):
+            d = self.datas[b]
+            noise = self.rngs[b].standard_normal((self.n, 3)) * np.sqrt(np.diag(self.Q[b]))
+            self.x[b] = odometry_step(self.x[b], d["odom"][k]) + noise
+            self.cov[b] = self.Q[b].copy()
+            if k <= 100:
+                self.x[b] = np.tile(d["gt"][k], (self.n, 1))
+                self.cov[b] = np.zeros((3, 3))
+            Zs.append(d["Z"][k] if k < len(d["Z"]) else np.zeros((0, 2)))
+        n_z = np.array([len(Z) for Z in Zs])
+        covs = [np.tile(c.ravel(), (self.n, 1)) for c in self.cov]
+        if self.batch is not None:
+            self.batch.cycle_async(True, Zs, poses=np.vstack(self.x), pose_cov=np.vstack(covs), normalize=True)
+            fired, plan = self.batch.update_and_resample(n_z, lambda b: self.rngs[b].random(), self.eff_n)
+            plans = [plan[self.batch.block(b)] - b * self.n for b in range(self.nF)]
+        else:
+            fired = np.zeros(self.nF, dtype=bool)
+            plans = []
+            for b, f in enumerate(self.handles):
+                if hasattr(f, "cycle_async"):
+                    f.cycle_async(True, Zs[b], poses=self.x[b], pose_cov=covs[b], normalize=True)
+                else:       # a handle with the plain calls only (the CPU oracle): the same cycle call by call
+                    f.predict_map(True)
+                    f.set_poses(self.x[b], covs[b])
+                    if n_z[b]:
+                        f.update(Zs[b])
+                    f.normalize_weights(f.weight_sums()[0])
+                plan = np.arange(self.n)
+                self.n_updates_since[b] += 1                 # (every cycle counts, RBPHDFilter.hpp:448 before :450-452)
+                if n_z[b]:
+                    self.n_meas_since[b] += int(n_z[b])
+                    c = self.cfgs[b]
+                    if self.n_updates_since[b] >= c.minUpdatesBeforeResample and self.n_meas_since[b] >= c.minMeasurementsBeforeResample:
+                        w = f.get_weights()
+                        neff = 1.0 / float(np.sum(w * w))
+                        if not (neff > self.eff_n[b] and neff / self.n > self.eff_n[b] / self.n):
+                            plan = systematic_resample_plan(w, float(self.rngs[b].random()))
+                            f.resample_apply(plan)
+                            fired[b] = True
+                            self.n_updates_since[b] = self.n_meas_since[b] = 0
+                plans.append(plan)
+        for b in range(self.nF):
+            if fired[b]:
+                self.x[b] = self.x[b][plans[b]]
+                self.resample_steps[b].append(k)
+        self.n_resamples += fired
+        self.last_n_z, self.last_fired, self.last_plans = n_z, fired, plans
+        return fired
+
+    def run(self, k_from=1, k_to=None, on_step=None):
+        for k in range(k_from, int(k_to or min(d["K"] for d in self.datas))):
             fired = self.step(k)
             if on_step is not None:
                 on_step(k, self, fired)

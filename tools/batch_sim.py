@@ -1,0 +1,102 @@
+#!/usr/bin/env python3
+"""A batchSim-style sweep on one GPU (the reference's scripts/batchSim/batchSim_rbphdslam.bash: Pd x clutter x seeds of independent
+rbphdslam2dSim runs) through a filter batch (rfsgpu_create_batch), against the same filters as independent handles stepped in turn.
+
+Prints filter-steps/s for batch sizes 1, 4, 16 and 64 at 200 particles (both forms, same per-filter realisations and randomness),
+then each run's final map error.  A tuning / evaluation tool, not part of bench.py.
+
+    python tools/batch_sim.py [--steps 200] [--sizes 1,4,16,64] [--particles 200] [--handles-max 64]
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def load_pkg():
+    sys.path.insert(0, ROOT)
+    import __graft_entry__ as g
+    return g.load_package() if hasattr(g, "load_package") else None
+
+
+def grid(sim, n, kmax):
+    pds = [0.5, 0.6, 0.7, 0.8, 0.9, 0.95, 0.99, 0.85, 0.75, 0.65]
+    clutters = [1e-4, 5e-4, 1e-3, 2e-3, 5e-3, 1e-2, 2e-2, 5e-2, 1e-1]
+    Ps, datas, seeds = [], [], []
+    for b in range(n):
+        P = dict(sim.C1_SIM)
+        P["Pd"] = pds[b % len(pds)]
+        P["clutter"] = clutters[(b // len(pds)) % len(clutters)]
+        Ps.append(P)
+        datas.append(sim.generate(P, traj_seed=1 + b, kmax=kmax))
+        seeds.append(100 + b)
+    return Ps, datas, seeds
+
+
+def timed(run, steps):
+    run.step(1)                       # warm-up (kernel loads, first allocations)
+    t0 = time.perf_counter()
+    for k in range(2, steps + 2):
+        run.step(k)
+    return time.perf_counter() - t0
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--steps", type=int, default=200)
+    ap.add_argument("--sizes", default="1,4,16,64")
+    ap.add_argument("--particles", type=int, default=200)
+    ap.add_argument("--handles-max", type=int, default=64, help="largest batch size also run as independent handles")
+    ap.add_argument("--capacity", type=int, default=256)
+    ap.add_argument("--json", default="")
+    a = ap.parse_args()
+    pkg = load_pkg()
+    sim = pkg.sim2d_driver
+    sizes = [int(s) for s in a.sizes.split(",")]
+    kmax = a.steps + 2
+    Ps, datas, seeds = grid(sim, max(sizes), kmax)
+    rows = []
+    for B in sizes:
+        batch = pkg.FilterBatch(B, a.particles, gm_capacity=a.capacity)
+        rb = sim.Sim2dBatchRun(batch, datas[:B], Ps[:B], seeds[:B])
+        tb = timed(rb, a.steps)
+        batch.synchronize()
+        row = dict(B=B, particles=a.particles, steps=a.steps, batch_filter_steps_per_s=B * a.steps / tb)
+        if B <= a.handles_max:
+            hs = [pkg.RBPHDFilter(a.particles, gm_capacity=a.capacity) for _ in range(B)]
+            rh = sim.Sim2dBatchRun(hs, datas[:B], Ps[:B], seeds[:B])
+            th = timed(rh, a.steps)
+            for h in hs:
+                h.synchronize()
+            row["handles_filter_steps_per_s"] = B * a.steps / th
+            row["speedup"] = th / tb
+            for h in hs:
+                h.close()
+        if B == max(sizes):
+            errs = []
+            for b in range(B):
+                w = batch.get_weights()[batch.block(b)]
+                i = b * a.particles + int(np.argmax(w))
+                nm, e, ns = sim.map_error(batch, i, datas[b]["landmarks"])
+                errs.append(dict(filter=b, Pd=Ps[b]["Pd"], clutter=Ps[b]["clutter"], seed=1 + b, matched=nm, n_landmarks=len(datas[b]["landmarks"]),
+                                 mean_error=e, strong=ns))
+            row["map_error"] = errs
+        batch.close()
+        rows.append(row)
+        print(json.dumps({k: v for k, v in row.items() if k != "map_error"}), flush=True)
+    for r in rows[-1].get("map_error", []):
+        print("filter %3d  Pd %.2f  clutter %.0e  seed %3d  matched %2d/%2d  mean error %.4f" % (r["filter"], r["Pd"], r["clutter"], r["seed"], r["matched"],
+                                                                                            r["n_landmarks"], r["mean_error"]))
+    if a.json:
+        os.makedirs(os.path.dirname(a.json) or ".", exist_ok=True)
+        with open(a.json, "w") as fh:
+            json.dump(rows, fh, indent=1)
+
+
+if __name__ == "__main__":
+    main()
