@@ -200,7 +200,10 @@ __device__ __forceinline__ void gm_merge_particle(const Buffers &B, const Params
   const float errAbs = 3.0e-7f * fabsmax + 1e-37f;
   // float rounding of the box / radius is covered by the 1e-3 relative slack on the cell edges; indices are clamped
   // (clamping is monotone, so adjacency is preserved for out-of-box values).  Cell edges are >= the largest prefilter
-  // radius in both directions, so every pair that can pass lies in adjacent cells.
+  // radius PLUS the rounding bound of an fp32 coordinate difference in both directions: a pair that can pass is at most one
+  // radius apart exactly, hence at most radius + errAbs apart in fp32, so it lies in adjacent cells.  (Without the errAbs term
+  // two such entries far from the origin -- where errAbs is a visible part of a radius -- could land two cells apart, and the
+  // pair was never listed.)
   const double x0 = (double)fxmin - 1e-3 * fabs((double)fxmin) - 1e-30, y0 = (double)fymin - 1e-3 * fabs((double)fymin) - 1e-30;
   const double spanx = (double)fxmax - x0, spany = (double)fymax - y0;
   // The 64 x 64 grid pays on sparse maps only (configs[2]'s shard: cells of two prefilter radii, fused step 254 -> 243 us).  Where
@@ -208,13 +211,14 @@ __device__ __forceinline__ void gm_merge_particle(const Buffers &B, const Params
   // to zero and every row that merges falls back to the sequential scan (2000 x 400 Gaussians within 2.5 m: 319 -> 573 us): such a
   // particle uses the first 32 x 32 cells of the array only (gxe x gye cells in use, row stride MERGE_GX).
   int gxe = MERGE_GX, gye = MERGE_GY;
+  const double fradE = (double)frad + 3.0 * (double)errAbs;   // the smallest cell edge: radius + rounding of the fp32 difference (1.5 errAbs is enough; 3 keeps slackOut >= 0)
   if constexpr (GL == 6) {
 #ifndef MERGE_FINE_MIN
 #define MERGE_FINE_MIN 1.5
 #endif
-    if (!(spanx / MERGE_GX >= MERGE_FINE_MIN * (double)frad) || !(spany / MERGE_GY >= MERGE_FINE_MIN * (double)frad)) { gxe = MERGE_GX / 2; gye = MERGE_GY / 2; }
+    if (!(spanx / MERGE_GX >= MERGE_FINE_MIN * fradE) || !(spany / MERGE_GY >= MERGE_FINE_MIN * fradE)) { gxe = MERGE_GX / 2; gye = MERGE_GY / 2; }
   }
-  const double cellx = fmax((double)frad, spanx / gxe) * 1.001 + 1e-300, celly = fmax((double)frad, spany / gye) * 1.001 + 1e-300;
+  const double cellx = fmax(fradE, spanx / gxe) * 1.001 + 1e-300, celly = fmax(fradE, spany / gye) * 1.001 + 1e-300;
   const bool degenerate = !(cellx < 1.0e30) || !(celly < 1.0e30) || !(spanx == spanx) || !(spany == spany) || !(errAbs < 1.0e30f);  // inf / NaN -> a single cell
   const float x0f = (float)x0, y0f = (float)y0;
   const float invCx = degenerate ? 0.f : (float)(1.0 / cellx) * (1.f - 1e-6f), invCy = degenerate ? 0.f : (float)(1.0 / celly) * (1.f - 1e-6f);

@@ -11,77 +11,9 @@ from scipy.sparse import csr_matrix
 from scipy.sparse.csgraph import connected_components
 from scipy.stats import multivariate_normal
 
+from tests.support.prefilter_reference import np_measure, np_merge, np_pd, np_update_map, wrap
+
 DENORM = np.nextafter(0, 1)
-
-
-def wrap(a):
-    return (a + np.pi) % (2 * np.pi) - np.pi
-
-
-def np_measure(P, pose, pose_cov, mu, Sig):
-    d = mu - pose[:2]
-    r2 = d @ d
-    r = np.sqrt(r2)
-    zexp = np.array([r, wrap(np.arctan2(d[1], d[0]) - pose[2])])
-    H = np.array([[d[0] / r, d[1] / r], [-d[1] / r2, d[0] / r2]])
-    Hr = np.array([[-d[0] / r, -d[1] / r, 0], [d[1] / r2, -d[0] / r2, -1]])
-    S = H @ Sig @ H.T + Hr @ pose_cov @ Hr.T + np.asarray(P["R"])
-    return zexp, H, S, (P["rmin"] <= r <= P["rmax"]), r
-
-
-def np_pd(P, r):
-    if P["rmin"] <= r <= P["rmax"]:
-        return P["Pd"], (r >= P["rmax"] - P["rbuf"] or r <= P["rmin"] + P["rbuf"])
-    return 0.0, (P["rmin"] - P["rbuf"] <= r <= P["rmax"] + P["rbuf"])
-
-
-def np_update_map(P, pose, pose_cov, w, mu, Sig, Z):
-    nM, nZ = len(w), len(Z)
-    W = np.zeros((nM, nZ))
-    new = {}
-    Pd = np.zeros(nM)
-    close = np.zeros(nM, bool)
-    for m in range(nM):
-        zexp, H, S, ok, r = np_measure(P, pose, pose_cov, mu[m], Sig[m])
-        Pd[m], close[m] = np_pd(P, r)
-        if close[m]:
-            Pd[m] = 1.0
-        if Pd[m] == 0 or not ok:
-            continue
-        Si = np.linalg.inv(S)
-        K = Sig[m] @ H.T @ Si
-        Pn = (np.eye(2) - K @ H) @ Sig[m]
-        Pn = (Pn + Pn.T) / 2
-        for z in range(nZ):
-            e = Z[z] - zexp
-            if P["kf_range"] > 0 and abs(e[0]) > P["kf_range"]:
-                continue
-            nu = np.array([e[0], wrap(e[1])])
-            if P["kf_bearing"] > 0 and abs(nu[1]) > P["kf_bearing"]:
-                continue
-            md2 = e @ Si @ e                                  # raw difference on purpose
-            if md2 > P["new_gaussian_md"] ** 2:
-                continue
-            lik = np.exp(-0.5 * md2) / np.sqrt((2 * np.pi) ** 2 * np.linalg.det(S))
-            if lik == 0:
-                continue
-            W[m, z] = Pd[m] * w[m] * lik
-            new[(m, z)] = (mu[m] + K @ nu, Pn)
-    colsum = P["clutter"] + W.sum(0)
-    Wn = W / colsum
-    out_w, out_mu, out_S = [], [], []
-    for (m, z), (x, Pn) in sorted(new.items()):
-        if Wn[m, z] > 0:
-            out_w.append(Wn[m, z]); out_mu.append(x); out_S.append(Pn)
-    wk = (1 - Pd) * w
-    for m in range(nM):
-        if close[m] and w[m] > P["birth_w"]:
-            dw = Pd[m] * w[m] - Wn[m].sum()
-            if dw > 0:
-                wk[m] = min(wk[m] + dw, 1.0)
-    unused = [z for z in range(nZ) if not np.any(Wn[:, z] != 0)]
-    return (np.concatenate([wk, out_w]), np.concatenate([w, np.zeros(len(out_w))]),
-            np.array(list(mu) + out_mu), np.array(list(Sig) + out_S), unused, int((Pd != 0).sum()), colsum)
 
 
 @pytest.mark.parametrize("seed,kw", [(1, {}), (2, dict(frac_in_fov=0.5)), (3, dict(n_landmarks=70, n_z=20))])
@@ -188,28 +120,6 @@ def test_importance_weighting_vs_numpy(ob, sc, seed):
         w, wp, mu, Sg = maps[i]
         want = np_importance_weight(scen["params"], scen["poses"][i], scen["pose_cov"][i], w, wp, mu, Sg, scen["Z"], 1.0)
         assert np.isclose(got[i], want, rtol=1e-8), (got[i], want)
-
-
-def np_merge(w, mu, Sg, t, f):
-    w, mu, Sg = w.copy(), mu.copy(), Sg.copy()
-    alive = np.ones(len(w), bool)
-    for a in range(len(w)):
-        if not alive[a]:
-            continue
-        for b in range(a + 1, len(w)):
-            if not alive[b]:
-                continue
-            e = mu[b] - mu[a]
-            if e @ np.linalg.solve(Sg[a], e) > t * t and e @ np.linalg.solve(Sg[b], e) > t * t:
-                continue
-            wm = w[a] + w[b]
-            if wm == 0:
-                continue
-            xm = (mu[a] * w[a] + mu[b] * w[b]) / wm
-            d1, d2 = xm - mu[a], xm - mu[b]
-            Sg[a] = (w[a] * (Sg[a] + f * np.outer(d1, d1)) + w[b] * (Sg[b] + f * np.outer(d2, d2))) / wm
-            mu[a], w[a], alive[b] = xm, wm, False
-    return w[alive], mu[alive], Sg[alive]
 
 
 @pytest.mark.parametrize("seed", [7, 8])
