@@ -42,7 +42,9 @@
  *   [state]    state injection and probes for tests and tools (import / export of mixtures, candidate lists, ids, masks);
  *   [bench]    snapshot / restore, kernel timing statistics, debug counters, test probes: declared only under
  *              RFSGPU_ENABLE_BENCH_API (a maintainer reading this header for the binding never meets them);
- *   [fastslam] FastSLAM / MH-FastSLAM on the same handle, the optional device-side Ackerman propagation, rfsgpu_mat_perm.
+ *   [fastslam] FastSLAM / MH-FastSLAM on the same handle, the optional device-side Ackerman propagation, rfsgpu_mat_perm;
+ *   [batch]    many independent 2-D filters in one handle, stepped together in one launch chain;
+ *   [metric]   per-step OSPA / COLA map error and pose error computed on the device, kept in a device-side log.
  * A maintainer wiring the reference to the library reads the CORE entries and INTEGRATION.md; nothing optional is required
  * for correct results.
  */
@@ -665,6 +667,61 @@ int rfsgpu_batch_resample_occured(const rfsgpu_filter *f, unsigned char *out);
 /* [test] 1 once a step of this handle (batch or not) has queued Murty-200 partitions, else 0.  Synchronising. */
 int rfsgpu_murty_seen(rfsgpu_filter *f);
 #endif
+
+/* ---- [metric] per-step map error and pose error on the device (outside the STABLE CORE) ------------------------------------------
+ * What the reference's analysis2dSim computes per time step from a run's log files (src/analysis2dSim.cpp:150-249), as one launch on
+ * the handle's stream for an ordinary 2-D handle (one filter) or for every filter of a batch: the weighted-mean pose error of the
+ * particle set (:265-317, getAverageError) and the OSPA / COLA error (include/OSPA.hpp:122-203, include/COLA.hpp:91-98) between the map estimate of
+ * the highest-weight particle and the ground-truth landmarks that have been in sensor range so far.  The kernel (csrc/map_metric.h)
+ * reads the filter state as it is at that point of the stream and writes one record per filter; nothing else changes.
+ * 2-D landmarks only: Victoria Park handles, handles on which rfsgpu_fastslam_update has run and the shard handles of an
+ * rfsgpu_group return RFSGPU_ERR_UNSUPPORTED (with a rfsgpu_last_error message) from every call of this section. */
+#define RFSGPU_MAX_METRIC_SET 512   /* hard limit of either set of one comparison (estimates, observable ground truth) */
+/* One record per filter and call; every field is 8 bytes wide.  status: 0 = ok; 1 = n_est or n_truth exceeds
+ * RFSGPU_MAX_METRIC_SET; 2 = no finite cost met (non-finite coordinates).  With status != 0 ospa, cola, e_dist, e_card are NaN
+ * and the other fields stand.  (A struct tag, not a typedef: the synchronous call below bears the same name.) */
+struct rfsgpu_step_error {
+  double t;              /* the time given with the call                                                                   */
+  long long status;
+  long long best_slot;   /* global slot of the highest-weight particle: the first slot of the filter's block whose weight is
+                            strictly greater than every earlier one, starting from 0 (analysis2dSim.cpp:159-167); slot 0 of the
+                            block when no weight is > 0                                                                    */
+  long long n_est;       /* its Gaussians with weight >= w_threshold (:187)                                                */
+  long long n_truth;     /* ground-truth landmarks with first_seen <= t (:213-220)                                         */
+  double cardinality;    /* the sum of ALL its Gaussians' weights (:194)                                                   */
+  double ospa;           /* (sum C^p / n)^(1/p) over an assignment that minimises sum C, n = max(n_est, n_truth); 0 for n = 0
+                            (OSPA.hpp:179-199)                                                                             */
+  double cola;           /* ospa * n^(1/p) / c (COLA.hpp:91-98)                                                            */
+  double e_dist;         /* sum of the assignment's cells != c (OSPA.hpp:191-192)                                          */
+  double e_card;         /* sum of the assignment's cells == c (:189-190)                                                  */
+  double pose_ex, pose_ey, pose_eth, pose_ed;   /* weighted means (weights w / sum w) of x - rx, y - ry, theta - rtheta with one
+                            +-2 pi correction, hypot(x - rx, y - ry) (analysis2dSim.cpp:265-317); NaN without a gt_pose     */
+  double weight_sum;     /* sum of the block's particle weights (:163)                                                     */
+};
+/* Ground-truth landmarks of filter `filter` (0 on an ordinary handle): xy [n][2], first_seen [n] = the time each landmark first came
+ * into sensor range (third column of the reference's gtLandmark.dat, src/rbphdslam2dSim.cpp:249-284; -1 = never, which counts from
+ * the start as in analysis2dSim.cpp:216) or NULL = all -1.  n <= RFSGPU_MAX_METRIC_SET, else RFSGPU_ERR_INVALID.  Uploaded once
+ * (synchronising); a filter without ground truth is compared with the empty set. */
+int rfsgpu_set_ground_truth(rfsgpu_filter *f, int filter, const double *xy, const double *first_seen, int n);
+/* The device-side log: log_capacity rows of n_filters records.  _create (re)allocates it empty (0 frees it), _reset empties it;
+ * rows stay where they are until then. */
+int rfsgpu_error_log_create(rfsgpu_filter *f, int log_capacity);
+int rfsgpu_error_log_reset(rfsgpu_filter *f);
+/* Appends one row: t [n_filters] the time of each filter's step, gt_pose [n_filters][3] its ground-truth pose (x, y, theta) or
+ * NULL (pose fields NaN); w_threshold, cutoff c > 0 and order p >= 1 as analysis2dSim.cpp:182, :232-233 (0.75, 0.20, 1.0).
+ * Stream-ordered on the handle's stream: t and gt_pose are copied into the pinned staging ring before the call returns, the kernel
+ * reads them there, nothing waits for the GPU.  A full log (or none): RFSGPU_ERR_CAPACITY, nothing is enqueued. */
+int rfsgpu_step_error_async(rfsgpu_filter *f, const double *t, const double *gt_pose, double w_threshold, double cutoff, double order);
+/* Synchronises the stream and copies the rows written so far ([row][filter], at most max_rows of them) to out; *n_rows = the
+ * number of rows in the log.  The log keeps them. */
+int rfsgpu_error_log_read(rfsgpu_filter *f, struct rfsgpu_step_error *out, int max_rows, int *n_rows);
+/* The synchronous form: the same kernel, its row delivered to out [n_filters]; needs no log and leaves the log alone. */
+int rfsgpu_step_error(rfsgpu_filter *f, const double *t, const double *gt_pose, double w_threshold, double cutoff, double order,
+                      struct rfsgpu_step_error *out);
+/* The map estimate of filter `filter`'s highest-weight particle for the host -- the selection of best_slot and n_est above, what the
+ * reference's landmarkEst.dat holds of that particle: up to max_n Gaussians with weight >= w_threshold in mixture order (mean [n][2],
+ * cov [n][4] row-major, w [n]; any may be NULL), *n = their number.  Synchronising. */
+int rfsgpu_get_map_estimate(rfsgpu_filter *f, int filter, double w_threshold, int max_n, int *n, double *mean, double *cov, double *w);
 
 #ifdef __cplusplus
 }

@@ -20,6 +20,7 @@ VP_MAX_PD = 16
 MAX_CANDIDATES = 256
 MAX_Z = 64
 MAX_EVAL = 64
+MAX_METRIC_SET = 512
 
 
 class FilterConfig(C.Structure):
@@ -103,6 +104,17 @@ class Timing(C.Structure):
                 for s in ("_wall", "_cpu")]
 
 
+class StepError(C.Structure):
+    """rfsgpu_step_error: one filter's record of one rfsgpu_step_error[_async] call (every field 8 bytes wide)."""
+    _fields_ = [("t", C.c_double), ("status", C.c_longlong), ("best_slot", C.c_longlong), ("n_est", C.c_longlong), ("n_truth", C.c_longlong),
+                ("cardinality", C.c_double), ("ospa", C.c_double), ("cola", C.c_double), ("e_dist", C.c_double), ("e_card", C.c_double),
+                ("pose_ex", C.c_double), ("pose_ey", C.c_double), ("pose_eth", C.c_double), ("pose_ed", C.c_double), ("weight_sum", C.c_double)]
+
+
+# the same layout as a numpy structured dtype (error_log_read / step_error return arrays of it)
+STEP_ERROR_DTYPE = np.dtype([(n, np.int64 if t is C.c_longlong else np.float64) for n, t in StepError._fields_])
+
+
 # every symbol include/rfsgpu.h declares, without prefix (tests check the product .so exports them all)
 ABI_SYMBOLS = [
     "abi_version", "create", "destroy", "last_error", "default_filter_config", "set_filter_config",
@@ -125,6 +137,7 @@ ABI_SYMBOLS = [
     "group_resample", "group_apply_plan", "group_migration_stats", "group_gm_size", "group_get_landmark", "group_synchronize", "group_set_birth_inheritance", "group_get_particle_ids",
     "group_update_io", "group_update_deferred", "group_set_model_victoriapark", "group_set_laser_scan", "group_set_phase_timing", "group_get_timing", "group_collective",
     "create_batch", "n_filters", "batch_configure", "batch_cycle_async", "batch_weight_sums", "batch_resample_apply", "batch_resample_occured", "murty_seen",
+    "set_ground_truth", "error_log_create", "error_log_reset", "step_error_async", "error_log_read", "step_error", "get_map_estimate",
 ]
 
 _dp = np.ctypeslib.ndpointer(dtype=np.float64, flags="C_CONTIGUOUS")
@@ -572,6 +585,66 @@ class CFilter:
         fn = self._fn("weights_device_ptr")
         fn.restype = C.c_void_p
         return fn(self._h)
+
+    # -- [metric] per-step map error and pose error on the device (rfsgpu_step_error*, csrc/map_metric.h) ------------
+    @property
+    def n_metric_filters(self):
+        """Records per row: the batch's filters, 1 for an ordinary handle."""
+        return int(getattr(self, "n_filters", 1))
+
+    def set_ground_truth(self, xy, first_seen=None, filter=0):
+        """Filter `filter`'s ground-truth landmarks xy [n, 2] and the time each first came into sensor range (None: all -1)."""
+        xy = _f64(xy).reshape(-1, 2)
+        fs = None if first_seen is None else _f64(first_seen, (xy.shape[0],))
+        self._call("set_ground_truth", C.c_int(int(filter)), self._ptr(xy), C.c_void_p(None) if fs is None else self._ptr(fs), C.c_int(xy.shape[0]))
+
+    def error_log_create(self, log_capacity):
+        self._call("error_log_create", C.c_int(int(log_capacity)))
+
+    def error_log_reset(self):
+        self._call("error_log_reset")
+
+    def _metric_inputs(self, t, gt_pose):
+        nF = self.n_metric_filters
+        t = _f64(np.broadcast_to(np.asarray(t, dtype=np.float64), (nF,)))
+        g = None if gt_pose is None else _f64(gt_pose, (nF, 3))
+        return t, g
+
+    def step_error_async(self, t, gt_pose=None, w_threshold=0.75, cutoff=0.20, order=1.0):
+        """Append one row to the device-side log: t [n_filters] (or a scalar), gt_pose [n_filters, 3] or None (pose fields NaN); the
+        defaults are the reference's constants (src/analysis2dSim.cpp:182, :232-233).  Stream-ordered, no host wait."""
+        t, g = self._metric_inputs(t, gt_pose)
+        self._call("step_error_async", self._ptr(t), C.c_void_p(None) if g is None else self._ptr(g), C.c_double(w_threshold), C.c_double(cutoff),
+                   C.c_double(order))
+
+    def error_log_read(self, max_rows=None):
+        """The rows written so far as a structured array [rows, n_filters] (STEP_ERROR_DTYPE).  Synchronises; the log keeps its rows."""
+        nF = self.n_metric_filters
+        n = C.c_int()
+        if max_rows is None:
+            self._call("error_log_read", C.c_void_p(None), C.c_int(0), C.byref(n))
+            max_rows = n.value
+        out = np.zeros((int(max_rows), nF), dtype=STEP_ERROR_DTYPE)
+        self._call("error_log_read", self._ptr(out), C.c_int(int(max_rows)), C.byref(n))
+        return out[: min(n.value, int(max_rows))]
+
+    def step_error(self, t, gt_pose=None, w_threshold=0.75, cutoff=0.20, order=1.0):
+        """The synchronous form: this call's row [n_filters] (STEP_ERROR_DTYPE); needs no log."""
+        t, g = self._metric_inputs(t, gt_pose)
+        out = np.zeros(self.n_metric_filters, dtype=STEP_ERROR_DTYPE)
+        self._call("step_error", self._ptr(t), C.c_void_p(None) if g is None else self._ptr(g), C.c_double(w_threshold), C.c_double(cutoff),
+                   C.c_double(order), self._ptr(out))
+        return out
+
+    def get_map_estimate(self, w_threshold=0.75, filter=0):
+        """(mean [n, 2], cov [n, 2, 2], w [n]) of the Gaussians with weight >= w_threshold of filter `filter`'s highest-weight particle."""
+        n = C.c_int()
+        self._call("get_map_estimate", C.c_int(int(filter)), C.c_double(w_threshold), C.c_int(0), C.byref(n), C.c_void_p(None), C.c_void_p(None), C.c_void_p(None))
+        k = n.value
+        mean, cov, w = np.empty((k, 2)), np.empty((k, 2, 2)), np.empty(k)
+        self._call("get_map_estimate", C.c_int(int(filter)), C.c_double(w_threshold), C.c_int(k), C.byref(n), self._ptr(mean), self._ptr(cov), self._ptr(w))
+        k = min(k, n.value)
+        return mean[:k], cov[:k], w[:k]
 
     # -- timing --------------------------------------------------------------------------------
     def getTimingInfo(self):

@@ -127,6 +127,7 @@ int rfsgpu_group_create(rfsgpu_group **out, int model, int n_particles, const in
     if (rc != RFSGPU_OK) { rfsgpu_group_destroy(g); return rc; }
     if (f->inheritMode == RFSGPU_INHERIT_EAGER) g->inheritMode = RFSGPU_INHERIT_EAGER;   // (RFSGPU_BIRTH_INHERITANCE=eager in the environment)
     else rfsgpu_set_birth_inheritance(f, RFSGPU_INHERIT_EXTERNAL);
+    f->groupShard = true;
     g->shard.push_back(f);
   }
   g->pid.resize(n_particles); g->ppid.resize(n_particles);

@@ -26,6 +26,7 @@
 #include "fastslam.h"
 #include "fastslam_mh.h"
 #include "motion.h"
+#include "map_metric.h"
 
 namespace {
 
@@ -169,6 +170,13 @@ struct rfsgpu_filter {
   unsigned char *hBStage[4] = {nullptr, nullptr, nullptr, nullptr};   // pinned ring of the per-cycle tables
   hipEvent_t evBStage[4] = {};
   int bStageNext = 0;
+  // [metric] per-step map / pose error (map_metric.h): ground truth per filter, the device-side log, one row for the synchronous calls
+  double *dGtXY = nullptr, *dGtSeen = nullptr;   // [nF][RFSGPU_MAX_METRIC_SET][2], [nF][RFSGPU_MAX_METRIC_SET] (allocated by the first rfsgpu_set_ground_truth)
+  int *dGtN = nullptr;                           // [nF]
+  struct rfsgpu_step_error *dErrLog = nullptr;          // [errLogCap][nF]
+  int errLogCap = 0, errLogRows = 0;
+  struct rfsgpu_step_error *dErrRow = nullptr;          // [nF]
+  bool groupShard = false;                       // a shard of an rfsgpu_group: the [metric] calls refuse
 };
 
 #define HIPCHK(call)                                                                       \
@@ -417,6 +425,7 @@ void rfsgpu_destroy(rfsgpu_filter *f) {
   murty_free(f->Q, f->MS);
   hipFree(f->dBFilt); hipFree(f->dBParams); hipFree(f->dBZ); hipFree(f->dBZPrev); hipFree(f->dBSums); hipFree(f->dBErrFilter); hipFree(f->dBMaskTmp); hipFree(f->dBInhSrc);
   for (int k = 0; k < 4; k++) { if (f->hBStage[k]) hipHostFree(f->hBStage[k]); if (f->evBStage[k]) hipEventDestroy(f->evBStage[k]); }
+  hipFree(f->dGtXY); hipFree(f->dGtSeen); hipFree(f->dGtN); hipFree(f->dErrLog); hipFree(f->dErrRow);
   if (f->hErr) hipHostFree(f->hErr);
   if (f->hJobCount) hipHostFree(f->hJobCount);
   if (f->hSums) hipHostFree(f->hSums);
@@ -2872,6 +2881,158 @@ int rfsgpu_murty_seen(rfsgpu_filter *f) {
 int rfsgpu_batch_resample_occured(const rfsgpu_filter *f, unsigned char *out) {
   if (!f || !f->batch || !out) return RFSGPU_ERR_INVALID;
   for (int b = 0; b < f->nF; b++) out[b] = f->bResampled[b] ? 1 : 0;
+  return RFSGPU_OK;
+}
+
+// ---- [metric] per-step map error and pose error (map_metric.h) ------------------------------------------------------------------------
+static int metric_check(rfsgpu_filter *f, const char *what) {
+  const char *why = f->D != 2 ? "the Victoria Park model" : (f->fastSlamHandle ? "a FastSLAM handle" : (f->groupShard ? "a shard of an rfsgpu_group" : nullptr));
+  if (!why) return RFSGPU_OK;
+  f->err = std::string(what) + ": the device-side map / pose error serves ordinary 2-D RB-PHD handles and filter batches only, not " + why;
+  return RFSGPU_ERR_UNSUPPORTED;
+}
+static inline int metric_nf(const rfsgpu_filter *f) { return f->batch ? f->nF : 1; }
+// One launch into `row` ([nF] records): the call's t / gt_pose go into a slot of the pinned staging ring, which the kernel reads in place.
+static int metric_launch(rfsgpu_filter *f, const double *t, const double *gt_pose, double w_threshold, double cutoff, double order, struct rfsgpu_step_error *row) {
+  const int nF = metric_nf(f);
+  hipSetDevice(f->device);
+  double *h = nullptr;
+  int k = 0;
+  { const int rc = stage_slot(f, &h, &k); if (rc != RFSGPU_OK) return rc; }
+  for (int b = 0; b < nF; b++) {
+    h[4 * b] = t ? t[b] : 0.0;
+    for (int q = 0; q < 3; q++) h[4 * b + 1 + q] = gt_pose ? gt_pose[3 * b + q] : 0.0;
+  }
+  MetricArg A{h, f->dGtXY, f->dGtSeen, f->dGtN, row, w_threshold, cutoff, order, f->batch ? f->nPer : f->N, gt_pose ? 1 : 0, f->holes ? 1 : 0};
+  map_metric_kernel<<<nF, 64, 0, f->stream>>>(f->B, f->cur, A);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipEventRecord(f->evStage[k], f->stream));
+  return RFSGPU_OK;
+}
+static int metric_args(rfsgpu_filter *f, const char *what, const double *t, double cutoff, double order) {
+  if (!t) { f->err = std::string(what) + ": null time array"; return RFSGPU_ERR_INVALID; }
+  if (!(cutoff > 0) || !(order >= 1)) { f->err = std::string(what) + ": cutoff must be > 0 and order >= 1"; return RFSGPU_ERR_INVALID; }
+  return RFSGPU_OK;
+}
+static int metric_row(rfsgpu_filter *f) {
+  if (!f->dErrRow) HIPCHK(hipMalloc(&f->dErrRow, (size_t)metric_nf(f) * sizeof(struct rfsgpu_step_error)));
+  return RFSGPU_OK;
+}
+
+int rfsgpu_set_ground_truth(rfsgpu_filter *f, int filter, const double *xy, const double *first_seen, int n) {
+  CHECK_HANDLE(f);
+  int rc = metric_check(f, "set_ground_truth");
+  if (rc != RFSGPU_OK) return rc;
+  const int nF = metric_nf(f);
+  if (filter < 0 || filter >= nF) return fail(f, RFSGPU_ERR_INVALID, "set_ground_truth: filter index out of range");
+  if (n < 0 || (n > 0 && !xy)) return fail(f, RFSGPU_ERR_INVALID, "set_ground_truth: bad arguments");
+  if (n > RFSGPU_MAX_METRIC_SET) return fail(f, RFSGPU_ERR_INVALID, "set_ground_truth: more than RFSGPU_MAX_METRIC_SET (512) landmarks");
+  hipSetDevice(f->device);
+  if (!f->dGtN) {
+    HIPCHK(hipMalloc(&f->dGtXY, (size_t)nF * RFSGPU_MAX_METRIC_SET * 2 * sizeof(double)));
+    HIPCHK(hipMalloc(&f->dGtSeen, (size_t)nF * RFSGPU_MAX_METRIC_SET * sizeof(double)));
+    int *cnt = nullptr;
+    HIPCHK(hipMalloc(&cnt, (size_t)nF * sizeof(int)));
+    if (hipMemset(cnt, 0, (size_t)nF * sizeof(int)) != hipSuccess) { hipFree(cnt); return fail(f, RFSGPU_ERR_HIP, "set_ground_truth: hipMemset failed"); }
+    f->dGtN = cnt;
+  }
+  HIPCHK(hipStreamSynchronize(f->stream));   // (an enqueued metric kernel may still be reading the old set)
+  std::vector<double> seen((size_t)std::max(n, 1), -1.0);
+  if (first_seen) for (int m = 0; m < n; m++) seen[m] = first_seen[m];
+  if (n > 0) {
+    HIPCHK(hipMemcpy(f->dGtXY + (size_t)filter * RFSGPU_MAX_METRIC_SET * 2, xy, (size_t)n * 2 * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(f->dGtSeen + (size_t)filter * RFSGPU_MAX_METRIC_SET, seen.data(), (size_t)n * sizeof(double), hipMemcpyHostToDevice));
+  }
+  HIPCHK(hipMemcpy(f->dGtN + filter, &n, sizeof(int), hipMemcpyHostToDevice));
+  return RFSGPU_OK;
+}
+int rfsgpu_error_log_create(rfsgpu_filter *f, int log_capacity) {
+  CHECK_HANDLE(f);
+  int rc = metric_check(f, "error_log_create");
+  if (rc != RFSGPU_OK) return rc;
+  if (log_capacity < 0) return fail(f, RFSGPU_ERR_INVALID, "error_log_create: negative capacity");
+  hipSetDevice(f->device);
+  HIPCHK(hipStreamSynchronize(f->stream));
+  hipFree(f->dErrLog);
+  f->dErrLog = nullptr;
+  f->errLogCap = f->errLogRows = 0;
+  if (log_capacity > 0) {
+    HIPCHK(hipMalloc(&f->dErrLog, (size_t)log_capacity * metric_nf(f) * sizeof(struct rfsgpu_step_error)));
+    f->errLogCap = log_capacity;
+  }
+  return RFSGPU_OK;
+}
+int rfsgpu_error_log_reset(rfsgpu_filter *f) {
+  CHECK_HANDLE(f);
+  int rc = metric_check(f, "error_log_reset");
+  if (rc != RFSGPU_OK) return rc;
+  f->errLogRows = 0;   // (stream order keeps a row that is still being written ahead of the next one that lands there)
+  return RFSGPU_OK;
+}
+int rfsgpu_step_error_async(rfsgpu_filter *f, const double *t, const double *gt_pose, double w_threshold, double cutoff, double order) {
+  CHECK_HANDLE(f);
+  int rc = metric_check(f, "step_error_async");
+  if (rc != RFSGPU_OK) return rc;
+  if ((rc = metric_args(f, "step_error_async", t, cutoff, order)) != RFSGPU_OK) return rc;
+  if (f->errLogRows >= f->errLogCap)
+    return fail(f, RFSGPU_ERR_CAPACITY, f->errLogCap ? "step_error_async: the error log is full (rfsgpu_error_log_read, then rfsgpu_error_log_reset)"
+                                                      : "step_error_async: no error log (rfsgpu_error_log_create)");
+  rc = metric_launch(f, t, gt_pose, w_threshold, cutoff, order, f->dErrLog + (size_t)f->errLogRows * metric_nf(f));
+  if (rc == RFSGPU_OK) f->errLogRows++;
+  return rc;
+}
+int rfsgpu_error_log_read(rfsgpu_filter *f, struct rfsgpu_step_error *out, int max_rows, int *n_rows) {
+  CHECK_HANDLE(f);
+  int rc = metric_check(f, "error_log_read");
+  if (rc != RFSGPU_OK) return rc;
+  if (max_rows < 0 || (max_rows > 0 && !out)) return fail(f, RFSGPU_ERR_INVALID, "error_log_read: bad arguments");
+  hipSetDevice(f->device);
+  const int rows = std::min(max_rows, f->errLogRows);
+  if (rows > 0) HIPCHK(hipMemcpyAsync(out, f->dErrLog, (size_t)rows * metric_nf(f) * sizeof(struct rfsgpu_step_error), hipMemcpyDeviceToHost, f->stream));
+  HIPCHK(hipStreamSynchronize(f->stream));
+  if (n_rows) *n_rows = f->errLogRows;
+  return RFSGPU_OK;
+}
+int rfsgpu_step_error(rfsgpu_filter *f, const double *t, const double *gt_pose, double w_threshold, double cutoff, double order, struct rfsgpu_step_error *out) {
+  CHECK_HANDLE(f);
+  int rc = metric_check(f, "step_error");
+  if (rc != RFSGPU_OK) return rc;
+  if ((rc = metric_args(f, "step_error", t, cutoff, order)) != RFSGPU_OK) return rc;
+  if (!out) return fail(f, RFSGPU_ERR_INVALID, "step_error: null output");
+  hipSetDevice(f->device);
+  if ((rc = metric_row(f)) != RFSGPU_OK) return rc;
+  if ((rc = metric_launch(f, t, gt_pose, w_threshold, cutoff, order, f->dErrRow)) != RFSGPU_OK) return rc;
+  HIPCHK(hipMemcpyAsync(out, f->dErrRow, (size_t)metric_nf(f) * sizeof(struct rfsgpu_step_error), hipMemcpyDeviceToHost, f->stream));
+  HIPCHK(hipStreamSynchronize(f->stream));
+  return RFSGPU_OK;
+}
+int rfsgpu_get_map_estimate(rfsgpu_filter *f, int filter, double w_threshold, int max_n, int *n, double *mean, double *cov, double *w) {
+  CHECK_HANDLE(f);
+  int rc = metric_check(f, "get_map_estimate");
+  if (rc != RFSGPU_OK) return rc;
+  const int nF = metric_nf(f);
+  if (filter < 0 || filter >= nF || max_n < 0) return fail(f, RFSGPU_ERR_INVALID, "get_map_estimate: bad arguments");
+  // the selection is the kernel's own (one rule, one implementation): a launch with no pose and the metric's cheapest arguments
+  std::vector<struct rfsgpu_step_error> row(nF);
+  std::vector<double> t(nF, 0.0);
+  if ((rc = rfsgpu_step_error(f, t.data(), nullptr, w_threshold, 1.0, 1.0, row.data())) != RFSGPU_OK) return rc;
+  const int slot = (int)row[filter].best_slot;
+  std::vector<double> pl;
+  int cnt = 0;
+  if ((rc = fetch_particle(f, slot, pl, cnt)) != RFSGPU_OK) return rc;
+  const size_t c = f->cap;
+  int k = 0;
+  for (int m = 0; m < cnt; m++) {
+    const double wm = pl[m];
+    if ((f->holes && wm < 0) || !(wm >= w_threshold)) continue;
+    if (k < max_n) {
+      if (w) w[k] = wm;
+      if (mean) { mean[2 * k] = pl[(size_t)PL_MX * c + m]; mean[2 * k + 1] = pl[(size_t)PL_MY * c + m]; }
+      if (cov) { cov[4 * k] = pl[(size_t)PL_SXX * c + m]; cov[4 * k + 1] = cov[4 * k + 2] = pl[(size_t)PL_SXY * c + m]; cov[4 * k + 3] = pl[(size_t)PL_SYY * c + m]; }
+    }
+    k++;
+  }
+  if (n) *n = k;
   return RFSGPU_OK;
 }
 

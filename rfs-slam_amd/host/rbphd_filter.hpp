@@ -224,6 +224,21 @@ class RBPHDFilter2d {
   }
   rfsgpu_filter *handle() { return h_; }
 
+  // What the reference's analysis2dSim computes for one time step (src/analysis2dSim.cpp:150-249), on the device: the weighted-mean pose
+  // error of the particle set and the OSPA / COLA error of the highest-weight particle's map (Gaussians with weight >= wThreshold)
+  // against the ground-truth landmarks with firstSeen <= t.  A thin wrapper over rfsgpu_step_error; the ground truth is uploaded once.
+  // One-GPU filters only (a filter sharded over several devices throws).
+  void setGroundTruth(const double *xy, const double *firstSeen, int n) {
+    if (g_) throw std::runtime_error("setGroundTruth: not available on a filter sharded over several devices");
+    check(rfsgpu_set_ground_truth(h_, 0, xy, firstSeen, n), "set_ground_truth");
+  }
+  struct rfsgpu_step_error stepError(double t, const double gtPose[3], double wThreshold = 0.75, double cutoff = 0.20, double order = 1.0) {
+    if (g_) throw std::runtime_error("stepError: not available on a filter sharded over several devices");
+    struct rfsgpu_step_error e;
+    check(::rfsgpu_step_error(h_, &t, gtPose, wThreshold, cutoff, order, &e), "step_error");
+    return e;
+  }
+
  protected:
   rfsgpu_filter *h_ = nullptr;
   rfsgpu_group *g_ = nullptr;   // set: the particle set is sharded over several devices

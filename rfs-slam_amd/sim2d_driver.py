@@ -99,6 +99,25 @@ def generate(P=C1_SIM, traj_seed=1, kmax=None):
     return dict(gt=gt, odom=odom, landmarks=lm, Z=Z, K=K)
 
 
+def first_seen_times(data, P=C1_SIM):
+    """Per ground-truth landmark the time k * dt of the first step k >= 1 whose TRUE range from gt[k] lies in [rmin, rmax], -1 if
+    there is none: the third column of the reference's gtLandmark.dat (lmkFirstObsTime_, src/rbphdslam2dSim.cpp:308-339, :404).
+    Reads `data` only: no random draw, nothing of generate() changes."""
+    gt, lm = data["gt"], data["landmarks"]
+    out = np.full(len(lm), -1.0)
+    if len(lm) == 0:
+        return out
+    r = np.hypot(lm[None, :, 0] - gt[1:, None, 0], lm[None, :, 1] - gt[1:, None, 1])     # [K - 1, L]
+    ok = (r >= P["rmin"]) & (r <= P["rmax"])
+    seen = ok.any(axis=0)
+    out[seen] = (np.argmax(ok, axis=0)[seen] + 1) * P["dt"]
+    return out
+
+
+# the reference's evaluation constants (src/analysis2dSim.cpp:182, :232-233): estimate weight threshold, COLA cutoff and order
+ERROR_W_THRESHOLD, ERROR_CUTOFF, ERROR_ORDER = 0.75, 0.20, 1.0
+
+
 def configure(f, P=C1_SIM):
     """setupRBPHDFilter (:444-492) through the C ABI."""
     dt = P["dt"]
@@ -123,7 +142,10 @@ def configure(f, P=C1_SIM):
 class Sim2dRun:
     """run() :540-643 over `filters` (all driven through the same realisation); `on_step(k, run)` is called after every update."""
 
-    def __init__(self, filters, data, P=C1_SIM, seed=1, eff_n=None):
+    def __init__(self, filters, data, P=C1_SIM, seed=1, eff_n=None, track_errors=False):
+        """track_errors: every filter gets the realisation's ground truth and a device-side error log; each cycle ends with one
+        stream-ordered step_error_async (after the resampling, where the reference driver logs its particle set); errors() reads
+        the logs once.  Off (the default) nothing is enqueued."""
         self.filters = list(filters)
         self.n = self.filters[0].n
         assert all(f.n == self.n for f in self.filters)
@@ -140,11 +162,29 @@ class Sim2dRun:
         self.n_updates = 0
         self.resample_steps = []
         self.z_of_step = None
+        self.track_errors = bool(track_errors)
+        if self.track_errors:
+            fs = first_seen_times(data, P)
+            for f in self.filters:
+                f.set_ground_truth(data["landmarks"], fs)
+                f.error_log_create(int(data["K"]))
 
     def _each(self, fn):
         return [fn(f) for f in self.filters]
 
     def step(self, k):
+        fired = self._step(k)
+        if self.track_errors:
+            t, g = k * self.P["dt"], self.data["gt"][k][None, :]
+            self._each(lambda f: f.step_error_async(t, g, ERROR_W_THRESHOLD, ERROR_CUTOFF, ERROR_ORDER))
+        return fired
+
+    def errors(self):
+        """One structured array [steps] (capi.STEP_ERROR_DTYPE) per filter: the rows logged so far (one read each)."""
+        assert self.track_errors, "Sim2dRun(..., track_errors=True)"
+        return [f.error_log_read()[:, 0] for f in self.filters]
+
+    def _step(self, k):
         P, d = self.P, self.data
         # predict (:588): births at the poses the last update used, then the static landmark step; host propagation
         self._each(lambda f: (f.set_poses(self.x, self.cov), f.predict_map(True)))
@@ -227,7 +267,9 @@ class Sim2dBatchRun:
     Sim2dRun, every cycle counts as an update for the gate (empty ones included), a filter draws its process noise every step and its
     resampling draw only when its N_eff test fires: a one-filter run takes the draws Sim2dRun takes with the same seed."""
 
-    def __init__(self, target, datas, Ps, seeds):
+    def __init__(self, target, datas, Ps, seeds, track_errors=False):
+        """track_errors: as in Sim2dRun -- each filter's ground truth is uploaded, every cycle ends with one step_error_async (one
+        launch for the whole batch; one per handle otherwise), errors() reads the log(s) once at the end."""
         self.batch = target if isinstance(target, capi.CBatch) else None
         self.handles = None if self.batch is not None else list(target)
         self.nF = len(datas)
@@ -252,8 +294,39 @@ class Sim2dBatchRun:
         self.last_plans = [np.arange(self.n) for _ in range(self.nF)]
         self.n_resamples = np.zeros(self.nF, dtype=np.int64)
         self.resample_steps = [[] for _ in range(self.nF)]    # the steps k at which each filter resampled
+        self.track_errors = bool(track_errors)
+        if self.track_errors:
+            rows = int(min(d["K"] for d in self.datas))
+            for b, (d, P) in enumerate(zip(self.datas, self.Ps)):
+                fs = first_seen_times(d, P)
+                if self.batch is not None:
+                    self.batch.set_ground_truth(d["landmarks"], fs, filter=b)
+                else:
+                    self.handles[b].set_ground_truth(d["landmarks"], fs)
+                    self.handles[b].error_log_create(rows)
+            if self.batch is not None:
+                self.batch.error_log_create(rows)
 
     def step(self, k):
+        fired = self._step(k)
+        if self.track_errors:
+            t = np.array([k * P["dt"] for P in self.Ps])
+            g = np.array([d["gt"][k] for d in self.datas])
+            if self.batch is not None:
+                self.batch.step_error_async(t, g, ERROR_W_THRESHOLD, ERROR_CUTOFF, ERROR_ORDER)
+            else:
+                for b, f in enumerate(self.handles):
+                    f.step_error_async(t[b], g[b][None, :], ERROR_W_THRESHOLD, ERROR_CUTOFF, ERROR_ORDER)
+        return fired
+
+    def errors(self):
+        """The rows logged so far as one structured array [steps, n_filters] (capi.STEP_ERROR_DTYPE): one read (per handle)."""
+        assert self.track_errors, "Sim2dBatchRun(..., track_errors=True)"
+        if self.batch is not None:
+            return self.batch.error_log_read()
+        return np.stack([f.error_log_read()[:, 0] for f in self.handles], axis=1)
+
+    def _step(self, k):
         Zs = []
         for b in range(self.nF):
             d = self.datas[b]

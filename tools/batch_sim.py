@@ -6,6 +6,11 @@ Prints filter-steps/s for batch sizes 1, 4, 16 and 64 at 200 particles (both for
 then each run's final map error.  A tuning / evaluation tool, not part of bench.py.
 
     python tools/batch_sim.py [--steps 200] [--sizes 1,4,16,64] [--particles 200] [--handles-max 64]
+
+--errors: the sweep with the device-side error tracking on (Sim2dBatchRun(track_errors=True): one rfsgpu_step_error_async per cycle, one
+log read at the end).  Per filter the final and mean COLA and pose error with the reference's constants (0.75, 0.20, 1.0: src/analysis2dSim.cpp),
+the curves in --json, and for every batch size three throughput figures from the one invocation: filter-steps/s (a) with tracking off, (b) with
+device tracking, (c) with the host route (per step and filter get_weights + export_gm of the best particle + tools/analysis2d_sim.py::cola).
 """
 import argparse
 import json
@@ -46,6 +51,65 @@ def timed(run, steps):
     return time.perf_counter() - t0
 
 
+def host_route_errors(batch, datas, firsts, Ps, k, a2d):
+    """What a caller had to do per step before the device metric: per filter the weights, the best particle's mixture, scipy."""
+    out = []
+    for b in range(batch.n_filters):
+        w = batch.get_weights()[batch.block(b)]
+        i = b * batch.n_per_filter + int(np.argmax(w))
+        gw, _, mean, _ = batch.export_gm(i)
+        seen = datas[b]["landmarks"][firsts[b] <= k * Ps[b]["dt"]]
+        out.append(a2d.cola(mean[gw >= a2d.W_THRESHOLD], seen))
+    return out
+
+
+def timed_host_route(run, steps, datas, firsts, Ps, a2d):
+    run.step(1)
+    t0 = time.perf_counter()
+    for k in range(2, steps + 2):
+        run.step(k)
+        host_route_errors(run.batch, datas, firsts, Ps, k, a2d)
+    return time.perf_counter() - t0
+
+
+def errors_sweep(pkg, a, sizes, Ps, datas, seeds):
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("analysis2d_sim", os.path.join(ROOT, "tools", "analysis2d_sim.py"))
+    a2d = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(a2d)
+    sim = pkg.sim2d_driver
+    firsts = [sim.first_seen_times(d, P) for d, P in zip(datas, Ps)]
+    rows = []
+    for B in sizes:
+        row = dict(B=B, particles=a.particles, steps=a.steps)
+        for name in ("off", "device", "host"):
+            batch = pkg.FilterBatch(B, a.particles, gm_capacity=a.capacity)
+            run = sim.Sim2dBatchRun(batch, datas[:B], Ps[:B], seeds[:B], track_errors=(name == "device"))
+            dt = timed_host_route(run, a.steps, datas, firsts, Ps, a2d) if name == "host" else timed(run, a.steps)
+            if name == "device":
+                t0 = time.perf_counter()
+                log = run.errors()                      # the one read (it also waits for the queued work)
+                dt += time.perf_counter() - t0
+            else:
+                batch.synchronize()
+            row["filter_steps_per_s_tracking_" + name] = B * a.steps / dt
+            if name == "device":
+                row["filters"] = [dict(filter=b, Pd=Ps[b]["Pd"], clutter=Ps[b]["clutter"], seed=1 + b, final_cola=float(log["cola"][-1, b]),
+                                       mean_cola=float(log["cola"][:, b].mean()), final_pose_error=float(log["pose_ed"][-1, b]),
+                                       mean_pose_error=float(log["pose_ed"][:, b].mean()), n_est=int(log["n_est"][-1, b]), n_truth=int(log["n_truth"][-1, b]),
+                                       curve_t=log["t"][:, b].tolist(), curve_cola=log["cola"][:, b].tolist(), curve_pose_error=log["pose_ed"][:, b].tolist())
+                                  for b in range(B)]
+            batch.close()
+        row["device_over_off"] = row["filter_steps_per_s_tracking_device"] / row["filter_steps_per_s_tracking_off"]
+        row["host_over_off"] = row["filter_steps_per_s_tracking_host"] / row["filter_steps_per_s_tracking_off"]
+        rows.append(row)
+        print(json.dumps({k: v for k, v in row.items() if k != "filters"}), flush=True)
+    for r in rows[-1]["filters"]:
+        print("filter %3d  Pd %.2f  clutter %.0e  seed %3d  COLA final %6.2f mean %6.2f (est %2d / truth %2d)  pose error final %.4f mean %.4f"
+              % (r["filter"], r["Pd"], r["clutter"], r["seed"], r["final_cola"], r["mean_cola"], r["n_est"], r["n_truth"], r["final_pose_error"], r["mean_pose_error"]))
+    return rows
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=200)
@@ -54,6 +118,7 @@ def main():
     ap.add_argument("--handles-max", type=int, default=64, help="largest batch size also run as independent handles")
     ap.add_argument("--capacity", type=int, default=256)
     ap.add_argument("--json", default="")
+    ap.add_argument("--errors", action="store_true", help="track COLA / pose error on the device; tracking off / device / host route timed side by side")
     a = ap.parse_args()
     pkg = load_pkg()
     sim = pkg.sim2d_driver
@@ -61,6 +126,8 @@ def main():
     kmax = a.steps + 2
     Ps, datas, seeds = grid(sim, max(sizes), kmax)
     rows = []
+    if a.errors:
+        erows = errors_sweep(pkg, a, sizes, Ps, datas, seeds)
     for B in sizes:
         batch = pkg.FilterBatch(B, a.particles, gm_capacity=a.capacity)
         rb = sim.Sim2dBatchRun(batch, datas[:B], Ps[:B], seeds[:B])
@@ -95,7 +162,7 @@ def main():
     if a.json:
         os.makedirs(os.path.dirname(a.json) or ".", exist_ok=True)
         with open(a.json, "w") as fh:
-            json.dump(rows, fh, indent=1)
+            json.dump(dict(sweep=rows, errors=erows) if a.errors else rows, fh, indent=1)
 
 
 if __name__ == "__main__":
