@@ -663,6 +663,49 @@ int rfsgpu_batch_weight_sums(rfsgpu_filter *f, double *out);
 int rfsgpu_batch_resample_apply(rfsgpu_filter *f, const int *src_slot, const unsigned char *resampled);
 /* resampleOccured_ of each filter: out [n_filters]. */
 int rfsgpu_batch_resample_occured(const rfsgpu_filter *f, unsigned char *out);
+/* -- the device loop: ParticleFilter::propagate and the resampling tail of RBPHDFilter::update for every filter of a batch, as
+ * stream-ordered launches.  With them a batch run is propagate -> cycle(x = NULL) -> resample per step and the host waits for nothing.
+ * Random numbers: Philox4x32-10 under the filter's 64-bit key (low word k0, high word k1) with counter
+ * (slot within the filter, block, call low word, call high word): a filter's draws do not depend on its place in the batch.
+ *
+ * Process noise of filter `filter` (-1: every filter): additive N(0, diag(var)) on (x, y, theta) after MotionModel_Odometry2d::step;
+ * seed is the filter's Philox key (propagation and resampling draws). */
+int rfsgpu_batch_set_motion_odometry(rfsgpu_filter *f, int filter, const double var[3], unsigned long long seed);
+/* The two thresholds of ParticleFilter::resample of filter `filter` (-1: every filter): it does NOT resample when
+ * N_eff > eff_n && N_eff / n_per_filter > eff_n_percent.  The minimum-update / minimum-measurement gates are those of the filter's
+ * rfsgpu_filter_config. */
+int rfsgpu_batch_set_resampling(rfsgpu_filter *f, int filter, double eff_n, double eff_n_percent);
+/* u [n_filters][3] the odometry inputs; pin [n_filters] (or NULL: none), pin_pose [n_filters][3] (may be NULL when nothing is pinned).
+ * Particle i of filter b becomes step(pose, u[b]) + sqrt(var_b) * g with g three standard normal deviates by Box-Muller
+ * (rad = sqrt(-2 ln u1), ang = 2 pi u2, u in (0, 1] from 53 bits of two words each): block 0 gives g_x = rad cos ang and
+ * g_y = rad sin ang, block 1's rad cos ang gives g_theta.  Its pose covariance becomes diag(var_b) (the handle goes to one pose
+ * covariance per particle).  Where pin[b] != 0 every particle of filter b takes pin_pose[b] with a zero covariance.  The inputs are
+ * copied into a pinned ring before the call returns; nothing waits for the GPU.  rfsgpu_get_poses returns the new poses; the births
+ * of the next rfsgpu_batch_cycle_async still happen at the poses from before the call (RBPHDFilter::predict), whether that cycle
+ * passes x or NULL; rfsgpu_set_poses in between ends that: the births then happen at the poses it set, as without a propagation.  A filter without rfsgpu_batch_set_motion_odometry: RFSGPU_ERR_INVALID, naming it. */
+int rfsgpu_batch_propagate_async(rfsgpu_filter *f, const double *u, const double *pin_pose, const unsigned char *pin, unsigned long long call);
+/* The tail of RBPHDFilter::update with ParticleFilter::resample for every filter, after a cycle with normalize != 0: n_z [n_filters]
+ * that cycle's measurement counts.  Every call counts as an update; a filter with n_z == 0 or under either gate stops there.
+ * N_eff = 1 / sum w^2 (summed in slot order); a filter that does not pass the test above is resampled by the reference's systematic
+ * plan with the draw u = (53 bits of block (0, 2, call)) / 2^53 in [0, 1): its mixtures, poses and pose covariances are gathered,
+ * its weights become 1, its resampleOccured_ is set, its counters go to 0.  The weights must be non-negative (normalised).
+ * Stream-ordered, nothing waits.  One workgroup resamples a filter: n_per_filter <= RFSGPU_BATCH_RESAMPLE_MAX_PER_FILTER, beyond
+ * it RFSGPU_ERR_UNSUPPORTED.  A filter without rfsgpu_batch_set_resampling or _set_motion_odometry: RFSGPU_ERR_INVALID, naming it.
+ * From the first call on, the particle ids, resampleOccured_ and the counters of this handle live on the device:
+ * rfsgpu_get_particle_ids / _set_particle_ids and rfsgpu_batch_resample_occured read / write them there (synchronising), the next
+ * predict's inheritance of the unused-measurement lists is computed there, and rfsgpu_batch_resample_apply (the host route) is
+ * refused with RFSGPU_ERR_UNSUPPORTED: the two routes do not mix on one handle.  Host route first, device route later is allowed
+ * (the host's ids and flags move to the device). */
+#define RFSGPU_BATCH_RESAMPLE_MAX_PER_FILTER 2048
+int rfsgpu_batch_resample_async(rfsgpu_filter *f, const int *n_z, unsigned long long call);
+/* The last rfsgpu_batch_resample_async: fired [n_filters], src_slot [N] its plan in global slots (identity where not fired),
+ * n_eff [n_filters] (0 where a filter stopped before the N_eff test); any may be NULL.  Synchronising. */
+int rfsgpu_batch_last_resample(rfsgpu_filter *f, unsigned char *fired, int *src_slot, double *n_eff);
+/* The pose covariance of every slot as the next update will read it: out [N][9], row-major (a handle with one shared covariance
+ * returns it N times).  Synchronising; for tests and drivers that want to see what rfsgpu_batch_propagate_async left. */
+int rfsgpu_batch_get_pose_covs(rfsgpu_filter *f, double *out);
+/* Resamplings of each filter by rfsgpu_batch_resample_async so far: out [n_filters].  Synchronising. */
+int rfsgpu_batch_resample_counts(rfsgpu_filter *f, long long *out);
 #ifdef RFSGPU_ENABLE_BENCH_API
 /* [test] 1 once a step of this handle (batch or not) has queued Murty-200 partitions, else 0.  Synchronising. */
 int rfsgpu_murty_seen(rfsgpu_filter *f);

@@ -137,6 +137,7 @@ ABI_SYMBOLS = [
     "group_resample", "group_apply_plan", "group_migration_stats", "group_gm_size", "group_get_landmark", "group_synchronize", "group_set_birth_inheritance", "group_get_particle_ids",
     "group_update_io", "group_update_deferred", "group_set_model_victoriapark", "group_set_laser_scan", "group_set_phase_timing", "group_get_timing", "group_collective",
     "create_batch", "n_filters", "batch_configure", "batch_cycle_async", "batch_weight_sums", "batch_resample_apply", "batch_resample_occured", "murty_seen",
+    "batch_set_motion_odometry", "batch_set_resampling", "batch_propagate_async", "batch_resample_async", "batch_last_resample", "batch_resample_counts", "batch_get_pose_covs",
     "set_ground_truth", "error_log_create", "error_log_reset", "step_error_async", "error_log_read", "step_error", "get_map_estimate",
 ]
 
@@ -720,6 +721,13 @@ class CBatch(CFilter):
         self._call("batch_cycle_async", C.c_int(-1 if predict is None else (1 if predict else 0)), C.c_void_p(None) if x is None else self._ptr(x),
                    C.c_void_p(None) if cv is None else self._ptr(cv), C.c_int(stride), self._ptr(z), self._ptr(nz), C.c_int(1 if normalize else 0))
 
+    def batch_cycle_async_packed(self, predict, z, nz, normalize=True):
+        """rfsgpu_batch_cycle_async with the sets already in the call's layout (z [n_filters, MAX_Z, 2] float64, nz [n_filters] int32,
+        both C-contiguous) and no new poses: what a loop that packs its measurement sets once issues per step."""
+        assert z.dtype == np.float64 and nz.dtype == np.int32 and z.shape == (self.n_filters, MAX_Z, 2) and z.flags.c_contiguous and nz.flags.c_contiguous
+        self._call("batch_cycle_async", C.c_int(-1 if predict is None else (1 if predict else 0)), C.c_void_p(None), C.c_void_p(None), C.c_int(0),
+                   self._ptr(z), self._ptr(nz), C.c_int(1 if normalize else 0))
+
     def batch_weight_sums(self):
         out = np.empty((self.n_filters, 2))
         self._call("batch_weight_sums", self._ptr(out))
@@ -737,6 +745,49 @@ class CBatch(CFilter):
         fn.restype = C.c_int
         fn(self._h, self._ptr(out))
         return out.astype(bool)
+
+    # -- the device loop ([batch] in include/rfsgpu.h: propagation and resampling without the host) ---------------------------
+    def set_motion_odometry(self, b, var, seed):
+        """rfsgpu_batch_set_motion_odometry: filter b's (None: every filter's) process noise N(0, diag(var)) and Philox key."""
+        v = _f64(var, (3,))
+        self._call("batch_set_motion_odometry", C.c_int(-1 if b is None else int(b)), self._ptr(v), C.c_ulonglong(int(seed) & 0xFFFFFFFFFFFFFFFF))
+
+    def set_resampling(self, b, eff_n, eff_n_percent):
+        """rfsgpu_batch_set_resampling: ParticleFilter::resample's two thresholds for filter b (None: every filter)."""
+        self._call("batch_set_resampling", C.c_int(-1 if b is None else int(b)), C.c_double(float(eff_n)), C.c_double(float(eff_n_percent)))
+
+    def propagate_async(self, u, call, pin=None, pin_pose=None):
+        """rfsgpu_batch_propagate_async: u [n_filters, 3]; pin [n_filters] bool and pin_pose [n_filters, 3], or None."""
+        u = _f64(u, (self.n_filters, 3))
+        pn = None if pin is None else np.ascontiguousarray(pin, dtype=np.uint8).reshape(self.n_filters)
+        pp = None if pin_pose is None else _f64(pin_pose, (self.n_filters, 3))
+        self._call("batch_propagate_async", self._ptr(u), C.c_void_p(None) if pp is None else self._ptr(pp),
+                   C.c_void_p(None) if pn is None else self._ptr(pn), C.c_ulonglong(int(call)))
+
+    def resample_async(self, n_z, call):
+        """rfsgpu_batch_resample_async: n_z [n_filters] the cycle's measurement counts."""
+        nz = np.ascontiguousarray(n_z, dtype=np.int32).reshape(self.n_filters)
+        self._call("batch_resample_async", self._ptr(nz), C.c_ulonglong(int(call)))
+
+    def last_resample(self):
+        """(fired [n_filters] bool, plan [N] global source slots, n_eff [n_filters]) of the last resample_async (synchronising)."""
+        fired = np.zeros(self.n_filters, dtype=np.uint8)
+        plan = np.zeros(self.n, dtype=np.int32)
+        neff = np.zeros(self.n_filters)
+        self._call("batch_last_resample", self._ptr(fired), self._ptr(plan), self._ptr(neff))
+        return fired.astype(bool), plan, neff
+
+    def get_pose_covs(self):
+        """Every slot's pose covariance [N, 3, 3] as the next update reads it (synchronising)."""
+        out = np.zeros((self.n, 9))
+        self._call("batch_get_pose_covs", self._ptr(out))
+        return out.reshape(self.n, 3, 3)
+
+    def resample_counts(self):
+        """Resamplings per filter by resample_async so far (synchronising)."""
+        out = np.zeros(self.n_filters, dtype=np.int64)
+        self._call("batch_resample_counts", self._ptr(out))
+        return out
 
     def n_filters_abi(self):
         fn = self._fn("n_filters")

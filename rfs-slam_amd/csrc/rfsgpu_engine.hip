@@ -27,6 +27,7 @@
 #include "fastslam_mh.h"
 #include "motion.h"
 #include "map_metric.h"
+#include "batch_loop.h"
 
 namespace {
 
@@ -170,6 +171,20 @@ struct rfsgpu_filter {
   unsigned char *hBStage[4] = {nullptr, nullptr, nullptr, nullptr};   // pinned ring of the per-cycle tables
   hipEvent_t evBStage[4] = {};
   int bStageNext = 0;
+  // the device loop of a batch (batch_loop.h): propagation and resampling without the host
+  std::vector<char> bMotionSet, bResSet;       // rfsgpu_batch_set_motion_odometry / _set_resampling have been called for the filter
+  std::vector<BatchMotion> bMotion;
+  std::vector<double> bEffN;                   // [nF][2] eff_n, eff_n_percent
+  bool bMotionDirty = true;
+  bool bBirthAlt = false;                      // poseAlt holds the poses from before the last rfsgpu_batch_propagate_async: the next cycle's births
+  bool bDevRoute = false;                      // the ids, resampleOccured_ and the resampling counters live on the device (first rfsgpu_batch_resample_async)
+  BatchMotion *dBMotion = nullptr;             // [nF]
+  BatchPropIn *dBPropIn = nullptr;             // [nF]
+  BatchResIn *dBResIn = nullptr;               // [nF]
+  BatchLoopState BL{};
+  unsigned char *hBLoop[8] = {};               // pinned ring of the two calls' per-filter inputs
+  hipEvent_t evBLoop[8] = {};
+  int bLoopNext = 0;
   // [metric] per-step map / pose error (map_metric.h): ground truth per filter, the device-side log, one row for the synchronous calls
   double *dGtXY = nullptr, *dGtSeen = nullptr;   // [nF][RFSGPU_MAX_METRIC_SET][2], [nF][RFSGPU_MAX_METRIC_SET] (allocated by the first rfsgpu_set_ground_truth)
   int *dGtN = nullptr;                           // [nF]
@@ -425,6 +440,9 @@ void rfsgpu_destroy(rfsgpu_filter *f) {
   murty_free(f->Q, f->MS);
   hipFree(f->dBFilt); hipFree(f->dBParams); hipFree(f->dBZ); hipFree(f->dBZPrev); hipFree(f->dBSums); hipFree(f->dBErrFilter); hipFree(f->dBMaskTmp); hipFree(f->dBInhSrc);
   for (int k = 0; k < 4; k++) { if (f->hBStage[k]) hipHostFree(f->hBStage[k]); if (f->evBStage[k]) hipEventDestroy(f->evBStage[k]); }
+  hipFree(f->dBMotion); hipFree(f->dBPropIn); hipFree(f->dBResIn); hipFree(f->BL.counters); hipFree(f->BL.nResamples); hipFree(f->BL.resampled);
+  hipFree(f->BL.fired); hipFree(f->BL.nEff); hipFree(f->BL.plan); hipFree(f->BL.pid); hipFree(f->BL.ppid);
+  for (int k = 0; k < 8; k++) { if (f->hBLoop[k]) hipHostFree(f->hBLoop[k]); if (f->evBLoop[k]) hipEventDestroy(f->evBLoop[k]); }
   hipFree(f->dGtXY); hipFree(f->dGtSeen); hipFree(f->dGtN); hipFree(f->dErrLog); hipFree(f->dErrRow);
   if (f->hErr) hipHostFree(f->hErr);
   if (f->hJobCount) hipHostFree(f->hJobCount);
@@ -1849,6 +1867,7 @@ int rfsgpu_set_step_inputs_async(rfsgpu_filter *f, const double *x, const double
   int k = 0;
   { const int rc = stage_slot(f, &h, &k); if (rc != RFSGPU_OK) return rc; }
   if (x) {
+    f->bBirthAlt = false;   // (a batch: poses set after rfsgpu_batch_propagate_async are the ones the next predict's births happen at, as on the host route)
     memcpy(h, x, (size_t)f->N * 3 * sizeof(double));
     HIPCHK(hipMemcpyAsync(f->B.pose, h, (size_t)f->N * 3 * sizeof(double), hipMemcpyHostToDevice, f->stream));
     double *hc = h + (size_t)f->Ncap * 3;
@@ -2017,13 +2036,29 @@ int rfsgpu_get_birth_inheritance(const rfsgpu_filter *f) { return f ? f->inherit
 int rfsgpu_get_particle_ids(rfsgpu_filter *f, int *id, int *parent_id) {
   CHECK_HANDLE(f);
   ensure_ids(f);
+  if (f->bDevRoute) {      // (a batch that resamples on the device: the ids live there)
+    hipSetDevice(f->device);
+    HIPCHK(hipMemcpyAsync(f->pid.data(), f->BL.pid, (size_t)f->N * sizeof(int), hipMemcpyDeviceToHost, f->stream));
+    HIPCHK(hipMemcpyAsync(f->ppid.data(), f->BL.ppid, (size_t)f->N * sizeof(int), hipMemcpyDeviceToHost, f->stream));
+    HIPCHK(hipStreamSynchronize(f->stream));
+  }
   for (int k = 0; k < f->N; k++) { if (id) id[k] = f->pid[k]; if (parent_id) parent_id[k] = f->ppid[k]; }
   return RFSGPU_OK;
 }
 int rfsgpu_set_particle_ids(rfsgpu_filter *f, const int *id, const int *parent_id) {
   CHECK_HANDLE(f);
   ensure_ids(f);
+  if (f->bDevRoute && (!id || !parent_id)) {      // the part that is not given stays what the device holds
+    int rc = rfsgpu_get_particle_ids(f, nullptr, nullptr);
+    if (rc != RFSGPU_OK) return rc;
+  }
   for (int k = 0; k < f->N; k++) { if (id) f->pid[k] = id[k]; if (parent_id) f->ppid[k] = parent_id[k]; }
+  if (f->bDevRoute) {
+    hipSetDevice(f->device);
+    HIPCHK(hipMemcpyAsync(f->BL.pid, f->pid.data(), (size_t)f->N * sizeof(int), hipMemcpyHostToDevice, f->stream));
+    HIPCHK(hipMemcpyAsync(f->BL.ppid, f->ppid.data(), (size_t)f->N * sizeof(int), hipMemcpyHostToDevice, f->stream));
+    HIPCHK(hipStreamSynchronize(f->stream));
+  }
   return RFSGPU_OK;
 }
 int rfsgpu_resample_occured(const rfsgpu_filter *f) { return (f && !f->batch) ? (f->resampleOccured ? 1 : 0) : -1; }   // (a batch: rfsgpu_batch_resample_occured)
@@ -2614,6 +2649,26 @@ int rfsgpu_create_batch(rfsgpu_filter **out, int model, int n_filters, int n_per
   ok &= hipMalloc(&f->dBInhSrc, (size_t)f->Ncap * sizeof(int)) == hipSuccess;
   if (ok) ok &= hipMemset(f->dBZPrev, 0, (size_t)n_filters * RFSGPU_MAX_Z * 2 * sizeof(double)) == hipSuccess;
   if (ok) ok &= hipMemset(f->dBSums, 0, (size_t)n_filters * 2 * sizeof(double)) == hipSuccess;
+  // the device loop's tables (batch_loop.h)
+  f->bMotionSet.assign(n_filters, 0); f->bResSet.assign(n_filters, 0);
+  f->bMotion.assign(n_filters, BatchMotion{});
+  f->bEffN.assign((size_t)2 * n_filters, 0.0);
+  ok &= hipMalloc(&f->dBMotion, (size_t)n_filters * sizeof(BatchMotion)) == hipSuccess;
+  ok &= hipMalloc(&f->dBPropIn, (size_t)n_filters * sizeof(BatchPropIn)) == hipSuccess;
+  ok &= hipMalloc(&f->dBResIn, (size_t)n_filters * sizeof(BatchResIn)) == hipSuccess;
+  ok &= hipMalloc(&f->BL.counters, (size_t)n_filters * 2 * sizeof(long long)) == hipSuccess;
+  ok &= hipMalloc(&f->BL.nResamples, (size_t)n_filters * sizeof(long long)) == hipSuccess;
+  ok &= hipMalloc(&f->BL.resampled, (size_t)n_filters * sizeof(int)) == hipSuccess;
+  ok &= hipMalloc(&f->BL.fired, (size_t)n_filters * sizeof(int)) == hipSuccess;
+  ok &= hipMalloc(&f->BL.nEff, (size_t)n_filters * sizeof(double)) == hipSuccess;
+  ok &= hipMalloc(&f->BL.plan, (size_t)f->Ncap * sizeof(int)) == hipSuccess;
+  ok &= hipMalloc(&f->BL.pid, (size_t)f->Ncap * sizeof(int)) == hipSuccess;
+  ok &= hipMalloc(&f->BL.ppid, (size_t)f->Ncap * sizeof(int)) == hipSuccess;
+  if (ok) ok &= hipMemset(f->BL.counters, 0, (size_t)n_filters * 2 * sizeof(long long)) == hipSuccess;
+  if (ok) ok &= hipMemset(f->BL.nResamples, 0, (size_t)n_filters * sizeof(long long)) == hipSuccess;
+  if (ok) ok &= hipMemset(f->BL.resampled, 0, (size_t)n_filters * sizeof(int)) == hipSuccess;
+  if (ok) ok &= hipMemset(f->BL.fired, 0, (size_t)n_filters * sizeof(int)) == hipSuccess;
+  if (ok) ok &= hipMemset(f->BL.nEff, 0, (size_t)n_filters * sizeof(double)) == hipSuccess;
   if (!ok) { rfsgpu_destroy(f); return RFSGPU_ERR_HIP; }
   *out = f;
   return RFSGPU_OK;
@@ -2669,7 +2724,7 @@ int rfsgpu_batch_cycle_async(rfsgpu_filter *f, int predict, const double *x, con
   // birth step: nothing once that filter has had an update (its births consume the whole mask), else what it inherited in turn.
   ensure_ids(f);
   std::vector<int> src;
-  if (predict == 1) {
+  if (predict == 1 && !f->bDevRoute) {     // (the device route: batch_inherit_dev_kernel below, from the ids on the device)
     for (int b = 0; b < nF; b++) {
       if (!f->bResampled[b]) continue;
       const int lo = b * nPer, hi = lo + nPer;
@@ -2726,11 +2781,16 @@ int rfsgpu_batch_cycle_async(rfsgpu_filter *f, int predict, const double *x, con
     HIPCHK(hipMemcpyAsync(f->dBMaskTmp, f->B.unusedMask, (size_t)f->N * sizeof(unsigned long long), hipMemcpyDeviceToDevice, f->stream));
     batch_inherit_kernel<<<(f->N + 255) / 256, 256, 0, f->stream>>>(f->B.unusedMask, f->dBMaskTmp, f->dBInhSrc, f->N);
   }
+  if (f->bDevRoute) {
+    batch_inherit_dev_kernel<<<nF, BATCH_LOOP_THREADS, 0, f->stream>>>(f->B.unusedMask, f->BL.ppid, f->BL.resampled, f->dBFilt, nPer, predict == 1 ? 1 : 0);
+    HIPCHK(hipGetLastError());
+  }
   HIPCHK(hipEventRecord(f->evBStage[kb], f->stream));
   // the host's new poses / covariances, pulled by the step kernel from a slot of the staging ring (rfsgpu_cycle_async's form)
   StepPredict sp = NO_HEAD;
   sp.mode = predict < 0 ? 0 : (predict ? 2 : 1);
-  sp.birthPose = f->B.pose;
+  sp.birthPose = f->bBirthAlt ? f->poseAlt : f->B.pose;   // after rfsgpu_batch_propagate_async the births still see the poses from before it
+  f->bBirthAlt = false;
   int ks = -1;
   if (x) {
     double *hx = nullptr;
@@ -2822,6 +2882,9 @@ int rfsgpu_batch_resample_apply(rfsgpu_filter *f, const int *src_slot, const uns
   int rc = batch_check(f, -1);
   if (rc != RFSGPU_OK) return rc;
   if (!src_slot || !resampled) return fail(f, RFSGPU_ERR_INVALID, "batch_resample_apply: null argument");
+  if (f->bDevRoute)
+    return fail(f, RFSGPU_ERR_UNSUPPORTED, "batch_resample_apply: this batch resamples on the device (rfsgpu_batch_resample_async has run): the particle ids, resampleOccured_ "
+                                           "and the resampling counters live there, and the two routes do not mix on one handle");
   const int nF = f->nF, nPer = f->nPer;
   bool any = false;
   for (int b = 0; b < nF; b++) {
@@ -2880,7 +2943,201 @@ int rfsgpu_murty_seen(rfsgpu_filter *f) {
 // resampleOccured_ of every filter, [n_filters]
 int rfsgpu_batch_resample_occured(const rfsgpu_filter *f, unsigned char *out) {
   if (!f || !f->batch || !out) return RFSGPU_ERR_INVALID;
+  if (f->bDevRoute) {      // (a batch that resamples on the device: the flags live there; synchronising)
+    std::vector<int> r(f->nF);
+    hipSetDevice(f->device);
+    if (hipMemcpyAsync(r.data(), f->BL.resampled, (size_t)f->nF * sizeof(int), hipMemcpyDeviceToHost, f->stream) != hipSuccess ||
+        hipStreamSynchronize(f->stream) != hipSuccess) return RFSGPU_ERR_HIP;
+    for (int b = 0; b < f->nF; b++) out[b] = r[b] ? 1 : 0;
+    return RFSGPU_OK;
+  }
   for (int b = 0; b < f->nF; b++) out[b] = f->bResampled[b] ? 1 : 0;
+  return RFSGPU_OK;
+}
+
+// ---- the device loop of a batch (batch_loop.h): propagation and resampling as stream-ordered launches -------------------------------
+int rfsgpu_batch_set_motion_odometry(rfsgpu_filter *f, int filter, const double *var, unsigned long long seed) {
+  CHECK_HANDLE(f);
+  int rc = batch_check(f, filter);
+  if (rc != RFSGPU_OK) return rc;
+  if (!var || !(var[0] >= 0.0) || !(var[1] >= 0.0) || !(var[2] >= 0.0)) return fail(f, RFSGPU_ERR_INVALID, "batch_set_motion_odometry: var is three variances >= 0");
+  for (int b = (filter < 0 ? 0 : filter); b < (filter < 0 ? f->nF : filter + 1); b++) {
+    BatchMotion &M = f->bMotion[b];
+    for (int q = 0; q < 3; q++) { M.var[q] = var[q]; M.sd[q] = sqrt(var[q]); }
+    M.seed = seed;
+    f->bMotionSet[b] = 1;
+  }
+  f->bMotionDirty = true;
+  return RFSGPU_OK;
+}
+int rfsgpu_batch_set_resampling(rfsgpu_filter *f, int filter, double eff_n, double eff_n_percent) {
+  CHECK_HANDLE(f);
+  int rc = batch_check(f, filter);
+  if (rc != RFSGPU_OK) return rc;
+  for (int b = (filter < 0 ? 0 : filter); b < (filter < 0 ? f->nF : filter + 1); b++) {
+    f->bEffN[2 * (size_t)b] = eff_n; f->bEffN[2 * (size_t)b + 1] = eff_n_percent;
+    f->bResSet[b] = 1;
+  }
+  return RFSGPU_OK;
+}
+// One slot of the device loop's pinned ring (as batch_stage; eight slots: two calls per cycle, four cycles)
+static int batch_loop_stage(rfsgpu_filter *f, unsigned char **h, int *k_out) {
+  const int k = f->bLoopNext;
+  f->bLoopNext = (k + 1) & 7;
+  const bool fresh = !f->hBLoop[k] || !f->evBLoop[k];
+  if (!f->hBLoop[k]) HIPCHK(hipHostMalloc(&f->hBLoop[k], (size_t)f->nF * std::max(sizeof(BatchMotion), std::max(sizeof(BatchPropIn), sizeof(BatchResIn)))));
+  if (!f->evBLoop[k]) HIPCHK(hipEventCreateWithFlags(&f->evBLoop[k], hipEventDisableTiming));
+  if (fresh) HIPCHK(hipStreamSynchronize(f->stream));
+  else HIPCHK(hipEventSynchronize(f->evBLoop[k]));
+  *h = f->hBLoop[k];
+  *k_out = k;
+  return RFSGPU_OK;
+}
+// The filters' motion parameters, when they have changed: through a slot of the pinned ring, like the per-call tables (nothing waits)
+static int batch_push_motion(rfsgpu_filter *f) {
+  if (!f->bMotionDirty) return RFSGPU_OK;
+  unsigned char *h = nullptr;
+  int k = 0;
+  int rc = batch_loop_stage(f, &h, &k);
+  if (rc != RFSGPU_OK) return rc;
+  memcpy(h, f->bMotion.data(), (size_t)f->nF * sizeof(BatchMotion));
+  HIPCHK(hipMemcpyAsync(f->dBMotion, h, (size_t)f->nF * sizeof(BatchMotion), hipMemcpyHostToDevice, f->stream));
+  HIPCHK(hipEventRecord(f->evBLoop[k], f->stream));
+  f->bMotionDirty = false;
+  return RFSGPU_OK;
+}
+int rfsgpu_batch_propagate_async(rfsgpu_filter *f, const double *u, const double *pin_pose, const unsigned char *pin, unsigned long long call) {
+  CHECK_HANDLE(f);
+  int rc = batch_check(f, -1);
+  if (rc != RFSGPU_OK) return rc;
+  if (!u) return fail(f, RFSGPU_ERR_INVALID, "batch_propagate: null odometry input");
+  const int nF = f->nF;
+  for (int b = 0; b < nF; b++) {
+    if (pin && pin[b] && !pin_pose) return fail(f, RFSGPU_ERR_INVALID, "batch_propagate: a pinned filter without pin_pose");
+    if (!f->bMotionSet[b]) {
+      f->err = "batch_propagate: filter " + std::to_string(b) + " has no motion parameters (rfsgpu_batch_set_motion_odometry)";
+      return RFSGPU_ERR_INVALID;
+    }
+  }
+  hipSetDevice(f->device);
+  if ((rc = batch_push_motion(f)) != RFSGPU_OK) return rc;
+  unsigned char *h = nullptr;
+  int k = 0;
+  if ((rc = batch_loop_stage(f, &h, &k)) != RFSGPU_OK) return rc;
+  BatchPropIn *hi = reinterpret_cast<BatchPropIn *>(h);
+  for (int b = 0; b < nF; b++) {
+    BatchPropIn &I = hi[b];
+    memset(&I, 0, sizeof I);
+    memcpy(I.u, u + 3 * (size_t)b, 3 * sizeof(double));
+    I.pin = (pin && pin[b]) ? 1 : 0;
+    if (I.pin) memcpy(I.pinPose, pin_pose + 3 * (size_t)b, 3 * sizeof(double));
+  }
+  HIPCHK(hipMemcpyAsync(f->dBPropIn, hi, (size_t)nF * sizeof(BatchPropIn), hipMemcpyHostToDevice, f->stream));
+  HIPCHK(hipEventRecord(f->evBLoop[k], f->stream));
+  // every particle gets its own pose covariance (handle-wide stride, as rfsgpu_batch_cycle_async sets it with x_cov [N][9])
+  if (f->P.poseCovStride != 9) { f->P.poseCovStride = 9; f->bParamsDirty = true; }
+  f->poseCovZero = false;
+  // the new poses go to the second pose buffer and the two change places: the next cycle's births read the old ones there.  A
+  // second propagation before that cycle works in place, so that the births still see the poses the last update used.
+  double *dst = f->bBirthAlt ? f->B.pose : f->poseAlt;
+  batch_propagate_kernel<<<(f->N + 255) / 256, 256, 0, f->stream>>>(f->B.pose, dst, f->B.poseCov, f->dBMotion, f->dBPropIn, f->N, f->nPer,
+                                                                     (unsigned)(call & 0xffffffffull), (unsigned)(call >> 32));
+  HIPCHK(hipGetLastError());
+  if (!f->bBirthAlt) { f->poseAlt = f->B.pose; f->B.pose = dst; f->bBirthAlt = true; }
+  return RFSGPU_OK;
+}
+int rfsgpu_batch_resample_async(rfsgpu_filter *f, const int *n_z, unsigned long long call) {
+  CHECK_HANDLE(f);
+  int rc = batch_check(f, -1);
+  if (rc != RFSGPU_OK) return rc;
+  if (!n_z) return fail(f, RFSGPU_ERR_INVALID, "batch_resample: null measurement counts");
+  const int nF = f->nF;
+  if (f->nPer > RFSGPU_BATCH_RESAMPLE_MAX_PER_FILTER)
+    return fail(f, RFSGPU_ERR_UNSUPPORTED, "batch_resample: more than RFSGPU_BATCH_RESAMPLE_MAX_PER_FILTER particles per filter (one workgroup resamples a filter)");
+  for (int b = 0; b < nF; b++) {
+    if (n_z[b] < 0 || n_z[b] > RFSGPU_MAX_Z) {
+      f->err = "batch_resample: filter " + std::to_string(b) + " has " + std::to_string(n_z[b]) + " measurements (0 ... RFSGPU_MAX_Z)";
+      return RFSGPU_ERR_INVALID;
+    }
+    if (!f->bMotionSet[b] || !f->bResSet[b]) {
+      f->err = "batch_resample: filter " + std::to_string(b) + (f->bResSet[b] ? " has no Philox key (rfsgpu_batch_set_motion_odometry)" : " has no resampling thresholds (rfsgpu_batch_set_resampling)");
+      return RFSGPU_ERR_INVALID;
+    }
+  }
+  hipSetDevice(f->device);
+  long long t0 = now_ns();
+  if (!f->bDevRoute) {     // from here on the ids and resampleOccured_ live on the device.  Once per handle, and host-synchronous: the
+                           // sources are pageable host vectors, which the runtime copies before the call returns; the synchronisation
+                           // below says so instead of relying on it
+    ensure_ids(f);
+    std::vector<int> r(nF);
+    for (int b = 0; b < nF; b++) r[b] = f->bResampled[b] ? 1 : 0;
+    HIPCHK(hipMemcpyAsync(f->BL.pid, f->pid.data(), (size_t)f->N * sizeof(int), hipMemcpyHostToDevice, f->stream));
+    HIPCHK(hipMemcpyAsync(f->BL.ppid, f->ppid.data(), (size_t)f->N * sizeof(int), hipMemcpyHostToDevice, f->stream));
+    HIPCHK(hipMemcpyAsync(f->BL.resampled, r.data(), (size_t)nF * sizeof(int), hipMemcpyHostToDevice, f->stream));
+    HIPCHK(hipStreamSynchronize(f->stream));
+    f->bDevRoute = true;
+  }
+  if ((rc = batch_push_motion(f)) != RFSGPU_OK) return rc;
+  unsigned char *h = nullptr;
+  int k = 0;
+  if ((rc = batch_loop_stage(f, &h, &k)) != RFSGPU_OK) return rc;
+  BatchResIn *hi = reinterpret_cast<BatchResIn *>(h);
+  for (int b = 0; b < nF; b++) {
+    BatchResIn &I = hi[b];
+    I.effN = f->bEffN[2 * (size_t)b]; I.effNPercent = f->bEffN[2 * (size_t)b + 1];
+    I.nZ = n_z[b];
+    I.minUpdates = f->bCfg[b].minUpdatesBeforeResample; I.minMeasurements = f->bCfg[b].minMeasurementsBeforeResample;
+    I.pad = 0;
+  }
+  HIPCHK(hipMemcpyAsync(f->dBResIn, hi, (size_t)nF * sizeof(BatchResIn), hipMemcpyHostToDevice, f->stream));
+  HIPCHK(hipEventRecord(f->evBLoop[k], f->stream));
+  batch_resample_kernel<<<nF, BATCH_LOOP_THREADS, 0, f->stream>>>(f->B.weight, f->BL, f->dBMotion, f->dBResIn, f->nPer, call);
+  resample_gather_kernel<<<f->N, 256, 0, f->stream>>>(f->B, f->cur, f->BL.plan, f->P.poseCovStride, 1);
+  HIPCHK(hipGetLastError());
+  const long long dtn = now_ns() - t0;
+  f->timing.particleResample_wall += dtn;
+  f->timing.particleResample_cpu += dtn;
+  return RFSGPU_OK;
+}
+int rfsgpu_batch_last_resample(rfsgpu_filter *f, unsigned char *fired, int *src_slot, double *n_eff) {
+  CHECK_HANDLE(f);
+  int rc = batch_check(f, -1);
+  if (rc != RFSGPU_OK) return rc;
+  hipSetDevice(f->device);
+  if (!f->bDevRoute) {     // no rfsgpu_batch_resample_async yet: nothing fired
+    for (int b = 0; b < f->nF; b++) { if (fired) fired[b] = 0; if (n_eff) n_eff[b] = 0.0; }
+    if (src_slot) for (int q = 0; q < f->N; q++) src_slot[q] = q;
+    return RFSGPU_OK;
+  }
+  std::vector<int> fi(f->nF);
+  HIPCHK(hipMemcpyAsync(fi.data(), f->BL.fired, (size_t)f->nF * sizeof(int), hipMemcpyDeviceToHost, f->stream));
+  if (src_slot) HIPCHK(hipMemcpyAsync(src_slot, f->BL.plan, (size_t)f->N * sizeof(int), hipMemcpyDeviceToHost, f->stream));
+  if (n_eff) HIPCHK(hipMemcpyAsync(n_eff, f->BL.nEff, (size_t)f->nF * sizeof(double), hipMemcpyDeviceToHost, f->stream));
+  HIPCHK(hipStreamSynchronize(f->stream));
+  if (fired) for (int b = 0; b < f->nF; b++) fired[b] = fi[b] ? 1 : 0;
+  return RFSGPU_OK;
+}
+int rfsgpu_batch_get_pose_covs(rfsgpu_filter *f, double *out) {
+  CHECK_HANDLE(f);
+  int rc = batch_check(f, -1);
+  if (rc != RFSGPU_OK) return rc;
+  if (!out) return fail(f, RFSGPU_ERR_INVALID, "batch_get_pose_covs: null output");
+  hipSetDevice(f->device);
+  const bool each = f->P.poseCovStride == 9;
+  HIPCHK(hipMemcpyAsync(out, f->B.poseCov, (each ? (size_t)f->N : 1) * 9 * sizeof(double), hipMemcpyDeviceToHost, f->stream));
+  HIPCHK(hipStreamSynchronize(f->stream));
+  if (!each) for (int k = 1; k < f->N; k++) memcpy(out + 9 * (size_t)k, out, 9 * sizeof(double));   // (one covariance shared by all slots)
+  return RFSGPU_OK;
+}
+int rfsgpu_batch_resample_counts(rfsgpu_filter *f, long long *out) {
+  CHECK_HANDLE(f);
+  int rc = batch_check(f, -1);
+  if (rc != RFSGPU_OK) return rc;
+  if (!out) return fail(f, RFSGPU_ERR_INVALID, "batch_resample_counts: null output");
+  hipSetDevice(f->device);
+  HIPCHK(hipMemcpyAsync(out, f->BL.nResamples, (size_t)f->nF * sizeof(long long), hipMemcpyDeviceToHost, f->stream));
+  HIPCHK(hipStreamSynchronize(f->stream));
   return RFSGPU_OK;
 }
 

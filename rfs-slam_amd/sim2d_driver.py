@@ -265,11 +265,18 @@ class Sim2dBatchRun:
     static step) with the new poses, the update with the step's measurements (none: no update), normalisation, and
     ParticleFilter::resample's gate / N_eff test / systematic plan (FilterBatch.update_and_resample; the same rule per handle).  As in
     Sim2dRun, every cycle counts as an update for the gate (empty ones included), a filter draws its process noise every step and its
-    resampling draw only when its N_eff test fires: a one-filter run takes the draws Sim2dRun takes with the same seed."""
+    resampling draw only when its N_eff test fires: a one-filter run takes the draws Sim2dRun takes with the same seed.
 
-    def __init__(self, target, datas, Ps, seeds, track_errors=False):
+    device_loop=True (a FilterBatch only): the whole cycle on the device.  Per step propagate_async -> cycle_async(poses=None) ->
+    resample_async (-> step_error_async when tracking), all stream-ordered: nothing is read back until errors(), resample_counts()
+    or the end of the run, so the host only feeds the pinned rings.  The randomness is then the device's (Philox under seeds[b],
+    call number = the step k), not the numpy streams of the host loop: the two loops run the same model on different realisations
+    of the noise.  step() returns None in this form (the decisions stay on the device; FilterBatch.last_resample reads the last ones)."""
+
+    def __init__(self, target, datas, Ps, seeds, track_errors=False, device_loop=False):
         """track_errors: as in Sim2dRun -- each filter's ground truth is uploaded, every cycle ends with one step_error_async (one
         launch for the whole batch; one per handle otherwise), errors() reads the log(s) once at the end."""
+        self.device_loop = bool(device_loop)
         self.batch = target if isinstance(target, capi.CBatch) else None
         self.handles = None if self.batch is not None else list(target)
         self.nF = len(datas)
@@ -306,8 +313,60 @@ class Sim2dBatchRun:
                     self.handles[b].error_log_create(rows)
             if self.batch is not None:
                 self.batch.error_log_create(rows)
+        if self.device_loop:
+            assert self.batch is not None, "the device loop needs a FilterBatch"
+            self._device_loop_setup(seeds)
+
+    def _device_loop_setup(self, seeds):
+        """The filters' motion / resampling parameters, and every step's inputs in the layout the calls take (packed once: the
+        measurements are pre-generated, the per-step host work is three calls)."""
+        K = int(min(d["K"] for d in self.datas))
+        nF = self.nF
+        for b in range(nF):
+            self.batch.set_motion_odometry(b, np.diag(self.Q[b]), seeds[b])
+            self.batch.set_resampling(b, self.eff_n[b], self.eff_n[b] / self.n)
+        self._u = np.ascontiguousarray(np.stack([d["odom"][:K] for d in self.datas], axis=1))          # [K, nF, 3]
+        self._gt = np.ascontiguousarray(np.stack([d["gt"][:K] for d in self.datas], axis=1))
+        self._z = np.zeros((K, nF, capi.MAX_Z, 2))
+        self._nz = np.zeros((K, nF), dtype=np.int32)
+        for b, d in enumerate(self.datas):
+            for k in range(K):
+                Z = d["Z"][k] if k < len(d["Z"]) else np.zeros((0, 2))
+                m = len(Z)
+                assert m <= capi.MAX_Z
+                self._nz[k, b] = m
+                if m:
+                    self._z[k, b, :m] = Z
+        self._t = np.array([[k * P["dt"] for P in self.Ps] for k in range(K)])
+        self._pin_all = np.ones(nF, dtype=np.uint8)
+
+    def _device_propagate(self, k):
+        bt = self.batch
+        if k <= 100:                                                                    # :590-593
+            bt.propagate_async(self._u[k], k, pin=self._pin_all, pin_pose=self._gt[k])
+        else:
+            bt.propagate_async(self._u[k], k)
+
+    def _device_step(self, k):
+        self._device_propagate(k)
+        return self._device_update(k)
+
+    def _device_update(self, k):
+        bt = self.batch
+        bt.batch_cycle_async_packed(True, self._z[k], self._nz[k], normalize=True)
+        bt.resample_async(self._nz[k], k)
+        self.last_n_z = self._nz[k]
+        if self.track_errors:
+            bt.step_error_async(self._t[k], self._gt[k], ERROR_W_THRESHOLD, ERROR_CUTOFF, ERROR_ORDER)
+        return None
+
+    def resample_counts(self):
+        """Resamplings per filter so far (the device loop: one read-back; the host loop: its own count)."""
+        return self.batch.resample_counts() if self.device_loop else self.n_resamples.copy()
 
     def step(self, k):
+        if self.device_loop:
+            return self._device_step(k)
         fired = self._step(k)
         if self.track_errors:
             t = np.array([k * P["dt"] for P in self.Ps])

@@ -11,6 +11,11 @@ then each run's final map error.  A tuning / evaluation tool, not part of bench.
 log read at the end).  Per filter the final and mean COLA and pose error with the reference's constants (0.75, 0.20, 1.0: src/analysis2dSim.cpp),
 the curves in --json, and for every batch size three throughput figures from the one invocation: filter-steps/s (a) with tracking off, (b) with
 device tracking, (c) with the host route (per step and filter get_weights + export_gm of the best particle + tools/analysis2d_sim.py::cola).
+
+--device-loop: the batch runs its whole cycle on the device (Sim2dBatchRun(device_loop=True): propagate_async -> cycle_async ->
+resample_async, nothing read back until the end; the final synchronisation is inside the timed span).  --both-loops: the host loop
+and the device loop from the one invocation, both figures in the line.  Every line names its loop kind ("loop").  --reps N: N timed
+repetitions of each figure (fresh batch each), all of them in the line ("..._reps") next to their median.
 """
 import argparse
 import json
@@ -48,6 +53,17 @@ def timed(run, steps):
     t0 = time.perf_counter()
     for k in range(2, steps + 2):
         run.step(k)
+    return time.perf_counter() - t0
+
+
+def timed_synced(run, steps):
+    """As timed(), for a loop that waits for nothing: the span ends when the queued work is done."""
+    run.step(1)
+    run.batch.synchronize()
+    t0 = time.perf_counter()
+    for k in range(2, steps + 2):
+        run.step(k)
+    run.batch.synchronize()
     return time.perf_counter() - t0
 
 
@@ -119,6 +135,9 @@ def main():
     ap.add_argument("--capacity", type=int, default=256)
     ap.add_argument("--json", default="")
     ap.add_argument("--errors", action="store_true", help="track COLA / pose error on the device; tracking off / device / host route timed side by side")
+    ap.add_argument("--device-loop", action="store_true", help="the batch's whole cycle on the device (propagation and resampling included)")
+    ap.add_argument("--both-loops", action="store_true", help="host loop and device loop side by side")
+    ap.add_argument("--reps", type=int, default=1, help="timed repetitions of every batch figure")
     a = ap.parse_args()
     pkg = load_pkg()
     sim = pkg.sim2d_driver
@@ -128,12 +147,29 @@ def main():
     rows = []
     if a.errors:
         erows = errors_sweep(pkg, a, sizes, Ps, datas, seeds)
+    loops = ["host", "device"] if a.both_loops else (["device"] if a.device_loop else ["host"])
     for B in sizes:
-        batch = pkg.FilterBatch(B, a.particles, gm_capacity=a.capacity)
-        rb = sim.Sim2dBatchRun(batch, datas[:B], Ps[:B], seeds[:B])
-        tb = timed(rb, a.steps)
-        batch.synchronize()
-        row = dict(B=B, particles=a.particles, steps=a.steps, batch_filter_steps_per_s=B * a.steps / tb)
+        figs = {}
+        for loop in loops:
+            figs[loop] = []
+            for rep in range(max(1, a.reps)):
+                if rep or loop != loops[0]:
+                    batch.close()
+                batch = pkg.FilterBatch(B, a.particles, gm_capacity=a.capacity)
+                rb = sim.Sim2dBatchRun(batch, datas[:B], Ps[:B], seeds[:B], device_loop=(loop == "device"))
+                t = timed_synced(rb, a.steps) if loop == "device" else timed(rb, a.steps)
+                batch.synchronize()
+                figs[loop].append(B * a.steps / t)
+        tb = B * a.steps / float(np.median(figs[loops[0]]))
+        row = dict(B=B, particles=a.particles, steps=a.steps, loop="+".join(loops), batch_filter_steps_per_s=float(np.median(figs[loops[0]])))
+        if a.reps > 1:
+            row["batch_filter_steps_per_s_reps"] = figs[loops[0]]
+        if len(loops) == 2:
+            row["device_loop_filter_steps_per_s"] = float(np.median(figs["device"]))
+            row["device_over_host_loop"] = row["device_loop_filter_steps_per_s"] / row["batch_filter_steps_per_s"]
+            if a.reps > 1:
+                row["device_loop_filter_steps_per_s_reps"] = figs["device"]
+            row["resamples_device_loop"] = rb.resample_counts().tolist()
         if B <= a.handles_max:
             hs = [pkg.RBPHDFilter(a.particles, gm_capacity=a.capacity) for _ in range(B)]
             rh = sim.Sim2dBatchRun(hs, datas[:B], Ps[:B], seeds[:B])
