@@ -628,7 +628,7 @@ int rfsgpu_fastslam_set_resample_occured(rfsgpu_filter *f, int flag);
 /* parent[k] = the slot particle k was copied from by the last rfsgpu_fastslam_update (k itself when it was not a copy). */
 int rfsgpu_particle_parents(rfsgpu_filter *f, int *parent, int max_n);
 
-/* ---- [batch] many independent 2-D RB-PHD filters in one handle (outside the STABLE CORE) -------------------------------------
+/* ---- [batch] many independent 2-D RB-PHD or FastSLAM filters in one handle (outside the STABLE CORE) -------------------------
  * A batch handle holds n_filters independent range-bearing filters of n_per_filter particles each, stepped together: one cycle is
  * one fused step launch + one post launch for all of them.  Particle slots are global -- filter b owns slots
  * [b * n_per_filter, (b + 1) * n_per_filter) -- so the per-slot calls work unchanged (rfsgpu_set_poses, rfsgpu_get_weights,
@@ -636,7 +636,9 @@ int rfsgpu_particle_parents(rfsgpu_filter *f, int *parent, int max_n);
  * measurement set, weights, normalisation, resampling and resampleOccured_; each equals a separate handle given the same inputs.
  * The whole-handle setters (rfsgpu_set_filter_config, _set_model_rngbrg, _set_kf_config, _set_lmk_process_noise) set every filter.
  * Not on a batch handle (RFSGPU_ERR_UNSUPPORTED, with a rfsgpu_last_error message): the Victoria Park model and
- * rfsgpu_set_laser_scan, FastSLAM, rfsgpu_update* and the phase calls, rfsgpu_step_async*, rfsgpu_cycle_async, rfsgpu_predict_map*,
+ * rfsgpu_set_laser_scan, the single-handle FastSLAM calls (rfsgpu_set_fastslam_config, rfsgpu_fastslam_update: a batch of FastSLAM
+ * filters has rfsgpu_batch_set_fastslam_config / rfsgpu_batch_fastslam_cycle_async below), multi-hypothesis FastSLAM and landmark
+ * candidate lists (count threshold != 1), rfsgpu_update* and the phase calls, rfsgpu_step_async*, rfsgpu_cycle_async, rfsgpu_predict_map*,
  * the collective calls, rfsgpu_resample_apply[_n], rfsgpu_weight_sums[_async], rfsgpu_normalize_weights[_parts] (one total for all
  * filters: rfsgpu_batch_weight_sums and the cycle's normalize instead), rfsgpu_import_birth_candidates, birth inheritance modes other
  * than RFSGPU_INHERIT_REFERENCE, and configurations with birthGaussianMeasurementCountThreshold != 1 (the births are immediate).
@@ -706,6 +708,28 @@ int rfsgpu_batch_last_resample(rfsgpu_filter *f, unsigned char *fired, int *src_
 int rfsgpu_batch_get_pose_covs(rfsgpu_filter *f, double *out);
 /* Resamplings of each filter by rfsgpu_batch_resample_async so far: out [n_filters].  Synchronising. */
 int rfsgpu_batch_resample_counts(rfsgpu_filter *f, long long *out);
+/* -- a batch of FastSLAM filters: every filter is a 2-D single-hypothesis rfs::FastSLAM (include/FastSLAM.hpp) with its own
+ * configuration, measurement set, weights, resampling and seed; each equals a separate handle driven through
+ * rfsgpu_predict_map(add_birth = 0) / rfsgpu_fastslam_update given the same inputs.  A batch is of ONE kind: the first of
+ * rfsgpu_batch_set_fastslam_config / rfsgpu_batch_fastslam_cycle_async (FastSLAM) or rfsgpu_batch_cycle_async (RB-PHD) decides, and
+ * from then on the other kind's calls return RFSGPU_ERR_UNSUPPORTED with a message.  The model, Kalman filter and
+ * landmark process noise of a filter come from rfsgpu_batch_configure as for an RB-PHD batch; propagation, resampling
+ * (rfsgpu_batch_propagate_async, _resample_async, _last_resample, _resample_counts, _resample_apply), rfsgpu_batch_weight_sums and the
+ * per-slot getters work unchanged.  The [metric] calls accept a FastSLAM batch (there a Gaussian's weight is a log-odds: see below).
+ *
+ * Filter `filter`'s (-1: every filter's) FastSLAM configuration.  RFSGPU_ERR_UNSUPPORTED, naming the filter, for
+ * maxNDataAssocHypotheses != 1 (the multi-hypothesis update grows the particle set) and for
+ * landmarkCandidateMeasurementCountThreshold != 1 (candidate lists would have to travel with a resampling).  On a FastSLAM batch the
+ * two gates of rfsgpu_batch_resample_async are this configuration's minUpdatesBeforeResample / minMeasurementsBeforeResample. */
+int rfsgpu_batch_set_fastslam_config(rfsgpu_filter *f, int filter, const rfsgpu_fastslam_config *cfg);
+/* FastSLAM::predict's map part and FastSLAM::update of every filter, arguments as rfsgpu_batch_cycle_async.  predict 0 or 1: the
+ * static landmark step (Sigma += Q_b, no births; it also runs for a filter with n_z == 0), RFSGPU_CYCLE_NO_PREDICT: none.  A filter
+ * with n_z == 0 is not updated and not normalised this cycle (FastSLAM.hpp:402-403).  A filter prunes only when n_z >= its
+ * pruningMeasurementsThreshold.  normalize != 0: each updated filter's weights are divided by their own sum (the summation order of
+ * rfsgpu_batch_weight_sums).  Stream-ordered, nothing synchronises; errors reach the host as with rfsgpu_batch_cycle_async (the shared
+ * device error word at the next synchronising call; rfsgpu_last_error names the lowest filter that ran out of gm_capacity). */
+int rfsgpu_batch_fastslam_cycle_async(rfsgpu_filter *f, int predict, const double *x, const double *x_cov, int cov_stride,
+                                      const double *z, const int *n_z, int normalize);
 #ifdef RFSGPU_ENABLE_BENCH_API
 /* [test] 1 once a step of this handle (batch or not) has queued Murty-200 partitions, else 0.  Synchronising. */
 int rfsgpu_murty_seen(rfsgpu_filter *f);
@@ -717,8 +741,12 @@ int rfsgpu_murty_seen(rfsgpu_filter *f);
  * particle set (:265-317, getAverageError) and the OSPA / COLA error (include/OSPA.hpp:122-203, include/COLA.hpp:91-98) between the map estimate of
  * the highest-weight particle and the ground-truth landmarks that have been in sensor range so far.  The kernel (csrc/map_metric.h)
  * reads the filter state as it is at that point of the stream and writes one record per filter; nothing else changes.
- * 2-D landmarks only: Victoria Park handles, handles on which rfsgpu_fastslam_update has run and the shard handles of an
- * rfsgpu_group return RFSGPU_ERR_UNSUPPORTED (with a rfsgpu_last_error message) from every call of this section. */
+ * 2-D landmarks only: Victoria Park handles, ordinary handles on which rfsgpu_fastslam_update has run and the shard handles of an
+ * rfsgpu_group return RFSGPU_ERR_UNSUPPORTED (with a rfsgpu_last_error message) from every call of this section.
+ * A batch of FastSLAM filters (rfsgpu_batch_fastslam_cycle_async) is served: a Gaussian's weight is a log-odds w there, and wherever
+ * this section says "weight" of a Gaussian (n_est, cardinality, rfsgpu_get_map_estimate's w) it means 1 - 1 / (1 + exp(w)), the
+ * number the reference's fastslam2dSim logs (src/fastslam2dSim.cpp:628) and analysis2dSim thresholds.  Lifting the refusal for an
+ * ordinary FastSLAM handle is a later change. */
 #define RFSGPU_MAX_METRIC_SET 512   /* hard limit of either set of one comparison (estimates, observable ground truth) */
 /* One record per filter and call; every field is 8 bytes wide.  status: 0 = ok; 1 = n_est or n_truth exceeds
  * RFSGPU_MAX_METRIC_SET; 2 = no finite cost met (non-finite coordinates).  With status != 0 ospa, cola, e_dist, e_card are NaN

@@ -138,6 +138,7 @@ ABI_SYMBOLS = [
     "group_update_io", "group_update_deferred", "group_set_model_victoriapark", "group_set_laser_scan", "group_set_phase_timing", "group_get_timing", "group_collective",
     "create_batch", "n_filters", "batch_configure", "batch_cycle_async", "batch_weight_sums", "batch_resample_apply", "batch_resample_occured", "murty_seen",
     "batch_set_motion_odometry", "batch_set_resampling", "batch_propagate_async", "batch_resample_async", "batch_last_resample", "batch_resample_counts", "batch_get_pose_covs",
+    "batch_set_fastslam_config", "batch_fastslam_cycle_async",
     "set_ground_truth", "error_log_create", "error_log_reset", "step_error_async", "error_log_read", "step_error", "get_map_estimate",
 ]
 
@@ -701,9 +702,8 @@ class CBatch(CFilter):
         self._call("batch_configure", C.c_int(int(b)), C.c_void_p(None) if cfg is None else C.byref(cfg), C.c_void_p(None) if m is None else C.byref(m),
                    C.c_void_p(None) if k is None else C.byref(k), C.c_void_p(None) if q is None else self._ptr(q))
 
-    def batch_cycle_async(self, predict, Zs, poses=None, pose_cov=None, normalize=True):
-        """rfsgpu_batch_cycle_async: Zs = one measurement array per filter ([n_z, 2], possibly empty); predict None / False / True as
-        rfsgpu_cycle_async."""
+    def _cycle_call(self, name, predict, Zs, poses, pose_cov, normalize):
+        """The two cycle calls share one argument layout: the sets packed as z [n_filters, MAX_Z, 2] / nz [n_filters]."""
         assert len(Zs) == self.n_filters
         z = np.zeros((self.n_filters, MAX_Z, 2))
         nz = np.zeros(self.n_filters, dtype=np.int32)
@@ -718,14 +718,34 @@ class CBatch(CFilter):
             cv = _f64(pose_cov)
             assert cv.size in (9, 9 * self.n)
             stride = 0 if cv.size == 9 else 9
-        self._call("batch_cycle_async", C.c_int(-1 if predict is None else (1 if predict else 0)), C.c_void_p(None) if x is None else self._ptr(x),
+        self._call(name, C.c_int(-1 if predict is None else (1 if predict else 0)), C.c_void_p(None) if x is None else self._ptr(x),
                    C.c_void_p(None) if cv is None else self._ptr(cv), C.c_int(stride), self._ptr(z), self._ptr(nz), C.c_int(1 if normalize else 0))
+
+    def batch_cycle_async(self, predict, Zs, poses=None, pose_cov=None, normalize=True):
+        """rfsgpu_batch_cycle_async: Zs = one measurement array per filter ([n_z, 2], possibly empty); predict None / False / True as
+        rfsgpu_cycle_async."""
+        self._cycle_call("batch_cycle_async", predict, Zs, poses, pose_cov, normalize)
 
     def batch_cycle_async_packed(self, predict, z, nz, normalize=True):
         """rfsgpu_batch_cycle_async with the sets already in the call's layout (z [n_filters, MAX_Z, 2] float64, nz [n_filters] int32,
         both C-contiguous) and no new poses: what a loop that packs its measurement sets once issues per step."""
         assert z.dtype == np.float64 and nz.dtype == np.int32 and z.shape == (self.n_filters, MAX_Z, 2) and z.flags.c_contiguous and nz.flags.c_contiguous
         self._call("batch_cycle_async", C.c_int(-1 if predict is None else (1 if predict else 0)), C.c_void_p(None), C.c_void_p(None), C.c_int(0),
+                   self._ptr(z), self._ptr(nz), C.c_int(1 if normalize else 0))
+
+    # -- a batch of FastSLAM filters ------------------------------------------------------------------------------------------
+    def batch_set_fastslam_config(self, b, cfg):
+        """rfsgpu_batch_set_fastslam_config: filter b's (None: every filter's) FastSlamConfig."""
+        self._call("batch_set_fastslam_config", C.c_int(-1 if b is None else int(b)), C.byref(cfg))
+
+    def batch_fastslam_cycle_async(self, predict, Zs, poses=None, pose_cov=None, normalize=True):
+        """rfsgpu_batch_fastslam_cycle_async: arguments as batch_cycle_async (predict None: no static landmark step)."""
+        self._cycle_call("batch_fastslam_cycle_async", predict, Zs, poses, pose_cov, normalize)
+
+    def batch_fastslam_cycle_async_packed(self, predict, z, nz, normalize=True):
+        """rfsgpu_batch_fastslam_cycle_async with the sets already in the call's layout and no new poses (as batch_cycle_async_packed)."""
+        assert z.dtype == np.float64 and nz.dtype == np.int32 and z.shape == (self.n_filters, MAX_Z, 2) and z.flags.c_contiguous and nz.flags.c_contiguous
+        self._call("batch_fastslam_cycle_async", C.c_int(-1 if predict is None else (1 if predict else 0)), C.c_void_p(None), C.c_void_p(None), C.c_int(0),
                    self._ptr(z), self._ptr(nz), C.c_int(1 if normalize else 0))
 
     def batch_weight_sums(self):

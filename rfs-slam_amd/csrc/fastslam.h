@@ -33,6 +33,27 @@ struct FsParams {
   unsigned countThr, curThr, checkThr;  // landmarkCandidateMeasurementCountThreshold_ / CurrentMeasurementCountThreshold_ / CheckThreshold_
 };
 
+// ---- a batch of FastSLAM filters (rfsgpu_batch_fastslam_cycle_async) ----------------------------------------------------------
+// The BATCH forms of the three update kernels take what a single handle passes as kernel arguments -- Params, FsParams, the measurement
+// set and its count -- from these device tables, per wave, for the filter of the particle it owns (particle / nPer), as the BATCH
+// instantiation of the fused step kernel does (step_fused.h).  The host writes them once per cycle.
+struct FsBatchFilter {
+  FsParams F;        // the filter's own fs_params(nZ): pfa computed on the host by the handle's expression
+  double pruneT;     // mapExistencePruneThreshold
+  int nZ;            // this cycle's measurements (0: no update, FastSLAM.hpp:402-403 -- the predict still runs)
+  int zOff;          // where its set starts in FsBatchArg::z (doubles)
+  int prune;         // nZ >= pruningMeasurementsThreshold: the prune runs for this filter (else its mixtures move unchanged)
+  int pad;
+};
+struct FsBatchArg {
+  const FsBatchFilter *filt;   // [nF]
+  const Params *params;        // [nF]
+  const double *z;             // this cycle's sets, packed (2 doubles per measurement)
+  int *errFilter;              // [1] lowest filter that ran out of gm_capacity (INT_MAX: none)
+  int nPer;
+  int predict;                 // FastSLAM::predict's static landmark step runs at the head of the associate kernel
+};
+
 #define FS_AMBIG_MAX 64    // rows / columns of ONE connected component of competing associations (the in-kernel Hungarian, MURTY_N)
 #define FS_AMBIG_ROWS 256  // rows with competing associations per particle, over all components
 #define FS_SMALL 12        // components up to this size are solved in LDS, larger ones in the particle's HBM scratch
@@ -187,18 +208,42 @@ __device__ __forceinline__ double fs_existence_step(const FsParams &F, double w,
   return w + log(pe / (1 - pe));
 }
 
-template <int WPB, int D>
-__global__ __launch_bounds__(WPB * 64) void fs_associate_update_kernel(Buffers B, Params P, FsParams F, int cur, int nZ, unsigned char *arena) {
-  extern __shared__ __align__(16) unsigned char smem_raw[];
-  __shared__ __align__(16) unsigned char sPdScratch[WPB][(D == 3) ? ((VP_PD_SCRATCH_BYTES + 15) & ~15) : 16];
+// LDS of the BATCH form: the single filter's layout, then one measurement set per wave (two waves of a workgroup may belong to
+// different filters)
+__host__ __device__ inline size_t fs_batch_lds_bytes(int cap, int wpb) {
+  return (size_t)(3 * RFSGPU_MAX_Z * 8) + (size_t)wpb * fs_lds_bytes_per_wave(cap) + (size_t)wpb * (2 * RFSGPU_MAX_Z * 8);
+}
+// The kernel's body, shared by the single filter's kernel and the batch's: BATCH reads the wave's filter from the tables of A (Parg,
+// Farg and nZarg are ignored), runs the static landmark step of FastSLAM::predict at its head when asked, and stops there for a
+// filter without measurements.  Everything else is one code path: the same expressions on the same values.
+template <int WPB, int D, bool BATCH>
+__device__ __forceinline__ void fs_associate_update_body(const Buffers &B, const Params &Parg, const FsParams &Farg, const int cur, const int nZarg, unsigned char *arena,
+                                                         unsigned char *smem_raw, unsigned char *pdScratch, const FsBatchArg &A) {
   double *sZ = reinterpret_cast<double *>(smem_raw);
   const int wave = threadIdx.x >> 6;
   const int lane = threadIdx.x & 63;
-  for (int t = threadIdx.x; t < D * nZ; t += WPB * 64) sZ[t] = B.Z[t];
-  __syncthreads();
+  int nZ = nZarg, bf = 0;
+  if constexpr (!BATCH) {
+    for (int t = threadIdx.x; t < D * nZ; t += WPB * 64) sZ[t] = B.Z[t];
+    __syncthreads();
+  }
   const int i = __builtin_amdgcn_readfirstlane(blockIdx.x * WPB + wave);
   if (i >= B.N) return;
+  if constexpr (BATCH) bf = __builtin_amdgcn_readfirstlane(i / A.nPer);
+  const Params &P = [&]() -> const Params & { if constexpr (BATCH) return A.params[bf]; else return Parg; }();
+  const FsParams &F = [&]() -> const FsParams & { if constexpr (BATCH) return A.filt[bf].F; else return Farg; }();
   const int cap = B.cap, LCAP = 2 * cap;
+  if constexpr (BATCH) {
+    nZ = __builtin_amdgcn_readfirstlane(A.filt[bf].nZ);
+    // FastSLAM::predict (:376-383): Sigma += Q on every landmark, no births; also for a filter whose scan is empty.  The lane that
+    // adds Q to an entry is the lane that reads it below (entry m belongs to lane m & 63 in both loops).
+    if (A.predict) predict_map_particle<64>(B, P, cur, i, lane, false, 0, B.pose, true);
+    if (nZ == 0) return;
+    sZ = reinterpret_cast<double *>(smem_raw + 3 * RFSGPU_MAX_Z * 8 + (size_t)WPB * fs_lds_bytes_per_wave(cap)) + (size_t)wave * (2 * RFSGPU_MAX_Z);
+    const double *zs = A.z + A.filt[bf].zOff;
+    for (int t = lane; t < D * nZ; t += 64) sZ[t] = zs[t];
+    wave_sync();
+  }
   unsigned char *wb = smem_raw + 3 * RFSGPU_MAX_Z * 8 + (size_t)wave * fs_lds_bytes_per_wave(cap);
   double *sPd = reinterpret_cast<double *>(wb);                    // [cap] Pd of in-range row k
   double *sC = sPd + cap;                                           // [cap] log-weight contribution of row k
@@ -233,7 +278,7 @@ __global__ __launch_bounds__(WPB * 64) void fs_associate_update_kernel(Buffers B
     const int m = c0 + lane;
     const bool act = m < nM;
     FsRow<D> row;
-    fs_row<D>(B, P, pr, slab, cap, i, m, act, row, sPdScratch[wave]);
+    fs_row<D>(B, P, pr, slab, cap, i, m, act, row, pdScratch);
     const double pd = row.pd;
     const bool inR = act && (pd != 0 || row.close);  // :446
     unsigned long long cells = 0;
@@ -267,7 +312,10 @@ __global__ __launch_bounds__(WPB * 64) void fs_associate_update_kernel(Buffers B
     nList += total;
   }
   if (__ballot(overflow) != 0ull) {
-    if (lane == 0) atomicOr(B.err, ERRBIT_CAPACITY);
+    if (lane == 0) {
+      atomicOr(B.err, ERRBIT_CAPACITY);
+      if constexpr (BATCH) atomicMin(A.errFilter, bf);
+    }
     nList = LCAP;
   }
   wave_sync();
@@ -439,6 +487,26 @@ __global__ __launch_bounds__(WPB * 64) void fs_associate_update_kernel(Buffers B
     B.nInFov[i] = nUpd;
   }
 }
+template <int WPB, int D>
+__global__ __launch_bounds__(WPB * 64) void fs_associate_update_kernel(Buffers B, Params P, FsParams F, int cur, int nZ, unsigned char *arena) {
+  extern __shared__ __align__(16) unsigned char smem_raw[];
+  __shared__ __align__(16) unsigned char sPdScratch[WPB][(D == 3) ? ((VP_PD_SCRATCH_BYTES + 15) & ~15) : 16];
+  fs_associate_update_body<WPB, D, false>(B, P, F, cur, nZ, arena, smem_raw, sPdScratch[threadIdx.x >> 6], FsBatchArg{});
+}
+// The batch's form (2-D only): launched over all slots of the batch, LDS fs_batch_lds_bytes(cap, WPB).
+template <int WPB>
+__global__ __launch_bounds__(WPB * 64) void fs_associate_update_batch_kernel(Buffers B, int cur, unsigned char *arena, FsBatchArg A) {
+  extern __shared__ __align__(16) unsigned char smem_raw[];
+  __shared__ __align__(16) unsigned char sPdScratch[WPB][16];
+  fs_associate_update_body<WPB, 2, true>(B, A.params[0], A.filt[0].F, cur, 0, arena, smem_raw, sPdScratch[threadIdx.x >> 6], A);
+}
+// Each filter's weights after its update: {sum w, sum w^2} and the division by the sum, in the order of rfsgpu_batch_weight_sums and of
+// the RB-PHD batch's post kernel (step_post_tail).  A filter without measurements keeps its weights (no normalisation, :402-403).
+__global__ __launch_bounds__(256) void fs_batch_post_kernel(double *weight, FsBatchArg A, double *sums, int normalize, int *resampled) {
+  if (A.filt[blockIdx.x].nZ <= 0) return;     // (workgroup-uniform)
+  if (resampled && threadIdx.x == 0) resampled[blockIdx.x] = 0;   // resampleOccured_ falls with an update (the device route's flag)
+  step_post_tail(weight + (size_t)blockIdx.x * A.nPer, A.nPer, sums + 2 * blockIdx.x, normalize);
+}
 
 // GaussianMixture::addGaussian(candidate, w, true) (:267-284) -- no process noise here (the update adds none)
 template <int D>
@@ -470,18 +538,36 @@ __device__ inline bool fs_append(const Buffers &B, int cur, int i, int &n, const
 // reference's order -- measurements in index order, first supporting candidate in list order, the promotion loop once per
 // unassociated measurement with its ++end() wrap).
 #define FS_NEWLM_WPB 4
-template <int D>
-__global__ __launch_bounds__(64 * FS_NEWLM_WPB) void fs_new_landmarks_kernel(Buffers B, Params P, FsParams F, int cur, int nZ) {
+// BATCH: one more argument, the FsBatchArg tables; the wave reads its filter's Params, FsParams, nZ and measurement set there and
+// stops when the filter has no measurements.  The other instantiations take no such argument and compile as before.
+template <int D, bool BATCH = false, typename... TBatch>
+__global__ __launch_bounds__(64 * FS_NEWLM_WPB) void fs_new_landmarks_kernel(Buffers B, Params P, FsParams F, int cur, int nZ, TBatch... batchArg) {
   const int wave = threadIdx.x >> 6;
   const int lane = threadIdx.x & 63;
   const int i = __builtin_amdgcn_readfirstlane(blockIdx.x * FS_NEWLM_WPB + wave);
   if (i >= B.N) return;
+  // The filter's Params and measurement set are read in place (Pb, Zb) where the single filter reads its kernel arguments: copied
+  // into the arguments they went to scratch (169 VGPRs + 168 B per lane), and read through one reference for both forms the single
+  // filter's instantiations moved by two VGPRs.  FsParams is small and is copied.
+  [[maybe_unused]] int bf = 0;
+  [[maybe_unused]] const Params *Pb = nullptr;
+  [[maybe_unused]] const double *Zb = nullptr;
+  if constexpr (BATCH) {
+    const auto &A = batch_first_arg(batchArg...);
+    bf = __builtin_amdgcn_readfirstlane(i / A.nPer);
+    nZ = __builtin_amdgcn_readfirstlane(A.filt[bf].nZ);
+    if (nZ == 0) return;     // no update for this filter this cycle
+    Pb = A.params + bf;
+    Zb = A.z + A.filt[bf].zOff;
+    F = A.filt[bf].F;
+  }
   int n = B.count[i];
   int nc = B.candCount[i];
   const int cap = B.cap;
   const unsigned nfov = (unsigned)B.nInFov[i];
   PoseReg pr;
-  load_pose(B, P, i, pr);
+  if constexpr (BATCH) load_pose(B, *Pb, i, pr);
+  else load_pose(B, P, i, pr);
   bool fail = false, listFull = false;
   int *supG = B.candSup + (size_t)i * RFSGPU_MAX_CANDIDATES, *chkG = B.candChk + (size_t)i * RFSGPU_MAX_CANDIDATES;
   Cand<D> k;
@@ -494,14 +580,18 @@ __global__ __launch_bounds__(64 * FS_NEWLM_WPB) void fs_new_landmarks_kernel(Buf
   for (int zi = 0; zi < nZ; zi++) {  // measurements in index order (:615)
     if (!((um >> zi) & 1ull)) continue;
     const double *z = B.Z + (size_t)D * zi;
+    if constexpr (BATCH) z = Zb + (size_t)D * zi;
     double d2 = 1.0e300;
-    if (lane < nc) d2 = cand_support_md2<D>(P, pr, k, z);
+    if constexpr (BATCH) { if (lane < nc) d2 = cand_support_md2<D>(*Pb, pr, k, z); }
+    else if (lane < nc) d2 = cand_support_md2<D>(P, pr, k, z);
     const unsigned long long hit = __ballot(lane < nc && d2 <= F.supportD2);
     if (hit != 0ull) {
-      if (lane == __builtin_ctzll(hit)) { cand_correct<D>(P, pr, k, z); sup++; }
+      if constexpr (BATCH) { if (lane == __builtin_ctzll(hit)) { cand_correct<D>(*Pb, pr, k, z); sup++; } }
+      else if (lane == __builtin_ctzll(hit)) { cand_correct<D>(P, pr, k, z); sup++; }
     } else {
       Cand<D> kn;
-      cand_inverse<D>(P, pr, z, kn);
+      if constexpr (BATCH) cand_inverse<D>(*Pb, pr, z, kn);
+      else cand_inverse<D>(P, pr, z, kn);
       if (F.countThr == 1u || nfov <= F.curThr) {
         if (n < cap) { if (lane == 0) { int nn = n; fs_append<D>(B, cur, i, nn, kn, F.newW); } n++; }
         else fail = true;
@@ -545,7 +635,10 @@ __global__ __launch_bounds__(64 * FS_NEWLM_WPB) void fs_new_landmarks_kernel(Buf
     B.unusedMask[i] = 0ull;
     B.candCount[i] = nc;
     B.count[i] = n;
-    if (fail) atomicOr(B.err, ERRBIT_CAPACITY);
+    if (fail) {
+      atomicOr(B.err, ERRBIT_CAPACITY);
+      if constexpr (BATCH) atomicMin(batch_first_arg(batchArg...).errFilter, bf);
+    }
     if (listFull) atomicOr(B.err, ERRBIT_BIRTHLIST);
   }
 }

@@ -44,6 +44,7 @@ struct MetricArg {
   int nPer;                // particles per filter
   int havePose;            // 0: pose fields NaN
   int holes;               // merged-away entries (w < 0) sit in the slab: skip them
+  int logOdds;             // a FastSLAM batch: a Gaussian's weight is the log-odds of existence; the estimate's weight is 1 - 1 / (1 + exp(w))
 };
 
 // (wave_min_f64: hungarian_wave.h -- DPP moves, the result in every lane)
@@ -97,7 +98,8 @@ __global__ __launch_bounds__(64) void map_metric_kernel(Buffers B, int cur, Metr
   for (int base = 0; base < cnt; base += 64) {
     const int m = base + lane;
     bool valid = m < cnt;
-    const double w = valid ? pw[m] : 0.0;
+    double w = valid ? pw[m] : 0.0;
+    if (A.logOdds) w = valid ? 1 - 1 / (1 + exp(w)) : 0.0;   // what fastslam2dSim.cpp:628 logs and analysis2dSim thresholds
     if (A.holes && w < 0) valid = false;
     if (valid) card += w;
     const bool keep = valid && w >= A.wThr;

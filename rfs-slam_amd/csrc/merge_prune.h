@@ -1071,13 +1071,34 @@ __host__ __device__ inline size_t gm_prune_lds_bytes_per_wave(int cap) {
 // NEG_IS_HOLE: the RB-PHD mixtures mark merged-away entries with w = -1; FastSLAM's log-odds weights are legitimately negative.
 // GaussianMixture::prune (include/GaussianMixture.hpp:477-534): std::sort of the whole list by weight, the sorted prefix with
 // w >= t stays.  Ranks by counting (ties by index), then equal weights in std::sort's order (stdsort_replay.h).
-template <int WPB, bool NEG_IS_HOLE = true>
-__global__ __launch_bounds__(WPB * 64) void gm_prune_kernel(Buffers B, Params P, int src, int dst) {
+// BATCH (a FastSLAM filter batch, fastslam.h): one more argument, the FsBatchArg tables.  The wave's filter prunes with its own threshold
+// when it has measurements and its gate says so; else its mixture moves unchanged to dst, because the batch flips `cur` as one.  The
+// other instantiations take no such argument and compile as before: every difference is behind `if constexpr`.
+// What this kernel reads of the argument (FsBatchArg, fastslam.h, which is included after this file): nPer, the particles per filter,
+// and of filt[particle / nPer] the fields nZ (this cycle's measurements), prune (the filter's gate) and pruneT (its threshold).
+template <typename T>
+__device__ __forceinline__ const T &batch_first_arg(const T &a) { return a; }
+template <int WPB, bool NEG_IS_HOLE = true, bool BATCH = false, typename... TBatch>
+__global__ __launch_bounds__(WPB * 64) void gm_prune_kernel(Buffers B, Params P, int src, int dst, TBatch... batchArg) {
   extern __shared__ __align__(16) unsigned char smem_raw[];
   const int wave = threadIdx.x >> 6;
   const int lane = threadIdx.x & 63;
   const int i = __builtin_amdgcn_readfirstlane(blockIdx.x * WPB + wave);
   if (i >= B.N) return;
+  if constexpr (BATCH) {
+    const auto &A = batch_first_arg(batchArg...);
+    const auto &T = A.filt[__builtin_amdgcn_readfirstlane(i / A.nPer)];
+    if (!(__builtin_amdgcn_readfirstlane(T.nZ) > 0 && __builtin_amdgcn_readfirstlane(T.prune))) {
+      const int n = B.count[i];
+      for (int pl = 0; pl < B.npl; pl++) {
+        const double *s = B.slab[src] + ((size_t)i * B.npl + pl) * B.cap;
+        double *d = B.slab[dst] + ((size_t)i * B.npl + pl) * B.cap;
+        for (int m = lane; m < n; m += 64) d[m] = s[m];
+      }
+      return;
+    }
+    P.pruneT = T.pruneT;
+  }
   const int cap = B.cap;
   unsigned char *base = smem_raw + (size_t)wave * gm_prune_lds_bytes_per_wave(cap);
   double *keys = reinterpret_cast<double *>(base);

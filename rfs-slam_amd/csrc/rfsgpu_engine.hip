@@ -185,6 +185,11 @@ struct rfsgpu_filter {
   unsigned char *hBLoop[8] = {};               // pinned ring of the two calls' per-filter inputs
   hipEvent_t evBLoop[8] = {};
   int bLoopNext = 0;
+  // a batch of FastSLAM filters (rfsgpu_batch_fastslam_cycle_async; fastslam.h FsBatchArg)
+  int bKind = 0;                               // what the batch steps: 0 not decided yet, 1 RB-PHD filters, 2 FastSLAM filters (the first cycle call decides)
+  std::vector<rfsgpu_fastslam_config> bFs;     // [nF]
+  std::vector<Params> bParamsHost;             // [nF] the device Params table as last written (each filter's pfa comes from its own model)
+  FsBatchFilter *dFsFilt = nullptr;            // [nF]
   // [metric] per-step map / pose error (map_metric.h): ground truth per filter, the device-side log, one row for the synchronous calls
   double *dGtXY = nullptr, *dGtSeen = nullptr;   // [nF][RFSGPU_MAX_METRIC_SET][2], [nF][RFSGPU_MAX_METRIC_SET] (allocated by the first rfsgpu_set_ground_truth)
   int *dGtN = nullptr;                           // [nF]
@@ -440,6 +445,7 @@ void rfsgpu_destroy(rfsgpu_filter *f) {
   murty_free(f->Q, f->MS);
   hipFree(f->dBFilt); hipFree(f->dBParams); hipFree(f->dBZ); hipFree(f->dBZPrev); hipFree(f->dBSums); hipFree(f->dBErrFilter); hipFree(f->dBMaskTmp); hipFree(f->dBInhSrc);
   for (int k = 0; k < 4; k++) { if (f->hBStage[k]) hipHostFree(f->hBStage[k]); if (f->evBStage[k]) hipEventDestroy(f->evBStage[k]); }
+  hipFree(f->dFsFilt);
   hipFree(f->dBMotion); hipFree(f->dBPropIn); hipFree(f->dBResIn); hipFree(f->BL.counters); hipFree(f->BL.nResamples); hipFree(f->BL.resampled);
   hipFree(f->BL.fired); hipFree(f->BL.nEff); hipFree(f->BL.plan); hipFree(f->BL.pid); hipFree(f->BL.ppid);
   for (int k = 0; k < 8; k++) { if (f->hBLoop[k]) hipHostFree(f->hBLoop[k]); if (f->evBLoop[k]) hipEventDestroy(f->evBLoop[k]); }
@@ -2346,19 +2352,24 @@ int rfsgpu_get_fastslam_config(const rfsgpu_filter *f, rfsgpu_fastslam_config *c
   *cfg = f->fs;
   return RFSGPU_OK;
 }
-static FsParams fs_params(const rfsgpu_filter *f, int n_z) {
+// (one expression for a handle and for every filter of a batch: a filter's bits do not depend on being in a batch)
+static FsParams fs_params_of(const rfsgpu_fastslam_config &fs, const Params &P, int D, int n_z) {
   FsParams F;
-  F.prior = f->fs.landmarkExistencePrior;
-  F.minLog = f->fs.minLogMeasurementLikelihood;
-  F.lockW = f->fs.landmarkLockWeight;
+  F.prior = fs.landmarkExistencePrior;
+  F.minLog = fs.minLogMeasurementLikelihood;
+  F.lockW = fs.landmarkLockWeight;
   // clutterIntensityIntegral(nZ) / nZ (:561-562): c * sensing area (RngBrg.cpp:175-178) or the expected clutter number (VictoriaPark)
-  F.pfa = ((f->D == 2) ? f->P.clutter * (2 * RFS_PI * (f->P.rmax - f->P.rmin)) : f->P.vpExpClutter) / n_z;
+  F.pfa = ((D == 2) ? P.clutter * (2 * RFS_PI * (P.rmax - P.rmin)) : P.vpExpClutter) / n_z;
   F.newW = log(F.prior / (1 - F.prior));
-  F.supportD2 = f->fs.landmarkCandidateMeasurementSupportDist * f->fs.landmarkCandidateMeasurementSupportDist;
-  F.countThr = f->fs.landmarkCandidateMeasurementCountThreshold;
+  F.supportD2 = fs.landmarkCandidateMeasurementSupportDist * fs.landmarkCandidateMeasurementSupportDist;
+  F.countThr = fs.landmarkCandidateMeasurementCountThreshold;
+  F.curThr = fs.landmarkCandidateCurrentMeasurementCountThreshold;
+  F.checkThr = fs.landmarkCandidateMeasurementCheckThreshold;
+  return F;
+}
+static FsParams fs_params(const rfsgpu_filter *f, int n_z) {
+  const FsParams F = fs_params_of(f->fs, f->P, f->D, n_z);
   if (F.countThr != 1u) const_cast<rfsgpu_filter *>(f)->candUsed = true;   // (migration rows carry the lists from now on)
-  F.curThr = f->fs.landmarkCandidateCurrentMeasurementCountThreshold;
-  F.checkThr = f->fs.landmarkCandidateMeasurementCheckThreshold;
   return F;
 }
 // prune by the existence threshold (:611-612) + new landmarks / candidates (:615-690) over all f->N particles
@@ -2601,7 +2612,7 @@ static Params batch_params(rfsgpu_filter *f, int b) {
   return out;
 }
 static size_t batch_stage_bytes(const rfsgpu_filter *f) {
-  return (size_t)f->nF * (sizeof(BatchFilter) + sizeof(Params) + RFSGPU_MAX_Z * 2 * sizeof(double) + sizeof(int)) + (size_t)f->N * sizeof(int);
+  return (size_t)f->nF * (std::max(sizeof(BatchFilter), sizeof(FsBatchFilter)) + sizeof(Params) + RFSGPU_MAX_Z * 2 * sizeof(double) + sizeof(int)) + (size_t)f->N * sizeof(int);
 }
 // One slot of the batch's pinned ring (as stage_slot): waits until the copies issued from it four cycles ago are done.
 static int batch_stage(rfsgpu_filter *f, unsigned char **h, int *k_out) {
@@ -2615,6 +2626,17 @@ static int batch_stage(rfsgpu_filter *f, unsigned char **h, int *k_out) {
   *h = f->hBStage[k];
   *k_out = k;
   return RFSGPU_OK;
+}
+// The handle-wide Params fields of a cycle (both kinds of batch): the pose covariance stride the call's x / x_cov ask for, and whatever
+// else of f->P every filter's record repeats; the table is rewritten when one of them has changed.
+static void batch_handle_wide(rfsgpu_filter *f, const double *x, const double *x_cov, int cov_stride) {
+  if (x) {
+    const int stride = x_cov ? cov_stride : 0;
+    if (f->P.poseCovStride != stride) { f->P.poseCovStride = stride; f->bParamsDirty = true; }
+  }
+  const int hw[3] = {f->P.poseCovStride, f->P.exactPartitions, f->P.denseIntensity};
+  for (int q = 0; q < 3; q++)
+    if (hw[q] != f->bHandleWide[q]) { f->bHandleWide[q] = hw[q]; f->bParamsDirty = true; }
 }
 static int batch_check(rfsgpu_filter *f, int filter) {
   if (!f->batch) return fail(f, RFSGPU_ERR_INVALID, "not a filter batch (rfsgpu_create_batch)");
@@ -2636,10 +2658,14 @@ int rfsgpu_create_batch(rfsgpu_filter **out, int model, int n_filters, int n_per
   f->bCfg.resize(n_filters); f->bRb.resize(n_filters); f->bKf.resize(n_filters); f->bQ.assign((size_t)9 * n_filters, 0.0);
   f->bNZ.assign(n_filters, 0);
   f->bResampled.assign(n_filters, 0);
+  f->bFs.resize(n_filters);
+  for (auto &c : f->bFs) rfsgpu_default_fastslam_config(&c);
+  f->bParamsHost.resize(n_filters);
   batch_set_all(f);
   bool ok = true;
   ok &= hipMalloc(&f->dBFilt, (size_t)n_filters * sizeof(BatchFilter)) == hipSuccess;
   ok &= hipMalloc(&f->dBParams, (size_t)n_filters * sizeof(Params)) == hipSuccess;
+  ok &= hipMalloc(&f->dFsFilt, (size_t)n_filters * sizeof(FsBatchFilter)) == hipSuccess;
   ok &= hipMalloc(&f->dBZ, (size_t)n_filters * RFSGPU_MAX_Z * 2 * sizeof(double)) == hipSuccess;
   ok &= hipMalloc(&f->dBZPrev, (size_t)n_filters * RFSGPU_MAX_Z * 2 * sizeof(double)) == hipSuccess;
   ok &= hipMalloc(&f->dBSums, (size_t)n_filters * 2 * sizeof(double)) == hipSuccess;
@@ -2712,6 +2738,9 @@ int rfsgpu_batch_cycle_async(rfsgpu_filter *f, int predict, const double *x, con
       return fail(f, RFSGPU_ERR_UNSUPPORTED, "batch_cycle: a filter batch takes immediate births only (birthGaussianMeasurementCountThreshold 1)");
     nZmax = std::max(nZmax, n_z[b]);
   }
+  if (f->bKind == 2)
+    return fail(f, RFSGPU_ERR_UNSUPPORTED, "batch_cycle: this batch steps FastSLAM filters (rfsgpu_batch_set_fastslam_config or rfsgpu_batch_fastslam_cycle_async has run): a batch is of one kind");
+  f->bKind = 1;
   hipSetDevice(f->device);
   long long t0 = now_ns();
   // pose covariance stride: handle-wide, as rfsgpu_cycle_async sets it
@@ -2856,6 +2885,123 @@ int rfsgpu_batch_cycle_async(rfsgpu_filter *f, int predict, const double *x, con
   if (murty_launch_batch(f->Q, f->MS, f->B, f->stream, A, normalize, f->hJobCount, sord) != 0) return fail(f, RFSGPU_ERR_HIP, "batch post kernel launch failed");
   if (ks >= 0) HIPCHK(hipEventRecord(f->evStage[ks], f->stream));   // the pinned input slot is free once the step kernel has read it
   f->cur ^= 1;   // (filters without an update had their mixture moved to the new slab by the step kernel)
+  for (int b = 0; b < nF; b++)
+    if (n_z[b] > 0) { f->bNZ[b] = n_z[b]; f->bResampled[b] = 0; }
+  f->holes = false;
+  f->timing.mapUpdate_cpu += now_ns() - t0;
+  return RFSGPU_OK;
+}
+// ---- a batch of FastSLAM filters: FastSLAM::predict's map part + the single-hypothesis FastSLAM::update (include/FastSLAM.hpp:376-383,
+// :387-706) of every filter in one launch chain -- [predict] -> associate + Kalman update + weights -> prune -> new landmarks -> per-filter
+// sums / division.  Nothing synchronises: errors reach the host through the shared error word, as with rfsgpu_batch_cycle_async.
+int rfsgpu_batch_set_fastslam_config(rfsgpu_filter *f, int filter, const rfsgpu_fastslam_config *cfg) {
+  CHECK_HANDLE(f);
+  int rc = batch_check(f, filter);
+  if (rc != RFSGPU_OK) return rc;
+  if (!cfg) return fail(f, RFSGPU_ERR_INVALID, "batch_set_fastslam_config: null configuration");
+  const std::string who = filter < 0 ? std::string("every filter") : "filter " + std::to_string(filter);
+  if (cfg->maxNDataAssocHypotheses != 1u) {
+    f->err = "batch_set_fastslam_config: " + who + ": maxNDataAssocHypotheses must be 1 on a filter batch (the multi-hypothesis update grows the particle set)";
+    return RFSGPU_ERR_UNSUPPORTED;
+  }
+  if (cfg->landmarkCandidateMeasurementCountThreshold != 1u) {
+    f->err = "batch_set_fastslam_config: " + who + ": landmarkCandidateMeasurementCountThreshold must be 1 on a filter batch (landmark candidate lists would have to travel with a resampling)";
+    return RFSGPU_ERR_UNSUPPORTED;
+  }
+  if (f->bKind == 1)
+    return fail(f, RFSGPU_ERR_UNSUPPORTED, "batch_set_fastslam_config: this batch steps RB-PHD filters (rfsgpu_batch_cycle_async has run): a batch is of one kind");
+  for (int b = (filter < 0 ? 0 : filter); b < (filter < 0 ? f->nF : filter + 1); b++) f->bFs[b] = *cfg;
+  f->bKind = 2;      // a FastSLAM batch from here on: the [metric] calls read the Gaussians' weights as log-odds
+  return RFSGPU_OK;
+}
+int rfsgpu_batch_fastslam_cycle_async(rfsgpu_filter *f, int predict, const double *x, const double *x_cov, int cov_stride, const double *z, const int *n_z,
+                                      int normalize) {
+  CHECK_HANDLE(f);
+  int rc = batch_check(f, -1);
+  if (rc != RFSGPU_OK) return rc;
+  if (predict < -1 || predict > 1) return fail(f, RFSGPU_ERR_INVALID, "batch_fastslam_cycle: predict is RFSGPU_CYCLE_NO_PREDICT (-1), or 0 / 1 (the static landmark step; FastSLAM has no births)");
+  if (x_cov && cov_stride != 0 && cov_stride != 9) return fail(f, RFSGPU_ERR_INVALID, "batch_fastslam_cycle: cov_stride must be 0 or 9");
+  if (!n_z) return fail(f, RFSGPU_ERR_INVALID, "batch_fastslam_cycle: null measurement counts");
+  const int nF = f->nF;
+  for (int b = 0; b < nF; b++) {
+    if (n_z[b] < 0 || n_z[b] > RFSGPU_MAX_Z) {
+      f->err = "batch_fastslam_cycle: filter " + std::to_string(b) + " has " + std::to_string(n_z[b]) + " measurements (0 ... RFSGPU_MAX_Z)";
+      return RFSGPU_ERR_INVALID;
+    }
+    if (n_z[b] > 0 && !z) return fail(f, RFSGPU_ERR_INVALID, "batch_fastslam_cycle: null measurement buffer");
+  }
+  if (f->bKind == 1)
+    return fail(f, RFSGPU_ERR_UNSUPPORTED, "batch_fastslam_cycle: this batch steps RB-PHD filters (rfsgpu_batch_cycle_async has run): a batch is of one kind");
+  f->bKind = 2;
+  hipSetDevice(f->device);
+  long long t0 = now_ns();
+  if (!f->fsArena) HIPCHK(hipMalloc(&f->fsArena, (size_t)f->Ncap * fs_arena_bytes()));   // the Hungarian scratch of every slot of the batch, once
+  batch_handle_wide(f, x, x_cov, cov_stride);
+  // per-cycle tables into a slot of the pinned ring, then to the device
+  unsigned char *h = nullptr;
+  int kb = 0;
+  if ((rc = batch_stage(f, &h, &kb)) != RFSGPU_OK) return rc;
+  FsBatchFilter *hf = reinterpret_cast<FsBatchFilter *>(h);
+  Params *hp = reinterpret_cast<Params *>(h + (size_t)nF * sizeof(FsBatchFilter));
+  double *hz = reinterpret_cast<double *>(h + (size_t)nF * (sizeof(FsBatchFilter) + sizeof(Params)));
+  if (f->bParamsDirty) {
+    for (int b = 0; b < nF; b++) hp[b] = f->bParamsHost[b] = batch_params(f, b);
+    HIPCHK(hipMemcpyAsync(f->dBParams, hp, (size_t)nF * sizeof(Params), hipMemcpyHostToDevice, f->stream));
+    f->bParamsDirty = false;
+  }
+  int zOff = 0;
+  for (int b = 0; b < nF; b++) {
+    FsBatchFilter &T = hf[b];
+    memset(&T, 0, sizeof T);
+    T.F = fs_params_of(f->bFs[b], f->bParamsHost[b], 2, n_z[b]);
+    T.pruneT = f->bFs[b].mapExistencePruneThreshold;
+    T.nZ = n_z[b];
+    T.zOff = zOff;
+    T.prune = ((unsigned)n_z[b] >= f->bFs[b].pruningMeasurementsThreshold) ? 1 : 0;
+    if (n_z[b] > 0) memcpy(hz + zOff, z + (size_t)b * RFSGPU_MAX_Z * 2, (size_t)n_z[b] * 2 * sizeof(double));
+    zOff += 2 * n_z[b];
+  }
+  HIPCHK(hipMemcpyAsync(f->dFsFilt, hf, (size_t)nF * sizeof(FsBatchFilter), hipMemcpyHostToDevice, f->stream));
+  if (zOff) HIPCHK(hipMemcpyAsync(f->dBZ, hz, (size_t)zOff * sizeof(double), hipMemcpyHostToDevice, f->stream));
+  HIPCHK(hipEventRecord(f->evBStage[kb], f->stream));
+  // the host's new poses / covariances through a slot of the staging ring
+  if (x) {
+    double *hx = nullptr;
+    int ks = -1;
+    if ((rc = stage_slot(f, &hx, &ks)) != RFSGPU_OK) return rc;
+    memcpy(hx, x, (size_t)f->N * 3 * sizeof(double));
+    HIPCHK(hipMemcpyAsync(f->B.pose, hx, (size_t)f->N * 3 * sizeof(double), hipMemcpyHostToDevice, f->stream));
+    double *hc = hx + (size_t)f->Ncap * 3;
+    if (x_cov) {
+      const size_t n = cov_stride == 9 ? (size_t)f->N * 9 : 9;
+      memcpy(hc, x_cov, n * sizeof(double));
+      HIPCHK(hipMemcpyAsync(f->B.poseCov, hc, n * sizeof(double), hipMemcpyHostToDevice, f->stream));
+      f->poseCovZero = false;
+    } else if (!f->poseCovZero) {
+      memset(hc, 0, 9 * sizeof(double));
+      HIPCHK(hipMemcpyAsync(f->B.poseCov, hc, 9 * sizeof(double), hipMemcpyHostToDevice, f->stream));
+      f->poseCovZero = true;
+    }
+    HIPCHK(hipEventRecord(f->evStage[ks], f->stream));
+  }
+  f->bBirthAlt = false;      // (no births here: the poses from before a propagation are not needed)
+  FsBatchArg A{f->dFsFilt, f->dBParams, f->dBZ, f->dBErrFilter, f->nPer, predict >= 0 ? 1 : 0};
+  const size_t b2 = fs_batch_lds_bytes(f->cap, 2), b1 = fs_batch_lds_bytes(f->cap, 1);
+  if (b2 <= 64 * 1024) {      // (the single handle's rule)
+    if ((rc = set_lds(f, (fs_associate_update_batch_kernel<2>), b2)) != RFSGPU_OK) return rc;
+    fs_associate_update_batch_kernel<2><<<(f->N + 1) / 2, 128, b2, f->stream>>>(f->B, f->cur, f->fsArena, A);
+  } else {
+    if ((rc = set_lds(f, (fs_associate_update_batch_kernel<1>), b1)) != RFSGPU_OK) return rc;
+    fs_associate_update_batch_kernel<1><<<f->N, 64, b1, f->stream>>>(f->B, f->cur, f->fsArena, A);
+  }
+  HIPCHK(hipGetLastError());
+  const size_t pb = gm_prune_lds_bytes_per_wave(f->cap);
+  if ((rc = set_lds(f, (gm_prune_kernel<4, false, true, FsBatchArg>), 4 * pb)) != RFSGPU_OK) return rc;
+  gm_prune_kernel<4, false, true, FsBatchArg><<<(f->N + 3) / 4, 256, 4 * pb, f->stream>>>(f->B, f->P, f->cur, f->cur ^ 1, A);
+  f->cur ^= 1;     // (filters that do not prune this cycle had their mixtures moved to the new slab)
+  fs_new_landmarks_kernel<2, true, FsBatchArg><<<(f->N + FS_NEWLM_WPB - 1) / FS_NEWLM_WPB, 64 * FS_NEWLM_WPB, 0, f->stream>>>(f->B, f->P, FsParams{}, f->cur, 0, A);
+  fs_batch_post_kernel<<<nF, 256, 0, f->stream>>>(f->B.weight, A, f->dBSums, normalize, f->bDevRoute ? f->BL.resampled : nullptr);
+  HIPCHK(hipGetLastError());
   for (int b = 0; b < nF; b++)
     if (n_z[b] > 0) { f->bNZ[b] = n_z[b]; f->bResampled[b] = 0; }
   f->holes = false;
@@ -3087,7 +3233,8 @@ int rfsgpu_batch_resample_async(rfsgpu_filter *f, const int *n_z, unsigned long 
     BatchResIn &I = hi[b];
     I.effN = f->bEffN[2 * (size_t)b]; I.effNPercent = f->bEffN[2 * (size_t)b + 1];
     I.nZ = n_z[b];
-    I.minUpdates = f->bCfg[b].minUpdatesBeforeResample; I.minMeasurements = f->bCfg[b].minMeasurementsBeforeResample;
+    if (f->bKind == 2) { I.minUpdates = (int)f->bFs[b].minUpdatesBeforeResample; I.minMeasurements = (int)f->bFs[b].minMeasurementsBeforeResample; }   // (a FastSLAM batch: FastSLAM.hpp:729-733)
+    else { I.minUpdates = f->bCfg[b].minUpdatesBeforeResample; I.minMeasurements = f->bCfg[b].minMeasurementsBeforeResample; }
     I.pad = 0;
   }
   HIPCHK(hipMemcpyAsync(f->dBResIn, hi, (size_t)nF * sizeof(BatchResIn), hipMemcpyHostToDevice, f->stream));
@@ -3145,7 +3292,7 @@ int rfsgpu_batch_resample_counts(rfsgpu_filter *f, long long *out) {
 static int metric_check(rfsgpu_filter *f, const char *what) {
   const char *why = f->D != 2 ? "the Victoria Park model" : (f->fastSlamHandle ? "a FastSLAM handle" : (f->groupShard ? "a shard of an rfsgpu_group" : nullptr));
   if (!why) return RFSGPU_OK;
-  f->err = std::string(what) + ": the device-side map / pose error serves ordinary 2-D RB-PHD handles and filter batches only, not " + why;
+  f->err = std::string(what) + ": the device-side map / pose error serves ordinary 2-D RB-PHD handles and filter batches (RB-PHD or FastSLAM) only, not " + why;
   return RFSGPU_ERR_UNSUPPORTED;
 }
 static inline int metric_nf(const rfsgpu_filter *f) { return f->batch ? f->nF : 1; }
@@ -3160,7 +3307,7 @@ static int metric_launch(rfsgpu_filter *f, const double *t, const double *gt_pos
     h[4 * b] = t ? t[b] : 0.0;
     for (int q = 0; q < 3; q++) h[4 * b + 1 + q] = gt_pose ? gt_pose[3 * b + q] : 0.0;
   }
-  MetricArg A{h, f->dGtXY, f->dGtSeen, f->dGtN, row, w_threshold, cutoff, order, f->batch ? f->nPer : f->N, gt_pose ? 1 : 0, f->holes ? 1 : 0};
+  MetricArg A{h, f->dGtXY, f->dGtSeen, f->dGtN, row, w_threshold, cutoff, order, f->batch ? f->nPer : f->N, gt_pose ? 1 : 0, f->holes ? 1 : 0, f->bKind == 2 ? 1 : 0};
   map_metric_kernel<<<nF, 64, 0, f->stream>>>(f->B, f->cur, A);
   HIPCHK(hipGetLastError());
   HIPCHK(hipEventRecord(f->evStage[k], f->stream));
@@ -3280,7 +3427,8 @@ int rfsgpu_get_map_estimate(rfsgpu_filter *f, int filter, double w_threshold, in
   const size_t c = f->cap;
   int k = 0;
   for (int m = 0; m < cnt; m++) {
-    const double wm = pl[m];
+    double wm = pl[m];
+    if (f->bKind == 2) wm = 1 - 1 / (1 + exp(wm));     // a FastSLAM batch: the existence probability of the log-odds (fastslam2dSim.cpp:628)
     if ((f->holes && wm < 0) || !(wm >= w_threshold)) continue;
     if (k < max_n) {
       if (w) w[k] = wm;

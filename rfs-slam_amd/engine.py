@@ -420,6 +420,10 @@ class FilterBatch(capi.CBatch):
         """One predict + update cycle of every filter (rfsgpu_batch_cycle_async)."""
         self.batch_cycle_async(predict, Zs, poses=poses, pose_cov=pose_cov, normalize=normalize)
 
+    def _gate_config(self, b):
+        """The configuration whose minUpdatesBeforeResample / minMeasurementsBeforeResample gate filter b's resampling."""
+        return self.configs[b]
+
     def weight_sums_per_filter(self):
         """{sum w, sum w^2} of each filter: [n_filters, 2]."""
         return self.batch_weight_sums()
@@ -450,7 +454,7 @@ class FilterBatch(capi.CBatch):
             if n_z[b] == 0:
                 continue
             self.nMeasurementsSinceResample[b] += int(n_z[b])
-            c = self.configs[b]
+            c = self._gate_config(b)
             if self.nUpdatesSinceResample[b] < c.minUpdatesBeforeResample or self.nMeasurementsSinceResample[b] < c.minMeasurementsBeforeResample:
                 continue
             wb = w[self.block(b)]
@@ -466,3 +470,28 @@ class FilterBatch(capi.CBatch):
             self.batch_resample_apply(plan, fired)
         return fired, plan
 
+
+class FastSLAMBatch(FilterBatch):
+    """n_filters independent 2-D single-hypothesis FastSLAM filters stepped together (rfsgpu_batch_fastslam_cycle_async): per cycle the
+    static landmark step, the association / Kalman update / weights, the existence prune, the new landmarks and each filter's
+    normalisation, one launch chain for all filters.  Each filter equals a separate FastSLAM handle given the same inputs.  The
+    model / Kalman filter / landmark noise of a filter come through configure(b, None, R=..., ...) as for a FilterBatch; the FastSLAM
+    configuration through configure_fastslam(b, fs_cfg), whose two gates also decide the resampling (update_and_resample, resample_async)."""
+
+    def __init__(self, n_filters, n_per_filter, device_id=0, gm_capacity=512):
+        super().__init__(n_filters, n_per_filter, device_id=device_id, gm_capacity=gm_capacity)
+        self.fs_configs = [self.default_fastslam_config() for _ in range(n_filters)]
+
+    def configure_fastslam(self, b, fs_cfg):
+        """Filter b's (None: every filter's) FastSlamConfig (rfsgpu_batch_set_fastslam_config; refused for more than one hypothesis or a
+        landmark-candidate count threshold other than 1)."""
+        self.batch_set_fastslam_config(b, fs_cfg)
+        for q in (range(self.n_filters) if b is None else [b]):
+            self.fs_configs[q] = fs_cfg
+
+    def cycle_async(self, predict, Zs, poses=None, pose_cov=None, normalize=True):
+        """One predict (static landmark step) + FastSLAM update cycle of every filter."""
+        self.batch_fastslam_cycle_async(predict, Zs, poses=poses, pose_cov=pose_cov, normalize=normalize)
+
+    def _gate_config(self, b):
+        return self.fs_configs[b]

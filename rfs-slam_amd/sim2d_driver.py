@@ -24,6 +24,12 @@ C1_SIM = dict(kmax=3000, dt=0.1, n_segments=20, max_dx=0.30, max_dy=0.0, max_dz=
               n_eval=15, min_weight=0.75, weighting_md=3.0, use_cluster=0, eff_n=100.0, min_updates=2, merge_thr=0.5, merge_infl=1.5,
               prune_thr=0.01)
 
+# values of the shipped cfg/fastslam2dSim.xml (tests/golden/fastslam2dSim_c1.xml): the simulator's own keys are those of C1_SIM; the
+# FastSLAM filter's: minLogMeasurementLikelihood, maxNDataAssocHypotheses, maxDataAssocLogLikelihoodDiff, the existence prune threshold;
+# landmarkExistencePrior is set to 0.5 by the driver (src/fastslam2dSim.cpp:481); pruning_meas_threshold is the constructor default
+C1_FASTSLAM_SIM = dict(C1_SIM, min_log_likelihood=-10.0, max_hypotheses=1, max_loglik_diff=3.0, existence_prune_thr=-5.0, existence_prior=0.5,
+                       pruning_meas_threshold=0)
+
 
 def odometry_step(x, u):
     """MotionModel_Odometry2d::step (src/ProcessModel_Odometry2D.cpp:40-90), vectorised: x [N,3] or [3], u [3] or [N,3]."""
@@ -137,6 +143,42 @@ def configure(f, P=C1_SIM):
     f.set_kf_config(P["kf_range"], P["kf_bearing"])
     f.set_lmk_process_noise(np.diag([P["varlmx"], P["varlmy"]]) * dt * dt)
     return cfg
+
+
+def fastslam_config(f, P=C1_FASTSLAM_SIM):
+    """The FastSLAM::Config of setupFastSLAMFilter (src/fastslam2dSim.cpp:474-481) as a capi.FastSlamConfig (f: anything with
+    default_fastslam_config)."""
+    c = f.default_fastslam_config()
+    c.minUpdatesBeforeResample = P["min_updates"]
+    c.minLogMeasurementLikelihood = P["min_log_likelihood"]
+    c.maxNDataAssocHypotheses = P["max_hypotheses"]
+    c.maxDataAssocLogLikelihoodDiff = P["max_loglik_diff"]
+    c.mapExistencePruneThreshold = P["existence_prune_thr"]
+    c.landmarkExistencePrior = P["existence_prior"]
+    c.pruningMeasurementsThreshold = P.get("pruning_meas_threshold", 0)
+    return c
+
+
+def configure_fastslam(f, P=C1_FASTSLAM_SIM):
+    """setupFastSLAMFilter (src/fastslam2dSim.cpp:438-482) for one handle through the C ABI."""
+    dt = P["dt"]
+    f.set_model_rngbrg(np.diag([P["varzr"], P["varzb"]]) * P["z_noise_inflation"], P["Pd"], P["clutter"], P["rmax"], P["rmin"], P["rbuf"])
+    f.set_kf_config(P["kf_range"], P["kf_bearing"])
+    f.set_lmk_process_noise(np.diag([P["varlmx"], P["varlmy"]]) * dt * dt)
+    c = fastslam_config(f, P)
+    f.set_fastslam_config(c)
+    return c
+
+
+def configure_fastslam_batch_filter(batch, b, P=C1_FASTSLAM_SIM):
+    """setupFastSLAMFilter for filter b of a FastSLAMBatch."""
+    dt = P["dt"]
+    R = np.diag([P["varzr"], P["varzb"]]) * P["z_noise_inflation"]
+    batch.configure(b, None, R=R, Pd=P["Pd"], clutter=P["clutter"], rmax=P["rmax"], rmin=P["rmin"], rbuf=P["rbuf"], kf=(P["kf_range"], P["kf_bearing"]),
+                    Q=np.diag([P["varlmx"], P["varlmy"]]) * dt * dt)
+    c = fastslam_config(batch, P)
+    batch.configure_fastslam(b, c)
+    return c
 
 
 class Sim2dRun:
@@ -271,12 +313,17 @@ class Sim2dBatchRun:
     resample_async (-> step_error_async when tracking), all stream-ordered: nothing is read back until errors(), resample_counts()
     or the end of the run, so the host only feeds the pinned rings.  The randomness is then the device's (Philox under seeds[b],
     call number = the step k), not the numpy streams of the host loop: the two loops run the same model on different realisations
-    of the noise.  step() returns None in this form (the decisions stay on the device; FilterBatch.last_resample reads the last ones)."""
+    of the noise.  step() returns None in this form (the decisions stay on the device; FilterBatch.last_resample reads the last ones).
 
-    def __init__(self, target, datas, Ps, seeds, track_errors=False, device_loop=False):
+    fastslam=True: the loop of src/fastslam2dSim.cpp:530-600 instead -- the same flow with FastSLAM::predict (propagation, static
+    landmark step, no births) and FastSLAM::update; `target` is a FastSLAMBatch or a list of FastSLAM handles (or oracle filters),
+    `Ps` dicts like C1_FASTSLAM_SIM.  A filter whose scan is empty is neither updated nor normalised that step (FastSLAM.hpp:402-403)."""
+
+    def __init__(self, target, datas, Ps, seeds, track_errors=False, device_loop=False, fastslam=False):
         """track_errors: as in Sim2dRun -- each filter's ground truth is uploaded, every cycle ends with one step_error_async (one
         launch for the whole batch; one per handle otherwise), errors() reads the log(s) once at the end."""
         self.device_loop = bool(device_loop)
+        self.fastslam = bool(fastslam)
         self.batch = target if isinstance(target, capi.CBatch) else None
         self.handles = None if self.batch is not None else list(target)
         self.nF = len(datas)
@@ -290,7 +337,12 @@ class Sim2dBatchRun:
         self.cov = [np.zeros((3, 3)) for _ in range(self.nF)]
         self.Q = [np.diag([P["vardx"], P["vardy"], P["vardz"]]) * P["p_noise_inflation"] * P["dt"] ** 2 for P in self.Ps]
         self.eff_n = np.array([float(P["eff_n"]) for P in self.Ps])
-        if self.batch is not None:
+        if self.fastslam:
+            if self.batch is not None:
+                self.cfgs = [configure_fastslam_batch_filter(self.batch, b, P) for b, P in enumerate(self.Ps)]
+            else:
+                self.cfgs = [configure_fastslam(f, P) for f, P in zip(self.handles, self.Ps)]
+        elif self.batch is not None:
             self.cfgs = [configure_batch_filter(self.batch, b, P) for b, P in enumerate(self.Ps)]
         else:
             self.cfgs = [configure(f, P) for f, P in zip(self.handles, self.Ps)]
@@ -353,7 +405,10 @@ class Sim2dBatchRun:
 
     def _device_update(self, k):
         bt = self.batch
-        bt.batch_cycle_async_packed(True, self._z[k], self._nz[k], normalize=True)
+        if self.fastslam:
+            bt.batch_fastslam_cycle_async_packed(True, self._z[k], self._nz[k], normalize=True)
+        else:
+            bt.batch_cycle_async_packed(True, self._z[k], self._nz[k], normalize=True)
         bt.resample_async(self._nz[k], k)
         self.last_n_z = self._nz[k]
         if self.track_errors:
@@ -406,7 +461,13 @@ class Sim2dBatchRun:
             fired = np.zeros(self.nF, dtype=bool)
             plans = []
             for b, f in enumerate(self.handles):
-                if hasattr(f, "cycle_async"):
+                if self.fastslam:   # FastSLAM::predict's map part, then FastSLAM::update; an empty scan: no update, no normalisation
+                    f.set_poses(self.x[b], covs[b])
+                    f.predict_map(False)
+                    if n_z[b]:
+                        f.fastslam_update(Zs[b])
+                        f.normalize_weights(f.weight_sums()[0])
+                elif hasattr(f, "cycle_async"):
                     f.cycle_async(True, Zs[b], poses=self.x[b], pose_cov=covs[b], normalize=True)
                 else:       # a handle with the plain calls only (the CPU oracle): the same cycle call by call
                     f.predict_map(True)

@@ -16,6 +16,10 @@ device tracking, (c) with the host route (per step and filter get_weights + expo
 resample_async, nothing read back until the end; the final synchronisation is inside the timed span).  --both-loops: the host loop
 and the device loop from the one invocation, both figures in the line.  Every line names its loop kind ("loop").  --reps N: N timed
 repetitions of each figure (fresh batch each), all of them in the line ("..._reps") next to their median.
+
+--fastslam: the same table for the FastSLAM half of a comparison sweep (the reference's fastslam2dSim over the same grid): a
+FastSLAMBatch (rfsgpu_batch_fastslam_cycle_async) against FastSLAM handles stepped in turn (predict_map, fastslam_update, normalise,
+resample per handle), host loop / device loop, --errors.  Every line then carries "filter": "fastslam".
 """
 import argparse
 import json
@@ -34,12 +38,12 @@ def load_pkg():
     return g.load_package() if hasattr(g, "load_package") else None
 
 
-def grid(sim, n, kmax):
+def grid(sim, n, kmax, fastslam=False):
     pds = [0.5, 0.6, 0.7, 0.8, 0.9, 0.95, 0.99, 0.85, 0.75, 0.65]
     clutters = [1e-4, 5e-4, 1e-3, 2e-3, 5e-3, 1e-2, 2e-2, 5e-2, 1e-1]
     Ps, datas, seeds = [], [], []
     for b in range(n):
-        P = dict(sim.C1_SIM)
+        P = dict(sim.C1_FASTSLAM_SIM if fastslam else sim.C1_SIM)
         P["Pd"] = pds[b % len(pds)]
         P["clutter"] = clutters[(b // len(pds)) % len(clutters)]
         Ps.append(P)
@@ -67,24 +71,26 @@ def timed_synced(run, steps):
     return time.perf_counter() - t0
 
 
-def host_route_errors(batch, datas, firsts, Ps, k, a2d):
+def host_route_errors(batch, datas, firsts, Ps, k, a2d, fastslam=False):
     """What a caller had to do per step before the device metric: per filter the weights, the best particle's mixture, scipy."""
     out = []
     for b in range(batch.n_filters):
         w = batch.get_weights()[batch.block(b)]
         i = b * batch.n_per_filter + int(np.argmax(w))
         gw, _, mean, _ = batch.export_gm(i)
+        if fastslam:
+            gw = 1 - 1 / (1 + np.exp(gw))         # log-odds -> existence probability (fastslam2dSim.cpp:628)
         seen = datas[b]["landmarks"][firsts[b] <= k * Ps[b]["dt"]]
         out.append(a2d.cola(mean[gw >= a2d.W_THRESHOLD], seen))
     return out
 
 
-def timed_host_route(run, steps, datas, firsts, Ps, a2d):
+def timed_host_route(run, steps, datas, firsts, Ps, a2d, fastslam=False):
     run.step(1)
     t0 = time.perf_counter()
     for k in range(2, steps + 2):
         run.step(k)
-        host_route_errors(run.batch, datas, firsts, Ps, k, a2d)
+        host_route_errors(run.batch, datas, firsts, Ps, k, a2d, fastslam)
     return time.perf_counter() - t0
 
 
@@ -98,10 +104,12 @@ def errors_sweep(pkg, a, sizes, Ps, datas, seeds):
     rows = []
     for B in sizes:
         row = dict(B=B, particles=a.particles, steps=a.steps)
+        if a.fastslam:
+            row["filter"] = "fastslam"
         for name in ("off", "device", "host"):
-            batch = pkg.FilterBatch(B, a.particles, gm_capacity=a.capacity)
-            run = sim.Sim2dBatchRun(batch, datas[:B], Ps[:B], seeds[:B], track_errors=(name == "device"))
-            dt = timed_host_route(run, a.steps, datas, firsts, Ps, a2d) if name == "host" else timed(run, a.steps)
+            batch = make_batch(pkg, a, B)
+            run = sim.Sim2dBatchRun(batch, datas[:B], Ps[:B], seeds[:B], track_errors=(name == "device"), fastslam=a.fastslam)
+            dt = timed_host_route(run, a.steps, datas, firsts, Ps, a2d, a.fastslam) if name == "host" else timed(run, a.steps)
             if name == "device":
                 t0 = time.perf_counter()
                 log = run.errors()                      # the one read (it also waits for the queued work)
@@ -126,6 +134,10 @@ def errors_sweep(pkg, a, sizes, Ps, datas, seeds):
     return rows
 
 
+def make_batch(pkg, a, B):
+    return pkg.FastSLAMBatch(B, a.particles, gm_capacity=a.capacity) if a.fastslam else pkg.FilterBatch(B, a.particles, gm_capacity=a.capacity)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=200)
@@ -137,13 +149,14 @@ def main():
     ap.add_argument("--errors", action="store_true", help="track COLA / pose error on the device; tracking off / device / host route timed side by side")
     ap.add_argument("--device-loop", action="store_true", help="the batch's whole cycle on the device (propagation and resampling included)")
     ap.add_argument("--both-loops", action="store_true", help="host loop and device loop side by side")
+    ap.add_argument("--fastslam", action="store_true", help="FastSLAM filters: a FastSLAMBatch against FastSLAM handles stepped in turn")
     ap.add_argument("--reps", type=int, default=1, help="timed repetitions of every batch figure")
     a = ap.parse_args()
     pkg = load_pkg()
     sim = pkg.sim2d_driver
     sizes = [int(s) for s in a.sizes.split(",")]
     kmax = a.steps + 2
-    Ps, datas, seeds = grid(sim, max(sizes), kmax)
+    Ps, datas, seeds = grid(sim, max(sizes), kmax, a.fastslam)
     rows = []
     if a.errors:
         erows = errors_sweep(pkg, a, sizes, Ps, datas, seeds)
@@ -155,13 +168,15 @@ def main():
             for rep in range(max(1, a.reps)):
                 if rep or loop != loops[0]:
                     batch.close()
-                batch = pkg.FilterBatch(B, a.particles, gm_capacity=a.capacity)
-                rb = sim.Sim2dBatchRun(batch, datas[:B], Ps[:B], seeds[:B], device_loop=(loop == "device"))
+                batch = make_batch(pkg, a, B)
+                rb = sim.Sim2dBatchRun(batch, datas[:B], Ps[:B], seeds[:B], device_loop=(loop == "device"), fastslam=a.fastslam)
                 t = timed_synced(rb, a.steps) if loop == "device" else timed(rb, a.steps)
                 batch.synchronize()
                 figs[loop].append(B * a.steps / t)
         tb = B * a.steps / float(np.median(figs[loops[0]]))
         row = dict(B=B, particles=a.particles, steps=a.steps, loop="+".join(loops), batch_filter_steps_per_s=float(np.median(figs[loops[0]])))
+        if a.fastslam:
+            row["filter"] = "fastslam"
         if a.reps > 1:
             row["batch_filter_steps_per_s_reps"] = figs[loops[0]]
         if len(loops) == 2:
@@ -171,13 +186,15 @@ def main():
                 row["device_loop_filter_steps_per_s_reps"] = figs["device"]
             row["resamples_device_loop"] = rb.resample_counts().tolist()
         if B <= a.handles_max:
-            hs = [pkg.RBPHDFilter(a.particles, gm_capacity=a.capacity) for _ in range(B)]
-            rh = sim.Sim2dBatchRun(hs, datas[:B], Ps[:B], seeds[:B])
+            hs = [(pkg.FastSLAM if a.fastslam else pkg.RBPHDFilter)(a.particles, gm_capacity=a.capacity) for _ in range(B)]
+            rh = sim.Sim2dBatchRun(hs, datas[:B], Ps[:B], seeds[:B], fastslam=a.fastslam)
             th = timed(rh, a.steps)
             for h in hs:
                 h.synchronize()
             row["handles_filter_steps_per_s"] = B * a.steps / th
             row["speedup"] = th / tb
+            if len(loops) == 2:
+                row["device_loop_speedup"] = row["device_loop_filter_steps_per_s"] / row["handles_filter_steps_per_s"]
             for h in hs:
                 h.close()
         if B == max(sizes):
@@ -185,7 +202,7 @@ def main():
             for b in range(B):
                 w = batch.get_weights()[batch.block(b)]
                 i = b * a.particles + int(np.argmax(w))
-                nm, e, ns = sim.map_error(batch, i, datas[b]["landmarks"])
+                nm, e, ns = sim.map_error(batch, i, datas[b]["landmarks"], w_min=(float(np.log(3.0)) if a.fastslam else 0.5))   # (log-odds of 0.75)
                 errs.append(dict(filter=b, Pd=Ps[b]["Pd"], clutter=Ps[b]["clutter"], seed=1 + b, matched=nm, n_landmarks=len(datas[b]["landmarks"]),
                                  mean_error=e, strong=ns))
             row["map_error"] = errs
