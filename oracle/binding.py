@@ -93,6 +93,7 @@ class OracleFilter:
         obj.murty_calls = lambda: _long(lib.rfsor_murty_calls, obj._h)
         obj.lonerow_bug_hits = lambda: _long(lib.rfsor_lonerow_bug_hits, obj._h)
         obj.fs_solver_max_dim = lambda: _long(lib.rfsor_fs_solver_max_dim, obj._h)
+        obj.fs_assoc_dims = lambda: _fs_assoc_dims(lib, obj)
         obj.set_stable_sort = lambda on: lib.rfsor_set_stable_sort(obj._h, C.c_int(1 if on else 0))
         return obj
 
@@ -124,6 +125,26 @@ def vp_clutter(f):
 def _long(fn, h):
     fn.restype = C.c_long
     return fn(h)
+
+
+def _fs_assoc_dims(lib, f):
+    """Per particle the last FastSLAM update visited: (nMZ, nRed, nH) -- the table dimension max(in-range landmarks,
+    measurements), the dimension of the reduced table Murty ran on (0: reduce fixed every row and Murty was skipped) and the
+    number of hypotheses kept."""
+    cap = max(int(f.n), 1)
+    a = [np.zeros(cap, dtype=np.int32) for _ in range(3)]
+    k = lib.rfsor_fs_last_assoc_dims(f._h, *(x.ctypes.data_as(C.c_void_p) for x in a), C.c_int(cap))
+    if k < 0:
+        raise RuntimeError("rfsor_fs_last_assoc_dims: %d" % k)
+    return tuple(x[:k].copy() for x in a)
+
+
+def hungarian_max_queue_tail(reset=False):
+    """Oracle probe: the most entries any augmenting search of the Hungarian restatement had enqueued when the expansion that
+    discovers its target began, since the last reset (the device's solver keeps entries from index 64 on in a second register)."""
+    lib = load()
+    lib.rfsor_hungarian_max_queue_tail.restype = C.c_long
+    return lib.rfsor_hungarian_max_queue_tail(C.c_int(1 if reset else 0))
 
 
 def set_threads(n):

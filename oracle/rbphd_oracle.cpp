@@ -412,6 +412,14 @@ struct PermLex {
  * 1e-14 / 1e-12 tolerances (:293, :487, :500, :538).
  * ---------------------------------------------------------------------------------------------- */
 static long g_hungarian_fail = 0;
+/* Test probe: the largest number of entries an augmenting search had put into its breadth-first queue when the expansion that
+ * discovers the target column began (what a solver that stops at the discovery has enqueued: the device keeps entries from
+ * index 64 on in a second register, csrc/hungarian_wave.h). */
+static long g_hungarian_max_queue_tail = 0;
+static inline void hungarian_note_queue_tail(long v) {
+  long cur = __atomic_load_n(&g_hungarian_max_queue_tail, __ATOMIC_RELAXED);
+  while (v > cur && !__atomic_compare_exchange_n(&g_hungarian_max_queue_tail, &cur, v, false, __ATOMIC_RELAXED, __ATOMIC_RELAXED)) {}
+}
 static bool hungarian_run(double **C, int n, int *soln, double *cost) {
   std::vector<double> lx(n), ly(n), slack(n);
   std::vector<int> xy(n, -1), yx(n, -1), p(2 * n);
@@ -481,6 +489,7 @@ static bool hungarian_run(double **C, int n, int *soln, double *cost) {
       bool augmentingPathFound = false;
       int target = y + n;
       std::queue<int> q;
+      long nPushed = 1, tailAtDiscovery = -1;
       q.push(root);
       for (x = 0; x < n; x++) { x_q[x] = 0; y_q[x] = 0; }
       x_q[root] = 1;
@@ -498,16 +507,21 @@ static bool hungarian_run(double **C, int n, int *soln, double *cost) {
         }
         q.pop();
         if (t < n) {
+          const long tailBefore = nPushed;
           for (y = 0; y < n; y++) {
-            if (fabs(lx[t] + ly[y] - C[t][y]) < 1e-12 && !y_q[y] && xy[t] != y) { y_q[y] = 1; p[y + n] = t; q.push(y + n); }
+            if (fabs(lx[t] + ly[y] - C[t][y]) < 1e-12 && !y_q[y] && xy[t] != y) {
+              y_q[y] = 1; p[y + n] = t; q.push(y + n); nPushed++;
+              if (y + n == target && tailAtDiscovery < 0) tailAtDiscovery = tailBefore;
+            }
           }
         } else {
           t -= n;
           for (x = 0; x < n; x++) {
-            if (fabs(lx[x] + ly[t] - C[x][t]) < 1e-12 && S[x] && !x_q[x] && yx[t] == x) { x_q[x] = 1; p[x] = t + n; q.push(x); }
+            if (fabs(lx[x] + ly[t] - C[x][t]) < 1e-12 && S[x] && !x_q[x] && yx[t] == x) { x_q[x] = 1; p[x] = t + n; q.push(x); nPushed++; }
           }
         }
       }
+      if (tailAtDiscovery >= 0) hungarian_note_queue_tail(tailAtDiscovery);
       if (!augmentingPathFound) { g_hungarian_fail++; return false; } /* :513-523 ("Cannot find alternating path") */
       pickFreeVertex = true;
     } else {
@@ -890,6 +904,8 @@ struct FilterBase {
                                true : (weight desc, index asc) == what the device path implements */
   long murty_calls = 0, lonerow_bug_hits = 0;
   long fs_solver_calls = 0, fs_solver_max_dim = 0; /* FastSLAM: reduced tables that needed the assignment solver */
+  std::vector<int> fs_last_nMZ, fs_last_nRed, fs_last_nH; /* per particle of the last FastSLAM update: table dimension, reduced
+                                                             dimension handed to Murty (0: skipped), hypotheses kept */
   rfsgpu_timing timing;
   std::string err;
   virtual ~FilterBase() {}
@@ -1415,10 +1431,13 @@ struct FilterT : FilterBase {
         if (ok) T[m][z] = fmax(lim, log(gauss_lik<D>(z_exp, S, &Z[(size_t)D * z], nullptr)));
     }
     ReducedCost R = cost_matrix_reduce(T, (int)nMZ, lim); /* :484-490 */
+    fs_last_nMZ[i] = (int)nMZ; /* (each particle writes its own entry) */
+    fs_last_nRed[i] = R.nRed;
     if (R.nRed == 0) {                                     /* :498-505 */
       std::vector<int> da(nMZ, -1);
       for (unsigned m = 0; m < nM; m++) da[m] = R.a_fixed[m];
       A.da.push_back(da);
+      fs_last_nH[i] = 1;
       return;
     }
     std::vector<std::vector<double>> Cr(R.nRed, std::vector<double>(R.nRed));
@@ -1456,6 +1475,7 @@ struct FilterT : FilterBase {
       }
       A.da.push_back(da);
     }
+    fs_last_nH[i] = (int)A.da.size();
     /* nH == 0 (the solver failed at once): no hypothesis, the particle is left untouched (:543-551 runs 0 times) */
   }
   void fastslam_apply(int i, const FsAssoc &A, const std::vector<int> &da) {
@@ -1546,6 +1566,9 @@ struct FilterT : FilterBase {
   int fastslam_update() override {
     const int n0 = n; /* stopIdx: particles added during this update are not visited (:389-391) */
     std::vector<FsAssoc> assoc(n0);
+    fs_last_nMZ.assign(n0, 0);
+    fs_last_nRed.assign(n0, 0);
+    fs_last_nH.assign(n0, 0);
 #pragma omp parallel for schedule(dynamic, 4)
     for (int i = 0; i < n0; i++) fastslam_associate(i, assoc[i]);
     /* landmarkCandidates_.resize(nParticles * maxNDataAssocHypotheses) (:392-395): only ever grows, old lists stay */
@@ -1894,7 +1917,22 @@ int rfsor_cost_matrix_reduce(double *C, int n, double lim, int *a_fixed, int *iR
   for (int i = 0; i < n; i++) { a_fixed[i] = R.a_fixed[i]; iRed[i] = i < (int)R.iRed.size() ? R.iRed[i] : -1; jRed[i] = i < (int)R.jRed.size() ? R.jRed[i] : -1; }
   return R.nRed;
 }
+/* the probe above; reset != 0 clears it after the read */
+long rfsor_hungarian_max_queue_tail(int reset) {
+  long v = __atomic_load_n(&orc::g_hungarian_max_queue_tail, __ATOMIC_RELAXED);
+  if (reset) __atomic_store_n(&orc::g_hungarian_max_queue_tail, 0L, __ATOMIC_RELAXED);
+  return v;
+}
 long rfsor_fs_solver_max_dim(void *f) { return F_(f)->fs_solver_max_dim; }
+/* per particle of the last FastSLAM update: nMZ, nRed (0 when Murty was skipped) and the number of hypotheses kept; returns
+ * the number of particles that update visited (-1: max_n is too small) */
+int rfsor_fs_last_assoc_dims(void *f, int *nMZ, int *nRed, int *nH, int max_n) {
+  FilterBase *F = F_(f);
+  const int k = (int)F->fs_last_nMZ.size();
+  if (max_n < k) return -1;
+  for (int i = 0; i < k; i++) { nMZ[i] = F->fs_last_nMZ[i]; nRed[i] = F->fs_last_nRed[i]; nH[i] = F->fs_last_nH[i]; }
+  return k;
+}
 void rfsor_default_fastslam_config(rfsgpu_fastslam_config *c) { orc::fastslam_defaults(c, 0); }
 int rfsor_set_fastslam_config(void *f, const rfsgpu_fastslam_config *c) { F_(f)->fs = *c; return RFSGPU_OK; }
 int rfsor_get_fastslam_config(const void *f, rfsgpu_fastslam_config *c) { *c = reinterpret_cast<const FilterBase *>(f)->fs; return RFSGPU_OK; }

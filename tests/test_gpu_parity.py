@@ -1306,7 +1306,7 @@ def test_mh_fastslam_host_mirror(pkg, ob, sc):
     assert forced > 0 and shrunk > 0
 
 
-def test_fastslam_hypothesis_count_limit(pkg, sc):
+def test_fastslam_hypothesis_count_limit(pkg, ob, sc):
     scen = sc.make_scenario(4, 5, 3, seed=1)
     dev = pkg.RBPHDFilter(4, gm_capacity=64)
     sc.load_scenario(dev, scen)
@@ -1318,10 +1318,20 @@ def test_fastslam_hypothesis_count_limit(pkg, sc):
     assert e.value.status == pkg.capi.ERR_UNSUPPORTED
     cfg.maxNDataAssocHypotheses = 3                 # no room for the copies: refused, not truncated
     dev.set_fastslam_config(cfg)
-    try:
+    orc = ob.OracleFilter(4)                        # (every particle keeps 3 hypotheses here: 12 particles for 4 slots)
+    sc.load_scenario(orc, scen)
+    orc.set_fastslam_config(cfg)
+    orc.fastslam_update(scen["Z"])
+    assert orc.n > dev.max_particles and np.all(orc.fs_assoc_dims()[2] == 3)
+    w0 = dev.get_weights().copy()
+    maps0 = [dev.export_gm(i) for i in range(4)]
+    with pytest.raises(pkg.capi.EngineError) as e2:
         dev.fastslam_update(scen["Z"])
-    except pkg.capi.EngineError as e2:
-        assert e2.status == pkg.capi.ERR_CAPACITY
+    assert e2.value.status == pkg.capi.ERR_CAPACITY
+    assert dev.n == 4 and np.array_equal(dev.get_weights(), w0)          # the state is untouched
+    for i in range(4):
+        for x, y in zip(dev.export_gm(i), maps0[i]):
+            assert np.array_equal(x, y)
 
 
 # ---- Victoria Park model (3-D landmarks, scan-based Pd, birth-candidate lists) -----------------------------------------
@@ -2147,6 +2157,9 @@ def test_randomised_differential_run_fastslam():
     out = subprocess.run([sys.executable, os.path.join(root, "tools", "fuzz_fastslam.py"), "40", "2025"], capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stdout[-3000:] + out.stderr[-2000:]
     assert ", 0 failures" in out.stdout
+    import re
+    crowded = re.search(r"(\d+) crowded cases", out.stdout)      # draws with more than one hypothesis on tables of up to 64 rows
+    assert crowded and int(crowded.group(1)) >= 5, out.stdout[-500:]
 
 
 def _vp_cpp(pkg, *args):

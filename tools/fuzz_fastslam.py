@@ -14,6 +14,7 @@ sc = pkg.scenarios
 ob = importlib.import_module("oracle.binding")
 n_cases = int(sys.argv[1]) if len(sys.argv) > 1 else 60
 rng = np.random.default_rng(int(sys.argv[2]) if len(sys.argv) > 2 else 1)
+rng_crowded = np.random.default_rng([int(sys.argv[2]) if len(sys.argv) > 2 else 1, 64])   # its own stream: the other draws of a seed stay as they were
 
 
 def compare(dev, orc):
@@ -38,17 +39,39 @@ def compare(dev, orc):
         np.testing.assert_allclose(md, mo, rtol=1e-9, atol=1e-11)
 
 
-bad = grown = 0
+def table_dim(orc, P, poses, n_z):
+    """The largest nMZ = max(landmarks in range, measurements) over the particles, range-bearing model: a landmark is in range when
+    its Pd is not 0 or it is close to the sensing limit, i.e. its distance lies in [rmin - rbuf, rmax + rbuf]."""
+    n_in = 0
+    for i in range(orc.n):
+        mu = orc.export_gm(i)[2]
+        r = np.hypot(mu[:, 0] - poses[i, 0], mu[:, 1] - poses[i, 1]) if len(mu) else np.zeros(0)
+        n_in = max(n_in, int(np.sum((r >= P["rmin"] - P["rbuf"]) & (r <= P["rmax"] + P["rbuf"]))))
+    return max(n_in, n_z)
+
+
+bad = grown = n_refused = n_crowded = 0
 n_degenerate = 0
 for case in range(n_cases):
     hyp = int(rng.choice([1, 1, 2, 3, 5]))
+    crowded = False
     n0 = int(rng.integers(3, 10))
     kw = dict(n_particles=n0, n_landmarks=int(rng.choice([2, 6, 12, 25, 40])), n_z=int(rng.integers(1, 14)), seed=int(rng.integers(1 << 30)),
               rmax=float(rng.choice([4.0, 5.0, 8.0])))
     if hyp == 1 and rng.random() < 0.4:
         kw.update(n_landmarks=int(rng.choice([70, 130, 200])), n_z=int(rng.integers(10, 40)), rmax=float(rng.choice([12.0, 25.0])))
+    elif hyp > 1 and rng_crowded.random() < 0.4:
+        # crowded tables for Murty: the default 2.5 m range, every landmark in range, nMZ = max(landmarks, measurements) up to 64 (the
+        # LDS tile's limit of 32, the second queue register and the largest table all lie in here).  Later cycles add landmarks: a
+        # table that outgrows 64 must be refused by the device (checked below against table_dim of the oracle's maps) and ends the case.
+        crowded = True
+        kw.pop("rmax")
+        kw.update(n_landmarks=int(rng_crowded.integers(8, 65)), n_z=int(rng_crowded.integers(4, 65)))
+        n_crowded += 1
     vp = rng.random() < 0.3          # Victoria Park model (3-D landmarks, scan-based Pd)
     if vp:
+        n_crowded -= int(crowded)
+        crowded = False
         kw = dict(n_particles=n0, n_landmarks=int(rng.choice([3, 10, 30, 60])), n_z=int(rng.integers(1, 14)), seed=int(rng.integers(1 << 30)),
                   scan=str(rng.choice(["const", "ragged"])))
         scen = sc.make_vp_scenario(**kw)
@@ -78,8 +101,19 @@ for case in range(n_cases):
         rz, ru = np.random.default_rng(kw["seed"]), np.random.default_rng(kw["seed"] + 1)
         for step in range(4):
             Z = scen["Z"] + rz.normal(0, 3e-3, scen["Z"].shape)
+            orc.predict_map(False)
+            dev.predict_map(False)
+            if crowded and table_dim(orc, scen["params"], poses, len(Z)) > 64:      # a table beyond Murty's 64: the device must refuse, untouched
+                n_before = dev.n
+                try:
+                    dev.fastslam_update(Z)
+                except pkg.capi.EngineError as e:
+                    assert e.status == pkg.capi.ERR_UNSUPPORTED and dev.n == n_before, (e.status, dev.n, n_before)
+                else:
+                    raise AssertionError("a table of more than 64 rows was accepted")
+                n_refused += 1
+                break
             for f in (dev, orc):
-                f.predict_map(False)
                 f.fastslam_update(Z)
             par = dev.particle_parents()
             assert np.array_equal(par, orc.particle_parents())
@@ -104,5 +138,5 @@ for case in range(n_cases):
         print("VP CASE" if vp else "CASE", case, kw, "hyp", hyp, "diff", diff, "->", type(e).__name__, str(e)[:300], flush=True)
     dev.close()
 print("fastslam fuzz: %d cases, %d failures (updates that multiplied particles: %d); %d weight comparisons had a zero / non-finite sum "
-      "and were made on the raw weights" % (n_cases, bad, grown, n_degenerate))
+      "and were made on the raw weights; %d crowded cases, %d of them ended in a correct refusal of a table beyond 64" % (n_cases, bad, grown, n_degenerate, n_crowded, n_refused))
 sys.exit(1 if bad else 0)
