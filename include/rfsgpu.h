@@ -388,6 +388,16 @@ int rfsgpu_step_launch_order(rfsgpu_filter *f, int mode, const int *order_in, fl
  * setRealAssignmentBlock(nR, nC) (include/RBPHDFilter.hpp:942-959, src/MurtyAlgorithm.cpp:141-336).  The handle's weights are
  * left as they were.  (tests/test_gpu_parity.py pins it to the reference's BruteForceLinearAssignment fixture.) */
 int rfsgpu_murty_partition_sums(rfsgpu_filter *f, const double *mats, const int *nR, const int *nC, int n_jobs, double *sums_out);
+/* [test] The partition stage of the particle weight (connected components of the likelihood table, the zero-partition merge and its
+ * indexing quirk, the <= 8 enumeration, the exact mode, the Murty-200 jobs: include/RBPHDFilter.hpp:865-990) on n_tables given
+ * likelihood tables by the weighting kernels' own device function, one wavefront per table; table k plays particle k
+ * (n_tables <= the handle's particle count).  Table k is nE[k] x nZ[k] row-major, already gated and including Pd; the tables lie
+ * back to back in L, the evaluation points' Pd (nE[k] each) back to back in pd; 0 <= nE[k], nZ[k] <= 64.  The handle's partition
+ * mode and Murty queue are used and its post kernel multiplies the Murty factors in, as in a step.  out[k] = the product over the
+ * visited partitions, before the division by the clutter integral.  The handle's weights are left as they were; a table the
+ * step would refuse (a Murty partition beyond 64) gives RFSGPU_ERR_UNSUPPORTED and no numbers. */
+int rfsgpu_partition_likelihoods(rfsgpu_filter *f, const double *L, const double *pd, const int *nE, const int *nZ, int n_tables,
+                                 double clutter, double *out);
 int rfsgpu_update_map(rfsgpu_filter *f, const double *z, int n_z);      /* updateMap       :543-725 */
 int rfsgpu_importance_weighting(rfsgpu_filter *f);                       /* importanceWeighting :728-997 */
 int rfsgpu_merge(rfsgpu_filter *f);                                      /* GaussianMixture::merge  GaussianMixture.hpp:394-475 */

@@ -204,15 +204,16 @@ def murty(Cm, nR=None, nC=None, kmax=200):
     return scores[:k].copy(), assign[:k].copy()
 
 
-def partition_likelihood(L, evalPd, clutter, clutter_integral):
+def partition_likelihood(L, evalPd, clutter, clutter_integral, exact=False):
+    """exact=True: the engine's opt-in RFSGPU_PARTITION_EXACT mode instead of Murty-200 for the partitions beyond 8."""
     lib = load()
     L = np.ascontiguousarray(L, dtype=np.float64)
     nE, nZ = L.shape
     pd = np.ascontiguousarray(evalPd, dtype=np.float64)
     mc, lr = C.c_long(0), C.c_long(0)
-    lib.rfsor_partition_likelihood.restype = C.c_double
-    v = lib.rfsor_partition_likelihood(L.ctypes.data_as(C.c_void_p), C.c_int(nE), C.c_int(nZ), pd.ctypes.data_as(C.c_void_p),
-                                       C.c_double(clutter), C.c_double(clutter_integral), C.byref(mc), C.byref(lr))
+    lib.rfsor_partition_likelihood_mode.restype = C.c_double
+    v = lib.rfsor_partition_likelihood_mode(L.ctypes.data_as(C.c_void_p), C.c_int(nE), C.c_int(nZ), pd.ctypes.data_as(C.c_void_p),
+                                            C.c_double(clutter), C.c_double(clutter_integral), C.byref(mc), C.byref(lr), C.c_int(1 if exact else 0))
     return v, mc.value, lr.value
 
 

@@ -2273,5 +2273,14 @@ double rfsor_partition_likelihood(const double *L, int nE, int nZ, const double 
   std::vector<double> pd(evalPd, evalPd + nE), cl(nZ, clutter);
   return orc::partitions_likelihood(cm, pd, cl, murty_calls, lonerow_hits) / clutterIntegral;
 }
+/* The same in either partition mode: exact != 0 is the checker of the engine's opt-in RFSGPU_PARTITION_EXACT (exact_partition_sum). */
+double rfsor_partition_likelihood_mode(const double *L, int nE, int nZ, const double *evalPd, double clutter, double clutterIntegral,
+                                       long *murty_calls, long *lonerow_hits, int exact) {
+  orc::CostMatrixGeneral cm(nE, nZ);
+  for (int m = 0; m < nE; m++)
+    for (int n = 0; n < nZ; n++) cm.C_[m][n] = L[m * nZ + n];
+  std::vector<double> pd(evalPd, evalPd + nE), cl(nZ, clutter);
+  return orc::partitions_likelihood(cm, pd, cl, murty_calls, lonerow_hits, exact != 0) / clutterIntegral;
+}
 
 } /* extern "C" */

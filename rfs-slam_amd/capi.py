@@ -130,7 +130,7 @@ ABI_SYMBOLS = [
     "normalize_weights_parts", "create_ex", "n_particles", "max_particles", "resample_apply_n",
     "fastslam_set_resample_occured", "particle_parents", "vp_probe_pd",
     "slab_row_bytes", "export_slab_rows", "import_slab_rows", "weights_device_ptr", "step_async", "set_step_inputs_async", "predict_map_async", "set_phase_timing", "static_steps_async", "propagate_ackerman_async", "propagate_ackerman_run_async", "set_partition_mode", "get_partition_mode",
-    "set_birth_inheritance", "get_birth_inheritance", "get_particle_ids", "set_particle_ids", "resample_occured", "get_unused_masks", "set_unused_masks", "has_birth_candidates", "predict_map_level", "murty_partition_sums", "cycle_async", "update_io", "step_async_deferred", "step_async_trailing", "collective_gate", "collective_publish", "collective_probe",
+    "set_birth_inheritance", "get_birth_inheritance", "get_particle_ids", "set_particle_ids", "resample_occured", "get_unused_masks", "set_unused_masks", "has_birth_candidates", "predict_map_level", "murty_partition_sums", "partition_likelihoods", "cycle_async", "update_io", "step_async_deferred", "step_async_trailing", "collective_gate", "collective_publish", "collective_probe",
     "group_create", "group_destroy", "group_last_error", "group_n_shards", "group_n_particles", "group_shard", "group_locate",
     "group_set_filter_config", "group_set_model_rngbrg", "group_set_kf_config", "group_set_lmk_process_noise", "group_set_poses",
     "group_get_poses", "group_set_weights", "group_get_weights", "group_predict_map", "group_update", "group_normalize",
@@ -506,6 +506,21 @@ class CFilter:
         c = np.ascontiguousarray(nC, dtype=np.int32)
         out = np.zeros(len(mats), dtype=np.float64)
         self._call("murty_partition_sums", self._ptr(flat), self._ptr(r), self._ptr(c), C.c_int(len(mats)), self._ptr(out))
+        return out
+
+    def partition_likelihoods(self, tables, pds, clutter):
+        """[test] The weighting phase's partition stage on given likelihood tables (rfsgpu_partition_likelihoods): one number per
+        table, the product over its visited partitions before the clutter-integral division."""
+        tabs = [np.asarray(t, dtype=np.float64) for t in tables]
+        assert all(t.ndim == 2 for t in tabs) and len(tabs) == len(pds)
+        nE = np.ascontiguousarray([t.shape[0] for t in tabs], dtype=np.int32)
+        nZ = np.ascontiguousarray([t.shape[1] for t in tabs], dtype=np.int32)
+        flat = np.ascontiguousarray(np.concatenate([t.ravel() for t in tabs] + [np.zeros(1)]))
+        pd = np.ascontiguousarray(np.concatenate([np.asarray(p, dtype=np.float64).ravel() for p in pds] + [np.zeros(1)]))
+        assert pd.size == int(nE.sum()) + 1
+        out = np.zeros(len(tabs), dtype=np.float64)
+        self._call("partition_likelihoods", self._ptr(flat), self._ptr(pd), self._ptr(nE), self._ptr(nZ), C.c_int(len(tabs)), C.c_double(clutter),
+                   self._ptr(out))
         return out
 
     def get_unused_masks(self):

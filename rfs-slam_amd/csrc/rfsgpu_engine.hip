@@ -216,6 +216,27 @@ static int fail(rfsgpu_filter *f, int code, const char *msg) {
   return code;
 }
 
+// rfsgpu_partition_likelihoods: one wavefront per table.  dims[4 k ..]: nE, nZ, the table's offset in L, its offset in pd.  The LDS view is
+// carved for the largest table (64 x 64, no mixture); the table keeps its own row stride nZ, as in the weighting kernels.
+__global__ __launch_bounds__(64) void partition_tables_kernel(const double *L, const double *pd, const int *dims, double clutter, MurtyQueue Q, int *err,
+                                                              int exactMode, double *weight) {
+  extern __shared__ __align__(16) unsigned char smem_raw[];
+  const int k = (int)blockIdx.x, lane = (int)threadIdx.x;
+  const int nE = dims[4 * k], nZ = dims[4 * k + 1];
+  const double *Lk = L + dims[4 * k + 2], *pdk = pd + dims[4 * k + 3];
+  WeightLDS s;
+  carve_weight_lds(smem_raw, 0, RFSGPU_MAX_EVAL, RFSGPU_MAX_Z, s);
+  for (int idx = lane; idx < nE * nZ; idx += 64) s.L[idx] = Lk[idx];
+  if (lane < nE) {
+    const double p = pdk[lane];
+    s.evPd[lane] = p;
+    s.evLog1mPd[lane] = log(1 - p);
+  }
+  wave_sync();
+  const double l = rfs_partitions_wave(s, nE, nZ, clutter, lane, k, Q, err, exactMode);
+  if (lane == 0) weight[k] = l;
+}
+
 static void batch_set_all(rfsgpu_filter *f);
 #define REFUSE_ON_BATCH(f, what)                                                                                                   \
   if ((f)->batch) return fail(f, RFSGPU_ERR_UNSUPPORTED, what " is not available on a filter batch (rfsgpu_create_batch): use the rfsgpu_batch_* calls")
@@ -506,6 +527,56 @@ int rfsgpu_murty_partition_sums(rfsgpu_filter *f, const double *mats, const int 
   HIPCHK(hipMemcpyAsync(sums_out, f->Q.results, (size_t)n_jobs * sizeof(double), hipMemcpyDeviceToHost, f->stream));
   HIPCHK(hipMemcpyAsync(f->B.weight, w.data(), (size_t)f->N * sizeof(double), hipMemcpyHostToDevice, f->stream));
   return check_device_errors(f);
+}
+// [test] The weighting phase's partition stage (weighting.h steps 5-6, rfs_partitions_wave) on given likelihood tables: table k plays
+// particle k.  One wavefront per table lays the table, the evaluation points' Pd and log(1 - Pd) into the LDS view the weighting
+// kernels use and calls the production device function with the handle's partition mode and Murty queue; the handle's post kernel
+// then multiplies the queued Murty-200 factors in, as in a step.  Nothing of the partition logic is restated here.
+int rfsgpu_partition_likelihoods(rfsgpu_filter *f, const double *L, const double *pd, const int *nE, const int *nZ, int n_tables, double clutter,
+                                 double *out) {
+  CHECK_HANDLE(f);
+  REFUSE_ON_BATCH(f, "rfsgpu_partition_likelihoods");
+  if (!L || !pd || !nE || !nZ || !out || n_tables < 1 || n_tables > f->N) return fail(f, RFSGPU_ERR_INVALID, "partition_likelihoods: bad arguments");
+  std::vector<int> dims((size_t)n_tables * 4);
+  size_t offL = 0, offPd = 0;
+  for (int k = 0; k < n_tables; k++) {
+    if (nE[k] < 0 || nE[k] > RFSGPU_MAX_EVAL || nZ[k] < 0 || nZ[k] > RFSGPU_MAX_Z)
+      return fail(f, RFSGPU_ERR_INVALID, "partition_likelihoods: table dimensions out of range (0 .. 64 evaluation points and measurements)");
+    dims[4 * k] = nE[k]; dims[4 * k + 1] = nZ[k]; dims[4 * k + 2] = (int)offL; dims[4 * k + 3] = (int)offPd;
+    offL += (size_t)nE[k] * nZ[k];
+    offPd += (size_t)nE[k];
+  }
+  hipSetDevice(f->device);
+  HIPCHK(hipStreamSynchronize(f->stream));
+  std::vector<double> w((size_t)f->N), got((size_t)n_tables);
+  HIPCHK(hipMemcpy(w.data(), f->B.weight, (size_t)f->N * sizeof(double), hipMemcpyDeviceToHost));
+  struct Tmp { void *p = nullptr; ~Tmp() { if (p) hipFree(p); } } dL, dPd, dDims;
+  HIPCHK(hipMalloc(&dL.p, (offL + 1) * sizeof(double)));
+  HIPCHK(hipMalloc(&dPd.p, (offPd + 1) * sizeof(double)));
+  HIPCHK(hipMalloc(&dDims.p, dims.size() * sizeof(int)));
+  if (offL) HIPCHK(hipMemcpy(dL.p, L, offL * sizeof(double), hipMemcpyHostToDevice));
+  if (offPd) HIPCHK(hipMemcpy(dPd.p, pd, offPd * sizeof(double), hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(dDims.p, dims.data(), dims.size() * sizeof(int), hipMemcpyHostToDevice));
+  const int cnt[2] = {0, 0};
+  HIPCHK(hipMemcpy(f->Q.count, cnt, sizeof(cnt), hipMemcpyHostToDevice));
+  const size_t lds = weight_lds_bytes_per_wave(0, RFSGPU_MAX_EVAL, RFSGPU_MAX_Z);
+  partition_tables_kernel<<<n_tables, 64, lds, f->stream>>>((const double *)dL.p, (const double *)dPd.p, (const int *)dDims.p, clutter, f->Q, f->B.err,
+                                                            f->P.exactPartitions, f->B.weight);
+  // from here on the weights are overwritten: whatever fails, they are put back before the call returns
+  hipError_t he = hipGetLastError();
+  const bool launched = he == hipSuccess && murty_launch(f->Q, f->MS, f->B, f->stream, nullptr, 0, nullptr, 0, f->hJobCount) == 0;
+  if (launched) he = hipMemcpyAsync(got.data(), f->B.weight, (size_t)n_tables * sizeof(double), hipMemcpyDeviceToHost, f->stream);
+  const hipError_t hr = hipMemcpyAsync(f->B.weight, w.data(), (size_t)f->N * sizeof(double), hipMemcpyHostToDevice, f->stream);
+  if (he != hipSuccess || hr != hipSuccess) {
+    hipStreamSynchronize(f->stream);
+    f->err = std::string("partition_likelihoods: ") + hipGetErrorString(he != hipSuccess ? he : hr);
+    return RFSGPU_ERR_HIP;
+  }
+  if (!launched) { hipStreamSynchronize(f->stream); return fail(f, RFSGPU_ERR_HIP, "murty launch failed"); }
+  const int rc = check_device_errors(f);   // (synchronises)
+  if (rc != RFSGPU_OK) return rc;          // a refused table: no number comes back
+  for (int k = 0; k < n_tables; k++) out[k] = got[k];
+  return RFSGPU_OK;
 }
 int rfsgpu_get_partition_mode(const rfsgpu_filter *f) { return f ? (f->P.exactPartitions ? RFSGPU_PARTITION_EXACT : RFSGPU_PARTITION_MURTY200) : -1; }
 int rfsgpu_get_filter_config(const rfsgpu_filter *f, rfsgpu_filter_config *c) {
