@@ -638,6 +638,41 @@ int rfsgpu_fastslam_set_resample_occured(rfsgpu_filter *f, int flag);
 /* parent[k] = the slot particle k was copied from by the last rfsgpu_fastslam_update (k itself when it was not a copy). */
 int rfsgpu_particle_parents(rfsgpu_filter *f, int *parent, int max_n);
 
+/* -- the whole FastSLAM::update on the device, without a host stop (outside the STABLE CORE) --
+ * rfsgpu_fastslam_update stops in the middle of a multi-hypothesis update (the hypothesis counts come back, the host lays out the
+ * copies) and leaves resampleWithMapCopy to the caller.  rfsgpu_fastslam_cycle_async enqueues one whole FastSLAM::update
+ * (FastSLAM.hpp:387-421) on the handle's stream and returns without synchronising: with `predict`, the static landmark step of
+ * FastSLAM::predict (:376-383, what rfsgpu_predict_map_async(f, 0) does); the association (Murty's k best with
+ * maxNDataAssocHypotheses > 1; 1 runs the same pipeline with one hypothesis); the particle copies, laid out on the device in the
+ * reference's order; Kalman correction, existence, weights; pruning and new landmarks; and resampleWithMapCopy (:729-757): forced
+ * down to n_init when the grown count exceeds nParticlesMax, else -- once minUpdatesBeforeResample / minMeasurementsBeforeResample
+ * are met -- ParticleFilter::resample(n_init) with its N_eff test (thresholds: rfsgpu_fastslam_set_resampling); weights 1 after a
+ * resampling, normalised otherwise.  u01 in [0, 1) is the caller's draw for the systematic plan (the reference's drand48()).  n_init:
+ * nParticles_init_ (0: the count stays).  n_z == 0 returns after counting the update (:399-402).  The two counters and
+ * resampleOccured_ live on the device for this route (resampleOccured_ starts from rfsgpu_fastslam_set_resample_occured's value).
+ *
+ * After the call the particle count is known to the device only.  rfsgpu_synchronize and every call that reads or sizes by the count
+ * (rfsgpu_n_particles, the getters and setters, exports, ...) first wait for the stream and take the count over; a further
+ * rfsgpu_fastslam_cycle_async does not (it is launched at max_particles and reads the count on the device), so cycles can be enqueued
+ * back to back.  A grown set that would exceed max_particles abandons its cycle and every cycle enqueued behind it: the state stays
+ * what it was before that cycle, and the next synchronising call returns RFSGPU_ERR_CAPACITY once.
+ *
+ * RFSGPU_ERR_UNSUPPORTED, state untouched: batch handles, shards of a group, the Victoria Park model, landmark candidate lists
+ * (landmarkCandidateMeasurementCountThreshold != 1), maxNDataAssocHypotheses outside [1, 16], rfsgpu_max_particles(f) >
+ * RFSGPU_FASTSLAM_CYCLE_MAX_PARTICLES (the resampling kernel holds the whole filter in LDS). */
+#define RFSGPU_FASTSLAM_CYCLE_MAX_PARTICLES 2048
+int rfsgpu_fastslam_cycle_async(rfsgpu_filter *f, int predict, const double *z, int n_z, double u01, int n_init);
+/* What the last rfsgpu_fastslam_cycle_async did (synchronises): the count after its update, the count after its resampling, whether
+ * that fired, N_eff (0 where the test did not run), parent[k] of the update for the *n_after_update grown slots (what
+ * rfsgpu_particle_parents gives after rfsgpu_fastslam_update), plan[k] for the *n_after_resample slots (the slot -- of the grown set
+ * -- that slot k now holds a copy of; k itself where it kept its particle or nothing fired).  Any pointer may be NULL; max_n: entries
+ * of parent and plan.  A cycle without measurements reports the unchanged count, identity arrays and no resampling. */
+int rfsgpu_fastslam_last_cycle(rfsgpu_filter *f, int *n_after_update, int *n_after_resample, int *fired, double *n_eff, int *parent,
+                               int *plan, int max_n);
+/* ParticleFilter::resample's thresholds for rfsgpu_fastslam_cycle_async: no resampling while N_eff > eff_n && N_eff / n >
+ * eff_n_percent.  Default: n_particles / 4 and 0.25 (ParticleFilter.hpp:232-233). */
+int rfsgpu_fastslam_set_resampling(rfsgpu_filter *f, double eff_n, double eff_n_percent);
+
 /* ---- [batch] many independent 2-D RB-PHD or FastSLAM filters in one handle (outside the STABLE CORE) -------------------------
  * A batch handle holds n_filters independent range-bearing filters of n_per_filter particles each, stepped together: one cycle is
  * one fused step launch + one post launch for all of them.  Particle slots are global -- filter b owns slots

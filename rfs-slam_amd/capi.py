@@ -128,7 +128,7 @@ ABI_SYMBOLS = [
     "update_async", "kernel_time_stats", "post_kernel_avg_ns", "set_step_timing_stride", "step_launch_order",
     "default_fastslam_config", "set_fastslam_config", "get_fastslam_config", "fastslam_update",
     "normalize_weights_parts", "create_ex", "n_particles", "max_particles", "resample_apply_n",
-    "fastslam_set_resample_occured", "particle_parents", "vp_probe_pd",
+    "fastslam_set_resample_occured", "particle_parents", "vp_probe_pd", "fastslam_cycle_async", "fastslam_last_cycle", "fastslam_set_resampling",
     "slab_row_bytes", "export_slab_rows", "import_slab_rows", "weights_device_ptr", "step_async", "set_step_inputs_async", "predict_map_async", "set_phase_timing", "static_steps_async", "propagate_ackerman_async", "propagate_ackerman_run_async", "set_partition_mode", "get_partition_mode",
     "set_birth_inheritance", "get_birth_inheritance", "get_particle_ids", "set_particle_ids", "resample_occured", "get_unused_masks", "set_unused_masks", "has_birth_candidates", "predict_map_level", "murty_partition_sums", "partition_likelihoods", "cycle_async", "update_io", "step_async_deferred", "step_async_trailing", "collective_gate", "collective_publish", "collective_probe",
     "group_create", "group_destroy", "group_last_error", "group_n_shards", "group_n_particles", "group_shard", "group_locate",
@@ -282,6 +282,27 @@ class CFilter:
         """FastSLAM::updateMap for every particle (:387-418); resampleWithMapCopy stays with the caller."""
         Z = _f64(Z).reshape(-1, self.dz)
         self._call("fastslam_update", self._ptr(Z), C.c_int(Z.shape[0]))
+
+    def fastslam_cycle_async(self, Z, u01, n_init, predict=False):
+        """One whole FastSLAM::update (association, particle copies, correction, map management, resampleWithMapCopy) enqueued on the
+        handle's stream; nothing is read back.  The particle count is the device's until the next call that synchronises."""
+        Z = _f64(Z).reshape(-1, self.dz)
+        self._call("fastslam_cycle_async", C.c_int(1 if predict else 0), self._ptr(Z), C.c_int(Z.shape[0]), C.c_double(float(u01)), C.c_int(int(n_init)))
+
+    def fastslam_last_cycle(self):
+        """What the last fastslam_cycle_async did (synchronises): dict of n_after_update, n_after_resample, fired, n_eff, parent
+        (slot -> the slot it was copied from by the update, over the grown set) and plan (slot -> the grown-set slot it now holds)."""
+        cap = self.max_particles
+        na, nr, fired, neff = C.c_int(), C.c_int(), C.c_int(), C.c_double()
+        parent = np.empty(cap, dtype=np.int32)
+        plan = np.empty(cap, dtype=np.int32)
+        self._call("fastslam_last_cycle", C.byref(na), C.byref(nr), C.byref(fired), C.byref(neff), self._ptr(parent), self._ptr(plan), C.c_int(cap))
+        return {"n_after_update": na.value, "n_after_resample": nr.value, "fired": bool(fired.value), "n_eff": neff.value,
+                "parent": parent[:na.value].copy(), "plan": plan[:nr.value].copy()}
+
+    def fastslam_set_resampling(self, eff_n, eff_n_percent):
+        """ParticleFilter::resample's two N_eff thresholds for fastslam_cycle_async."""
+        self._call("fastslam_set_resampling", C.c_double(float(eff_n)), C.c_double(float(eff_n_percent)))
 
     def set_model_rngbrg(self, R, Pd, c, rmax, rmin, rbuf):
         m = RngBrgConfig()

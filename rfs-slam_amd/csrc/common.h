@@ -118,6 +118,20 @@ struct BirthLevel {
   __device__ bool mine(int i) const { return level == nullptr || level[i] == cur; }
 };
 
+// The live particle count of a handle whose count is known to the device only (rfsgpu_fastslam_cycle_async, fastslam_cycle.h): a
+// kernel that is given one is launched at the handle's capacity, and a wave for a slot at or beyond *n -- or any wave once *ovf is
+// set (the grown set would not have fitted: the cycle is abandoned) -- leaves before it touches memory.  Kernels take it as an
+// optional trailing argument (a parameter pack that is empty for every other caller: those instantiations compile as before).
+struct LiveCount {
+  const int *n;     // [1] live particle count
+  const int *ovf;   // [1] != 0: the cycle overflowed max_particles
+};
+template <typename T>
+__device__ __forceinline__ const T &pack_first(const T &a) { return a; }
+__device__ __forceinline__ bool live_beyond(const LiveCount &L, int slot) {
+  return __builtin_amdgcn_readfirstlane(*L.ovf) != 0 || slot >= __builtin_amdgcn_readfirstlane(*L.n);
+}
+
 // Section timing for kernel tuning (tools/kernel_sections.py builds a separate -DRFS_PROFILE library):
 // particle `RFS_PROFILE_PARTICLE`'s lane 0 stamps s_memtime at section boundaries.
 #ifdef RFS_PROFILE

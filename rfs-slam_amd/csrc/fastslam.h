@@ -540,12 +540,15 @@ __device__ inline bool fs_append(const Buffers &B, int cur, int i, int &n, const
 #define FS_NEWLM_WPB 4
 // BATCH: one more argument, the FsBatchArg tables; the wave reads its filter's Params, FsParams, nZ and measurement set there and
 // stops when the filter has no measurements.  The other instantiations take no such argument and compile as before.
+// Without BATCH the one further argument is a LiveCount (common.h), as for gm_prune_kernel.
 template <int D, bool BATCH = false, typename... TBatch>
 __global__ __launch_bounds__(64 * FS_NEWLM_WPB) void fs_new_landmarks_kernel(Buffers B, Params P, FsParams F, int cur, int nZ, TBatch... batchArg) {
   const int wave = threadIdx.x >> 6;
   const int lane = threadIdx.x & 63;
   const int i = __builtin_amdgcn_readfirstlane(blockIdx.x * FS_NEWLM_WPB + wave);
-  if (i >= B.N) return;
+  if constexpr (!BATCH && sizeof...(TBatch) == 1) {   // a LiveCount (common.h): the count lives on the device
+    if (live_beyond(batch_first_arg(batchArg...), i)) return;
+  } else if (i >= B.N) return;
   // The filter's Params and measurement set are read in place (Pb, Zb) where the single filter reads its kernel arguments: copied
   // into the arguments they went to scratch (169 VGPRs + 168 B per lane), and read through one reference for both forms the single
   // filter's instantiations moved by two VGPRs.  FsParams is small and is copied.

@@ -15,6 +15,7 @@
 //                    over the waves, the wave-parallel Hungarian solver of hungarian_wave.h inside).
 //                    Leaves per particle: the in-range list, the table, nH and the nH assignments (HBM).
 //  (host)            slots of the copies, in particle order: pi[h] = nParticles_ - h after each particle's copies (:543-556)
+//                    -- or fs_mh_plan_kernel (fastslam_cycle.h) on the device, for rfsgpu_fastslam_cycle_async
 //  fs_mh_copy        one workgroup per new slot: the source particle's map, counters, pose, weight / nH (+ candidates when
 //                    the previous update resampled, :551-553)
 //  fs_mh_apply       one wavefront per (slot, hypothesis): KF correction, existence log-odds, particle weight (:559-604,696)
@@ -78,10 +79,15 @@ __device__ inline void fs_mh_carve(unsigned char *base, const FsMhLayout &L, Mur
 }
 
 // errBits: ERRBIT_MURTY when the table is larger than FSMH_N or Murty runs out of nodes.
-template <int D>
+// live (here and in the kernels below): nothing, or a LiveCount (common.h) for a launch at the handle's capacity whose particle count
+// is on the device (fastslam_cycle.h); a workgroup beyond it leaves before it touches memory.
+template <int D, typename... TLive>
 __global__ __launch_bounds__(64 * FSMH_WAVES) __attribute__((amdgpu_waves_per_eu(D == 2 ? 4 : 3)))   // 2-D: <= 128 VGPRs, 8 workgroups per CU, 2048 particles at once
 void fs_mh_associate_kernel(Buffers B, Params P, FsParams F, int cur, int nZ, int kmax, double maxDiff,
-                                                                        unsigned char *arena) {
+                                                                        unsigned char *arena, TLive... live) {
+  if constexpr (sizeof...(TLive) == 1) {
+    if (live_beyond(pack_first(live...), (int)blockIdx.x)) return;     // (workgroup-uniform)
+  }
   __shared__ double sZ[3 * RFSGPU_MAX_Z];
   __shared__ __align__(16) unsigned char sPdScratch[(D == 3) ? ((VP_PD_SCRATCH_BYTES + 15) & ~15) : 16];
   __shared__ double sTile[FSMH_WAVES][FSMH_LDS_N * FSMH_LDS_N];
@@ -247,7 +253,12 @@ void fs_mh_associate_kernel(Buffers B, Params P, FsParams F, int cur, int nZ, in
 }
 
 // One workgroup per NEW slot: ParticleFilter::copyParticle (ParticleFilter.hpp:273-294) of slot src -> slot dst.
-__global__ __launch_bounds__(256) void fs_mh_copy_kernel(Buffers B, int cur, const int *dstSlot, const int *srcSlot, int copyCand, int poseCovStride) {
+// live: its count is the number of copies.
+template <typename... TLive>
+__global__ __launch_bounds__(256) void fs_mh_copy_kernel(Buffers B, int cur, const int *dstSlot, const int *srcSlot, int copyCand, int poseCovStride, TLive... live) {
+  if constexpr (sizeof...(TLive) == 1) {
+    if (live_beyond(pack_first(live...), (int)blockIdx.x)) return;
+  }
   const int d = dstSlot[blockIdx.x], s = srcSlot[blockIdx.x];
   const int n = B.count[s];
   for (int pl = 0; pl < B.npl; pl++) {
@@ -276,21 +287,27 @@ __global__ __launch_bounds__(256) void fs_mh_copy_kernel(Buffers B, int cur, con
 }
 // weight of every hypothesis slot of a multiplied particle := weight / nH (:545-548)
 // phase 0: the copies read the source's undivided weight; phase 1 (a later launch): the sources divide their own
-__global__ void fs_mh_split_weights_kernel(double *weight, const int *slotSrc, const int *slotNH, int nSlots, int phase) {
+template <typename... TLive>
+__global__ void fs_mh_split_weights_kernel(double *weight, const int *slotSrc, const int *slotNH, int nSlots, int phase, TLive... live) {
   const int s = blockIdx.x * blockDim.x + threadIdx.x;
-  if (s >= nSlots) return;
+  if constexpr (sizeof...(TLive) == 1) {
+    if (live_beyond(pack_first(live...), s)) return;
+  } else if (s >= nSlots) return;
   const int nh = slotNH[s], src = slotSrc[s];
   if (nh > 1 && ((phase == 0) == (src != s))) weight[s] = weight[src] / nh;
 }
 
 // One wavefront per slot: the update of one particle under one hypothesis (:559-604, :696-697).
-template <int D>
+template <int D, typename... TLive>
 __global__ __launch_bounds__(64) void fs_mh_apply_kernel(Buffers B, Params P, FsParams F, int cur, int nZ, const int *slotSrc, const int *slotHyp,
-                                                       const unsigned char *arena) {
+                                                       const unsigned char *arena, TLive... live) {
   __shared__ double sZ[3 * RFSGPU_MAX_Z];
   __shared__ double sC[FSMH_N];
   const int lane = threadIdx.x;
   const int i = blockIdx.x;
+  if constexpr (sizeof...(TLive) == 1) {
+    if (live_beyond(pack_first(live...), i)) return;
+  }
   const int src = slotSrc[i], h = slotHyp[i];
   if (h < 0) return;  // no hypothesis: the particle is left untouched
   for (int t = lane; t < D * nZ; t += 64) sZ[t] = B.Z[t];

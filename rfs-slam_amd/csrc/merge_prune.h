@@ -1074,6 +1074,8 @@ __host__ __device__ inline size_t gm_prune_lds_bytes_per_wave(int cap) {
 // BATCH (a FastSLAM filter batch, fastslam.h): one more argument, the FsBatchArg tables.  The wave's filter prunes with its own threshold
 // when it has measurements and its gate says so; else its mixture moves unchanged to dst, because the batch flips `cur` as one.  The
 // other instantiations take no such argument and compile as before: every difference is behind `if constexpr`.
+// Without BATCH the one further argument is a LiveCount (common.h): the launch covers the handle's capacity and a wave beyond the
+// live count leaves at once (the multi-hypothesis FastSLAM device cycle).
 // What this kernel reads of the argument (FsBatchArg, fastslam.h, which is included after this file): nPer, the particles per filter,
 // and of filt[particle / nPer] the fields nZ (this cycle's measurements), prune (the filter's gate) and pruneT (its threshold).
 template <typename T>
@@ -1084,7 +1086,9 @@ __global__ __launch_bounds__(WPB * 64) void gm_prune_kernel(Buffers B, Params P,
   const int wave = threadIdx.x >> 6;
   const int lane = threadIdx.x & 63;
   const int i = __builtin_amdgcn_readfirstlane(blockIdx.x * WPB + wave);
-  if (i >= B.N) return;
+  if constexpr (!BATCH && sizeof...(TBatch) == 1) {   // a LiveCount (common.h): the count lives on the device
+    if (live_beyond(batch_first_arg(batchArg...), i)) return;
+  } else if (i >= B.N) return;
   if constexpr (BATCH) {
     const auto &A = batch_first_arg(batchArg...);
     const auto &T = A.filt[__builtin_amdgcn_readfirstlane(i / A.nPer)];
@@ -1160,8 +1164,15 @@ __global__ __launch_bounds__(WPB * 64) void gm_prune_kernel(Buffers B, Params P,
 // ---- small kernels ---------------------------------------------------------------------------------
 
 // {sum w, sum w^2} of this shard; one block, deterministic tree.
-__global__ __launch_bounds__(1024) void weight_sums_kernel(const double *w, int N, double *out2) {
+// live: nothing, or a LiveCount (common.h) whose count replaces N; after an overflow nothing is written.
+template <typename... TLive>
+__global__ __launch_bounds__(1024) void weight_sums_kernel(const double *w, int N, double *out2, TLive... live) {
   __shared__ double s0[16], s1[16];
+  if constexpr (sizeof...(TLive) == 1) {
+    const LiveCount &L = pack_first(live...);
+    if (__builtin_amdgcn_readfirstlane(*L.ovf) != 0) return;     // (workgroup-uniform)
+    N = __builtin_amdgcn_readfirstlane(*L.n);
+  }
   double a = 0, b = 0;
   for (int k = threadIdx.x; k < N; k += 1024) { double v = w[k]; a += v; b += v * v; }
   a = wave_sum(a); b = wave_sum(b);
@@ -1174,7 +1185,12 @@ __global__ __launch_bounds__(1024) void weight_sums_kernel(const double *w, int 
   }
 }
 // sumDev: nParts pairs {sum w, sum w^2} (one per shard sharing the normalisation); the divisor is their sum, in order
-__global__ void normalize_kernel(double *w, int N, double sum, const double *sumDev, int nParts) {
+template <typename... TLive>
+__global__ void normalize_kernel(double *w, int N, double sum, const double *sumDev, int nParts, TLive... live) {
+  if constexpr (sizeof...(TLive) == 1) {
+    if (live_beyond(pack_first(live...), blockIdx.x * blockDim.x + threadIdx.x)) return;
+    N = 0x7fffffff;
+  }
   double sdiv = sum;
   if (sumDev) {
     sdiv = sumDev[0];
@@ -1190,8 +1206,13 @@ __global__ void set_weights_kernel(double *w, int N, double v) {
 
 // Resample copy: slot k takes slot src[k]'s mixture (Particle::copy -> GaussianMixture copy ctor).
 // One block per destination slot; sources are slots that keep themselves, so in-place is hazard-free.
-__global__ __launch_bounds__(256) void resample_gather_kernel(Buffers B, int cur, const int *srcSlot, int poseCovStride, int mapOnly) {
+// live: nothing, or a LiveCount (common.h): destination slots at or beyond the live count are left alone.
+template <typename... TLive>
+__global__ __launch_bounds__(256) void resample_gather_kernel(Buffers B, int cur, const int *srcSlot, int poseCovStride, int mapOnly, TLive... live) {
   const int k = blockIdx.x;
+  if constexpr (sizeof...(TLive) == 1) {
+    if (live_beyond(pack_first(live...), k)) return;
+  }
   const int s = srcSlot[k];
   if (s == k) return;
   const int n = B.count[s];

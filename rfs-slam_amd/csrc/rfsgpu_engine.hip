@@ -25,6 +25,7 @@
 #include "birth.h"
 #include "fastslam.h"
 #include "fastslam_mh.h"
+#include "fastslam_cycle.h"
 #include "motion.h"
 #include "map_metric.h"
 #include "batch_loop.h"
@@ -117,6 +118,22 @@ struct rfsgpu_filter {
   int *mhInts = nullptr;              // [5][Ncap] slotSrc, slotHyp, slotNH, copyDst, copySrc
   bool fsResampleOccured = false;     // FastSLAM::resampleOccured_ of the previous update (rfsgpu_fastslam_set_resample_occured)
   std::vector<int> parents;           // source slot of every particle after the last FastSLAM update (identity when none multiplied)
+  // rfsgpu_fastslam_cycle_async (fastslam_cycle.h): the whole FastSLAM::update on the device
+  unsigned char *mhcBlock = nullptr;  // device: the FsCycleState block
+  unsigned char *hMhcBlock = nullptr; // pinned: where it lands when the host next synchronises
+  int *mhcInts = nullptr;             // [4][Ncap] slotHyp, slotNH, copyDst, copySrc (slotSrc is in the block)
+  FsCycleState mhc{};                 // the block's device view
+  bool mhcPending = false;            // cycles are enqueued and N, fsResampleOccured, the ids and `parents` are behind the device
+  bool mhcIdsDirty = true;            // pid / ppid changed on the host since the device copy was written
+  bool mhcHave = false;               // a cycle has run (rfsgpu_fastslam_last_cycle has something to report)
+  bool mhcLastEmpty = false;          // the last enqueued cycle had no measurements
+  int mhcStashedRc = 0;               // a pending cycle's error met by a call that cannot return it: returned by the next call that can
+  std::vector<char> mhcFlips;         // per pending cycle with measurements: whether it flipped `cur` (its prune ran)
+  int mhcDone = 0;                    // FSC_DONE as last read
+  double fsEffN = -1.0, fsEffNPercent = -1.0;   // rfsgpu_fastslam_set_resampling (negative: n_particles / 4 and 1 / 4 at the first cycle)
+  int mhcNGrown = 0, mhcNAfter = 0, mhcFired = 0;   // the last cycle, as resolved
+  double mhcNEff = 0.0;
+  std::vector<int> mhcPlan;
   // birth-state inheritance after a resampling (rfsgpu_set_birth_inheritance; RBPHDFilter.hpp:1005-1011)
   int inheritMode = RFSGPU_INHERIT_REFERENCE;
   std::vector<int> pid, ppid;         // Particle::id_ / idParent_ of the particle in each slot (ParticleFilter.hpp:446-479)
@@ -208,7 +225,18 @@ struct rfsgpu_filter {
     }                                                                                      \
   } while (0)
 
-#define CHECK_HANDLE(f) \
+// (a handle whose particle count is still on the device -- rfsgpu_fastslam_cycle_async -- takes it over first: every entry point
+//  that reads or sizes by N starts here)
+static int mhc_resolve(rfsgpu_filter *f);
+#define CHECK_HANDLE(f)                                                       \
+  if (!(f)) return RFSGPU_ERR_INVALID;                                        \
+  if ((f)->mhcPending || (f)->mhcStashedRc) {                                 \
+    const int rcMhc_ = mhc_resolve(f);                                        \
+    if (rcMhc_ != RFSGPU_OK) return rcMhc_;                                   \
+  }
+// ... and the setters that neither read nor size by N (their values travel by value with each launch) start here: a host that
+// pushes its configuration before every cycle does not wait for the cycles in flight
+#define CHECK_HANDLE_HOST(f) \
   if (!(f)) return RFSGPU_ERR_INVALID;
 
 static int fail(rfsgpu_filter *f, int code, const char *msg) {
@@ -458,7 +486,7 @@ void rfsgpu_destroy(rfsgpu_filter *f) {
   hipFree(f->snapSlab); hipFree(f->snapWeight); hipFree(f->snapCount); hipFree(f->snapFov); hipFree(f->snapUnused);
   for (auto &r : f->stateRing) { hipFree(r.slab); hipFree(r.weight); hipFree(r.count); hipFree(r.fov); hipFree(r.unused); }
   hipFree(B.slab[0]); hipFree(B.slab[1]); hipFree(B.count); hipFree(B.pose); hipFree(f->poseAlt); hipFree(f->dCollSeq); if (f->vpCost) hipFree(f->vpCost); if (f->vpOrder) hipFree(f->vpOrder); hipFree(B.poseCov); hipFree(B.weight);
-  hipFree(B.unusedMask); hipFree(B.nInFov); hipFree(B.err); hipFree(B.Z); hipFree(f->ownSums); hipFree(f->dSrcSlot); if (f->dRowSlots) hipFree(f->dRowSlots); if (f->fsArena) hipFree(f->fsArena); if (f->mhArena) hipFree(f->mhArena); if (f->mhInts) hipFree(f->mhInts);
+  hipFree(B.unusedMask); hipFree(B.nInFov); hipFree(B.err); hipFree(B.Z); hipFree(f->ownSums); hipFree(f->dSrcSlot); if (f->dRowSlots) hipFree(f->dRowSlots); if (f->fsArena) hipFree(f->fsArena); if (f->mhArena) hipFree(f->mhArena); if (f->mhInts) hipFree(f->mhInts); if (f->mhcBlock) hipFree(f->mhcBlock); if (f->mhcInts) hipFree(f->mhcInts); if (f->hMhcBlock) hipHostFree(f->hMhcBlock);
   if (f->dInhParent) hipFree(f->dInhParent);
   if (f->dInhLevel) hipFree(f->dInhLevel);
   hipFree(f->inhTmp.unused); hipFree(f->inhTmp.count); hipFree(f->inhTmp.sup); hipFree(f->inhTmp.chk); hipFree(f->inhTmp.mean); hipFree(f->inhTmp.cov);  // (hipFree(nullptr) is a no-op)
@@ -487,7 +515,7 @@ void rfsgpu_destroy(rfsgpu_filter *f) {
 const char *rfsgpu_last_error(const rfsgpu_filter *f) { return f ? f->err.c_str() : "null handle"; }
 
 int rfsgpu_set_filter_config(rfsgpu_filter *f, const rfsgpu_filter_config *c) {
-  CHECK_HANDLE(f);
+  CHECK_HANDLE_HOST(f);
   if (!c) return RFSGPU_ERR_INVALID;
   f->cfg = *c;
   rebuild_params(f);
@@ -2040,7 +2068,15 @@ int rfsgpu_normalize_weights_parts(rfsgpu_filter *f, double sum, const void *sum
   f->timing.particleResample_cpu += now_ns() - t0;
   return RFSGPU_OK;
 }
-int rfsgpu_n_particles(const rfsgpu_filter *f) { return f ? f->N : -1; }
+int rfsgpu_n_particles(const rfsgpu_filter *f) {
+  if (!f) return -1;
+  if (f->mhcPending) {      // the count is on the device: take it over; an error of the pending cycles goes to the next call that returns a status
+    rfsgpu_filter *g = const_cast<rfsgpu_filter *>(f);
+    const int rc = mhc_resolve(g);
+    if (rc != RFSGPU_OK) g->mhcStashedRc = rc;
+  }
+  return f->N;
+}
 int rfsgpu_max_particles(const rfsgpu_filter *f) { return f ? f->Ncap : -1; }
 int rfsgpu_resample_apply(rfsgpu_filter *f, const int *src_slot) { return f ? rfsgpu_resample_apply_n(f, src_slot, f->N) : RFSGPU_ERR_INVALID; }
 int rfsgpu_resample_apply_n(rfsgpu_filter *f, const int *src_slot, int n_out) {
@@ -2065,6 +2101,7 @@ int rfsgpu_resample_apply_n(rfsgpu_filter *f, const int *src_slot, int n_out) {
   }
   f->resampleOccured = true;
   f->externalAck = false;
+  f->mhcIdsDirty = true;
   hipSetDevice(f->device);
   long long t0 = now_ns();
   // Round 6: stream-ordered.  The plan goes into a slot of the pinned staging ring (the caller's buffer is free when the call returns) and
@@ -2130,6 +2167,7 @@ int rfsgpu_set_particle_ids(rfsgpu_filter *f, const int *id, const int *parent_i
     if (rc != RFSGPU_OK) return rc;
   }
   for (int k = 0; k < f->N; k++) { if (id) f->pid[k] = id[k]; if (parent_id) f->ppid[k] = parent_id[k]; }
+  f->mhcIdsDirty = true;
   if (f->bDevRoute) {
     hipSetDevice(f->device);
     HIPCHK(hipMemcpyAsync(f->BL.pid, f->pid.data(), (size_t)f->N * sizeof(int), hipMemcpyHostToDevice, f->stream));
@@ -2412,7 +2450,7 @@ void rfsgpu_default_fastslam_config(rfsgpu_fastslam_config *c) {  // constructor
   c->pruningMeasurementsThreshold = 0;
 }
 int rfsgpu_set_fastslam_config(rfsgpu_filter *f, const rfsgpu_fastslam_config *cfg) {
-  CHECK_HANDLE(f);
+  CHECK_HANDLE_HOST(f);
   REFUSE_ON_BATCH(f, "FastSLAM");
   if (!cfg) return RFSGPU_ERR_INVALID;
   f->fs = *cfg;
@@ -2535,6 +2573,171 @@ int rfsgpu_particle_parents(rfsgpu_filter *f, int *parent, int max_n) {
   CHECK_HANDLE(f);
   if (!parent || max_n < f->N) return RFSGPU_ERR_INVALID;
   for (int k = 0; k < f->N; k++) parent[k] = (k < (int)f->parents.size()) ? f->parents[k] : k;
+  return RFSGPU_OK;
+}
+// ---- the whole FastSLAM::update on the device (fastslam_cycle.h) ------------------------------------------------------------------
+// The particle count comes back: one stream-ordered copy of the cycle block into pinned memory, then the wait.  Cycles that an
+// overflow abandoned did not prune, so the slab flips the host made for them are taken back.
+static int mhc_resolve(rfsgpu_filter *f) {
+  if (f->mhcStashedRc) { const int rc = f->mhcStashedRc; f->mhcStashedRc = 0; return rc; }   // (f->err still holds its message)
+  if (!f->mhcPending) return RFSGPU_OK;
+  f->mhcPending = false;
+  hipSetDevice(f->device);
+  HIPCHK(hipMemcpyAsync(f->hMhcBlock, f->mhcBlock, fs_cycle_state_bytes(f->Ncap), hipMemcpyDeviceToHost, f->stream));
+  const int rc = check_device_errors(f);   // waits for the stream
+  harvest_async(f);
+  FsCycleState H;
+  fs_cycle_carve(f->hMhcBlock, f->Ncap, H);
+  const int done = H.w[FSC_DONE] - f->mhcDone;      // of the pending cycles with measurements, the first `done` ran
+  f->mhcDone = H.w[FSC_DONE];
+  for (size_t k = (size_t)std::max(done, 0); k < f->mhcFlips.size(); k++) f->cur ^= f->mhcFlips[k] ? 1 : 0;
+  const bool lastRan = f->mhcFlips.empty() || done >= (int)f->mhcFlips.size();
+  f->mhcFlips.clear();
+  const int n = H.w[FSC_N];
+  if (n < 1 || n > f->Ncap) return fail(f, RFSGPU_ERR_HIP, "fastslam_cycle: the device returned a particle count outside [1, max_particles]");
+  f->N = n;
+  f->B.N = n;
+  f->fsResampleOccured = H.w[FSC_RESAMPLED] != 0;
+  ensure_ids(f);
+  memcpy(f->pid.data(), H.pid, (size_t)f->Ncap * sizeof(int));
+  memcpy(f->ppid.data(), H.ppid, (size_t)f->Ncap * sizeof(int));
+  f->mhcIdsDirty = false;
+  if (f->mhcLastEmpty && lastRan) {
+    f->mhcNGrown = f->mhcNAfter = n; f->mhcFired = 0; f->mhcNEff = 0.0;
+    f->mhcPlan.resize(n);
+    f->parents.resize(n);
+    for (int k = 0; k < n; k++) { f->mhcPlan[k] = k; f->parents[k] = k; }
+  } else if (lastRan) {
+    f->mhcNGrown = H.w[FSC_NGROWN]; f->mhcNAfter = n; f->mhcFired = H.w[FSC_FIRED]; f->mhcNEff = H.nEff[0];
+    const int ng = std::min(std::max(f->mhcNGrown, 0), f->Ncap);
+    f->parents.assign(H.slotSrc, H.slotSrc + ng);
+    f->mhcPlan.assign(H.plan, H.plan + n);
+    if (f->mhcFired) { f->resampleOccured = true; f->externalAck = false; }
+  }
+  if (H.w[FSC_OVF]) {
+    HIPCHK(hipMemsetAsync(f->mhc.w + FSC_OVF, 0, sizeof(int), f->stream));
+    if (rc == RFSGPU_OK)
+      return fail(f, RFSGPU_ERR_CAPACITY, "fastslam_cycle: the particle copies of a multi-hypothesis update exceed max_particles (rfsgpu_create_ex); that cycle and "
+                                          "those enqueued behind it were abandoned, the state is the one before it");
+  }
+  return rc;
+}
+int rfsgpu_fastslam_set_resampling(rfsgpu_filter *f, double eff_n, double eff_n_percent) {
+  CHECK_HANDLE_HOST(f);
+  REFUSE_ON_BATCH(f, "rfsgpu_fastslam_set_resampling (use rfsgpu_batch_set_resampling)");
+  if (!(eff_n >= 0.0) || !(eff_n_percent >= 0.0)) return fail(f, RFSGPU_ERR_INVALID, "fastslam_set_resampling: thresholds must be non-negative");
+  f->fsEffN = eff_n;
+  f->fsEffNPercent = eff_n_percent;
+  return RFSGPU_OK;
+}
+int rfsgpu_fastslam_cycle_async(rfsgpu_filter *f, int predict, const double *z, int n_z, double u01, int n_init) {
+  if (!f) return RFSGPU_ERR_INVALID;
+  if (f->mhcStashedRc) return mhc_resolve(f);
+  REFUSE_ON_BATCH(f, "rfsgpu_fastslam_cycle_async");
+  if (f->groupShard) return fail(f, RFSGPU_ERR_UNSUPPORTED, "fastslam_cycle: not available on a shard of an rfsgpu_group (the particle count would be known to one device only)");
+  if (f->D != 2) return fail(f, RFSGPU_ERR_UNSUPPORTED, "fastslam_cycle: the Victoria Park model is not served (the 2-D range-bearing model only)");
+  if (f->fs.landmarkCandidateMeasurementCountThreshold != 1u)
+    return fail(f, RFSGPU_ERR_UNSUPPORTED, "fastslam_cycle: landmarkCandidateMeasurementCountThreshold must be 1 (landmark candidate lists are not served on this route)");
+  if (f->fs.maxNDataAssocHypotheses < 1 || f->fs.maxNDataAssocHypotheses > FSMH_MAX_HYP)
+    return fail(f, RFSGPU_ERR_UNSUPPORTED, "fastslam_cycle: maxNDataAssocHypotheses must be in [1, 16]");
+  if (f->Ncap > RFSGPU_FASTSLAM_CYCLE_MAX_PARTICLES)
+    return fail(f, RFSGPU_ERR_UNSUPPORTED, "fastslam_cycle: max_particles exceeds RFSGPU_FASTSLAM_CYCLE_MAX_PARTICLES (2048): the resampling kernel holds the whole filter in LDS");
+  if (n_z < 0 || n_z > RFSGPU_MAX_Z) return fail(f, RFSGPU_ERR_INVALID, "at most RFSGPU_MAX_Z measurements per update");
+  if (n_z > 0 && !z) return fail(f, RFSGPU_ERR_INVALID, "null measurement buffer");
+  if (!(u01 >= 0.0 && u01 < 1.0)) return fail(f, RFSGPU_ERR_INVALID, "fastslam_cycle: u01 must lie in [0, 1)");
+  if (n_init < 0) return fail(f, RFSGPU_ERR_INVALID, "fastslam_cycle: negative n_init");
+  hipSetDevice(f->device);
+  const int Ncap = f->Ncap;
+  const FsMhLayout L = fs_mh_layout();
+  if (!f->mhArena) HIPCHK(hipMalloc(&f->mhArena, (size_t)Ncap * L.total));
+  if (!f->mhcInts) HIPCHK(hipMalloc(&f->mhcInts, (size_t)4 * Ncap * sizeof(int)));
+  if (!f->hMhcBlock) HIPCHK(hipHostMalloc(&f->hMhcBlock, fs_cycle_state_bytes(Ncap)));
+  if (!f->mhcBlock) {
+    HIPCHK(hipMalloc(&f->mhcBlock, fs_cycle_state_bytes(Ncap)));
+    HIPCHK(hipMemsetAsync(f->mhcBlock, 0, fs_cycle_state_bytes(Ncap), f->stream));
+    fs_cycle_carve(f->mhcBlock, Ncap, f->mhc);
+    f->mhcIdsDirty = true;
+  }
+  if (f->fsEffN < 0.0) { f->fsEffN = f->N / 4.0; f->fsEffNPercent = 0.25; }   // ParticleFilter.hpp:232
+  const FsCycleState &S = f->mhc;
+  if (!f->mhcPending && f->mhcIdsDirty) {
+    ensure_ids(f);
+    HIPCHK(hipMemcpyAsync(S.pid, f->pid.data(), (size_t)Ncap * sizeof(int), hipMemcpyHostToDevice, f->stream));
+    HIPCHK(hipMemcpyAsync(S.ppid, f->ppid.data(), (size_t)Ncap * sizeof(int), hipMemcpyHostToDevice, f->stream));
+    f->mhcIdsDirty = false;
+  }
+  f->holes = false;
+  f->fastSlamHandle = true;
+  f->mhcHave = true;
+  const LiveCount live{S.w + FSC_N, S.w + FSC_OVF};
+  fs_cycle_begin_kernel<<<1, 64, 0, f->stream>>>(S, f->mhcPending ? -1 : f->N, f->mhcPending ? -1 : (f->fsResampleOccured ? 1 : 0), n_z == 0 ? 1 : 0);
+  if (predict) fs_cycle_static_step_kernel<<<(Ncap + 3) / 4, 256, 0, f->stream>>>(f->B, f->P, f->cur, live);
+  HIPCHK(hipGetLastError());
+  if (n_z == 0) {    // :399-402: the update is counted, nothing else happens
+    f->mhcLastEmpty = true;
+    if (!f->mhcPending) {       // (the count is still the host's: nothing to wait for)
+      f->mhcNGrown = f->mhcNAfter = f->N; f->mhcFired = 0; f->mhcNEff = 0.0;
+      f->mhcPlan.resize(f->N);
+      f->parents.resize(f->N);
+      for (int k = 0; k < f->N; k++) { f->mhcPlan[k] = k; f->parents[k] = k; }
+    }
+    return RFSGPU_OK;
+  }
+  int rc = stage_measurements(f, z, n_z);
+  if (rc != RFSGPU_OK) return rc;
+  const FsParams F = fs_params(f, n_z);
+  int *dSlotHyp = f->mhcInts, *dSlotNH = dSlotHyp + Ncap, *dDst = dSlotNH + Ncap, *dSrc = dDst + Ncap;
+  fs_mh_associate_kernel<2><<<Ncap, 64 * FSMH_WAVES, 0, f->stream>>>(f->B, f->P, F, f->cur, n_z, (int)f->fs.maxNDataAssocHypotheses, f->fs.maxDataAssocLogLikelihoodDiff,
+                                                                     f->mhArena, live);
+  fs_mh_plan_kernel<<<1, FS_CYCLE_THREADS, 0, f->stream>>>(f->mhArena, S, dSlotHyp, dSlotNH, dDst, dSrc, Ncap);
+  LiveCopy lc;
+  lc.n = S.w + FSC_NCOPY; lc.ovf = S.w + FSC_OVF; lc.copyCand = S.w + FSC_RESAMPLED;
+  fs_mh_copy_kernel<<<Ncap, 256, 0, f->stream>>>(f->B, f->cur, dDst, dSrc, 0, f->P.poseCovStride, lc);
+  fs_mh_split_weights_kernel<<<(Ncap + 255) / 256, 256, 0, f->stream>>>(f->B.weight, S.slotSrc, dSlotNH, 0, 0, live);
+  fs_mh_split_weights_kernel<<<(Ncap + 255) / 256, 256, 0, f->stream>>>(f->B.weight, S.slotSrc, dSlotNH, 0, 1, live);
+  fs_mh_apply_kernel<2><<<Ncap, 64, 0, f->stream>>>(f->B, f->P, F, f->cur, n_z, S.slotSrc, dSlotHyp, f->mhArena, live);
+  HIPCHK(hipGetLastError());
+  bool flipped = false;
+  if ((unsigned)n_z >= f->fs.pruningMeasurementsThreshold) {   // :611-612
+    Params Pp = f->P;
+    Pp.pruneT = f->fs.mapExistencePruneThreshold;
+    const size_t pb = gm_prune_lds_bytes_per_wave(f->cap);
+    if ((rc = set_lds(f, (gm_prune_kernel<4, false, false, LiveCount>), 4 * pb)) != RFSGPU_OK) return rc;
+    gm_prune_kernel<4, false, false, LiveCount><<<(Ncap + 3) / 4, 256, 4 * pb, f->stream>>>(f->B, Pp, f->cur, f->cur ^ 1, live);
+    HIPCHK(hipGetLastError());
+    f->cur ^= 1;
+    flipped = true;
+  }
+  fs_new_landmarks_kernel<2, false, LiveCount><<<(Ncap + FS_NEWLM_WPB - 1) / FS_NEWLM_WPB, 64 * FS_NEWLM_WPB, 0, f->stream>>>(f->B, f->P, F, f->cur, n_z, live);
+  // resampleWithMapCopy: the normalisation that ParticleFilter::resample starts with (or, where the gates keep it from running, the
+  // one of :743), the decision and the plan, the copies, and the second normalisation of a resample() that returned false
+  weight_sums_kernel<<<1, 1024, 0, f->stream>>>(f->B.weight, 0, f->dSums, live);
+  normalize_kernel<<<(Ncap + 255) / 256, 256, 0, f->stream>>>(f->B.weight, 0, 0.0, (const double *)f->dSums, 1, live);
+  FsShrinkArg A;
+  A.effN = f->fsEffN; A.effNPercent = f->fsEffNPercent; A.u01 = u01;
+  A.nInit = n_init; A.nMax = f->fs.nParticlesMax; A.nZ = n_z;
+  A.minUpdates = f->fs.minUpdatesBeforeResample; A.minMeasurements = f->fs.minMeasurementsBeforeResample;
+  fs_resample_shrink_kernel<<<1, FS_CYCLE_THREADS, 0, f->stream>>>(f->B.weight, S, A);
+  resample_gather_kernel<<<Ncap, 256, 0, f->stream>>>(f->B, f->cur, S.plan, f->P.poseCovStride, map_only(f), live);
+  const LiveCount renorm{S.w + FSC_RENORM_N, S.w + FSC_OVF};
+  weight_sums_kernel<<<1, 1024, 0, f->stream>>>(f->B.weight, 0, f->dSums, renorm);
+  normalize_kernel<<<(Ncap + 255) / 256, 256, 0, f->stream>>>(f->B.weight, 0, 0.0, (const double *)f->dSums, 1, renorm);
+  HIPCHK(hipGetLastError());
+  f->mhcFlips.push_back(flipped ? 1 : 0);
+  f->mhcLastEmpty = false;
+  f->mhcPending = true;
+  return RFSGPU_OK;
+}
+int rfsgpu_fastslam_last_cycle(rfsgpu_filter *f, int *n_after_update, int *n_after_resample, int *fired, double *n_eff, int *parent, int *plan, int max_n) {
+  CHECK_HANDLE(f);
+  if (!f->mhcHave) return fail(f, RFSGPU_ERR_INVALID, "fastslam_last_cycle: no rfsgpu_fastslam_cycle_async has run on this handle");
+  if ((parent && max_n < f->mhcNGrown) || (plan && max_n < f->mhcNAfter)) return fail(f, RFSGPU_ERR_INVALID, "fastslam_last_cycle: max_n is below the particle count");
+  if (n_after_update) *n_after_update = f->mhcNGrown;
+  if (n_after_resample) *n_after_resample = f->mhcNAfter;
+  if (fired) *fired = f->mhcFired;
+  if (n_eff) *n_eff = f->mhcNEff;
+  if (parent) for (int k = 0; k < f->mhcNGrown; k++) parent[k] = k < (int)f->parents.size() ? f->parents[k] : k;
+  if (plan) for (int k = 0; k < f->mhcNAfter; k++) plan[k] = f->mhcPlan[k];
   return RFSGPU_OK;
 }
 int rfsgpu_fastslam_update(rfsgpu_filter *f, const double *z, int n_z) {

@@ -257,7 +257,7 @@ class FastSLAM(RBPHDFilter):
     handle has room for nParticlesMax * max_hypotheses particles; `parents` (slot -> the particle it was copied from in the
     last update) and `last_resample_plan` let a caller holding poses follow the copies."""
 
-    def __init__(self, n_particles, device_id=0, gm_capacity=512, max_hypotheses=1, n_particles_max=None):
+    def __init__(self, n_particles, device_id=0, gm_capacity=512, max_hypotheses=1, n_particles_max=None, device_cycle=False):
         n_max = 3 * n_particles if n_particles_max is None else int(n_particles_max)    # FastSLAM.hpp:250
         cap = max(n_particles, n_max) * max(1, int(max_hypotheses)) if max_hypotheses > 1 else None
         super().__init__(n_particles, device_id=device_id, gm_capacity=gm_capacity, max_particles=cap)
@@ -266,6 +266,29 @@ class FastSLAM(RBPHDFilter):
         self.fs_config.maxNDataAssocHypotheses = max(1, int(max_hypotheses))
         self.parents = np.arange(n_particles, dtype=np.int32)
         self.last_resample_plan = None
+        # device_cycle: update_and_resample runs as one rfsgpu_fastslam_cycle_async (copy plan and resampleWithMapCopy on the device,
+        # no host round trip inside the cycle); the handle must hold max_particles <= 2048 and keep no landmark candidate lists
+        self.device_cycle = bool(device_cycle)
+        self.last_cycle = None
+
+    def cycle_async(self, Z, u01, predict=False):
+        """One whole FastSLAM::update enqueued, nothing read back (rfsgpu_fastslam_cycle_async): u01 is the draw a resampling would
+        use.  Cycles may follow one another without a synchronisation; sync_cycle() brings parents / last_resample_plan /
+        resampleOccured up to date."""
+        self.apply_config()
+        self.set_fastslam_config(self.fs_config)
+        self.fastslam_set_resampling(self.effNParticles_t, self.effNParticles_t_percent)
+        Z = np.asarray(Z, dtype=np.float64).reshape(-1, self.dz)
+        self.fastslam_cycle_async(Z, u01, self.n_init, predict)
+
+    def sync_cycle(self):
+        """The results of the last cycle_async (synchronises)."""
+        lc = self.fastslam_last_cycle()
+        self.last_cycle = lc
+        self.parents = lc["parent"]
+        self.resampleOccured = lc["fired"]
+        self.last_resample_plan = lc["plan"] if lc["fired"] else None
+        return lc
 
     # FastSLAM::predict (:362-385), map part: staticStep on every landmark, no births
     def predict_map(self, add_birth=False):
@@ -273,6 +296,20 @@ class FastSLAM(RBPHDFilter):
 
     # FastSLAM::update (:387-421) + resampleWithMapCopy (:708-735)
     def update_and_resample(self, Z, u01_fn=np.random.random):
+        if self.device_cycle:
+            # the draw is made whether or not the cycle resamples: the decision is the device's, and the host reads nothing before it.
+            # The two counters the gates use live on the device on this route; the host's copies follow them.
+            Z = np.asarray(Z, dtype=np.float64).reshape(-1, self.dz)
+            self.cycle_async(Z, float(u01_fn()))
+            self.nUpdatesSinceResample += 1
+            if Z.shape[0] == 0:
+                return False
+            self.nMeasurementsSinceResample += Z.shape[0]
+            lc = self.sync_cycle()
+            if lc["fired"]:
+                self.nUpdatesSinceResample = 0
+                self.nMeasurementsSinceResample = 0
+            return lc["fired"]
         self.apply_config()
         self.set_fastslam_config(self.fs_config)
         self.nUpdatesSinceResample += 1

@@ -1,7 +1,11 @@
 #!/usr/bin/env python3
 """FastSLAM 1.0 update rate -- not the headline metric (bench.py), a measurement for DESIGN.md.
 2000 particles, 200 landmarks over a 25 m disc, 30 measurements per update; state re-seeded every step.
-  python tools/fastslam_bench.py [--cpu]    (--cpu also times the oracle on the host cores)"""
+  python tools/fastslam_bench.py [--cpu]    (--cpu also times the oracle on the host cores)
+  python tools/fastslam_bench.py --mh-device-cycle
+      MH-FastSLAM cycles per second over one simulator trajectory, timed both ways in this one invocation: the host-planned route
+      (rfsgpu_fastslam_update + the numpy resampling of FastSLAM.update_and_resample) and rfsgpu_fastslam_cycle_async
+      (FastSLAM(device_cycle=True)).  FS_N particles (200), FS_HYP hypotheses (4), FS_STEPS steps (100), median of FS_REPS (3)."""
 import os
 import sys
 import time
@@ -11,6 +15,55 @@ sys.path.insert(0, ROOT)
 from __graft_entry__ import load_package
 pkg = load_package()
 sc = pkg.scenarios
+
+
+def mh_route_times(pkg, device_cycle, n, hyp, steps, reps, quiet=False):
+    """Seconds per cycle (one per repetition) of `steps` MH-FastSLAM cycles of the 2-D simulator's configuration, poses at the ground
+    truth (the driver's first 100 steps): set_poses, predict, update with its resampling.  device_cycle is ignored by a package that
+    does not know it (False must be passed there)."""
+    drv = pkg.sim2d_driver
+    P = dict(drv.C1_FASTSLAM_SIM, max_hypotheses=hyp, kmax=3 * steps)     # (kmax spaces the generator's landmarks: one per 6 steps)
+    data = drv.generate(P, traj_seed=3, kmax=steps + 1)
+    draws = np.random.default_rng(8).random(steps + 1)
+    out = []
+    for rep in range(reps + 1):                       # (the first repetition warms up: code objects, allocations)
+        kw = dict(device_cycle=True) if device_cycle else {}
+        f = pkg.FastSLAM(n, gm_capacity=64, max_hypotheses=hyp, n_particles_max=2048 // hyp, **kw)
+        drv.configure(f, P)
+        f.config = f.get_filter_config()
+        f.fs_config = drv.fastslam_config(f, P)
+        f.fs_config.nParticlesMax = 2048 // hyp
+        f.setEffectiveParticleCountThreshold(P["eff_n"])
+        f.synchronize()
+        fired = grown = 0
+        t0 = time.perf_counter()
+        for k in range(1, steps + 1):
+            f.set_poses(np.tile(data["gt"][k], (f.n, 1)), np.zeros((3, 3)))
+            f.predict_map()
+            fired += bool(f.update_and_resample(data["Z"][k], u01_fn=lambda: float(draws[k])))
+            grown = max(grown, len(f.parents))
+        f.synchronize()
+        dt = (time.perf_counter() - t0) / steps
+        sizes = int(np.asarray(f.gm_sizes()).mean())
+        f.close()
+        if rep:
+            out.append(dt)
+        if not quiet:
+            print("  %s rep %d: %.4f ms/cycle, %d resamplings, largest grown set %d, mean map size %d%s" %
+                  ("device cycle" if device_cycle else "host-planned", rep, dt * 1e3, fired, grown, sizes, "" if rep else "  (warm-up)"))
+    return out
+
+
+if "--mh-device-cycle" in sys.argv:
+    n, hyp, steps, reps = [int(os.environ.get(k, d)) for k, d in (("FS_N", 200), ("FS_HYP", 4), ("FS_STEPS", 100), ("FS_REPS", 3))]
+    print("MH-FastSLAM, %d particles, %d hypotheses, %d steps, %d repetitions" % (n, hyp, steps, reps))
+    th = mh_route_times(pkg, False, n, hyp, steps, reps)
+    td = mh_route_times(pkg, True, n, hyp, steps, reps)
+    mh, md = float(np.median(th)), float(np.median(td))
+    print("host-planned route: median %.4f ms/cycle (min %.4f, max %.4f)" % (mh * 1e3, min(th) * 1e3, max(th) * 1e3))
+    print("device cycle:       median %.4f ms/cycle (min %.4f, max %.4f)  -> %.2fx" % (md * 1e3, min(td) * 1e3, max(td) * 1e3, mh / md))
+    sys.exit(0)
+
 N, NM, NZ, HYP = [int(os.environ.get(k, d)) for k, d in (("FS_N", 2000), ("FS_NM", 200), ("FS_NZ", 30), ("FS_HYP", 1))]
 scen = sc.make_scenario(N, NM, NZ, seed=4242, rmax=25.0)
 f = pkg.FastSLAM(N, gm_capacity=384, max_hypotheses=HYP)    # FS_HYP > 1: MH-FastSLAM (dense table: keep FS_NM, FS_NZ <= 64)
