@@ -46,6 +46,7 @@ struct Params {
   int poseCovStride;       // 0 shared, 9 per particle
   int exactPartitions;     // rfsgpu_set_partition_mode: partitions with nR + nC > 8 by the exact subset recurrence instead of Murty-200
   int denseIntensity;      // RFSGPU_DENSE_INTENSITY=1: the intensity sums over EVERY (evaluation point, Gaussian) pair, the reference's term list (deviation 9 off)
+  int gateIndex;           // 0 (RFSGPU_GATE_INDEX=0 at create): the map update's gate prefilter sweeps the whole set for every landmark instead of looking its index up
   // MeasurementModel_VictoriaPark (model 1); R[] above then holds its 2x2 range-bearing block
   double R9[9];
   double Slb;

@@ -82,6 +82,7 @@ struct rfsgpu_filter {
   bool outArmed = false;              // the step in flight delivers through hOutW / hOutFlag (update_io_end spins instead of synchronising)
 
   int stagePendingSlot = -1;          // a staging slot whose event must be recorded behind the step that reads it
+  bool gateIndex = true;              // RFSGPU_GATE_INDEX=0 at create: the map update finds its gate candidates by the dense sweep (update_map.h), for A/B runs against the index
   bool denseIntensity = false;        // RFSGPU_DENSE_INTENSITY=1 at create: deviation 9 off (the dense loop for every mixture size), for runs against a future pinned fixture
   bool ioPull = true;                 // RFSGPU_IO_PULL=0: inputs by copy commands, outputs by copies + a stream synchronisation (A/B, rounds 3-4 form)
   int vpParity = 0;                   // which pair of duration extrema (vpCost[Ncap ..]) the next post kernel reads
@@ -150,6 +151,7 @@ struct rfsgpu_filter {
   bool fuseSteps = true;    // rfsgpu_update / _update_async / _step_async use phd_step_fused_kernel (2-D model); RFSGPU_FUSED_STEP=0 turns it off
   bool phaseTiming = false; // rfsgpu_set_phase_timing: rfsgpu_update runs its phases as separate launches (TimingInfo per phase)
   int stepWppOverride = 0;  // RFSGPU_STEP_WPP: waves per particle of the fused step kernel (2 or 3); 0 = chosen per launch
+  int updMapWppOverride = 0;  // RFSGPU_UPDMAP_WPP at create: waves per particle of the stand-alone map update (1 .. 4); 0 = chosen by capacity
   unsigned stepSeq = 0;      // fused steps launched so far
   int timingStride = 8;      // every timingStride-th of them carries the timing events (rfsgpu_set_step_timing_stride; round 5: 8 by default --
                              // three marker packets per step cost a configs[1] step 8 us; the FIRST step of a filter is always timed)
@@ -273,6 +275,7 @@ static std::string batch_error_note(rfsgpu_filter *f, int e);
 static void rebuild_params(rfsgpu_filter *f) {
   Params &P = f->P;
   P.denseIntensity = f->denseIntensity ? 1 : 0;
+  P.gateIndex = f->gateIndex ? 1 : 0;
   for (int k = 0; k < 4; k++) P.R[k] = f->rb.R[k];
   P.Pd = f->rb.probabilityOfDetection;
   P.clutter = f->rb.uniformClutterIntensity;
@@ -397,7 +400,9 @@ int rfsgpu_create_ex(rfsgpu_filter **out, int model, int n_particles, int device
   { const char *e = getenv("RFSGPU_FUSED_STEP"); if (e && e[0] == '0') f->fuseSteps = false; }
   { const char *e = getenv("RFSGPU_IO_PULL"); if (e && e[0] == '0') f->ioPull = false; }
   { const char *e = getenv("RFSGPU_DENSE_INTENSITY"); if (e && e[0] == '1') f->denseIntensity = true; }
+  { const char *e = getenv("RFSGPU_GATE_INDEX"); if (e && e[0] == '0') f->gateIndex = false; }
   { const char *e = getenv("RFSGPU_STEP_WPP"); if (e) f->stepWppOverride = atoi(e); }
+  { const char *e = getenv("RFSGPU_UPDMAP_WPP"); if (e) f->updMapWppOverride = atoi(e); }
   { const char *e = getenv("RFSGPU_BIRTH_INHERITANCE"); if (e && !strcmp(e, "eager")) f->inheritMode = RFSGPU_INHERIT_EAGER; }   // (initial mode; rfsgpu_set_birth_inheritance)
   { const char *e = getenv("RFSGPU_MERGE_GRID"); if (e) f->mergeGridOverride = atoi(e); }
   if (f->cap > 2048) { delete f; return RFSGPU_ERR_INVALID; }
@@ -948,7 +953,7 @@ static int launch_update_map(rfsgpu_filter *f) {
   // 43.7 with four; configs[2]'s shard (cap 640): 106.8 / 75.4 / 77.1 / 67.8.  RFSGPU_UPDMAP_WPP = 1 .. 4 overrides (1: the
   // one-wave kernels below).
   const size_t bb = (size_t)RFS_Z_LDS_BYTES + update_map_block_lds_bytes(f->cap);
-  static const int wppEnv = [] { const char *e = getenv("RFSGPU_UPDMAP_WPP"); return e ? atoi(e) : 0; }();
+  const int wppEnv = f->updMapWppOverride;   // (read at create, like the other switches)
   const int wppU = (wppEnv >= 1 && wppEnv <= 4) ? wppEnv : (f->cap > 512 ? 4 : 2);
   if (wppU != 1 && bb <= 64 * 1024) {
     if (wppU == 2) {

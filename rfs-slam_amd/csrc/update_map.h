@@ -74,8 +74,16 @@ __device__ __forceinline__ double pair_weight(const Params &P, const LmKF &k, do
   return pdw * lik;
 }
 
-// LDS per wave: survivor list (value, packed (m,z)) + per-landmark segment (start, count) + final normalisers.
+// The measurement index of the gate prefilter (below): cumulative bearing masks [256], cumulative range masks [64], header.
+#define GATE_INDEX_BBINS 256
+#define GATE_INDEX_RBINS 64
+#define GATE_INDEX_BYTES ((GATE_INDEX_BBINS + GATE_INDEX_RBINS) * 8 + 32)
+// LDS per wave: survivor list (value, packed (m,z)) + per-landmark segment (start, count) + final normalisers + the measurement index.
 __host__ __device__ inline size_t update_map_lds_bytes_per_wave(int cap) {
+  return (size_t)cap * (8 + 4 + 4) + RFSGPU_MAX_Z * 8 + GATE_INDEX_BYTES;
+}
+// where the index starts inside a wave's / workgroup's block (behind sV | sCol | sMZ | sSeg)
+__host__ __device__ inline size_t update_map_index_offset(int cap) {
   return (size_t)cap * (8 + 4 + 4) + RFSGPU_MAX_Z * 8;
 }
 
@@ -136,8 +144,9 @@ __device__ __forceinline__ void stage_measurements_lds(unsigned char *smem_raw, 
   }
 }
 
-// Candidate mask of one landmark: bit z set if measurement z MAY pass both innovation gates.
-__device__ __forceinline__ unsigned long long gate_candidates(const Params &P, const LmKF &k, const bool live, const int nZ, const float *sZf) {
+// Candidate mask of one landmark: bit z set if measurement z MAY pass both innovation gates.  The dense form: every measurement
+// against the landmark.  gate_candidates (below) takes it for the sets its index cannot bound.
+__device__ __forceinline__ unsigned long long gate_candidates_sweep(const Params &P, const LmKF &k, const bool live, const int nZ, const float *sZf) {
   const float zx0 = (float)k.zx0, zx1 = (float)k.zx1;
   const float zrMax = sZf[2 * RFSGPU_MAX_Z], zbMax = sZf[2 * RFSGPU_MAX_Z + 1];
   const float inf = __builtin_huge_valf();
@@ -175,6 +184,151 @@ __device__ __forceinline__ unsigned long long gate_candidates(const Params &P, c
   }
   unsigned long long m = ((unsigned long long)hi << 32) | lo;
   m &= (nZ >= 64) ? ~0ull : ((1ull << nZ) - 1ull);
+  return live ? m : 0ull;
+}
+
+// ---- measurement index ------------------------------------------------------------------------------------------------------
+// The sweep tests all nZ measurements against every landmark to find the one or two inside its gates (the bearing gate alone
+// passes a few per cent of the circle).  The index turns that round: once per particle, before the pass loop, the measurement
+// set is binned -- 256 bearing bins over [-pi, pi), 64 range bins between the set's smallest and largest range -- and two
+// tables of cumulative masks are left in LDS: cumB[b] / cumR[b] = the measurements whose bin is <= b.  A landmark's candidates
+// are then two table differences: (cumB[hi] & ~cumB[lo - 1]) & (cumR[hi'] & ~cumR[lo' - 1]), a few dozen instructions instead
+// of a loop over the set.  As with the sweep the mask may only be too large, never too small -- every candidate still goes
+// through pair_gate in fp64 -- and that is argued as follows.
+//  Bearing: a measurement's bin comes from its fp32 bearing reduced like the sweep's difference (b - rint(b / 2pi) 2pi); the
+//    window is the landmark's fp32 bearing +- thrB, the sweep's threshold, whose allowances (rounded operands, |k| multiples of
+//    an fp32 2pi) cover the reduction of the measurement alone as they cover that of the difference; one guard bin on either
+//    side (2pi / 256 = 0.0245 rad, four orders above any of those errors) takes up the bin arithmetic, a reduced bearing that
+//    lands a rounding beyond +-pi (clamped into the end bins) and the rounding of the window's ends.  A window that crosses
+//    +-pi is the union of its two end pieces.
+//  Range: bin(x) = clamp(floor((x - rMin) * scale)) is a monotone function of the fp32 range, and the SAME function is applied
+//    to the window's ends: lo <= r <= hi implies bin(lo) <= bin(r) <= bin(hi), whatever the rounding inside bin().  The window is
+//    the landmark's fp32 range +- (thrR + guard), where thrR is the sweep's threshold and the guard, another 2.5e-7 (max |range|
+//    + |landmark range|), covers the rounding of the two ends themselves.
+//  A measurement with a NaN coordinate is a candidate of every landmark (as in the sweep, whose comparisons a NaN passes).
+// The sweep stays for what the index cannot bound, decided once per particle and wave-uniformly: a gate that is disabled, a
+// threshold that is not finite (|bearing| >= 50, |range| >= 1e30, inf), a bearing window that would cover the circle (thrB >= 3),
+// a range span that is zero or not finite -- and for handles created under RFSGPU_GATE_INDEX=0 (Params::gateIndex).
+struct GateIndex {   // wave-uniform: lives in SGPRs
+  const unsigned long long *cumB, *cumR;
+  float rMin, rMax, rScale;     // range bins: (r - rMin) * rScale
+  float thrB, kfR1, zrMax;      // the sweep's bearing threshold; (float)kfRange (1 + 1e-6); max |range| of the set
+  unsigned long long always;    // measurements with a NaN coordinate
+  bool use;
+};
+#define GATE_INDEX_THRB_MAX 3.0f   // 2 thrB * 256 / 2pi + 3 bins (floors, guards) must stay below 255 bins: thrB < 3.08
+
+__device__ __forceinline__ unsigned gate_or_scan_u32(unsigned x) {   // inclusive OR-scan over the lanes (wave_excl_scan's moves)
+  x |= (unsigned)dpp_i32<0x111, 0xf>((int)x);  // row_shr:1
+  x |= (unsigned)dpp_i32<0x112, 0xf>((int)x);  // row_shr:2
+  x |= (unsigned)dpp_i32<0x114, 0xf>((int)x);  // row_shr:4
+  x |= (unsigned)dpp_i32<0x118, 0xf>((int)x);  // row_shr:8
+  x |= (unsigned)dpp_i32<0x142, 0xa>((int)x);  // row_bcast:15 into rows 1 and 3
+  x |= (unsigned)dpp_i32<0x143, 0xc>((int)x);  // row_bcast:31 into rows 2 and 3
+  return x;
+}
+__device__ __forceinline__ unsigned long long gate_or_scan_u64(unsigned long long v) {
+  return ((unsigned long long)gate_or_scan_u32((unsigned)(v >> 32)) << 32) | gate_or_scan_u32((unsigned)v);
+}
+// bin coordinate of a bearing in [-pi, pi]: 256 bins over the circle
+__device__ __forceinline__ float gate_bearing_coord(float b) { return (b + 3.14159265358979323846f) * (float)(GATE_INDEX_BBINS / (2 * RFS_PI)); }
+__device__ __forceinline__ int gate_range_bin(float r, float rMin, float rScale) {
+  return (int)__builtin_fminf(__builtin_fmaxf(__builtin_floorf((r - rMin) * rScale), 0.f), (float)(GATE_INDEX_RBINS - 1));
+}
+
+// One wave bins the staged set's bearings and leaves cumB in `tab` (its first 256 entries).
+__device__ __forceinline__ void gate_index_build_bearing(unsigned char *tabRaw, const float *sZf, const int nZ, const int lane) {
+  unsigned long long *cumB = reinterpret_cast<unsigned long long *>(tabRaw);
+#pragma unroll
+  for (int j = 0; j < GATE_INDEX_BBINS / 64; j++) cumB[64 * j + lane] = 0ull;
+  wave_sync();
+  if (lane < nZ) {
+    const float zb = sZf[RFSGPU_MAX_Z + lane];
+    const float red = zb - __builtin_rintf(zb * 0.15915494309189533577f) * 6.2831853071795864769f;
+    const int bin = (int)__builtin_fminf(__builtin_fmaxf(__builtin_floorf(gate_bearing_coord(red)), 0.f), (float)(GATE_INDEX_BBINS - 1));  // (NaN: bin 0, and `always`)
+    atomicOr(&cumB[bin], 1ull << lane);
+  }
+  wave_sync();
+  unsigned long long carry = 0ull;   // the bins of the segments before: wave-uniform
+#pragma unroll
+  for (int j = 0; j < GATE_INDEX_BBINS / 64; j++) {   // lane l holds bin 64 j + l
+    const unsigned long long v = gate_or_scan_u64(cumB[64 * j + lane]) | carry;
+    cumB[64 * j + lane] = v;
+    carry = readlane_u64(v, 63);
+  }
+}
+// One wave bins the ranges, leaves cumR and the header: {rMin, rMax, rScale, span usable} | always.
+__device__ __forceinline__ void gate_index_build_range(unsigned char *tabRaw, const float *sZf, const int nZ, const int lane) {
+  unsigned long long *cumR = reinterpret_cast<unsigned long long *>(tabRaw) + GATE_INDEX_BBINS;
+  float *hdr = reinterpret_cast<float *>(cumR + GATE_INDEX_RBINS);
+  const float zr = sZf[lane], zb = sZf[RFSGPU_MAX_Z + lane];   // (lanes beyond nZ read measurement 0 again: stage_measurements_lds)
+  const float rMin = wave_min_f32(zr), rMax = wave_max_f32(zr);
+  const float span = rMax - rMin, rScale = (float)GATE_INDEX_RBINS / span;
+  const bool ok = nZ > 0 && span > 0.f && rScale < __builtin_huge_valf();
+  const unsigned long long always = __ballot(lane < nZ && (zr != zr || zb != zb));
+  cumR[lane] = 0ull;
+  wave_sync();
+  if (ok && lane < nZ) atomicOr(&cumR[gate_range_bin(zr, rMin, rScale)], 1ull << lane);
+  wave_sync();
+  cumR[lane] = gate_or_scan_u64(cumR[lane]);
+  if (lane == 0) {
+    hdr[0] = rMin; hdr[1] = rMax; hdr[2] = rScale;
+    reinterpret_cast<int *>(hdr)[3] = ok ? 1 : 0;
+    reinterpret_cast<unsigned long long *>(hdr)[2] = always;
+  }
+}
+// After the build (and a barrier): the wave's view of the index, and whether this set can use it at all.
+__device__ __forceinline__ GateIndex gate_index_load(const Params &P, const unsigned char *tabRaw, const float *sZf) {
+  GateIndex G;
+  G.cumB = reinterpret_cast<const unsigned long long *>(tabRaw);
+  G.cumR = G.cumB + GATE_INDEX_BBINS;
+  const float *hdr = reinterpret_cast<const float *>(G.cumR + GATE_INDEX_RBINS);
+  const float zrMax = sZf[2 * RFSGPU_MAX_Z], zbMax = sZf[2 * RFSGPU_MAX_Z + 1];
+  const float inf = __builtin_huge_valf();
+  const float thrB = (float)P.kfBearing * (1.f + 1e-6f) + 1e-6f * (zbMax + 3.2f) + 1e-6f;   // as in the sweep
+  const float kfR1 = (float)P.kfRange * (1.f + 1e-6f);
+  int use = 0;
+  if (P.gateIndex) {
+    const bool ok = P.kfRange > 0 && P.kfBearing > 0 && zbMax < 50.f && zrMax < 1.0e30f && thrB < GATE_INDEX_THRB_MAX && kfR1 < inf &&
+                    reinterpret_cast<const int *>(hdr)[3] != 0;
+    use = ok ? 1 : 0;
+  }
+  auto sf = [](float v) { return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v))); };
+  G.use = __builtin_amdgcn_readfirstlane(use) != 0;
+  G.rMin = sf(hdr[0]); G.rMax = sf(hdr[1]); G.rScale = sf(hdr[2]);
+  G.thrB = sf(thrB); G.kfR1 = sf(kfR1); G.zrMax = sf(zrMax);
+  const unsigned long long al = reinterpret_cast<const unsigned long long *>(hdr)[2];
+  G.always = ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(al >> 32)) << 32) | (unsigned)__builtin_amdgcn_readfirstlane((int)al);
+  return G;
+}
+
+// Candidate mask of one landmark: bit z set if measurement z MAY pass both innovation gates.
+__device__ __forceinline__ unsigned long long gate_candidates(const Params &P, const LmKF &k, const bool live, const int nZ, const float *sZf,
+                                                              const GateIndex &G) {
+  if (!G.use) return gate_candidates_sweep(P, k, live, nZ, sZf);
+  const float zx0 = (float)k.zx0, zx1 = (float)k.zx1;
+  const float inf = __builtin_huge_valf();
+  const unsigned long long zmask = (nZ >= 64) ? ~0ull : ((1ull << nZ) - 1ull);
+  // bearing: bins [ilo, ihi] modulo 256 (zx1 lies in [-pi, pi] and thrB < 3, so ilo >= -130, ihi <= 386 and ihi - ilo < 255)
+  const int ilo = (int)__builtin_floorf(gate_bearing_coord(zx1 - G.thrB)) - 1, ihi = (int)__builtin_floorf(gate_bearing_coord(zx1 + G.thrB)) + 1;
+  const int bl = ilo & (GATE_INDEX_BBINS - 1), bh = ihi & (GATE_INDEX_BBINS - 1);
+  unsigned long long bA = G.cumB[(bl - 1) & (GATE_INDEX_BBINS - 1)];
+  const unsigned long long bH = G.cumB[bh];
+  bA = (bl == 0) ? 0ull : bA;
+  const unsigned long long mB = (bl > bh) ? (bH | ~bA) : (bH & ~bA);   // across the seam: [bl, 255] and [0, bh]
+  // range
+  const float thrR = G.kfR1 + 2.5e-7f * (G.zrMax + fabsf(zx0)) + 1e-30f;   // as in the sweep
+  const float guard = 2.5e-7f * (G.zrMax + fabsf(zx0));
+  const float lo = zx0 - thrR - guard, hi = zx0 + thrR + guard;
+  const int rl = gate_range_bin(lo, G.rMin, G.rScale), rh = gate_range_bin(hi, G.rMin, G.rScale);
+  unsigned long long rA = G.cumR[(rl - 1) & (GATE_INDEX_RBINS - 1)];
+  const unsigned long long rH = G.cumR[rh];
+  rA = (rl == 0) ? 0ull : rA;
+  unsigned long long mR = rH & ~rA;
+  mR = (hi < G.rMin || lo > G.rMax) ? 0ull : mR;   // (every fp32 range of the set lies in [rMin, rMax])
+  unsigned long long m = (mB & mR) | G.always;
+  m = (fabsf(zx0) < inf && fabsf(zx1) < inf) ? m : ~0ull;   // a landmark without a finite expected measurement: the exact test decides
+  m &= zmask;
   return live ? m : 0ull;
 }
 
@@ -259,6 +413,15 @@ __device__ __forceinline__ void phd_update_map_particle(const Buffers &B, const 
   PoseReg pr;
   load_pose(B, P, i, pr);
 
+  // the measurement index of the gate prefilter, in this wave's own block
+  unsigned char *gTab = wb + update_map_index_offset(cap);
+  if (P.gateIndex) {
+    gate_index_build_bearing(gTab, sZf, nZ, lane);
+    gate_index_build_range(gTab, sZf, nZ, lane);
+    wave_sync();
+  }
+  const GateIndex G = gate_index_load(P, gTab, sZf);
+
   const int nPass = (nM + 63) >> 6;
   const int room = cap - nM;  // survivors that still fit as new Gaussians
   int nFov = 0;
@@ -284,7 +447,7 @@ __device__ __forceinline__ void phd_update_map_particle(const Buffers &B, const 
     nFov += __popcll(__ballot(fov));
     if (P.useCluster) wsum += act ? w : 0.0;
     if (p == 0) DBG_T(0, 4);
-    const unsigned long long cand = gate_candidates(P, k, fov && k.ok, nZ, sZf);
+    const unsigned long long cand = gate_candidates(P, k, fov && k.ok, nZ, sZf, G);
     if (p == 0) DBG_T(0, 5);
     // exact innovation gates + Mahalanobis gate + likelihood for the candidates
     unsigned long long surv = 0;
@@ -446,7 +609,8 @@ __device__ __forceinline__ void phd_update_map_block(const Buffers &B, const Par
   double *sCol = sV + cap;                                      // [MAX_Z] final normalisers
   unsigned *sMZ = reinterpret_cast<unsigned *>(sCol + RFSGPU_MAX_Z);  // [cap] (m << 8) | z
   unsigned *sSeg = sMZ + cap;                                   // [cap] per landmark: (start << 8) | count
-  int *sTot = reinterpret_cast<int *>(sSeg + cap);              // [2][8] survivors per wave of a pass (double-buffered)
+  unsigned char *gTab = wb + update_map_index_offset(cap);      // the measurement index of the gate prefilter (GATE_INDEX_BYTES)
+  int *sTot = reinterpret_cast<int *>(wb + update_map_lds_bytes_per_wave(cap));  // [2][8] survivors per wave of a pass (double-buffered)
   int *sMisc = sTot + 16;                                       // [0] overflow flag [1] landmarks in FOV [2] a new Gaussian has to be dropped
   unsigned *sUsed = reinterpret_cast<unsigned *>(sMisc + 4);    // [2] used-measurement mask (lo, hi)
 
@@ -467,6 +631,13 @@ __device__ __forceinline__ void phd_update_map_block(const Buffers &B, const Par
   PoseReg pr;
   load_pose(B, P, i, pr);
   if (tid < 6) { if (tid < 4) sMisc[tid] = 0; else sUsed[tid - 4] = 0u; }
+  // the measurement index, once per workgroup: wave 0 bins the bearings, wave 1 the ranges
+  if (P.gateIndex) {
+    if (wave == 0) gate_index_build_bearing(gTab, sZf, nZ, lane);
+    if (wave == (WPP > 1 ? 1 : 0)) gate_index_build_range(gTab, sZf, nZ, lane);
+    __syncthreads();
+  }
+  const GateIndex G = gate_index_load(P, gTab, sZf);
 
   const int nPass = (nM + NT - 1) / NT;
   const int room = cap - nM;  // survivors that still fit as new Gaussians
@@ -499,7 +670,7 @@ __device__ __forceinline__ void phd_update_map_block(const Buffers &B, const Par
     const double pdw = pd * w;
     nFov += __popcll(__ballot(fov));
     RFS_CUT(1);
-    const unsigned long long cand = gate_candidates(P, k, fov && k.ok, nZ, sZf);
+    const unsigned long long cand = gate_candidates(P, k, fov && k.ok, nZ, sZf, G);
     RFS_CUT(2);
     unsigned long long surv = 0;
     double keepV[UPDMAP_KEEP];
