@@ -775,6 +775,52 @@ int rfsgpu_batch_set_fastslam_config(rfsgpu_filter *f, int filter, const rfsgpu_
  * device error word at the next synchronising call; rfsgpu_last_error names the lowest filter that ran out of gm_capacity). */
 int rfsgpu_batch_fastslam_cycle_async(rfsgpu_filter *f, int predict, const double *x, const double *x_cov, int cov_stride,
                                       const double *z, const int *n_z, int normalize);
+/* -- a batch of multi-hypothesis FastSLAM filters: every filter is a 2-D rfs::FastSLAM with maxNDataAssocHypotheses in [1, 16]
+ * (include/FastSLAM.hpp:492-556), whose update multiplies its particles and whose resampleWithMapCopy (:729-757) brings them back.
+ * Filter b owns the global slots [b * max_per_filter, (b + 1) * max_per_filter); its live particles are the first n_b of them, and
+ * n_b -- n_per_filter at creation, which is also the count a resampling brings the filter back to (nParticles_init_) -- lives in a
+ * word on the device.  SLOTS AT OR BEYOND A FILTER'S COUNT HOLD NOTHING MEANINGFUL: the per-slot getters and setters work on global
+ * slots as on any batch (rfsgpu_n_particles stays n_filters * max_per_filter, so they wait for no count), and what they return for
+ * such a slot is whatever an earlier, larger set left there; rfsgpu_batch_live_counts says where each filter ends.  Particle ids
+ * start as the slot within the filter.  max_per_filter < n_per_filter: RFSGPU_ERR_INVALID; max_per_filter >
+ * RFSGPU_FASTSLAM_CYCLE_MAX_PARTICLES: RFSGPU_ERR_UNSUPPORTED (one workgroup resamples a filter in LDS); the 2-D model only.
+ * rfsgpu_create_batch and the handles it makes are unchanged and still refuse more than one hypothesis.
+ *
+ * On such a handle rfsgpu_batch_set_fastslam_config accepts maxNDataAssocHypotheses 1 ... 16 per filter (filters of one batch may
+ * differ, 1 included; nParticlesMax defaults to 3 * n_per_filter, FastSLAM.hpp:250); landmarkCandidateMeasurementCountThreshold != 1
+ * stays refused.  The N_eff thresholds are rfsgpu_batch_set_resampling's; unset: n_per_filter / 4 and 0.25 (ParticleFilter.hpp:232).
+ * rfsgpu_batch_propagate_async is allowed and moves every slot of every block (its draws are keyed by the slot within the filter, so
+ * a live slot's draw does not depend on the counts).  Refused with RFSGPU_ERR_UNSUPPORTED, state untouched, because each assumes
+ * that every filter fills its block: rfsgpu_batch_cycle_async, rfsgpu_batch_fastslam_cycle_async, rfsgpu_batch_resample_async /
+ * _resample_apply / _last_resample / _resample_counts, rfsgpu_batch_weight_sums and the [metric] calls. */
+int rfsgpu_create_batch_mh(rfsgpu_filter **out, int model, int n_filters, int n_per_filter, int max_per_filter, int device_id,
+                           int gm_capacity);
+/* One whole FastSLAM::update (FastSLAM.hpp:387-421) of every filter, enqueued as one launch chain: per filter what
+ * rfsgpu_fastslam_cycle_async does on a handle created with max_particles = max_per_filter -- with predict != 0 the static landmark
+ * step (:376-383; it also runs for a filter with n_z == 0); the association with Murty's k best; the copy plan in the reference's
+ * order (:543-556); copies, weight split, Kalman correction / existence / weights; prune (when n_z >= the filter's
+ * pruningMeasurementsThreshold, :611-612) and new landmarks; normalisation; resampleWithMapCopy (:729-757) with its two gates, the
+ * N_eff test, the forced resampling above nParticlesMax, the shrink to n_per_filter, ids and weights; and the second normalisation
+ * when resample() ran its test and returned false (:743).  x [N][3], x_cov, cov_stride: as rfsgpu_batch_cycle_async (every global
+ * slot; NULL: the poses on the device stay).  z [n_filters][RFSGPU_MAX_Z][2], n_z [n_filters]; a filter with n_z == 0 only counts the
+ * update (:399-402).  u01 [n_filters]: the caller's draws in [0, 1) for the systematic plans; a value outside is RFSGPU_ERR_INVALID
+ * and names the filter.  The tables travel through the batch's pinned ring; nothing in the call waits for the GPU, cycles queue back
+ * to back.
+ *
+ * Overflow is per filter: a filter whose grown set would exceed max_per_filter is left as it was before the cycle's update (a static
+ * step asked for by `predict` has run) while the other filters' cycles complete; further cycles enqueued behind it are abandoned for
+ * that filter only.  The next synchronising call returns RFSGPU_ERR_CAPACITY once, names the lowest such filter and clears the
+ * condition. */
+int rfsgpu_batch_fastslam_mh_cycle_async(rfsgpu_filter *f, int predict, const double *x, const double *x_cov, int cov_stride,
+                                         const double *z, const int *n_z, const double *u01);
+/* What the last rfsgpu_batch_fastslam_mh_cycle_async did (synchronises; any pointer may be NULL).  [n_filters]: the count after the
+ * update, the count after the resampling, whether that fired, N_eff (0 where the test did not run), whether the filter overflowed.
+ * parent and plan: [n_filters * max_per_filter], as rfsgpu_fastslam_last_cycle's but in slots local to the filter; identity where
+ * nothing happened (no measurements, overflow), -1 at and beyond the respective count. */
+int rfsgpu_batch_fastslam_last_cycle(rfsgpu_filter *f, int *n_after_update, int *n_after_resample, unsigned char *fired,
+                                     double *n_eff, unsigned char *overflowed, int *parent, int *plan);
+/* The live particle count of every filter: out [n_filters].  Synchronising. */
+int rfsgpu_batch_live_counts(rfsgpu_filter *f, int *out);
 #ifdef RFSGPU_ENABLE_BENCH_API
 /* [test] 1 once a step of this handle (batch or not) has queued Murty-200 partitions, else 0.  Synchronising. */
 int rfsgpu_murty_seen(rfsgpu_filter *f);

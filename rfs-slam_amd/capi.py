@@ -139,6 +139,7 @@ ABI_SYMBOLS = [
     "create_batch", "n_filters", "batch_configure", "batch_cycle_async", "batch_weight_sums", "batch_resample_apply", "batch_resample_occured", "murty_seen",
     "batch_set_motion_odometry", "batch_set_resampling", "batch_propagate_async", "batch_resample_async", "batch_last_resample", "batch_resample_counts", "batch_get_pose_covs",
     "batch_set_fastslam_config", "batch_fastslam_cycle_async",
+    "create_batch_mh", "batch_fastslam_mh_cycle_async", "batch_fastslam_last_cycle", "batch_live_counts",
     "set_ground_truth", "error_log_create", "error_log_reset", "step_error_async", "error_log_read", "step_error", "get_map_estimate",
 ]
 
@@ -849,6 +850,78 @@ class CBatch(CFilter):
         fn = self._fn("n_filters")
         fn.restype = C.c_int
         return int(fn(self._h))
+
+
+class CBatchMH(CBatch):
+    """A batch of multi-hypothesis FastSLAM filters behind the C ABI (rfsgpu_create_batch_mh): filter b owns the global slots
+    [b * max_per_filter, (b + 1) * max_per_filter), of which the first live_counts()[b] are live; n_per_filter is the count a filter
+    starts with and returns to at a resampling.  Slots beyond a filter's count hold nothing meaningful."""
+
+    def __init__(self, lib, prefix, n_filters, n_per_filter, max_per_filter, model=MODEL_RNGBRG_2D, device_id=0, gm_capacity=512):
+        self._lib, self._p = lib, prefix
+        self.model = model
+        self.device_id = device_id
+        self.dm = self.dz = 2
+        self._borrowed = False
+        self._h = C.c_void_p()
+        fn = self._fn("create_batch_mh")
+        fn.restype = C.c_int
+        rc = fn(C.byref(self._h), C.c_int(model), C.c_int(int(n_filters)), C.c_int(int(n_per_filter)), C.c_int(int(max_per_filter)), C.c_int(device_id),
+                C.c_int(gm_capacity))
+        if rc != OK:
+            self._h = C.c_void_p()
+            raise EngineError(rc, "create_batch_mh failed: " + ("max_per_filter beyond 2048 (one workgroup resamples a filter), or the Victoria Park model" if rc == ERR_UNSUPPORTED
+                                                                else "no gfx950 device / bad arguments (max_per_filter < n_per_filter?)"))
+        self.n_filters = int(n_filters)
+        self.n_per_filter = int(n_per_filter)
+        self.max_per_filter = int(max_per_filter)
+
+    def block(self, b, n=None):
+        """The global slots of filter b: all max_per_filter of them, or the first n."""
+        return slice(b * self.max_per_filter, b * self.max_per_filter + (self.max_per_filter if n is None else int(n)))
+
+    def batch_fastslam_mh_cycle_async(self, predict, Zs, u01, poses=None, pose_cov=None):
+        """rfsgpu_batch_fastslam_mh_cycle_async: Zs one measurement array per filter, u01 [n_filters] the draws in [0, 1)."""
+        assert len(Zs) == self.n_filters
+        z = np.zeros((self.n_filters, MAX_Z, 2))
+        nz = np.zeros(self.n_filters, dtype=np.int32)
+        for b, Z in enumerate(Zs):
+            Z = _f64(Z).reshape(-1, 2) if np.size(Z) else np.zeros((0, 2))
+            nz[b] = Z.shape[0]
+            z[b, : min(Z.shape[0], MAX_Z)] = Z[:MAX_Z]
+        self.batch_fastslam_mh_cycle_async_packed(predict, z, nz, u01, poses=poses, pose_cov=pose_cov)
+
+    def batch_fastslam_mh_cycle_async_packed(self, predict, z, nz, u01, poses=None, pose_cov=None):
+        """The same with the sets already in the call's layout (z [n_filters, MAX_Z, 2] float64, nz [n_filters] int32)."""
+        assert z.dtype == np.float64 and nz.dtype == np.int32 and z.shape == (self.n_filters, MAX_Z, 2) and z.flags.c_contiguous and nz.flags.c_contiguous
+        u = _f64(u01, (self.n_filters,))
+        x = None if poses is None else _f64(poses, (self.n, 3))
+        stride = 0
+        cv = None
+        if pose_cov is not None:
+            cv = _f64(pose_cov)
+            assert cv.size in (9, 9 * self.n)
+            stride = 0 if cv.size == 9 else 9
+        self._call("batch_fastslam_mh_cycle_async", C.c_int(1 if predict else 0), C.c_void_p(None) if x is None else self._ptr(x),
+                   C.c_void_p(None) if cv is None else self._ptr(cv), C.c_int(stride), self._ptr(z), self._ptr(nz), self._ptr(u))
+
+    def batch_fastslam_last_cycle(self):
+        """rfsgpu_batch_fastslam_last_cycle (synchronising): per filter the counts after the update and after the resampling, whether it
+        fired, N_eff, whether the filter overflowed; parent / plan [n_filters, max_per_filter] in slots local to the filter (-1 beyond
+        the counts)."""
+        nF, m = self.n_filters, self.max_per_filter
+        nu, nr = np.zeros(nF, dtype=np.int32), np.zeros(nF, dtype=np.int32)
+        fired, ovf = np.zeros(nF, dtype=np.uint8), np.zeros(nF, dtype=np.uint8)
+        neff = np.zeros(nF)
+        parent, plan = np.zeros((nF, m), dtype=np.int32), np.zeros((nF, m), dtype=np.int32)
+        self._call("batch_fastslam_last_cycle", self._ptr(nu), self._ptr(nr), self._ptr(fired), self._ptr(neff), self._ptr(ovf), self._ptr(parent), self._ptr(plan))
+        return dict(n_after_update=nu, n_after_resample=nr, fired=fired.astype(bool), n_eff=neff, overflowed=ovf.astype(bool), parent=parent, plan=plan)
+
+    def batch_live_counts(self):
+        """rfsgpu_batch_live_counts (synchronising): the live particle count of every filter."""
+        out = np.zeros(self.n_filters, dtype=np.int32)
+        self._call("batch_live_counts", self._ptr(out))
+        return out
 
 
 def mat_perm(lib, prefix, A, device_id=0):

@@ -133,6 +133,13 @@ __device__ __forceinline__ bool live_beyond(const LiveCount &L, int slot) {
   return __builtin_amdgcn_readfirstlane(*L.ovf) != 0 || slot >= __builtin_amdgcn_readfirstlane(*L.n);
 }
 
+// The same for a batch of multi-hypothesis FastSLAM filters (rfsgpu_create_batch_mh; MhBatchArg, fastslam.h): every filter has its
+// own count and its own overflow word.  Kernels that take a LiveCount take an MhBatchArg in the same trailing position; what they do
+// differently for it is behind `if constexpr (is_mh_batch<...>::value)`, so every other instantiation compiles as before.
+struct MhBatchArg;
+template <typename... T> struct is_mh_batch { static constexpr bool value = false; };
+template <> struct is_mh_batch<MhBatchArg> { static constexpr bool value = true; };
+
 // Section timing for kernel tuning (tools/kernel_sections.py builds a separate -DRFS_PROFILE library):
 // particle `RFS_PROFILE_PARTICLE`'s lane 0 stamps s_memtime at section boundaries.
 #ifdef RFS_PROFILE

@@ -54,6 +54,58 @@ struct FsBatchArg {
   int predict;                 // FastSLAM::predict's static landmark step runs at the head of the associate kernel
 };
 
+// ---- a batch of multi-hypothesis FastSLAM filters (rfsgpu_create_batch_mh, rfsgpu_batch_fastslam_mh_cycle_async) ---------------
+// Filter b owns the slots [b * nPer, (b + 1) * nPer) -- nPer is the stride, max_per_filter -- of which the first n_b are live; n_b
+// is a word of the filter's cycle state on the device (FsCycleState, fastslam_cycle.h: the filters' words are wordStride ints
+// apart).  The record repeats FsBatchFilter's field names and the argument FsBatchArg's, so the BATCH forms of gm_prune_kernel and
+// fs_new_landmarks_kernel read it as they read those; the kernels of fastslam_mh.h and the gather take it where a single handle's
+// device cycle passes its LiveCount.  Slot numbers in the plan arrays (copyDst / copySrc, slotSrc, the resampling plan) and the
+// particle ids are local to the filter's block.
+struct MhBatchFilter {
+  FsParams F;
+  double pruneT;
+  int nZ, zOff, prune;
+  int kmax;                     // maxNDataAssocHypotheses
+  double maxDiff;               // maxDataAssocLogLikelihoodDiff
+  double effN, effNPercent;     // ParticleFilter::resample's two thresholds
+  double u01;                   // the caller's draw for this cycle's systematic plan
+  int nInit, nMax;              // the count a resampling returns to; nParticlesMax (above it the resampling is forced)
+  int minUpdates, minMeasurements;
+};
+#define MHB_OVF_WORD 1          // == FSC_OVF (fastslam_cycle.h)
+struct MhBatchArg {
+  const MhBatchFilter *filt;    // [nF]
+  const Params *params;         // [nF]
+  const double *z;              // this cycle's sets, packed
+  int *errFilter;               // [1]
+  int nPer;                     // the stride: slots per filter
+  int predict;
+  int nF;
+  const int *words;             // filter 0's cycle words; filter b's start wordStride * b ints further
+  int wordStride;
+  int word;                     // which word is the count of this launch: FSC_N, FSC_NCOPY (the copy kernel) or FSC_RENORM_N
+};
+// (slot wave-uniform: scalar reads, as live_beyond(LiveCount))
+__device__ __forceinline__ bool mhb_ovf(const MhBatchArg &A, int b) {
+  return __builtin_amdgcn_readfirstlane(A.words[(size_t)b * A.wordStride + MHB_OVF_WORD]) != 0;
+}
+__device__ __forceinline__ bool mhb_beyond_count(const MhBatchArg &A, int slot) {
+  const int b = slot / A.nPer;
+  return slot - b * A.nPer >= __builtin_amdgcn_readfirstlane(A.words[(size_t)b * A.wordStride + A.word]);
+}
+// Nothing to do for this slot in this cycle: beyond its filter's count, or the filter overflowed (its cycle is abandoned), or the
+// filter has no measurements (FastSLAM.hpp:399-402: the update is only counted).
+__device__ __forceinline__ bool live_beyond(const MhBatchArg &A, int slot) {
+  const int b = __builtin_amdgcn_readfirstlane(slot / A.nPer);
+  return mhb_ovf(A, b) || __builtin_amdgcn_readfirstlane(A.filt[b].nZ) == 0 || mhb_beyond_count(A, slot);
+}
+// The same where every lane has a slot of its own (lanes of one wave may belong to different filters)
+__device__ __forceinline__ bool live_beyond_lane(const MhBatchArg &A, int slot) {
+  const int b = slot / A.nPer;
+  const int *w = A.words + (size_t)b * A.wordStride;
+  return w[MHB_OVF_WORD] != 0 || A.filt[b].nZ == 0 || slot - b * A.nPer >= w[A.word];
+}
+
 #define FS_AMBIG_MAX 64    // rows / columns of ONE connected component of competing associations (the in-kernel Hungarian, MURTY_N)
 #define FS_AMBIG_ROWS 256  // rows with competing associations per particle, over all components
 #define FS_SMALL 12        // components up to this size are solved in LDS, larger ones in the particle's HBM scratch
@@ -540,7 +592,8 @@ __device__ inline bool fs_append(const Buffers &B, int cur, int i, int &n, const
 #define FS_NEWLM_WPB 4
 // BATCH: one more argument, the FsBatchArg tables; the wave reads its filter's Params, FsParams, nZ and measurement set there and
 // stops when the filter has no measurements.  The other instantiations take no such argument and compile as before.
-// Without BATCH the one further argument is a LiveCount (common.h), as for gm_prune_kernel.
+// Without BATCH the one further argument is a LiveCount (common.h), as for gm_prune_kernel.  BATCH with an MhBatchArg: a wave beyond
+// its filter's own count leaves at once (waves of one workgroup may belong to different filters: no workgroup barrier below).
 template <int D, bool BATCH = false, typename... TBatch>
 __global__ __launch_bounds__(64 * FS_NEWLM_WPB) void fs_new_landmarks_kernel(Buffers B, Params P, FsParams F, int cur, int nZ, TBatch... batchArg) {
   const int wave = threadIdx.x >> 6;
@@ -557,6 +610,9 @@ __global__ __launch_bounds__(64 * FS_NEWLM_WPB) void fs_new_landmarks_kernel(Buf
   [[maybe_unused]] const double *Zb = nullptr;
   if constexpr (BATCH) {
     const auto &A = batch_first_arg(batchArg...);
+    if constexpr (is_mh_batch<TBatch...>::value) {   // a multi-hypothesis batch: the filter's own count and overflow word
+      if (live_beyond(A, i)) return;
+    }
     bf = __builtin_amdgcn_readfirstlane(i / A.nPer);
     nZ = __builtin_amdgcn_readfirstlane(A.filt[bf].nZ);
     if (nZ == 0) return;     // no update for this filter this cycle

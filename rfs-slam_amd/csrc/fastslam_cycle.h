@@ -97,8 +97,8 @@ __global__ void fs_cycle_begin_kernel(FsCycleState S, int nHost, int flagHost, i
 // [first_i, first_i + nH_i - 1) with first_i = N0 + sum_{j < i} max(nH_j - 1, 0), hypothesis h in first_i + (nH_i - 1) - h -- the
 // reference appends a copy per hypothesis and then addresses them as nParticles_ - h.  copyDst / copySrc list the copies in the
 // order the reference makes them.  One workgroup; a thread owns a run of consecutive particles.
-__global__ __launch_bounds__(FS_CYCLE_THREADS) void fs_mh_plan_kernel(const unsigned char *arena, FsCycleState S, int *slotHyp, int *slotNH, int *copyDst,
-                                                                      int *copySrc, int Ncap) {
+// (the body: fs_mh_plan_kernel for a handle, fs_mh_plan_batch_kernel for one filter of a batch, whose pointers start at its block)
+__device__ __forceinline__ void fs_mh_plan_body(const unsigned char *arena, const FsCycleState &S, int *slotHyp, int *slotNH, int *copyDst, int *copySrc, int Ncap) {
   __shared__ int sw[FS_CYCLE_THREADS / 64 + 1];
   const int t = threadIdx.x;
   if (S.w[FSC_OVF] != 0) return;                                     // (workgroup-uniform: an earlier cycle overflowed)
@@ -132,6 +132,10 @@ __global__ __launch_bounds__(FS_CYCLE_THREADS) void fs_mh_plan_kernel(const unsi
     S.w[FSC_N] = n; S.w[FSC_NCOPY] = total; S.w[FSC_NGROWN] = n;
   }
 }
+__global__ __launch_bounds__(FS_CYCLE_THREADS) void fs_mh_plan_kernel(const unsigned char *arena, FsCycleState S, int *slotHyp, int *slotNH, int *copyDst,
+                                                                      int *copySrc, int Ncap) {
+  fs_mh_plan_body(arena, S, slotHyp, slotNH, copyDst, copySrc, Ncap);
+}
 
 struct FsShrinkArg {
   double effN, effNPercent;   // ParticleFilter::resample's two thresholds
@@ -149,7 +153,7 @@ struct FsShrinkArg {
 // n samples out of the count (cases 1-4 of ParticleFilter.hpp:459-478): a sampled slot below n keeps its particle; every other
 // sample -- a repeat, or a first sample of a slot at or beyond n -- is copied, in sampling order, into the un-sampled slots in
 // ascending order, all of which lie below n.  The mixtures and poses move afterwards (resample_gather_kernel on S.plan).
-__global__ __launch_bounds__(FS_CYCLE_THREADS) void fs_resample_shrink_kernel(double *weight, FsCycleState S, FsShrinkArg A) {
+__device__ __forceinline__ void fs_resample_shrink_body(double *weight, const FsCycleState &S, const FsShrinkArg &A) {
   __shared__ double cum[FS_CYCLE_MAX_PARTICLES];     // the weights, then their running sum
   __shared__ double sp[FS_CYCLE_MAX_PARTICLES];      // the sample points
   __shared__ int sidx[FS_CYCLE_MAX_PARTICLES];       // the particle each sample point falls on
@@ -238,4 +242,89 @@ __global__ __launch_bounds__(FS_CYCLE_THREADS) void fs_resample_shrink_kernel(do
     else S.ppid[j] = S.pid[j];
     weight[j] = 1.0;
   }
+}
+__global__ __launch_bounds__(FS_CYCLE_THREADS) void fs_resample_shrink_kernel(double *weight, FsCycleState S, FsShrinkArg A) {
+  fs_resample_shrink_body(weight, S, A);
+}
+
+// ---- a batch of multi-hypothesis FastSLAM filters (rfsgpu_batch_fastslam_mh_cycle_async; MhBatchArg, fastslam.h) -------------------
+// One allocation holds every filter's cycle state as arrays over the filters and over the slots of the batch:
+// nEff [nF] | counters [nF][2] | words [nF][FSC_WORDS] | slotSrc | plan | pid | ppid, [nF * stride] each.  Filter b's FsCycleState
+// is the view that starts at its entries, so the count, the overflow word, the counters, N_eff, the plans and the ids are per
+// filter, and the two one-workgroup kernels above run with one workgroup per filter on pointers that start at the filter's block:
+// every slot number they write is local to it.
+static_assert(FSC_OVF == MHB_OVF_WORD, "MhBatchArg reads the overflow word by this index");
+__host__ __device__ inline size_t mhb_state_bytes(int nF, int stride) { return (size_t)nF * (24 + (size_t)FSC_WORDS * 4) + (size_t)4 * nF * stride * 4; }
+__host__ __device__ inline void mhb_state(unsigned char *base, int nF, int stride, int b, FsCycleState &S) {
+  S.nEff = (double *)base + b;
+  S.counters = (long long *)(base + (size_t)8 * nF) + 2 * b;
+  int *w0 = (int *)(base + (size_t)24 * nF);
+  S.w = w0 + (size_t)FSC_WORDS * b;
+  const size_t n = (size_t)nF * stride;
+  S.slotSrc = w0 + (size_t)FSC_WORDS * nF + (size_t)b * stride;
+  S.plan = S.slotSrc + n;
+  S.pid = S.plan + n;
+  S.ppid = S.pid + n;
+}
+// The head of a cycle: a filter without measurements only counts the update (:399-402).
+__global__ void fs_cycle_begin_batch_kernel(unsigned char *state, MhBatchArg A, int nF) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= nF) return;
+  FsCycleState S;
+  mhb_state(state, A.nF, A.nPer, b, S);
+  if (A.filt[b].nZ == 0 && S.w[FSC_OVF] == 0) S.counters[0] += 1;
+}
+// FastSLAM::predict's map part for every live slot, also of a filter whose scan is empty.  Four waves of a workgroup may belong to
+// four filters: no workgroup barrier.
+__global__ __launch_bounds__(256) void fs_cycle_static_step_batch_kernel(Buffers B, int cur, MhBatchArg A) {
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int i = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + wave);
+  if (i >= B.N) return;
+  const int bf = __builtin_amdgcn_readfirstlane(i / A.nPer);
+  if (mhb_ovf(A, bf) || mhb_beyond_count(A, i)) return;
+  predict_map_particle<64>(B, A.params[bf], cur, i, lane, false, 0, B.pose, true);
+}
+__global__ __launch_bounds__(FS_CYCLE_THREADS) void fs_mh_plan_batch_kernel(const unsigned char *arena, unsigned char *state, int *slotHyp, int *slotNH, int *copyDst,
+                                                                            int *copySrc, MhBatchArg A) {
+  const int b = blockIdx.x, base = b * A.nPer;
+  if (A.filt[b].nZ == 0) return;                                     // (workgroup-uniform)
+  FsCycleState S;
+  mhb_state(state, A.nF, A.nPer, b, S);
+  fs_mh_plan_body(arena + (size_t)base * fs_mh_layout().total, S, slotHyp + base, slotNH + base, copyDst + base, copySrc + base, A.nPer);
+}
+// {sum w, sum w^2} of every filter's live weights in weight_sums_kernel's order (thread t adds the slots t, t + 1024, ... of the
+// filter; a wave reduction; the 16 wave sums in order), so a filter's sum has the bits its own handle's has.  A.word names the count.
+__global__ __launch_bounds__(1024) void mhb_weight_sums_kernel(const double *w, double *sums, MhBatchArg A) {
+  __shared__ double s0[16], s1[16];
+  const int b = blockIdx.x;
+  if (live_beyond(A, b * A.nPer)) return;                            // (workgroup-uniform: overflowed, no measurements, or a count of 0)
+  const int N = __builtin_amdgcn_readfirstlane(A.words[(size_t)b * A.wordStride + A.word]);
+  w += (size_t)b * A.nPer;
+  double a = 0, c = 0;
+  for (int k = threadIdx.x; k < N; k += 1024) { double v = w[k]; a += v; c += v * v; }
+  a = wave_sum(a); c = wave_sum(c);
+  if ((threadIdx.x & 63) == 0) { s0[threadIdx.x >> 6] = a; s1[threadIdx.x >> 6] = c; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double x = 0, y = 0;
+    for (int k = 0; k < 16; k++) { x += s0[k]; y += s1[k]; }
+    sums[2 * b] = x; sums[2 * b + 1] = y;
+  }
+}
+__global__ void mhb_normalize_kernel(double *w, int nSlots, const double *sums, MhBatchArg A) {
+  const int k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= nSlots || live_beyond_lane(A, k)) return;
+  w[k] = w[k] / sums[2 * (k / A.nPer)];
+}
+__global__ __launch_bounds__(FS_CYCLE_THREADS) void fs_resample_shrink_batch_kernel(double *weight, unsigned char *state, MhBatchArg A) {
+  const int b = blockIdx.x;
+  const MhBatchFilter &T = A.filt[b];
+  if (T.nZ == 0) return;                                             // (workgroup-uniform)
+  FsCycleState S;
+  mhb_state(state, A.nF, A.nPer, b, S);
+  FsShrinkArg R;
+  R.effN = T.effN; R.effNPercent = T.effNPercent; R.u01 = T.u01;
+  R.nInit = T.nInit; R.nMax = T.nMax; R.nZ = T.nZ;
+  R.minUpdates = T.minUpdates; R.minMeasurements = T.minMeasurements;
+  fs_resample_shrink_body(weight + (size_t)b * A.nPer, S, R);
 }

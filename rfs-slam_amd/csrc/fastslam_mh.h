@@ -81,13 +81,28 @@ __device__ inline void fs_mh_carve(unsigned char *base, const FsMhLayout &L, Mur
 // errBits: ERRBIT_MURTY when the table is larger than FSMH_N or Murty runs out of nodes.
 // live (here and in the kernels below): nothing, or a LiveCount (common.h) for a launch at the handle's capacity whose particle count
 // is on the device (fastslam_cycle.h); a workgroup beyond it leaves before it touches memory.
+// An MhBatchArg (fastslam.h) in its place: a batch of filters with a count each (rfsgpu_batch_fastslam_mh_cycle_async); the slot's
+// filter gives what the arguments give a single handle, and the plan arrays hold slots of the filter's own block.
 template <int D, typename... TLive>
-__global__ __launch_bounds__(64 * FSMH_WAVES) __attribute__((amdgpu_waves_per_eu(D == 2 ? 4 : 3)))   // 2-D: <= 128 VGPRs, 8 workgroups per CU, 2048 particles at once
-void fs_mh_associate_kernel(Buffers B, Params P, FsParams F, int cur, int nZ, int kmax, double maxDiff,
+__global__ __launch_bounds__(64 * FSMH_WAVES) __attribute__((amdgpu_waves_per_eu((D == 2 && !is_mh_batch<TLive...>::value) ? 4 : 3)))   // 2-D: <= 128 VGPRs, 8 workgroups per CU, 2048 particles at once (a batch's form, which reads Params through the table, spills under that cap: 3 waves)
+void fs_mh_associate_kernel(Buffers B, Params Parg, FsParams Farg, int cur, int nZ, int kmax, double maxDiff,
                                                                         unsigned char *arena, TLive... live) {
   if constexpr (sizeof...(TLive) == 1) {
     if (live_beyond(pack_first(live...), (int)blockIdx.x)) return;     // (workgroup-uniform)
   }
+  // A multi-hypothesis batch (MhBatchArg, fastslam.h): the workgroup's filter gives Params, FsParams, the measurement set, the limit
+  // and the window, read in place as fs_associate_update_body does (Parg, Farg, nZ, kmax and maxDiff are ignored).
+  // (the set is read through Zset: writing the filter's pointer into B would move the whole argument struct to scratch)
+  [[maybe_unused]] int bf = 0;
+  const double *Zset = B.Z;
+  if constexpr (is_mh_batch<TLive...>::value) {
+    const MhBatchArg &A = pack_first(live...);
+    bf = (int)blockIdx.x / A.nPer;
+    nZ = A.filt[bf].nZ; kmax = A.filt[bf].kmax; maxDiff = A.filt[bf].maxDiff;
+    Zset = A.z + A.filt[bf].zOff;
+  }
+  const Params &P = [&]() -> const Params & { if constexpr (is_mh_batch<TLive...>::value) return pack_first(live...).params[bf]; else return Parg; }();
+  const FsParams &F = [&]() -> const FsParams & { if constexpr (is_mh_batch<TLive...>::value) return pack_first(live...).filt[bf].F; else return Farg; }();
   __shared__ double sZ[3 * RFSGPU_MAX_Z];
   __shared__ __align__(16) unsigned char sPdScratch[(D == 3) ? ((VP_PD_SCRATCH_BYTES + 15) & ~15) : 16];
   __shared__ double sTile[FSMH_WAVES][FSMH_LDS_N * FSMH_LDS_N];
@@ -97,7 +112,7 @@ void fs_mh_associate_kernel(Buffers B, Params P, FsParams F, int cur, int nZ, in
   __shared__ unsigned char sPushed[FSMH_N];
   const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
   const int i = blockIdx.x;
-  for (int t = threadIdx.x; t < D * nZ; t += 64 * FSMH_WAVES) sZ[t] = B.Z[t];
+  for (int t = threadIdx.x; t < D * nZ; t += 64 * FSMH_WAVES) sZ[t] = Zset[t];
   if (threadIdx.x == 0) { sNRed = 0; sNH = 0; }
   __syncthreads();
 #ifdef RFS_PROFILE
@@ -259,7 +274,11 @@ __global__ __launch_bounds__(256) void fs_mh_copy_kernel(Buffers B, int cur, con
   if constexpr (sizeof...(TLive) == 1) {
     if (live_beyond(pack_first(live...), (int)blockIdx.x)) return;
   }
-  const int d = dstSlot[blockIdx.x], s = srcSlot[blockIdx.x];
+  int d = dstSlot[blockIdx.x], s = srcSlot[blockIdx.x];
+  if constexpr (is_mh_batch<TLive...>::value) {    // the lists are per filter, in slots of the filter's own block
+    const int nPer = pack_first(live...).nPer, base = ((int)blockIdx.x / nPer) * nPer;
+    d += base; s += base;
+  }
   const int n = B.count[s];
   for (int pl = 0; pl < B.npl; pl++) {
     const double *q = B.slab[cur] + ((size_t)s * B.npl + pl) * (size_t)B.cap;
@@ -290,16 +309,21 @@ __global__ __launch_bounds__(256) void fs_mh_copy_kernel(Buffers B, int cur, con
 template <typename... TLive>
 __global__ void fs_mh_split_weights_kernel(double *weight, const int *slotSrc, const int *slotNH, int nSlots, int phase, TLive... live) {
   const int s = blockIdx.x * blockDim.x + threadIdx.x;
-  if constexpr (sizeof...(TLive) == 1) {
+  [[maybe_unused]] int base = 0;
+  if constexpr (is_mh_batch<TLive...>::value) {    // nSlots: every slot of the batch; lanes of a wave may belong to different filters
+    if (s >= nSlots || live_beyond_lane(pack_first(live...), s)) return;
+    const int nPer = pack_first(live...).nPer;
+    base = (s / nPer) * nPer;
+  } else if constexpr (sizeof...(TLive) == 1) {
     if (live_beyond(pack_first(live...), s)) return;
   } else if (s >= nSlots) return;
-  const int nh = slotNH[s], src = slotSrc[s];
+  const int nh = slotNH[s], src = base + slotSrc[s];
   if (nh > 1 && ((phase == 0) == (src != s))) weight[s] = weight[src] / nh;
 }
 
 // One wavefront per slot: the update of one particle under one hypothesis (:559-604, :696-697).
 template <int D, typename... TLive>
-__global__ __launch_bounds__(64) void fs_mh_apply_kernel(Buffers B, Params P, FsParams F, int cur, int nZ, const int *slotSrc, const int *slotHyp,
+__global__ __launch_bounds__(64) void fs_mh_apply_kernel(Buffers B, Params Parg, FsParams Farg, int cur, int nZ, const int *slotSrc, const int *slotHyp,
                                                        const unsigned char *arena, TLive... live) {
   __shared__ double sZ[3 * RFSGPU_MAX_Z];
   __shared__ double sC[FSMH_N];
@@ -308,9 +332,19 @@ __global__ __launch_bounds__(64) void fs_mh_apply_kernel(Buffers B, Params P, Fs
   if constexpr (sizeof...(TLive) == 1) {
     if (live_beyond(pack_first(live...), i)) return;
   }
-  const int src = slotSrc[i], h = slotHyp[i];
+  [[maybe_unused]] int bf = 0, slot0 = 0;
+  const double *Zset = B.Z;
+  if constexpr (is_mh_batch<TLive...>::value) {    // as in fs_mh_associate_kernel; slotSrc is in slots of the filter's own block
+    const MhBatchArg &A = pack_first(live...);
+    bf = i / A.nPer; slot0 = bf * A.nPer;
+    nZ = A.filt[bf].nZ;
+    Zset = A.z + A.filt[bf].zOff;
+  }
+  const Params &P = [&]() -> const Params & { if constexpr (is_mh_batch<TLive...>::value) return pack_first(live...).params[bf]; else return Parg; }();
+  const FsParams &F = [&]() -> const FsParams & { if constexpr (is_mh_batch<TLive...>::value) return pack_first(live...).filt[bf].F; else return Farg; }();
+  const int src = slot0 + slotSrc[i], h = slotHyp[i];
   if (h < 0) return;  // no hypothesis: the particle is left untouched
-  for (int t = lane; t < D * nZ; t += 64) sZ[t] = B.Z[t];
+  for (int t = lane; t < D * nZ; t += 64) sZ[t] = Zset[t];
   wave_sync();
   const FsMhLayout L = fs_mh_layout();
   const unsigned char *base = arena + (size_t)src * L.total;

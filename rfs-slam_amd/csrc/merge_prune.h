@@ -1092,7 +1092,12 @@ __global__ __launch_bounds__(WPB * 64) void gm_prune_kernel(Buffers B, Params P,
   if constexpr (BATCH) {
     const auto &A = batch_first_arg(batchArg...);
     const auto &T = A.filt[__builtin_amdgcn_readfirstlane(i / A.nPer)];
-    if (!(__builtin_amdgcn_readfirstlane(T.nZ) > 0 && __builtin_amdgcn_readfirstlane(T.prune))) {
+    bool carry = !(__builtin_amdgcn_readfirstlane(T.nZ) > 0 && __builtin_amdgcn_readfirstlane(T.prune));
+    if constexpr (is_mh_batch<TBatch...>::value) {   // (MhBatchArg, fastslam.h: every filter has its own live count and overflow word)
+      if (mhb_beyond_count(A, i)) return;
+      carry = carry || mhb_ovf(A, __builtin_amdgcn_readfirstlane(i / A.nPer));   // an overflowed filter is left as it was, in the new slab
+    }
+    if (carry) {
       const int n = B.count[i];
       for (int pl = 0; pl < B.npl; pl++) {
         const double *s = B.slab[src] + ((size_t)i * B.npl + pl) * B.cap;
@@ -1207,13 +1212,18 @@ __global__ void set_weights_kernel(double *w, int N, double v) {
 // Resample copy: slot k takes slot src[k]'s mixture (Particle::copy -> GaussianMixture copy ctor).
 // One block per destination slot; sources are slots that keep themselves, so in-place is hazard-free.
 // live: nothing, or a LiveCount (common.h): destination slots at or beyond the live count are left alone.
+// An MhBatchArg (fastslam.h) in its place: every filter of the batch has its own count, and srcSlot holds slots of the filter's own block.
 template <typename... TLive>
 __global__ __launch_bounds__(256) void resample_gather_kernel(Buffers B, int cur, const int *srcSlot, int poseCovStride, int mapOnly, TLive... live) {
   const int k = blockIdx.x;
   if constexpr (sizeof...(TLive) == 1) {
     if (live_beyond(pack_first(live...), k)) return;
   }
-  const int s = srcSlot[k];
+  int s = srcSlot[k];
+  if constexpr (is_mh_batch<TLive...>::value) {    // (MhBatchArg, fastslam.h: the plan is in slots of the filter's own block)
+    const int nPer = pack_first(live...).nPer;
+    s += (k / nPer) * nPer;
+  }
   if (s == k) return;
   const int n = B.count[s];
   double *slab = B.slab[cur];

@@ -205,10 +205,20 @@ struct rfsgpu_filter {
   hipEvent_t evBLoop[8] = {};
   int bLoopNext = 0;
   // a batch of FastSLAM filters (rfsgpu_batch_fastslam_cycle_async; fastslam.h FsBatchArg)
-  int bKind = 0;                               // what the batch steps: 0 not decided yet, 1 RB-PHD filters, 2 FastSLAM filters (the first cycle call decides)
+  int bKind = 0;                               // what the batch steps: 0 not decided yet, 1 RB-PHD filters, 2 FastSLAM filters (the first cycle call decides), 3 multi-hypothesis FastSLAM filters (rfsgpu_create_batch_mh decides)
   std::vector<rfsgpu_fastslam_config> bFs;     // [nF]
   std::vector<Params> bParamsHost;             // [nF] the device Params table as last written (each filter's pfa comes from its own model)
   FsBatchFilter *dFsFilt = nullptr;            // [nF]
+  // a batch of multi-hypothesis FastSLAM filters (rfsgpu_create_batch_mh; fastslam_cycle.h): nPer is the stride max_per_filter, every
+  // filter has its own cycle block on the device and its live count is a word of it
+  bool mhBatch = false;
+  int nInitPer = 0;                            // n_per_filter: the count a filter starts with and a resampling brings it back to
+  unsigned char *mhbBlock = nullptr;           // device: nF cycle blocks of fs_cycle_state_bytes(nPer) bytes
+  unsigned char *hMhbBlock = nullptr;          // pinned: where they land when the host next synchronises
+  MhBatchFilter *dMhFilt = nullptr;            // [nF] this cycle's per-filter records
+  bool mhbPending = false;                     // cycles are enqueued: the counts, ids and flags on the host are behind the device
+  bool mhbHave = false;                        // a cycle has run
+  std::vector<int> mhbLastNZ;                  // [nF] the last enqueued cycle's measurement counts
   // [metric] per-step map / pose error (map_metric.h): ground truth per filter, the device-side log, one row for the synchronous calls
   double *dGtXY = nullptr, *dGtSeen = nullptr;   // [nF][RFSGPU_MAX_METRIC_SET][2], [nF][RFSGPU_MAX_METRIC_SET] (allocated by the first rfsgpu_set_ground_truth)
   int *dGtN = nullptr;                           // [nF]
@@ -232,7 +242,7 @@ struct rfsgpu_filter {
 static int mhc_resolve(rfsgpu_filter *f);
 #define CHECK_HANDLE(f)                                                       \
   if (!(f)) return RFSGPU_ERR_INVALID;                                        \
-  if ((f)->mhcPending || (f)->mhcStashedRc) {                                 \
+  if ((f)->mhcPending || (f)->mhcStashedRc || (f)->mhbPending) {              \
     const int rcMhc_ = mhc_resolve(f);                                        \
     if (rcMhc_ != RFSGPU_OK) return rcMhc_;                                   \
   }
@@ -270,6 +280,10 @@ __global__ __launch_bounds__(64) void partition_tables_kernel(const double *L, c
 static void batch_set_all(rfsgpu_filter *f);
 #define REFUSE_ON_BATCH(f, what)                                                                                                   \
   if ((f)->batch) return fail(f, RFSGPU_ERR_UNSUPPORTED, what " is not available on a filter batch (rfsgpu_create_batch): use the rfsgpu_batch_* calls")
+
+// (the calls that assume that every filter of a batch fills its block)
+#define REFUSE_ON_MH_BATCH(f, what)                                                                                                 \
+  if ((f)->mhBatch) return fail(f, RFSGPU_ERR_UNSUPPORTED, what " is not available on a batch of multi-hypothesis FastSLAM filters (rfsgpu_create_batch_mh): it assumes that every filter fills its block")
 
 static std::string batch_error_note(rfsgpu_filter *f, int e);
 static void rebuild_params(rfsgpu_filter *f) {
@@ -500,6 +514,7 @@ void rfsgpu_destroy(rfsgpu_filter *f) {
   hipFree(f->dBFilt); hipFree(f->dBParams); hipFree(f->dBZ); hipFree(f->dBZPrev); hipFree(f->dBSums); hipFree(f->dBErrFilter); hipFree(f->dBMaskTmp); hipFree(f->dBInhSrc);
   for (int k = 0; k < 4; k++) { if (f->hBStage[k]) hipHostFree(f->hBStage[k]); if (f->evBStage[k]) hipEventDestroy(f->evBStage[k]); }
   hipFree(f->dFsFilt);
+  hipFree(f->dMhFilt); hipFree(f->mhbBlock); if (f->hMhbBlock) hipHostFree(f->hMhbBlock);
   hipFree(f->dBMotion); hipFree(f->dBPropIn); hipFree(f->dBResIn); hipFree(f->BL.counters); hipFree(f->BL.nResamples); hipFree(f->BL.resampled);
   hipFree(f->BL.fired); hipFree(f->BL.nEff); hipFree(f->BL.plan); hipFree(f->BL.pid); hipFree(f->BL.ppid);
   for (int k = 0; k < 8; k++) { if (f->hBLoop[k]) hipHostFree(f->hBLoop[k]); if (f->evBLoop[k]) hipEventDestroy(f->evBLoop[k]); }
@@ -2173,6 +2188,14 @@ int rfsgpu_set_particle_ids(rfsgpu_filter *f, const int *id, const int *parent_i
   }
   for (int k = 0; k < f->N; k++) { if (id) f->pid[k] = id[k]; if (parent_id) f->ppid[k] = parent_id[k]; }
   f->mhcIdsDirty = true;
+  if (f->mhBatch) {      // (the ids live in the filters' cycle state on the device)
+    FsCycleState S0;
+    mhb_state(f->mhbBlock, f->nF, f->nPer, 0, S0);
+    hipSetDevice(f->device);
+    HIPCHK(hipMemcpyAsync(S0.pid, f->pid.data(), (size_t)f->N * sizeof(int), hipMemcpyHostToDevice, f->stream));
+    HIPCHK(hipMemcpyAsync(S0.ppid, f->ppid.data(), (size_t)f->N * sizeof(int), hipMemcpyHostToDevice, f->stream));
+    HIPCHK(hipStreamSynchronize(f->stream));
+  }
   if (f->bDevRoute) {
     hipSetDevice(f->device);
     HIPCHK(hipMemcpyAsync(f->BL.pid, f->pid.data(), (size_t)f->N * sizeof(int), hipMemcpyHostToDevice, f->stream));
@@ -2583,7 +2606,9 @@ int rfsgpu_particle_parents(rfsgpu_filter *f, int *parent, int max_n) {
 // ---- the whole FastSLAM::update on the device (fastslam_cycle.h) ------------------------------------------------------------------
 // The particle count comes back: one stream-ordered copy of the cycle block into pinned memory, then the wait.  Cycles that an
 // overflow abandoned did not prune, so the slab flips the host made for them are taken back.
+static int mhb_resolve(rfsgpu_filter *f);
 static int mhc_resolve(rfsgpu_filter *f) {
+  if (f->mhbPending) return mhb_resolve(f);     // (a batch of multi-hypothesis filters: its own blocks)
   if (f->mhcStashedRc) { const int rc = f->mhcStashedRc; f->mhcStashedRc = 0; return rc; }   // (f->err still holds its message)
   if (!f->mhcPending) return RFSGPU_OK;
   f->mhcPending = false;
@@ -2891,7 +2916,7 @@ static Params batch_params(rfsgpu_filter *f, int b) {
   return out;
 }
 static size_t batch_stage_bytes(const rfsgpu_filter *f) {
-  return (size_t)f->nF * (std::max(sizeof(BatchFilter), sizeof(FsBatchFilter)) + sizeof(Params) + RFSGPU_MAX_Z * 2 * sizeof(double) + sizeof(int)) + (size_t)f->N * sizeof(int);
+  return (size_t)f->nF * (std::max(sizeof(MhBatchFilter), std::max(sizeof(BatchFilter), sizeof(FsBatchFilter))) + sizeof(Params) + RFSGPU_MAX_Z * 2 * sizeof(double) + sizeof(int)) + (size_t)f->N * sizeof(int);
 }
 // One slot of the batch's pinned ring (as stage_slot): waits until the copies issued from it four cycles ago are done.
 static int batch_stage(rfsgpu_filter *f, unsigned char **h, int *k_out) {
@@ -3002,6 +3027,7 @@ int rfsgpu_batch_cycle_async(rfsgpu_filter *f, int predict, const double *x, con
   CHECK_HANDLE(f);
   int rc = batch_check(f, -1);
   if (rc != RFSGPU_OK) return rc;
+  REFUSE_ON_MH_BATCH(f, "rfsgpu_batch_cycle_async");
   if (predict < -1 || predict > 1) return fail(f, RFSGPU_ERR_INVALID, "batch_cycle: predict is RFSGPU_CYCLE_NO_PREDICT (-1), 0 (static step only) or 1 (births + static step)");
   if (x_cov && cov_stride != 0 && cov_stride != 9) return fail(f, RFSGPU_ERR_INVALID, "batch_cycle: cov_stride must be 0 or 9");
   if (!n_z) return fail(f, RFSGPU_ERR_INVALID, "batch_cycle: null measurement counts");
@@ -3179,7 +3205,12 @@ int rfsgpu_batch_set_fastslam_config(rfsgpu_filter *f, int filter, const rfsgpu_
   if (rc != RFSGPU_OK) return rc;
   if (!cfg) return fail(f, RFSGPU_ERR_INVALID, "batch_set_fastslam_config: null configuration");
   const std::string who = filter < 0 ? std::string("every filter") : "filter " + std::to_string(filter);
-  if (cfg->maxNDataAssocHypotheses != 1u) {
+  if (f->mhBatch) {
+    if (cfg->maxNDataAssocHypotheses < 1u || cfg->maxNDataAssocHypotheses > (unsigned)FSMH_MAX_HYP) {
+      f->err = "batch_set_fastslam_config: " + who + ": maxNDataAssocHypotheses must be in [1, 16]";
+      return RFSGPU_ERR_UNSUPPORTED;
+    }
+  } else if (cfg->maxNDataAssocHypotheses != 1u) {
     f->err = "batch_set_fastslam_config: " + who + ": maxNDataAssocHypotheses must be 1 on a filter batch (the multi-hypothesis update grows the particle set)";
     return RFSGPU_ERR_UNSUPPORTED;
   }
@@ -3190,6 +3221,7 @@ int rfsgpu_batch_set_fastslam_config(rfsgpu_filter *f, int filter, const rfsgpu_
   if (f->bKind == 1)
     return fail(f, RFSGPU_ERR_UNSUPPORTED, "batch_set_fastslam_config: this batch steps RB-PHD filters (rfsgpu_batch_cycle_async has run): a batch is of one kind");
   for (int b = (filter < 0 ? 0 : filter); b < (filter < 0 ? f->nF : filter + 1); b++) f->bFs[b] = *cfg;
+  if (f->mhBatch) return RFSGPU_OK;     // (its kind was decided at creation)
   f->bKind = 2;      // a FastSLAM batch from here on: the [metric] calls read the Gaussians' weights as log-odds
   return RFSGPU_OK;
 }
@@ -3198,6 +3230,7 @@ int rfsgpu_batch_fastslam_cycle_async(rfsgpu_filter *f, int predict, const doubl
   CHECK_HANDLE(f);
   int rc = batch_check(f, -1);
   if (rc != RFSGPU_OK) return rc;
+  REFUSE_ON_MH_BATCH(f, "rfsgpu_batch_fastslam_cycle_async");
   if (predict < -1 || predict > 1) return fail(f, RFSGPU_ERR_INVALID, "batch_fastslam_cycle: predict is RFSGPU_CYCLE_NO_PREDICT (-1), or 0 / 1 (the static landmark step; FastSLAM has no births)");
   if (x_cov && cov_stride != 0 && cov_stride != 9) return fail(f, RFSGPU_ERR_INVALID, "batch_fastslam_cycle: cov_stride must be 0 or 9");
   if (!n_z) return fail(f, RFSGPU_ERR_INVALID, "batch_fastslam_cycle: null measurement counts");
@@ -3287,11 +3320,251 @@ int rfsgpu_batch_fastslam_cycle_async(rfsgpu_filter *f, int predict, const doubl
   f->timing.mapUpdate_cpu += now_ns() - t0;
   return RFSGPU_OK;
 }
+// ---- a batch of multi-hypothesis FastSLAM filters (fastslam_cycle.h, the kernels at its end) -------------------------------------
+// rfsgpu_fastslam_cycle_async for every filter of the batch in one launch chain.  Filter b owns max_per_filter slots of which the
+// first n_b are live; n_b, the overflow word, the counters, the plans and the ids are in the filter's own cycle block on the device.
+static inline size_t mhb_bytes(const rfsgpu_filter *f) { return mhb_state_bytes(f->nF, f->nPer); }
+static void mhb_view(const rfsgpu_filter *f, unsigned char *base, int b, FsCycleState &S) { mhb_state(base, f->nF, f->nPer, b, S); }
+int rfsgpu_create_batch_mh(rfsgpu_filter **out, int model, int n_filters, int n_per_filter, int max_per_filter, int device_id, int gm_capacity) {
+  if (!out) return RFSGPU_ERR_INVALID;
+  *out = nullptr;
+  if (model == RFSGPU_MODEL_VICTORIAPARK_3D) return RFSGPU_ERR_UNSUPPORTED;    // (2-D range-bearing filters only)
+  if (model != RFSGPU_MODEL_RNGBRG_2D || n_filters < 1 || n_per_filter < 1 || max_per_filter < n_per_filter) return RFSGPU_ERR_INVALID;
+  if (max_per_filter > RFSGPU_FASTSLAM_CYCLE_MAX_PARTICLES) return RFSGPU_ERR_UNSUPPORTED;   // (the resampling workgroup holds one filter in LDS)
+  rfsgpu_filter *f = nullptr;
+  int rc = rfsgpu_create_batch(&f, model, n_filters, max_per_filter, device_id, gm_capacity);
+  if (rc != RFSGPU_OK) return rc;
+  f->mhBatch = true;
+  f->bKind = 3;
+  f->nInitPer = n_per_filter;
+  f->mhbLastNZ.assign(n_filters, 0);
+  for (auto &c : f->bFs) c.nParticlesMax = 3 * n_per_filter;      // FastSLAM.hpp:250
+  // the cycle blocks: every filter starts with n_per_filter particles whose ids are their slots within the filter
+  const size_t bytes = mhb_bytes(f);
+  bool ok = hipMalloc(&f->mhbBlock, bytes) == hipSuccess;
+  ok &= hipHostMalloc(&f->hMhbBlock, bytes) == hipSuccess;
+  ok &= hipMalloc(&f->dMhFilt, (size_t)n_filters * sizeof(MhBatchFilter)) == hipSuccess;
+  if (ok) {
+    memset(f->hMhbBlock, 0, bytes);
+    f->pid.resize(f->Ncap); f->ppid.resize(f->Ncap);
+    for (int b = 0; b < n_filters; b++) {
+      FsCycleState H;
+      mhb_view(f, f->hMhbBlock, b, H);
+      H.w[FSC_N] = n_per_filter; H.w[FSC_NGROWN] = n_per_filter;
+      for (int k = 0; k < max_per_filter; k++) {
+        H.slotSrc[k] = k; H.plan[k] = k; H.pid[k] = k; H.ppid[k] = k;
+        f->pid[(size_t)b * max_per_filter + k] = k; f->ppid[(size_t)b * max_per_filter + k] = k;
+      }
+    }
+    ok &= hipMemcpy(f->mhbBlock, f->hMhbBlock, bytes, hipMemcpyHostToDevice) == hipSuccess;
+  }
+  if (!ok) { rfsgpu_destroy(f); return RFSGPU_ERR_HIP; }
+  *out = f;
+  return RFSGPU_OK;
+}
+// The blocks come back: one stream-ordered copy into pinned memory, then the wait.  The ids and resampleOccured_ follow the device; a
+// filter whose overflow word is up is reported once (the lowest such filter is named) and the words are cleared.
+static int mhb_resolve(rfsgpu_filter *f) {
+  if (!f->mhbPending) return RFSGPU_OK;
+  f->mhbPending = false;
+  hipSetDevice(f->device);
+  HIPCHK(hipMemcpyAsync(f->hMhbBlock, f->mhbBlock, mhb_bytes(f), hipMemcpyDeviceToHost, f->stream));
+  const int rc = check_device_errors(f);   // waits for the stream
+  int first = -1;
+  bool badCount = false;
+  for (int b = 0; b < f->nF; b++) {
+    FsCycleState H;
+    mhb_view(f, f->hMhbBlock, b, H);
+    memcpy(f->pid.data() + (size_t)b * f->nPer, H.pid, (size_t)f->nPer * sizeof(int));
+    memcpy(f->ppid.data() + (size_t)b * f->nPer, H.ppid, (size_t)f->nPer * sizeof(int));
+    f->bResampled[b] = H.w[FSC_RESAMPLED] ? 1 : 0;
+    if (H.w[FSC_OVF] && first < 0) first = b;
+    badCount |= H.w[FSC_N] < 1 || H.w[FSC_N] > f->nPer;
+  }
+  if (rc != RFSGPU_OK) {      // another device error comes first; an overflow word that is up stays up (its filter stays abandoned) and
+    if (first >= 0) f->mhbPending = true;     // is reported by the next synchronising call
+    return rc;
+  }
+  if (badCount) return fail(f, RFSGPU_ERR_HIP, "batch_fastslam_mh_cycle: the device returned a particle count outside [1, max_per_filter]");
+  if (first >= 0) {
+    HIPCHK(hipMemset2DAsync(f->mhbBlock + (size_t)24 * f->nF + sizeof(int) * FSC_OVF, sizeof(int) * FSC_WORDS, 0, sizeof(int), (size_t)f->nF, f->stream));
+    f->err = "batch_fastslam_mh_cycle: filter " + std::to_string(first) + ": the particle copies of a multi-hypothesis update exceed max_per_filter (rfsgpu_create_batch_mh); "
+             "that cycle of the filter and those enqueued behind it were abandoned for it, its state is the one before (the other filters' cycles completed)";
+    return RFSGPU_ERR_CAPACITY;
+  }
+  return RFSGPU_OK;
+}
+int rfsgpu_batch_fastslam_mh_cycle_async(rfsgpu_filter *f, int predict, const double *x, const double *x_cov, int cov_stride, const double *z, const int *n_z,
+                                         const double *u01) {
+  if (!f) return RFSGPU_ERR_INVALID;
+  int rc = batch_check(f, -1);
+  if (rc != RFSGPU_OK) return rc;
+  if (!f->mhBatch) return fail(f, RFSGPU_ERR_UNSUPPORTED, "batch_fastslam_mh_cycle: not a batch of multi-hypothesis FastSLAM filters (rfsgpu_create_batch_mh)");
+  if (predict < 0 || predict > 1) return fail(f, RFSGPU_ERR_INVALID, "batch_fastslam_mh_cycle: predict is 0 or 1 (the static landmark step; FastSLAM has no births)");
+  if (x_cov && cov_stride != 0 && cov_stride != 9) return fail(f, RFSGPU_ERR_INVALID, "batch_fastslam_mh_cycle: cov_stride must be 0 or 9");
+  if (!n_z || !u01) return fail(f, RFSGPU_ERR_INVALID, "batch_fastslam_mh_cycle: null measurement counts or draws");
+  const int nF = f->nF, N = f->N, stride = f->nPer;
+  for (int b = 0; b < nF; b++) {
+    if (n_z[b] < 0 || n_z[b] > RFSGPU_MAX_Z) {
+      f->err = "batch_fastslam_mh_cycle: filter " + std::to_string(b) + " has " + std::to_string(n_z[b]) + " measurements (0 ... RFSGPU_MAX_Z)";
+      return RFSGPU_ERR_INVALID;
+    }
+    if (n_z[b] > 0 && !z) return fail(f, RFSGPU_ERR_INVALID, "batch_fastslam_mh_cycle: null measurement buffer");
+    if (!(u01[b] >= 0.0 && u01[b] < 1.0)) {
+      f->err = "batch_fastslam_mh_cycle: filter " + std::to_string(b) + ": u01 must lie in [0, 1)";
+      return RFSGPU_ERR_INVALID;
+    }
+  }
+  hipSetDevice(f->device);
+  long long t0 = now_ns();
+  const FsMhLayout L = fs_mh_layout();
+  if (!f->mhArena) HIPCHK(hipMalloc(&f->mhArena, (size_t)N * L.total));          // every slot's table / Murty arena / assignments, once
+  if (!f->mhcInts) HIPCHK(hipMalloc(&f->mhcInts, (size_t)4 * N * sizeof(int)));
+  batch_handle_wide(f, x, x_cov, cov_stride);
+  unsigned char *h = nullptr;
+  int kb = 0;
+  if ((rc = batch_stage(f, &h, &kb)) != RFSGPU_OK) return rc;
+  MhBatchFilter *hf = reinterpret_cast<MhBatchFilter *>(h);
+  Params *hp = reinterpret_cast<Params *>(h + (size_t)nF * sizeof(MhBatchFilter));
+  double *hz = reinterpret_cast<double *>(h + (size_t)nF * (sizeof(MhBatchFilter) + sizeof(Params)));
+  if (f->bParamsDirty) {
+    for (int b = 0; b < nF; b++) hp[b] = f->bParamsHost[b] = batch_params(f, b);
+    HIPCHK(hipMemcpyAsync(f->dBParams, hp, (size_t)nF * sizeof(Params), hipMemcpyHostToDevice, f->stream));
+    f->bParamsDirty = false;
+  }
+  int zOff = 0;
+  for (int b = 0; b < nF; b++) {
+    MhBatchFilter &T = hf[b];
+    const rfsgpu_fastslam_config &c = f->bFs[b];
+    memset(&T, 0, sizeof T);
+    T.F = fs_params_of(c, f->bParamsHost[b], 2, n_z[b]);
+    T.pruneT = c.mapExistencePruneThreshold;
+    T.nZ = n_z[b];
+    T.zOff = zOff;
+    T.prune = ((unsigned)n_z[b] >= c.pruningMeasurementsThreshold) ? 1 : 0;
+    T.kmax = (int)c.maxNDataAssocHypotheses;
+    T.maxDiff = c.maxDataAssocLogLikelihoodDiff;
+    T.effN = f->bResSet[b] ? f->bEffN[2 * (size_t)b] : f->nInitPer / 4.0;        // ParticleFilter.hpp:232
+    T.effNPercent = f->bResSet[b] ? f->bEffN[2 * (size_t)b + 1] : 0.25;
+    T.u01 = u01[b];
+    T.nInit = f->nInitPer;
+    T.nMax = (int)c.nParticlesMax;
+    T.minUpdates = (int)c.minUpdatesBeforeResample;
+    T.minMeasurements = (int)c.minMeasurementsBeforeResample;
+    if (n_z[b] > 0) memcpy(hz + zOff, z + (size_t)b * RFSGPU_MAX_Z * 2, (size_t)n_z[b] * 2 * sizeof(double));
+    zOff += 2 * n_z[b];
+  }
+  HIPCHK(hipMemcpyAsync(f->dMhFilt, hf, (size_t)nF * sizeof(MhBatchFilter), hipMemcpyHostToDevice, f->stream));
+  if (zOff) HIPCHK(hipMemcpyAsync(f->dBZ, hz, (size_t)zOff * sizeof(double), hipMemcpyHostToDevice, f->stream));
+  HIPCHK(hipEventRecord(f->evBStage[kb], f->stream));
+  if (x) {      // the host's new poses / covariances through a slot of the staging ring (every slot of every block)
+    double *hx = nullptr;
+    int ks = -1;
+    if ((rc = stage_slot(f, &hx, &ks)) != RFSGPU_OK) return rc;
+    memcpy(hx, x, (size_t)N * 3 * sizeof(double));
+    HIPCHK(hipMemcpyAsync(f->B.pose, hx, (size_t)N * 3 * sizeof(double), hipMemcpyHostToDevice, f->stream));
+    double *hc = hx + (size_t)f->Ncap * 3;
+    if (x_cov) {
+      const size_t n = cov_stride == 9 ? (size_t)N * 9 : 9;
+      memcpy(hc, x_cov, n * sizeof(double));
+      HIPCHK(hipMemcpyAsync(f->B.poseCov, hc, n * sizeof(double), hipMemcpyHostToDevice, f->stream));
+      f->poseCovZero = false;
+    } else if (!f->poseCovZero) {
+      memset(hc, 0, 9 * sizeof(double));
+      HIPCHK(hipMemcpyAsync(f->B.poseCov, hc, 9 * sizeof(double), hipMemcpyHostToDevice, f->stream));
+      f->poseCovZero = true;
+    }
+    HIPCHK(hipEventRecord(f->evStage[ks], f->stream));
+  }
+  f->bBirthAlt = false;
+  FsCycleState S0;      // filter 0's view: its slot arrays are the batch's, [N] each, holding slots local to each filter's block
+  mhb_view(f, f->mhbBlock, 0, S0);
+  MhBatchArg A{f->dMhFilt, f->dBParams, f->dBZ, f->dBErrFilter, stride, predict, nF, S0.w, FSC_WORDS, FSC_N};
+  MhBatchArg Acopy = A, Arenorm = A;
+  Acopy.word = FSC_NCOPY;
+  Arenorm.word = FSC_RENORM_N;
+  int *dSlotHyp = f->mhcInts, *dSlotNH = dSlotHyp + N, *dDst = dSlotNH + N, *dSrc = dDst + N;
+  fs_cycle_begin_batch_kernel<<<(nF + 63) / 64, 64, 0, f->stream>>>(f->mhbBlock, A, nF);
+  if (predict) fs_cycle_static_step_batch_kernel<<<(N + 3) / 4, 256, 0, f->stream>>>(f->B, f->cur, A);
+  fs_mh_associate_kernel<2><<<N, 64 * FSMH_WAVES, 0, f->stream>>>(f->B, f->P, FsParams{}, f->cur, 0, 0, 0.0, f->mhArena, A);
+  fs_mh_plan_batch_kernel<<<nF, FS_CYCLE_THREADS, 0, f->stream>>>(f->mhArena, f->mhbBlock, dSlotHyp, dSlotNH, dDst, dSrc, A);
+  fs_mh_copy_kernel<<<N, 256, 0, f->stream>>>(f->B, f->cur, dDst, dSrc, 0, f->P.poseCovStride, Acopy);
+  fs_mh_split_weights_kernel<<<(N + 255) / 256, 256, 0, f->stream>>>(f->B.weight, S0.slotSrc, dSlotNH, N, 0, A);
+  fs_mh_split_weights_kernel<<<(N + 255) / 256, 256, 0, f->stream>>>(f->B.weight, S0.slotSrc, dSlotNH, N, 1, A);
+  fs_mh_apply_kernel<2><<<N, 64, 0, f->stream>>>(f->B, f->P, FsParams{}, f->cur, 0, S0.slotSrc, dSlotHyp, f->mhArena, A);
+  HIPCHK(hipGetLastError());
+  // the prune of the filters that prune this cycle (:611-612); the others' mixtures -- no measurements, below their
+  // pruningMeasurementsThreshold, overflowed -- move unchanged to the other slab, because the batch flips `cur` as one
+  const size_t pb = gm_prune_lds_bytes_per_wave(f->cap);
+  if ((rc = set_lds(f, (gm_prune_kernel<4, false, true, MhBatchArg>), 4 * pb)) != RFSGPU_OK) return rc;
+  gm_prune_kernel<4, false, true, MhBatchArg><<<(N + 3) / 4, 256, 4 * pb, f->stream>>>(f->B, f->P, f->cur, f->cur ^ 1, A);
+  f->cur ^= 1;
+  fs_new_landmarks_kernel<2, true, MhBatchArg><<<(N + FS_NEWLM_WPB - 1) / FS_NEWLM_WPB, 64 * FS_NEWLM_WPB, 0, f->stream>>>(f->B, f->P, FsParams{}, f->cur, 0, A);
+  // resampleWithMapCopy per filter, as rfsgpu_fastslam_cycle_async: normalisation, decision and plan, copies, and the second
+  // normalisation of a resample() that returned false
+  mhb_weight_sums_kernel<<<nF, 1024, 0, f->stream>>>(f->B.weight, f->dBSums, A);
+  mhb_normalize_kernel<<<(N + 255) / 256, 256, 0, f->stream>>>(f->B.weight, N, f->dBSums, A);
+  fs_resample_shrink_batch_kernel<<<nF, FS_CYCLE_THREADS, 0, f->stream>>>(f->B.weight, f->mhbBlock, A);
+  resample_gather_kernel<<<N, 256, 0, f->stream>>>(f->B, f->cur, S0.plan, f->P.poseCovStride, 0, A);
+  mhb_weight_sums_kernel<<<nF, 1024, 0, f->stream>>>(f->B.weight, f->dBSums, Arenorm);
+  mhb_normalize_kernel<<<(N + 255) / 256, 256, 0, f->stream>>>(f->B.weight, N, f->dBSums, Arenorm);
+  HIPCHK(hipGetLastError());
+  for (int b = 0; b < nF; b++) {
+    f->mhbLastNZ[b] = n_z[b];
+    if (n_z[b] > 0) f->bNZ[b] = n_z[b];
+  }
+  f->holes = false;
+  f->mhbPending = true;
+  f->mhbHave = true;
+  f->timing.mapUpdate_cpu += now_ns() - t0;
+  return RFSGPU_OK;
+}
+// The last cycle of every filter (synchronising).  Per-filter arrays [n_filters]; parent and plan [n_filters * max_per_filter] in slots
+// local to the filter: identity where nothing happened, -1 beyond the counts.
+int rfsgpu_batch_fastslam_last_cycle(rfsgpu_filter *f, int *n_after_update, int *n_after_resample, unsigned char *fired, double *n_eff, unsigned char *overflowed,
+                                     int *parent, int *plan) {
+  CHECK_HANDLE(f);
+  int rc = batch_check(f, -1);
+  if (rc != RFSGPU_OK) return rc;
+  if (!f->mhBatch) return fail(f, RFSGPU_ERR_UNSUPPORTED, "batch_fastslam_last_cycle: not a batch of multi-hypothesis FastSLAM filters (rfsgpu_create_batch_mh)");
+  if (!f->mhbHave) return fail(f, RFSGPU_ERR_INVALID, "batch_fastslam_last_cycle: no rfsgpu_batch_fastslam_mh_cycle_async has run on this handle");
+  const int stride = f->nPer;
+  for (int b = 0; b < f->nF; b++) {
+    FsCycleState H;
+    mhb_view(f, f->hMhbBlock, b, H);
+    const bool ovf = H.w[FSC_OVF] != 0, idle = ovf || f->mhbLastNZ[b] == 0;     // (nothing happened to this filter in the last cycle)
+    const int n = H.w[FSC_N], ng = idle ? n : H.w[FSC_NGROWN];
+    if (n_after_update) n_after_update[b] = ng;
+    if (n_after_resample) n_after_resample[b] = n;
+    if (fired) fired[b] = (!idle && H.w[FSC_FIRED]) ? 1 : 0;
+    if (n_eff) n_eff[b] = idle ? 0.0 : H.nEff[0];
+    if (overflowed) overflowed[b] = ovf ? 1 : 0;
+    for (int k = 0; k < stride; k++) {
+      if (parent) parent[(size_t)b * stride + k] = k < ng ? (idle ? k : H.slotSrc[k]) : -1;
+      if (plan) plan[(size_t)b * stride + k] = k < n ? (idle ? k : H.plan[k]) : -1;
+    }
+  }
+  return RFSGPU_OK;
+}
+int rfsgpu_batch_live_counts(rfsgpu_filter *f, int *out) {
+  CHECK_HANDLE(f);
+  int rc = batch_check(f, -1);
+  if (rc != RFSGPU_OK) return rc;
+  if (!f->mhBatch) return fail(f, RFSGPU_ERR_UNSUPPORTED, "batch_live_counts: not a batch of multi-hypothesis FastSLAM filters (rfsgpu_create_batch_mh)");
+  if (!out) return fail(f, RFSGPU_ERR_INVALID, "batch_live_counts: null output");
+  for (int b = 0; b < f->nF; b++) {
+    FsCycleState H;
+    mhb_view(f, f->hMhbBlock, b, H);
+    out[b] = H.w[FSC_N];
+  }
+  return RFSGPU_OK;
+}
 // {sum w, sum w^2} of every filter's current weights, [n_filters][2] (synchronising).
 int rfsgpu_batch_weight_sums(rfsgpu_filter *f, double *out) {
   CHECK_HANDLE(f);
   int rc = batch_check(f, -1);
   if (rc != RFSGPU_OK) return rc;
+  REFUSE_ON_MH_BATCH(f, "rfsgpu_batch_weight_sums");
   if (!out) return fail(f, RFSGPU_ERR_INVALID, "batch_weight_sums: null output");
   hipSetDevice(f->device);
   batch_weight_sums_kernel<<<f->nF, 256, 0, f->stream>>>(f->B.weight, f->nPer, f->dBSums);
@@ -3306,6 +3579,7 @@ int rfsgpu_batch_resample_apply(rfsgpu_filter *f, const int *src_slot, const uns
   CHECK_HANDLE(f);
   int rc = batch_check(f, -1);
   if (rc != RFSGPU_OK) return rc;
+  REFUSE_ON_MH_BATCH(f, "rfsgpu_batch_resample_apply");
   if (!src_slot || !resampled) return fail(f, RFSGPU_ERR_INVALID, "batch_resample_apply: null argument");
   if (f->bDevRoute)
     return fail(f, RFSGPU_ERR_UNSUPPORTED, "batch_resample_apply: this batch resamples on the device (rfsgpu_batch_resample_async has run): the particle ids, resampleOccured_ "
@@ -3368,6 +3642,10 @@ int rfsgpu_murty_seen(rfsgpu_filter *f) {
 // resampleOccured_ of every filter, [n_filters]
 int rfsgpu_batch_resample_occured(const rfsgpu_filter *f, unsigned char *out) {
   if (!f || !f->batch || !out) return RFSGPU_ERR_INVALID;
+  if (f->mhbPending) {     // (a batch of multi-hypothesis filters with cycles in flight: the flags are the device's; synchronising)
+    const int rc = mhb_resolve(const_cast<rfsgpu_filter *>(f));
+    if (rc != RFSGPU_OK) return rc;
+  }
   if (f->bDevRoute) {      // (a batch that resamples on the device: the flags live there; synchronising)
     std::vector<int> r(f->nF);
     hipSetDevice(f->device);
@@ -3475,6 +3753,7 @@ int rfsgpu_batch_resample_async(rfsgpu_filter *f, const int *n_z, unsigned long 
   CHECK_HANDLE(f);
   int rc = batch_check(f, -1);
   if (rc != RFSGPU_OK) return rc;
+  REFUSE_ON_MH_BATCH(f, "rfsgpu_batch_resample_async");
   if (!n_z) return fail(f, RFSGPU_ERR_INVALID, "batch_resample: null measurement counts");
   const int nF = f->nF;
   if (f->nPer > RFSGPU_BATCH_RESAMPLE_MAX_PER_FILTER)
@@ -3530,6 +3809,7 @@ int rfsgpu_batch_last_resample(rfsgpu_filter *f, unsigned char *fired, int *src_
   CHECK_HANDLE(f);
   int rc = batch_check(f, -1);
   if (rc != RFSGPU_OK) return rc;
+  REFUSE_ON_MH_BATCH(f, "rfsgpu_batch_last_resample");
   hipSetDevice(f->device);
   if (!f->bDevRoute) {     // no rfsgpu_batch_resample_async yet: nothing fired
     for (int b = 0; b < f->nF; b++) { if (fired) fired[b] = 0; if (n_eff) n_eff[b] = 0.0; }
@@ -3560,6 +3840,7 @@ int rfsgpu_batch_resample_counts(rfsgpu_filter *f, long long *out) {
   CHECK_HANDLE(f);
   int rc = batch_check(f, -1);
   if (rc != RFSGPU_OK) return rc;
+  REFUSE_ON_MH_BATCH(f, "rfsgpu_batch_resample_counts");
   if (!out) return fail(f, RFSGPU_ERR_INVALID, "batch_resample_counts: null output");
   hipSetDevice(f->device);
   HIPCHK(hipMemcpyAsync(out, f->BL.nResamples, (size_t)f->nF * sizeof(long long), hipMemcpyDeviceToHost, f->stream));
@@ -3569,7 +3850,7 @@ int rfsgpu_batch_resample_counts(rfsgpu_filter *f, long long *out) {
 
 // ---- [metric] per-step map error and pose error (map_metric.h) ------------------------------------------------------------------------
 static int metric_check(rfsgpu_filter *f, const char *what) {
-  const char *why = f->D != 2 ? "the Victoria Park model" : (f->fastSlamHandle ? "a FastSLAM handle" : (f->groupShard ? "a shard of an rfsgpu_group" : nullptr));
+  const char *why = f->D != 2 ? "the Victoria Park model" : (f->fastSlamHandle ? "a FastSLAM handle" : (f->groupShard ? "a shard of an rfsgpu_group" : (f->mhBatch ? "a batch of multi-hypothesis FastSLAM filters (rfsgpu_create_batch_mh: the step-error kernel assumes that every filter fills its block)" : nullptr)));
   if (!why) return RFSGPU_OK;
   f->err = std::string(what) + ": the device-side map / pose error serves ordinary 2-D RB-PHD handles and filter batches (RB-PHD or FastSLAM) only, not " + why;
   return RFSGPU_ERR_UNSUPPORTED;

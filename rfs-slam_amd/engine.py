@@ -257,9 +257,11 @@ class FastSLAM(RBPHDFilter):
     handle has room for nParticlesMax * max_hypotheses particles; `parents` (slot -> the particle it was copied from in the
     last update) and `last_resample_plan` let a caller holding poses follow the copies."""
 
-    def __init__(self, n_particles, device_id=0, gm_capacity=512, max_hypotheses=1, n_particles_max=None, device_cycle=False):
+    def __init__(self, n_particles, device_id=0, gm_capacity=512, max_hypotheses=1, n_particles_max=None, device_cycle=False, max_particles=None):
         n_max = 3 * n_particles if n_particles_max is None else int(n_particles_max)    # FastSLAM.hpp:250
         cap = max(n_particles, n_max) * max(1, int(max_hypotheses)) if max_hypotheses > 1 else None
+        if max_particles is not None:       # the handle's particle slots, given outright (the yardstick of one filter of an MHFastSLAMBatch)
+            cap = int(max_particles)
         super().__init__(n_particles, device_id=device_id, gm_capacity=gm_capacity, max_particles=cap)
         self.fs_config = self.default_fastslam_config()
         self.fs_config.nParticlesMax = n_max
@@ -532,3 +534,45 @@ class FastSLAMBatch(FilterBatch):
 
     def _gate_config(self, b):
         return self.fs_configs[b]
+
+
+class MHFastSLAMBatch(capi.CBatchMH):
+    """n_filters independent 2-D multi-hypothesis FastSLAM filters stepped together (rfsgpu_create_batch_mh,
+    rfsgpu_batch_fastslam_mh_cycle_async): per cycle one launch chain runs every filter's whole FastSLAM::update -- association with
+    Murty's k best, particle copies, Kalman update, prune, new landmarks, normalisation and resampleWithMapCopy -- with each filter's
+    live particle count on the device.  Filter b owns max_per_filter global slots (block(b)), of which the first live_counts()[b] are
+    live; each filter equals a FastSLAM(n_per_filter, max_hypotheses=..., device_cycle=True) handle with max_particles =
+    max_per_filter given the same inputs.  The model / Kalman filter / landmark noise of a filter come through configure(b, None,
+    R=..., ...), the FastSLAM configuration through configure_fastslam(b, fs_cfg), the N_eff thresholds through set_resampling."""
+
+    def __init__(self, n_filters, n_per_filter, max_per_filter=None, device_id=0, gm_capacity=512, max_hypotheses=3):
+        # default: nParticlesMax x max_hypotheses slots (a set at nParticlesMax = 3 n is not forced back, and the next update can multiply
+        # it once more before any resampling), at most the 2048 one resampling workgroup holds
+        m = min(2048, 3 * int(n_per_filter) * max(1, int(max_hypotheses))) if max_per_filter is None else int(max_per_filter)
+        super().__init__(load_library(), "rfsgpu_", n_filters, n_per_filter, m, device_id=device_id, gm_capacity=gm_capacity)
+        self.fs_configs = [self.default_fastslam_config() for _ in range(n_filters)]
+        for c in self.fs_configs:
+            c.nParticlesMax = 3 * int(n_per_filter)          # FastSLAM.hpp:250
+
+    def configure(self, b, cfg=None, **model):
+        """Filter b's model / Kalman filter / landmark noise (see CBatch.batch_configure)."""
+        self.batch_configure(b, cfg=cfg, **model)
+
+    def configure_fastslam(self, b, fs_cfg):
+        """Filter b's (None: every filter's) FastSlamConfig: maxNDataAssocHypotheses 1 ... 16; a landmark-candidate count threshold other
+        than 1 is refused."""
+        self.batch_set_fastslam_config(b, fs_cfg)
+        for q in (range(self.n_filters) if b is None else [b]):
+            self.fs_configs[q] = fs_cfg
+
+    def cycle_async(self, predict, Zs, u01, poses=None, pose_cov=None):
+        """One whole FastSLAM::update of every filter, enqueued; nothing is read back.  u01 [n_filters]: the draws a resampling would use."""
+        self.batch_fastslam_mh_cycle_async(predict, Zs, u01, poses=poses, pose_cov=pose_cov)
+
+    def last_cycle(self):
+        """What the last cycle did, per filter (synchronises): see CBatchMH.batch_fastslam_last_cycle."""
+        return self.batch_fastslam_last_cycle()
+
+    def live_counts(self):
+        """The live particle count of every filter (synchronises)."""
+        return self.batch_live_counts()

@@ -20,6 +20,11 @@ repetitions of each figure (fresh batch each), all of them in the line ("..._rep
 --fastslam: the same table for the FastSLAM half of a comparison sweep (the reference's fastslam2dSim over the same grid): a
 FastSLAMBatch (rfsgpu_batch_fastslam_cycle_async) against FastSLAM handles stepped in turn (predict_map, fastslam_update, normalise,
 resample per handle), host loop / device loop, --errors.  Every line then carries "filter": "fastslam".
+
+--mhfastslam: the third sweep of the reference's scripts/batchSim (batchSim_mhfastslam.bash): multi-hypothesis FastSLAM filters with the
+filter values of tests/golden/mhfastslam2dSim_c1.xml (200 particles, 3 hypotheses, log-likelihood window 3.0) as an MHFastSLAMBatch
+(rfsgpu_batch_fastslam_mh_cycle_async; --max-per-filter slots per filter, default nParticlesMax x hypotheses = 1800) against the same filters as handles on
+rfsgpu_fastslam_cycle_async stepped in turn.  --both-loops / --device-loop / --reps as above; every line carries "filter": "mhfastslam".
 """
 import argparse
 import json
@@ -134,6 +139,149 @@ def errors_sweep(pkg, a, sizes, Ps, datas, seeds):
     return rows
 
 
+def mh_params(sim):
+    """C1_FASTSLAM_SIM with the filter values of tests/golden/mhfastslam2dSim_c1.xml (200 particles, 3 hypotheses, window 3.0)."""
+    import xml.etree.ElementTree as ET
+    t = ET.parse(os.path.join(ROOT, "tests", "golden", "mhfastslam2dSim_c1.xml")).getroot()
+    g = lambda path: t.find(path).text
+    P = dict(sim.C1_FASTSLAM_SIM, max_hypotheses=int(g("filter/update/maxNDataAssocHypotheses")), max_loglik_diff=float(g("filter/update/maxDataAssocLogLikelihoodDiff")),
+             min_log_likelihood=float(g("filter/weighting/minLogMeasurementLikelihood")), existence_prune_thr=float(g("filter/prune/threshold")),
+             eff_n=float(g("filter/resampling/effNParticle")), min_updates=int(g("filter/resampling/minTimesteps")))
+    return P, int(next(t.iter("nParticles")).text)
+
+
+class MhRun:
+    """The simulator loop for multi-hypothesis FastSLAM filters in one of three forms: an MHFastSLAMBatch with its host loop (the host
+    reads the counts and poses back, propagates the live slots and passes them with the cycle) or its device loop (propagate_async +
+    cycle, nothing read back), or handles on rfsgpu_fastslam_cycle_async stepped in turn.  Every filter's draws are pre-drawn from its
+    seed, so the device loop waits for nothing."""
+
+    def __init__(self, pkg, target, datas, Ps, seeds, n, device_loop=False):
+        sim = pkg.sim2d_driver
+        self.sim, self.datas, self.Ps, self.n, self.nF = sim, datas, Ps, n, len(datas)
+        self.batch = target if isinstance(target, pkg.capi.CBatchMH) else None
+        self.handles = None if self.batch is not None else list(target)
+        self.device_loop = bool(device_loop)
+        K = int(min(d["K"] for d in datas))
+        self.rngs = [np.random.default_rng(s) for s in seeds]
+        self.u01 = np.ascontiguousarray(np.stack([np.random.default_rng(10_000 + s).random(K) for s in seeds], axis=1))      # [K, nF]
+        self.Q = [np.diag([P["vardx"], P["vardy"], P["vardz"]]) * P["p_noise_inflation"] * P["dt"] ** 2 for P in Ps]
+        for b, P in enumerate(Ps):
+            if self.batch is not None:
+                c = sim.configure_fastslam_batch_filter(self.batch, b, P)
+                c.nParticlesMax = 3 * n
+                self.batch.configure_fastslam(b, c)
+                self.batch.set_resampling(b, P["eff_n"], P["eff_n"] / n)
+                self.batch.set_motion_odometry(b, np.diag(self.Q[b]), seeds[b])
+            else:
+                h = self.handles[b]
+                h.fs_config = sim.configure_fastslam(h, P)
+                h.fs_config.nParticlesMax = 3 * n
+                h.setEffectiveParticleCountThreshold(P["eff_n"])
+        self._u = np.ascontiguousarray(np.stack([d["odom"][:K] for d in datas], axis=1))
+        self._gt = np.ascontiguousarray(np.stack([d["gt"][:K] for d in datas], axis=1))
+        self._z = np.zeros((K, self.nF, pkg.capi.MAX_Z, 2))
+        self._nz = np.zeros((K, self.nF), dtype=np.int32)
+        for b, d in enumerate(datas):
+            for k in range(K):
+                Z = d["Z"][k] if k < len(d["Z"]) else np.zeros((0, 2))
+                self._nz[k, b] = len(Z)
+                self._z[k, b, :len(Z)] = Z
+        self._pin_all = np.ones(self.nF, dtype=np.uint8)
+
+    def _moved(self, b, x, k):
+        """ParticleFilter::propagate of filter b's live particles on the host (the ground truth for the first 100 steps, :590-593)."""
+        if k <= 100:
+            return np.tile(self._gt[k, b], (x.shape[0], 1)), np.zeros(9)
+        noise = self.rngs[b].standard_normal(x.shape) * np.sqrt(np.diag(self.Q[b]))
+        return self.sim.odometry_step(x, self._u[k, b]) + noise, self.Q[b].ravel()
+
+    def step(self, k):
+        bt = self.batch
+        if self.device_loop:
+            bt.propagate_async(self._u[k], k, pin=self._pin_all if k <= 100 else None, pin_pose=self._gt[k] if k <= 100 else None)
+            bt.batch_fastslam_mh_cycle_async_packed(True, self._z[k], self._nz[k], self.u01[k])
+        elif bt is not None:
+            counts = bt.live_counts()
+            x = bt.get_poses()
+            cov = np.zeros((bt.n, 9))
+            for b in range(self.nF):
+                blk = bt.block(b, counts[b])
+                x[blk], cov[blk] = self._moved(b, x[blk], k)
+            bt.batch_fastslam_mh_cycle_async_packed(True, self._z[k], self._nz[k], self.u01[k], poses=x, pose_cov=cov)
+        else:
+            for b, h in enumerate(self.handles):
+                x, c = self._moved(b, h.get_poses(), k)
+                h.set_poses(x, np.tile(c, (x.shape[0], 1)))
+                h.cycle_async(self._z[k, b, :self._nz[k, b]], float(self.u01[k, b]), predict=True)
+
+    def synchronize(self):
+        for f in ([self.batch] if self.batch is not None else self.handles):
+            f.synchronize()
+
+
+def mh_handle(pkg, n, max_per_filter, capacity):
+    """A FastSLAM handle on the device cycle with exactly max_per_filter particle slots: the batch's yardstick."""
+    return pkg.FastSLAM(n, gm_capacity=capacity, device_cycle=True, max_particles=max_per_filter)
+
+
+def mh_sweep(pkg, a, sizes):
+    """--mhfastslam: filter-steps/s of an MHFastSLAMBatch (host loop and / or device loop) and of the same filters as handles on
+    rfsgpu_fastslam_cycle_async stepped in turn; each figure the median of --reps timed repetitions within this invocation."""
+    sim = pkg.sim2d_driver
+    P0, n_xml = mh_params(sim)
+    n = a.particles or n_xml
+    stride = a.max_per_filter or min(2048, 3 * n * P0["max_hypotheses"])      # nParticlesMax x hypotheses: cannot overflow
+    pds = [0.5, 0.6, 0.7, 0.8, 0.9, 0.95, 0.99, 0.85, 0.75, 0.65]
+    clutters = [1e-4, 5e-4, 1e-3, 2e-3, 5e-3, 1e-2, 2e-2, 5e-2, 1e-1]
+    Ps = [dict(P0, Pd=pds[b % len(pds)], clutter=clutters[(b // len(pds)) % len(clutters)]) for b in range(max(sizes))]
+    datas = [sim.generate(P, traj_seed=1 + b, kmax=a.steps + 2) for b, P in enumerate(Ps)]
+    seeds = [100 + b for b in range(max(sizes))]
+    loops = ["host", "device"] if a.both_loops else (["device"] if a.device_loop else ["host"])
+
+    def timed_run(make):
+        figs = []
+        for _ in range(max(1, a.reps)):
+            run, close = make()
+            run.step(1)
+            run.synchronize()
+            t0 = time.perf_counter()
+            for k in range(2, a.steps + 2):
+                run.step(k)
+            run.synchronize()
+            figs.append(len(run.datas) * a.steps / (time.perf_counter() - t0))
+            extra = run.batch.live_counts().tolist() if run.batch is not None else None
+            close()
+        return figs, extra
+
+    rows = []
+    for B in sizes:
+        row = dict(B=B, particles=n, max_per_filter=stride, steps=a.steps, filter="mhfastslam", hypotheses=P0["max_hypotheses"], loop="+".join(loops))
+        for loop in loops:
+            def make(loop=loop):
+                bt = pkg.MHFastSLAMBatch(B, n, stride, gm_capacity=a.capacity)
+                return MhRun(pkg, bt, datas[:B], Ps[:B], seeds[:B], n, device_loop=(loop == "device")), bt.close
+            figs, counts = timed_run(make)
+            key = "batch_filter_steps_per_s" if loop == "host" else "device_loop_filter_steps_per_s"
+            row[key], row[key + "_reps"] = float(np.median(figs)), figs
+            row["final_counts_" + loop] = counts
+        if B <= a.handles_max:
+            def make_h():
+                hs = [mh_handle(pkg, n, stride, a.capacity) for _ in range(B)]
+                return MhRun(pkg, hs, datas[:B], Ps[:B], seeds[:B], n), (lambda: [h.close() for h in hs])
+            figs, _ = timed_run(make_h)
+            row["handles_filter_steps_per_s"], row["handles_filter_steps_per_s_reps"] = float(np.median(figs)), figs
+            for key, name in (("batch_filter_steps_per_s", "speedup"), ("device_loop_filter_steps_per_s", "device_loop_speedup")):
+                if key in row:
+                    row[name] = row[key] / row["handles_filter_steps_per_s"]
+        rows.append(row)
+        print(json.dumps(row), flush=True)
+    if a.json:
+        os.makedirs(os.path.dirname(a.json) or ".", exist_ok=True)
+        with open(a.json, "w") as fh:
+            json.dump(rows, fh, indent=1)
+
+
 def make_batch(pkg, a, B):
     return pkg.FastSLAMBatch(B, a.particles, gm_capacity=a.capacity) if a.fastslam else pkg.FilterBatch(B, a.particles, gm_capacity=a.capacity)
 
@@ -142,7 +290,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--sizes", default="1,4,16,64")
-    ap.add_argument("--particles", type=int, default=200)
+    ap.add_argument("--particles", type=int, default=None, help="particles per filter (default 200; --mhfastslam: the golden configuration's)")
     ap.add_argument("--handles-max", type=int, default=64, help="largest batch size also run as independent handles")
     ap.add_argument("--capacity", type=int, default=256)
     ap.add_argument("--json", default="")
@@ -151,8 +299,13 @@ def main():
     ap.add_argument("--both-loops", action="store_true", help="host loop and device loop side by side")
     ap.add_argument("--fastslam", action="store_true", help="FastSLAM filters: a FastSLAMBatch against FastSLAM handles stepped in turn")
     ap.add_argument("--reps", type=int, default=1, help="timed repetitions of every batch figure")
+    ap.add_argument("--mhfastslam", action="store_true", help="multi-hypothesis FastSLAM filters: an MHFastSLAMBatch against handles on the device cycle stepped in turn")
+    ap.add_argument("--max-per-filter", type=int, default=0, help="--mhfastslam: particle slots per filter (default nParticlesMax x hypotheses = 9 x particles, which cannot overflow; at most 2048)")
     a = ap.parse_args()
     pkg = load_pkg()
+    if a.mhfastslam:
+        return mh_sweep(pkg, a, [int(s) for s in a.sizes.split(",")])
+    a.particles = a.particles or 200
     sim = pkg.sim2d_driver
     sizes = [int(s) for s in a.sizes.split(",")]
     kmax = a.steps + 2
