@@ -792,7 +792,8 @@ int rfsgpu_batch_fastslam_cycle_async(rfsgpu_filter *f, int predict, const doubl
  * rfsgpu_batch_propagate_async is allowed and moves every slot of every block (its draws are keyed by the slot within the filter, so
  * a live slot's draw does not depend on the counts).  Refused with RFSGPU_ERR_UNSUPPORTED, state untouched, because each assumes
  * that every filter fills its block: rfsgpu_batch_cycle_async, rfsgpu_batch_fastslam_cycle_async, rfsgpu_batch_resample_async /
- * _resample_apply / _last_resample / _resample_counts, rfsgpu_batch_weight_sums and the [metric] calls. */
+ * _resample_apply / _last_resample / _resample_counts, rfsgpu_batch_weight_sums and -- until rfsgpu_batch_mh_serve_metrics below
+ * switches their live-count form on -- the [metric] calls. */
 int rfsgpu_create_batch_mh(rfsgpu_filter **out, int model, int n_filters, int n_per_filter, int max_per_filter, int device_id,
                            int gm_capacity);
 /* One whole FastSLAM::update (FastSLAM.hpp:387-421) of every filter, enqueued as one launch chain: per filter what
@@ -821,6 +822,29 @@ int rfsgpu_batch_fastslam_last_cycle(rfsgpu_filter *f, int *n_after_update, int 
                                      double *n_eff, unsigned char *overflowed, int *parent, int *plan);
 /* The live particle count of every filter: out [n_filters].  Synchronising. */
 int rfsgpu_batch_live_counts(rfsgpu_filter *f, int *out);
+/* on != 0: from this call on the [metric] calls serve this multi-hypothesis batch (see below); on == 0: they refuse again.
+ * Not a handle of rfsgpu_create_batch_mh: RFSGPU_ERR_UNSUPPORTED with a message.  Synchronising; the filters' state is untouched.
+ * The switch is off at creation: the refusal of the [metric] calls is what such a handle was published with.
+ *
+ * With the switch on, rfsgpu_set_ground_truth, rfsgpu_error_log_create / _reset / _read, rfsgpu_step_error_async, rfsgpu_step_error
+ * and rfsgpu_get_map_estimate work on the handle with the signatures, records, log semantics and error codes of the [metric] section.
+ * A record of filter b then means:
+ *   - its particle set is the global slots [b * max_per_filter, b * max_per_filter + n_b), n_b being the filter's live count AS THE
+ *     DEVICE HOLDS IT AT THE KERNEL'S POINT OF THE STREAM (n_per_filter before the first cycle), not a host copy: so
+ *     rfsgpu_batch_propagate_async -> rfsgpu_batch_fastslam_mh_cycle_async -> rfsgpu_step_error_async queue back to back, and
+ *     rfsgpu_step_error_async waits for nothing (cycles in flight stay in flight);
+ *   - slots at or beyond n_b are never read -- weight, pose, count or mixture: after a shrink they hold what a larger set left;
+ *   - best_slot is global: the first live slot holding the maximum weight, slot 0 of the block when no live weight is > 0;
+ *   - weight_sum and the four pose means go over the live slots in the kernel's fixed tree (lane l adds the slots l, l + 64, ... < n_b
+ *     in ascending order, then the wave's butterfly): the bits of a full block of n_b particles holding the same values;
+ *   - a Gaussian's weight is a log-odds w, as on a FastSLAM batch: every "weight" of the record and of rfsgpu_get_map_estimate is
+ *     1 - 1 / (1 + exp(w));
+ *   - a filter that overflowed in the last cycle was left as before that cycle's update and is evaluated on that state with status 0;
+ *     the pending RFSGPU_ERR_CAPACITY is reported by the next synchronising call as always (once, naming the lowest filter), and
+ *     rfsgpu_step_error_async itself still enqueues.  A filter with n_z == 0 in the last cycle, or one that was just resampled (all
+ *     weights 1: slot 0 of the block is the best), is evaluated like any other.
+ * Everything else that is refused on such a batch stays refused (rfsgpu_batch_weight_sums, the resampling calls). */
+int rfsgpu_batch_mh_serve_metrics(rfsgpu_filter *f, int on);
 #ifdef RFSGPU_ENABLE_BENCH_API
 /* [test] 1 once a step of this handle (batch or not) has queued Murty-200 partitions, else 0.  Synchronising. */
 int rfsgpu_murty_seen(rfsgpu_filter *f);
@@ -837,7 +861,11 @@ int rfsgpu_murty_seen(rfsgpu_filter *f);
  * A batch of FastSLAM filters (rfsgpu_batch_fastslam_cycle_async) is served: a Gaussian's weight is a log-odds w there, and wherever
  * this section says "weight" of a Gaussian (n_est, cardinality, rfsgpu_get_map_estimate's w) it means 1 - 1 / (1 + exp(w)), the
  * number the reference's fastslam2dSim logs (src/fastslam2dSim.cpp:628) and analysis2dSim thresholds.  Lifting the refusal for an
- * ordinary FastSLAM handle is a later change. */
+ * ordinary FastSLAM handle is a later change.
+ * A batch of multi-hypothesis FastSLAM filters (rfsgpu_create_batch_mh) returns RFSGPU_ERR_UNSUPPORTED from every call of this section
+ * until rfsgpu_batch_mh_serve_metrics(f, 1); from then on it is served as a FastSLAM batch is (log-odds weights), with "the filter's
+ * block" read as its LIVE slots -- the first n_b of its max_per_filter, n_b taken from the device where the kernel runs: see
+ * rfsgpu_batch_mh_serve_metrics for what a record means there. */
 #define RFSGPU_MAX_METRIC_SET 512   /* hard limit of either set of one comparison (estimates, observable ground truth) */
 /* One record per filter and call; every field is 8 bytes wide.  status: 0 = ok; 1 = n_est or n_truth exceeds
  * RFSGPU_MAX_METRIC_SET; 2 = no finite cost met (non-finite coordinates).  With status != 0 ospa, cola, e_dist, e_card are NaN

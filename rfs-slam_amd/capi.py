@@ -139,7 +139,7 @@ ABI_SYMBOLS = [
     "create_batch", "n_filters", "batch_configure", "batch_cycle_async", "batch_weight_sums", "batch_resample_apply", "batch_resample_occured", "murty_seen",
     "batch_set_motion_odometry", "batch_set_resampling", "batch_propagate_async", "batch_resample_async", "batch_last_resample", "batch_resample_counts", "batch_get_pose_covs",
     "batch_set_fastslam_config", "batch_fastslam_cycle_async",
-    "create_batch_mh", "batch_fastslam_mh_cycle_async", "batch_fastslam_last_cycle", "batch_live_counts",
+    "create_batch_mh", "batch_fastslam_mh_cycle_async", "batch_fastslam_last_cycle", "batch_live_counts", "batch_mh_serve_metrics",
     "set_ground_truth", "error_log_create", "error_log_reset", "step_error_async", "error_log_read", "step_error", "get_map_estimate",
 ]
 
@@ -922,6 +922,12 @@ class CBatchMH(CBatch):
         out = np.zeros(self.n_filters, dtype=np.int32)
         self._call("batch_live_counts", self._ptr(out))
         return out
+
+    def serve_metrics(self, on=True):
+        """rfsgpu_batch_mh_serve_metrics (synchronising): from now on the [metric] calls (set_ground_truth, error_log_*, step_error_async,
+        step_error, get_map_estimate) serve this batch, each filter's record over its live slots as the device counts them where the
+        kernel runs; on=False: they refuse again."""
+        self._call("batch_mh_serve_metrics", C.c_int(1 if on else 0))
 
 
 def mat_perm(lib, prefix, A, device_id=0):

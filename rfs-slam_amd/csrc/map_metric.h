@@ -30,6 +30,13 @@
 // A filter whose n_est or n_truth exceeds RFSGPU_MAX_METRIC_SET gets status 1 and NaN metrics (its n_est / n_truth / cardinality /
 // pose fields are still filled); nothing beyond entry 511 of any LDS array is ever addressed.  Status 2: the search met no finite
 // reduced cost (non-finite coordinates): NaN metrics as well.
+//
+// live: nothing, or a MetricLive for a batch of multi-hypothesis FastSLAM filters (rfsgpu_create_batch_mh), where filter b owns A.nPer
+// slots (the stride) of which only the first n_b are live and n_b is a word of the filter's cycle state on the device
+// (fastslam_cycle.h).  The wave reads that word once, as it is at the kernel's point of the stream (a scalar read), clamps it to
+// [0, stride], and steps 1 and 2 run to it: no slot at or beyond the count is read (weight, pose, count or slab -- they hold whatever
+// a larger set left there).  Lane l adds the slots l, l + 64, ... < n_b, so a filter of n_b live slots sums in the tree of a full
+// block of n_b.  Steps 3 and 4 are the same code.
 #pragma once
 
 #define METRIC_MAXS RFSGPU_MAX_METRIC_SET
@@ -47,22 +54,35 @@ struct MetricArg {
   int logOdds;             // a FastSLAM batch: a Gaussian's weight is the log-odds of existence; the estimate's weight is 1 - 1 / (1 + exp(w))
 };
 
+struct MetricLive {
+  const int *words;        // filter 0's cycle words; filter b's start wordStride ints further (as MhBatchArg, fastslam.h)
+  int wordStride;
+  int word;                // which word is the live count (FSC_N)
+};
+
 // (wave_min_f64: hungarian_wave.h -- DPP moves, the result in every lane)
 __device__ __forceinline__ double metric_pow(double x, double p) { return p == 1.0 ? x : (p == 2.0 ? x * x : pow(x, p)); }
 
-__global__ __launch_bounds__(64) void map_metric_kernel(Buffers B, int cur, MetricArg A) {
+template <typename... TLive>
+__global__ __launch_bounds__(64) void map_metric_kernel(Buffers B, int cur, MetricArg A, TLive... live) {
   __shared__ double sEx[METRIC_MAXS], sEy[METRIC_MAXS], sGx[METRIC_MAXS], sGy[METRIC_MAXS];
   __shared__ double sU[METRIC_MAXS], sV[METRIC_MAXS], sSpc[METRIC_MAXS];
   __shared__ int sPath[METRIC_MAXS], sRow4Col[METRIC_MAXS], sCol4Row[METRIC_MAXS];
   const int b = blockIdx.x, lane = threadIdx.x;
   const int nPer = A.nPer, lo = b * nPer;
+  int nLive = nPer;
+  if constexpr (sizeof...(TLive) == 1) {   // a MetricLive: the filter's count lives on the device (wave-uniform: one scalar read)
+    const MetricLive &L = pack_first(live...);
+    nLive = __builtin_amdgcn_readfirstlane(L.words[(size_t)b * L.wordStride + L.word]);
+    nLive = nLive < 0 ? 0 : (nLive > nPer ? nPer : nLive);
+  }
   const double qnan = __longlong_as_double(0x7ff8000000000000ll);
   const double t = A.in[4 * b], rx = A.in[4 * b + 1], ry = A.in[4 * b + 2], rth = A.in[4 * b + 3];
 
   // ---- 1 + 2: highest-weight particle, weight sum, pose error -------------------------------------------------------------------
   double bw = 0.0, sw = 0.0, sx = 0.0, sy = 0.0, sth = 0.0, sd = 0.0;
   int bi = -1;
-  for (int s = lane; s < nPer; s += 64) {
+  for (int s = lane; s < nLive; s += 64) {
     const double w = B.weight[lo + s];
     if (w > bw) { bw = w; bi = s; }
     sw += w;

@@ -219,6 +219,7 @@ struct rfsgpu_filter {
   bool mhbPending = false;                     // cycles are enqueued: the counts, ids and flags on the host are behind the device
   bool mhbHave = false;                        // a cycle has run
   std::vector<int> mhbLastNZ;                  // [nF] the last enqueued cycle's measurement counts
+  bool mhbMetrics = false;                     // rfsgpu_batch_mh_serve_metrics: the [metric] calls serve this batch (the kernel's live-count form)
   // [metric] per-step map / pose error (map_metric.h): ground truth per filter, the device-side log, one row for the synchronous calls
   double *dGtXY = nullptr, *dGtSeen = nullptr;   // [nF][RFSGPU_MAX_METRIC_SET][2], [nF][RFSGPU_MAX_METRIC_SET] (allocated by the first rfsgpu_set_ground_truth)
   int *dGtN = nullptr;                           // [nF]
@@ -3850,12 +3851,14 @@ int rfsgpu_batch_resample_counts(rfsgpu_filter *f, long long *out) {
 
 // ---- [metric] per-step map error and pose error (map_metric.h) ------------------------------------------------------------------------
 static int metric_check(rfsgpu_filter *f, const char *what) {
-  const char *why = f->D != 2 ? "the Victoria Park model" : (f->fastSlamHandle ? "a FastSLAM handle" : (f->groupShard ? "a shard of an rfsgpu_group" : (f->mhBatch ? "a batch of multi-hypothesis FastSLAM filters (rfsgpu_create_batch_mh: the step-error kernel assumes that every filter fills its block)" : nullptr)));
+  const char *why = f->D != 2 ? "the Victoria Park model" : (f->fastSlamHandle ? "a FastSLAM handle" : (f->groupShard ? "a shard of an rfsgpu_group" : ((f->mhBatch && !f->mhbMetrics) ? "a batch of multi-hypothesis FastSLAM filters (rfsgpu_create_batch_mh: the step-error kernel assumes that every filter fills its block; rfsgpu_batch_mh_serve_metrics switches its live-count form on)" : nullptr)));
   if (!why) return RFSGPU_OK;
   f->err = std::string(what) + ": the device-side map / pose error serves ordinary 2-D RB-PHD handles and filter batches (RB-PHD or FastSLAM) only, not " + why;
   return RFSGPU_ERR_UNSUPPORTED;
 }
 static inline int metric_nf(const rfsgpu_filter *f) { return f->batch ? f->nF : 1; }
+// (FastSLAM filters, single- or multi-hypothesis: a Gaussian's weight is the log-odds of existence)
+static inline bool metric_log_odds(const rfsgpu_filter *f) { return f->bKind == 2 || f->bKind == 3; }
 // One launch into `row` ([nF] records): the call's t / gt_pose go into a slot of the pinned staging ring, which the kernel reads in place.
 static int metric_launch(rfsgpu_filter *f, const double *t, const double *gt_pose, double w_threshold, double cutoff, double order, struct rfsgpu_step_error *row) {
   const int nF = metric_nf(f);
@@ -3867,8 +3870,14 @@ static int metric_launch(rfsgpu_filter *f, const double *t, const double *gt_pos
     h[4 * b] = t ? t[b] : 0.0;
     for (int q = 0; q < 3; q++) h[4 * b + 1 + q] = gt_pose ? gt_pose[3 * b + q] : 0.0;
   }
-  MetricArg A{h, f->dGtXY, f->dGtSeen, f->dGtN, row, w_threshold, cutoff, order, f->batch ? f->nPer : f->N, gt_pose ? 1 : 0, f->holes ? 1 : 0, f->bKind == 2 ? 1 : 0};
-  map_metric_kernel<<<nF, 64, 0, f->stream>>>(f->B, f->cur, A);
+  MetricArg A{h, f->dGtXY, f->dGtSeen, f->dGtN, row, w_threshold, cutoff, order, f->batch ? f->nPer : f->N, gt_pose ? 1 : 0, f->holes ? 1 : 0, metric_log_odds(f) ? 1 : 0};
+  if (f->mhBatch) {     // every filter's count is a word of its cycle block, read by the kernel where it runs: nothing waits for it
+    FsCycleState S0;
+    mhb_view(f, f->mhbBlock, 0, S0);
+    map_metric_kernel<<<nF, 64, 0, f->stream>>>(f->B, f->cur, A, MetricLive{S0.w, FSC_WORDS, FSC_N});
+  } else {
+    map_metric_kernel<<<nF, 64, 0, f->stream>>>(f->B, f->cur, A);
+  }
   HIPCHK(hipGetLastError());
   HIPCHK(hipEventRecord(f->evStage[k], f->stream));
   return RFSGPU_OK;
@@ -3883,6 +3892,15 @@ static int metric_row(rfsgpu_filter *f) {
   return RFSGPU_OK;
 }
 
+// The switch of a multi-hypothesis batch: off at creation, so the refusals it was published with stand until a caller asks.
+int rfsgpu_batch_mh_serve_metrics(rfsgpu_filter *f, int on) {
+  CHECK_HANDLE(f);
+  if (!f->mhBatch) return fail(f, RFSGPU_ERR_UNSUPPORTED, "batch_mh_serve_metrics: not a batch of multi-hypothesis FastSLAM filters (rfsgpu_create_batch_mh)");
+  hipSetDevice(f->device);
+  HIPCHK(hipStreamSynchronize(f->stream));
+  f->mhbMetrics = on != 0;
+  return RFSGPU_OK;
+}
 int rfsgpu_set_ground_truth(rfsgpu_filter *f, int filter, const double *xy, const double *first_seen, int n) {
   CHECK_HANDLE(f);
   int rc = metric_check(f, "set_ground_truth");
@@ -3934,7 +3952,10 @@ int rfsgpu_error_log_reset(rfsgpu_filter *f) {
   return RFSGPU_OK;
 }
 int rfsgpu_step_error_async(rfsgpu_filter *f, const double *t, const double *gt_pose, double w_threshold, double cutoff, double order) {
-  CHECK_HANDLE(f);
+  if (!f) return RFSGPU_ERR_INVALID;
+  if (!(f->mhBatch && f->mhbMetrics)) {    // (a served multi-hypothesis batch: the kernel reads the counts on the device, so cycles in
+    CHECK_HANDLE(f);                       //  flight stay in flight and a pending overflow is the next synchronising call's to report)
+  }
   int rc = metric_check(f, "step_error_async");
   if (rc != RFSGPU_OK) return rc;
   if ((rc = metric_args(f, "step_error_async", t, cutoff, order)) != RFSGPU_OK) return rc;
@@ -3988,7 +4009,7 @@ int rfsgpu_get_map_estimate(rfsgpu_filter *f, int filter, double w_threshold, in
   int k = 0;
   for (int m = 0; m < cnt; m++) {
     double wm = pl[m];
-    if (f->bKind == 2) wm = 1 - 1 / (1 + exp(wm));     // a FastSLAM batch: the existence probability of the log-odds (fastslam2dSim.cpp:628)
+    if (metric_log_odds(f)) wm = 1 - 1 / (1 + exp(wm));     // a FastSLAM batch: the existence probability of the log-odds (fastslam2dSim.cpp:628)
     if ((f->holes && wm < 0) || !(wm >= w_threshold)) continue;
     if (k < max_n) {
       if (w) w[k] = wm;

@@ -543,9 +543,10 @@ class MHFastSLAMBatch(capi.CBatchMH):
     live particle count on the device.  Filter b owns max_per_filter global slots (block(b)), of which the first live_counts()[b] are
     live; each filter equals a FastSLAM(n_per_filter, max_hypotheses=..., device_cycle=True) handle with max_particles =
     max_per_filter given the same inputs.  The model / Kalman filter / landmark noise of a filter come through configure(b, None,
-    R=..., ...), the FastSLAM configuration through configure_fastslam(b, fs_cfg), the N_eff thresholds through set_resampling."""
+    R=..., ...), the FastSLAM configuration through configure_fastslam(b, fs_cfg), the N_eff thresholds through set_resampling.
+    metrics=True switches the device-side map / pose error on at construction (serve_metrics): the [metric] calls refuse otherwise."""
 
-    def __init__(self, n_filters, n_per_filter, max_per_filter=None, device_id=0, gm_capacity=512, max_hypotheses=3):
+    def __init__(self, n_filters, n_per_filter, max_per_filter=None, device_id=0, gm_capacity=512, max_hypotheses=3, metrics=False):
         # default: nParticlesMax x max_hypotheses slots (a set at nParticlesMax = 3 n is not forced back, and the next update can multiply
         # it once more before any resampling), at most the 2048 one resampling workgroup holds
         m = min(2048, 3 * int(n_per_filter) * max(1, int(max_hypotheses))) if max_per_filter is None else int(max_per_filter)
@@ -553,6 +554,8 @@ class MHFastSLAMBatch(capi.CBatchMH):
         self.fs_configs = [self.default_fastslam_config() for _ in range(n_filters)]
         for c in self.fs_configs:
             c.nParticlesMax = 3 * int(n_per_filter)          # FastSLAM.hpp:250
+        if metrics:
+            self.serve_metrics(True)
 
     def configure(self, b, cfg=None, **model):
         """Filter b's model / Kalman filter / landmark noise (see CBatch.batch_configure)."""

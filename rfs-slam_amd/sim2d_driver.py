@@ -505,6 +505,104 @@ class Sim2dBatchRun:
         return self
 
 
+class Sim2dMHBatchRun:
+    """The simulator loop for multi-hypothesis FastSLAM filters in one of three forms: an MHFastSLAMBatch with its host loop (the host
+    reads the counts and poses back, propagates the live slots and passes them with the cycle) or its device loop (propagate_async +
+    cycle, nothing read back), or handles on rfsgpu_fastslam_cycle_async stepped in turn.  Every filter's draws are pre-drawn from its
+    seed, so the device loop waits for nothing.  `n`: the particles a filter starts with (None: the target's own count).
+
+    track_errors=True (a batch target only; the contract of Sim2dBatchRun): the batch's metric service is switched on
+    (serve_metrics), each filter's ground truth is uploaded with its first_seen_times, the log is sized to the run, every step ends
+    with one step_error_async(t = k * dt, gt_pose) -- the kernel reads each filter's live count on the device, so the device loop
+    still reads nothing back -- and errors() is the one read at the end."""
+
+    def __init__(self, target, datas, Ps, seeds, n=None, device_loop=False, track_errors=False):
+        self.datas, self.Ps, self.nF = list(datas), list(Ps), len(datas)
+        self.batch = target if isinstance(target, capi.CBatchMH) else None
+        self.handles = None if self.batch is not None else list(target)
+        self.n = n = int(n if n is not None else (self.batch.n_per_filter if self.batch is not None else self.handles[0].n))
+        self.device_loop = bool(device_loop)
+        self.track_errors = bool(track_errors)
+        assert self.batch is not None or not (self.device_loop or self.track_errors), "the device loop and the error tracking need an MHFastSLAMBatch"
+        K = int(min(d["K"] for d in datas))
+        self.rngs = [np.random.default_rng(s) for s in seeds]
+        self.u01 = np.ascontiguousarray(np.stack([np.random.default_rng(10_000 + s).random(K) for s in seeds], axis=1))      # [K, nF]
+        self.Q = [np.diag([P["vardx"], P["vardy"], P["vardz"]]) * P["p_noise_inflation"] * P["dt"] ** 2 for P in Ps]
+        for b, P in enumerate(Ps):
+            if self.batch is not None:
+                c = configure_fastslam_batch_filter(self.batch, b, P)
+                c.nParticlesMax = 3 * n
+                self.batch.configure_fastslam(b, c)
+                self.batch.set_resampling(b, P["eff_n"], P["eff_n"] / n)
+                self.batch.set_motion_odometry(b, np.diag(self.Q[b]), seeds[b])
+            else:
+                h = self.handles[b]
+                h.fs_config = configure_fastslam(h, P)
+                h.fs_config.nParticlesMax = 3 * n
+                h.setEffectiveParticleCountThreshold(P["eff_n"])
+        self._u = np.ascontiguousarray(np.stack([d["odom"][:K] for d in datas], axis=1))
+        self._gt = np.ascontiguousarray(np.stack([d["gt"][:K] for d in datas], axis=1))
+        self._z = np.zeros((K, self.nF, capi.MAX_Z, 2))
+        self._nz = np.zeros((K, self.nF), dtype=np.int32)
+        for b, d in enumerate(datas):
+            for k in range(K):
+                Z = d["Z"][k] if k < len(d["Z"]) else np.zeros((0, 2))
+                self._nz[k, b] = len(Z)
+                self._z[k, b, :len(Z)] = Z
+        self._t = np.array([[k * P["dt"] for P in Ps] for k in range(K)])
+        self._pin_all = np.ones(self.nF, dtype=np.uint8)
+        if self.track_errors:
+            self.batch.serve_metrics(True)
+            for b, (d, P) in enumerate(zip(self.datas, self.Ps)):
+                self.batch.set_ground_truth(d["landmarks"], first_seen_times(d, P), filter=b)
+            self.batch.error_log_create(K)
+
+    def _moved(self, b, x, k):
+        """ParticleFilter::propagate of filter b's live particles on the host (the ground truth for the first 100 steps, :590-593)."""
+        if k <= 100:
+            return np.tile(self._gt[k, b], (x.shape[0], 1)), np.zeros(9)
+        noise = self.rngs[b].standard_normal(x.shape) * np.sqrt(np.diag(self.Q[b]))
+        return odometry_step(x, self._u[k, b]) + noise, self.Q[b].ravel()
+
+    def step(self, k):
+        bt = self.batch
+        if self.device_loop:
+            bt.propagate_async(self._u[k], k, pin=self._pin_all if k <= 100 else None, pin_pose=self._gt[k] if k <= 100 else None)
+            bt.batch_fastslam_mh_cycle_async_packed(True, self._z[k], self._nz[k], self.u01[k])
+        elif bt is not None:
+            counts = bt.live_counts()
+            x = bt.get_poses()
+            cov = np.zeros((bt.n, 9))
+            for b in range(self.nF):
+                blk = bt.block(b, counts[b])
+                x[blk], cov[blk] = self._moved(b, x[blk], k)
+            bt.batch_fastslam_mh_cycle_async_packed(True, self._z[k], self._nz[k], self.u01[k], poses=x, pose_cov=cov)
+        else:
+            for b, h in enumerate(self.handles):
+                x, c = self._moved(b, h.get_poses(), k)
+                h.set_poses(x, np.tile(c, (x.shape[0], 1)))
+                h.cycle_async(self._z[k, b, :self._nz[k, b]], float(self.u01[k, b]), predict=True)
+        if self.track_errors:
+            bt.step_error_async(self._t[k], self._gt[k], ERROR_W_THRESHOLD, ERROR_CUTOFF, ERROR_ORDER)
+
+    def errors(self):
+        """The rows logged so far as one structured array [steps, n_filters] (capi.STEP_ERROR_DTYPE): the one read (it also waits for
+        the queued work)."""
+        assert self.track_errors, "Sim2dMHBatchRun(..., track_errors=True)"
+        return self.batch.error_log_read()
+
+    def run(self, k_from=1, k_to=None, on_step=None):
+        for k in range(k_from, int(k_to or min(d["K"] for d in self.datas))):
+            self.step(k)
+            if on_step is not None:
+                on_step(k, self)
+        return self
+
+    def synchronize(self):
+        for f in ([self.batch] if self.batch is not None else self.handles):
+            f.synchronize()
+
+
 def map_error(f, i, landmarks, w_min=0.5, cutoff=0.5):
     """Matched landmarks / mean error of particle i's strong Gaussians against the ground truth (greedy nearest, as the C++ driver's summary)."""
     w, _, mean, _ = f.export_gm(i)

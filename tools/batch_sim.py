@@ -24,7 +24,16 @@ resample per handle), host loop / device loop, --errors.  Every line then carrie
 --mhfastslam: the third sweep of the reference's scripts/batchSim (batchSim_mhfastslam.bash): multi-hypothesis FastSLAM filters with the
 filter values of tests/golden/mhfastslam2dSim_c1.xml (200 particles, 3 hypotheses, log-likelihood window 3.0) as an MHFastSLAMBatch
 (rfsgpu_batch_fastslam_mh_cycle_async; --max-per-filter slots per filter, default nParticlesMax x hypotheses = 1800) against the same filters as handles on
-rfsgpu_fastslam_cycle_async stepped in turn.  --both-loops / --device-loop / --reps as above; every line carries "filter": "mhfastslam".
+rfsgpu_fastslam_cycle_async stepped in turn (sim2d_driver.Sim2dMHBatchRun).  --both-loops / --device-loop / --reps as above; every line
+carries "filter": "mhfastslam".  With --errors the sweep is the tracking one instead: per batch size and loop kind filter-steps/s with
+tracking off, with device tracking (the batch's metric service on, one rfsgpu_step_error_async per step whose kernel reads every filter's
+live count on the device, the log read inside the span) and with the host route (per step and filter live_counts + get_weights of the live
+slots + export_gm of the best one + tools/analysis2d_sim.py::cola on 1 - 1 / (1 + exp(w))); then per filter the final and mean COLA and
+pose error, the curves in --json.
+
+--results FILE (with --errors, any of the three kinds): one line per filter of the largest batch, "Pd  c  posError  mapError" -- the final
+row's pose_ed and cola, the two columns the reference's batchSim scripts cut out of poseEstError.dat (field 5) and landmarkEstError.dat
+(field 4).
 """
 import argparse
 import json
@@ -100,10 +109,7 @@ def timed_host_route(run, steps, datas, firsts, Ps, a2d, fastslam=False):
 
 
 def errors_sweep(pkg, a, sizes, Ps, datas, seeds):
-    import importlib.util
-    spec = importlib.util.spec_from_file_location("analysis2d_sim", os.path.join(ROOT, "tools", "analysis2d_sim.py"))
-    a2d = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(a2d)
+    a2d = load_a2d()
     sim = pkg.sim2d_driver
     firsts = [sim.first_seen_times(d, P) for d, P in zip(datas, Ps)]
     rows = []
@@ -123,19 +129,108 @@ def errors_sweep(pkg, a, sizes, Ps, datas, seeds):
                 batch.synchronize()
             row["filter_steps_per_s_tracking_" + name] = B * a.steps / dt
             if name == "device":
-                row["filters"] = [dict(filter=b, Pd=Ps[b]["Pd"], clutter=Ps[b]["clutter"], seed=1 + b, final_cola=float(log["cola"][-1, b]),
-                                       mean_cola=float(log["cola"][:, b].mean()), final_pose_error=float(log["pose_ed"][-1, b]),
-                                       mean_pose_error=float(log["pose_ed"][:, b].mean()), n_est=int(log["n_est"][-1, b]), n_truth=int(log["n_truth"][-1, b]),
-                                       curve_t=log["t"][:, b].tolist(), curve_cola=log["cola"][:, b].tolist(), curve_pose_error=log["pose_ed"][:, b].tolist())
-                                  for b in range(B)]
+                row["filters"] = filter_rows(log, Ps, B)
             batch.close()
         row["device_over_off"] = row["filter_steps_per_s_tracking_device"] / row["filter_steps_per_s_tracking_off"]
         row["host_over_off"] = row["filter_steps_per_s_tracking_host"] / row["filter_steps_per_s_tracking_off"]
         rows.append(row)
         print(json.dumps({k: v for k, v in row.items() if k != "filters"}), flush=True)
-    for r in rows[-1]["filters"]:
+    print_filters(rows[-1]["filters"])
+    write_results(a.results, rows[-1]["filters"])
+    return rows
+
+
+def filter_rows(log, Ps, B):
+    """Per filter what an --errors sweep reports of a log [steps, B]: final and mean COLA / pose error, the curves."""
+    return [dict(filter=b, Pd=Ps[b]["Pd"], clutter=Ps[b]["clutter"], seed=1 + b, final_cola=float(log["cola"][-1, b]),
+                 mean_cola=float(log["cola"][:, b].mean()), final_pose_error=float(log["pose_ed"][-1, b]),
+                 mean_pose_error=float(log["pose_ed"][:, b].mean()), n_est=int(log["n_est"][-1, b]), n_truth=int(log["n_truth"][-1, b]),
+                 curve_t=log["t"][:, b].tolist(), curve_cola=log["cola"][:, b].tolist(), curve_pose_error=log["pose_ed"][:, b].tolist())
+            for b in range(B)]
+
+
+def print_filters(filters):
+    for r in filters:
         print("filter %3d  Pd %.2f  clutter %.0e  seed %3d  COLA final %6.2f mean %6.2f (est %2d / truth %2d)  pose error final %.4f mean %.4f"
               % (r["filter"], r["Pd"], r["clutter"], r["seed"], r["final_cola"], r["mean_cola"], r["n_est"], r["n_truth"], r["final_pose_error"], r["mean_pose_error"]))
+
+
+def write_results(path, filters):
+    """--results: one line per filter, Pd  c  posError  mapError (the final row's pose_ed and cola), as the reference's batchSim scripts end."""
+    if not path:
+        return
+    os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
+    with open(path, "w") as fh:
+        for r in filters:
+            fh.write("%g  %g  %.9g  %.9g\n" % (r["Pd"], r["clutter"], r["final_pose_error"], r["final_cola"]))
+
+
+def load_a2d():
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("analysis2d_sim", os.path.join(ROOT, "tools", "analysis2d_sim.py"))
+    a2d = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(a2d)
+    return a2d
+
+
+def mh_host_route_errors(batch, datas, firsts, Ps, k, a2d):
+    """The only route to an error curve of an MH batch before the metric service: per step the counts, per filter the weights of its live
+    slots, the best one's mixture, scipy."""
+    counts = batch.live_counts()
+    wall = batch.get_weights()                    # (one read per step for all filters: the cheapest form of this route)
+    out = []
+    for b in range(batch.n_filters):
+        w = wall[batch.block(b, counts[b])]
+        i = b * batch.max_per_filter + int(np.argmax(w))
+        gw, _, mean, _ = batch.export_gm(i)
+        gw = 1 - 1 / (1 + np.exp(gw))             # log-odds -> existence probability (fastslam2dSim.cpp:628)
+        seen = datas[b]["landmarks"][firsts[b] <= k * Ps[b]["dt"]]
+        out.append(a2d.cola(mean[gw >= a2d.W_THRESHOLD], seen))
+    return out
+
+
+def mh_errors_sweep(pkg, a, sizes, n, stride, P0, Ps, datas, seeds, loops):
+    """--mhfastslam --errors: per batch size and loop kind, filter-steps/s with tracking off / device tracking (log read in the span) /
+    the host route, medians of --reps repetitions; the largest batch's per-filter figures from its last device-tracked run."""
+    sim = pkg.sim2d_driver
+    a2d = load_a2d()
+    firsts = [sim.first_seen_times(d, P) for d, P in zip(datas, Ps)]
+    rows = []
+    for B in sizes:
+        row = dict(B=B, particles=n, max_per_filter=stride, steps=a.steps, filter="mhfastslam", hypotheses=P0["max_hypotheses"], loop="+".join(loops))
+        for loop in loops:
+            for name in ("off", "device", "host"):
+                figs = []
+                for _ in range(max(1, a.reps)):
+                    bt = pkg.MHFastSLAMBatch(B, n, stride, gm_capacity=a.capacity)
+                    run = sim.Sim2dMHBatchRun(bt, datas[:B], Ps[:B], seeds[:B], n, device_loop=(loop == "device"), track_errors=(name == "device"))
+                    run.step(1)
+                    run.synchronize()
+                    t0 = time.perf_counter()
+                    for k in range(2, a.steps + 2):
+                        run.step(k)
+                        if name == "host":
+                            mh_host_route_errors(bt, datas, firsts, Ps, k, a2d)
+                    if name == "device":
+                        log = run.errors()                  # the one read (it also waits for the queued work)
+                    else:
+                        run.synchronize()
+                    figs.append(B * a.steps / (time.perf_counter() - t0))
+                    bt.close()
+                key = "%s_loop_filter_steps_per_s_tracking_%s" % (loop, name)
+                row[key], row[key + "_reps"] = float(np.median(figs)), figs
+                if name == "device":
+                    row["filters"] = filter_rows(log, Ps, B)
+            row[loop + "_loop_device_over_off"] = row[loop + "_loop_filter_steps_per_s_tracking_device"] / row[loop + "_loop_filter_steps_per_s_tracking_off"]
+            row[loop + "_loop_device_over_host_route"] = row[loop + "_loop_filter_steps_per_s_tracking_device"] / row[loop + "_loop_filter_steps_per_s_tracking_host"]
+        rows.append(row)
+        print(json.dumps({k: v for k, v in row.items() if k != "filters"}), flush=True)
+    print_filters(rows[-1]["filters"])
+    write_results(a.results, rows[-1]["filters"])
+    if a.json:
+        os.makedirs(os.path.dirname(a.json) or ".", exist_ok=True)
+        with open(a.json, "w") as fh:
+            json.dump(rows, fh, indent=1)
     return rows
 
 
@@ -148,76 +243,6 @@ def mh_params(sim):
              min_log_likelihood=float(g("filter/weighting/minLogMeasurementLikelihood")), existence_prune_thr=float(g("filter/prune/threshold")),
              eff_n=float(g("filter/resampling/effNParticle")), min_updates=int(g("filter/resampling/minTimesteps")))
     return P, int(next(t.iter("nParticles")).text)
-
-
-class MhRun:
-    """The simulator loop for multi-hypothesis FastSLAM filters in one of three forms: an MHFastSLAMBatch with its host loop (the host
-    reads the counts and poses back, propagates the live slots and passes them with the cycle) or its device loop (propagate_async +
-    cycle, nothing read back), or handles on rfsgpu_fastslam_cycle_async stepped in turn.  Every filter's draws are pre-drawn from its
-    seed, so the device loop waits for nothing."""
-
-    def __init__(self, pkg, target, datas, Ps, seeds, n, device_loop=False):
-        sim = pkg.sim2d_driver
-        self.sim, self.datas, self.Ps, self.n, self.nF = sim, datas, Ps, n, len(datas)
-        self.batch = target if isinstance(target, pkg.capi.CBatchMH) else None
-        self.handles = None if self.batch is not None else list(target)
-        self.device_loop = bool(device_loop)
-        K = int(min(d["K"] for d in datas))
-        self.rngs = [np.random.default_rng(s) for s in seeds]
-        self.u01 = np.ascontiguousarray(np.stack([np.random.default_rng(10_000 + s).random(K) for s in seeds], axis=1))      # [K, nF]
-        self.Q = [np.diag([P["vardx"], P["vardy"], P["vardz"]]) * P["p_noise_inflation"] * P["dt"] ** 2 for P in Ps]
-        for b, P in enumerate(Ps):
-            if self.batch is not None:
-                c = sim.configure_fastslam_batch_filter(self.batch, b, P)
-                c.nParticlesMax = 3 * n
-                self.batch.configure_fastslam(b, c)
-                self.batch.set_resampling(b, P["eff_n"], P["eff_n"] / n)
-                self.batch.set_motion_odometry(b, np.diag(self.Q[b]), seeds[b])
-            else:
-                h = self.handles[b]
-                h.fs_config = sim.configure_fastslam(h, P)
-                h.fs_config.nParticlesMax = 3 * n
-                h.setEffectiveParticleCountThreshold(P["eff_n"])
-        self._u = np.ascontiguousarray(np.stack([d["odom"][:K] for d in datas], axis=1))
-        self._gt = np.ascontiguousarray(np.stack([d["gt"][:K] for d in datas], axis=1))
-        self._z = np.zeros((K, self.nF, pkg.capi.MAX_Z, 2))
-        self._nz = np.zeros((K, self.nF), dtype=np.int32)
-        for b, d in enumerate(datas):
-            for k in range(K):
-                Z = d["Z"][k] if k < len(d["Z"]) else np.zeros((0, 2))
-                self._nz[k, b] = len(Z)
-                self._z[k, b, :len(Z)] = Z
-        self._pin_all = np.ones(self.nF, dtype=np.uint8)
-
-    def _moved(self, b, x, k):
-        """ParticleFilter::propagate of filter b's live particles on the host (the ground truth for the first 100 steps, :590-593)."""
-        if k <= 100:
-            return np.tile(self._gt[k, b], (x.shape[0], 1)), np.zeros(9)
-        noise = self.rngs[b].standard_normal(x.shape) * np.sqrt(np.diag(self.Q[b]))
-        return self.sim.odometry_step(x, self._u[k, b]) + noise, self.Q[b].ravel()
-
-    def step(self, k):
-        bt = self.batch
-        if self.device_loop:
-            bt.propagate_async(self._u[k], k, pin=self._pin_all if k <= 100 else None, pin_pose=self._gt[k] if k <= 100 else None)
-            bt.batch_fastslam_mh_cycle_async_packed(True, self._z[k], self._nz[k], self.u01[k])
-        elif bt is not None:
-            counts = bt.live_counts()
-            x = bt.get_poses()
-            cov = np.zeros((bt.n, 9))
-            for b in range(self.nF):
-                blk = bt.block(b, counts[b])
-                x[blk], cov[blk] = self._moved(b, x[blk], k)
-            bt.batch_fastslam_mh_cycle_async_packed(True, self._z[k], self._nz[k], self.u01[k], poses=x, pose_cov=cov)
-        else:
-            for b, h in enumerate(self.handles):
-                x, c = self._moved(b, h.get_poses(), k)
-                h.set_poses(x, np.tile(c, (x.shape[0], 1)))
-                h.cycle_async(self._z[k, b, :self._nz[k, b]], float(self.u01[k, b]), predict=True)
-
-    def synchronize(self):
-        for f in ([self.batch] if self.batch is not None else self.handles):
-            f.synchronize()
 
 
 def mh_handle(pkg, n, max_per_filter, capacity):
@@ -238,6 +263,8 @@ def mh_sweep(pkg, a, sizes):
     datas = [sim.generate(P, traj_seed=1 + b, kmax=a.steps + 2) for b, P in enumerate(Ps)]
     seeds = [100 + b for b in range(max(sizes))]
     loops = ["host", "device"] if a.both_loops else (["device"] if a.device_loop else ["host"])
+    if a.errors:
+        return mh_errors_sweep(pkg, a, sizes, n, stride, P0, Ps, datas, seeds, loops)
 
     def timed_run(make):
         figs = []
@@ -260,7 +287,7 @@ def mh_sweep(pkg, a, sizes):
         for loop in loops:
             def make(loop=loop):
                 bt = pkg.MHFastSLAMBatch(B, n, stride, gm_capacity=a.capacity)
-                return MhRun(pkg, bt, datas[:B], Ps[:B], seeds[:B], n, device_loop=(loop == "device")), bt.close
+                return sim.Sim2dMHBatchRun(bt, datas[:B], Ps[:B], seeds[:B], n, device_loop=(loop == "device")), bt.close
             figs, counts = timed_run(make)
             key = "batch_filter_steps_per_s" if loop == "host" else "device_loop_filter_steps_per_s"
             row[key], row[key + "_reps"] = float(np.median(figs)), figs
@@ -268,7 +295,7 @@ def mh_sweep(pkg, a, sizes):
         if B <= a.handles_max:
             def make_h():
                 hs = [mh_handle(pkg, n, stride, a.capacity) for _ in range(B)]
-                return MhRun(pkg, hs, datas[:B], Ps[:B], seeds[:B], n), (lambda: [h.close() for h in hs])
+                return sim.Sim2dMHBatchRun(hs, datas[:B], Ps[:B], seeds[:B], n), (lambda: [h.close() for h in hs])
             figs, _ = timed_run(make_h)
             row["handles_filter_steps_per_s"], row["handles_filter_steps_per_s_reps"] = float(np.median(figs)), figs
             for key, name in (("batch_filter_steps_per_s", "speedup"), ("device_loop_filter_steps_per_s", "device_loop_speedup")):
@@ -300,6 +327,7 @@ def main():
     ap.add_argument("--fastslam", action="store_true", help="FastSLAM filters: a FastSLAMBatch against FastSLAM handles stepped in turn")
     ap.add_argument("--reps", type=int, default=1, help="timed repetitions of every batch figure")
     ap.add_argument("--mhfastslam", action="store_true", help="multi-hypothesis FastSLAM filters: an MHFastSLAMBatch against handles on the device cycle stepped in turn")
+    ap.add_argument("--results", default="", help="--errors: write one line per filter of the largest batch, 'Pd  c  posError  mapError' (the final row's pose_ed and cola)")
     ap.add_argument("--max-per-filter", type=int, default=0, help="--mhfastslam: particle slots per filter (default nParticlesMax x hypotheses = 9 x particles, which cannot overflow; at most 2048)")
     a = ap.parse_args()
     pkg = load_pkg()

@@ -8,6 +8,9 @@
            the realisations hold 2 landmarks: a new one appears every 60 steps).
 --batch B --planted N: no simulation: every filter's best particle holds N planted estimates against N landmarks (a finished
            configs[0] map holds 50), scored --calls times.
+--batch B --mhfastslam: the multi-hypothesis sweep of tools/batch_sim.py --mhfastslam (golden configuration, --max-per-filter slots per
+           filter, default nParticlesMax x hypotheses) on its device loop with tracking: the kernel's live-count instantiation
+           (map_metric_kernel<MetricLive>).
 --big N:   one ordinary handle whose best particle holds N estimates (jittered copies of N ground-truth landmarks), scored --calls times.
 Prints the host's wall time per call; the kernel's own time comes from the trace."""
 import argparse
@@ -30,6 +33,8 @@ def main():
     ap.add_argument("--planted", type=int, default=0)
     ap.add_argument("--big", type=int, default=0)
     ap.add_argument("--calls", type=int, default=50)
+    ap.add_argument("--mhfastslam", action="store_true")
+    ap.add_argument("--max-per-filter", type=int, default=0)
     a = ap.parse_args()
     import __graft_entry__ as g
     pkg = g.load_package()
@@ -54,6 +59,25 @@ def main():
         dt = time.perf_counter() - t0
         print("batch %d, %d planted estimates against %d landmarks per filter: %.1f us per call (host wall, %d calls); mean cola %.3f"
               % (a.batch, n, n, 1e6 * dt / a.calls, a.calls, log["cola"][-1].mean()))
+        batch.close()
+    elif a.batch and a.mhfastslam:
+        import batch_sim
+        P0, n = batch_sim.mh_params(sim)
+        stride = a.max_per_filter or min(2048, 3 * n * P0["max_hypotheses"])
+        Ps, _, seeds = batch_sim.grid(sim, a.batch, 3, fastslam=True)
+        Ps = [dict(P0, Pd=P["Pd"], clutter=P["clutter"]) for P in Ps]
+        datas = [sim.generate(P, traj_seed=1 + b, kmax=a.steps + 2) for b, P in enumerate(Ps)]
+        batch = pkg.MHFastSLAMBatch(a.batch, n, stride, gm_capacity=256)
+        run = sim.Sim2dMHBatchRun(batch, datas, Ps, seeds, n, device_loop=True, track_errors=True)
+        run.step(1)
+        run.synchronize()
+        t0 = time.perf_counter()
+        for k in range(2, a.steps + 2):
+            run.step(k)
+        log = run.errors()
+        dt = time.perf_counter() - t0
+        print("MH batch %d (stride %d): %.1f filter-steps/s on the device loop with tracking; final counts %s; last row n_est %s n_truth %s"
+              % (a.batch, stride, a.batch * a.steps / dt, batch.live_counts().tolist(), log["n_est"][-1].tolist(), log["n_truth"][-1].tolist()))
         batch.close()
     elif a.batch:
         import batch_sim
