@@ -39,6 +39,15 @@ inline long long now_ns() {
 
 enum { EV_UM0 = 0, EV_UM1, EV_W1, EV_MG1, EV_PR1, EV_P0, EV_P1, EV_R0, EV_R1, EV_COUNT };
 
+// A ring of pinned staging blocks (ring_acquire): a call writes its inputs into the next block, enqueues the copies or kernels that read
+// it and records the block's event behind the last of them; the block is handed out again once that event has passed.
+struct PinnedRing {
+  unsigned char *h[8] = {};
+  hipEvent_t ev[8] = {};
+  int depth = 4, next = 0;   // blocks in use (4 or 8), cursor
+  size_t bytes = 0;          // of one block (set where the handle is created)
+};
+
 }  // namespace
 
 struct rfsgpu_filter {
@@ -75,7 +84,7 @@ struct rfsgpu_filter {
   int *dSrcSlot = nullptr;  // [N]
   int *dRowSlots = nullptr; // slots of the rows being exported / imported (allocated on first use, grown on demand)
   int rowSlotsCap = 0;
-  double *hStage[4] = {nullptr, nullptr, nullptr, nullptr};  // pinned staging ring of rfsgpu_set_step_inputs_async
+  PinnedRing stage;                   // staging ring of rfsgpu_set_step_inputs_async and every other call that hands the device a few host arrays
   double *hWeights = nullptr;         // pinned landing buffer of rfsgpu_get_weights
   double *hOutW = nullptr;            // pinned: where the post kernel leaves the weights of a synchronous rfsgpu_update_io ...
   int *hOutFlag = nullptr;            // ... and {error word, sequence number} behind them (same allocation)
@@ -95,8 +104,6 @@ struct rfsgpu_filter {
   int *dCollSeq = nullptr;            // [2 + 2] device: {number of the last step whose sums are out, number of the last step whose collective is done} (rfsgpu_step_async_trailing)
   int collStep = 0;                   // steps issued in the event-free trailing form
   double *poseAlt = nullptr;          // [Ncap][3] second pose buffer: a fused predict + update cycle births at the old poses and updates at the new ones (rfsgpu_cycle_async)
-  hipEvent_t evStage[4] = {};
-  int stageNext = 0;
   bool predPending = false;  // rfsgpu_predict_map_async's event pair has not been accumulated yet
   bool candUsed = false;     // candidate lists were imported or the FastSLAM path ran with landmark candidates: migration rows carry them
   bool poseCovZero = false;  // B.poseCov[0..9) holds zeros (the "no covariance" form), so a further cov == NULL push need not rewrite it
@@ -199,9 +206,7 @@ struct rfsgpu_filter {
   int *dBErrFilter = nullptr;         // [1] BatchArg::errFilter
   unsigned long long *dBMaskTmp = nullptr;   // [N] birth inheritance: the masks before the walk
   int *dBInhSrc = nullptr;            // [N]
-  unsigned char *hBStage[4] = {nullptr, nullptr, nullptr, nullptr};   // pinned ring of the per-cycle tables
-  hipEvent_t evBStage[4] = {};
-  int bStageNext = 0;
+  PinnedRing bStage;                  // ring of the per-cycle tables (batch_push_tables)
   // the device loop of a batch (batch_loop.h): propagation and resampling without the host
   std::vector<char> bMotionSet, bResSet;       // rfsgpu_batch_set_motion_odometry / _set_resampling have been called for the filter
   std::vector<BatchMotion> bMotion;
@@ -213,9 +218,7 @@ struct rfsgpu_filter {
   BatchPropIn *dBPropIn = nullptr;             // [nF]
   BatchResIn *dBResIn = nullptr;               // [nF]
   BatchLoopState BL{};
-  unsigned char *hBLoop[8] = {};               // pinned ring of the two calls' per-filter inputs
-  hipEvent_t evBLoop[8] = {};
-  int bLoopNext = 0;
+  PinnedRing bLoop;                            // ring of the two calls' per-filter inputs (eight blocks: two calls per cycle, four cycles)
   // a batch of FastSLAM filters (rfsgpu_batch_fastslam_cycle_async; fastslam.h FsBatchArg)
   int bKind = 0;                               // what the batch steps: 0 not decided yet, 1 RB-PHD filters, 2 FastSLAM filters (the first cycle call decides), 3 multi-hypothesis FastSLAM filters (rfsgpu_create_batch_mh decides)
   std::vector<rfsgpu_fastslam_config> bFs;     // [nF]
@@ -275,6 +278,48 @@ static int mhc_resolve(rfsgpu_filter *f);
 static int fail(rfsgpu_filter *f, int code, const char *msg) {
   f->err = msg;
   return code;
+}
+
+// The next block of a pinned ring (created on first use): waits until whatever was enqueued from it one turn of the ring ago is done.
+// The caller writes into *h, enqueues its host-to-device copies (or the kernels that read the block in place) on the stream and
+// records R.ev[*k_out] behind the last of them.
+template <class T>
+static int ring_acquire(rfsgpu_filter *f, PinnedRing &R, T **h, int *k_out) {
+  const int k = R.next;
+  R.next = (k + 1) & (R.depth - 1);
+  const bool fresh = !R.h[k] || !R.ev[k];               // (either creation may have failed on an earlier call: each is retried on its own)
+  if (!R.h[k]) HIPCHK(hipHostMalloc(&R.h[k], R.bytes));
+  if (!R.ev[k]) HIPCHK(hipEventCreateWithFlags(&R.ev[k], hipEventDisableTiming));
+  if (fresh) HIPCHK(hipStreamSynchronize(f->stream));   // nothing recorded on this block's event yet
+  else HIPCHK(hipEventSynchronize(R.ev[k]));            // what this block fed one turn of the ring ago
+  *h = reinterpret_cast<T *>(R.h[k]);
+  *k_out = k;
+  return RFSGPU_OK;
+}
+// The pose covariance that goes with a push of poses, through hc (pinned, inside the block the caller holds): one shared [9]
+// (cov_stride 0), one per particle [N][9] (cov_stride 9) or none -- then B.poseCov[0 .. 9) gets zeros, once (poseCovZero).  inPacked:
+// the per-particle covariances ride in the step kernel's packed block (its pull form) and no copy command is issued.  The stride is
+// the caller's to set: a single handle writes f->P.poseCovStride, a batch goes through batch_handle_wide and bParamsDirty.
+static int push_pose_cov(rfsgpu_filter *f, double *hc, const double *cov, int cov_stride, bool inPacked = false) {
+  if (cov) {
+    if (!inPacked) {
+      const size_t n = cov_stride == 9 ? (size_t)f->N * 9 : 9;
+      memcpy(hc, cov, n * sizeof(double));
+      HIPCHK(hipMemcpyAsync(f->B.poseCov, hc, n * sizeof(double), hipMemcpyHostToDevice, f->stream));
+    }
+    f->poseCovZero = false;
+  } else if (!f->poseCovZero) {   // (the shared all-zero covariance is written once, not per call)
+    memset(hc, 0, 9 * sizeof(double));
+    HIPCHK(hipMemcpyAsync(f->B.poseCov, hc, 9 * sizeof(double), hipMemcpyHostToDevice, f->stream));
+    f->poseCovZero = true;
+  }
+  return RFSGPU_OK;
+}
+// Poses by copy command through the staging block h: x [N][3] to dst, the covariance behind it (push_pose_cov)
+static int push_poses(rfsgpu_filter *f, double *h, double *dst, const double *x, const double *cov, int cov_stride) {
+  memcpy(h, x, (size_t)f->N * 3 * sizeof(double));
+  HIPCHK(hipMemcpyAsync(dst, h, (size_t)f->N * 3 * sizeof(double), hipMemcpyHostToDevice, f->stream));
+  return push_pose_cov(f, h + (size_t)f->Ncap * 3, cov, cov_stride);
 }
 
 // rfsgpu_partition_likelihoods: one wavefront per table.  dims[4 k ..]: nE, nZ, the table's offset in L, its offset in pd.  The LDS view is
@@ -427,6 +472,7 @@ int rfsgpu_create_ex(rfsgpu_filter **out, int model, int n_particles, int device
   f->device = device_id;
   f->N = n_particles;
   f->Ncap = max_particles;
+  f->stage.bytes = ((size_t)f->Ncap * 22 + RFSGPU_VP_MAX_SCAN) * sizeof(double);   // poses | pose covariances | weights (or the 13-per-particle packed form) | covariances of the packed form's copy path | laser scan
   f->model = model;
   f->D = (model == RFSGPU_MODEL_VICTORIAPARK_3D) ? 3 : 2;
   f->cap = ((gm_capacity + 63) / 64) * 64;
@@ -533,19 +579,18 @@ void rfsgpu_destroy(rfsgpu_filter *f) {
   hipFree(B.scan); hipFree(B.candMean); hipFree(B.candCov); hipFree(B.candSup); hipFree(B.candChk); hipFree(B.candCount);
   murty_free(f->Q, f->MS);
   hipFree(f->dBFilt); hipFree(f->dBParams); hipFree(f->dBZ); hipFree(f->dBZPrev); hipFree(f->dBSums); hipFree(f->dBErrFilter); hipFree(f->dBMaskTmp); hipFree(f->dBInhSrc);
-  for (int k = 0; k < 4; k++) { if (f->hBStage[k]) hipHostFree(f->hBStage[k]); if (f->evBStage[k]) hipEventDestroy(f->evBStage[k]); }
   hipFree(f->dFsFilt);
   hipFree(f->dMhFilt); hipFree(f->mhbBlock); if (f->hMhbBlock) hipHostFree(f->hMhbBlock);
   hipFree(f->dBMotion); hipFree(f->dBPropIn); hipFree(f->dBResIn); hipFree(f->BL.counters); hipFree(f->BL.nResamples); hipFree(f->BL.resampled);
   hipFree(f->BL.fired); hipFree(f->BL.nEff); hipFree(f->BL.plan); hipFree(f->BL.pid); hipFree(f->BL.ppid);
-  for (int k = 0; k < 8; k++) { if (f->hBLoop[k]) hipHostFree(f->hBLoop[k]); if (f->evBLoop[k]) hipEventDestroy(f->evBLoop[k]); }
   hipFree(f->dGtXY); hipFree(f->dGtSeen); hipFree(f->dGtN); hipFree(f->dErrLog); hipFree(f->dErrRow);
   if (f->hErr) hipHostFree(f->hErr);
   if (f->hJobCount) hipHostFree(f->hJobCount);
   if (f->hSums) hipHostFree(f->hSums);
   if (f->hWeights) hipHostFree(f->hWeights);
   if (f->hOutW) hipHostFree(f->hOutW);
-  for (int k = 0; k < 4; k++) { if (f->hStage[k]) hipHostFree(f->hStage[k]); if (f->evStage[k]) hipEventDestroy(f->evStage[k]); }
+  for (PinnedRing *R : {&f->stage, &f->bStage, &f->bLoop})
+    for (int k = 0; k < 8; k++) { if (R->h[k]) hipHostFree(R->h[k]); if (R->ev[k]) hipEventDestroy(R->ev[k]); }
   for (int k = 0; k < RFSGPU_ASYNC_RING; k++)
     for (int e = 0; e < 5; e++) if (f->ring[k][e]) hipEventDestroy(f->ring[k][e]);
   for (int k = 0; k < EV_COUNT; k++) if (f->ev[k]) hipEventDestroy(f->ev[k]);
@@ -727,23 +772,6 @@ int rfsgpu_set_lmk_process_noise(rfsgpu_filter *f, const double *Q) {
   return RFSGPU_OK;
 }
 
-// One slot of the pinned staging ring (four slots of Ncap * 12 + RFSGPU_VP_MAX_SCAN doubles, created on first use): waits until
-// the copies issued from this slot four calls ago are done; the caller copies into *h, enqueues its host-to-device copies on the
-// stream and records f->evStage[*k].
-static int stage_slot(rfsgpu_filter *f, double **h, int *k_out) {
-  const int k = f->stageNext;
-  f->stageNext = (k + 1) & 3;
-  const size_t slotDoubles = (size_t)f->Ncap * 22 + RFSGPU_VP_MAX_SCAN;   // poses | pose covariances | weights (or the 13-per-particle packed form) | covariances of the packed form's copy path | laser scan
-  const bool fresh = !f->hStage[k] || !f->evStage[k];   // (either creation may have failed on an earlier call: each is retried on its own)
-  if (!f->hStage[k]) HIPCHK(hipHostMalloc(&f->hStage[k], slotDoubles * sizeof(double)));
-  if (!f->evStage[k]) HIPCHK(hipEventCreateWithFlags(&f->evStage[k], hipEventDisableTiming));
-  if (fresh) HIPCHK(hipStreamSynchronize(f->stream));    // nothing recorded on this slot's event yet
-  else HIPCHK(hipEventSynchronize(f->evStage[k]));       // the copies issued from this slot four calls ago
-  *h = f->hStage[k];
-  *k_out = k;
-  return RFSGPU_OK;
-}
-
 // (r04: poses and weights go through the pinned staging ring of rfsgpu_set_step_inputs_async -- the caller's buffers are copied
 //  before the call returns, the host-to-device copies are stream-ordered and nothing waits for the GPU.  The synchronous forms
 //  these replaced -- a copy from pageable memory + a stream synchronisation each -- were 46 + 23 us of the 261 us that one
@@ -766,10 +794,10 @@ int rfsgpu_set_weights(rfsgpu_filter *f, const double *w) {
   hipSetDevice(f->device);
   double *h = nullptr;
   int k = 0;
-  { const int rc = stage_slot(f, &h, &k); if (rc != RFSGPU_OK) return rc; }
+  { const int rc = ring_acquire(f, f->stage, &h, &k); if (rc != RFSGPU_OK) return rc; }
   memcpy(h, w, (size_t)f->N * sizeof(double));
   HIPCHK(hipMemcpyAsync(f->B.weight, h, (size_t)f->N * sizeof(double), hipMemcpyHostToDevice, f->stream));
-  HIPCHK(hipEventRecord(f->evStage[k], f->stream));
+  HIPCHK(hipEventRecord(f->stage.ev[k], f->stream));
   return RFSGPU_OK;
 }
 int rfsgpu_get_weights(rfsgpu_filter *f, double *w) {
@@ -1172,6 +1200,36 @@ int rfsgpu_prune(rfsgpu_filter *f) {
   return RFSGPU_OK;
 }
 
+// The fused step's variant for a launch of N particles: waves per particle, phase priorities, the LDS block of a workgroup (and how
+// many workgroups a CU holds at that).  stepWppOverride 2 | 3 and prioOverride 0 | 1 replace the rule's choices (0 / negative: none).
+struct StepVariant { int wpp, phasePrio, perCU; size_t ldsBytes; };
+static StepVariant step_variant(int cap, int evalCap, int nZ, int N, int nCU, int stepWppOverride, int prioOverride) {
+  // Waves per particle: two, unless the two-wave grid cannot be resident at once (large mixtures: the LDS block limits the
+  // workgroups per CU) -- then three waves per particle finish each workgroup sooner and free its slot (measured on the
+  // configs[2] shard, 2500 x 500 x 30 at cap 640: fused step 327 -> 263 us; at C2a, where all 2000 two-wave workgroups are
+  // resident, three waves lose: 133 -> 180 us).  RFSGPU_STEP_WPP = 2 | 3 overrides.
+  const size_t b2 = step_fused_lds_total(cap, evalCap, nZ, 2);
+  const int perCU2 = (int)std::min<size_t>(8, b2 ? (size_t)(160 * 1024) / b2 : 8);
+  // (three waves only where it is the LDS block that keeps two-wave workgroups below the 8 per CU the wave slots allow: at
+  //  capacity 384 -- 9 blocks of LDS per CU -- a launch of more than 2048 particles is better off with two waves per particle
+  //  in several rounds: 3000 particles 229 us against 389, 8000: 474 against 882)
+  StepVariant v;
+  v.wpp = ((long long)perCU2 * nCU >= N || perCU2 >= 8) ? 2 : 3;
+  {  // (round 5) a launch small enough for every THREE-wave workgroup to be resident at once takes three waves per particle: a
+     // particle's own chain is what such a launch lasts, and the third wave shortens it -- fused step at configs[1]'s shape with
+     // 1000 / 500 / 250 particles 103.6 / 95.4 / 102.4 -> 99.3 / 86.1 / 94.6 us; at 2000 particles (1280 three-wave workgroups
+     // resident) two waves stay: 112 against 180 us
+    const size_t b3 = step_fused_lds_total(cap, evalCap, nZ, 3);
+    const int perCU3 = (int)std::min<size_t>(16 / 3, b3 ? (size_t)(160 * 1024) / b3 : 16 / 3);
+    if ((long long)perCU3 * nCU >= N) v.wpp = 3;
+  }
+  if (stepWppOverride == 2 || stepWppOverride == 3) v.wpp = stepWppOverride;
+  v.ldsBytes = step_fused_lds_total(cap, evalCap, nZ, v.wpp);
+  // phase priorities only when every workgroup is resident at once: 16 waves per CU at 128 VGPRs, LDS permitting
+  v.perCU = (int)std::min<size_t>(16 / v.wpp, v.ldsBytes ? (size_t)(160 * 1024) / v.ldsBytes : 16);
+  v.phasePrio = prioOverride >= 0 ? (prioOverride ? 1 : 0) : ((long long)v.perCU * nCU >= N ? 1 : 0);
+  return v;
+}
 // All four phases back to back on the stream, ONE host sync at the end (RBPHDFilter::update body :444-523).
 static const StepOut NO_OUT{nullptr, nullptr, 0, nullptr, nullptr, 0, 0};
 static const StepPredict NO_HEAD{0, 0, nullptr, nullptr, 0};
@@ -1291,31 +1349,11 @@ static int update_async_impl(rfsgpu_filter *f, const double *z, int n_z, bool wi
     const bool timed = step_carries_events(f);   // (rfsgpu_set_step_timing_stride)
     if (timed) HIPCHK(hipEventRecord(e[0], f->stream));
     const int ec = eval_cap(f), useW = f->cfg.useClusterProcess ? 0 : 1;
-    // Waves per particle: two, unless the two-wave grid cannot be resident at once (large mixtures: the LDS block limits the
-    // workgroups per CU) -- then three waves per particle finish each workgroup sooner and free its slot (measured on the
-    // configs[2] shard, 2500 x 500 x 30 at cap 640: fused step 327 -> 263 us; at C2a, where all 2000 two-wave workgroups are
-    // resident, three waves lose: 133 -> 180 us).  RFSGPU_STEP_WPP = 2 | 3 overrides.
-    const size_t b2 = step_fused_lds_total(f->cap, ec, f->nZ, 2);
-    const int perCU2 = (int)std::min<size_t>(8, b2 ? (size_t)(160 * 1024) / b2 : 8);
-    // (three waves only where it is the LDS block that keeps two-wave workgroups below the 8 per CU the wave slots allow: at
-    //  capacity 384 -- 9 blocks of LDS per CU -- a launch of more than 2048 particles is better off with two waves per particle
-    //  in several rounds: 3000 particles 229 us against 389, 8000: 474 against 882)
-    int wpp = ((long long)perCU2 * f->nCU >= f->N || perCU2 >= 8) ? 2 : 3;
-    {  // (round 5) a launch small enough for every THREE-wave workgroup to be resident at once takes three waves per particle: a
-       // particle's own chain is what such a launch lasts, and the third wave shortens it -- fused step at configs[1]'s shape with
-       // 1000 / 500 / 250 particles 103.6 / 95.4 / 102.4 -> 99.3 / 86.1 / 94.6 us; at 2000 particles (1280 three-wave workgroups
-       // resident) two waves stay: 112 against 180 us
-      const size_t b3 = step_fused_lds_total(f->cap, ec, f->nZ, 3);
-      const int perCU3 = (int)std::min<size_t>(16 / 3, b3 ? (size_t)(160 * 1024) / b3 : 16 / 3);
-      if ((long long)perCU3 * f->nCU >= f->N) wpp = 3;
-    }
-    if (f->stepWppOverride == 2 || f->stepWppOverride == 3) wpp = f->stepWppOverride;
-    const size_t b = step_fused_lds_total(f->cap, ec, f->nZ, wpp);
-    // phase priorities only when every workgroup is resident at once: 16 waves per CU at 128 VGPRs, LDS permitting
-    const int perCU = (int)std::min<size_t>(16 / wpp, b ? (size_t)(160 * 1024) / b : 16);
-    // (RFSGPU_STEP_PHASE_PRIO = 0 | 1: tuning override of the choice below)
+    // (RFSGPU_STEP_PHASE_PRIO = 0 | 1: tuning override of the rule's choice)
     static const int prioOverride = [] { const char *e = getenv("RFSGPU_STEP_PHASE_PRIO"); return e ? atoi(e) : -1; }();
-    const int phasePrio = prioOverride >= 0 ? (prioOverride ? 1 : 0) : ((long long)perCU * f->nCU >= f->N ? 1 : 0);
+    const StepVariant sv = step_variant(f->cap, ec, f->nZ, f->N, f->nCU, f->stepWppOverride, prioOverride);
+    const int wpp = sv.wpp, phasePrio = sv.phasePrio, perCU = sv.perCU;
+    const size_t b = sv.ldsBytes;
     f->lastStepVariant[0] = wpp; f->lastStepVariant[1] = phasePrio; f->lastStepVariant[2] = 5; f->lastStepVariant[3] = sp.mode ? 2 : (sp.inMask ? 3 : 1);   // ([3]: 1 = fused step, 2 = with the predict at its head, 3 = with the input pull only)
     // (one instantiation per {waves per particle, phase priorities, merge grid} x {plain step, step with the predict at its head})
     // cost-ordered launch for the instantiations without phase priorities (several rounds of workgroups; step_fused.h StepLaunchOrder)
@@ -1626,7 +1664,7 @@ static int cycle_impl(rfsgpu_filter *f, int predict, const double *x, const doub
   if (x || w_in) {
     double *h = nullptr;
     int k = 0;
-    { const int rc = stage_slot(f, &h, &k); if (rc != RFSGPU_OK) return rc; }
+    { const int rc = ring_acquire(f, f->stage, &h, &k); if (rc != RFSGPU_OK) return rc; }
     const bool pullCov = pull && x && cov && cov_stride == 9;
     if (pull) {
       // 13 doubles per particle side by side: the workgroup that owns a particle reads them in one go (step_fused.h, StepPredict)
@@ -1646,30 +1684,16 @@ static int cycle_impl(rfsgpu_filter *f, int predict, const double *x, const doub
         HIPCHK(hipMemcpyAsync(dst, h, (size_t)f->N * 3 * sizeof(double), hipMemcpyHostToDevice, f->stream));
         if (fuse) { f->poseAlt = f->B.pose; f->B.pose = dst; }
       }
-      double *hc = h + (size_t)f->Ncap * 13;               // (behind the packed block: the small / copy-command forms of the covariance)
-      if (cov) {                                           // (the births do not read the pose covariance)
-        if (!pullCov) {
-          const size_t n = cov_stride == 9 ? (size_t)f->N * 9 : 9;
-          memcpy(hc, cov, n * sizeof(double));
-          HIPCHK(hipMemcpyAsync(f->B.poseCov, hc, n * sizeof(double), hipMemcpyHostToDevice, f->stream));
-        }
-        f->P.poseCovStride = cov_stride;
-        f->poseCovZero = false;
-      } else {
-        if (!f->poseCovZero) {
-          memset(hc, 0, 9 * sizeof(double));
-          HIPCHK(hipMemcpyAsync(f->B.poseCov, hc, 9 * sizeof(double), hipMemcpyHostToDevice, f->stream));
-          f->poseCovZero = true;
-        }
-        f->P.poseCovStride = 0;
-      }
+      // (the covariance's small / copy-command forms go behind the packed block; the births do not read the pose covariance)
+      { const int rc = push_pose_cov(f, h + (size_t)f->Ncap * 13, cov, cov_stride, pullCov); if (rc != RFSGPU_OK) return rc; }
+      f->P.poseCovStride = cov ? cov_stride : 0;
     }
     if (w_in && !pull) {
       double *hw = h + (size_t)f->Ncap * 12;
       memcpy(hw, w_in, (size_t)f->N * sizeof(double));
       HIPCHK(hipMemcpyAsync(f->B.weight, hw, (size_t)f->N * sizeof(double), hipMemcpyHostToDevice, f->stream));
     }
-    if (!pull) HIPCHK(hipEventRecord(f->evStage[k], f->stream));
+    if (!pull) HIPCHK(hipEventRecord(f->stage.ev[k], f->stream));
     else f->stagePendingSlot = k;
   }
   if (n_z == 0) {       // no update (:450-452); the weights are still summed / normalised as the caller asked
@@ -1692,7 +1716,7 @@ static int cycle_impl(rfsgpu_filter *f, int predict, const double *x, const doub
   const int rc = update_async_impl(f, z, n_z, with_sums, normalize, sp, so);
   if (g_ioProf.on) { const long long tp2 = now_ns(); g_ioProf.stage += tp1 - tp0; g_ioProf.launch += tp2 - tp1; }
   if (f->stagePendingSlot >= 0) {            // the pinned slot is read by the kernels just enqueued: its event goes behind them
-    if (rc == RFSGPU_OK) HIPCHK(hipEventRecord(f->evStage[f->stagePendingSlot], f->stream));
+    if (rc == RFSGPU_OK) HIPCHK(hipEventRecord(f->stage.ev[f->stagePendingSlot], f->stream));
     f->stagePendingSlot = -1;
   }
   return rc;
@@ -2011,26 +2035,11 @@ int rfsgpu_set_step_inputs_async(rfsgpu_filter *f, const double *x, const double
   hipSetDevice(f->device);
   double *h = nullptr;
   int k = 0;
-  { const int rc = stage_slot(f, &h, &k); if (rc != RFSGPU_OK) return rc; }
+  { const int rc = ring_acquire(f, f->stage, &h, &k); if (rc != RFSGPU_OK) return rc; }
   if (x) {
     f->bBirthAlt = false;   // (a batch: poses set after rfsgpu_batch_propagate_async are the ones the next predict's births happen at, as on the host route)
-    memcpy(h, x, (size_t)f->N * 3 * sizeof(double));
-    HIPCHK(hipMemcpyAsync(f->B.pose, h, (size_t)f->N * 3 * sizeof(double), hipMemcpyHostToDevice, f->stream));
-    double *hc = h + (size_t)f->Ncap * 3;
-    if (cov) {
-      const size_t n = cov_stride == 9 ? (size_t)f->N * 9 : 9;
-      memcpy(hc, cov, n * sizeof(double));
-      HIPCHK(hipMemcpyAsync(f->B.poseCov, hc, n * sizeof(double), hipMemcpyHostToDevice, f->stream));
-      f->P.poseCovStride = cov_stride;
-      f->poseCovZero = false;
-    } else {
-      if (!f->poseCovZero) {   // (the shared all-zero covariance is written once, not per call)
-        memset(hc, 0, 9 * sizeof(double));
-        HIPCHK(hipMemcpyAsync(f->B.poseCov, hc, 9 * sizeof(double), hipMemcpyHostToDevice, f->stream));
-        f->poseCovZero = true;
-      }
-      f->P.poseCovStride = 0;
-    }
+    { const int rc = push_poses(f, h, f->B.pose, x, cov, cov_stride); if (rc != RFSGPU_OK) return rc; }
+    f->P.poseCovStride = cov ? cov_stride : 0;
   }
   if (scan) {
     double area = 0;
@@ -2044,7 +2053,7 @@ int rfsgpu_set_step_inputs_async(rfsgpu_filter *f, const double *x, const double
     f->B.nScan = n_scan;
     rebuild_params(f);
   }
-  HIPCHK(hipEventRecord(f->evStage[k], f->stream));
+  HIPCHK(hipEventRecord(f->stage.ev[k], f->stream));
   return RFSGPU_OK;
 }
 
@@ -2166,13 +2175,13 @@ int rfsgpu_resample_apply_n(rfsgpu_filter *f, const int *src_slot, int n_out) {
   }
   double *hs;
   int ks;
-  int rc = stage_slot(f, &hs, &ks);
+  int rc = ring_acquire(f, f->stage, &hs, &ks);
   if (rc != RFSGPU_OK) return rc;
   memcpy(hs, src_slot, (size_t)f->N * sizeof(int));
   resample_gather_kernel<<<f->N, 256, 0, f->stream>>>(f->B, f->cur, reinterpret_cast<const int *>(hs), f->P.poseCovStride, map_only(f));
   set_weights_kernel<<<(f->N + 255) / 256, 256, 0, f->stream>>>(f->B.weight, f->N, 1.0);
   HIPCHK(hipGetLastError());
-  HIPCHK(hipEventRecord(f->evStage[ks], f->stream));      // the slot is free again once the gather has read it
+  HIPCHK(hipEventRecord(f->stage.ev[ks], f->stream));      // the slot is free again once the gather has read it
   const long long dtn = now_ns() - t0;
   f->timing.particleResample_wall += dtn;
   f->timing.particleResample_cpu += dtn;
@@ -3067,19 +3076,6 @@ static Params batch_params(rfsgpu_filter *f, int b) {
 static size_t batch_stage_bytes(const rfsgpu_filter *f) {
   return (size_t)f->nF * (std::max(sizeof(MhBatchFilter), std::max(sizeof(BatchFilter), sizeof(FsBatchFilter))) + sizeof(Params) + RFSGPU_MAX_Z * 2 * sizeof(double) + sizeof(int)) + (size_t)f->N * sizeof(int);
 }
-// One slot of the batch's pinned ring (as stage_slot): waits until the copies issued from it four cycles ago are done.
-static int batch_stage(rfsgpu_filter *f, unsigned char **h, int *k_out) {
-  const int k = f->bStageNext;
-  f->bStageNext = (k + 1) & 3;
-  const bool fresh = !f->hBStage[k] || !f->evBStage[k];
-  if (!f->hBStage[k]) HIPCHK(hipHostMalloc(&f->hBStage[k], batch_stage_bytes(f)));
-  if (!f->evBStage[k]) HIPCHK(hipEventCreateWithFlags(&f->evBStage[k], hipEventDisableTiming));
-  if (fresh) HIPCHK(hipStreamSynchronize(f->stream));
-  else HIPCHK(hipEventSynchronize(f->evBStage[k]));
-  *h = f->hBStage[k];
-  *k_out = k;
-  return RFSGPU_OK;
-}
 // The handle-wide Params fields of a cycle (both kinds of batch): the pose covariance stride the call's x / x_cov ask for, and whatever
 // else of f->P every filter's record repeats; the table is rewritten when one of them has changed.
 static void batch_handle_wide(rfsgpu_filter *f, const double *x, const double *x_cov, int cov_stride) {
@@ -3094,6 +3090,81 @@ static void batch_handle_wide(rfsgpu_filter *f, const double *x, const double *x
 static int batch_check(rfsgpu_filter *f, int filter) {
   if (!f->batch) return fail(f, RFSGPU_ERR_INVALID, "not a filter batch (rfsgpu_create_batch)");
   if (filter < -1 || filter >= f->nF) return fail(f, RFSGPU_ERR_INVALID, "batch: filter index out of range");
+  return RFSGPU_OK;
+}
+// The argument checks that the batch's cycle calls and rfsgpu_batch_resample_async share, each under the call's own prefix and wording.
+// predictIs: what the call's predict may be, from predictMin to 1 (nullptr: a call without predict, pose and measurement arguments).
+struct BatchCall { const char *who; int predictMin; const char *predictIs, *nullCounts; };
+static const BatchCall BATCH_CYCLE{"batch_cycle", -1, "RFSGPU_CYCLE_NO_PREDICT (-1), 0 (static step only) or 1 (births + static step)", "null measurement counts"};
+static const BatchCall BATCH_FS_CYCLE{"batch_fastslam_cycle", -1, "RFSGPU_CYCLE_NO_PREDICT (-1), or 0 / 1 (the static landmark step; FastSLAM has no births)", "null measurement counts"};
+static const BatchCall BATCH_MH_CYCLE{"batch_fastslam_mh_cycle", 0, "0 or 1 (the static landmark step; FastSLAM has no births)", "null measurement counts or draws"};
+static const BatchCall BATCH_RESAMPLE{"batch_resample", 0, nullptr, "null measurement counts"};
+static int batch_fail(rfsgpu_filter *f, const BatchCall &C, const std::string &msg) {
+  f->err = std::string(C.who) + ": " + msg;
+  return RFSGPU_ERR_INVALID;
+}
+// ... the call as a whole: predict, cov_stride, the counts array (counts: n_z, or null when another per-filter array of the call is)
+static int batch_check_call(rfsgpu_filter *f, const BatchCall &C, int predict, const double *x_cov, int cov_stride, const void *counts) {
+  if (C.predictIs && (predict < C.predictMin || predict > 1)) return batch_fail(f, C, std::string("predict is ") + C.predictIs);
+  if (C.predictIs && x_cov && cov_stride != 0 && cov_stride != 9) return batch_fail(f, C, "cov_stride must be 0 or 9");
+  if (!counts) return batch_fail(f, C, C.nullCounts);
+  return RFSGPU_OK;
+}
+// ... and filter b's measurement set; the caller's own per-filter checks follow it in the caller's loop, so that the first offending
+// filter is reported whichever check it fails
+static int batch_check_filter(rfsgpu_filter *f, const BatchCall &C, int b, const double *z, const int *n_z) {
+  if (n_z[b] < 0 || n_z[b] > RFSGPU_MAX_Z) return batch_fail(f, C, "filter " + std::to_string(b) + " has " + std::to_string(n_z[b]) + " measurements (0 ... RFSGPU_MAX_Z)");
+  if (C.predictIs && n_z[b] > 0 && !z) return batch_fail(f, C, "null measurement buffer");
+  return RFSGPU_OK;
+}
+}  // extern "C" (templates need C++ linkage)
+// One cycle's per-filter tables, through a block of the batch's pinned ring to the device: {records [nF] | Params [nF] | z, packed |
+// extra}.  The Params table is rebuilt and pushed when the configuration or a handle-wide field has changed (bParamsDirty; bParamsHost
+// keeps what the device holds).  Every record is zeroed (its padding travels too), gets its filter's count and offset into the packed
+// sets, and goes to fill(record, b) for the rest.  extra: one more host table for the block's tail, copied to dExtra (null: none).
+template <class Rec, class Fill>
+static int batch_push_tables(rfsgpu_filter *f, Rec *dRec, const double *z, const int *n_z, const void *extra, size_t extraBytes, void *dExtra, Fill fill) {
+  const int nF = f->nF;
+  unsigned char *h = nullptr;
+  int k = 0;
+  { const int rc = ring_acquire(f, f->bStage, &h, &k); if (rc != RFSGPU_OK) return rc; }
+  Rec *hf = reinterpret_cast<Rec *>(h);
+  Params *hp = reinterpret_cast<Params *>(h + (size_t)nF * sizeof(Rec));
+  double *hz = reinterpret_cast<double *>(h + (size_t)nF * (sizeof(Rec) + sizeof(Params)));
+  if (f->bParamsDirty) {
+    for (int b = 0; b < nF; b++) hp[b] = f->bParamsHost[b] = batch_params(f, b);
+    HIPCHK(hipMemcpyAsync(f->dBParams, hp, (size_t)nF * sizeof(Params), hipMemcpyHostToDevice, f->stream));
+    f->bParamsDirty = false;
+  }
+  int zOff = 0;
+  for (int b = 0; b < nF; b++) {
+    Rec &T = hf[b];
+    memset(&T, 0, sizeof T);
+    T.nZ = n_z[b];
+    T.zOff = zOff;
+    fill(T, b);
+    if (n_z[b] > 0) memcpy(hz + zOff, z + (size_t)b * RFSGPU_MAX_Z * 2, (size_t)n_z[b] * 2 * sizeof(double));
+    zOff += 2 * n_z[b];
+  }
+  HIPCHK(hipMemcpyAsync(dRec, hf, (size_t)nF * sizeof(Rec), hipMemcpyHostToDevice, f->stream));
+  if (zOff) HIPCHK(hipMemcpyAsync(f->dBZ, hz, (size_t)zOff * sizeof(double), hipMemcpyHostToDevice, f->stream));
+  if (extra) {
+    void *he = hz + (size_t)nF * RFSGPU_MAX_Z * 2;
+    memcpy(he, extra, extraBytes);
+    HIPCHK(hipMemcpyAsync(dExtra, he, extraBytes, hipMemcpyHostToDevice, f->stream));
+  }
+  HIPCHK(hipEventRecord(f->bStage.ev[k], f->stream));
+  return RFSGPU_OK;
+}
+extern "C" {
+// The host's new poses / covariances of a batch by copy command, through a block of the staging ring (batch_handle_wide has the stride)
+static int batch_push_poses(rfsgpu_filter *f, const double *x, const double *x_cov, int cov_stride) {
+  double *hx = nullptr;
+  int ks = 0;
+  int rc = ring_acquire(f, f->stage, &hx, &ks);
+  if (rc != RFSGPU_OK) return rc;
+  if ((rc = push_poses(f, hx, f->B.pose, x, x_cov, cov_stride)) != RFSGPU_OK) return rc;
+  HIPCHK(hipEventRecord(f->stage.ev[ks], f->stream));
   return RFSGPU_OK;
 }
 
@@ -3114,6 +3185,9 @@ int rfsgpu_create_batch(rfsgpu_filter **out, int model, int n_filters, int n_per
   f->bFs.resize(n_filters);
   for (auto &c : f->bFs) rfsgpu_default_fastslam_config(&c);
   f->bParamsHost.resize(n_filters);
+  f->bStage.bytes = batch_stage_bytes(f);
+  f->bLoop.bytes = (size_t)n_filters * std::max(sizeof(BatchMotion), std::max(sizeof(BatchPropIn), sizeof(BatchResIn)));
+  f->bLoop.depth = 8;
   batch_set_all(f);
   bool ok = true;
   ok &= hipMalloc(&f->dBFilt, (size_t)n_filters * sizeof(BatchFilter)) == hipSuccess;
@@ -3177,17 +3251,11 @@ int rfsgpu_batch_cycle_async(rfsgpu_filter *f, int predict, const double *x, con
   int rc = batch_check(f, -1);
   if (rc != RFSGPU_OK) return rc;
   REFUSE_ON_MH_BATCH(f, "rfsgpu_batch_cycle_async");
-  if (predict < -1 || predict > 1) return fail(f, RFSGPU_ERR_INVALID, "batch_cycle: predict is RFSGPU_CYCLE_NO_PREDICT (-1), 0 (static step only) or 1 (births + static step)");
-  if (x_cov && cov_stride != 0 && cov_stride != 9) return fail(f, RFSGPU_ERR_INVALID, "batch_cycle: cov_stride must be 0 or 9");
-  if (!n_z) return fail(f, RFSGPU_ERR_INVALID, "batch_cycle: null measurement counts");
+  if ((rc = batch_check_call(f, BATCH_CYCLE, predict, x_cov, cov_stride, n_z)) != RFSGPU_OK) return rc;
   const int nF = f->nF, nPer = f->nPer;
   int nZmax = 0, ecMax = 1;
   for (int b = 0; b < nF; b++) {
-    if (n_z[b] < 0 || n_z[b] > RFSGPU_MAX_Z) {
-      f->err = "batch_cycle: filter " + std::to_string(b) + " has " + std::to_string(n_z[b]) + " measurements (0 ... RFSGPU_MAX_Z)";
-      return RFSGPU_ERR_INVALID;
-    }
-    if (n_z[b] > 0 && !z) return fail(f, RFSGPU_ERR_INVALID, "batch_cycle: null measurement buffer");
+    if ((rc = batch_check_filter(f, BATCH_CYCLE, b, z, n_z)) != RFSGPU_OK) return rc;
     if (f->bCfg[b].birthGaussianMeasurementCountThreshold != 1u)
       return fail(f, RFSGPU_ERR_UNSUPPORTED, "batch_cycle: a filter batch takes immediate births only (birthGaussianMeasurementCountThreshold 1)");
     nZmax = std::max(nZmax, n_z[b]);
@@ -3197,11 +3265,7 @@ int rfsgpu_batch_cycle_async(rfsgpu_filter *f, int predict, const double *x, con
   f->bKind = 1;
   hipSetDevice(f->device);
   long long t0 = now_ns();
-  // pose covariance stride: handle-wide, as rfsgpu_cycle_async sets it
-  if (x) {
-    const int stride = x_cov ? cov_stride : 0;
-    if (f->P.poseCovStride != stride) { f->P.poseCovStride = stride; f->bParamsDirty = true; }
-  }
+  batch_handle_wide(f, x, x_cov, cov_stride);   // (the pose covariance stride: handle-wide, as rfsgpu_cycle_async sets it)
   // the reference's lazy birth-state copy after a resampling (birth.h): with immediate births only the unused-measurement mask moves.
   // A slot copies from a HIGHER slot what that slot held before this predict, and from a LOWER slot what that one holds after its own
   // birth step: nothing once that filter has had an update (its births consume the whole mask), else what it inherited in turn.
@@ -3222,19 +3286,8 @@ int rfsgpu_batch_cycle_async(rfsgpu_filter *f, int predict, const double *x, con
       }
     }
   }
-  // per-cycle tables into a slot of the pinned ring, then to the device
-  unsigned char *h = nullptr;
-  int kb = 0;
-  if ((rc = batch_stage(f, &h, &kb)) != RFSGPU_OK) return rc;
-  BatchFilter *hf = reinterpret_cast<BatchFilter *>(h);
-  Params *hp = reinterpret_cast<Params *>(h + (size_t)nF * sizeof(BatchFilter));
-  double *hz = reinterpret_cast<double *>(h + (size_t)nF * (sizeof(BatchFilter) + sizeof(Params)));
-  int *hsrc = reinterpret_cast<int *>(hz + (size_t)nF * RFSGPU_MAX_Z * 2);
-  int zOff = 0;
-  for (int b = 0; b < nF; b++) {
-    BatchFilter &F = hf[b];
-    memset(&F, 0, sizeof F);
-    F.nZ = n_z[b];
+  // per-cycle tables (the host route's inheritance table at their tail)
+  rc = batch_push_tables(f, f->dBFilt, z, n_z, src.empty() ? nullptr : src.data(), (size_t)f->N * sizeof(int), f->dBInhSrc, [&](BatchFilter &F, int b) {
     F.nZprev = f->bNZ[b];
     int c = f->bCfg[b].importanceWeightingEvalPointCount;
     if (c < 0 || c > RFSGPU_MAX_EVAL) c = RFSGPU_MAX_EVAL;
@@ -3242,25 +3295,9 @@ int rfsgpu_batch_cycle_async(rfsgpu_filter *f, int predict, const double *x, con
     F.evalCap = c;
     ecMax = std::max(ecMax, c);
     F.useW = f->bCfg[b].useClusterProcess ? 0 : 1;
-    F.zOff = zOff;
-    if (n_z[b] > 0) memcpy(hz + zOff, z + (size_t)b * RFSGPU_MAX_Z * 2, (size_t)n_z[b] * 2 * sizeof(double));
-    zOff += 2 * n_z[b];
-  }
-  HIPCHK(hipMemcpyAsync(f->dBFilt, hf, (size_t)nF * sizeof(BatchFilter), hipMemcpyHostToDevice, f->stream));
-  if (zOff) HIPCHK(hipMemcpyAsync(f->dBZ, hz, (size_t)zOff * sizeof(double), hipMemcpyHostToDevice, f->stream));
-  {
-    const int hw[3] = {f->P.poseCovStride, f->P.exactPartitions, f->P.denseIntensity};
-    for (int q = 0; q < 3; q++)
-      if (hw[q] != f->bHandleWide[q]) { f->bHandleWide[q] = hw[q]; f->bParamsDirty = true; }
-  }
-  if (f->bParamsDirty) {
-    for (int b = 0; b < nF; b++) hp[b] = batch_params(f, b);
-    HIPCHK(hipMemcpyAsync(f->dBParams, hp, (size_t)nF * sizeof(Params), hipMemcpyHostToDevice, f->stream));
-    f->bParamsDirty = false;
-  }
+  });
+  if (rc != RFSGPU_OK) return rc;
   if (!src.empty()) {
-    memcpy(hsrc, src.data(), (size_t)f->N * sizeof(int));
-    HIPCHK(hipMemcpyAsync(f->dBInhSrc, hsrc, (size_t)f->N * sizeof(int), hipMemcpyHostToDevice, f->stream));
     HIPCHK(hipMemcpyAsync(f->dBMaskTmp, f->B.unusedMask, (size_t)f->N * sizeof(unsigned long long), hipMemcpyDeviceToDevice, f->stream));
     batch_inherit_kernel<<<(f->N + 255) / 256, 256, 0, f->stream>>>(f->B.unusedMask, f->dBMaskTmp, f->dBInhSrc, f->N);
   }
@@ -3268,7 +3305,6 @@ int rfsgpu_batch_cycle_async(rfsgpu_filter *f, int predict, const double *x, con
     batch_inherit_dev_kernel<<<nF, BATCH_LOOP_THREADS, 0, f->stream>>>(f->B.unusedMask, f->BL.ppid, f->BL.resampled, f->dBFilt, nPer, predict == 1 ? 1 : 0);
     HIPCHK(hipGetLastError());
   }
-  HIPCHK(hipEventRecord(f->evBStage[kb], f->stream));
   // the host's new poses / covariances, pulled by the step kernel from a slot of the staging ring (rfsgpu_cycle_async's form)
   StepPredict sp = NO_HEAD;
   sp.mode = predict < 0 ? 0 : (predict ? 2 : 1);
@@ -3277,7 +3313,7 @@ int rfsgpu_batch_cycle_async(rfsgpu_filter *f, int predict, const double *x, con
   int ks = -1;
   if (x) {
     double *hx = nullptr;
-    if ((rc = stage_slot(f, &hx, &ks)) != RFSGPU_OK) return rc;
+    if ((rc = ring_acquire(f, f->stage, &hx, &ks)) != RFSGPU_OK) return rc;
     const bool pullCov = x_cov && cov_stride == 9;
     sp.inPacked = hx;
     sp.inMask = 1 | (pullCov ? 2 : 0);
@@ -3286,34 +3322,14 @@ int rfsgpu_batch_cycle_async(rfsgpu_filter *f, int predict, const double *x, con
       d[0] = x[3 * i]; d[1] = x[3 * i + 1]; d[2] = x[3 * i + 2];
       if (pullCov) memcpy(d + 3, x_cov + (size_t)9 * i, 9 * sizeof(double));
     }
-    double *hc = hx + (size_t)f->Ncap * 13;
-    if (x_cov) {
-      if (!pullCov) {
-        memcpy(hc, x_cov, 9 * sizeof(double));
-        HIPCHK(hipMemcpyAsync(f->B.poseCov, hc, 9 * sizeof(double), hipMemcpyHostToDevice, f->stream));
-      }
-      f->poseCovZero = false;
-    } else if (!f->poseCovZero) {
-      memset(hc, 0, 9 * sizeof(double));
-      HIPCHK(hipMemcpyAsync(f->B.poseCov, hc, 9 * sizeof(double), hipMemcpyHostToDevice, f->stream));
-      f->poseCovZero = true;
-    }
+    if ((rc = push_pose_cov(f, hx + (size_t)f->Ncap * 13, x_cov, cov_stride, pullCov)) != RFSGPU_OK) return rc;
   }
   BatchArg A{f->dBFilt, f->dBParams, f->dBZ, f->dBZPrev, f->dBSums, f->dBErrFilter, nF, nPer};
-  // waves per particle and phase priorities: the single handle's rule (update_async_impl) for the whole launch, LDS sized for the
-  // batch's largest evalCap and set (every filter's own layout lies inside it)
-  const size_t b2 = step_fused_lds_total(f->cap, ecMax, nZmax, 2);
-  const int perCU2 = (int)std::min<size_t>(8, b2 ? (size_t)(160 * 1024) / b2 : 8);
-  int wpp = ((long long)perCU2 * f->nCU >= f->N || perCU2 >= 8) ? 2 : 3;
-  {
-    const size_t b3 = step_fused_lds_total(f->cap, ecMax, nZmax, 3);
-    const int perCU3 = (int)std::min<size_t>(16 / 3, b3 ? (size_t)(160 * 1024) / b3 : 16 / 3);
-    if ((long long)perCU3 * f->nCU >= f->N) wpp = 3;
-  }
-  if (f->stepWppOverride == 2 || f->stepWppOverride == 3) wpp = f->stepWppOverride;
-  const size_t lds = step_fused_lds_total(f->cap, ecMax, nZmax, wpp);
-  const int perCU = (int)std::min<size_t>(16 / wpp, lds ? (size_t)(160 * 1024) / lds : 16);
-  const int phasePrio = (long long)perCU * f->nCU >= f->N ? 1 : 0;
+  // waves per particle and phase priorities: the single handle's rule (step_variant) for the whole launch, LDS sized for the batch's
+  // largest evalCap and set (every filter's own layout lies inside it)
+  const StepVariant sv = step_variant(f->cap, ecMax, nZmax, f->N, f->nCU, f->stepWppOverride, -1);
+  const int wpp = sv.wpp, phasePrio = sv.phasePrio;
+  const size_t lds = sv.ldsBytes;
   f->lastStepVariant[0] = wpp; f->lastStepVariant[1] = phasePrio; f->lastStepVariant[2] = 5; f->lastStepVariant[3] = sp.mode ? 2 : (sp.inMask ? 3 : 1);
   if ((rc = vp_order_buffers(f)) != RFSGPU_OK) return rc;
   const StepLaunchOrder sloOn{f->vpOrderMode ? f->vpCost : nullptr, f->vpOrderMode ? f->vpOrder : nullptr}, sloOff{nullptr, nullptr};
@@ -3337,7 +3353,7 @@ int rfsgpu_batch_cycle_async(rfsgpu_filter *f, int predict, const double *x, con
   const StepOrderArg sord{sortCosts ? f->vpCost : nullptr, f->vpOrder, f->N, f->vpCost + f->Ncap, f->vpParity};
   if (sortCosts) f->vpParity ^= 1;
   if (murty_launch_batch(f->Q, f->MS, f->B, f->stream, A, normalize, f->hJobCount, sord) != 0) return fail(f, RFSGPU_ERR_HIP, "batch post kernel launch failed");
-  if (ks >= 0) HIPCHK(hipEventRecord(f->evStage[ks], f->stream));   // the pinned input slot is free once the step kernel has read it
+  if (ks >= 0) HIPCHK(hipEventRecord(f->stage.ev[ks], f->stream));   // the pinned input slot is free once the step kernel has read it
   f->cur ^= 1;   // (filters without an update had their mixture moved to the new slab by the step kernel)
   for (int b = 0; b < nF; b++)
     if (n_z[b] > 0) { f->bNZ[b] = n_z[b]; f->bResampled[b] = 0; }
@@ -3380,17 +3396,10 @@ int rfsgpu_batch_fastslam_cycle_async(rfsgpu_filter *f, int predict, const doubl
   int rc = batch_check(f, -1);
   if (rc != RFSGPU_OK) return rc;
   REFUSE_ON_MH_BATCH(f, "rfsgpu_batch_fastslam_cycle_async");
-  if (predict < -1 || predict > 1) return fail(f, RFSGPU_ERR_INVALID, "batch_fastslam_cycle: predict is RFSGPU_CYCLE_NO_PREDICT (-1), or 0 / 1 (the static landmark step; FastSLAM has no births)");
-  if (x_cov && cov_stride != 0 && cov_stride != 9) return fail(f, RFSGPU_ERR_INVALID, "batch_fastslam_cycle: cov_stride must be 0 or 9");
-  if (!n_z) return fail(f, RFSGPU_ERR_INVALID, "batch_fastslam_cycle: null measurement counts");
+  if ((rc = batch_check_call(f, BATCH_FS_CYCLE, predict, x_cov, cov_stride, n_z)) != RFSGPU_OK) return rc;
   const int nF = f->nF;
-  for (int b = 0; b < nF; b++) {
-    if (n_z[b] < 0 || n_z[b] > RFSGPU_MAX_Z) {
-      f->err = "batch_fastslam_cycle: filter " + std::to_string(b) + " has " + std::to_string(n_z[b]) + " measurements (0 ... RFSGPU_MAX_Z)";
-      return RFSGPU_ERR_INVALID;
-    }
-    if (n_z[b] > 0 && !z) return fail(f, RFSGPU_ERR_INVALID, "batch_fastslam_cycle: null measurement buffer");
-  }
+  for (int b = 0; b < nF; b++)
+    if ((rc = batch_check_filter(f, BATCH_FS_CYCLE, b, z, n_z)) != RFSGPU_OK) return rc;
   if (f->bKind == 1)
     return fail(f, RFSGPU_ERR_UNSUPPORTED, "batch_fastslam_cycle: this batch steps RB-PHD filters (rfsgpu_batch_cycle_async has run): a batch is of one kind");
   f->bKind = 2;
@@ -3398,53 +3407,13 @@ int rfsgpu_batch_fastslam_cycle_async(rfsgpu_filter *f, int predict, const doubl
   long long t0 = now_ns();
   if (!f->fsArena) HIPCHK(hipMalloc(&f->fsArena, (size_t)f->Ncap * fs_arena_bytes()));   // the Hungarian scratch of every slot of the batch, once
   batch_handle_wide(f, x, x_cov, cov_stride);
-  // per-cycle tables into a slot of the pinned ring, then to the device
-  unsigned char *h = nullptr;
-  int kb = 0;
-  if ((rc = batch_stage(f, &h, &kb)) != RFSGPU_OK) return rc;
-  FsBatchFilter *hf = reinterpret_cast<FsBatchFilter *>(h);
-  Params *hp = reinterpret_cast<Params *>(h + (size_t)nF * sizeof(FsBatchFilter));
-  double *hz = reinterpret_cast<double *>(h + (size_t)nF * (sizeof(FsBatchFilter) + sizeof(Params)));
-  if (f->bParamsDirty) {
-    for (int b = 0; b < nF; b++) hp[b] = f->bParamsHost[b] = batch_params(f, b);
-    HIPCHK(hipMemcpyAsync(f->dBParams, hp, (size_t)nF * sizeof(Params), hipMemcpyHostToDevice, f->stream));
-    f->bParamsDirty = false;
-  }
-  int zOff = 0;
-  for (int b = 0; b < nF; b++) {
-    FsBatchFilter &T = hf[b];
-    memset(&T, 0, sizeof T);
+  rc = batch_push_tables(f, f->dFsFilt, z, n_z, nullptr, 0, nullptr, [&](FsBatchFilter &T, int b) {
     T.F = fs_params_of(f->bFs[b], f->bParamsHost[b], 2, n_z[b]);
     T.pruneT = f->bFs[b].mapExistencePruneThreshold;
-    T.nZ = n_z[b];
-    T.zOff = zOff;
     T.prune = ((unsigned)n_z[b] >= f->bFs[b].pruningMeasurementsThreshold) ? 1 : 0;
-    if (n_z[b] > 0) memcpy(hz + zOff, z + (size_t)b * RFSGPU_MAX_Z * 2, (size_t)n_z[b] * 2 * sizeof(double));
-    zOff += 2 * n_z[b];
-  }
-  HIPCHK(hipMemcpyAsync(f->dFsFilt, hf, (size_t)nF * sizeof(FsBatchFilter), hipMemcpyHostToDevice, f->stream));
-  if (zOff) HIPCHK(hipMemcpyAsync(f->dBZ, hz, (size_t)zOff * sizeof(double), hipMemcpyHostToDevice, f->stream));
-  HIPCHK(hipEventRecord(f->evBStage[kb], f->stream));
-  // the host's new poses / covariances through a slot of the staging ring
-  if (x) {
-    double *hx = nullptr;
-    int ks = -1;
-    if ((rc = stage_slot(f, &hx, &ks)) != RFSGPU_OK) return rc;
-    memcpy(hx, x, (size_t)f->N * 3 * sizeof(double));
-    HIPCHK(hipMemcpyAsync(f->B.pose, hx, (size_t)f->N * 3 * sizeof(double), hipMemcpyHostToDevice, f->stream));
-    double *hc = hx + (size_t)f->Ncap * 3;
-    if (x_cov) {
-      const size_t n = cov_stride == 9 ? (size_t)f->N * 9 : 9;
-      memcpy(hc, x_cov, n * sizeof(double));
-      HIPCHK(hipMemcpyAsync(f->B.poseCov, hc, n * sizeof(double), hipMemcpyHostToDevice, f->stream));
-      f->poseCovZero = false;
-    } else if (!f->poseCovZero) {
-      memset(hc, 0, 9 * sizeof(double));
-      HIPCHK(hipMemcpyAsync(f->B.poseCov, hc, 9 * sizeof(double), hipMemcpyHostToDevice, f->stream));
-      f->poseCovZero = true;
-    }
-    HIPCHK(hipEventRecord(f->evStage[ks], f->stream));
-  }
+  });
+  if (rc != RFSGPU_OK) return rc;
+  if (x && (rc = batch_push_poses(f, x, x_cov, cov_stride)) != RFSGPU_OK) return rc;
   f->bBirthAlt = false;      // (no births here: the poses from before a propagation are not needed)
   FsBatchArg A{f->dFsFilt, f->dBParams, f->dBZ, f->dBErrFilter, f->nPer, predict >= 0 ? 1 : 0};
   const size_t b2 = fs_batch_lds_bytes(f->cap, 2), b1 = fs_batch_lds_bytes(f->cap, 1);
@@ -3549,16 +3518,10 @@ int rfsgpu_batch_fastslam_mh_cycle_async(rfsgpu_filter *f, int predict, const do
   int rc = batch_check(f, -1);
   if (rc != RFSGPU_OK) return rc;
   if (!f->mhBatch) return fail(f, RFSGPU_ERR_UNSUPPORTED, "batch_fastslam_mh_cycle: not a batch of multi-hypothesis FastSLAM filters (rfsgpu_create_batch_mh)");
-  if (predict < 0 || predict > 1) return fail(f, RFSGPU_ERR_INVALID, "batch_fastslam_mh_cycle: predict is 0 or 1 (the static landmark step; FastSLAM has no births)");
-  if (x_cov && cov_stride != 0 && cov_stride != 9) return fail(f, RFSGPU_ERR_INVALID, "batch_fastslam_mh_cycle: cov_stride must be 0 or 9");
-  if (!n_z || !u01) return fail(f, RFSGPU_ERR_INVALID, "batch_fastslam_mh_cycle: null measurement counts or draws");
+  if ((rc = batch_check_call(f, BATCH_MH_CYCLE, predict, x_cov, cov_stride, u01 ? n_z : nullptr)) != RFSGPU_OK) return rc;
   const int nF = f->nF, N = f->N, stride = f->nPer;
   for (int b = 0; b < nF; b++) {
-    if (n_z[b] < 0 || n_z[b] > RFSGPU_MAX_Z) {
-      f->err = "batch_fastslam_mh_cycle: filter " + std::to_string(b) + " has " + std::to_string(n_z[b]) + " measurements (0 ... RFSGPU_MAX_Z)";
-      return RFSGPU_ERR_INVALID;
-    }
-    if (n_z[b] > 0 && !z) return fail(f, RFSGPU_ERR_INVALID, "batch_fastslam_mh_cycle: null measurement buffer");
+    if ((rc = batch_check_filter(f, BATCH_MH_CYCLE, b, z, n_z)) != RFSGPU_OK) return rc;
     if (!(u01[b] >= 0.0 && u01[b] < 1.0)) {
       f->err = "batch_fastslam_mh_cycle: filter " + std::to_string(b) + ": u01 must lie in [0, 1)";
       return RFSGPU_ERR_INVALID;
@@ -3570,26 +3533,10 @@ int rfsgpu_batch_fastslam_mh_cycle_async(rfsgpu_filter *f, int predict, const do
   if (!f->mhArena) HIPCHK(hipMalloc(&f->mhArena, (size_t)N * L.total));          // every slot's table / Murty arena / assignments, once
   if (!f->mhcInts) HIPCHK(hipMalloc(&f->mhcInts, (size_t)4 * N * sizeof(int)));
   batch_handle_wide(f, x, x_cov, cov_stride);
-  unsigned char *h = nullptr;
-  int kb = 0;
-  if ((rc = batch_stage(f, &h, &kb)) != RFSGPU_OK) return rc;
-  MhBatchFilter *hf = reinterpret_cast<MhBatchFilter *>(h);
-  Params *hp = reinterpret_cast<Params *>(h + (size_t)nF * sizeof(MhBatchFilter));
-  double *hz = reinterpret_cast<double *>(h + (size_t)nF * (sizeof(MhBatchFilter) + sizeof(Params)));
-  if (f->bParamsDirty) {
-    for (int b = 0; b < nF; b++) hp[b] = f->bParamsHost[b] = batch_params(f, b);
-    HIPCHK(hipMemcpyAsync(f->dBParams, hp, (size_t)nF * sizeof(Params), hipMemcpyHostToDevice, f->stream));
-    f->bParamsDirty = false;
-  }
-  int zOff = 0;
-  for (int b = 0; b < nF; b++) {
-    MhBatchFilter &T = hf[b];
+  rc = batch_push_tables(f, f->dMhFilt, z, n_z, nullptr, 0, nullptr, [&](MhBatchFilter &T, int b) {
     const rfsgpu_fastslam_config &c = f->bFs[b];
-    memset(&T, 0, sizeof T);
     T.F = fs_params_of(c, f->bParamsHost[b], 2, n_z[b]);
     T.pruneT = c.mapExistencePruneThreshold;
-    T.nZ = n_z[b];
-    T.zOff = zOff;
     T.prune = ((unsigned)n_z[b] >= c.pruningMeasurementsThreshold) ? 1 : 0;
     T.kmax = (int)c.maxNDataAssocHypotheses;
     T.maxDiff = c.maxDataAssocLogLikelihoodDiff;
@@ -3600,31 +3547,9 @@ int rfsgpu_batch_fastslam_mh_cycle_async(rfsgpu_filter *f, int predict, const do
     T.nMax = (int)c.nParticlesMax;
     T.minUpdates = (int)c.minUpdatesBeforeResample;
     T.minMeasurements = (int)c.minMeasurementsBeforeResample;
-    if (n_z[b] > 0) memcpy(hz + zOff, z + (size_t)b * RFSGPU_MAX_Z * 2, (size_t)n_z[b] * 2 * sizeof(double));
-    zOff += 2 * n_z[b];
-  }
-  HIPCHK(hipMemcpyAsync(f->dMhFilt, hf, (size_t)nF * sizeof(MhBatchFilter), hipMemcpyHostToDevice, f->stream));
-  if (zOff) HIPCHK(hipMemcpyAsync(f->dBZ, hz, (size_t)zOff * sizeof(double), hipMemcpyHostToDevice, f->stream));
-  HIPCHK(hipEventRecord(f->evBStage[kb], f->stream));
-  if (x) {      // the host's new poses / covariances through a slot of the staging ring (every slot of every block)
-    double *hx = nullptr;
-    int ks = -1;
-    if ((rc = stage_slot(f, &hx, &ks)) != RFSGPU_OK) return rc;
-    memcpy(hx, x, (size_t)N * 3 * sizeof(double));
-    HIPCHK(hipMemcpyAsync(f->B.pose, hx, (size_t)N * 3 * sizeof(double), hipMemcpyHostToDevice, f->stream));
-    double *hc = hx + (size_t)f->Ncap * 3;
-    if (x_cov) {
-      const size_t n = cov_stride == 9 ? (size_t)N * 9 : 9;
-      memcpy(hc, x_cov, n * sizeof(double));
-      HIPCHK(hipMemcpyAsync(f->B.poseCov, hc, n * sizeof(double), hipMemcpyHostToDevice, f->stream));
-      f->poseCovZero = false;
-    } else if (!f->poseCovZero) {
-      memset(hc, 0, 9 * sizeof(double));
-      HIPCHK(hipMemcpyAsync(f->B.poseCov, hc, 9 * sizeof(double), hipMemcpyHostToDevice, f->stream));
-      f->poseCovZero = true;
-    }
-    HIPCHK(hipEventRecord(f->evStage[ks], f->stream));
-  }
+  });
+  if (rc != RFSGPU_OK) return rc;
+  if (x && (rc = batch_push_poses(f, x, x_cov, cov_stride)) != RFSGPU_OK) return rc;     // (every slot of every block)
   f->bBirthAlt = false;
   FsCycleState S0;      // filter 0's view: its slot arrays are the batch's, [N] each, holding slots local to each filter's block
   mhb_view(f, f->mhbBlock, 0, S0);
@@ -3757,7 +3682,7 @@ int rfsgpu_batch_resample_apply(rfsgpu_filter *f, const int *src_slot, const uns
   long long t0 = now_ns();
   double *hs;
   int ks;
-  if ((rc = stage_slot(f, &hs, &ks)) != RFSGPU_OK) return rc;
+  if ((rc = ring_acquire(f, f->stage, &hs, &ks)) != RFSGPU_OK) return rc;
   int *hsrc = reinterpret_cast<int *>(hs);
   int *hflag = hsrc + f->N;
   for (int b = 0; b < nF; b++) {
@@ -3775,7 +3700,7 @@ int rfsgpu_batch_resample_apply(rfsgpu_filter *f, const int *src_slot, const uns
   resample_gather_kernel<<<f->N, 256, 0, f->stream>>>(f->B, f->cur, hsrc, f->P.poseCovStride, 1);
   batch_reset_weights_kernel<<<(f->N + 255) / 256, 256, 0, f->stream>>>(f->B.weight, f->N, nPer, hflag);
   HIPCHK(hipGetLastError());
-  HIPCHK(hipEventRecord(f->evStage[ks], f->stream));
+  HIPCHK(hipEventRecord(f->stage.ev[ks], f->stream));
   const long long dtn = now_ns() - t0;
   f->timing.particleResample_wall += dtn;
   f->timing.particleResample_cpu += dtn;
@@ -3832,29 +3757,16 @@ int rfsgpu_batch_set_resampling(rfsgpu_filter *f, int filter, double eff_n, doub
   }
   return RFSGPU_OK;
 }
-// One slot of the device loop's pinned ring (as batch_stage; eight slots: two calls per cycle, four cycles)
-static int batch_loop_stage(rfsgpu_filter *f, unsigned char **h, int *k_out) {
-  const int k = f->bLoopNext;
-  f->bLoopNext = (k + 1) & 7;
-  const bool fresh = !f->hBLoop[k] || !f->evBLoop[k];
-  if (!f->hBLoop[k]) HIPCHK(hipHostMalloc(&f->hBLoop[k], (size_t)f->nF * std::max(sizeof(BatchMotion), std::max(sizeof(BatchPropIn), sizeof(BatchResIn)))));
-  if (!f->evBLoop[k]) HIPCHK(hipEventCreateWithFlags(&f->evBLoop[k], hipEventDisableTiming));
-  if (fresh) HIPCHK(hipStreamSynchronize(f->stream));
-  else HIPCHK(hipEventSynchronize(f->evBLoop[k]));
-  *h = f->hBLoop[k];
-  *k_out = k;
-  return RFSGPU_OK;
-}
 // The filters' motion parameters, when they have changed: through a slot of the pinned ring, like the per-call tables (nothing waits)
 static int batch_push_motion(rfsgpu_filter *f) {
   if (!f->bMotionDirty) return RFSGPU_OK;
   unsigned char *h = nullptr;
   int k = 0;
-  int rc = batch_loop_stage(f, &h, &k);
+  int rc = ring_acquire(f, f->bLoop, &h, &k);
   if (rc != RFSGPU_OK) return rc;
   memcpy(h, f->bMotion.data(), (size_t)f->nF * sizeof(BatchMotion));
   HIPCHK(hipMemcpyAsync(f->dBMotion, h, (size_t)f->nF * sizeof(BatchMotion), hipMemcpyHostToDevice, f->stream));
-  HIPCHK(hipEventRecord(f->evBLoop[k], f->stream));
+  HIPCHK(hipEventRecord(f->bLoop.ev[k], f->stream));
   f->bMotionDirty = false;
   return RFSGPU_OK;
 }
@@ -3875,7 +3787,7 @@ int rfsgpu_batch_propagate_async(rfsgpu_filter *f, const double *u, const double
   if ((rc = batch_push_motion(f)) != RFSGPU_OK) return rc;
   unsigned char *h = nullptr;
   int k = 0;
-  if ((rc = batch_loop_stage(f, &h, &k)) != RFSGPU_OK) return rc;
+  if ((rc = ring_acquire(f, f->bLoop, &h, &k)) != RFSGPU_OK) return rc;
   BatchPropIn *hi = reinterpret_cast<BatchPropIn *>(h);
   for (int b = 0; b < nF; b++) {
     BatchPropIn &I = hi[b];
@@ -3885,7 +3797,7 @@ int rfsgpu_batch_propagate_async(rfsgpu_filter *f, const double *u, const double
     if (I.pin) memcpy(I.pinPose, pin_pose + 3 * (size_t)b, 3 * sizeof(double));
   }
   HIPCHK(hipMemcpyAsync(f->dBPropIn, hi, (size_t)nF * sizeof(BatchPropIn), hipMemcpyHostToDevice, f->stream));
-  HIPCHK(hipEventRecord(f->evBLoop[k], f->stream));
+  HIPCHK(hipEventRecord(f->bLoop.ev[k], f->stream));
   // every particle gets its own pose covariance (handle-wide stride, as rfsgpu_batch_cycle_async sets it with x_cov [N][9])
   if (f->P.poseCovStride != 9) { f->P.poseCovStride = 9; f->bParamsDirty = true; }
   f->poseCovZero = false;
@@ -3903,15 +3815,12 @@ int rfsgpu_batch_resample_async(rfsgpu_filter *f, const int *n_z, unsigned long 
   int rc = batch_check(f, -1);
   if (rc != RFSGPU_OK) return rc;
   REFUSE_ON_MH_BATCH(f, "rfsgpu_batch_resample_async");
-  if (!n_z) return fail(f, RFSGPU_ERR_INVALID, "batch_resample: null measurement counts");
+  if ((rc = batch_check_call(f, BATCH_RESAMPLE, 0, nullptr, 0, n_z)) != RFSGPU_OK) return rc;
   const int nF = f->nF;
   if (f->nPer > RFSGPU_BATCH_RESAMPLE_MAX_PER_FILTER)
     return fail(f, RFSGPU_ERR_UNSUPPORTED, "batch_resample: more than RFSGPU_BATCH_RESAMPLE_MAX_PER_FILTER particles per filter (one workgroup resamples a filter)");
   for (int b = 0; b < nF; b++) {
-    if (n_z[b] < 0 || n_z[b] > RFSGPU_MAX_Z) {
-      f->err = "batch_resample: filter " + std::to_string(b) + " has " + std::to_string(n_z[b]) + " measurements (0 ... RFSGPU_MAX_Z)";
-      return RFSGPU_ERR_INVALID;
-    }
+    if ((rc = batch_check_filter(f, BATCH_RESAMPLE, b, nullptr, n_z)) != RFSGPU_OK) return rc;
     if (!f->bMotionSet[b] || !f->bResSet[b]) {
       f->err = "batch_resample: filter " + std::to_string(b) + (f->bResSet[b] ? " has no Philox key (rfsgpu_batch_set_motion_odometry)" : " has no resampling thresholds (rfsgpu_batch_set_resampling)");
       return RFSGPU_ERR_INVALID;
@@ -3934,7 +3843,7 @@ int rfsgpu_batch_resample_async(rfsgpu_filter *f, const int *n_z, unsigned long 
   if ((rc = batch_push_motion(f)) != RFSGPU_OK) return rc;
   unsigned char *h = nullptr;
   int k = 0;
-  if ((rc = batch_loop_stage(f, &h, &k)) != RFSGPU_OK) return rc;
+  if ((rc = ring_acquire(f, f->bLoop, &h, &k)) != RFSGPU_OK) return rc;
   BatchResIn *hi = reinterpret_cast<BatchResIn *>(h);
   for (int b = 0; b < nF; b++) {
     BatchResIn &I = hi[b];
@@ -3945,7 +3854,7 @@ int rfsgpu_batch_resample_async(rfsgpu_filter *f, const int *n_z, unsigned long 
     I.pad = 0;
   }
   HIPCHK(hipMemcpyAsync(f->dBResIn, hi, (size_t)nF * sizeof(BatchResIn), hipMemcpyHostToDevice, f->stream));
-  HIPCHK(hipEventRecord(f->evBLoop[k], f->stream));
+  HIPCHK(hipEventRecord(f->bLoop.ev[k], f->stream));
   batch_resample_kernel<<<nF, BATCH_LOOP_THREADS, 0, f->stream>>>(f->B.weight, f->BL, f->dBMotion, f->dBResIn, f->nPer, call);
   resample_gather_kernel<<<f->N, 256, 0, f->stream>>>(f->B, f->cur, f->BL.plan, f->P.poseCovStride, 1);
   HIPCHK(hipGetLastError());
@@ -4013,7 +3922,7 @@ static int metric_launch(rfsgpu_filter *f, const double *t, const double *gt_pos
   hipSetDevice(f->device);
   double *h = nullptr;
   int k = 0;
-  { const int rc = stage_slot(f, &h, &k); if (rc != RFSGPU_OK) return rc; }
+  { const int rc = ring_acquire(f, f->stage, &h, &k); if (rc != RFSGPU_OK) return rc; }
   for (int b = 0; b < nF; b++) {
     h[4 * b] = t ? t[b] : 0.0;
     for (int q = 0; q < 3; q++) h[4 * b + 1 + q] = gt_pose ? gt_pose[3 * b + q] : 0.0;
@@ -4027,7 +3936,7 @@ static int metric_launch(rfsgpu_filter *f, const double *t, const double *gt_pos
     map_metric_kernel<<<nF, 64, 0, f->stream>>>(f->B, f->cur, A);
   }
   HIPCHK(hipGetLastError());
-  HIPCHK(hipEventRecord(f->evStage[k], f->stream));
+  HIPCHK(hipEventRecord(f->stage.ev[k], f->stream));
   return RFSGPU_OK;
 }
 static int metric_args(rfsgpu_filter *f, const char *what, const double *t, double cutoff, double order) {
