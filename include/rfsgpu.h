@@ -45,7 +45,8 @@
  *   [fastslam] FastSLAM / MH-FastSLAM on the same handle, the optional device-side Ackerman propagation, rfsgpu_mat_perm;
  *   [batch]    many independent 2-D filters in one handle, stepped together in one launch chain;
  *   [metric]   per-step OSPA / COLA map error and pose error computed on the device, kept in a device-side log;
- *   [resample] ParticleFilter::resample for an ordinary handle of any size on the device, without a host stop.
+ *   [resample] ParticleFilter::resample for an ordinary handle of any size on the device, without a host stop;
+ *   [sensor]   the simulator's range-bearing sensor of every filter of an RB-PHD batch drawn on the device, for batch sweeps.
  * A maintainer wiring the reference to the library reads the CORE entries and INTEGRATION.md; nothing optional is required
  * for correct results.
  */
@@ -950,6 +951,76 @@ int rfsgpu_resample_async(rfsgpu_filter *f, double eff_n, double eff_n_percent, 
  * a copy of (:474), k itself where the particle stayed (case 1, :465) or nothing fired.  Any pointer may be NULL; max_n >= the
  * count when plan is given. */
 int rfsgpu_last_resample(rfsgpu_filter *f, int *fired, double *n_eff, int *n_after, int *plan, int max_n);
+
+/* ---- [sensor] every filter's scan drawn on the device, for batches of RB-PHD filters (outside the STABLE CORE) --------------------
+ * generateMeasurements of the reference's 2-D simulator (src/rbphdslam2dSim.cpp:283-366) for one time step and every filter of a
+ * batch (rfsgpu_create_batch handles stepped by rfsgpu_batch_cycle_async) in one launch: per step the host hands over one ground-truth
+ * pose per filter, the device draws each filter's scan into the batch's measurement table and writes the cycle's per-filter record,
+ * and the cycle and the resampling tail read both there.  A batch run is then
+ *   rfsgpu_batch_propagate_async -> rfsgpu_batch_sense_async -> rfsgpu_batch_cycle_sensed_async -> rfsgpu_batch_resample_sensed_async
+ * per step and the host builds no measurement table.
+ * Random numbers: Philox4x32-10 under the SENSOR's 64-bit key (low word k0, high word k1) with counter
+ * (index, block | attempt << 8, call low word, call high word):
+ *   block 3, index = landmark m:  g = (rad cos ang, rad sin ang) with rad = sqrt(-2 ln u1), ang = 2 pi u2, u in (0, 1] from 53 bits
+ *                                 of two words each (the Box-Muller form of rfsgpu_batch_propagate_async);
+ *   block 4, index = landmark m:  the detection draw, v = (53 bits of words 0, 1) / 2^53 in [0, 1), as every draw below;
+ *   block 5, index = 0:           the clutter-count draw;
+ *   block 6, index = clutter j:   attempt a = 0, 1, ... (in bits 8 and up of the block word) of point j's range draw;
+ *   block 7, index = clutter j:   point j's bearing draw.
+ * Propagation uses blocks 0 and 1 and the resampling draw block 2, so one key may serve a filter's motion and its sensor; every draw is
+ * a pure function of (key, call, block, index, attempt): a filter's scan depends neither on its place in the batch nor on the others.
+ * The scan of one filter, in this order:
+ *   detections (:321-342, MeasurementModel::sample / MeasurementModel_RngBrg::measure): a landmark whose TRUE range lies in
+ *     [rangeLimMin, rangeLimMax] gets z = (range, bearing wrapped to [-pi, pi]) + L g, L the lower Cholesky factor of R (the bearing is
+ *     not wrapped again); it is kept when the NOISY range lies in the limits and v <= probabilityOfDetection.  Kept detections stand
+ *     in landmark order;
+ *   clutter (:344-362): the count is the first n with v <= CMF[n] of the 100-entry Poisson table of mean
+ *     uniformClutterIntensity * 2 pi (rangeLimMax - rangeLimMin), computed on the host by the loop of :294-306 -- and 99 where no
+ *     n < 99 does (the reference walks off its table there).  Point j has r = v rangeLimMax, drawn again (next attempt) while
+ *     r < rangeLimMin -- after 64 attempts the last draw is mapped into the limits, r = rangeLimMin + v (rangeLimMax - rangeLimMin)
+ *     (probability (rangeLimMin / rangeLimMax)^64) -- and b = v 2 pi - pi.
+ * A set beyond max_nz is cut to its first max_nz entries (detections before clutter) and reported through the device error word: the
+ * next synchronising call returns RFSGPU_ERR_CAPACITY once, and rfsgpu_last_error names the lowest such filter and its scan.
+ * Every call of the section returns RFSGPU_ERR_UNSUPPORTED, with a message and the state untouched, on an ordinary handle, a shard of
+ * an rfsgpu_group, a batch of FastSLAM filters and a batch of multi-hypothesis FastSLAM filters: their per-filter records carry
+ * host-computed, count-dependent parameters.
+ *
+ * Filter `filter`'s (-1: every filter's) simulated sensor: model = ITS R, probabilityOfDetection, uniformClutterIntensity and range
+ * limits (rangeLimBuffer is not read; the filter's own model, rfsgpu_batch_configure, usually has an inflated R), landmarks_xy
+ * [n_landmarks][2] with 0 <= n_landmarks <= RFSGPU_SENSOR_MAX_LANDMARKS, 1 <= max_nz <= RFSGPU_MAX_Z, seed the sensor's Philox key.
+ * RFSGPU_ERR_INVALID with a message: R not symmetric positive definite, rangeLimMin >= rangeLimMax, probabilityOfDetection outside
+ * [0, 1], a negative clutter intensity, a clutter mean whose table is not finite, a landmark that is not finite.  Synchronising. */
+#define RFSGPU_SENSOR_MAX_LANDMARKS 512
+int rfsgpu_batch_set_sensor(rfsgpu_filter *f, int filter, const rfsgpu_rngbrg_config *model, const double *landmarks_xy, int n_landmarks,
+                            int max_nz, unsigned long long seed);
+/* Draw every filter's scan of call `call` at gt_pose [n_filters][3] (finite, |heading| <= 64 rad) and write this cycle's records:
+ * the count, the set's place, the count of the filter's last non-empty update (its births) and the evaluation-point cap and weighting
+ * switch of its configuration.  One kernel, one wavefront per filter; the poses travel through the batch's pinned ring and nothing
+ * waits for the GPU.  A filter without rfsgpu_batch_set_sensor: RFSGPU_ERR_INVALID, naming it. */
+int rfsgpu_batch_sense_async(rfsgpu_filter *f, const double *gt_pose, unsigned long long call);
+/* rfsgpu_batch_cycle_async on the sets and records the last rfsgpu_batch_sense_async left (predict, x, x_cov, cov_stride, normalize as
+ * there).  The launch is sized for what that sense call could write: the filters' largest max_nz and evaluation-point cap AT THE SENSE
+ * CALL; results do not depend on the max_nz bound.  The records carry each filter's evaluation-point cap and weighting switch as the
+ * sense call found them, and the step kernel lays out its LDS by them: a rfsgpu_batch_configure between the sense call and the cycle
+ * that changes either (importanceWeightingEvalPointCount, useClusterProcess) makes the cycle return RFSGPU_ERR_INVALID, naming the
+ * filter, until the next rfsgpu_batch_sense_async; any other field may change and holds from this cycle on, as with the host-fed
+ * cycle.  A rfsgpu_batch_set_sensor between the two, for any filter, ends the sense call's validity in the same way.  The call puts the handle on the
+ * device route, as the first rfsgpu_batch_resample_async does (ids, resampleOccured_ and the inheritance of the unused-measurement
+ * lists on the device), and from the first sensed cycle on the count of each filter's last update lives on the device too: the
+ * host-fed rfsgpu_batch_cycle_async and rfsgpu_batch_resample_async then return RFSGPU_ERR_UNSUPPORTED on this handle.  (Host-fed
+ * cycles BEFORE the first sensed one are allowed: their counts move to the device.)  RFSGPU_ERR_INVALID, naming the filter: no
+ * rfsgpu_batch_sense_async since the last cycle of either kind, a filter without a sensor.  Beyond
+ * RFSGPU_BATCH_RESAMPLE_MAX_PER_FILTER particles per filter: RFSGPU_ERR_UNSUPPORTED. */
+int rfsgpu_batch_cycle_sensed_async(rfsgpu_filter *f, int predict, const double *x, const double *x_cov, int cov_stride, int normalize);
+/* rfsgpu_batch_resample_async with each filter's n_z taken from its record on the device.  After the sensed cycle and before the next
+ * rfsgpu_batch_sense_async (else RFSGPU_ERR_INVALID: the records would be another cycle's). */
+int rfsgpu_batch_resample_sensed_async(rfsgpu_filter *f, unsigned long long call);
+/* The sets of the last rfsgpu_batch_sense_async: z [n_filters][RFSGPU_MAX_Z][2] (zeros beyond a filter's set), n_z [n_filters].
+ * Synchronising, for tests and logging; a scan that was cut is reported here like by any synchronising call, with the outputs filled. */
+int rfsgpu_batch_last_scan(rfsgpu_filter *f, double *z, int *n_z);
+/* [test] Bytes of LDS that a workgroup of the step kernel had in the last cycle of this batch (host-fed or sensed; 0 before the
+ * first) -- so that a test can say that two max_nz bounds gave two launch sizes and the same results.  Any batch; never waits. */
+int rfsgpu_batch_last_cycle_lds(rfsgpu_filter *f, long long *bytes);
 
 #ifdef __cplusplus
 }

@@ -142,6 +142,7 @@ ABI_SYMBOLS = [
     "create_batch_mh", "batch_fastslam_mh_cycle_async", "batch_fastslam_last_cycle", "batch_live_counts", "batch_mh_serve_metrics",
     "set_ground_truth", "error_log_create", "error_log_reset", "step_error_async", "error_log_read", "step_error", "get_map_estimate",
     "resample_async", "last_resample", "get_pose_covs",
+    "batch_set_sensor", "batch_sense_async", "batch_cycle_sensed_async", "batch_resample_sensed_async", "batch_last_scan", "batch_last_cycle_lds",
 ]
 
 _dp = np.ctypeslib.ndpointer(dtype=np.float64, flags="C_CONTIGUOUS")
@@ -866,6 +867,58 @@ class CBatch(CFilter):
         out = np.zeros(self.n_filters, dtype=np.int64)
         self._call("batch_resample_counts", self._ptr(out))
         return out
+
+    # -- the device sensor ([sensor] in include/rfsgpu.h: every filter's scan drawn on the device) -----------------------------
+    def set_sensor(self, b, R, Pd, clutter, rmax, rmin, landmarks, max_nz=MAX_Z, seed=0):
+        """rfsgpu_batch_set_sensor: filter b's (None: every filter's) simulated sensor -- ITS noise R [2, 2], Pd, clutter intensity and
+        range limits -- the landmarks [n, 2] it sees, the largest set it may deliver and its Philox key."""
+        m = RngBrgConfig()
+        R = _f64(R, (4,))
+        for k in range(4):
+            m.R[k] = R[k]
+        m.probabilityOfDetection, m.uniformClutterIntensity = float(Pd), float(clutter)
+        m.rangeLimMax, m.rangeLimMin, m.rangeLimBuffer = float(rmax), float(rmin), 0.0
+        lm = _f64(landmarks).reshape(-1, 2) if np.size(landmarks) else np.zeros((0, 2))
+        self._call("batch_set_sensor", C.c_int(-1 if b is None else int(b)), C.byref(m), self._ptr(lm) if len(lm) else C.c_void_p(None), C.c_int(len(lm)),
+                   C.c_int(int(max_nz)), C.c_ulonglong(int(seed) & 0xFFFFFFFFFFFFFFFF))
+
+    def sense_async(self, gt_pose, call):
+        """rfsgpu_batch_sense_async: gt_pose [n_filters, 3]; every filter's scan of call `call` is drawn on the device."""
+        g = _f64(gt_pose, (self.n_filters, 3))
+        self._call("batch_sense_async", self._ptr(g), C.c_ulonglong(int(call)))
+
+    def cycle_sensed_async(self, predict, poses=None, pose_cov=None, normalize=True):
+        """rfsgpu_batch_cycle_sensed_async: batch_cycle_async on the sets the last sense_async left on the device."""
+        x = None if poses is None else _f64(poses, (self.n, 3))
+        stride = 0
+        cv = None
+        if pose_cov is not None:
+            cv = _f64(pose_cov)
+            assert cv.size in (9, 9 * self.n)
+            stride = 0 if cv.size == 9 else 9
+        self._call("batch_cycle_sensed_async", C.c_int(-1 if predict is None else (1 if predict else 0)), C.c_void_p(None) if x is None else self._ptr(x),
+                   C.c_void_p(None) if cv is None else self._ptr(cv), C.c_int(stride), C.c_int(1 if normalize else 0))
+
+    def resample_sensed_async(self, call):
+        """rfsgpu_batch_resample_sensed_async: resample_async with the measurement counts the device holds."""
+        self._call("batch_resample_sensed_async", C.c_ulonglong(int(call)))
+
+    def last_scan(self):
+        """The sets of the last sense_async as a list of [n_z, 2] arrays, one per filter (synchronising)."""
+        z = np.zeros((self.n_filters, MAX_Z, 2))
+        nz = np.zeros(self.n_filters, dtype=np.int32)
+        try:
+            self._call("batch_last_scan", self._ptr(z), self._ptr(nz))
+        except EngineError as e:
+            e.scans = [z[b, : nz[b]].copy() for b in range(self.n_filters)]      # (a scan that was cut: the sets as delivered ride on the error)
+            raise
+        return [z[b, : nz[b]].copy() for b in range(self.n_filters)]
+
+    def last_cycle_lds(self):
+        """Bytes of LDS a workgroup of the step kernel had in the batch's last cycle (0 before the first)."""
+        out = C.c_longlong(0)
+        self._call("batch_last_cycle_lds", C.byref(out))
+        return int(out.value)
 
     def n_filters_abi(self):
         fn = self._fn("n_filters")

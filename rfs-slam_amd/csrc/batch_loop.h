@@ -105,7 +105,7 @@ __device__ __forceinline__ int batch_block_exscan(int v, int *sc) {
 // sample point, the first-occurrence flags and the two compactions by all lanes), ids, weights, resampleOccured_.  The mixtures
 // and poses move afterwards (resample_gather_kernel on S.plan: slots that keep themselves exit at once).
 __global__ __launch_bounds__(BATCH_LOOP_THREADS) void batch_resample_kernel(double *weight, BatchLoopState S, const BatchMotion *mot, const BatchResIn *in,
-                                                                            int nPer, unsigned long long call) {
+                                                                            int nPer, unsigned long long call, const BatchFilter *filt) {
   __shared__ double cum[BATCH_LOOP_MAX_PER_FILTER];     // the weights, then their running sum
   __shared__ double sp[BATCH_LOOP_MAX_PER_FILTER];      // the sample points
   __shared__ int sidx[BATCH_LOOP_MAX_PER_FILTER];       // the particle each sample point falls on
@@ -115,7 +115,8 @@ __global__ __launch_bounds__(BATCH_LOOP_THREADS) void batch_resample_kernel(doub
   __shared__ int sFire;
   const int b = blockIdx.x, t = threadIdx.x, n = nPer, lo = b * nPer;
   if (n > BATCH_LOOP_MAX_PER_FILTER) return;            // (refused by the host)
-  const BatchResIn I = in[b];
+  BatchResIn I = in[b];
+  if (filt) I.nZ = filt[b].nZ;      // (rfsgpu_batch_resample_sensed_async: the count of the set the device drew; null: the host's)
   for (int j = t; j < n; j += BATCH_LOOP_THREADS) { cum[j] = weight[lo + j]; sampled[j] = 0; }
   __syncthreads();
   if (t == 0) {
@@ -193,8 +194,9 @@ __global__ __launch_bounds__(BATCH_LOOP_THREADS) void batch_resample_kernel(doub
 // a LOWER slot what that one holds after its own birth step -- nothing once the filter has had an update (nZprev > 0: its births
 // consume the whole list), else what it inherited in turn (a serial walk, by one lane).  One workgroup per filter, with the
 // particle ids and the resampleOccured_ flags where the device route left them.  The flag falls when this cycle updates the filter.
+// prevCount (null: the host keeps it): the count of each filter's last update, which rfsgpu_batch_sense_async's records carry as nZprev.
 __global__ __launch_bounds__(BATCH_LOOP_THREADS) void batch_inherit_dev_kernel(unsigned long long *mask, const int *ppid, int *resampled, const BatchFilter *filt,
-                                                                               int nPer, int doInherit) {
+                                                                               int nPer, int doInherit, int *prevCount) {
   __shared__ unsigned long long before[BATCH_LOOP_MAX_PER_FILTER];
   __shared__ int par[BATCH_LOOP_MAX_PER_FILTER];
   __shared__ int src[BATCH_LOOP_MAX_PER_FILTER];
@@ -221,4 +223,5 @@ __global__ __launch_bounds__(BATCH_LOOP_THREADS) void batch_inherit_dev_kernel(u
   }
   __syncthreads();
   if (t == 0 && nZ > 0 && r) resampled[b] = 0;
+  if (t == 0 && nZ > 0 && prevCount) prevCount[b] = nZ;     // (a sensed cycle, batch_sensor.h: the next sense call's nZprev)
 }

@@ -29,6 +29,7 @@
 #include "motion.h"
 #include "map_metric.h"
 #include "batch_loop.h"
+#include "batch_sensor.h"
 #include "resample_plan.h"
 
 namespace {
@@ -218,7 +219,23 @@ struct rfsgpu_filter {
   BatchPropIn *dBPropIn = nullptr;             // [nF]
   BatchResIn *dBResIn = nullptr;               // [nF]
   BatchLoopState BL{};
-  PinnedRing bLoop;                            // ring of the two calls' per-filter inputs (eight blocks: two calls per cycle, four cycles)
+  PinnedRing bLoop;                            // ring of the loop calls' per-filter inputs, a block per call (eight blocks: propagate + resample, four cycles; with a sense call three per cycle, 2 2/3 cycles)
+  // the sensor of a batch (batch_sensor.h): every filter's scan drawn on the device
+  std::vector<char> bSensorSet;                // rfsgpu_batch_set_sensor has been called for the filter
+  std::vector<int> bSensorMaxNz;               // [nF] its max_nz
+  std::vector<int> bSensorCaps;                // [nF][2] evalCap, useW as the device table holds them (-1: not staged yet)
+  BatchSensor *dBSensor = nullptr;             // [nF]
+  double *dBSensorLm = nullptr;                // [nF][SENSOR_MAX_LANDMARKS][2]
+  double *dBSensorPose = nullptr;              // [nF][3]
+  int *dBSensorCaps = nullptr;                 // [nF][2]
+  int *dBSensorPrev = nullptr;                 // [nF] BatchSensorArg::prevCount
+  int *dBSensorErrFilter = nullptr;            // [1] BatchSensorArg::errFilter
+  bool bSenseFresh = false;                    // a sense call has run since the last cycle and no rfsgpu_batch_set_sensor since: the records and sets on the device are this cycle's
+  long long bLastCycleLds = 0;                 // bytes of LDS a workgroup of the last batch cycle's step kernel had (rfsgpu_batch_last_cycle_lds)
+  int bSenseNzMax = 0, bSenseEcMax = 1;       // the largest max_nz and evalCap that sense call's records can carry: the sensed cycle's launch is sized for them
+  bool bScanHeld = false;                      // the records and sets on the device are a sense call's (no host-fed cycle has written over them): rfsgpu_batch_last_scan may read them
+  bool bSensedTail = false;                   // a sensed cycle has run since the last sense call: rfsgpu_batch_resample_sensed_async may read its records
+  bool bSensed = false;                        // a sensed cycle has run on this handle: nZprev lives on the device, the host-fed cycle and resampling refuse
   // a batch of FastSLAM filters (rfsgpu_batch_fastslam_cycle_async; fastslam.h FsBatchArg)
   int bKind = 0;                               // what the batch steps: 0 not decided yet, 1 RB-PHD filters, 2 FastSLAM filters (the first cycle call decides), 3 multi-hypothesis FastSLAM filters (rfsgpu_create_batch_mh decides)
   std::vector<rfsgpu_fastslam_config> bFs;     // [nF]
@@ -422,6 +439,7 @@ static int check_device_errors(rfsgpu_filter *f) {
   add(ERRBIT_EVALPTS, RFSGPU_ERR_UNSUPPORTED, "more than RFSGPU_MAX_EVAL evaluation points requested");
   add(ERRBIT_BIRTHLIST, RFSGPU_ERR_UNSUPPORTED, "a particle's birth-candidate / landmark-candidate list outgrew RFSGPU_MAX_CANDIDATES");
   add(ERRBIT_COLLECTIVE, RFSGPU_ERR_UNSUPPORTED, "collective hand-over timed out: the sequence number of the weight all-reduce was not published within 0.5 s (rfsgpu_step_async_trailing / rfsgpu_collective_gate / _publish)");
+  add(ERRBIT_SCAN, RFSGPU_ERR_CAPACITY, "a sensed scan outgrew its sensor's max_nz and was cut to its first max_nz entries (rfsgpu_batch_set_sensor)");
   if (code != RFSGPU_OK && f->batch) msg += batch_error_note(f, e);
   if (code != RFSGPU_OK) { f->err = msg; return code; }
   return fail(f, RFSGPU_ERR_HIP, "unknown device error flag");
@@ -583,6 +601,7 @@ void rfsgpu_destroy(rfsgpu_filter *f) {
   hipFree(f->dMhFilt); hipFree(f->mhbBlock); if (f->hMhbBlock) hipHostFree(f->hMhbBlock);
   hipFree(f->dBMotion); hipFree(f->dBPropIn); hipFree(f->dBResIn); hipFree(f->BL.counters); hipFree(f->BL.nResamples); hipFree(f->BL.resampled);
   hipFree(f->BL.fired); hipFree(f->BL.nEff); hipFree(f->BL.plan); hipFree(f->BL.pid); hipFree(f->BL.ppid);
+  hipFree(f->dBSensor); hipFree(f->dBSensorLm); hipFree(f->dBSensorPose); hipFree(f->dBSensorCaps); hipFree(f->dBSensorPrev); hipFree(f->dBSensorErrFilter);
   hipFree(f->dGtXY); hipFree(f->dGtSeen); hipFree(f->dGtN); hipFree(f->dErrLog); hipFree(f->dErrRow);
   if (f->hErr) hipHostFree(f->hErr);
   if (f->hJobCount) hipHostFree(f->hJobCount);
@@ -3046,6 +3065,13 @@ static std::string batch_error_note(rfsgpu_filter *f, int e) {
     add(b >= 0 ? "evaluation points beyond RFSGPU_MAX_EVAL in filter " + std::to_string(b) : std::string("evaluation points beyond RFSGPU_MAX_EVAL"));
   }
   if (e & (ERRBIT_MURTY | ERRBIT_MURTY_POOL)) add("raised by the Murty-200 post kernel, which all filters share");
+  if (e & ERRBIT_SCAN) {
+    int b = INT_MAX;
+    const int none = INT_MAX;
+    if (f->dBSensorErrFilter && hipMemcpy(&b, f->dBSensorErrFilter, sizeof(int), hipMemcpyDeviceToHost) == hipSuccess)
+      hipMemcpy(f->dBSensorErrFilter, &none, sizeof(int), hipMemcpyHostToDevice);
+    add(b >= 0 && b < f->nF ? "scan of filter " + std::to_string(b) + " beyond max_nz" : std::string("scan beyond max_nz, filter not identified"));
+  }
   return note.empty() ? note : note + ")";
 }
 static void batch_set_all(rfsgpu_filter *f) {
@@ -3107,7 +3133,7 @@ static int batch_fail(rfsgpu_filter *f, const BatchCall &C, const std::string &m
 static int batch_check_call(rfsgpu_filter *f, const BatchCall &C, int predict, const double *x_cov, int cov_stride, const void *counts) {
   if (C.predictIs && (predict < C.predictMin || predict > 1)) return batch_fail(f, C, std::string("predict is ") + C.predictIs);
   if (C.predictIs && x_cov && cov_stride != 0 && cov_stride != 9) return batch_fail(f, C, "cov_stride must be 0 or 9");
-  if (!counts) return batch_fail(f, C, C.nullCounts);
+  if (C.nullCounts && !counts) return batch_fail(f, C, C.nullCounts);     // (nullCounts null: a call without a counts array)
   return RFSGPU_OK;
 }
 // ... and filter b's measurement set; the caller's own per-filter checks follow it in the caller's loop, so that the first offending
@@ -3156,6 +3182,22 @@ static int batch_push_tables(rfsgpu_filter *f, Rec *dRec, const double *z, const
   HIPCHK(hipEventRecord(f->bStage.ev[k], f->stream));
   return RFSGPU_OK;
 }
+// The Params table alone, when it is behind the configuration (a sensed cycle: the records and sets are on the device already)
+static int batch_push_params(rfsgpu_filter *f) {
+  if (!f->bParamsDirty) return RFSGPU_OK;
+  unsigned char *h = nullptr;
+  int k = 0;
+  { const int rc = ring_acquire(f, f->bStage, &h, &k); if (rc != RFSGPU_OK) return rc; }
+  Params *hp = reinterpret_cast<Params *>(h + (size_t)f->nF * sizeof(BatchFilter));     // (where batch_push_tables keeps it in the block)
+  for (int b = 0; b < f->nF; b++) hp[b] = f->bParamsHost[b] = batch_params(f, b);
+  HIPCHK(hipMemcpyAsync(f->dBParams, hp, (size_t)f->nF * sizeof(Params), hipMemcpyHostToDevice, f->stream));
+  HIPCHK(hipEventRecord(f->bStage.ev[k], f->stream));
+  f->bParamsDirty = false;
+  return RFSGPU_OK;
+}
+static int batch_cycle_core(rfsgpu_filter *f, int predict, const double *x, const double *x_cov, int cov_stride, const double *z, const int *n_z, int normalize);
+static int batch_resample_core(rfsgpu_filter *f, const BatchCall &C, const int *n_z, unsigned long long call);
+static int batch_enter_dev_route(rfsgpu_filter *f);
 extern "C" {
 // The host's new poses / covariances of a batch by copy command, through a block of the staging ring (batch_handle_wide has the stride)
 static int batch_push_poses(rfsgpu_filter *f, const double *x, const double *x_cov, int cov_stride) {
@@ -3222,6 +3264,19 @@ int rfsgpu_create_batch(rfsgpu_filter **out, int model, int n_filters, int n_per
   if (ok) ok &= hipMemset(f->BL.resampled, 0, (size_t)n_filters * sizeof(int)) == hipSuccess;
   if (ok) ok &= hipMemset(f->BL.fired, 0, (size_t)n_filters * sizeof(int)) == hipSuccess;
   if (ok) ok &= hipMemset(f->BL.nEff, 0, (size_t)n_filters * sizeof(double)) == hipSuccess;
+  // the sensor's tables (batch_sensor.h)
+  f->bSensorSet.assign(n_filters, 0);
+  f->bSensorMaxNz.assign(n_filters, 0);
+  f->bSensorCaps.assign((size_t)2 * n_filters, -1);
+  ok &= hipMalloc(&f->dBSensor, (size_t)n_filters * sizeof(BatchSensor)) == hipSuccess;
+  ok &= hipMalloc(&f->dBSensorLm, (size_t)n_filters * SENSOR_MAX_LANDMARKS * 2 * sizeof(double)) == hipSuccess;
+  ok &= hipMalloc(&f->dBSensorPose, (size_t)n_filters * 3 * sizeof(double)) == hipSuccess;
+  ok &= hipMalloc(&f->dBSensorCaps, (size_t)n_filters * 2 * sizeof(int)) == hipSuccess;
+  ok &= hipMalloc(&f->dBSensorPrev, (size_t)n_filters * sizeof(int)) == hipSuccess;
+  ok &= hipMalloc(&f->dBSensorErrFilter, sizeof(int)) == hipSuccess;
+  if (ok) ok &= hipMemset(f->dBSensor, 0, (size_t)n_filters * sizeof(BatchSensor)) == hipSuccess;
+  if (ok) ok &= hipMemset(f->dBSensorPrev, 0, (size_t)n_filters * sizeof(int)) == hipSuccess;
+  if (ok) { const int none = INT_MAX; ok &= hipMemcpy(f->dBSensorErrFilter, &none, sizeof(int), hipMemcpyHostToDevice) == hipSuccess; }
   if (!ok) { rfsgpu_destroy(f); return RFSGPU_ERR_HIP; }
   *out = f;
   return RFSGPU_OK;
@@ -3252,17 +3307,35 @@ int rfsgpu_batch_cycle_async(rfsgpu_filter *f, int predict, const double *x, con
   if (rc != RFSGPU_OK) return rc;
   REFUSE_ON_MH_BATCH(f, "rfsgpu_batch_cycle_async");
   if ((rc = batch_check_call(f, BATCH_CYCLE, predict, x_cov, cov_stride, n_z)) != RFSGPU_OK) return rc;
-  const int nF = f->nF, nPer = f->nPer;
-  int nZmax = 0, ecMax = 1;
-  for (int b = 0; b < nF; b++) {
+  for (int b = 0; b < f->nF; b++) {
     if ((rc = batch_check_filter(f, BATCH_CYCLE, b, z, n_z)) != RFSGPU_OK) return rc;
     if (f->bCfg[b].birthGaussianMeasurementCountThreshold != 1u)
       return fail(f, RFSGPU_ERR_UNSUPPORTED, "batch_cycle: a filter batch takes immediate births only (birthGaussianMeasurementCountThreshold 1)");
-    nZmax = std::max(nZmax, n_z[b]);
   }
   if (f->bKind == 2)
     return fail(f, RFSGPU_ERR_UNSUPPORTED, "batch_cycle: this batch steps FastSLAM filters (rfsgpu_batch_set_fastslam_config or rfsgpu_batch_fastslam_cycle_async has run): a batch is of one kind");
+  if (f->bSensed)
+    return fail(f, RFSGPU_ERR_UNSUPPORTED, "batch_cycle: this batch has run a sensed cycle (rfsgpu_batch_cycle_sensed_async): the count of each filter's last update lives on the device, the host-fed cycle no longer knows it");
   f->bKind = 1;
+  return batch_cycle_core(f, predict, x, x_cov, cov_stride, z, n_z, normalize);
+}
+// eval_cap() of filter b's configuration, as its BatchFilter record carries it
+static int batch_eval_cap(const rfsgpu_filter *f, int b) {
+  int c = f->bCfg[b].importanceWeightingEvalPointCount;
+  if (c < 0 || c > RFSGPU_MAX_EVAL) c = RFSGPU_MAX_EVAL;
+  return c < 1 ? 1 : c;
+}
+// The cycle behind rfsgpu_batch_cycle_async (n_z given: the host's sets and records go to the device first) and
+// rfsgpu_batch_cycle_sensed_async (n_z null: the sets and records are where the last rfsgpu_batch_sense_async left them, and the launch
+// is sized for the sensors' largest max_nz).  The arguments have been checked.
+static int batch_cycle_core(rfsgpu_filter *f, int predict, const double *x, const double *x_cov, int cov_stride, const double *z, const int *n_z, int normalize) {
+  const bool sensed = n_z == nullptr;
+  const int nF = f->nF, nPer = f->nPer;
+  int rc = RFSGPU_OK, nZmax = 0, ecMax = 1;
+  // (a sensed cycle: the step kernel takes nZ and evalCap from the records the sense call wrote, so the launch is sized by what that
+  //  call could write; rfsgpu_batch_cycle_sensed_async has checked that the sensors and the configuration still say the same)
+  if (sensed) { nZmax = f->bSenseNzMax; ecMax = f->bSenseEcMax; }
+  else for (int b = 0; b < nF; b++) nZmax = std::max(nZmax, n_z[b]);
   hipSetDevice(f->device);
   long long t0 = now_ns();
   batch_handle_wide(f, x, x_cov, cov_stride);   // (the pose covariance stride: handle-wide, as rfsgpu_cycle_async sets it)
@@ -3287,13 +3360,11 @@ int rfsgpu_batch_cycle_async(rfsgpu_filter *f, int predict, const double *x, con
     }
   }
   // per-cycle tables (the host route's inheritance table at their tail)
-  rc = batch_push_tables(f, f->dBFilt, z, n_z, src.empty() ? nullptr : src.data(), (size_t)f->N * sizeof(int), f->dBInhSrc, [&](BatchFilter &F, int b) {
+  if (!sensed) for (int b = 0; b < nF; b++) ecMax = std::max(ecMax, batch_eval_cap(f, b));
+  if (sensed) rc = batch_push_params(f);
+  else rc = batch_push_tables(f, f->dBFilt, z, n_z, src.empty() ? nullptr : src.data(), (size_t)f->N * sizeof(int), f->dBInhSrc, [&](BatchFilter &F, int b) {
     F.nZprev = f->bNZ[b];
-    int c = f->bCfg[b].importanceWeightingEvalPointCount;
-    if (c < 0 || c > RFSGPU_MAX_EVAL) c = RFSGPU_MAX_EVAL;
-    if (c < 1) c = 1;
-    F.evalCap = c;
-    ecMax = std::max(ecMax, c);
+    F.evalCap = batch_eval_cap(f, b);
     F.useW = f->bCfg[b].useClusterProcess ? 0 : 1;
   });
   if (rc != RFSGPU_OK) return rc;
@@ -3302,7 +3373,8 @@ int rfsgpu_batch_cycle_async(rfsgpu_filter *f, int predict, const double *x, con
     batch_inherit_kernel<<<(f->N + 255) / 256, 256, 0, f->stream>>>(f->B.unusedMask, f->dBMaskTmp, f->dBInhSrc, f->N);
   }
   if (f->bDevRoute) {
-    batch_inherit_dev_kernel<<<nF, BATCH_LOOP_THREADS, 0, f->stream>>>(f->B.unusedMask, f->BL.ppid, f->BL.resampled, f->dBFilt, nPer, predict == 1 ? 1 : 0);
+    batch_inherit_dev_kernel<<<nF, BATCH_LOOP_THREADS, 0, f->stream>>>(f->B.unusedMask, f->BL.ppid, f->BL.resampled, f->dBFilt, nPer, predict == 1 ? 1 : 0,
+                                                                           sensed ? f->dBSensorPrev : nullptr);
     HIPCHK(hipGetLastError());
   }
   // the host's new poses / covariances, pulled by the step kernel from a slot of the staging ring (rfsgpu_cycle_async's form)
@@ -3331,6 +3403,7 @@ int rfsgpu_batch_cycle_async(rfsgpu_filter *f, int predict, const double *x, con
   const int wpp = sv.wpp, phasePrio = sv.phasePrio;
   const size_t lds = sv.ldsBytes;
   f->lastStepVariant[0] = wpp; f->lastStepVariant[1] = phasePrio; f->lastStepVariant[2] = 5; f->lastStepVariant[3] = sp.mode ? 2 : (sp.inMask ? 3 : 1);
+  f->bLastCycleLds = (long long)lds;
   if ((rc = vp_order_buffers(f)) != RFSGPU_OK) return rc;
   const StepLaunchOrder sloOn{f->vpOrderMode ? f->vpCost : nullptr, f->vpOrderMode ? f->vpOrder : nullptr}, sloOff{nullptr, nullptr};
   static const ZArg noZ{};
@@ -3355,8 +3428,12 @@ int rfsgpu_batch_cycle_async(rfsgpu_filter *f, int predict, const double *x, con
   if (murty_launch_batch(f->Q, f->MS, f->B, f->stream, A, normalize, f->hJobCount, sord) != 0) return fail(f, RFSGPU_ERR_HIP, "batch post kernel launch failed");
   if (ks >= 0) HIPCHK(hipEventRecord(f->stage.ev[ks], f->stream));   // the pinned input slot is free once the step kernel has read it
   f->cur ^= 1;   // (filters without an update had their mixture moved to the new slab by the step kernel)
-  for (int b = 0; b < nF; b++)
-    if (n_z[b] > 0) { f->bNZ[b] = n_z[b]; f->bResampled[b] = 0; }
+  if (!sensed)
+    for (int b = 0; b < nF; b++)
+      if (n_z[b] > 0) { f->bNZ[b] = n_z[b]; f->bResampled[b] = 0; }
+  f->bSenseFresh = false;     // (either kind of cycle: the next sensed cycle needs a sense call of its own)
+  f->bSensedTail = sensed;
+  if (!sensed) f->bScanHeld = false;
   f->holes = false;
   f->timing.mapUpdate_cpu += now_ns() - t0;
   return RFSGPU_OK;
@@ -3816,30 +3893,42 @@ int rfsgpu_batch_resample_async(rfsgpu_filter *f, const int *n_z, unsigned long 
   if (rc != RFSGPU_OK) return rc;
   REFUSE_ON_MH_BATCH(f, "rfsgpu_batch_resample_async");
   if ((rc = batch_check_call(f, BATCH_RESAMPLE, 0, nullptr, 0, n_z)) != RFSGPU_OK) return rc;
+  if (f->bSensed)
+    return fail(f, RFSGPU_ERR_UNSUPPORTED, "batch_resample: this batch has run a sensed cycle (rfsgpu_batch_cycle_sensed_async): its measurement counts live on the device (rfsgpu_batch_resample_sensed_async)");
+  return batch_resample_core(f, BATCH_RESAMPLE, n_z, call);
+}
+// From here on the ids and resampleOccured_ live on the device.  Once per handle, and host-synchronous: the sources are pageable host
+// vectors, which the runtime copies before the call returns; the synchronisation says so instead of relying on it.
+static int batch_enter_dev_route(rfsgpu_filter *f) {
+  if (f->bDevRoute) return RFSGPU_OK;
   const int nF = f->nF;
-  if (f->nPer > RFSGPU_BATCH_RESAMPLE_MAX_PER_FILTER)
-    return fail(f, RFSGPU_ERR_UNSUPPORTED, "batch_resample: more than RFSGPU_BATCH_RESAMPLE_MAX_PER_FILTER particles per filter (one workgroup resamples a filter)");
+  ensure_ids(f);
+  std::vector<int> r(nF);
+  for (int b = 0; b < nF; b++) r[b] = f->bResampled[b] ? 1 : 0;
+  HIPCHK(hipMemcpyAsync(f->BL.pid, f->pid.data(), (size_t)f->N * sizeof(int), hipMemcpyHostToDevice, f->stream));
+  HIPCHK(hipMemcpyAsync(f->BL.ppid, f->ppid.data(), (size_t)f->N * sizeof(int), hipMemcpyHostToDevice, f->stream));
+  HIPCHK(hipMemcpyAsync(f->BL.resampled, r.data(), (size_t)nF * sizeof(int), hipMemcpyHostToDevice, f->stream));
+  HIPCHK(hipStreamSynchronize(f->stream));
+  f->bDevRoute = true;
+  return RFSGPU_OK;
+}
+// The resampling tail behind rfsgpu_batch_resample_async (n_z: the host's counts) and rfsgpu_batch_resample_sensed_async (n_z null:
+// each filter's count is the nZ of its record on the device)
+static int batch_resample_core(rfsgpu_filter *f, const BatchCall &C, const int *n_z, unsigned long long call) {
+  int rc = RFSGPU_OK;
+  const int nF = f->nF;
+  if (f->nPer > RFSGPU_BATCH_RESAMPLE_MAX_PER_FILTER) {
+    f->err = std::string(C.who) + ": more than RFSGPU_BATCH_RESAMPLE_MAX_PER_FILTER particles per filter (one workgroup resamples a filter)";
+    return RFSGPU_ERR_UNSUPPORTED;
+  }
   for (int b = 0; b < nF; b++) {
-    if ((rc = batch_check_filter(f, BATCH_RESAMPLE, b, nullptr, n_z)) != RFSGPU_OK) return rc;
-    if (!f->bMotionSet[b] || !f->bResSet[b]) {
-      f->err = "batch_resample: filter " + std::to_string(b) + (f->bResSet[b] ? " has no Philox key (rfsgpu_batch_set_motion_odometry)" : " has no resampling thresholds (rfsgpu_batch_set_resampling)");
-      return RFSGPU_ERR_INVALID;
-    }
+    if (n_z && (rc = batch_check_filter(f, C, b, nullptr, n_z)) != RFSGPU_OK) return rc;
+    if (!f->bMotionSet[b] || !f->bResSet[b])
+      return batch_fail(f, C, "filter " + std::to_string(b) + (f->bResSet[b] ? " has no Philox key (rfsgpu_batch_set_motion_odometry)" : " has no resampling thresholds (rfsgpu_batch_set_resampling)"));
   }
   hipSetDevice(f->device);
   long long t0 = now_ns();
-  if (!f->bDevRoute) {     // from here on the ids and resampleOccured_ live on the device.  Once per handle, and host-synchronous: the
-                           // sources are pageable host vectors, which the runtime copies before the call returns; the synchronisation
-                           // below says so instead of relying on it
-    ensure_ids(f);
-    std::vector<int> r(nF);
-    for (int b = 0; b < nF; b++) r[b] = f->bResampled[b] ? 1 : 0;
-    HIPCHK(hipMemcpyAsync(f->BL.pid, f->pid.data(), (size_t)f->N * sizeof(int), hipMemcpyHostToDevice, f->stream));
-    HIPCHK(hipMemcpyAsync(f->BL.ppid, f->ppid.data(), (size_t)f->N * sizeof(int), hipMemcpyHostToDevice, f->stream));
-    HIPCHK(hipMemcpyAsync(f->BL.resampled, r.data(), (size_t)nF * sizeof(int), hipMemcpyHostToDevice, f->stream));
-    HIPCHK(hipStreamSynchronize(f->stream));
-    f->bDevRoute = true;
-  }
+  if ((rc = batch_enter_dev_route(f)) != RFSGPU_OK) return rc;
   if ((rc = batch_push_motion(f)) != RFSGPU_OK) return rc;
   unsigned char *h = nullptr;
   int k = 0;
@@ -3848,14 +3937,14 @@ int rfsgpu_batch_resample_async(rfsgpu_filter *f, const int *n_z, unsigned long 
   for (int b = 0; b < nF; b++) {
     BatchResIn &I = hi[b];
     I.effN = f->bEffN[2 * (size_t)b]; I.effNPercent = f->bEffN[2 * (size_t)b + 1];
-    I.nZ = n_z[b];
+    I.nZ = n_z ? n_z[b] : 0;
     if (f->bKind == 2) { I.minUpdates = (int)f->bFs[b].minUpdatesBeforeResample; I.minMeasurements = (int)f->bFs[b].minMeasurementsBeforeResample; }   // (a FastSLAM batch: FastSLAM.hpp:729-733)
     else { I.minUpdates = f->bCfg[b].minUpdatesBeforeResample; I.minMeasurements = f->bCfg[b].minMeasurementsBeforeResample; }
     I.pad = 0;
   }
   HIPCHK(hipMemcpyAsync(f->dBResIn, hi, (size_t)nF * sizeof(BatchResIn), hipMemcpyHostToDevice, f->stream));
   HIPCHK(hipEventRecord(f->bLoop.ev[k], f->stream));
-  batch_resample_kernel<<<nF, BATCH_LOOP_THREADS, 0, f->stream>>>(f->B.weight, f->BL, f->dBMotion, f->dBResIn, f->nPer, call);
+  batch_resample_kernel<<<nF, BATCH_LOOP_THREADS, 0, f->stream>>>(f->B.weight, f->BL, f->dBMotion, f->dBResIn, f->nPer, call, n_z ? nullptr : f->dBFilt);
   resample_gather_kernel<<<f->N, 256, 0, f->stream>>>(f->B, f->cur, f->BL.plan, f->P.poseCovStride, 1);
   HIPCHK(hipGetLastError());
   const long long dtn = now_ns() - t0;
@@ -3903,6 +3992,200 @@ int rfsgpu_batch_resample_counts(rfsgpu_filter *f, long long *out) {
   hipSetDevice(f->device);
   HIPCHK(hipMemcpyAsync(out, f->BL.nResamples, (size_t)f->nF * sizeof(long long), hipMemcpyDeviceToHost, f->stream));
   HIPCHK(hipStreamSynchronize(f->stream));
+  return RFSGPU_OK;
+}
+
+// ---- [sensor] every filter's scan drawn on the device (batch_sensor.h) ----------------------------------------------------------------
+static const BatchCall BATCH_SET_SENSOR{"batch_set_sensor", 0, nullptr, nullptr};
+static const BatchCall BATCH_SENSE{"batch_sense", 0, nullptr, nullptr};
+static const BatchCall BATCH_CYCLE_SENSED{"batch_cycle_sensed", -1, "RFSGPU_CYCLE_NO_PREDICT (-1), 0 (static step only) or 1 (births + static step)", nullptr};
+static const BatchCall BATCH_RESAMPLE_SENSED{"batch_resample_sensed", 0, nullptr, nullptr};
+static const BatchCall BATCH_LAST_SCAN{"batch_last_scan", 0, nullptr, nullptr};
+// What the section serves: RB-PHD filter batches.  The records of the other kinds carry host-computed, count-dependent parameters.
+static int sensor_check(rfsgpu_filter *f, const BatchCall &C) {
+  const char *why = !f->batch ? (f->groupShard ? "a shard of an rfsgpu_group" : "an ordinary handle")
+                              : (f->mhBatch ? "a batch of multi-hypothesis FastSLAM filters (rfsgpu_create_batch_mh)" : (f->bKind == 2 ? "a batch of FastSLAM filters" : nullptr));
+  if (!why) return RFSGPU_OK;
+  f->err = std::string(C.who) + ": the device sensor serves batches of RB-PHD filters (rfsgpu_create_batch, rfsgpu_batch_cycle_async) only, not " + why;
+  return RFSGPU_ERR_UNSUPPORTED;
+}
+int rfsgpu_batch_set_sensor(rfsgpu_filter *f, int filter, const rfsgpu_rngbrg_config *model, const double *landmarks_xy, int n_landmarks, int max_nz,
+                            unsigned long long seed) {
+  CHECK_HANDLE(f);
+  const BatchCall &C = BATCH_SET_SENSOR;
+  int rc = sensor_check(f, C);
+  if (rc != RFSGPU_OK) return rc;
+  if (filter < -1 || filter >= f->nF) return batch_fail(f, C, "filter index out of range");
+  if (!model) return batch_fail(f, C, "null sensor model");
+  if (n_landmarks < 0 || n_landmarks > RFSGPU_SENSOR_MAX_LANDMARKS) return batch_fail(f, C, "n_landmarks must lie in 0 ... RFSGPU_SENSOR_MAX_LANDMARKS");
+  if (n_landmarks > 0 && !landmarks_xy) return batch_fail(f, C, "null landmark array");
+  if (max_nz < 1 || max_nz > RFSGPU_MAX_Z) return batch_fail(f, C, "max_nz must lie in 1 ... RFSGPU_MAX_Z");
+  for (int q = 0; q < 2 * n_landmarks; q++)
+    if (!std::isfinite(landmarks_xy[q])) return batch_fail(f, C, "landmark " + std::to_string(q / 2) + " is not finite");
+  BatchSensor S;
+  memset(&S, 0, sizeof S);
+  // the lower Cholesky factor of R (Eigen's LLT reads the lower triangle; RandomVec::sample multiplies it with the deviates)
+  const double *R = model->R;
+  S.L[0] = sqrt(R[0]);
+  S.L[1] = R[2] / S.L[0];
+  S.L[2] = sqrt(R[3] - S.L[1] * S.L[1]);
+  if (!(R[0] > 0.0) || R[1] != R[2] || !(R[3] - S.L[1] * S.L[1] > 0.0) || !std::isfinite(S.L[0]) || !std::isfinite(S.L[1]) || !std::isfinite(S.L[2]))
+    return batch_fail(f, C, "R is not (symmetric) positive definite");
+  if (!std::isfinite(model->rangeLimMin) || !std::isfinite(model->rangeLimMax) || !(model->rangeLimMin < model->rangeLimMax))
+    return batch_fail(f, C, "rangeLimMin must lie below rangeLimMax");
+  if (!(model->probabilityOfDetection >= 0.0 && model->probabilityOfDetection <= 1.0)) return batch_fail(f, C, "probabilityOfDetection must lie in [0, 1]");
+  if (!(model->uniformClutterIntensity >= 0.0)) return batch_fail(f, C, "uniformClutterIntensity must not be negative");
+  S.Pd = model->probabilityOfDetection; S.rmin = model->rangeLimMin; S.rmax = model->rangeLimMax;
+  S.seed = seed; S.nLm = n_landmarks; S.maxNz = max_nz;
+  {   // the Poisson table of src/rbphdslam2dSim.cpp:292-306: same loop, same order of operations
+    const double PI = acos(-1);
+    const double sensingArea = 2 * PI * (model->rangeLimMax - model->rangeLimMin);     // MeasurementModel_RngBrg::clutterIntensityIntegral
+    const double meanClutter = model->uniformClutterIntensity * sensingArea;
+    const double expNegMeanClutter = exp(-meanClutter);
+    double poissonPmf[SENSOR_CMF];
+    double mean_pow_i = 1;
+    double i_factorial = 1;
+    poissonPmf[0] = expNegMeanClutter;
+    S.cmf[0] = poissonPmf[0];
+    for (int i = 1; i < SENSOR_CMF; i++) {
+      mean_pow_i *= meanClutter;
+      i_factorial *= i;
+      poissonPmf[i] = mean_pow_i / i_factorial * expNegMeanClutter;
+      S.cmf[i] = S.cmf[i - 1] + poissonPmf[i];
+    }
+    for (int i = 0; i < SENSOR_CMF; i++)
+      if (!std::isfinite(S.cmf[i])) return batch_fail(f, C, "the mean clutter count is beyond what the 100-entry Poisson table can hold (a term of it is not finite)");
+  }
+  // configuration is rare: the tables are written in place once the stream has drained (a sense kernel in flight reads them)
+  hipSetDevice(f->device);
+  HIPCHK(hipStreamSynchronize(f->stream));
+  for (int b = (filter < 0 ? 0 : filter); b < (filter < 0 ? f->nF : filter + 1); b++) {
+    HIPCHK(hipMemcpy(f->dBSensor + b, &S, sizeof S, hipMemcpyHostToDevice));
+    if (n_landmarks > 0)
+      HIPCHK(hipMemcpy(f->dBSensorLm + (size_t)b * SENSOR_MAX_LANDMARKS * 2, landmarks_xy, (size_t)n_landmarks * 2 * sizeof(double), hipMemcpyHostToDevice));
+    f->bSensorSet[b] = 1;
+    f->bSensorMaxNz[b] = max_nz;
+  }
+  f->bSenseFresh = false;     // (a scan drawn before this call is not this sensor's: the next sensed cycle needs a sense call of its own)
+  return RFSGPU_OK;
+}
+int rfsgpu_batch_sense_async(rfsgpu_filter *f, const double *gt_pose, unsigned long long call) {
+  CHECK_HANDLE(f);
+  const BatchCall &C = BATCH_SENSE;
+  int rc = sensor_check(f, C);
+  if (rc != RFSGPU_OK) return rc;
+  if (!gt_pose) return batch_fail(f, C, "null ground-truth poses");
+  const int nF = f->nF;
+  for (int b = 0; b < nF; b++) {
+    if (!f->bSensorSet[b]) return batch_fail(f, C, "filter " + std::to_string(b) + " has no sensor (rfsgpu_batch_set_sensor)");
+    const double *p = gt_pose + 3 * (size_t)b;
+    if (!std::isfinite(p[0]) || !std::isfinite(p[1]) || !(fabs(p[2]) <= 64.0))
+      return batch_fail(f, C, "filter " + std::to_string(b) + ": the pose must be finite, its heading within +-64 rad");
+  }
+  hipSetDevice(f->device);
+  unsigned char *h = nullptr;
+  int k = 0;
+  // One block of the loop ring per call: {poses [nF][3] | counts [nF] | evalCap, useW [nF][2]} (36 bytes a filter, inside the block's
+  // size).  The block is acquired before the host's tables change, so that a failure leaves them as they were.
+  static_assert(sizeof(BatchPropIn) >= 3 * sizeof(double) + 3 * sizeof(int), "a block of the loop ring holds a sense call's tables");
+  if ((rc = ring_acquire(f, f->bLoop, &h, &k)) != RFSGPU_OK) return rc;
+  memcpy(h, gt_pose, (size_t)nF * 3 * sizeof(double));
+  HIPCHK(hipMemcpyAsync(f->dBSensorPose, h, (size_t)nF * 3 * sizeof(double), hipMemcpyHostToDevice, f->stream));
+  // ... until a sensed cycle has run, the counts of the filters' last updates as the host-fed cycles left them
+  if (!f->bSensed) {
+    int *hp = reinterpret_cast<int *>(h + (size_t)nF * 3 * sizeof(double));
+    memcpy(hp, f->bNZ.data(), (size_t)nF * sizeof(int));
+    HIPCHK(hipMemcpyAsync(f->dBSensorPrev, hp, (size_t)nF * sizeof(int), hipMemcpyHostToDevice, f->stream));
+  }
+  // ... evalCap / useW of the records: a table on the device, staged again when a filter's configuration has changed
+  bool capsDirty = false;
+  int ecMax = 1, nzMax = 0;
+  for (int b = 0; b < nF; b++) {
+    const int c[2] = {batch_eval_cap(f, b), f->bCfg[b].useClusterProcess ? 0 : 1};
+    if (c[0] != f->bSensorCaps[2 * (size_t)b] || c[1] != f->bSensorCaps[2 * (size_t)b + 1]) { f->bSensorCaps[2 * (size_t)b] = c[0]; f->bSensorCaps[2 * (size_t)b + 1] = c[1]; capsDirty = true; }
+    ecMax = std::max(ecMax, c[0]);
+    nzMax = std::max(nzMax, f->bSensorMaxNz[b]);
+  }
+  if (capsDirty) {
+    int *hc = reinterpret_cast<int *>(h + (size_t)nF * (3 * sizeof(double) + sizeof(int)));
+    memcpy(hc, f->bSensorCaps.data(), (size_t)nF * 2 * sizeof(int));
+    HIPCHK(hipMemcpyAsync(f->dBSensorCaps, hc, (size_t)nF * 2 * sizeof(int), hipMemcpyHostToDevice, f->stream));
+  }
+  HIPCHK(hipEventRecord(f->bLoop.ev[k], f->stream));
+  BatchSensorArg A{f->dBSensor, f->dBSensorLm, f->dBSensorPose, f->dBSensorCaps, f->dBSensorPrev, f->dBZ, f->dBFilt, f->B.err, f->dBSensorErrFilter, nF};
+  batch_sense_kernel<<<nF, 64, 0, f->stream>>>(A, (unsigned)(call & 0xffffffffull), (unsigned)(call >> 32));
+  HIPCHK(hipGetLastError());
+  f->bSenseFresh = true;
+  f->bSenseNzMax = nzMax; f->bSenseEcMax = ecMax;
+  f->bScanHeld = true;
+  f->bSensedTail = false;
+  return RFSGPU_OK;
+}
+int rfsgpu_batch_cycle_sensed_async(rfsgpu_filter *f, int predict, const double *x, const double *x_cov, int cov_stride, int normalize) {
+  CHECK_HANDLE(f);
+  const BatchCall &C = BATCH_CYCLE_SENSED;
+  int rc = sensor_check(f, C);
+  if (rc != RFSGPU_OK) return rc;
+  if ((rc = batch_check_call(f, C, predict, x_cov, cov_stride, nullptr)) != RFSGPU_OK) return rc;
+  for (int b = 0; b < f->nF; b++) {
+    if (!f->bSensorSet[b]) return batch_fail(f, C, "filter " + std::to_string(b) + " has no sensor (rfsgpu_batch_set_sensor)");
+    if (f->bCfg[b].birthGaussianMeasurementCountThreshold != 1u) {
+      f->err = "batch_cycle_sensed: a filter batch takes immediate births only (birthGaussianMeasurementCountThreshold 1)";
+      return RFSGPU_ERR_UNSUPPORTED;
+    }
+  }
+  if (!f->bSenseFresh) return batch_fail(f, C, "no rfsgpu_batch_sense_async has run since the last cycle or the last rfsgpu_batch_set_sensor: filter 0 (and every other) has no scan for this one");
+  // (the step kernel lays out a filter's LDS by the record's evalCap and picks its evaluation points by the Params table's count: the
+  //  record, written at the sense call, must still be the configuration's)
+  for (int b = 0; b < f->nF; b++)
+    if (batch_eval_cap(f, b) != f->bSensorCaps[2 * (size_t)b] || (f->bCfg[b].useClusterProcess ? 0 : 1) != f->bSensorCaps[2 * (size_t)b + 1])
+      return batch_fail(f, C, "filter " + std::to_string(b) + ": importanceWeightingEvalPointCount or useClusterProcess has changed since the last rfsgpu_batch_sense_async, whose record carries them: sense again");
+  if (f->nPer > RFSGPU_BATCH_RESAMPLE_MAX_PER_FILTER) {
+    f->err = "batch_cycle_sensed: more than RFSGPU_BATCH_RESAMPLE_MAX_PER_FILTER particles per filter (the device route's inheritance kernel takes a filter per workgroup)";
+    return RFSGPU_ERR_UNSUPPORTED;
+  }
+  hipSetDevice(f->device);
+  // the inheritance then reads the records where the sensor wrote them.  (Entering the device route is what the first
+  // rfsgpu_batch_resample_async does too: it moves the ids, it refuses nothing, and it stays if the cycle below fails.)
+  if ((rc = batch_enter_dev_route(f)) != RFSGPU_OK) return rc;
+  if ((rc = batch_cycle_core(f, predict, x, x_cov, cov_stride, nullptr, nullptr, normalize)) != RFSGPU_OK) return rc;
+  f->bKind = 1;
+  f->bSensed = true;     // (only now: a cycle that failed leaves the host-fed calls open)
+  return RFSGPU_OK;
+}
+int rfsgpu_batch_resample_sensed_async(rfsgpu_filter *f, unsigned long long call) {
+  CHECK_HANDLE(f);
+  const BatchCall &C = BATCH_RESAMPLE_SENSED;
+  int rc = sensor_check(f, C);
+  if (rc != RFSGPU_OK) return rc;
+  if (!f->bSensedTail) return batch_fail(f, C, "no rfsgpu_batch_cycle_sensed_async has run since the last rfsgpu_batch_sense_async: the records on the device are not those of a finished cycle");
+  return batch_resample_core(f, C, nullptr, call);
+}
+int rfsgpu_batch_last_scan(rfsgpu_filter *f, double *z, int *n_z) {
+  CHECK_HANDLE(f);
+  const BatchCall &C = BATCH_LAST_SCAN;
+  int rc = sensor_check(f, C);
+  if (rc != RFSGPU_OK) return rc;
+  if (!z || !n_z) return batch_fail(f, C, "null output");
+  if (!f->bScanHeld) return batch_fail(f, C, "no rfsgpu_batch_sense_async has run on this handle since its last host-fed cycle");
+  const int nF = f->nF;
+  hipSetDevice(f->device);
+  std::vector<BatchFilter> rec(nF);
+  HIPCHK(hipMemcpyAsync(rec.data(), f->dBFilt, (size_t)nF * sizeof(BatchFilter), hipMemcpyDeviceToHost, f->stream));
+  HIPCHK(hipMemcpyAsync(z, f->dBZ, (size_t)nF * RFSGPU_MAX_Z * 2 * sizeof(double), hipMemcpyDeviceToHost, f->stream));
+  HIPCHK(hipStreamSynchronize(f->stream));
+  for (int b = 0; b < nF; b++) {
+    n_z[b] = rec[b].nZ;
+    memset(z + ((size_t)b * RFSGPU_MAX_Z + (size_t)n_z[b]) * 2, 0, (size_t)(RFSGPU_MAX_Z - n_z[b]) * 2 * sizeof(double));     // (beyond the set: whatever an earlier scan left)
+  }
+  return check_device_errors(f);     // (a scan that was cut: RFSGPU_ERR_CAPACITY once; the outputs hold the sets as delivered)
+}
+int rfsgpu_batch_last_cycle_lds(rfsgpu_filter *f, long long *bytes) {
+  CHECK_HANDLE(f);
+  int rc = batch_check(f, -1);
+  if (rc != RFSGPU_OK) return rc;
+  if (!bytes) return fail(f, RFSGPU_ERR_INVALID, "batch_last_cycle_lds: null output");
+  *bytes = f->bLastCycleLds;
   return RFSGPU_OK;
 }
 

@@ -46,8 +46,10 @@ def odometry_step(x, u):
     return out
 
 
-def generate(P=C1_SIM, traj_seed=1, kmax=None):
-    """gt poses [K,3], odometry [K,3], landmarks [L,2], per-step measurement lists."""
+def generate(P=C1_SIM, traj_seed=1, kmax=None, measurements=True):
+    """gt poses [K,3], odometry [K,3], landmarks [L,2], per-step measurement lists.  measurements=False: the scans are not drawn
+    (Z is None) -- for runs whose sensor is the device's (Sim2dBatchRun(device_sensor=True)); the trajectory, landmarks and odometry
+    are drawn before the scans from the one generator, so they are the same either way."""
     K = int(kmax or P["kmax"])
     K_full = int(P["kmax"])           # segment / landmark spacing follows the configured length even when fewer steps are run
     dt = P["dt"]
@@ -82,6 +84,8 @@ def generate(P=C1_SIM, traj_seed=1, kmax=None):
     odom = np.zeros((K, 3))
     for k in range(1, K):
         odom[k] = disp[k] + np.sqrt(Qd) * dt * rng.standard_normal(3)
+    if not measurements:
+        return dict(gt=gt, odom=odom, landmarks=lm, Z=None, K=K)
     # measurements (:287-366): noisy range-bearing of the landmarks in range with probability Pd + Poisson clutter
     mean_clutter = P["clutter"] * (2 * np.pi) * (P["rmax"] - P["rmin"])      # MeasurementModel_RngBrg::clutterIntensityIntegral
     sr, sb = np.sqrt(P["varzr"]), np.sqrt(P["varzb"])
@@ -304,6 +308,29 @@ class Sim2dRun:
         return self
 
 
+def sensor_max_nz(data, P=C1_SIM, margin=2):
+    """A bound that no scan of the device sensor (rfsgpu_batch_set_sensor) exceeds along data["gt"]: the most landmarks whose TRUE range
+    lies within the limits at any step (only those can be detected) + the clutter count that a draw exceeds with probability below
+    2^-40 per scan (the first n whose CMF reaches 1 - 2^-40; the rounded table of a larger mean never reaches the largest draw itself)
+    + `margin` for a range that rounds differently on the device; at most capi.MAX_Z.  A scan beyond the bound would be cut and
+    reported (RFSGPU_ERR_CAPACITY), not silently wrong.  The step kernel's LDS block, and with it how many workgroups a CU holds, is
+    sized for the batch's largest bound."""
+    gt, lm = data["gt"], data["landmarks"]
+    n_det = 0
+    if len(lm):
+        r = np.hypot(lm[None, :, 0] - gt[1:, None, 0], lm[None, :, 1] - gt[1:, None, 1])
+        n_det = int(((r >= P["rmin"]) & (r <= P["rmax"])).sum(axis=1).max()) if len(r) else 0
+    mean = P["clutter"] * (2 * np.pi * (P["rmax"] - P["rmin"]))
+    e = np.exp(-mean)
+    cmf, p, fact, n_c = e, 1.0, 1.0, 0
+    while n_c < 99 and cmf < 1.0 - 2.0 ** -40:      # (src/rbphdslam2dSim.cpp:294-306 and the walk of :347-349)
+        n_c += 1
+        p *= mean
+        fact *= n_c
+        cmf += p / fact * e
+    return int(min(capi.MAX_Z, max(1, n_det + n_c + margin)))
+
+
 def configure_batch_filter(batch, b, P=C1_SIM):
     """setupRBPHDFilter for filter b of a FilterBatch (what configure() does for a handle)."""
     dt = P["dt"]
@@ -340,14 +367,21 @@ class Sim2dBatchRun:
     call number = the step k), not the numpy streams of the host loop: the two loops run the same model on different realisations
     of the noise.  step() returns None in this form (the decisions stay on the device; FilterBatch.last_resample reads the last ones).
 
+    device_sensor=True (with device_loop, RB-PHD filters): the scans are the device's too ([sensor] in include/rfsgpu.h).  Each filter's
+    sensor is configured from Ps[b] -- the unpadded varzr / varzb, Pd, clutter, the range limits -- with the landmarks of datas[b] and
+    the key seeds[b]; a step is propagate_async -> sense_async(gt[k]) -> cycle_sensed_async -> resample_sensed_async (->
+    step_error_async), and no table of scans is built: datas[b]["Z"] is not read (generate(..., measurements=False) leaves it None).
+
     fastslam=True: the loop of src/fastslam2dSim.cpp:530-600 instead -- the same flow with FastSLAM::predict (propagation, static
     landmark step, no births) and FastSLAM::update; `target` is a FastSLAMBatch or a list of FastSLAM handles (or oracle filters),
     `Ps` dicts like C1_FASTSLAM_SIM.  A filter whose scan is empty is neither updated nor normalised that step (FastSLAM.hpp:402-403)."""
 
-    def __init__(self, target, datas, Ps, seeds, track_errors=False, device_loop=False, fastslam=False):
+    def __init__(self, target, datas, Ps, seeds, track_errors=False, device_loop=False, fastslam=False, device_sensor=False):
         """track_errors: as in Sim2dRun -- each filter's ground truth is uploaded, every cycle ends with one step_error_async (one
         launch for the whole batch; one per handle otherwise), errors() reads the log(s) once at the end."""
         self.device_loop = bool(device_loop)
+        self.device_sensor = bool(device_sensor)
+        assert not self.device_sensor or (self.device_loop and not fastslam), "the device sensor serves the device loop of an RB-PHD FilterBatch"
         self.fastslam = bool(fastslam)
         self.batch = target if isinstance(target, capi.CBatch) else None
         self.handles = None if self.batch is not None else list(target)
@@ -404,6 +438,13 @@ class Sim2dBatchRun:
             self.batch.set_resampling(b, self.eff_n[b], self.eff_n[b] / self.n)
         self._u = np.ascontiguousarray(np.stack([d["odom"][:K] for d in self.datas], axis=1))          # [K, nF, 3]
         self._gt = np.ascontiguousarray(np.stack([d["gt"][:K] for d in self.datas], axis=1))
+        self._t = np.array([[k * P["dt"] for P in self.Ps] for k in range(K)])
+        self._pin_all = np.ones(nF, dtype=np.uint8)
+        if self.device_sensor:      # each filter's simulated sensor: the UNPADDED noise (the filter's own R is inflated); no table of scans
+            for b, (d, P) in enumerate(zip(self.datas, self.Ps)):
+                self.batch.set_sensor(b, np.diag([P["varzr"], P["varzb"]]), P["Pd"], P["clutter"], P["rmax"], P["rmin"], d["landmarks"],
+                                      max_nz=sensor_max_nz(d, P), seed=seeds[b])
+            return
         self._z = np.zeros((K, nF, capi.MAX_Z, 2))
         self._nz = np.zeros((K, nF), dtype=np.int32)
         for b, d in enumerate(self.datas):
@@ -414,8 +455,6 @@ class Sim2dBatchRun:
                 self._nz[k, b] = m
                 if m:
                     self._z[k, b, :m] = Z
-        self._t = np.array([[k * P["dt"] for P in self.Ps] for k in range(K)])
-        self._pin_all = np.ones(nF, dtype=np.uint8)
 
     def _device_propagate(self, k):
         bt = self.batch
@@ -430,6 +469,14 @@ class Sim2dBatchRun:
 
     def _device_update(self, k):
         bt = self.batch
+        if self.device_sensor:
+            bt.sense_async(self._gt[k], k)
+            bt.cycle_sensed_async(True, normalize=True)
+            bt.resample_sensed_async(k)
+            self.last_n_z = None            # (on the device: FilterBatch.last_scan reads the sets)
+            if self.track_errors:
+                bt.step_error_async(self._t[k], self._gt[k], ERROR_W_THRESHOLD, ERROR_CUTOFF, ERROR_ORDER)
+            return None
         if self.fastslam:
             bt.batch_fastslam_cycle_async_packed(True, self._z[k], self._nz[k], normalize=True)
         else:

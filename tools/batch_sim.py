@@ -17,6 +17,13 @@ resample_async, nothing read back until the end; the final synchronisation is in
 and the device loop from the one invocation, both figures in the line.  Every line names its loop kind ("loop").  --reps N: N timed
 repetitions of each figure (fresh batch each), all of them in the line ("..._reps") next to their median.
 
+--device-sensor (RB-PHD batches; implies the device loop, --device-loop / --both-loops are accepted and ignored): per batch size the
+device loop fed with host-made scans against the device loop whose scans the device draws (Sim2dBatchRun(device_sensor=True):
+propagate_async -> sense_async -> cycle_sensed_async -> resample_sensed_async).  Each line has, for either route and from the one
+invocation, the setup time (sim2d_driver.generate + packing, or generate(measurements=False) + set_sensor) and the run time
+separately, with all --reps repetitions and their medians, and filter-steps/s without and with the setup.  --errors / --results / --json
+work as elsewhere (the filters listed are the device-sensor route's).
+
 --fastslam: the same table for the FastSLAM half of a comparison sweep (the reference's fastslam2dSim over the same grid): a
 FastSLAMBatch (rfsgpu_batch_fastslam_cycle_async) against FastSLAM handles stepped in turn (predict_map, fastslam_update, normalise,
 resample per handle), host loop / device loop, --errors.  Every line then carries "filter": "fastslam".
@@ -309,6 +316,67 @@ def mh_sweep(pkg, a, sizes):
             json.dump(rows, fh, indent=1)
 
 
+def sensor_sweep(pkg, a, sizes):
+    """--device-sensor: the device loop with host-made scans (generate() draws them, Sim2dBatchRun packs them) against the device loop
+    with device-made scans (generate(measurements=False), one rfsgpu_batch_set_sensor per filter, sense_async per step).  Per batch size
+    and route, from the one invocation: the setup time (generation + packing / sensor configuration) and the run time (timed span with
+    the final synchronisation inside) separately, medians and all --reps repetitions, and filter-steps/s of the run alone and of setup +
+    run.  With --errors both routes track the errors on the device (the log read inside the span) and the largest batch's device-sensor
+    filters are listed (--results, --json as elsewhere).  The two routes run the same model on different realisations of the scans."""
+    sim = pkg.sim2d_driver
+    pds = [0.5, 0.6, 0.7, 0.8, 0.9, 0.95, 0.99, 0.85, 0.75, 0.65]
+    clutters = [1e-4, 5e-4, 1e-3, 2e-3, 5e-3, 1e-2, 2e-2, 5e-2, 1e-1]
+    Ps = [dict(sim.C1_SIM, Pd=pds[b % len(pds)], clutter=clutters[(b // len(pds)) % len(clutters)]) for b in range(max(sizes))]
+    seeds = [100 + b for b in range(max(sizes))]
+    kmax = a.steps + 2
+    rows = []
+    for B in sizes:
+        row = dict(B=B, particles=a.particles, steps=a.steps, loop="device", reps=max(1, a.reps))
+        for route in ("host", "device"):
+            setup, run_t = [], []
+            for _ in range(max(1, a.reps)):
+                batch = pkg.FilterBatch(B, a.particles, gm_capacity=a.capacity)
+                batch.synchronize()
+                t0 = time.perf_counter()
+                datas = [sim.generate(Ps[b], traj_seed=1 + b, kmax=kmax, measurements=(route == "host")) for b in range(B)]
+                rb = sim.Sim2dBatchRun(batch, datas, Ps[:B], seeds[:B], track_errors=a.errors, device_loop=True, device_sensor=(route == "device"))
+                setup.append(time.perf_counter() - t0)
+                rb.step(1)
+                batch.synchronize()
+                t0 = time.perf_counter()
+                for k in range(2, a.steps + 2):
+                    rb.step(k)
+                if a.errors:
+                    log = rb.errors()               # the one read (it also waits for the queued work)
+                else:
+                    batch.synchronize()
+                run_t.append(time.perf_counter() - t0)
+                if route == "device":
+                    row["resamples_device_scans"] = rb.resample_counts().tolist()
+                    if a.errors:
+                        row["filters"] = filter_rows(log, Ps, B)
+                batch.close()
+            key = route + "_scans_"
+            row[key + "setup_s"], row[key + "setup_s_reps"] = float(np.median(setup)), setup
+            row[key + "run_s"], row[key + "run_s_reps"] = float(np.median(run_t)), run_t
+            row[key + "filter_steps_per_s"] = B * a.steps / row[key + "run_s"]
+            row[key + "filter_steps_per_s_with_setup"] = B * a.steps / (row[key + "setup_s"] + row[key + "run_s"])
+            if route == "host":
+                row["host_scans_packed_bytes_per_step"] = int(B * pkg.capi.MAX_Z * 2 * 8 + B * 4)
+        row["device_over_host_scans_run"] = row["host_scans_run_s"] / row["device_scans_run_s"]
+        row["device_over_host_scans_with_setup"] = (row["host_scans_setup_s"] + row["host_scans_run_s"]) / (row["device_scans_setup_s"] + row["device_scans_run_s"])
+        rows.append(row)
+        print(json.dumps({k: v for k, v in row.items() if k != "filters"}), flush=True)
+    if a.errors:
+        print_filters(rows[-1]["filters"])
+        write_results(a.results, rows[-1]["filters"])
+    if a.json:
+        os.makedirs(os.path.dirname(a.json) or ".", exist_ok=True)
+        with open(a.json, "w") as fh:
+            json.dump(rows, fh, indent=1)
+    return rows
+
+
 def make_batch(pkg, a, B):
     return pkg.FastSLAMBatch(B, a.particles, gm_capacity=a.capacity) if a.fastslam else pkg.FilterBatch(B, a.particles, gm_capacity=a.capacity)
 
@@ -324,18 +392,23 @@ def main():
     ap.add_argument("--errors", action="store_true", help="track COLA / pose error on the device; tracking off / device / host route timed side by side")
     ap.add_argument("--device-loop", action="store_true", help="the batch's whole cycle on the device (propagation and resampling included)")
     ap.add_argument("--both-loops", action="store_true", help="host loop and device loop side by side")
+    ap.add_argument("--device-sensor", action="store_true", help="the device loop with host-made scans against device-made scans (rfsgpu_batch_sense_async): setup and run time of each")
     ap.add_argument("--fastslam", action="store_true", help="FastSLAM filters: a FastSLAMBatch against FastSLAM handles stepped in turn")
     ap.add_argument("--reps", type=int, default=1, help="timed repetitions of every batch figure")
     ap.add_argument("--mhfastslam", action="store_true", help="multi-hypothesis FastSLAM filters: an MHFastSLAMBatch against handles on the device cycle stepped in turn")
     ap.add_argument("--results", default="", help="--errors: write one line per filter of the largest batch, 'Pd  c  posError  mapError' (the final row's pose_ed and cola)")
     ap.add_argument("--max-per-filter", type=int, default=0, help="--mhfastslam: particle slots per filter (default nParticlesMax x hypotheses = 9 x particles, which cannot overflow; at most 2048)")
     a = ap.parse_args()
+    if a.device_sensor and (a.fastslam or a.mhfastslam):
+        ap.error("--device-sensor serves RB-PHD batches (the sensor section refuses FastSLAM and multi-hypothesis FastSLAM batches)")
     pkg = load_pkg()
     if a.mhfastslam:
         return mh_sweep(pkg, a, [int(s) for s in a.sizes.split(",")])
     a.particles = a.particles or 200
     sim = pkg.sim2d_driver
     sizes = [int(s) for s in a.sizes.split(",")]
+    if a.device_sensor:
+        return sensor_sweep(pkg, a, sizes)
     kmax = a.steps + 2
     Ps, datas, seeds = grid(sim, max(sizes), kmax, a.fastslam)
     rows = []
