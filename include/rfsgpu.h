@@ -46,7 +46,8 @@
  *   [batch]    many independent 2-D filters in one handle, stepped together in one launch chain;
  *   [metric]   per-step OSPA / COLA map error and pose error computed on the device, kept in a device-side log;
  *   [resample] ParticleFilter::resample for an ordinary handle of any size on the device, without a host stop;
- *   [sensor]   the simulator's range-bearing sensor of every filter of an RB-PHD batch drawn on the device, for batch sweeps.
+ *   [sensor]   the simulator's range-bearing sensor of every filter of an RB-PHD batch drawn on the device, for batch sweeps;
+ *   [truth]    the simulator's trajectory, odometry and landmarks of every filter of a batch drawn on the device, and a run of steps in one call.
  * A maintainer wiring the reference to the library reads the CORE entries and INTEGRATION.md; nothing optional is required
  * for correct results.
  */
@@ -1021,6 +1022,69 @@ int rfsgpu_batch_last_scan(rfsgpu_filter *f, double *z, int *n_z);
 /* [test] Bytes of LDS that a workgroup of the step kernel had in the last cycle of this batch (host-fed or sensed; 0 before the
  * first) -- so that a test can say that two max_nz bounds gave two launch sizes and the same results.  Any batch; never waits. */
 int rfsgpu_batch_last_cycle_lds(rfsgpu_filter *f, long long *bytes);
+
+/* ---- [truth] every filter's ground truth drawn on the device, and a run of steps in one call (outside the STABLE CORE) -------------
+ * generateTrajectory, generateOdometry and generateLandmarks of the reference's 2-D simulator (src/rbphdslam2dSim.cpp:146-284) for every
+ * filter of a batch in one launch (csrc/batch_truth.h), by the rules the Python driver's generate() follows: n_steps poses, the noisy
+ * odometry between them and the landmarks, plus each landmark's first-seen time (the third column of gtLandmark.dat) and the most
+ * landmarks whose true range lies in [rmin, rmax] at any step.  The tables are step-major on the device: row k holds what call k of
+ * the batch's device loop takes from the host -- the propagation input (odometry, the pose to pin to, the pin flag), the sensing
+ * pose, the step error's time and pose -- so that a run of steps needs nothing from the host and is one call here.
+ * Random numbers: Philox4x32-10 under the TRUTH's 64-bit key with counter (index, block | attempt << 8, 0, 0); the blocks follow the
+ * sensor's (3 ... 7), so one key may serve a filter's motion, sensor and truth:
+ *   block 8,  index = segment s:   attempt a of the segment's dx = u max_dx dt, u in [0, 1) from 53 bits of words 0, 1; drawn again while
+ *                                  dx < min_dx dt; after 64 attempts the last draw is mapped: dx = (min_dx + u (max_dx - min_dx)) dt;
+ *   block 9,  index = segment s:   dy = (u max_dy 2 - max_dy) dt from words 0, 1; dz likewise from words 2, 3 and max_dz;
+ *   block 10, index = landmark j:  r = u1 rmax, b = u2 2 pi; the landmark is (x + r cos(theta + b), y + r sin(theta + b)) from the pose
+ *                                  of the step that places it;
+ *   block 11, index = step k:      g_x = rad cos ang, g_y = rad sin ang (the Box-Muller form of the batch's propagation);
+ *   block 12, index = step k:      g_theta = rad cos ang;  odometry[k] = displacement[k] + sqrt(var_odo) dt g.
+ * The steps up to n_still do not move; segment s starts at step max((k_full / n_segments) s, n_still + 1 + s); landmark j is placed at
+ * step max((k_full / n_landmarks) j, j + 1) when that lies below n_steps (n_landmarks 0: none); pose[0] = 0 and pose[k] is
+ * MotionModel_Odometry2d::step of pose[k - 1] by displacement[k].  A filter's truth depends neither on its place in the batch nor on
+ * the other filters.  The realisations are the device's, not those of the Python driver's numpy generator: same model, other draws.
+ * Every call of the section: RFSGPU_ERR_UNSUPPORTED on a handle that is not a filter batch (an ordinary handle, a shard of an
+ * rfsgpu_group). */
+#define RFSGPU_TRUTH_MAX_STEPS 4096   /* 112 bytes of tables per step and filter: at most 448 KiB a filter */
+typedef struct rfsgpu_truth_config {
+  int k_full;          /* the configured run length (kmax): segment and landmark spacing follow it, whatever n_steps is */
+  int n_segments;      /* k_full / n_segments steps between two draws of the displacement                                */
+  int n_landmarks;     /* k_full / n_landmarks steps between two landmarks (0: no landmarks)                             */
+  int n_still;         /* the first steps, which do not move (the simulator's 50)                                        */
+  int n_pinned;        /* steps k <= n_pinned pin the particles to the true pose (the simulator's 100)                   */
+  double dt;
+  double max_dx, max_dy, max_dz, min_dx;
+  double var_odo[3];   /* vardx, vardy, vardz of the odometry noise                                                      */
+  double rmax, rmin;   /* landmark placement and the first-seen limits                                                   */
+} rfsgpu_truth_config;
+/* Filter `filter`'s (-1: every filter's) configuration and Philox key for the next rfsgpu_batch_generate_truth.  Any kind of batch.
+ * RFSGPU_ERR_INVALID with a message: a field that is negative or not finite, min_dx > max_dx, rmin >= rmax, n_segments < 1,
+ * k_full / n_segments == 0, n_landmarks > 0 and k_full / n_landmarks == 0, more than RFSGPU_SENSOR_MAX_LANDMARKS landmarks that a run
+ * of k_full steps could place.  Nothing waits for the GPU. */
+int rfsgpu_batch_set_truth(rfsgpu_filter *f, int filter, const rfsgpu_truth_config *cfg, unsigned long long seed);
+/* Draws n_steps steps (rows 0 ... n_steps - 1) of every filter's truth in one launch and waits for it; the tables of an earlier call
+ * are replaced.  2 <= n_steps <= RFSGPU_TRUTH_MAX_STEPS and n_steps <= every filter's k_full, else RFSGPU_ERR_INVALID; a filter
+ * without rfsgpu_batch_set_truth: RFSGPU_ERR_INVALID, naming the lowest such filter.  A refused call leaves the tables as they were. */
+int rfsgpu_batch_generate_truth(rfsgpu_filter *f, int n_steps);
+/* Filter `filter`'s tables for the host (synchronising; any pointer may be NULL): gt [n_steps][3], odom [n_steps][3], landmarks_xy and
+ * first_seen with room for RFSGPU_SENSOR_MAX_LANDMARKS landmarks, of which the first *n_landmarks are written (first_seen = k dt of
+ * the first step k >= 1 with the true range in [rmin, rmax], -1: none), *n_det_max the most landmarks in range at any step k >= 1.
+ * The host configures the sensor (rfsgpu_batch_set_sensor) and the metric's ground truth (rfsgpu_set_ground_truth) from them.
+ * RFSGPU_ERR_INVALID before the first rfsgpu_batch_generate_truth. */
+int rfsgpu_batch_get_truth(rfsgpu_filter *f, int filter, double *gt, double *odom, double *landmarks_xy, double *first_seen, int *n_landmarks,
+                           int *n_det_max);
+/* Steps k_from ... k_to - 1 of a batch of RB-PHD filters (1 <= k_from <= k_to <= n_steps), each one the device loop's sequence with
+ * the device sensor, its inputs read from row k of the tables: the propagation (call k), the scan at gt[k] (call k), the sensed cycle
+ * (predict 1, no new poses, normalize 1), the sensed resampling (call k) and, with track_errors != 0, one row of the error log with
+ * t = k dt and gt[k] (w_threshold, cutoff, order as rfsgpu_step_error_async).  Everything is enqueued here and stream-ordered;
+ * nothing is read back, and device-side errors (gm_capacity, a cut scan) surface at the next synchronising call.  The same kernels
+ * with the same arguments as the per-step calls: the same bits.  Refused before anything is enqueued -- RFSGPU_ERR_UNSUPPORTED: a
+ * batch of FastSLAM or multi-hypothesis FastSLAM filters (as the [sensor] section refuses them), delayed births, more than
+ * RFSGPU_BATCH_RESAMPLE_MAX_PER_FILTER particles per filter; RFSGPU_ERR_INVALID, naming the filter: no rfsgpu_batch_generate_truth
+ * yet, a range outside [1, n_steps], a filter without sensor, motion parameters or resampling thresholds, track_errors with a filter
+ * that has no ground truth (rfsgpu_set_ground_truth) or without an error log; RFSGPU_ERR_CAPACITY: a log with fewer free rows than
+ * the run has steps. */
+int rfsgpu_batch_run_truth_async(rfsgpu_filter *f, int k_from, int k_to, int track_errors, double w_threshold, double cutoff, double order);
 
 #ifdef __cplusplus
 }

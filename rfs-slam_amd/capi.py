@@ -21,6 +21,8 @@ MAX_CANDIDATES = 256
 MAX_Z = 64
 MAX_EVAL = 64
 MAX_METRIC_SET = 512
+SENSOR_MAX_LANDMARKS = 512
+TRUTH_MAX_STEPS = 4096
 
 
 class FilterConfig(C.Structure):
@@ -97,6 +99,13 @@ class FastSlamConfig(C.Structure):
     ]
 
 
+class TruthConfig(C.Structure):
+    """rfsgpu_truth_config: the simulator's generation keys of one filter ([truth] in include/rfsgpu.h)."""
+    _fields_ = [("k_full", C.c_int), ("n_segments", C.c_int), ("n_landmarks", C.c_int), ("n_still", C.c_int), ("n_pinned", C.c_int),
+                ("dt", C.c_double), ("max_dx", C.c_double), ("max_dy", C.c_double), ("max_dz", C.c_double), ("min_dx", C.c_double),
+                ("var_odo", C.c_double * 3), ("rmax", C.c_double), ("rmin", C.c_double)]
+
+
 class Timing(C.Structure):
     """RBPHDFilter::TimingInfo (include/RBPHDFilter.hpp:152-167), ns."""
     _fields_ = [(n + s, C.c_longlong) for n in
@@ -143,6 +152,7 @@ ABI_SYMBOLS = [
     "set_ground_truth", "error_log_create", "error_log_reset", "step_error_async", "error_log_read", "step_error", "get_map_estimate",
     "resample_async", "last_resample", "get_pose_covs",
     "batch_set_sensor", "batch_sense_async", "batch_cycle_sensed_async", "batch_resample_sensed_async", "batch_last_scan", "batch_last_cycle_lds",
+    "batch_set_truth", "batch_generate_truth", "batch_get_truth", "batch_run_truth_async",
 ]
 
 _dp = np.ctypeslib.ndpointer(dtype=np.float64, flags="C_CONTIGUOUS")
@@ -913,6 +923,36 @@ class CBatch(CFilter):
             e.scans = [z[b, : nz[b]].copy() for b in range(self.n_filters)]      # (a scan that was cut: the sets as delivered ride on the error)
             raise
         return [z[b, : nz[b]].copy() for b in range(self.n_filters)]
+
+    # -- the device truth ([truth] in include/rfsgpu.h: trajectory, odometry and landmarks drawn on the device; a run in one call) ----
+    def set_truth(self, b, cfg, seed):
+        """rfsgpu_batch_set_truth: filter b's (None: every filter's) TruthConfig and Philox key for the next generate_truth."""
+        self._call("batch_set_truth", C.c_int(-1 if b is None else int(b)), C.c_void_p(None) if cfg is None else C.byref(cfg),
+                   C.c_ulonglong(int(seed) & 0xFFFFFFFFFFFFFFFF))
+
+    def generate_truth(self, n_steps):
+        """rfsgpu_batch_generate_truth: n_steps rows of every filter's truth in one launch (synchronous); earlier tables are replaced."""
+        self._call("batch_generate_truth", C.c_int(int(n_steps)))
+        self.truth_steps = int(n_steps)
+
+    def get_truth(self, b, trajectory=True):
+        """rfsgpu_batch_get_truth: filter b's tables as a dict -- landmarks [L, 2], first_seen [L], n_det_max, K and, unless
+        trajectory=False, gt [K, 3] and odom [K, 3] (else None).  Synchronising."""
+        K = int(getattr(self, "truth_steps", 0))
+        gt = np.zeros((K, 3)) if trajectory else None
+        od = np.zeros((K, 3)) if trajectory else None
+        lm = np.zeros((SENSOR_MAX_LANDMARKS, 2))
+        fs = np.zeros(SENSOR_MAX_LANDMARKS)
+        n, nd = C.c_int(0), C.c_int(0)
+        self._call("batch_get_truth", C.c_int(int(b)), C.c_void_p(None) if gt is None else self._ptr(gt), C.c_void_p(None) if od is None else self._ptr(od),
+                   self._ptr(lm), self._ptr(fs), C.byref(n), C.byref(nd))
+        return dict(gt=gt, odom=od, landmarks=lm[: n.value].copy(), first_seen=fs[: n.value].copy(), n_det_max=int(nd.value), K=K, Z=None)
+
+    def run_truth_async(self, k_from, k_to, track_errors=False, w_threshold=0.75, cutoff=0.20, order=1.0):
+        """rfsgpu_batch_run_truth_async: the steps k_from ... k_to - 1 of the device loop with the device sensor, their inputs read from
+        the truth tables; enqueued in one call, nothing waits for the GPU."""
+        self._call("batch_run_truth_async", C.c_int(int(k_from)), C.c_int(int(k_to)), C.c_int(1 if track_errors else 0), C.c_double(w_threshold),
+                   C.c_double(cutoff), C.c_double(order))
 
     def last_cycle_lds(self):
         """Bytes of LDS a workgroup of the step kernel had in the batch's last cycle (0 before the first)."""

@@ -30,6 +30,7 @@
 #include "map_metric.h"
 #include "batch_loop.h"
 #include "batch_sensor.h"
+#include "batch_truth.h"
 #include "resample_plan.h"
 
 namespace {
@@ -236,6 +237,18 @@ struct rfsgpu_filter {
   bool bScanHeld = false;                      // the records and sets on the device are a sense call's (no host-fed cycle has written over them): rfsgpu_batch_last_scan may read them
   bool bSensedTail = false;                   // a sensed cycle has run since the last sense call: rfsgpu_batch_resample_sensed_async may read its records
   bool bSensed = false;                        // a sensed cycle has run on this handle: nZprev lives on the device, the host-fed cycle and resampling refuse
+  // the truth of a batch (batch_truth.h): every filter's trajectory, odometry and landmarks drawn on the device, in step-major tables
+  std::vector<char> bTruthSet;                 // rfsgpu_batch_set_truth has been called for the filter
+  std::vector<BatchTruth> bTruth;              // [nF] as the next generation uploads it
+  int truthK = 0;                              // steps the tables hold (0: no generation yet)
+  size_t truthRows = 0;                        // rows the step tables have room for
+  BatchTruth *dTruthCfg = nullptr;             // [nF]
+  BatchPropIn *dTruthProp = nullptr;           // [truthRows][nF]
+  double *dTruthGt = nullptr;                  // [truthRows][nF][3]
+  double *dTruthTgt = nullptr;                 // [truthRows][nF][4]
+  double *dTruthLm = nullptr;                  // [nF][SENSOR_MAX_LANDMARKS][2]
+  double *dTruthSeen = nullptr;                // [nF][SENSOR_MAX_LANDMARKS]
+  int *dTruthCounts = nullptr;                 // [nF][2]
   // a batch of FastSLAM filters (rfsgpu_batch_fastslam_cycle_async; fastslam.h FsBatchArg)
   int bKind = 0;                               // what the batch steps: 0 not decided yet, 1 RB-PHD filters, 2 FastSLAM filters (the first cycle call decides), 3 multi-hypothesis FastSLAM filters (rfsgpu_create_batch_mh decides)
   std::vector<rfsgpu_fastslam_config> bFs;     // [nF]
@@ -255,6 +268,7 @@ struct rfsgpu_filter {
   // [metric] per-step map / pose error (map_metric.h): ground truth per filter, the device-side log, one row for the synchronous calls
   double *dGtXY = nullptr, *dGtSeen = nullptr;   // [nF][RFSGPU_MAX_METRIC_SET][2], [nF][RFSGPU_MAX_METRIC_SET] (allocated by the first rfsgpu_set_ground_truth)
   int *dGtN = nullptr;                           // [nF]
+  std::vector<char> gtSet;                       // [nF] rfsgpu_set_ground_truth has been called for the filter
   struct rfsgpu_step_error *dErrLog = nullptr;          // [errLogCap][nF]
   int errLogCap = 0, errLogRows = 0;
   struct rfsgpu_step_error *dErrRow = nullptr;          // [nF]
@@ -602,6 +616,7 @@ void rfsgpu_destroy(rfsgpu_filter *f) {
   hipFree(f->dBMotion); hipFree(f->dBPropIn); hipFree(f->dBResIn); hipFree(f->BL.counters); hipFree(f->BL.nResamples); hipFree(f->BL.resampled);
   hipFree(f->BL.fired); hipFree(f->BL.nEff); hipFree(f->BL.plan); hipFree(f->BL.pid); hipFree(f->BL.ppid);
   hipFree(f->dBSensor); hipFree(f->dBSensorLm); hipFree(f->dBSensorPose); hipFree(f->dBSensorCaps); hipFree(f->dBSensorPrev); hipFree(f->dBSensorErrFilter);
+  hipFree(f->dTruthCfg); hipFree(f->dTruthProp); hipFree(f->dTruthGt); hipFree(f->dTruthTgt); hipFree(f->dTruthLm); hipFree(f->dTruthSeen); hipFree(f->dTruthCounts);
   hipFree(f->dGtXY); hipFree(f->dGtSeen); hipFree(f->dGtN); hipFree(f->dErrLog); hipFree(f->dErrRow);
   if (f->hErr) hipHostFree(f->hErr);
   if (f->hJobCount) hipHostFree(f->hJobCount);
@@ -3196,8 +3211,10 @@ static int batch_push_params(rfsgpu_filter *f) {
   return RFSGPU_OK;
 }
 static int batch_cycle_core(rfsgpu_filter *f, int predict, const double *x, const double *x_cov, int cov_stride, const double *z, const int *n_z, int normalize);
-static int batch_resample_core(rfsgpu_filter *f, const BatchCall &C, const int *n_z, unsigned long long call);
+static int batch_resample_core(rfsgpu_filter *f, const BatchCall &C, const int *n_z, unsigned long long call, bool stageIn = true);
 static int batch_enter_dev_route(rfsgpu_filter *f);
+static int batch_propagate_core(rfsgpu_filter *f, const double *u, const double *pin_pose, const unsigned char *pin, const BatchPropIn *devRow, unsigned long long call);
+static int batch_sense_core(rfsgpu_filter *f, const double *gt_pose, const double *devPose, unsigned long long call);
 extern "C" {
 // The host's new poses / covariances of a batch by copy command, through a block of the staging ring (batch_handle_wide has the stride)
 static int batch_push_poses(rfsgpu_filter *f, const double *x, const double *x_cov, int cov_stride) {
@@ -3268,6 +3285,8 @@ int rfsgpu_create_batch(rfsgpu_filter **out, int model, int n_filters, int n_per
   f->bSensorSet.assign(n_filters, 0);
   f->bSensorMaxNz.assign(n_filters, 0);
   f->bSensorCaps.assign((size_t)2 * n_filters, -1);
+  f->bTruthSet.assign(n_filters, 0);
+  f->bTruth.assign(n_filters, BatchTruth{});
   ok &= hipMalloc(&f->dBSensor, (size_t)n_filters * sizeof(BatchSensor)) == hipSuccess;
   ok &= hipMalloc(&f->dBSensorLm, (size_t)n_filters * SENSOR_MAX_LANDMARKS * 2 * sizeof(double)) == hipSuccess;
   ok &= hipMalloc(&f->dBSensorPose, (size_t)n_filters * 3 * sizeof(double)) == hipSuccess;
@@ -3860,28 +3879,37 @@ int rfsgpu_batch_propagate_async(rfsgpu_filter *f, const double *u, const double
       return RFSGPU_ERR_INVALID;
     }
   }
+  return batch_propagate_core(f, u, pin_pose, pin, nullptr, call);
+}
+// The propagation behind rfsgpu_batch_propagate_async (devRow null: the host's row goes through a block of the loop ring) and
+// rfsgpu_batch_run_truth_async (devRow: the call's row of the truth tables on the device).  The arguments have been checked.
+static int batch_propagate_core(rfsgpu_filter *f, const double *u, const double *pin_pose, const unsigned char *pin, const BatchPropIn *devRow, unsigned long long call) {
+  int rc = RFSGPU_OK;
+  const int nF = f->nF;
   hipSetDevice(f->device);
   if ((rc = batch_push_motion(f)) != RFSGPU_OK) return rc;
-  unsigned char *h = nullptr;
-  int k = 0;
-  if ((rc = ring_acquire(f, f->bLoop, &h, &k)) != RFSGPU_OK) return rc;
-  BatchPropIn *hi = reinterpret_cast<BatchPropIn *>(h);
-  for (int b = 0; b < nF; b++) {
-    BatchPropIn &I = hi[b];
-    memset(&I, 0, sizeof I);
-    memcpy(I.u, u + 3 * (size_t)b, 3 * sizeof(double));
-    I.pin = (pin && pin[b]) ? 1 : 0;
-    if (I.pin) memcpy(I.pinPose, pin_pose + 3 * (size_t)b, 3 * sizeof(double));
+  if (!devRow) {
+    unsigned char *h = nullptr;
+    int k = 0;
+    if ((rc = ring_acquire(f, f->bLoop, &h, &k)) != RFSGPU_OK) return rc;
+    BatchPropIn *hi = reinterpret_cast<BatchPropIn *>(h);
+    for (int b = 0; b < nF; b++) {
+      BatchPropIn &I = hi[b];
+      memset(&I, 0, sizeof I);
+      memcpy(I.u, u + 3 * (size_t)b, 3 * sizeof(double));
+      I.pin = (pin && pin[b]) ? 1 : 0;
+      if (I.pin) memcpy(I.pinPose, pin_pose + 3 * (size_t)b, 3 * sizeof(double));
+    }
+    HIPCHK(hipMemcpyAsync(f->dBPropIn, hi, (size_t)nF * sizeof(BatchPropIn), hipMemcpyHostToDevice, f->stream));
+    HIPCHK(hipEventRecord(f->bLoop.ev[k], f->stream));
   }
-  HIPCHK(hipMemcpyAsync(f->dBPropIn, hi, (size_t)nF * sizeof(BatchPropIn), hipMemcpyHostToDevice, f->stream));
-  HIPCHK(hipEventRecord(f->bLoop.ev[k], f->stream));
   // every particle gets its own pose covariance (handle-wide stride, as rfsgpu_batch_cycle_async sets it with x_cov [N][9])
   if (f->P.poseCovStride != 9) { f->P.poseCovStride = 9; f->bParamsDirty = true; }
   f->poseCovZero = false;
   // the new poses go to the second pose buffer and the two change places: the next cycle's births read the old ones there.  A
   // second propagation before that cycle works in place, so that the births still see the poses the last update used.
   double *dst = f->bBirthAlt ? f->B.pose : f->poseAlt;
-  batch_propagate_kernel<<<(f->N + 255) / 256, 256, 0, f->stream>>>(f->B.pose, dst, f->B.poseCov, f->dBMotion, f->dBPropIn, f->N, f->nPer,
+  batch_propagate_kernel<<<(f->N + 255) / 256, 256, 0, f->stream>>>(f->B.pose, dst, f->B.poseCov, f->dBMotion, devRow ? devRow : f->dBPropIn, f->N, f->nPer,
                                                                      (unsigned)(call & 0xffffffffull), (unsigned)(call >> 32));
   HIPCHK(hipGetLastError());
   if (!f->bBirthAlt) { f->poseAlt = f->B.pose; f->B.pose = dst; f->bBirthAlt = true; }
@@ -3913,8 +3941,9 @@ static int batch_enter_dev_route(rfsgpu_filter *f) {
   return RFSGPU_OK;
 }
 // The resampling tail behind rfsgpu_batch_resample_async (n_z: the host's counts) and rfsgpu_batch_resample_sensed_async (n_z null:
-// each filter's count is the nZ of its record on the device)
-static int batch_resample_core(rfsgpu_filter *f, const BatchCall &C, const int *n_z, unsigned long long call) {
+// each filter's count is the nZ of its record on the device).  stageIn false (the later steps of rfsgpu_batch_run_truth_async, n_z null):
+// the per-filter table on the device is still the one the run's first step staged -- thresholds and gates cannot change inside the call
+static int batch_resample_core(rfsgpu_filter *f, const BatchCall &C, const int *n_z, unsigned long long call, bool stageIn) {
   int rc = RFSGPU_OK;
   const int nF = f->nF;
   if (f->nPer > RFSGPU_BATCH_RESAMPLE_MAX_PER_FILTER) {
@@ -3930,20 +3959,22 @@ static int batch_resample_core(rfsgpu_filter *f, const BatchCall &C, const int *
   long long t0 = now_ns();
   if ((rc = batch_enter_dev_route(f)) != RFSGPU_OK) return rc;
   if ((rc = batch_push_motion(f)) != RFSGPU_OK) return rc;
-  unsigned char *h = nullptr;
-  int k = 0;
-  if ((rc = ring_acquire(f, f->bLoop, &h, &k)) != RFSGPU_OK) return rc;
-  BatchResIn *hi = reinterpret_cast<BatchResIn *>(h);
-  for (int b = 0; b < nF; b++) {
-    BatchResIn &I = hi[b];
-    I.effN = f->bEffN[2 * (size_t)b]; I.effNPercent = f->bEffN[2 * (size_t)b + 1];
-    I.nZ = n_z ? n_z[b] : 0;
-    if (f->bKind == 2) { I.minUpdates = (int)f->bFs[b].minUpdatesBeforeResample; I.minMeasurements = (int)f->bFs[b].minMeasurementsBeforeResample; }   // (a FastSLAM batch: FastSLAM.hpp:729-733)
-    else { I.minUpdates = f->bCfg[b].minUpdatesBeforeResample; I.minMeasurements = f->bCfg[b].minMeasurementsBeforeResample; }
-    I.pad = 0;
+  if (stageIn) {
+    unsigned char *h = nullptr;
+    int k = 0;
+    if ((rc = ring_acquire(f, f->bLoop, &h, &k)) != RFSGPU_OK) return rc;
+    BatchResIn *hi = reinterpret_cast<BatchResIn *>(h);
+    for (int b = 0; b < nF; b++) {
+      BatchResIn &I = hi[b];
+      I.effN = f->bEffN[2 * (size_t)b]; I.effNPercent = f->bEffN[2 * (size_t)b + 1];
+      I.nZ = n_z ? n_z[b] : 0;
+      if (f->bKind == 2) { I.minUpdates = (int)f->bFs[b].minUpdatesBeforeResample; I.minMeasurements = (int)f->bFs[b].minMeasurementsBeforeResample; }   // (a FastSLAM batch: FastSLAM.hpp:729-733)
+      else { I.minUpdates = f->bCfg[b].minUpdatesBeforeResample; I.minMeasurements = f->bCfg[b].minMeasurementsBeforeResample; }
+      I.pad = 0;
+    }
+    HIPCHK(hipMemcpyAsync(f->dBResIn, hi, (size_t)nF * sizeof(BatchResIn), hipMemcpyHostToDevice, f->stream));
+    HIPCHK(hipEventRecord(f->bLoop.ev[k], f->stream));
   }
-  HIPCHK(hipMemcpyAsync(f->dBResIn, hi, (size_t)nF * sizeof(BatchResIn), hipMemcpyHostToDevice, f->stream));
-  HIPCHK(hipEventRecord(f->bLoop.ev[k], f->stream));
   batch_resample_kernel<<<nF, BATCH_LOOP_THREADS, 0, f->stream>>>(f->B.weight, f->BL, f->dBMotion, f->dBResIn, f->nPer, call, n_z ? nullptr : f->dBFilt);
   resample_gather_kernel<<<f->N, 256, 0, f->stream>>>(f->B, f->cur, f->BL.plan, f->P.poseCovStride, 1);
   HIPCHK(hipGetLastError());
@@ -4082,15 +4113,29 @@ int rfsgpu_batch_sense_async(rfsgpu_filter *f, const double *gt_pose, unsigned l
     if (!std::isfinite(p[0]) || !std::isfinite(p[1]) || !(fabs(p[2]) <= 64.0))
       return batch_fail(f, C, "filter " + std::to_string(b) + ": the pose must be finite, its heading within +-64 rad");
   }
+  return batch_sense_core(f, gt_pose, nullptr, call);
+}
+// The scan behind rfsgpu_batch_sense_async (devPose null: the host's poses go through a block of the loop ring) and
+// rfsgpu_batch_run_truth_async (devPose: the call's row of the truth tables on the device; the generator's headings come out of atan2).
+// The arguments have been checked.
+static int batch_sense_core(rfsgpu_filter *f, const double *gt_pose, const double *devPose, unsigned long long call) {
+  int rc = RFSGPU_OK;
+  const int nF = f->nF;
   hipSetDevice(f->device);
   unsigned char *h = nullptr;
   int k = 0;
   // One block of the loop ring per call: {poses [nF][3] | counts [nF] | evalCap, useW [nF][2]} (36 bytes a filter, inside the block's
-  // size).  The block is acquired before the host's tables change, so that a failure leaves them as they were.
+  // size).  The block is acquired before the host's tables change, so that a failure leaves them as they were.  (A call with its
+  // poses on the device takes a block only when it has one of the other two tables to send.)
   static_assert(sizeof(BatchPropIn) >= 3 * sizeof(double) + 3 * sizeof(int), "a block of the loop ring holds a sense call's tables");
-  if ((rc = ring_acquire(f, f->bLoop, &h, &k)) != RFSGPU_OK) return rc;
-  memcpy(h, gt_pose, (size_t)nF * 3 * sizeof(double));
-  HIPCHK(hipMemcpyAsync(f->dBSensorPose, h, (size_t)nF * 3 * sizeof(double), hipMemcpyHostToDevice, f->stream));
+  bool needBlock = !devPose || !f->bSensed;
+  for (int b = 0; b < nF && !needBlock; b++)
+    needBlock = batch_eval_cap(f, b) != f->bSensorCaps[2 * (size_t)b] || (f->bCfg[b].useClusterProcess ? 0 : 1) != f->bSensorCaps[2 * (size_t)b + 1];
+  if (needBlock && (rc = ring_acquire(f, f->bLoop, &h, &k)) != RFSGPU_OK) return rc;
+  if (!devPose) {
+    memcpy(h, gt_pose, (size_t)nF * 3 * sizeof(double));
+    HIPCHK(hipMemcpyAsync(f->dBSensorPose, h, (size_t)nF * 3 * sizeof(double), hipMemcpyHostToDevice, f->stream));
+  }
   // ... until a sensed cycle has run, the counts of the filters' last updates as the host-fed cycles left them
   if (!f->bSensed) {
     int *hp = reinterpret_cast<int *>(h + (size_t)nF * 3 * sizeof(double));
@@ -4111,8 +4156,8 @@ int rfsgpu_batch_sense_async(rfsgpu_filter *f, const double *gt_pose, unsigned l
     memcpy(hc, f->bSensorCaps.data(), (size_t)nF * 2 * sizeof(int));
     HIPCHK(hipMemcpyAsync(f->dBSensorCaps, hc, (size_t)nF * 2 * sizeof(int), hipMemcpyHostToDevice, f->stream));
   }
-  HIPCHK(hipEventRecord(f->bLoop.ev[k], f->stream));
-  BatchSensorArg A{f->dBSensor, f->dBSensorLm, f->dBSensorPose, f->dBSensorCaps, f->dBSensorPrev, f->dBZ, f->dBFilt, f->B.err, f->dBSensorErrFilter, nF};
+  if (needBlock) HIPCHK(hipEventRecord(f->bLoop.ev[k], f->stream));
+  BatchSensorArg A{f->dBSensor, f->dBSensorLm, devPose ? devPose : f->dBSensorPose, f->dBSensorCaps, f->dBSensorPrev, f->dBZ, f->dBFilt, f->B.err, f->dBSensorErrFilter, nF};
   batch_sense_kernel<<<nF, 64, 0, f->stream>>>(A, (unsigned)(call & 0xffffffffull), (unsigned)(call >> 32));
   HIPCHK(hipGetLastError());
   f->bSenseFresh = true;
@@ -4200,17 +4245,21 @@ static inline int metric_nf(const rfsgpu_filter *f) { return f->batch ? f->nF : 
 // (FastSLAM filters, single- or multi-hypothesis: a Gaussian's weight is the log-odds of existence)
 static inline bool metric_log_odds(const rfsgpu_filter *f) { return f->bKind == 2 || f->bKind == 3; }
 // One launch into `row` ([nF] records): the call's t / gt_pose go into a slot of the pinned staging ring, which the kernel reads in place.
-static int metric_launch(rfsgpu_filter *f, const double *t, const double *gt_pose, double w_threshold, double cutoff, double order, struct rfsgpu_step_error *row) {
+// devIn (rfsgpu_batch_run_truth_async): the call's {t, pose} block is a row of the truth tables on the device instead, with a pose.
+static int metric_launch(rfsgpu_filter *f, const double *t, const double *gt_pose, double w_threshold, double cutoff, double order, struct rfsgpu_step_error *row,
+                         const double *devIn = nullptr) {
   const int nF = metric_nf(f);
   hipSetDevice(f->device);
   double *h = nullptr;
   int k = 0;
-  { const int rc = ring_acquire(f, f->stage, &h, &k); if (rc != RFSGPU_OK) return rc; }
-  for (int b = 0; b < nF; b++) {
-    h[4 * b] = t ? t[b] : 0.0;
-    for (int q = 0; q < 3; q++) h[4 * b + 1 + q] = gt_pose ? gt_pose[3 * b + q] : 0.0;
+  if (!devIn) {
+    { const int rc = ring_acquire(f, f->stage, &h, &k); if (rc != RFSGPU_OK) return rc; }
+    for (int b = 0; b < nF; b++) {
+      h[4 * b] = t ? t[b] : 0.0;
+      for (int q = 0; q < 3; q++) h[4 * b + 1 + q] = gt_pose ? gt_pose[3 * b + q] : 0.0;
+    }
   }
-  MetricArg A{h, f->dGtXY, f->dGtSeen, f->dGtN, row, w_threshold, cutoff, order, f->batch ? f->nPer : f->N, gt_pose ? 1 : 0, f->holes ? 1 : 0, metric_log_odds(f) ? 1 : 0};
+  MetricArg A{devIn ? devIn : h, f->dGtXY, f->dGtSeen, f->dGtN, row, w_threshold, cutoff, order, f->batch ? f->nPer : f->N, (gt_pose || devIn) ? 1 : 0, f->holes ? 1 : 0, metric_log_odds(f) ? 1 : 0};
   if (f->mhBatch) {     // every filter's count is a word of its cycle block, read by the kernel where it runs: nothing waits for it
     FsCycleState S0;
     mhb_view(f, f->mhbBlock, 0, S0);
@@ -4219,7 +4268,7 @@ static int metric_launch(rfsgpu_filter *f, const double *t, const double *gt_pos
     map_metric_kernel<<<nF, 64, 0, f->stream>>>(f->B, f->cur, A);
   }
   HIPCHK(hipGetLastError());
-  HIPCHK(hipEventRecord(f->stage.ev[k], f->stream));
+  if (!devIn) HIPCHK(hipEventRecord(f->stage.ev[k], f->stream));
   return RFSGPU_OK;
 }
 static int metric_args(rfsgpu_filter *f, const char *what, const double *t, double cutoff, double order) {
@@ -4266,6 +4315,8 @@ int rfsgpu_set_ground_truth(rfsgpu_filter *f, int filter, const double *xy, cons
     HIPCHK(hipMemcpy(f->dGtSeen + (size_t)filter * RFSGPU_MAX_METRIC_SET, seen.data(), (size_t)n * sizeof(double), hipMemcpyHostToDevice));
   }
   HIPCHK(hipMemcpy(f->dGtN + filter, &n, sizeof(int), hipMemcpyHostToDevice));
+  if (f->gtSet.empty()) f->gtSet.assign(nF, 0);
+  f->gtSet[filter] = 1;
   return RFSGPU_OK;
 }
 int rfsgpu_error_log_create(rfsgpu_filter *f, int log_capacity) {
@@ -4359,6 +4410,163 @@ int rfsgpu_get_map_estimate(rfsgpu_filter *f, int filter, double w_threshold, in
     k++;
   }
   if (n) *n = k;
+  return RFSGPU_OK;
+}
+
+// ---- [truth] every filter's ground truth drawn on the device, and a run of steps in one call (batch_truth.h) --------------------------
+static const BatchCall BATCH_SET_TRUTH{"batch_set_truth", 0, nullptr, nullptr};
+static const BatchCall BATCH_GENERATE_TRUTH{"batch_generate_truth", 0, nullptr, nullptr};
+static const BatchCall BATCH_GET_TRUTH{"batch_get_truth", 0, nullptr, nullptr};
+static const BatchCall BATCH_RUN_TRUTH{"batch_run_truth", 0, nullptr, nullptr};
+static int truth_check(rfsgpu_filter *f, const BatchCall &C) {
+  if (f->batch) return RFSGPU_OK;
+  f->err = std::string(C.who) + ": the device truth serves filter batches only, not " + (f->groupShard ? "a shard of an rfsgpu_group" : "an ordinary handle");
+  return RFSGPU_ERR_UNSUPPORTED;
+}
+// Landmarks that a run of k_full steps could place: the j with max(spacing j, j + 1) < k_full (batch_truth.h)
+static long long truth_landmarks_possible(int k_full, int n_landmarks) {
+  if (n_landmarks <= 0) return 0;
+  const long long sp = k_full / n_landmarks;
+  long long n = 0;
+  while (n <= RFSGPU_SENSOR_MAX_LANDMARKS && std::max(sp * n, n + 1) < k_full) n++;
+  return n;
+}
+int rfsgpu_batch_set_truth(rfsgpu_filter *f, int filter, const rfsgpu_truth_config *cfg, unsigned long long seed) {
+  CHECK_HANDLE_HOST(f);
+  const BatchCall &C = BATCH_SET_TRUTH;
+  int rc = truth_check(f, C);
+  if (rc != RFSGPU_OK) return rc;
+  if (filter < -1 || filter >= f->nF) return batch_fail(f, C, "filter index out of range");
+  if (!cfg) return batch_fail(f, C, "null configuration");
+  const double d[11] = {cfg->dt, cfg->max_dx, cfg->max_dy, cfg->max_dz, cfg->min_dx, cfg->var_odo[0], cfg->var_odo[1], cfg->var_odo[2], cfg->rmax, cfg->rmin, 0.0};
+  static const char *const dn[10] = {"dt", "max_dx", "max_dy", "max_dz", "min_dx", "var_odo[0]", "var_odo[1]", "var_odo[2]", "rmax", "rmin"};
+  for (int q = 0; q < 10; q++)
+    if (!std::isfinite(d[q]) || d[q] < 0.0) return batch_fail(f, C, std::string(dn[q]) + " must be finite and not negative");
+  const int iv[5] = {cfg->k_full, cfg->n_segments, cfg->n_landmarks, cfg->n_still, cfg->n_pinned};
+  static const char *const in[5] = {"k_full", "n_segments", "n_landmarks", "n_still", "n_pinned"};
+  for (int q = 0; q < 5; q++)
+    if (iv[q] < 0) return batch_fail(f, C, std::string(in[q]) + " must not be negative");
+  if (cfg->min_dx > cfg->max_dx) return batch_fail(f, C, "min_dx must not exceed max_dx");
+  if (!(cfg->rmin < cfg->rmax)) return batch_fail(f, C, "rmin must lie below rmax");
+  if (cfg->n_segments < 1) return batch_fail(f, C, "n_segments must be at least 1");
+  if (cfg->k_full / cfg->n_segments == 0) return batch_fail(f, C, "k_full / n_segments is 0: fewer steps than segments");
+  if (cfg->n_landmarks > 0 && cfg->k_full / cfg->n_landmarks == 0) return batch_fail(f, C, "k_full / n_landmarks is 0: fewer steps than landmarks");
+  if (truth_landmarks_possible(cfg->k_full, cfg->n_landmarks) > RFSGPU_SENSOR_MAX_LANDMARKS)
+    return batch_fail(f, C, "a run of k_full steps could place more than RFSGPU_SENSOR_MAX_LANDMARKS landmarks");
+  BatchTruth T;
+  memset(&T, 0, sizeof T);
+  T.dt = cfg->dt; T.maxDx = cfg->max_dx; T.maxDy = cfg->max_dy; T.maxDz = cfg->max_dz; T.minDx = cfg->min_dx;
+  for (int q = 0; q < 3; q++) T.sdOdoDt[q] = sqrt(cfg->var_odo[q]) * cfg->dt;
+  T.rmax = cfg->rmax; T.rmin = cfg->rmin;
+  T.seed = seed;
+  T.kFull = cfg->k_full; T.nSegments = cfg->n_segments; T.nLandmarks = cfg->n_landmarks; T.nStill = cfg->n_still; T.nPinned = cfg->n_pinned;
+  for (int b = (filter < 0 ? 0 : filter); b < (filter < 0 ? f->nF : filter + 1); b++) { f->bTruth[b] = T; f->bTruthSet[b] = 1; }
+  return RFSGPU_OK;
+}
+int rfsgpu_batch_generate_truth(rfsgpu_filter *f, int n_steps) {
+  CHECK_HANDLE(f);
+  const BatchCall &C = BATCH_GENERATE_TRUTH;
+  int rc = truth_check(f, C);
+  if (rc != RFSGPU_OK) return rc;
+  const int nF = f->nF;
+  if (n_steps < 2 || n_steps > RFSGPU_TRUTH_MAX_STEPS) return batch_fail(f, C, "n_steps must lie in 2 ... RFSGPU_TRUTH_MAX_STEPS");
+  for (int b = 0; b < nF; b++)
+    if (!f->bTruthSet[b]) return batch_fail(f, C, "filter " + std::to_string(b) + " has no truth configuration (rfsgpu_batch_set_truth)");
+  for (int b = 0; b < nF; b++)
+    if (n_steps > f->bTruth[b].kFull) return batch_fail(f, C, "filter " + std::to_string(b) + ": n_steps exceeds its k_full");
+  hipSetDevice(f->device);
+  HIPCHK(hipStreamSynchronize(f->stream));     // (a run in flight reads the tables)
+  if (!f->dTruthCfg) {
+    HIPCHK(hipMalloc(&f->dTruthCfg, (size_t)nF * sizeof(BatchTruth)));
+    HIPCHK(hipMalloc(&f->dTruthLm, (size_t)nF * SENSOR_MAX_LANDMARKS * 2 * sizeof(double)));
+    HIPCHK(hipMalloc(&f->dTruthSeen, (size_t)nF * SENSOR_MAX_LANDMARKS * sizeof(double)));
+    HIPCHK(hipMalloc(&f->dTruthCounts, (size_t)nF * 2 * sizeof(int)));
+  }
+  f->truthK = 0;     // (from here on the old tables are gone)
+  if ((size_t)n_steps > f->truthRows) {
+    hipFree(f->dTruthProp); hipFree(f->dTruthGt); hipFree(f->dTruthTgt);
+    f->dTruthProp = nullptr; f->dTruthGt = nullptr; f->dTruthTgt = nullptr;
+    f->truthRows = 0;
+    HIPCHK(hipMalloc(&f->dTruthProp, (size_t)n_steps * nF * sizeof(BatchPropIn)));
+    HIPCHK(hipMalloc(&f->dTruthGt, (size_t)n_steps * nF * 3 * sizeof(double)));
+    HIPCHK(hipMalloc(&f->dTruthTgt, (size_t)n_steps * nF * 4 * sizeof(double)));
+    f->truthRows = (size_t)n_steps;
+  }
+  HIPCHK(hipMemcpy(f->dTruthCfg, f->bTruth.data(), (size_t)nF * sizeof(BatchTruth), hipMemcpyHostToDevice));
+  BatchTruthArg A{f->dTruthCfg, f->dTruthProp, f->dTruthGt, f->dTruthTgt, f->dTruthLm, f->dTruthSeen, f->dTruthCounts, nF, n_steps};
+  batch_truth_kernel<<<nF, TRUTH_THREADS, 0, f->stream>>>(A);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(f->stream));
+  f->truthK = n_steps;
+  return RFSGPU_OK;
+}
+int rfsgpu_batch_get_truth(rfsgpu_filter *f, int filter, double *gt, double *odom, double *landmarks_xy, double *first_seen, int *n_landmarks, int *n_det_max) {
+  CHECK_HANDLE(f);
+  const BatchCall &C = BATCH_GET_TRUTH;
+  int rc = truth_check(f, C);
+  if (rc != RFSGPU_OK) return rc;
+  const int nF = f->nF, K = f->truthK;
+  if (filter < 0 || filter >= nF) return batch_fail(f, C, "filter index out of range");
+  if (K <= 0) return batch_fail(f, C, "no rfsgpu_batch_generate_truth has run on this handle");
+  hipSetDevice(f->device);
+  int cnt[2] = {0, 0};
+  HIPCHK(hipMemcpyAsync(cnt, f->dTruthCounts + 2 * (size_t)filter, sizeof cnt, hipMemcpyDeviceToHost, f->stream));
+  if (gt) HIPCHK(hipMemcpy2DAsync(gt, 3 * sizeof(double), f->dTruthGt + 3 * (size_t)filter, (size_t)nF * 3 * sizeof(double), 3 * sizeof(double), (size_t)K, hipMemcpyDeviceToHost, f->stream));
+  if (odom) HIPCHK(hipMemcpy2DAsync(odom, 3 * sizeof(double), f->dTruthProp[filter].u, (size_t)nF * sizeof(BatchPropIn), 3 * sizeof(double), (size_t)K, hipMemcpyDeviceToHost, f->stream));
+  HIPCHK(hipStreamSynchronize(f->stream));
+  const int L = std::min(std::max(cnt[0], 0), RFSGPU_SENSOR_MAX_LANDMARKS);
+  if (L > 0 && landmarks_xy) HIPCHK(hipMemcpy(landmarks_xy, f->dTruthLm + (size_t)filter * SENSOR_MAX_LANDMARKS * 2, (size_t)L * 2 * sizeof(double), hipMemcpyDeviceToHost));
+  if (L > 0 && first_seen) HIPCHK(hipMemcpy(first_seen, f->dTruthSeen + (size_t)filter * SENSOR_MAX_LANDMARKS, (size_t)L * sizeof(double), hipMemcpyDeviceToHost));
+  if (n_landmarks) *n_landmarks = L;
+  if (n_det_max) *n_det_max = cnt[1];
+  return RFSGPU_OK;
+}
+int rfsgpu_batch_run_truth_async(rfsgpu_filter *f, int k_from, int k_to, int track_errors, double w_threshold, double cutoff, double order) {
+  CHECK_HANDLE(f);
+  const BatchCall &C = BATCH_RUN_TRUTH;
+  int rc = truth_check(f, C);
+  if (rc != RFSGPU_OK) return rc;
+  if ((rc = sensor_check(f, C)) != RFSGPU_OK) return rc;
+  const int nF = f->nF;
+  if (f->truthK <= 0) return batch_fail(f, C, "no rfsgpu_batch_generate_truth has run on this handle: filter 0 (and every other) has no truth tables");
+  if (k_from < 1 || k_to < k_from || k_to > f->truthK) return batch_fail(f, C, "the steps must satisfy 1 <= k_from <= k_to <= n_steps (" + std::to_string(f->truthK) + ")");
+  // everything the per-step calls would refuse, before the first of them enqueues anything
+  for (int b = 0; b < nF; b++) {
+    if (!f->bSensorSet[b]) return batch_fail(f, C, "filter " + std::to_string(b) + " has no sensor (rfsgpu_batch_set_sensor)");
+    if (!f->bMotionSet[b]) return batch_fail(f, C, "filter " + std::to_string(b) + " has no motion parameters (rfsgpu_batch_set_motion_odometry)");
+    if (!f->bResSet[b]) return batch_fail(f, C, "filter " + std::to_string(b) + " has no resampling thresholds (rfsgpu_batch_set_resampling)");
+    if (f->bCfg[b].birthGaussianMeasurementCountThreshold != 1u) {
+      f->err = "batch_run_truth: a filter batch takes immediate births only (birthGaussianMeasurementCountThreshold 1)";
+      return RFSGPU_ERR_UNSUPPORTED;
+    }
+  }
+  if (f->nPer > RFSGPU_BATCH_RESAMPLE_MAX_PER_FILTER) {
+    f->err = "batch_run_truth: more than RFSGPU_BATCH_RESAMPLE_MAX_PER_FILTER particles per filter (one workgroup resamples a filter)";
+    return RFSGPU_ERR_UNSUPPORTED;
+  }
+  if (track_errors) {
+    if ((rc = metric_check(f, "batch_run_truth")) != RFSGPU_OK) return rc;
+    if (!(cutoff > 0) || !(order >= 1)) return batch_fail(f, C, "cutoff must be > 0 and order >= 1");
+    for (int b = 0; b < nF; b++)
+      if (f->gtSet.empty() || !f->gtSet[b]) return batch_fail(f, C, "filter " + std::to_string(b) + " has no ground truth for its step errors (rfsgpu_set_ground_truth)");
+    if (f->errLogCap <= 0) return batch_fail(f, C, "track_errors without an error log (rfsgpu_error_log_create)");
+    if (f->errLogRows + (k_to - k_from) > f->errLogCap) {
+      f->err = "batch_run_truth: the error log has fewer free rows than the run has steps (rfsgpu_error_log_read, then rfsgpu_error_log_reset)";
+      return RFSGPU_ERR_CAPACITY;
+    }
+  }
+  for (int k = k_from; k < k_to; k++) {
+    const size_t row = (size_t)k * nF;
+    const unsigned long long call = (unsigned long long)k;
+    if ((rc = batch_propagate_core(f, nullptr, nullptr, nullptr, f->dTruthProp + row, call)) != RFSGPU_OK) return rc;
+    if ((rc = batch_sense_core(f, nullptr, f->dTruthGt + 3 * row, call)) != RFSGPU_OK) return rc;
+    if ((rc = rfsgpu_batch_cycle_sensed_async(f, 1, nullptr, nullptr, 0, 1)) != RFSGPU_OK) return rc;
+    if ((rc = batch_resample_core(f, BATCH_RESAMPLE_SENSED, nullptr, call, k == k_from)) != RFSGPU_OK) return rc;
+    if (track_errors) {
+      if ((rc = metric_launch(f, nullptr, nullptr, w_threshold, cutoff, order, f->dErrLog + (size_t)f->errLogRows * nF, f->dTruthTgt + 4 * row)) != RFSGPU_OK) return rc;
+      f->errLogRows++;
+    }
+  }
   return RFSGPU_OK;
 }
 

@@ -320,6 +320,12 @@ def sensor_max_nz(data, P=C1_SIM, margin=2):
     if len(lm):
         r = np.hypot(lm[None, :, 0] - gt[1:, None, 0], lm[None, :, 1] - gt[1:, None, 1])
         n_det = int(((r >= P["rmin"]) & (r <= P["rmax"])).sum(axis=1).max()) if len(r) else 0
+    return sensor_max_nz_of(n_det, P, margin)
+
+
+def sensor_max_nz_of(n_det, P=C1_SIM, margin=2):
+    """sensor_max_nz from its first term, the most landmarks in range at any step (the device truth's n_det_max, or the count
+    sensor_max_nz takes along data["gt"]): + the clutter quantile + margin, at most capi.MAX_Z."""
     mean = P["clutter"] * (2 * np.pi * (P["rmax"] - P["rmin"]))
     e = np.exp(-mean)
     cmf, p, fact, n_c = e, 1.0, 1.0, 0
@@ -351,6 +357,19 @@ def configure_batch_filter(batch, b, P=C1_SIM):
     return cfg
 
 
+def truth_config(P=C1_SIM, b=None):
+    """The generation keys of a configuration dict like C1_SIM as a capi.TruthConfig (rfsgpu_batch_set_truth): k_full = P["kmax"], the
+    50 still and 100 pinned steps of generate() and the run loop.  b (a filter index, optional) is for the caller's bookkeeping only: a
+    configuration does not depend on the filter's place."""
+    c = capi.TruthConfig()
+    c.k_full, c.n_segments, c.n_landmarks = int(P["kmax"]), int(P["n_segments"]), int(P["n_landmarks"])
+    c.n_still, c.n_pinned = 50, 100
+    c.dt, c.max_dx, c.max_dy, c.max_dz, c.min_dx = P["dt"], P["max_dx"], P["max_dy"], P["max_dz"], P["min_dx"]
+    c.var_odo[0], c.var_odo[1], c.var_odo[2] = P["vardx"], P["vardy"], P["vardz"]
+    c.rmax, c.rmin = P["rmax"], P["rmin"]
+    return c
+
+
 class Sim2dBatchRun:
     """run() :540-643 for MANY independent filters, each with its own realisation (`datas[b]`, its own generate(traj_seed=...)), its
     own configuration dict `Ps[b]` and its own host RNG stream (`seeds[b]`: process noise, resampling draws).  `target` is either a
@@ -374,11 +393,27 @@ class Sim2dBatchRun:
 
     fastslam=True: the loop of src/fastslam2dSim.cpp:530-600 instead -- the same flow with FastSLAM::predict (propagation, static
     landmark step, no births) and FastSLAM::update; `target` is a FastSLAMBatch or a list of FastSLAM handles (or oracle filters),
-    `Ps` dicts like C1_FASTSLAM_SIM.  A filter whose scan is empty is neither updated nor normalised that step (FastSLAM.hpp:402-403)."""
+    `Ps` dicts like C1_FASTSLAM_SIM.  A filter whose scan is empty is neither updated nor normalised that step (FastSLAM.hpp:402-403).
 
-    def __init__(self, target, datas, Ps, seeds, track_errors=False, device_loop=False, fastslam=False, device_sensor=False):
+    device_truth=True (an RB-PHD FilterBatch; implies device_loop and device_sensor; datas=None, kmax = the steps to generate): the
+    ground truth is the device's as well ([truth] in include/rfsgpu.h).  Each filter's generation keys come from Ps[b]
+    (truth_config) under the key seeds[b]; one generate_truth draws every trajectory, and the landmarks, first-seen times and
+    n_det_max are read back once, for the sensors (max_nz = sensor_max_nz_of(n_det_max)) and the metric's ground truth.  run() is
+    then ONE run_truth_async -- the loop over steps is the library's -- and errors() the one read.  The realisations are not
+    generate()'s: the same model under another generator, as with the device loop."""
+
+    def __init__(self, target, datas, Ps, seeds, track_errors=False, device_loop=False, fastslam=False, device_sensor=False, device_truth=False,
+                 kmax=None):
         """track_errors: as in Sim2dRun -- each filter's ground truth is uploaded, every cycle ends with one step_error_async (one
         launch for the whole batch; one per handle otherwise), errors() reads the log(s) once at the end."""
+        self.device_truth = bool(device_truth)
+        if self.device_truth:
+            assert datas is None and kmax is not None and not fastslam and isinstance(target, capi.CBatch), "device_truth: an RB-PHD FilterBatch, datas=None, kmax given"
+            device_loop = device_sensor = True
+            for b, P in enumerate(Ps):
+                target.set_truth(b, truth_config(P, b), seeds[b])
+            target.generate_truth(int(kmax))
+            datas = [target.get_truth(b, trajectory=False) for b in range(len(Ps))]      # landmarks, first_seen, n_det_max: the one read
         self.device_loop = bool(device_loop)
         self.device_sensor = bool(device_sensor)
         assert not self.device_sensor or (self.device_loop and not fastslam), "the device sensor serves the device loop of an RB-PHD FilterBatch"
@@ -416,7 +451,7 @@ class Sim2dBatchRun:
         if self.track_errors:
             rows = int(min(d["K"] for d in self.datas))
             for b, (d, P) in enumerate(zip(self.datas, self.Ps)):
-                fs = first_seen_times(d, P)
+                fs = d["first_seen"] if self.device_truth else first_seen_times(d, P)
                 if self.batch is not None:
                     self.batch.set_ground_truth(d["landmarks"], fs, filter=b)
                 else:
@@ -436,6 +471,11 @@ class Sim2dBatchRun:
         for b in range(nF):
             self.batch.set_motion_odometry(b, np.diag(self.Q[b]), seeds[b])
             self.batch.set_resampling(b, self.eff_n[b], self.eff_n[b] / self.n)
+        if self.device_truth:       # no per-step host table at all: the steps' inputs are rows of the truth tables on the device
+            for b, (d, P) in enumerate(zip(self.datas, self.Ps)):
+                self.batch.set_sensor(b, np.diag([P["varzr"], P["varzb"]]), P["Pd"], P["clutter"], P["rmax"], P["rmin"], d["landmarks"],
+                                      max_nz=sensor_max_nz_of(d["n_det_max"], P), seed=seeds[b])
+            return
         self._u = np.ascontiguousarray(np.stack([d["odom"][:K] for d in self.datas], axis=1))          # [K, nF, 3]
         self._gt = np.ascontiguousarray(np.stack([d["gt"][:K] for d in self.datas], axis=1))
         self._t = np.array([[k * P["dt"] for P in self.Ps] for k in range(K)])
@@ -492,6 +532,10 @@ class Sim2dBatchRun:
         return self.batch.resample_counts() if self.device_loop else self.n_resamples.copy()
 
     def step(self, k):
+        if self.device_truth:
+            self.batch.run_truth_async(k, k + 1, self.track_errors, ERROR_W_THRESHOLD, ERROR_CUTOFF, ERROR_ORDER)
+            self.last_n_z = None
+            return None
         if self.device_loop:
             return self._device_step(k)
         fired = self._step(k)
@@ -570,7 +614,12 @@ class Sim2dBatchRun:
         return fired
 
     def run(self, k_from=1, k_to=None, on_step=None):
-        for k in range(k_from, int(k_to or min(d["K"] for d in self.datas))):
+        k_to = int(k_to or min(d["K"] for d in self.datas))
+        if self.device_truth and on_step is None:      # the loop over steps is the library's: one call
+            self.batch.run_truth_async(k_from, k_to, self.track_errors, ERROR_W_THRESHOLD, ERROR_CUTOFF, ERROR_ORDER)
+            self.last_n_z = None
+            return self
+        for k in range(k_from, k_to):
             fired = self.step(k)
             if on_step is not None:
                 on_step(k, self, fired)

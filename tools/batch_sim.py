@@ -24,6 +24,11 @@ invocation, the setup time (sim2d_driver.generate + packing, or generate(measure
 separately, with all --reps repetitions and their medians, and filter-steps/s without and with the setup.  --errors / --results / --json
 work as elsewhere (the filters listed are the device-sensor route's).
 
+--device-truth (RB-PHD batches; implies --device-loop --device-sensor, refused with --fastslam and --mhfastslam): per batch size the
+device loop with device-made scans on a host-made ground truth (generate(measurements=False): the "device_scans" route above) against
+the same loop on a device-made ground truth (Sim2dBatchRun(device_truth=True): set_truth + one generate_truth, the landmarks read back
+once for the sensors, and the whole run ONE rfsgpu_batch_run_truth_async).  Setup and run time of each route as with --device-sensor.
+
 --fastslam: the same table for the FastSLAM half of a comparison sweep (the reference's fastslam2dSim over the same grid): a
 FastSLAMBatch (rfsgpu_batch_fastslam_cycle_async) against FastSLAM handles stepped in turn (predict_map, fastslam_update, normalise,
 resample per handle), host loop / device loop, --errors.  Every line then carries "filter": "fastslam".
@@ -330,41 +335,52 @@ def sensor_sweep(pkg, a, sizes):
     seeds = [100 + b for b in range(max(sizes))]
     kmax = a.steps + 2
     rows = []
+    routes = ("device", "truth") if a.device_truth else ("host", "device")
     for B in sizes:
         row = dict(B=B, particles=a.particles, steps=a.steps, loop="device", reps=max(1, a.reps))
-        for route in ("host", "device"):
+        for route in routes:
             setup, run_t = [], []
             for _ in range(max(1, a.reps)):
                 batch = pkg.FilterBatch(B, a.particles, gm_capacity=a.capacity)
                 batch.synchronize()
                 t0 = time.perf_counter()
-                datas = [sim.generate(Ps[b], traj_seed=1 + b, kmax=kmax, measurements=(route == "host")) for b in range(B)]
-                rb = sim.Sim2dBatchRun(batch, datas, Ps[:B], seeds[:B], track_errors=a.errors, device_loop=True, device_sensor=(route == "device"))
+                if route == "truth":
+                    rb = sim.Sim2dBatchRun(batch, None, Ps[:B], seeds[:B], track_errors=a.errors, device_truth=True, kmax=kmax)
+                else:
+                    datas = [sim.generate(Ps[b], traj_seed=1 + b, kmax=kmax, measurements=(route == "host")) for b in range(B)]
+                    rb = sim.Sim2dBatchRun(batch, datas, Ps[:B], seeds[:B], track_errors=a.errors, device_loop=True, device_sensor=(route == "device"))
                 setup.append(time.perf_counter() - t0)
                 rb.step(1)
                 batch.synchronize()
                 t0 = time.perf_counter()
-                for k in range(2, a.steps + 2):
-                    rb.step(k)
+                if route == "truth":
+                    rb.run(2, a.steps + 2)            # one call: the loop over steps is the library's
+                else:
+                    for k in range(2, a.steps + 2):
+                        rb.step(k)
                 if a.errors:
                     log = rb.errors()               # the one read (it also waits for the queued work)
                 else:
                     batch.synchronize()
                 run_t.append(time.perf_counter() - t0)
-                if route == "device":
-                    row["resamples_device_scans"] = rb.resample_counts().tolist()
+                if route == routes[-1]:
+                    row["resamples_device_" + ("truth" if route == "truth" else "scans")] = rb.resample_counts().tolist()
                     if a.errors:
                         row["filters"] = filter_rows(log, Ps, B)
                 batch.close()
-            key = route + "_scans_"
+            key = "device_truth_" if route == "truth" else route + "_scans_"
             row[key + "setup_s"], row[key + "setup_s_reps"] = float(np.median(setup)), setup
             row[key + "run_s"], row[key + "run_s_reps"] = float(np.median(run_t)), run_t
             row[key + "filter_steps_per_s"] = B * a.steps / row[key + "run_s"]
             row[key + "filter_steps_per_s_with_setup"] = B * a.steps / (row[key + "setup_s"] + row[key + "run_s"])
             if route == "host":
                 row["host_scans_packed_bytes_per_step"] = int(B * pkg.capi.MAX_Z * 2 * 8 + B * 4)
-        row["device_over_host_scans_run"] = row["host_scans_run_s"] / row["device_scans_run_s"]
-        row["device_over_host_scans_with_setup"] = (row["host_scans_setup_s"] + row["host_scans_run_s"]) / (row["device_scans_setup_s"] + row["device_scans_run_s"])
+        if a.device_truth:
+            row["device_over_host_truth_run"] = row["device_scans_run_s"] / row["device_truth_run_s"]
+            row["device_over_host_truth_with_setup"] = (row["device_scans_setup_s"] + row["device_scans_run_s"]) / (row["device_truth_setup_s"] + row["device_truth_run_s"])
+        else:
+            row["device_over_host_scans_run"] = row["host_scans_run_s"] / row["device_scans_run_s"]
+            row["device_over_host_scans_with_setup"] = (row["host_scans_setup_s"] + row["host_scans_run_s"]) / (row["device_scans_setup_s"] + row["device_scans_run_s"])
         rows.append(row)
         print(json.dumps({k: v for k, v in row.items() if k != "filters"}), flush=True)
     if a.errors:
@@ -393,12 +409,17 @@ def main():
     ap.add_argument("--device-loop", action="store_true", help="the batch's whole cycle on the device (propagation and resampling included)")
     ap.add_argument("--both-loops", action="store_true", help="host loop and device loop side by side")
     ap.add_argument("--device-sensor", action="store_true", help="the device loop with host-made scans against device-made scans (rfsgpu_batch_sense_async): setup and run time of each")
+    ap.add_argument("--device-truth", action="store_true", help="the device loop with device scans on a host-made ground truth against a device-made one run in one call (rfsgpu_batch_generate_truth, rfsgpu_batch_run_truth_async)")
     ap.add_argument("--fastslam", action="store_true", help="FastSLAM filters: a FastSLAMBatch against FastSLAM handles stepped in turn")
     ap.add_argument("--reps", type=int, default=1, help="timed repetitions of every batch figure")
     ap.add_argument("--mhfastslam", action="store_true", help="multi-hypothesis FastSLAM filters: an MHFastSLAMBatch against handles on the device cycle stepped in turn")
     ap.add_argument("--results", default="", help="--errors: write one line per filter of the largest batch, 'Pd  c  posError  mapError' (the final row's pose_ed and cola)")
     ap.add_argument("--max-per-filter", type=int, default=0, help="--mhfastslam: particle slots per filter (default nParticlesMax x hypotheses = 9 x particles, which cannot overflow; at most 2048)")
     a = ap.parse_args()
+    if a.device_truth and (a.fastslam or a.mhfastslam):
+        ap.error("--device-truth serves RB-PHD batches (rfsgpu_batch_run_truth_async refuses FastSLAM and multi-hypothesis FastSLAM batches)")
+    if a.device_truth:
+        a.device_loop = a.device_sensor = True
     if a.device_sensor and (a.fastslam or a.mhfastslam):
         ap.error("--device-sensor serves RB-PHD batches (the sensor section refuses FastSLAM and multi-hypothesis FastSLAM batches)")
     pkg = load_pkg()
