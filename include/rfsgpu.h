@@ -46,7 +46,7 @@
  *   [batch]    many independent 2-D filters in one handle, stepped together in one launch chain;
  *   [metric]   per-step OSPA / COLA map error and pose error computed on the device, kept in a device-side log;
  *   [resample] ParticleFilter::resample for an ordinary handle of any size on the device, without a host stop;
- *   [sensor]   the simulator's range-bearing sensor of every filter of an RB-PHD batch drawn on the device, for batch sweeps;
+ *   [sensor]   the simulator's range-bearing sensor of every filter of a batch (RB-PHD; FastSLAM kinds by a switch) drawn on the device, for batch sweeps;
  *   [truth]    the simulator's trajectory, odometry and landmarks of every filter of a batch drawn on the device, and a run of steps in one call.
  * A maintainer wiring the reference to the library reads the CORE entries and INTEGRATION.md; nothing optional is required
  * for correct results.
@@ -983,8 +983,9 @@ int rfsgpu_last_resample(rfsgpu_filter *f, int *fired, double *n_eff, int *n_aft
  * A set beyond max_nz is cut to its first max_nz entries (detections before clutter) and reported through the device error word: the
  * next synchronising call returns RFSGPU_ERR_CAPACITY once, and rfsgpu_last_error names the lowest such filter and its scan.
  * Every call of the section returns RFSGPU_ERR_UNSUPPORTED, with a message and the state untouched, on an ordinary handle, a shard of
- * an rfsgpu_group, a batch of FastSLAM filters and a batch of multi-hypothesis FastSLAM filters: their per-filter records carry
- * host-computed, count-dependent parameters.
+ * an rfsgpu_group and -- until rfsgpu_batch_fastslam_serve_sensor below switches the section on for it -- a batch of FastSLAM
+ * filters and a batch of multi-hypothesis FastSLAM filters: their per-filter records carry three count-dependent fields, which only
+ * the sensed cycle of their own kind derives on the device.
  *
  * Filter `filter`'s (-1: every filter's) simulated sensor: model = ITS R, probabilityOfDetection, uniformClutterIntensity and range
  * limits (rangeLimBuffer is not read; the filter's own model, rfsgpu_batch_configure, usually has an inflated R), landmarks_xy
@@ -1019,6 +1020,36 @@ int rfsgpu_batch_resample_sensed_async(rfsgpu_filter *f, unsigned long long call
 /* The sets of the last rfsgpu_batch_sense_async: z [n_filters][RFSGPU_MAX_Z][2] (zeros beyond a filter's set), n_z [n_filters].
  * Synchronising, for tests and logging; a scan that was cut is reported here like by any synchronising call, with the outputs filled. */
 int rfsgpu_batch_last_scan(rfsgpu_filter *f, double *z, int *n_z);
+/* The section's switch for the other two kinds of batch: a batch of FastSLAM filters (rfsgpu_batch_set_fastslam_config or
+ * rfsgpu_batch_fastslam_cycle_async has run) and a batch made by rfsgpu_create_batch_mh.  Off at creation; on = 0 restores the
+ * refusals, and is itself refused with RFSGPU_ERR_INVALID once a sensed cycle has run on the handle.  RFSGPU_ERR_UNSUPPORTED, naming
+ * which: an RB-PHD batch (it is served as it is), a batch whose kind is not decided yet, an ordinary handle, a shard of an
+ * rfsgpu_group.  Synchronising.  With the switch on
+ *   rfsgpu_batch_set_sensor, rfsgpu_batch_sense_async and rfsgpu_batch_last_scan serve the batch unchanged (the same kernel, the same
+ *     draws, filter b's set at b * 2 * RFSGPU_MAX_Z of the measurement table);
+ *   rfsgpu_batch_resample_sensed_async serves a FastSLAM batch after its sensed cycle and refuses a multi-hypothesis batch, which
+ *     resamples inside its cycle;
+ *   rfsgpu_batch_cycle_sensed_async keeps refusing both kinds (RFSGPU_ERR_UNSUPPORTED) and names the call of the kind below;
+ *   rfsgpu_batch_run_truth_async ([truth]) serves both kinds.
+ * A kind's per-filter record is configuration but for three fields: pfa = clutterIntensityIntegral / n_z (uniformClutterIntensity *
+ * 2 pi (rangeLimMax - rangeLimMin) on the host, one correctly rounded division by the count on the device: the host-fed cycle's bits),
+ * prune = n_z >= pruningMeasurementsThreshold, and the multi-hypothesis cycle's draw.  One kernel at the head of a sensed cycle, one
+ * lane per filter, derives them from the sense call's records and a table of the static fields that is staged only when a
+ * configuration has changed -- at the CYCLE, so a rfsgpu_batch_set_fastslam_config / rfsgpu_batch_configure between the sense call and
+ * the cycle holds from this cycle on, as with the host-fed cycle (there is no "sense again" refusal here).  Results do not depend on
+ * a sensor's max_nz.  Once a sensed cycle has returned RFSGPU_OK the filters' counts live on the device: the host-fed cycle of the
+ * kind and rfsgpu_batch_resample_async return RFSGPU_ERR_UNSUPPORTED on this handle (host-fed cycles BEFORE the first sensed one are
+ * allowed), and rfsgpu_batch_fastslam_last_cycle takes each filter's last count from the device records in its own read-back. */
+int rfsgpu_batch_fastslam_serve_sensor(rfsgpu_filter *f, int on);
+/* rfsgpu_batch_fastslam_cycle_async on the sets the last rfsgpu_batch_sense_async left (predict, x, x_cov, cov_stride, normalize as
+ * there).  Puts the handle on the device route, as rfsgpu_batch_cycle_sensed_async does.  RFSGPU_ERR_INVALID, naming the filter: no
+ * rfsgpu_batch_sense_async since the last cycle or the last rfsgpu_batch_set_sensor, a filter without a sensor.
+ * RFSGPU_ERR_UNSUPPORTED: the switch is off, a batch of another kind (the text names its call). */
+int rfsgpu_batch_fastslam_cycle_sensed_async(rfsgpu_filter *f, int predict, const double *x, const double *x_cov, int cov_stride, int normalize);
+/* rfsgpu_batch_fastslam_mh_cycle_async likewise.  Filter b's u01 is the resampling draw of (its motion key, call): 53 bits of words
+ * 0, 1 of Philox block (0, 2, call low word, call high word) over 2^53, the draw rfsgpu_batch_resample_async makes.  Refusals as
+ * above, and RFSGPU_ERR_INVALID for a filter without rfsgpu_batch_set_motion_odometry (it has no key).  Nothing waits for the GPU. */
+int rfsgpu_batch_fastslam_mh_cycle_sensed_async(rfsgpu_filter *f, int predict, const double *x, const double *x_cov, int cov_stride, unsigned long long call);
 /* [test] Bytes of LDS that a workgroup of the step kernel had in the last cycle of this batch (host-fed or sensed; 0 before the
  * first) -- so that a test can say that two max_nz bounds gave two launch sizes and the same results.  Any batch; never waits. */
 int rfsgpu_batch_last_cycle_lds(rfsgpu_filter *f, long long *bytes);
@@ -1078,8 +1109,12 @@ int rfsgpu_batch_get_truth(rfsgpu_filter *f, int filter, double *gt, double *odo
  * (predict 1, no new poses, normalize 1), the sensed resampling (call k) and, with track_errors != 0, one row of the error log with
  * t = k dt and gt[k] (w_threshold, cutoff, order as rfsgpu_step_error_async).  Everything is enqueued here and stream-ordered;
  * nothing is read back, and device-side errors (gm_capacity, a cut scan) surface at the next synchronising call.  The same kernels
- * with the same arguments as the per-step calls: the same bits.  Refused before anything is enqueued -- RFSGPU_ERR_UNSUPPORTED: a
- * batch of FastSLAM or multi-hypothesis FastSLAM filters (as the [sensor] section refuses them), delayed births, more than
+ * with the same arguments as the per-step calls: the same bits.  A batch of FastSLAM filters with rfsgpu_batch_fastslam_serve_sensor
+ * on runs the same sequence with its own sensed cycle (rfsgpu_batch_fastslam_cycle_sensed_async); a multi-hypothesis batch with the
+ * switch on runs propagation, scan, rfsgpu_batch_fastslam_mh_cycle_sensed_async with call k (its resampling is inside the cycle; the
+ * thresholds of rfsgpu_batch_set_resampling have defaults there) and the log row, which needs rfsgpu_batch_mh_serve_metrics.
+ * Refused before anything is enqueued -- RFSGPU_ERR_UNSUPPORTED: a batch of FastSLAM or multi-hypothesis FastSLAM filters whose
+ * switch is off (as the [sensor] section refuses them), delayed births (RB-PHD), more than
  * RFSGPU_BATCH_RESAMPLE_MAX_PER_FILTER particles per filter; RFSGPU_ERR_INVALID, naming the filter: no rfsgpu_batch_generate_truth
  * yet, a range outside [1, n_steps], a filter without sensor, motion parameters or resampling thresholds, track_errors with a filter
  * that has no ground truth (rfsgpu_set_ground_truth) or without an error log; RFSGPU_ERR_CAPACITY: a log with fewer free rows than

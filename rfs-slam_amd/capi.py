@@ -153,6 +153,7 @@ ABI_SYMBOLS = [
     "resample_async", "last_resample", "get_pose_covs",
     "batch_set_sensor", "batch_sense_async", "batch_cycle_sensed_async", "batch_resample_sensed_async", "batch_last_scan", "batch_last_cycle_lds",
     "batch_set_truth", "batch_generate_truth", "batch_get_truth", "batch_run_truth_async",
+    "batch_fastslam_serve_sensor", "batch_fastslam_cycle_sensed_async", "batch_fastslam_mh_cycle_sensed_async",
 ]
 
 _dp = np.ctypeslib.ndpointer(dtype=np.float64, flags="C_CONTIGUOUS")
@@ -913,6 +914,28 @@ class CBatch(CFilter):
         """rfsgpu_batch_resample_sensed_async: resample_async with the measurement counts the device holds."""
         self._call("batch_resample_sensed_async", C.c_ulonglong(int(call)))
 
+    def serve_sensor(self, on=True):
+        """rfsgpu_batch_fastslam_serve_sensor (synchronising): from now on set_sensor, sense_async, last_scan and run_truth_async serve
+        this batch of FastSLAM filters (or, on a CBatchMH, of multi-hypothesis FastSLAM filters), resample_sensed_async a FastSLAM
+        batch; on=False: they refuse again (refused itself once a sensed cycle has run)."""
+        self._call("batch_fastslam_serve_sensor", C.c_int(1 if on else 0))
+
+    def _pose_args(self, poses, pose_cov):
+        """(x, x_cov, cov_stride) of a cycle call as ctypes arguments; the arrays ride along so that they outlive the call."""
+        x = None if poses is None else _f64(poses, (self.n, 3))
+        stride = 0
+        cv = None
+        if pose_cov is not None:
+            cv = _f64(pose_cov)
+            assert cv.size in (9, 9 * self.n)
+            stride = 0 if cv.size == 9 else 9
+        return C.c_void_p(None) if x is None else self._ptr(x), C.c_void_p(None) if cv is None else self._ptr(cv), C.c_int(stride), (x, cv)
+
+    def fastslam_cycle_sensed_async(self, predict, poses=None, pose_cov=None, normalize=True):
+        """rfsgpu_batch_fastslam_cycle_sensed_async: batch_fastslam_cycle_async on the sets the last sense_async left on the device."""
+        px, pc, stride, keep = self._pose_args(poses, pose_cov)
+        self._call("batch_fastslam_cycle_sensed_async", C.c_int(-1 if predict is None else (1 if predict else 0)), px, pc, stride, C.c_int(1 if normalize else 0))
+
     def last_scan(self):
         """The sets of the last sense_async as a list of [n_z, 2] arrays, one per filter (synchronising)."""
         z = np.zeros((self.n_filters, MAX_Z, 2))
@@ -1018,6 +1041,12 @@ class CBatchMH(CBatch):
             stride = 0 if cv.size == 9 else 9
         self._call("batch_fastslam_mh_cycle_async", C.c_int(1 if predict else 0), C.c_void_p(None) if x is None else self._ptr(x),
                    C.c_void_p(None) if cv is None else self._ptr(cv), C.c_int(stride), self._ptr(z), self._ptr(nz), self._ptr(u))
+
+    def fastslam_mh_cycle_sensed_async(self, predict, call, poses=None, pose_cov=None):
+        """rfsgpu_batch_fastslam_mh_cycle_sensed_async: the multi-hypothesis cycle on the sets the last sense_async left on the device;
+        every filter's draw is the resampling draw of (its motion key, call)."""
+        px, pc, stride, keep = self._pose_args(poses, pose_cov)
+        self._call("batch_fastslam_mh_cycle_sensed_async", C.c_int(1 if predict else 0), px, pc, stride, C.c_ulonglong(int(call)))
 
     def batch_fastslam_last_cycle(self):
         """rfsgpu_batch_fastslam_last_cycle (synchronising): per filter the counts after the update and after the resampling, whether it

@@ -31,6 +31,7 @@
 #include "batch_loop.h"
 #include "batch_sensor.h"
 #include "batch_truth.h"
+#include "fastslam_sensed.h"
 #include "resample_plan.h"
 
 namespace {
@@ -264,6 +265,12 @@ struct rfsgpu_filter {
   bool mhbPending = false;                     // cycles are enqueued: the counts, ids and flags on the host are behind the device
   bool mhbHave = false;                        // a cycle has run
   std::vector<int> mhbLastNZ;                  // [nF] the last enqueued cycle's measurement counts
+  // the device sensor on a FastSLAM / multi-hypothesis batch (rfsgpu_batch_fastslam_serve_sensor; fastslam_sensed.h)
+  bool mhbLastSensed = false;                  // the last enqueued multi-hypothesis cycle was a sensed one: mhb_resolve reads mhbLastNZ back from its records
+  bool bServeSensor = false;                 // the switch: the [sensor] and [truth] calls serve this batch
+  void *dFsTmpl = nullptr;                     // [nF] FsSensedTemplate<FsBatchFilter | MhBatchFilter>: the records' static part (allocated by the switch)
+  std::vector<unsigned char> bFsTmplHost;      // the table as the device holds it (empty: not staged yet)
+  int *dFsLastNZ = nullptr, *hFsLastNZ = nullptr;   // [nF] a multi-hypothesis batch: the counts of the last sensed cycle's records, compact on the device | pinned, where mhb_resolve lands them
   bool mhbMetrics = false;                     // rfsgpu_batch_mh_serve_metrics: the [metric] calls serve this batch (the kernel's live-count form)
   // [metric] per-step map / pose error (map_metric.h): ground truth per filter, the device-side log, one row for the synchronous calls
   double *dGtXY = nullptr, *dGtSeen = nullptr;   // [nF][RFSGPU_MAX_METRIC_SET][2], [nF][RFSGPU_MAX_METRIC_SET] (allocated by the first rfsgpu_set_ground_truth)
@@ -611,7 +618,7 @@ void rfsgpu_destroy(rfsgpu_filter *f) {
   hipFree(B.scan); hipFree(B.candMean); hipFree(B.candCov); hipFree(B.candSup); hipFree(B.candChk); hipFree(B.candCount);
   murty_free(f->Q, f->MS);
   hipFree(f->dBFilt); hipFree(f->dBParams); hipFree(f->dBZ); hipFree(f->dBZPrev); hipFree(f->dBSums); hipFree(f->dBErrFilter); hipFree(f->dBMaskTmp); hipFree(f->dBInhSrc);
-  hipFree(f->dFsFilt);
+  hipFree(f->dFsFilt); hipFree(f->dFsTmpl); hipFree(f->dFsLastNZ); if (f->hFsLastNZ) hipHostFree(f->hFsLastNZ);
   hipFree(f->dMhFilt); hipFree(f->mhbBlock); if (f->hMhbBlock) hipHostFree(f->hMhbBlock);
   hipFree(f->dBMotion); hipFree(f->dBPropIn); hipFree(f->dBResIn); hipFree(f->BL.counters); hipFree(f->BL.nResamples); hipFree(f->BL.resampled);
   hipFree(f->BL.fired); hipFree(f->BL.nEff); hipFree(f->BL.plan); hipFree(f->BL.pid); hipFree(f->BL.ppid);
@@ -2573,13 +2580,15 @@ int rfsgpu_get_fastslam_config(const rfsgpu_filter *f, rfsgpu_fastslam_config *c
   return RFSGPU_OK;
 }
 // (one expression for a handle and for every filter of a batch: a filter's bits do not depend on being in a batch)
+// clutterIntensityIntegral(nZ) (:561-562): c * sensing area (RngBrg.cpp:175-178) or the expected clutter number (VictoriaPark).  One
+// function for the host-fed records and the sensed cycle's template (fastslam_sensed.h), whose kernel does the division below.
+static double fs_pfa_num(const Params &P, int D) { return (D == 2) ? P.clutter * (2 * RFS_PI * (P.rmax - P.rmin)) : P.vpExpClutter; }
 static FsParams fs_params_of(const rfsgpu_fastslam_config &fs, const Params &P, int D, int n_z) {
   FsParams F;
   F.prior = fs.landmarkExistencePrior;
   F.minLog = fs.minLogMeasurementLikelihood;
   F.lockW = fs.landmarkLockWeight;
-  // clutterIntensityIntegral(nZ) / nZ (:561-562): c * sensing area (RngBrg.cpp:175-178) or the expected clutter number (VictoriaPark)
-  F.pfa = ((D == 2) ? P.clutter * (2 * RFS_PI * (P.rmax - P.rmin)) : P.vpExpClutter) / n_z;
+  F.pfa = fs_pfa_num(P, D) / n_z;     // clutterIntensityIntegral(nZ) / nZ
   F.newW = log(F.prior / (1 - F.prior));
   F.supportD2 = fs.landmarkCandidateMeasurementSupportDist * fs.landmarkCandidateMeasurementSupportDist;
   F.countThr = fs.landmarkCandidateMeasurementCountThreshold;
@@ -3210,7 +3219,43 @@ static int batch_push_params(rfsgpu_filter *f) {
   f->bParamsDirty = false;
   return RFSGPU_OK;
 }
+// The records of a sensed FastSLAM / multi-hypothesis cycle (fastslam_sensed.h): the Params table when it is behind, the template table
+// when a filter's static part has changed since the device got it (fill(record, b) writes that part, as it does for batch_push_tables),
+// then the one launch that makes dRec from the sensor's records.  call: the multi-hypothesis cycle's draw counter.
+template <class Rec, class Fill>
+static int batch_sensed_records(rfsgpu_filter *f, Rec *dRec, unsigned long long call, Fill fill) {
+  typedef FsSensedTemplate<Rec> Tmpl;
+  static_assert(sizeof(Tmpl) <= sizeof(Rec) + sizeof(Params), "a block of the staging ring holds the template table");
+  const int nF = f->nF;
+  int rc = batch_push_params(f);     // (first: a record's pfaNum comes from bParamsHost)
+  if (rc != RFSGPU_OK) return rc;
+  std::vector<unsigned char> now((size_t)nF * sizeof(Tmpl), 0);     // (zeroed: the padding is compared and travels too)
+  Tmpl *t = reinterpret_cast<Tmpl *>(now.data());
+  for (int b = 0; b < nF; b++) {
+    fill(t[b].rec, b);
+    t[b].rec.F.pfa = 0.0;     // (derived on the device, like nZ, zOff, prune and u01, which fill leaves at zero)
+    t[b].pfaNum = fs_pfa_num(f->bParamsHost[b], 2);
+    t[b].pruneThr = f->bFs[b].pruningMeasurementsThreshold;
+  }
+  if (now != f->bFsTmplHost) {
+    unsigned char *h = nullptr;
+    int k = 0;
+    if ((rc = ring_acquire(f, f->bStage, &h, &k)) != RFSGPU_OK) return rc;
+    memcpy(h, now.data(), now.size());
+    HIPCHK(hipMemcpyAsync(f->dFsTmpl, h, now.size(), hipMemcpyHostToDevice, f->stream));
+    HIPCHK(hipEventRecord(f->bStage.ev[k], f->stream));
+    f->bFsTmplHost.swap(now);
+  }
+  fs_sensed_records_kernel<Rec><<<(nF + 63) / 64, 64, 0, f->stream>>>(reinterpret_cast<const Tmpl *>(f->dFsTmpl), f->dBFilt, dRec, f->dBMotion, nF, call,
+                                                                      f->mhBatch ? f->dFsLastNZ : nullptr);
+  HIPCHK(hipGetLastError());
+  return RFSGPU_OK;
+}
 static int batch_cycle_core(rfsgpu_filter *f, int predict, const double *x, const double *x_cov, int cov_stride, const double *z, const int *n_z, int normalize);
+static int batch_fs_cycle_core(rfsgpu_filter *f, int predict, const double *x, const double *x_cov, int cov_stride, const double *z, const int *n_z, int normalize);
+static int batch_mh_cycle_core(rfsgpu_filter *f, int predict, const double *x, const double *x_cov, int cov_stride, const double *z, const int *n_z, const double *u01,
+                               unsigned long long call);
+static int batch_push_motion(rfsgpu_filter *f);
 static int batch_resample_core(rfsgpu_filter *f, const BatchCall &C, const int *n_z, unsigned long long call, bool stageIn = true);
 static int batch_enter_dev_route(rfsgpu_filter *f);
 static int batch_propagate_core(rfsgpu_filter *f, const double *u, const double *pin_pose, const unsigned char *pin, const BatchPropIn *devRow, unsigned long long call);
@@ -3498,12 +3543,27 @@ int rfsgpu_batch_fastslam_cycle_async(rfsgpu_filter *f, int predict, const doubl
     if ((rc = batch_check_filter(f, BATCH_FS_CYCLE, b, z, n_z)) != RFSGPU_OK) return rc;
   if (f->bKind == 1)
     return fail(f, RFSGPU_ERR_UNSUPPORTED, "batch_fastslam_cycle: this batch steps RB-PHD filters (rfsgpu_batch_cycle_async has run): a batch is of one kind");
+  if (f->bSensed)
+    return fail(f, RFSGPU_ERR_UNSUPPORTED, "batch_fastslam_cycle: this batch has run a sensed cycle (rfsgpu_batch_fastslam_cycle_sensed_async): its measurement counts live on the device, the host-fed cycle no longer knows them");
   f->bKind = 2;
+  return batch_fs_cycle_core(f, predict, x, x_cov, cov_stride, z, n_z, normalize);
+}
+// The cycle behind rfsgpu_batch_fastslam_cycle_async (n_z given: the host's sets and records go to the device first) and
+// rfsgpu_batch_fastslam_cycle_sensed_async (n_z null: the sets are where the last rfsgpu_batch_sense_async left them, the records are
+// made from that call's on the device).  The arguments have been checked.
+static int batch_fs_cycle_core(rfsgpu_filter *f, int predict, const double *x, const double *x_cov, int cov_stride, const double *z, const int *n_z, int normalize) {
+  const bool sensed = n_z == nullptr;
+  const int nF = f->nF;
+  int rc = RFSGPU_OK;
   hipSetDevice(f->device);
   long long t0 = now_ns();
   if (!f->fsArena) HIPCHK(hipMalloc(&f->fsArena, (size_t)f->Ncap * fs_arena_bytes()));   // the Hungarian scratch of every slot of the batch, once
   batch_handle_wide(f, x, x_cov, cov_stride);
-  rc = batch_push_tables(f, f->dFsFilt, z, n_z, nullptr, 0, nullptr, [&](FsBatchFilter &T, int b) {
+  if (sensed) rc = batch_sensed_records(f, f->dFsFilt, 0ull, [&](FsBatchFilter &T, int b) {
+    T.F = fs_params_of(f->bFs[b], f->bParamsHost[b], 2, 1);
+    T.pruneT = f->bFs[b].mapExistencePruneThreshold;
+  });
+  else rc = batch_push_tables(f, f->dFsFilt, z, n_z, nullptr, 0, nullptr, [&](FsBatchFilter &T, int b) {
     T.F = fs_params_of(f->bFs[b], f->bParamsHost[b], 2, n_z[b]);
     T.pruneT = f->bFs[b].mapExistencePruneThreshold;
     T.prune = ((unsigned)n_z[b] >= f->bFs[b].pruningMeasurementsThreshold) ? 1 : 0;
@@ -3528,8 +3588,12 @@ int rfsgpu_batch_fastslam_cycle_async(rfsgpu_filter *f, int predict, const doubl
   fs_new_landmarks_kernel<2, true, FsBatchArg><<<(f->N + FS_NEWLM_WPB - 1) / FS_NEWLM_WPB, 64 * FS_NEWLM_WPB, 0, f->stream>>>(f->B, f->P, FsParams{}, f->cur, 0, A);
   fs_batch_post_kernel<<<nF, 256, 0, f->stream>>>(f->B.weight, A, f->dBSums, normalize, f->bDevRoute ? f->BL.resampled : nullptr);
   HIPCHK(hipGetLastError());
-  for (int b = 0; b < nF; b++)
-    if (n_z[b] > 0) { f->bNZ[b] = n_z[b]; f->bResampled[b] = 0; }
+  if (!sensed)
+    for (int b = 0; b < nF; b++)
+      if (n_z[b] > 0) { f->bNZ[b] = n_z[b]; f->bResampled[b] = 0; }
+  f->bSenseFresh = false;     // (either kind of cycle: the next sensed cycle needs a sense call of its own)
+  f->bSensedTail = sensed;
+  if (!sensed) f->bScanHeld = false;     // (the host's sets lie over the sensor's)
   f->holes = false;
   f->timing.mapUpdate_cpu += now_ns() - t0;
   return RFSGPU_OK;
@@ -3583,7 +3647,10 @@ static int mhb_resolve(rfsgpu_filter *f) {
   f->mhbPending = false;
   hipSetDevice(f->device);
   HIPCHK(hipMemcpyAsync(f->hMhbBlock, f->mhbBlock, mhb_bytes(f), hipMemcpyDeviceToHost, f->stream));
+  if (f->mhbLastSensed)     // (the last cycle's counts are the device's own: the nZ of its records, in the same read-back)
+    HIPCHK(hipMemcpyAsync(f->hFsLastNZ, f->dFsLastNZ, (size_t)f->nF * sizeof(int), hipMemcpyDeviceToHost, f->stream));
   const int rc = check_device_errors(f);   // waits for the stream
+  if (f->mhbLastSensed) memcpy(f->mhbLastNZ.data(), f->hFsLastNZ, (size_t)f->nF * sizeof(int));
   int first = -1;
   bool badCount = false;
   for (int b = 0; b < f->nF; b++) {
@@ -3615,7 +3682,7 @@ int rfsgpu_batch_fastslam_mh_cycle_async(rfsgpu_filter *f, int predict, const do
   if (rc != RFSGPU_OK) return rc;
   if (!f->mhBatch) return fail(f, RFSGPU_ERR_UNSUPPORTED, "batch_fastslam_mh_cycle: not a batch of multi-hypothesis FastSLAM filters (rfsgpu_create_batch_mh)");
   if ((rc = batch_check_call(f, BATCH_MH_CYCLE, predict, x_cov, cov_stride, u01 ? n_z : nullptr)) != RFSGPU_OK) return rc;
-  const int nF = f->nF, N = f->N, stride = f->nPer;
+  const int nF = f->nF;
   for (int b = 0; b < nF; b++) {
     if ((rc = batch_check_filter(f, BATCH_MH_CYCLE, b, z, n_z)) != RFSGPU_OK) return rc;
     if (!(u01[b] >= 0.0 && u01[b] < 1.0)) {
@@ -3623,27 +3690,48 @@ int rfsgpu_batch_fastslam_mh_cycle_async(rfsgpu_filter *f, int predict, const do
       return RFSGPU_ERR_INVALID;
     }
   }
+  if (f->bSensed)
+    return fail(f, RFSGPU_ERR_UNSUPPORTED, "batch_fastslam_mh_cycle: this batch has run a sensed cycle (rfsgpu_batch_fastslam_mh_cycle_sensed_async): its measurement counts live on the device, the host-fed cycle no longer knows them");
+  return batch_mh_cycle_core(f, predict, x, x_cov, cov_stride, z, n_z, u01, 0ull);
+}
+// The cycle behind rfsgpu_batch_fastslam_mh_cycle_async (n_z, u01 given: the host's sets and records go to the device first) and
+// rfsgpu_batch_fastslam_mh_cycle_sensed_async (n_z null: the sets are where the last rfsgpu_batch_sense_async left them, the records are
+// made from that call's on the device, each filter's draw is the resampling draw of (its motion key, call)).  The arguments have been checked.
+static int batch_mh_cycle_core(rfsgpu_filter *f, int predict, const double *x, const double *x_cov, int cov_stride, const double *z, const int *n_z, const double *u01,
+                               unsigned long long call) {
+  const bool sensed = n_z == nullptr;
+  const int nF = f->nF, N = f->N, stride = f->nPer;
+  int rc = RFSGPU_OK;
   hipSetDevice(f->device);
   long long t0 = now_ns();
   const FsMhLayout L = fs_mh_layout();
   if (!f->mhArena) HIPCHK(hipMalloc(&f->mhArena, (size_t)N * L.total));          // every slot's table / Murty arena / assignments, once
   if (!f->mhcInts) HIPCHK(hipMalloc(&f->mhcInts, (size_t)4 * N * sizeof(int)));
   batch_handle_wide(f, x, x_cov, cov_stride);
-  rc = batch_push_tables(f, f->dMhFilt, z, n_z, nullptr, 0, nullptr, [&](MhBatchFilter &T, int b) {
+  // (the record's static part: one filler for both routes; nz 1 where the device derives pfa)
+  auto fillStatic = [&](MhBatchFilter &T, int b, int nz) {
     const rfsgpu_fastslam_config &c = f->bFs[b];
-    T.F = fs_params_of(c, f->bParamsHost[b], 2, n_z[b]);
+    T.F = fs_params_of(c, f->bParamsHost[b], 2, nz);
     T.pruneT = c.mapExistencePruneThreshold;
-    T.prune = ((unsigned)n_z[b] >= c.pruningMeasurementsThreshold) ? 1 : 0;
     T.kmax = (int)c.maxNDataAssocHypotheses;
     T.maxDiff = c.maxDataAssocLogLikelihoodDiff;
     T.effN = f->bResSet[b] ? f->bEffN[2 * (size_t)b] : f->nInitPer / 4.0;        // ParticleFilter.hpp:232
     T.effNPercent = f->bResSet[b] ? f->bEffN[2 * (size_t)b + 1] : 0.25;
-    T.u01 = u01[b];
     T.nInit = f->nInitPer;
     T.nMax = (int)c.nParticlesMax;
     T.minUpdates = (int)c.minUpdatesBeforeResample;
     T.minMeasurements = (int)c.minMeasurementsBeforeResample;
-  });
+  };
+  if (sensed) {
+    if ((rc = batch_push_motion(f)) != RFSGPU_OK) return rc;     // (the keys of the draws)
+    rc = batch_sensed_records(f, f->dMhFilt, call, [&](MhBatchFilter &T, int b) { fillStatic(T, b, 1); });
+  } else {
+    rc = batch_push_tables(f, f->dMhFilt, z, n_z, nullptr, 0, nullptr, [&](MhBatchFilter &T, int b) {
+      fillStatic(T, b, n_z[b]);
+      T.prune = ((unsigned)n_z[b] >= f->bFs[b].pruningMeasurementsThreshold) ? 1 : 0;
+      T.u01 = u01[b];
+    });
+  }
   if (rc != RFSGPU_OK) return rc;
   if (x && (rc = batch_push_poses(f, x, x_cov, cov_stride)) != RFSGPU_OK) return rc;     // (every slot of every block)
   f->bBirthAlt = false;
@@ -3679,11 +3767,16 @@ int rfsgpu_batch_fastslam_mh_cycle_async(rfsgpu_filter *f, int predict, const do
   mhb_weight_sums_kernel<<<nF, 1024, 0, f->stream>>>(f->B.weight, f->dBSums, Arenorm);
   mhb_normalize_kernel<<<(N + 255) / 256, 256, 0, f->stream>>>(f->B.weight, N, f->dBSums, Arenorm);
   HIPCHK(hipGetLastError());
-  for (int b = 0; b < nF; b++) {
-    f->mhbLastNZ[b] = n_z[b];
-    if (n_z[b] > 0) f->bNZ[b] = n_z[b];
-  }
+  if (!sensed)      // (a sensed cycle: mhb_resolve takes the counts from the records on the device)
+    for (int b = 0; b < nF; b++) {
+      f->mhbLastNZ[b] = n_z[b];
+      if (n_z[b] > 0) f->bNZ[b] = n_z[b];
+    }
+  f->bSenseFresh = false;     // (either kind of cycle: the next sensed cycle needs a sense call of its own)
+  f->bSensedTail = false;     // (the resampling is inside the cycle)
+  if (!sensed) f->bScanHeld = false;     // (the host's sets lie over the sensor's)
   f->holes = false;
+  f->mhbLastSensed = sensed;
   f->mhbPending = true;
   f->mhbHave = true;
   f->timing.mapUpdate_cpu += now_ns() - t0;
@@ -3922,7 +4015,7 @@ int rfsgpu_batch_resample_async(rfsgpu_filter *f, const int *n_z, unsigned long 
   REFUSE_ON_MH_BATCH(f, "rfsgpu_batch_resample_async");
   if ((rc = batch_check_call(f, BATCH_RESAMPLE, 0, nullptr, 0, n_z)) != RFSGPU_OK) return rc;
   if (f->bSensed)
-    return fail(f, RFSGPU_ERR_UNSUPPORTED, "batch_resample: this batch has run a sensed cycle (rfsgpu_batch_cycle_sensed_async): its measurement counts live on the device (rfsgpu_batch_resample_sensed_async)");
+    return fail(f, RFSGPU_ERR_UNSUPPORTED, "batch_resample: this batch has run a sensed cycle (rfsgpu_batch_cycle_sensed_async or rfsgpu_batch_fastslam_cycle_sensed_async): its measurement counts live on the device (rfsgpu_batch_resample_sensed_async)");
   return batch_resample_core(f, BATCH_RESAMPLE, n_z, call);
 }
 // From here on the ids and resampleOccured_ live on the device.  Once per handle, and host-synchronous: the sources are pageable host
@@ -4032,13 +4125,40 @@ static const BatchCall BATCH_SENSE{"batch_sense", 0, nullptr, nullptr};
 static const BatchCall BATCH_CYCLE_SENSED{"batch_cycle_sensed", -1, "RFSGPU_CYCLE_NO_PREDICT (-1), 0 (static step only) or 1 (births + static step)", nullptr};
 static const BatchCall BATCH_RESAMPLE_SENSED{"batch_resample_sensed", 0, nullptr, nullptr};
 static const BatchCall BATCH_LAST_SCAN{"batch_last_scan", 0, nullptr, nullptr};
-// What the section serves: RB-PHD filter batches.  The records of the other kinds carry host-computed, count-dependent parameters.
+// What the section serves: RB-PHD filter batches, and -- once rfsgpu_batch_fastslam_serve_sensor has switched it on -- batches of
+// FastSLAM and of multi-hypothesis FastSLAM filters.  Their records carry three count-dependent fields (pfa, prune, the multi-hypothesis
+// draw), which the sensed cycle of their kind derives on the device (fastslam_sensed.h); the switch is off at creation, so the refusals
+// the section was published with stand until a caller asks.
 static int sensor_check(rfsgpu_filter *f, const BatchCall &C) {
+  const bool served = f->batch && f->bServeSensor;
   const char *why = !f->batch ? (f->groupShard ? "a shard of an rfsgpu_group" : "an ordinary handle")
-                              : (f->mhBatch ? "a batch of multi-hypothesis FastSLAM filters (rfsgpu_create_batch_mh)" : (f->bKind == 2 ? "a batch of FastSLAM filters" : nullptr));
+                              : (served ? nullptr : (f->mhBatch ? "a batch of multi-hypothesis FastSLAM filters (rfsgpu_create_batch_mh)" : (f->bKind == 2 ? "a batch of FastSLAM filters" : nullptr)));
   if (!why) return RFSGPU_OK;
   f->err = std::string(C.who) + ": the device sensor serves batches of RB-PHD filters (rfsgpu_create_batch, rfsgpu_batch_cycle_async) only, not " + why;
+  if (f->batch) f->err += " (rfsgpu_batch_fastslam_serve_sensor switches the section on for it)";
   return RFSGPU_ERR_UNSUPPORTED;
+}
+// The switch of a FastSLAM or multi-hypothesis batch: off at creation (rfsgpu_batch_mh_serve_metrics is the precedent).
+int rfsgpu_batch_fastslam_serve_sensor(rfsgpu_filter *f, int on) {
+  CHECK_HANDLE(f);
+  const char *why = !f->batch ? (f->groupShard ? "a shard of an rfsgpu_group" : "an ordinary handle")
+                              : (f->mhBatch || f->bKind == 2 ? nullptr : (f->bKind == 1 ? "a batch of RB-PHD filters (the [sensor] calls serve it as it is)"
+                                                                                         : "a batch whose kind is not decided yet (rfsgpu_batch_set_fastslam_config decides it)"));
+  if (why) {
+    f->err = std::string("batch_fastslam_serve_sensor: the switch is for batches of FastSLAM or multi-hypothesis FastSLAM filters, not ") + why;
+    return RFSGPU_ERR_UNSUPPORTED;
+  }
+  if (!on && f->bSensed)
+    return fail(f, RFSGPU_ERR_INVALID, "batch_fastslam_serve_sensor: a sensed cycle has run on this handle: its measurement counts live on the device, the host-fed calls could not take over");
+  hipSetDevice(f->device);
+  HIPCHK(hipStreamSynchronize(f->stream));
+  if (on && !f->dFsTmpl)
+    HIPCHK(hipMalloc(&f->dFsTmpl, (size_t)f->nF * std::max(sizeof(FsSensedTemplate<FsBatchFilter>), sizeof(FsSensedTemplate<MhBatchFilter>))));
+  if (on && f->mhBatch && !f->dFsLastNZ) HIPCHK(hipMalloc(&f->dFsLastNZ, (size_t)f->nF * sizeof(int)));
+  if (on && f->mhBatch && !f->hFsLastNZ) HIPCHK(hipHostMalloc(&f->hFsLastNZ, (size_t)f->nF * sizeof(int)));
+  f->bServeSensor = on != 0;
+  if (!on) f->bSenseFresh = false;
+  return RFSGPU_OK;
 }
 int rfsgpu_batch_set_sensor(rfsgpu_filter *f, int filter, const rfsgpu_rngbrg_config *model, const double *landmarks_xy, int n_landmarks, int max_nz,
                             unsigned long long seed) {
@@ -4171,6 +4291,8 @@ int rfsgpu_batch_cycle_sensed_async(rfsgpu_filter *f, int predict, const double 
   const BatchCall &C = BATCH_CYCLE_SENSED;
   int rc = sensor_check(f, C);
   if (rc != RFSGPU_OK) return rc;
+  if (f->mhBatch) return fail(f, RFSGPU_ERR_UNSUPPORTED, "batch_cycle_sensed: this is the RB-PHD cycle; a batch of multi-hypothesis FastSLAM filters (rfsgpu_create_batch_mh) takes rfsgpu_batch_fastslam_mh_cycle_sensed_async");
+  if (f->bKind == 2) return fail(f, RFSGPU_ERR_UNSUPPORTED, "batch_cycle_sensed: this is the RB-PHD cycle; a batch of FastSLAM filters takes rfsgpu_batch_fastslam_cycle_sensed_async");
   if ((rc = batch_check_call(f, C, predict, x_cov, cov_stride, nullptr)) != RFSGPU_OK) return rc;
   for (int b = 0; b < f->nF; b++) {
     if (!f->bSensorSet[b]) return batch_fail(f, C, "filter " + std::to_string(b) + " has no sensor (rfsgpu_batch_set_sensor)");
@@ -4198,11 +4320,57 @@ int rfsgpu_batch_cycle_sensed_async(rfsgpu_filter *f, int predict, const double 
   f->bSensed = true;     // (only now: a cycle that failed leaves the host-fed calls open)
   return RFSGPU_OK;
 }
+// ---- the sensed cycles of the other two kinds (rfsgpu_batch_fastslam_serve_sensor) ----------------------------------------------------
+static const BatchCall BATCH_FS_CYCLE_SENSED{"batch_fastslam_cycle_sensed", -1, "RFSGPU_CYCLE_NO_PREDICT (-1), or 0 / 1 (the static landmark step; FastSLAM has no births)", nullptr};
+static const BatchCall BATCH_MH_CYCLE_SENSED{"batch_fastslam_mh_cycle_sensed", 0, "0 or 1 (the static landmark step; FastSLAM has no births)", nullptr};
+// What the two calls check alike, after the kind: the call's arguments, every filter's sensor (mh: and its motion key, the key of
+// its draw), a sense call since the last cycle.  Nothing has been enqueued or changed when one of them refuses.
+static int fs_sensed_check(rfsgpu_filter *f, const BatchCall &C, int predict, const double *x_cov, int cov_stride, bool mh) {
+  int rc = batch_check_call(f, C, predict, x_cov, cov_stride, nullptr);
+  if (rc != RFSGPU_OK) return rc;
+  for (int b = 0; b < f->nF; b++) {
+    if (!f->bSensorSet[b]) return batch_fail(f, C, "filter " + std::to_string(b) + " has no sensor (rfsgpu_batch_set_sensor)");
+    if (mh && !f->bMotionSet[b]) return batch_fail(f, C, "filter " + std::to_string(b) + " has no Philox key for its resampling draw (rfsgpu_batch_set_motion_odometry)");
+  }
+  if (!f->bSenseFresh) return batch_fail(f, C, "no rfsgpu_batch_sense_async has run since the last cycle or the last rfsgpu_batch_set_sensor: filter 0 (and every other) has no scan for this one");
+  return RFSGPU_OK;
+}
+int rfsgpu_batch_fastslam_cycle_sensed_async(rfsgpu_filter *f, int predict, const double *x, const double *x_cov, int cov_stride, int normalize) {
+  CHECK_HANDLE(f);
+  const BatchCall &C = BATCH_FS_CYCLE_SENSED;
+  int rc = sensor_check(f, C);
+  if (rc != RFSGPU_OK) return rc;
+  if (f->mhBatch) return fail(f, RFSGPU_ERR_UNSUPPORTED, "batch_fastslam_cycle_sensed: a batch of multi-hypothesis FastSLAM filters (rfsgpu_create_batch_mh) takes rfsgpu_batch_fastslam_mh_cycle_sensed_async");
+  if (f->bKind != 2)
+    return fail(f, RFSGPU_ERR_UNSUPPORTED, f->bKind == 1 ? "batch_fastslam_cycle_sensed: this batch steps RB-PHD filters (rfsgpu_batch_cycle_async has run): it takes rfsgpu_batch_cycle_sensed_async"
+                                                         : "batch_fastslam_cycle_sensed: not a batch of FastSLAM filters yet (rfsgpu_batch_set_fastslam_config, then rfsgpu_batch_fastslam_serve_sensor)");
+  if ((rc = fs_sensed_check(f, C, predict, x_cov, cov_stride, false)) != RFSGPU_OK) return rc;
+  hipSetDevice(f->device);
+  // (as rfsgpu_batch_cycle_sensed_async: resampleOccured_ falls with an update on the device, where the sensed resampling keeps it)
+  if ((rc = batch_enter_dev_route(f)) != RFSGPU_OK) return rc;
+  if ((rc = batch_fs_cycle_core(f, predict, x, x_cov, cov_stride, nullptr, nullptr, normalize)) != RFSGPU_OK) return rc;
+  f->bSensed = true;     // (only now: a cycle that failed leaves the host-fed calls open)
+  return RFSGPU_OK;
+}
+int rfsgpu_batch_fastslam_mh_cycle_sensed_async(rfsgpu_filter *f, int predict, const double *x, const double *x_cov, int cov_stride, unsigned long long call) {
+  if (!f) return RFSGPU_ERR_INVALID;     // (as rfsgpu_batch_fastslam_mh_cycle_async: cycles in flight stay in flight)
+  const BatchCall &C = BATCH_MH_CYCLE_SENSED;
+  int rc = sensor_check(f, C);
+  if (rc != RFSGPU_OK) return rc;
+  if (!f->mhBatch)
+    return fail(f, RFSGPU_ERR_UNSUPPORTED, f->bKind == 2 ? "batch_fastslam_mh_cycle_sensed: not a batch of multi-hypothesis FastSLAM filters (rfsgpu_create_batch_mh): a batch of FastSLAM filters takes rfsgpu_batch_fastslam_cycle_sensed_async"
+                                                         : "batch_fastslam_mh_cycle_sensed: not a batch of multi-hypothesis FastSLAM filters (rfsgpu_create_batch_mh): an RB-PHD batch takes rfsgpu_batch_cycle_sensed_async");
+  if ((rc = fs_sensed_check(f, C, predict, x_cov, cov_stride, true)) != RFSGPU_OK) return rc;
+  if ((rc = batch_mh_cycle_core(f, predict, x, x_cov, cov_stride, nullptr, nullptr, nullptr, call)) != RFSGPU_OK) return rc;
+  f->bSensed = true;
+  return RFSGPU_OK;
+}
 int rfsgpu_batch_resample_sensed_async(rfsgpu_filter *f, unsigned long long call) {
   CHECK_HANDLE(f);
   const BatchCall &C = BATCH_RESAMPLE_SENSED;
   int rc = sensor_check(f, C);
   if (rc != RFSGPU_OK) return rc;
+  REFUSE_ON_MH_BATCH(f, "rfsgpu_batch_resample_sensed_async (a multi-hypothesis cycle resamples inside the cycle)");
   if (!f->bSensedTail) return batch_fail(f, C, "no rfsgpu_batch_cycle_sensed_async has run since the last rfsgpu_batch_sense_async: the records on the device are not those of a finished cycle");
   return batch_resample_core(f, C, nullptr, call);
 }
@@ -4531,16 +4699,19 @@ int rfsgpu_batch_run_truth_async(rfsgpu_filter *f, int k_from, int k_to, int tra
   if (f->truthK <= 0) return batch_fail(f, C, "no rfsgpu_batch_generate_truth has run on this handle: filter 0 (and every other) has no truth tables");
   if (k_from < 1 || k_to < k_from || k_to > f->truthK) return batch_fail(f, C, "the steps must satisfy 1 <= k_from <= k_to <= n_steps (" + std::to_string(f->truthK) + ")");
   // everything the per-step calls would refuse, before the first of them enqueues anything
+  // (the kind: a FastSLAM or multi-hypothesis batch gets here with its switch on only, sensor_check above; a multi-hypothesis cycle
+  //  resamples inside the cycle, by thresholds that have defaults, and only RB-PHD filters have births)
+  const int kind = f->mhBatch ? 3 : (f->bKind == 2 ? 2 : 1);
   for (int b = 0; b < nF; b++) {
     if (!f->bSensorSet[b]) return batch_fail(f, C, "filter " + std::to_string(b) + " has no sensor (rfsgpu_batch_set_sensor)");
     if (!f->bMotionSet[b]) return batch_fail(f, C, "filter " + std::to_string(b) + " has no motion parameters (rfsgpu_batch_set_motion_odometry)");
-    if (!f->bResSet[b]) return batch_fail(f, C, "filter " + std::to_string(b) + " has no resampling thresholds (rfsgpu_batch_set_resampling)");
-    if (f->bCfg[b].birthGaussianMeasurementCountThreshold != 1u) {
+    if (kind != 3 && !f->bResSet[b]) return batch_fail(f, C, "filter " + std::to_string(b) + " has no resampling thresholds (rfsgpu_batch_set_resampling)");
+    if (kind == 1 && f->bCfg[b].birthGaussianMeasurementCountThreshold != 1u) {
       f->err = "batch_run_truth: a filter batch takes immediate births only (birthGaussianMeasurementCountThreshold 1)";
       return RFSGPU_ERR_UNSUPPORTED;
     }
   }
-  if (f->nPer > RFSGPU_BATCH_RESAMPLE_MAX_PER_FILTER) {
+  if (kind != 3 && f->nPer > RFSGPU_BATCH_RESAMPLE_MAX_PER_FILTER) {
     f->err = "batch_run_truth: more than RFSGPU_BATCH_RESAMPLE_MAX_PER_FILTER particles per filter (one workgroup resamples a filter)";
     return RFSGPU_ERR_UNSUPPORTED;
   }
@@ -4560,8 +4731,17 @@ int rfsgpu_batch_run_truth_async(rfsgpu_filter *f, int k_from, int k_to, int tra
     const unsigned long long call = (unsigned long long)k;
     if ((rc = batch_propagate_core(f, nullptr, nullptr, nullptr, f->dTruthProp + row, call)) != RFSGPU_OK) return rc;
     if ((rc = batch_sense_core(f, nullptr, f->dTruthGt + 3 * row, call)) != RFSGPU_OK) return rc;
-    if ((rc = rfsgpu_batch_cycle_sensed_async(f, 1, nullptr, nullptr, 0, 1)) != RFSGPU_OK) return rc;
-    if ((rc = batch_resample_core(f, BATCH_RESAMPLE_SENSED, nullptr, call, k == k_from)) != RFSGPU_OK) return rc;
+    if (kind == 1) {
+      if ((rc = rfsgpu_batch_cycle_sensed_async(f, 1, nullptr, nullptr, 0, 1)) != RFSGPU_OK) return rc;
+    } else if (kind == 2) {
+      if ((rc = batch_enter_dev_route(f)) != RFSGPU_OK) return rc;     // (as rfsgpu_batch_fastslam_cycle_sensed_async; once per handle)
+      if ((rc = batch_fs_cycle_core(f, 1, nullptr, nullptr, 0, nullptr, nullptr, 1)) != RFSGPU_OK) return rc;
+      f->bSensed = true;
+    } else {
+      if ((rc = batch_mh_cycle_core(f, 1, nullptr, nullptr, 0, nullptr, nullptr, nullptr, call)) != RFSGPU_OK) return rc;
+      f->bSensed = true;
+    }
+    if (kind != 3 && (rc = batch_resample_core(f, BATCH_RESAMPLE_SENSED, nullptr, call, k == k_from)) != RFSGPU_OK) return rc;
     if (track_errors) {
       if ((rc = metric_launch(f, nullptr, nullptr, w_threshold, cutoff, order, f->dErrLog + (size_t)f->errLogRows * nF, f->dTruthTgt + 4 * row)) != RFSGPU_OK) return rc;
       f->errLogRows++;

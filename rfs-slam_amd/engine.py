@@ -535,7 +535,9 @@ class FastSLAMBatch(FilterBatch):
     static landmark step, the association / Kalman update / weights, the existence prune, the new landmarks and each filter's
     normalisation, one launch chain for all filters.  Each filter equals a separate FastSLAM handle given the same inputs.  The
     model / Kalman filter / landmark noise of a filter come through configure(b, None, R=..., ...) as for a FilterBatch; the FastSLAM
-    configuration through configure_fastslam(b, fs_cfg), whose two gates also decide the resampling (update_and_resample, resample_async)."""
+    configuration through configure_fastslam(b, fs_cfg), whose two gates also decide the resampling (update_and_resample, resample_async).
+    serve_sensor(True) (after the first configure_fastslam) opens the device sensor and truth to the batch: set_sensor, sense_async,
+    fastslam_cycle_sensed_async, resample_sensed_async, last_scan and run_truth_async; the host-fed cycle refuses once a sensed one has run."""
 
     def __init__(self, n_filters, n_per_filter, device_id=0, gm_capacity=512):
         super().__init__(n_filters, n_per_filter, device_id=device_id, gm_capacity=gm_capacity)
@@ -564,7 +566,9 @@ class MHFastSLAMBatch(capi.CBatchMH):
     live; each filter equals a FastSLAM(n_per_filter, max_hypotheses=..., device_cycle=True) handle with max_particles =
     max_per_filter given the same inputs.  The model / Kalman filter / landmark noise of a filter come through configure(b, None,
     R=..., ...), the FastSLAM configuration through configure_fastslam(b, fs_cfg), the N_eff thresholds through set_resampling.
-    metrics=True switches the device-side map / pose error on at construction (serve_metrics): the [metric] calls refuse otherwise."""
+    metrics=True switches the device-side map / pose error on at construction (serve_metrics): the [metric] calls refuse otherwise.
+    serve_sensor(True) opens the device sensor and truth to the batch: set_sensor, sense_async, fastslam_mh_cycle_sensed_async(predict,
+    call) -- every filter's resampling draw is then the device's, of (its motion key, call) -- last_scan and run_truth_async."""
 
     def __init__(self, n_filters, n_per_filter, max_per_filter=None, device_id=0, gm_capacity=512, max_hypotheses=3, metrics=False):
         # default: nParticlesMax x max_hypotheses slots (a set at nParticlesMax = 3 n is not forced back, and the next update can multiply

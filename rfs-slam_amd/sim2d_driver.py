@@ -370,6 +370,16 @@ def truth_config(P=C1_SIM, b=None):
     return c
 
 
+def device_truth_datas(batch, Ps, seeds, kmax):
+    """The device's ground truth for every filter of `batch` ([truth] in include/rfsgpu.h): each filter's generation keys from Ps[b]
+    under the key seeds[b], one generate_truth of kmax steps, and the one read of what the host needs -- landmarks, first_seen,
+    n_det_max -- as a list of dicts in generate()'s layout (gt, odom and Z are None: the steps' inputs stay on the device)."""
+    for b, P in enumerate(Ps):
+        batch.set_truth(b, truth_config(P, b), seeds[b])
+    batch.generate_truth(int(kmax))
+    return [batch.get_truth(b, trajectory=False) for b in range(len(Ps))]
+
+
 class Sim2dBatchRun:
     """run() :540-643 for MANY independent filters, each with its own realisation (`datas[b]`, its own generate(traj_seed=...)), its
     own configuration dict `Ps[b]` and its own host RNG stream (`seeds[b]`: process noise, resampling draws).  `target` is either a
@@ -386,7 +396,8 @@ class Sim2dBatchRun:
     call number = the step k), not the numpy streams of the host loop: the two loops run the same model on different realisations
     of the noise.  step() returns None in this form (the decisions stay on the device; FilterBatch.last_resample reads the last ones).
 
-    device_sensor=True (with device_loop, RB-PHD filters): the scans are the device's too ([sensor] in include/rfsgpu.h).  Each filter's
+    device_sensor=True (with device_loop; with fastslam=True the batch's sensor service is switched on, serve_sensor, and the sensed
+    cycle is the FastSLAM one): the scans are the device's too ([sensor] in include/rfsgpu.h).  Each filter's
     sensor is configured from Ps[b] -- the unpadded varzr / varzb, Pd, clutter, the range limits -- with the landmarks of datas[b] and
     the key seeds[b]; a step is propagate_async -> sense_async(gt[k]) -> cycle_sensed_async -> resample_sensed_async (->
     step_error_async), and no table of scans is built: datas[b]["Z"] is not read (generate(..., measurements=False) leaves it None).
@@ -395,7 +406,7 @@ class Sim2dBatchRun:
     landmark step, no births) and FastSLAM::update; `target` is a FastSLAMBatch or a list of FastSLAM handles (or oracle filters),
     `Ps` dicts like C1_FASTSLAM_SIM.  A filter whose scan is empty is neither updated nor normalised that step (FastSLAM.hpp:402-403).
 
-    device_truth=True (an RB-PHD FilterBatch; implies device_loop and device_sensor; datas=None, kmax = the steps to generate): the
+    device_truth=True (a FilterBatch, or a FastSLAMBatch with fastslam=True; implies device_loop and device_sensor; datas=None, kmax = the steps to generate): the
     ground truth is the device's as well ([truth] in include/rfsgpu.h).  Each filter's generation keys come from Ps[b]
     (truth_config) under the key seeds[b]; one generate_truth draws every trajectory, and the landmarks, first-seen times and
     n_det_max are read back once, for the sensors (max_nz = sensor_max_nz_of(n_det_max)) and the metric's ground truth.  run() is
@@ -408,15 +419,12 @@ class Sim2dBatchRun:
         launch for the whole batch; one per handle otherwise), errors() reads the log(s) once at the end."""
         self.device_truth = bool(device_truth)
         if self.device_truth:
-            assert datas is None and kmax is not None and not fastslam and isinstance(target, capi.CBatch), "device_truth: an RB-PHD FilterBatch, datas=None, kmax given"
+            assert datas is None and kmax is not None and isinstance(target, capi.CBatch), "device_truth: a FilterBatch or FastSLAMBatch, datas=None, kmax given"
             device_loop = device_sensor = True
-            for b, P in enumerate(Ps):
-                target.set_truth(b, truth_config(P, b), seeds[b])
-            target.generate_truth(int(kmax))
-            datas = [target.get_truth(b, trajectory=False) for b in range(len(Ps))]      # landmarks, first_seen, n_det_max: the one read
+            datas = device_truth_datas(target, Ps, seeds, kmax)
         self.device_loop = bool(device_loop)
         self.device_sensor = bool(device_sensor)
-        assert not self.device_sensor or (self.device_loop and not fastslam), "the device sensor serves the device loop of an RB-PHD FilterBatch"
+        assert not self.device_sensor or self.device_loop, "the device sensor serves the device loop of a FilterBatch or FastSLAMBatch"
         self.fastslam = bool(fastslam)
         self.batch = target if isinstance(target, capi.CBatch) else None
         self.handles = None if self.batch is not None else list(target)
@@ -434,6 +442,8 @@ class Sim2dBatchRun:
         if self.fastslam:
             if self.batch is not None:
                 self.cfgs = [configure_fastslam_batch_filter(self.batch, b, P) for b, P in enumerate(self.Ps)]
+                if self.device_sensor:      # (after the configuration, which decides the batch's kind: the switch is per kind)
+                    self.batch.serve_sensor(True)
             else:
                 self.cfgs = [configure_fastslam(f, P) for f, P in zip(self.handles, self.Ps)]
         elif self.batch is not None:
@@ -511,7 +521,10 @@ class Sim2dBatchRun:
         bt = self.batch
         if self.device_sensor:
             bt.sense_async(self._gt[k], k)
-            bt.cycle_sensed_async(True, normalize=True)
+            if self.fastslam:
+                bt.fastslam_cycle_sensed_async(True, normalize=True)
+            else:
+                bt.cycle_sensed_async(True, normalize=True)
             bt.resample_sensed_async(k)
             self.last_n_z = None            # (on the device: FilterBatch.last_scan reads the sets)
             if self.track_errors:
@@ -635,9 +648,23 @@ class Sim2dMHBatchRun:
     track_errors=True (a batch target only; the contract of Sim2dBatchRun): the batch's metric service is switched on
     (serve_metrics), each filter's ground truth is uploaded with its first_seen_times, the log is sized to the run, every step ends
     with one step_error_async(t = k * dt, gt_pose) -- the kernel reads each filter's live count on the device, so the device loop
-    still reads nothing back -- and errors() is the one read at the end."""
+    still reads nothing back -- and errors() is the one read at the end.
 
-    def __init__(self, target, datas, Ps, seeds, n=None, device_loop=False, track_errors=False):
+    device_sensor=True (a batch target; implies device_loop): the batch's sensor service is switched on (serve_sensor), each filter's
+    sensor is configured as Sim2dBatchRun configures it, a step is propagate_async -> sense_async(gt[k]) ->
+    fastslam_mh_cycle_sensed_async(True, k), and neither a table of scans nor the resampling draws are made on the host: a filter's draw
+    is the device's resampling draw of (seeds[b], k).  device_truth=True (implies device_sensor; datas=None, kmax = the steps to
+    generate): the ground truth is the device's too (device_truth_datas), and run() without on_step is ONE run_truth_async."""
+
+    def __init__(self, target, datas, Ps, seeds, n=None, device_loop=False, track_errors=False, device_sensor=False, device_truth=False, kmax=None):
+        self.device_truth = bool(device_truth)
+        self.device_sensor = bool(device_sensor) or self.device_truth
+        if self.device_sensor:
+            assert isinstance(target, capi.CBatchMH), "the device sensor and truth need an MHFastSLAMBatch"
+            device_loop = True
+        if self.device_truth:
+            assert datas is None and kmax is not None, "device_truth: datas=None, kmax given"
+            datas = device_truth_datas(target, Ps, seeds, kmax)
         self.datas, self.Ps, self.nF = list(datas), list(Ps), len(datas)
         self.batch = target if isinstance(target, capi.CBatchMH) else None
         self.handles = None if self.batch is not None else list(target)
@@ -647,7 +674,8 @@ class Sim2dMHBatchRun:
         assert self.batch is not None or not (self.device_loop or self.track_errors), "the device loop and the error tracking need an MHFastSLAMBatch"
         K = int(min(d["K"] for d in datas))
         self.rngs = [np.random.default_rng(s) for s in seeds]
-        self.u01 = np.ascontiguousarray(np.stack([np.random.default_rng(10_000 + s).random(K) for s in seeds], axis=1))      # [K, nF]
+        if not self.device_sensor:
+            self.u01 = np.ascontiguousarray(np.stack([np.random.default_rng(10_000 + s).random(K) for s in seeds], axis=1))      # [K, nF]
         self.Q = [np.diag([P["vardx"], P["vardy"], P["vardz"]]) * P["p_noise_inflation"] * P["dt"] ** 2 for P in Ps]
         for b, P in enumerate(Ps):
             if self.batch is not None:
@@ -661,21 +689,28 @@ class Sim2dMHBatchRun:
                 h.fs_config = configure_fastslam(h, P)
                 h.fs_config.nParticlesMax = 3 * n
                 h.setEffectiveParticleCountThreshold(P["eff_n"])
-        self._u = np.ascontiguousarray(np.stack([d["odom"][:K] for d in datas], axis=1))
-        self._gt = np.ascontiguousarray(np.stack([d["gt"][:K] for d in datas], axis=1))
-        self._z = np.zeros((K, self.nF, capi.MAX_Z, 2))
-        self._nz = np.zeros((K, self.nF), dtype=np.int32)
-        for b, d in enumerate(datas):
-            for k in range(K):
-                Z = d["Z"][k] if k < len(d["Z"]) else np.zeros((0, 2))
-                self._nz[k, b] = len(Z)
-                self._z[k, b, :len(Z)] = Z
-        self._t = np.array([[k * P["dt"] for P in Ps] for k in range(K)])
-        self._pin_all = np.ones(self.nF, dtype=np.uint8)
+        if self.device_sensor:      # each filter's simulated sensor: the UNPADDED noise (the filter's own R is inflated); no table of scans
+            self.batch.serve_sensor(True)
+            for b, (d, P) in enumerate(zip(self.datas, self.Ps)):
+                self.batch.set_sensor(b, np.diag([P["varzr"], P["varzb"]]), P["Pd"], P["clutter"], P["rmax"], P["rmin"], d["landmarks"],
+                                      max_nz=sensor_max_nz_of(d["n_det_max"], P) if self.device_truth else sensor_max_nz(d, P), seed=seeds[b])
+        if not self.device_truth:      # (else no per-step host table at all: the steps' inputs are rows of the truth tables on the device)
+            self._u = np.ascontiguousarray(np.stack([d["odom"][:K] for d in datas], axis=1))
+            self._gt = np.ascontiguousarray(np.stack([d["gt"][:K] for d in datas], axis=1))
+            self._t = np.array([[k * P["dt"] for P in Ps] for k in range(K)])
+            self._pin_all = np.ones(self.nF, dtype=np.uint8)
+        if not self.device_sensor:
+            self._z = np.zeros((K, self.nF, capi.MAX_Z, 2))
+            self._nz = np.zeros((K, self.nF), dtype=np.int32)
+            for b, d in enumerate(datas):
+                for k in range(K):
+                    Z = d["Z"][k] if k < len(d["Z"]) else np.zeros((0, 2))
+                    self._nz[k, b] = len(Z)
+                    self._z[k, b, :len(Z)] = Z
         if self.track_errors:
             self.batch.serve_metrics(True)
             for b, (d, P) in enumerate(zip(self.datas, self.Ps)):
-                self.batch.set_ground_truth(d["landmarks"], first_seen_times(d, P), filter=b)
+                self.batch.set_ground_truth(d["landmarks"], d["first_seen"] if self.device_truth else first_seen_times(d, P), filter=b)
             self.batch.error_log_create(K)
 
     def _moved(self, b, x, k):
@@ -687,7 +722,14 @@ class Sim2dMHBatchRun:
 
     def step(self, k):
         bt = self.batch
-        if self.device_loop:
+        if self.device_truth:
+            bt.run_truth_async(k, k + 1, self.track_errors, ERROR_W_THRESHOLD, ERROR_CUTOFF, ERROR_ORDER)
+            return
+        if self.device_sensor:
+            bt.propagate_async(self._u[k], k, pin=self._pin_all if k <= 100 else None, pin_pose=self._gt[k] if k <= 100 else None)
+            bt.sense_async(self._gt[k], k)
+            bt.fastslam_mh_cycle_sensed_async(True, k)
+        elif self.device_loop:
             bt.propagate_async(self._u[k], k, pin=self._pin_all if k <= 100 else None, pin_pose=self._gt[k] if k <= 100 else None)
             bt.batch_fastslam_mh_cycle_async_packed(True, self._z[k], self._nz[k], self.u01[k])
         elif bt is not None:
@@ -713,7 +755,11 @@ class Sim2dMHBatchRun:
         return self.batch.error_log_read()
 
     def run(self, k_from=1, k_to=None, on_step=None):
-        for k in range(k_from, int(k_to or min(d["K"] for d in self.datas))):
+        k_to = int(k_to or min(d["K"] for d in self.datas))
+        if self.device_truth and on_step is None:      # the loop over steps is the library's: one call
+            self.batch.run_truth_async(k_from, k_to, self.track_errors, ERROR_W_THRESHOLD, ERROR_CUTOFF, ERROR_ORDER)
+            return self
+        for k in range(k_from, k_to):
             self.step(k)
             if on_step is not None:
                 on_step(k, self)

@@ -17,14 +17,16 @@ resample_async, nothing read back until the end; the final synchronisation is in
 and the device loop from the one invocation, both figures in the line.  Every line names its loop kind ("loop").  --reps N: N timed
 repetitions of each figure (fresh batch each), all of them in the line ("..._reps") next to their median.
 
---device-sensor (RB-PHD batches; implies the device loop, --device-loop / --both-loops are accepted and ignored): per batch size the
+--device-sensor (any of the three kinds: with --fastslam / --mhfastslam the batch's sensor service is switched on,
+rfsgpu_batch_fastslam_serve_sensor, and the sensed cycle is the kind's own; implies the device loop, --device-loop / --both-loops are accepted and ignored): per batch size the
 device loop fed with host-made scans against the device loop whose scans the device draws (Sim2dBatchRun(device_sensor=True):
 propagate_async -> sense_async -> cycle_sensed_async -> resample_sensed_async).  Each line has, for either route and from the one
 invocation, the setup time (sim2d_driver.generate + packing, or generate(measurements=False) + set_sensor) and the run time
 separately, with all --reps repetitions and their medians, and filter-steps/s without and with the setup.  --errors / --results / --json
 work as elsewhere (the filters listed are the device-sensor route's).
 
---device-truth (RB-PHD batches; implies --device-loop --device-sensor, refused with --fastslam and --mhfastslam): per batch size the
+--device-truth (any of the three kinds; implies --device-loop --device-sensor; given TOGETHER with --device-sensor the line has all
+three routes -- host-made scans, device-made scans, device-made truth -- and the host-made against the device-made ratio): per batch size the
 device loop with device-made scans on a host-made ground truth (generate(measurements=False): the "device_scans" route above) against
 the same loop on a device-made ground truth (Sim2dBatchRun(device_truth=True): set_truth + one generate_truth, the landmarks read back
 once for the sensors, and the whole run ONE rfsgpu_batch_run_truth_async).  Setup and run time of each route as with --device-sensor.
@@ -331,24 +333,39 @@ def sensor_sweep(pkg, a, sizes):
     sim = pkg.sim2d_driver
     pds = [0.5, 0.6, 0.7, 0.8, 0.9, 0.95, 0.99, 0.85, 0.75, 0.65]
     clutters = [1e-4, 5e-4, 1e-3, 2e-3, 5e-3, 1e-2, 2e-2, 5e-2, 1e-1]
-    Ps = [dict(sim.C1_SIM, Pd=pds[b % len(pds)], clutter=clutters[(b // len(pds)) % len(clutters)]) for b in range(max(sizes))]
+    # (--fastslam / --mhfastslam: the same table for a FastSLAMBatch / an MHFastSLAMBatch, whose sensor service the run switches on)
+    n, stride = a.particles, 0
+    P0 = sim.C1_FASTSLAM_SIM if a.fastslam else sim.C1_SIM
+    if a.mhfastslam:
+        P0, n_xml = mh_params(sim)
+        n = a.particles or n_xml
+        stride = a.max_per_filter or min(2048, 3 * n * P0["max_hypotheses"])
+    Ps = [dict(P0, Pd=pds[b % len(pds)], clutter=clutters[(b // len(pds)) % len(clutters)]) for b in range(max(sizes))]
     seeds = [100 + b for b in range(max(sizes))]
     kmax = a.steps + 2
     rows = []
-    routes = ("device", "truth") if a.device_truth else ("host", "device")
+    routes = (("host", "device", "truth") if a.all_routes else ("device", "truth")) if a.device_truth else ("host", "device")
+
+    def make_run(batch, B, route):
+        datas = None if route == "truth" else [sim.generate(Ps[b], traj_seed=1 + b, kmax=kmax, measurements=(route == "host")) for b in range(B)]
+        if a.mhfastslam:
+            return sim.Sim2dMHBatchRun(batch, datas, Ps[:B], seeds[:B], n, device_loop=True, track_errors=a.errors, device_sensor=(route == "device"),
+                                       device_truth=(route == "truth"), kmax=kmax)
+        if route == "truth":
+            return sim.Sim2dBatchRun(batch, None, Ps[:B], seeds[:B], track_errors=a.errors, fastslam=a.fastslam, device_truth=True, kmax=kmax)
+        return sim.Sim2dBatchRun(batch, datas, Ps[:B], seeds[:B], track_errors=a.errors, fastslam=a.fastslam, device_loop=True, device_sensor=(route == "device"))
+
     for B in sizes:
-        row = dict(B=B, particles=a.particles, steps=a.steps, loop="device", reps=max(1, a.reps))
+        row = dict(B=B, particles=n, steps=a.steps, loop="device", reps=max(1, a.reps))
+        if a.fastslam or a.mhfastslam:
+            row["filter"] = "mhfastslam" if a.mhfastslam else "fastslam"
         for route in routes:
             setup, run_t = [], []
             for _ in range(max(1, a.reps)):
-                batch = pkg.FilterBatch(B, a.particles, gm_capacity=a.capacity)
+                batch = pkg.MHFastSLAMBatch(B, n, stride, gm_capacity=a.capacity) if a.mhfastslam else make_batch(pkg, a, B)
                 batch.synchronize()
                 t0 = time.perf_counter()
-                if route == "truth":
-                    rb = sim.Sim2dBatchRun(batch, None, Ps[:B], seeds[:B], track_errors=a.errors, device_truth=True, kmax=kmax)
-                else:
-                    datas = [sim.generate(Ps[b], traj_seed=1 + b, kmax=kmax, measurements=(route == "host")) for b in range(B)]
-                    rb = sim.Sim2dBatchRun(batch, datas, Ps[:B], seeds[:B], track_errors=a.errors, device_loop=True, device_sensor=(route == "device"))
+                rb = make_run(batch, B, route)
                 setup.append(time.perf_counter() - t0)
                 rb.step(1)
                 batch.synchronize()
@@ -364,7 +381,10 @@ def sensor_sweep(pkg, a, sizes):
                     batch.synchronize()
                 run_t.append(time.perf_counter() - t0)
                 if route == routes[-1]:
-                    row["resamples_device_" + ("truth" if route == "truth" else "scans")] = rb.resample_counts().tolist()
+                    if a.mhfastslam:
+                        row["final_counts_device_" + ("truth" if route == "truth" else "scans")] = batch.live_counts().tolist()
+                    else:
+                        row["resamples_device_" + ("truth" if route == "truth" else "scans")] = rb.resample_counts().tolist()
                     if a.errors:
                         row["filters"] = filter_rows(log, Ps, B)
                 batch.close()
@@ -375,6 +395,9 @@ def sensor_sweep(pkg, a, sizes):
             row[key + "filter_steps_per_s_with_setup"] = B * a.steps / (row[key + "setup_s"] + row[key + "run_s"])
             if route == "host":
                 row["host_scans_packed_bytes_per_step"] = int(B * pkg.capi.MAX_Z * 2 * 8 + B * 4)
+        if a.device_truth and a.all_routes:      # the host-made route (scans and truth made and packed on the host) against the device-made one
+            row["device_truth_over_host_scans_run"] = row["host_scans_run_s"] / row["device_truth_run_s"]
+            row["device_truth_over_host_scans_with_setup"] = (row["host_scans_setup_s"] + row["host_scans_run_s"]) / (row["device_truth_setup_s"] + row["device_truth_run_s"])
         if a.device_truth:
             row["device_over_host_truth_run"] = row["device_scans_run_s"] / row["device_truth_run_s"]
             row["device_over_host_truth_with_setup"] = (row["device_scans_setup_s"] + row["device_scans_run_s"]) / (row["device_truth_setup_s"] + row["device_truth_run_s"])
@@ -416,13 +439,12 @@ def main():
     ap.add_argument("--results", default="", help="--errors: write one line per filter of the largest batch, 'Pd  c  posError  mapError' (the final row's pose_ed and cola)")
     ap.add_argument("--max-per-filter", type=int, default=0, help="--mhfastslam: particle slots per filter (default nParticlesMax x hypotheses = 9 x particles, which cannot overflow; at most 2048)")
     a = ap.parse_args()
-    if a.device_truth and (a.fastslam or a.mhfastslam):
-        ap.error("--device-truth serves RB-PHD batches (rfsgpu_batch_run_truth_async refuses FastSLAM and multi-hypothesis FastSLAM batches)")
+    a.all_routes = a.device_truth and a.device_sensor      # both given: host-made scans, device-made scans and device-made truth in one line
     if a.device_truth:
         a.device_loop = a.device_sensor = True
-    if a.device_sensor and (a.fastslam or a.mhfastslam):
-        ap.error("--device-sensor serves RB-PHD batches (the sensor section refuses FastSLAM and multi-hypothesis FastSLAM batches)")
     pkg = load_pkg()
+    if a.mhfastslam and a.device_sensor:
+        return sensor_sweep(pkg, a, [int(s) for s in a.sizes.split(",")])
     if a.mhfastslam:
         return mh_sweep(pkg, a, [int(s) for s in a.sizes.split(",")])
     a.particles = a.particles or 200
