@@ -47,7 +47,8 @@
  *   [metric]   per-step OSPA / COLA map error and pose error computed on the device, kept in a device-side log;
  *   [resample] ParticleFilter::resample for an ordinary handle of any size on the device, without a host stop;
  *   [sensor]   the simulator's range-bearing sensor of every filter of a batch (RB-PHD; FastSLAM kinds by a switch) drawn on the device, for batch sweeps;
- *   [truth]    the simulator's trajectory, odometry and landmarks of every filter of a batch drawn on the device, and a run of steps in one call.
+ *   [truth]    the simulator's trajectory, odometry and landmarks of every filter of a batch drawn on the device, and a run of steps in one call;
+ *   [estimate] every filter's pose and map estimate per step (the reference's particlePose.dat / landmarkEst.dat) kept in a device-side log.
  * A maintainer wiring the reference to the library reads the CORE entries and INTEGRATION.md; nothing optional is required
  * for correct results.
  */
@@ -1120,6 +1121,59 @@ int rfsgpu_batch_get_truth(rfsgpu_filter *f, int filter, double *gt, double *odo
  * that has no ground truth (rfsgpu_set_ground_truth) or without an error log; RFSGPU_ERR_CAPACITY: a log with fewer free rows than
  * the run has steps. */
 int rfsgpu_batch_run_truth_async(rfsgpu_filter *f, int k_from, int k_to, int track_errors, double w_threshold, double cutoff, double order);
+
+/* ---- [estimate] every filter's pose and map estimate per step, kept on the device (outside the STABLE CORE) ---------------------------
+ * What the reference's simulators write per time step into particlePose.dat and landmarkEst.dat (src/rbphdslam2dSim.cpp:620-638,
+ * src/fastslam2dSim.cpp:613-632) -- the particle set, and the map of the highest-weight particle with means, covariances and weights --
+ * as one launch on the handle's stream (csrc/estimate_log.h) that appends one row to a device-side log beside the error log of
+ * [metric].  The kernel reads the filter state as it is at that point of the stream and changes nothing of it; without a log nothing
+ * runs.  The section is served exactly where [metric] is served, with [metric]'s refusals and texts: ordinary 2-D RB-PHD handles,
+ * RB-PHD and FastSLAM batches, a multi-hypothesis batch once rfsgpu_batch_mh_serve_metrics(f, 1) has been called; everything else
+ * gets RFSGPU_ERR_UNSUPPORTED from every call below.  The selection of the best particle, the weight of a Gaussian (a FastSLAM kind:
+ * 1 - 1 / (1 + exp(log-odds))), the skipping of holes and the summation trees are [metric]'s, so best_slot, cardinality and
+ * weight_sum of a row equal those of an rfsgpu_step_error record taken at the same point, bit for bit.
+ * One record per filter and row; every field is 8 bytes wide. */
+struct rfsgpu_step_estimate {
+  double t;                 /* the time given with the call                                                                  */
+  long long status;         /* 0 ok; 1: n_est > max_est, the Gaussians are cut to the first max_est in mixture order         */
+  long long best_slot;      /* global slot of the highest-weight particle: the first slot of the filter's block whose weight is
+                               strictly greater than every earlier one, starting from 0 (analysis2dSim.cpp:159-167); slot 0 of the
+                               block when no weight is > 0                                                                   */
+  long long n_particles;    /* slots the selection ran over: N, n_per_filter, or the LIVE count of a multi-hypothesis filter  */
+  long long n_est;          /* the best particle's Gaussians with weight >= w_threshold (holes skipped, log-odds converted as in [metric]) */
+  long long n_logged;       /* min(n_est, max_est)                                                                           */
+  double cardinality;       /* sum of ALL its Gaussians' weights, the fixed tree of map_metric.h                             */
+  double best_weight, weight_sum;   /* the best particle's weight, copied; the sum of the block's weights (the same tree)   */
+  double best_x, best_y, best_theta;            /* the best particle's pose, copied                                          */
+  double mean_x, mean_y, mean_cos, mean_sin;    /* sum w q / sum w over the block for q = x, y, cos theta, sin theta; the host takes atan2 */
+};
+/* The log: log_capacity rows; 0 <= max_est <= the handle's gm_capacity Gaussians kept per filter and row (else RFSGPU_ERR_INVALID);
+ * log_particles != 0 keeps the particle set too.  Three arrays on the device, row-major:
+ *   hdr   [cap][n_filters]                      one rfsgpu_step_estimate (128 bytes) per filter and row;
+ *   gauss [cap][n_filters][6][max_est]          planes mx, my, sxx, sxy, syy, w (48 max_est bytes per filter and row);
+ *   part  [cap][n_filters][4][slots]            planes x, y, theta, w; slots = n_particles of an ordinary handle, n_per_filter of a
+ *                                               batch, max_per_filter of a multi-hypothesis batch (32 slots bytes per filter and row);
+ *                                               only the first n_particles entries of each plane of a row are written.
+ * _create (re)allocates the log empty (synchronising; capacity 0 frees everything); an allocation that fails: RFSGPU_ERR_HIP and no
+ * log is left.  _reset empties it; rows stay where they are until then. */
+int rfsgpu_estimate_log_create(rfsgpu_filter *f, int log_capacity, int max_est, int log_particles);
+int rfsgpu_estimate_log_reset(rfsgpu_filter *f);
+/* Appends one row: t [n_filters] the time of each filter's step, copied into the pinned staging ring before the call returns (the
+ * kernel reads it there); w_threshold as rfsgpu_step_error_async's (-inf: every Gaussian of the particle, what landmarkEst.dat holds).
+ * Stream-ordered, nothing waits for the GPU.  A full log (or none): RFSGPU_ERR_CAPACITY, nothing is enqueued. */
+int rfsgpu_step_estimate_async(rfsgpu_filter *f, const double *t, double w_threshold);
+/* Synchronises the stream and copies those of the rows [row_from, row_from + max_rows) that exist: hdr [rows][n_filters], gauss
+ * [rows][n_filters][6][max_est], part [rows][n_filters][4][slots] (any may be NULL; part is ignored by a log without particles);
+ * *n_rows = the number of rows in the log.  row_from outside [0, rows] or max_rows < 0: RFSGPU_ERR_INVALID.  The log keeps its rows:
+ * with _reset a long run is drained in chunks. */
+int rfsgpu_estimate_log_read(rfsgpu_filter *f, int row_from, int max_rows, struct rfsgpu_step_estimate *hdr, double *gauss, double *part,
+                             int *n_rows);
+/* on != 0: from now on every step of rfsgpu_batch_run_truth_async also appends one estimate row (w_threshold as above), taken at the
+ * point of the stream where that step's error row is taken (behind the step's resampling), its t read from the truth table row on the
+ * device; all three kinds of batch.  The run call then also checks, before anything is enqueued, that an estimate log exists and has
+ * as many free rows as the run has steps (else RFSGPU_ERR_CAPACITY), and that [metric] serves the handle.  Off (the default) the run
+ * enqueues exactly what it enqueues without this section.  RFSGPU_ERR_UNSUPPORTED on a handle that is not a filter batch. */
+int rfsgpu_batch_run_log_estimates(rfsgpu_filter *f, int on, double w_threshold);
 
 #ifdef __cplusplus
 }

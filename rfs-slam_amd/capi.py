@@ -124,6 +124,20 @@ class StepError(C.Structure):
 STEP_ERROR_DTYPE = np.dtype([(n, np.int64 if t is C.c_longlong else np.float64) for n, t in StepError._fields_])
 
 
+class StepEstimate(C.Structure):
+    """rfsgpu_step_estimate: one filter's header of one row of the estimate log (every field 8 bytes wide)."""
+    _fields_ = [("t", C.c_double), ("status", C.c_longlong), ("best_slot", C.c_longlong), ("n_particles", C.c_longlong), ("n_est", C.c_longlong),
+                ("n_logged", C.c_longlong), ("cardinality", C.c_double), ("best_weight", C.c_double), ("weight_sum", C.c_double),
+                ("best_x", C.c_double), ("best_y", C.c_double), ("best_theta", C.c_double),
+                ("mean_x", C.c_double), ("mean_y", C.c_double), ("mean_cos", C.c_double), ("mean_sin", C.c_double)]
+
+
+STEP_ESTIMATE_DTYPE = np.dtype([(n, np.int64 if t is C.c_longlong else np.float64) for n, t in StepEstimate._fields_])
+# the planes of the estimate log's gauss [rows, n_filters, 6, max_est] and part [rows, n_filters, 4, slots] arrays
+ESTIMATE_GAUSS_PLANES = ("mx", "my", "sxx", "sxy", "syy", "w")
+ESTIMATE_PART_PLANES = ("x", "y", "theta", "w")
+
+
 # every symbol include/rfsgpu.h declares, without prefix (tests check the product .so exports them all)
 ABI_SYMBOLS = [
     "abi_version", "create", "destroy", "last_error", "default_filter_config", "set_filter_config",
@@ -154,6 +168,7 @@ ABI_SYMBOLS = [
     "batch_set_sensor", "batch_sense_async", "batch_cycle_sensed_async", "batch_resample_sensed_async", "batch_last_scan", "batch_last_cycle_lds",
     "batch_set_truth", "batch_generate_truth", "batch_get_truth", "batch_run_truth_async",
     "batch_fastslam_serve_sensor", "batch_fastslam_cycle_sensed_async", "batch_fastslam_mh_cycle_sensed_async",
+    "estimate_log_create", "estimate_log_reset", "step_estimate_async", "estimate_log_read", "batch_run_log_estimates",
 ]
 
 _dp = np.ctypeslib.ndpointer(dtype=np.float64, flags="C_CONTIGUOUS")
@@ -182,6 +197,7 @@ class CFilter:
         self.device_id = device_id
         self.dm = self.dz = 3 if model == MODEL_VICTORIAPARK_3D else 2
         self._borrowed = borrowed is not None
+        self.gm_capacity = int(gm_capacity)
         if self._borrowed:          # a shard handle owned by an rfsgpu_group
             self._h = C.c_void_p(borrowed)
             return
@@ -718,6 +734,53 @@ class CFilter:
         k = min(k, n.value)
         return mean[:k], cov[:k], w[:k]
 
+    # -- [estimate] per-step pose and map estimates in a device-side log (rfsgpu_step_estimate*, csrc/estimate_log.h) ------------
+    @property
+    def n_estimate_slots(self):
+        """Slots per particle plane of the estimate log: max_per_filter, n_per_filter, or the particle count of an ordinary handle."""
+        return int(getattr(self, "max_per_filter", getattr(self, "n_per_filter", None) or self.n))
+
+    def estimate_log_create(self, log_capacity, max_est, log_particles=False):
+        """The device-side estimate log: log_capacity rows, max_est Gaussians kept per filter and row, the particle set too with
+        log_particles.  Capacity 0 frees it."""
+        slots = self.n_estimate_slots if log_particles else 0
+        self._call("estimate_log_create", C.c_int(int(log_capacity)), C.c_int(int(max_est)), C.c_int(1 if log_particles else 0))
+        self._est_shape = (int(max_est), slots) if int(log_capacity) > 0 else None
+
+    def estimate_log_reset(self):
+        self._call("estimate_log_reset")
+
+    def step_estimate_async(self, t, w_threshold=0.75):
+        """Append one row to the estimate log: t [n_filters] (or a scalar); w_threshold -inf keeps every Gaussian of the best particle.
+        Stream-ordered, no host wait."""
+        t, _ = self._metric_inputs(t, None)
+        self._call("step_estimate_async", self._ptr(t), C.c_double(w_threshold))
+
+    def estimate_log_read(self, row_from=0, max_rows=None):
+        """(hdr, gauss, part): the rows [row_from, row_from + max_rows) that exist (None: all from row_from) -- hdr a structured array
+        [rows, n_filters] (STEP_ESTIMATE_DTYPE), gauss [rows, n_filters, 6, max_est] (ESTIMATE_GAUSS_PLANES), part
+        [rows, n_filters, 4, slots] (ESTIMATE_PART_PLANES; None for a log without particles).  Gaussians at or beyond a header's n_logged
+        and particles at or beyond its n_particles are not the log's: they come back as zeros.  Synchronises; the log keeps its rows."""
+        nF = self.n_metric_filters
+        max_est, slots = getattr(self, "_est_shape", None) or (0, 0)
+        n = C.c_int()
+        null = C.c_void_p(None)
+        self._call("estimate_log_read", C.c_int(int(row_from)), C.c_int(0), null, null, null, C.byref(n))
+        rows = max(0, n.value - int(row_from))
+        if max_rows is not None:
+            rows = min(rows, int(max_rows))
+        hdr = np.zeros((rows, nF), dtype=STEP_ESTIMATE_DTYPE)
+        gauss = np.zeros((rows, nF, 6, max_est))
+        part = np.zeros((rows, nF, 4, slots)) if slots else None
+        self._call("estimate_log_read", C.c_int(int(row_from)), C.c_int(rows), self._ptr(hdr), self._ptr(gauss) if max_est else null,
+                   self._ptr(part) if part is not None else null, C.byref(n))
+        # what the kernel did not write (Gaussians beyond n_logged, particles beyond n_particles) is uninitialised device memory: zeros here
+        if max_est:
+            np.copyto(gauss, 0.0, where=(np.arange(max_est) >= hdr["n_logged"][..., None])[:, :, None, :])
+        if part is not None:
+            np.copyto(part, 0.0, where=(np.arange(slots) >= hdr["n_particles"][..., None])[:, :, None, :])
+        return hdr, gauss, part
+
     # -- timing --------------------------------------------------------------------------------
     def getTimingInfo(self):
         t = Timing()
@@ -751,6 +814,7 @@ class CBatch(CFilter):
                                                              else "no gfx950 device / bad arguments"))
         self.n_filters = int(n_filters)
         self.n_per_filter = int(n_per_filter)
+        self.gm_capacity = int(gm_capacity)
 
     def block(self, b):
         """The global slots of filter b."""
@@ -977,6 +1041,11 @@ class CBatch(CFilter):
         self._call("batch_run_truth_async", C.c_int(int(k_from)), C.c_int(int(k_to)), C.c_int(1 if track_errors else 0), C.c_double(w_threshold),
                    C.c_double(cutoff), C.c_double(order))
 
+    def run_log_estimates(self, on=True, w_threshold=0.75):
+        """rfsgpu_batch_run_log_estimates: while on, every step of run_truth_async appends one row to the estimate log
+        (estimate_log_create), taken where the step's error row is taken."""
+        self._call("batch_run_log_estimates", C.c_int(1 if on else 0), C.c_double(w_threshold))
+
     def last_cycle_lds(self):
         """Bytes of LDS a workgroup of the step kernel had in the batch's last cycle (0 before the first)."""
         out = C.c_longlong(0)
@@ -1011,6 +1080,7 @@ class CBatchMH(CBatch):
                                                                 else "no gfx950 device / bad arguments (max_per_filter < n_per_filter?)"))
         self.n_filters = int(n_filters)
         self.n_per_filter = int(n_per_filter)
+        self.gm_capacity = int(gm_capacity)
         self.max_per_filter = int(max_per_filter)
 
     def block(self, b, n=None):

@@ -1,0 +1,135 @@
+// estimate_log.h -- what each filter ESTIMATED at a step, kept on the device (rfsgpu.h [estimate]): the reference's simulators write
+// particlePose.dat and landmarkEst.dat per time step (src/rbphdslam2dSim.cpp:620-638, src/fastslam2dSim.cpp:613-632); this kernel writes
+// the same content into a row of a device-side log, for an ordinary 2-D handle (one filter) or every filter of a batch, in ONE launch
+// that reads weights, poses, counts and the current slab as they are at its point of the stream and changes nothing of them.
+//
+// Grid (nF, 1 + ceil(slots / 256)), 64 lanes per workgroup (one wave: wave-synchronous, no barrier, no LDS):
+//   blockIdx.y == 0 -- the header and the Gaussians of filter blockIdx.x.  The SELECTION is map_metric_kernel's steps 1 and 2,
+//     restated: lane l scans slots l, l + 64, ... of the block in ascending order for the first weight strictly greater than
+//     everything before it, starting from 0; the 64 candidates meet in an xor butterfly that prefers the larger weight, then the lower
+//     slot; no weight > 0 (all zero, negative or NaN): the block's slot 0.  The sums (weights, w x, w y, w cos theta, w sin theta, the
+//     cardinality) run over the metric's FIXED TREE: every lane adds its own entries in ascending order, then wave_sum's butterfly
+//     (32, 16, ..., 1) -- so weight_sum and cardinality carry the bits rfsgpu_step_error reports.  The PREDICATE is the metric's step 3:
+//     entries beyond the count do not exist, log-odds become 1 - 1 / (1 + exp(w)), holes (w < 0) are skipped, w >= w_threshold keeps, and
+//     a ballot prefix per 64 entries gives each kept Gaussian its position in mixture order.  Where the metric fills LDS tables, this
+//     kernel stores the six planes (mx, my, sxx, sxy, syy, w) to global memory for positions < max_est: the lanes of one ballot round
+//     hold consecutive positions, so each plane's stores are consecutive doubles.
+//   blockIdx.y >= 1 -- the particle planes (x, y, theta, w) of slots [256 (y - 1), 256 y) of the filter, four slots per lane at a
+//     stride of 64: they need nothing from the selection.  Launched only when the log keeps particles.
+//
+// live: nothing, or a MetricLive (map_metric.h) for a batch of multi-hypothesis FastSLAM filters: the wave reads the filter's live
+// count once (a scalar read), clamps it to [0, stride], and no slot at or beyond it is read -- by either kind of workgroup.  A count of
+// 0 reads nothing of the block at all: best_slot is the block's first slot, n_est and cardinality are 0, pose and mean fields NaN.
+//
+// Bounds: a Gaussian is stored at pos < maxEst <= cap (the engine checks max_est against gm_capacity), a particle at s < nLive <=
+// nPer <= slots (the stride the part array was allocated with); nothing else is written but lane 0's header.
+#pragma once
+
+struct EstimateArg {
+  const double *in;        // the call's times: filter b's at in[inStride * b] (a slot of the pinned staging ring read in place, stride 1; or a
+  int inStride;            //  row of the truth tables on the device, {t, x, y, theta} per filter: stride 4)
+  struct rfsgpu_step_estimate *hdr;   // [nF] the row's headers
+  double *gauss;           // [nF][6][maxEst] the row's Gaussian planes (nullptr with maxEst 0)
+  double *part;            // [nF][4][slots] the row's particle planes (nullptr: not kept)
+  double wThr;
+  int nPer;                // particles per filter (a multi-hypothesis batch: the stride)
+  int slots;               // the part array's slots per plane (>= nPer)
+  int maxEst;
+  int holes;               // merged-away entries (w < 0) sit in the slab: skip them
+  int logOdds;             // FastSLAM kinds: a Gaussian's weight is the log-odds of existence
+};
+
+#define ESTIMATE_PART_SLOTS 256   // slots per particle-plane workgroup
+
+template <typename... TLive>
+__global__ __launch_bounds__(64) void estimate_log_kernel(Buffers B, int cur, EstimateArg A, TLive... live) {
+  const int b = blockIdx.x, lane = threadIdx.x;
+  const int nPer = A.nPer, lo = b * nPer;
+  int nLive = nPer;
+  if constexpr (sizeof...(TLive) == 1) {   // a MetricLive: the filter's count lives on the device (wave-uniform: one scalar read)
+    const MetricLive &L = pack_first(live...);
+    nLive = __builtin_amdgcn_readfirstlane(L.words[(size_t)b * L.wordStride + L.word]);
+    nLive = nLive < 0 ? 0 : (nLive > nPer ? nPer : nLive);
+  }
+
+  if (blockIdx.y >= 1) {   // ---- the particle planes: a plain copy of the live slots -----------------------------------------------
+    if (!A.part) return;
+    double *px = A.part + (size_t)b * 4 * A.slots, *py = px + A.slots, *pth = py + A.slots, *pwt = pth + A.slots;
+    const int s0 = ((int)blockIdx.y - 1) * ESTIMATE_PART_SLOTS;
+#pragma unroll
+    for (int q = 0; q < ESTIMATE_PART_SLOTS / 64; q++) {
+      const int s = s0 + q * 64 + lane;
+      if (s < nLive) {
+        const double *x = B.pose + (size_t)3 * (lo + s);
+        px[s] = x[0]; py[s] = x[1]; pth[s] = x[2]; pwt[s] = B.weight[lo + s];
+      }
+    }
+    return;
+  }
+
+  const double qnan = __longlong_as_double(0x7ff8000000000000ll);
+  const double t = A.in[(size_t)A.inStride * b];
+
+  // ---- 1 + 2 of map_metric_kernel: highest-weight particle, weight sum, the weighted pose sums ------------------------------------
+  double bw = 0.0, sw = 0.0, sx = 0.0, sy = 0.0, sc = 0.0, ss = 0.0;
+  int bi = -1;
+  for (int s = lane; s < nLive; s += 64) {
+    const double w = B.weight[lo + s];
+    if (w > bw) { bw = w; bi = s; }
+    sw += w;
+    const double *x = B.pose + (size_t)3 * (lo + s);
+    double sn, cs;
+    sincos(x[2], &sn, &cs);
+    sx += x[0] * w; sy += x[1] * w; sc += cs * w; ss += sn * w;
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const double ow = __shfl_xor(bw, o, 64);
+    const int oi = __shfl_xor(bi, o, 64);
+    if (oi >= 0 && (ow > bw || (ow == bw && (bi < 0 || oi < bi)))) { bw = ow; bi = oi; }
+  }
+  const int best = lo + (bi < 0 ? 0 : bi);
+  sw = wave_sum(sw);
+  sx = wave_sum(sx) / sw; sy = wave_sum(sy) / sw; sc = wave_sum(sc) / sw; ss = wave_sum(ss) / sw;
+
+  // ---- 3 of map_metric_kernel: the best particle's Gaussians, compacted in mixture order, straight to the row's planes -------------
+  double card = 0.0, bestW = 0.0, bx = qnan, by = qnan, bth = qnan;
+  int n1 = 0;
+  if (nLive > 0) {
+    int cnt = B.count[best];
+    cnt = cnt < 0 ? 0 : (cnt > B.cap ? B.cap : cnt);
+    const double *pl = B.slab[cur] + (size_t)best * PL_COUNT * (size_t)B.cap;
+    const double *pw = pl + (size_t)PL_W * B.cap, *pmx = pl + (size_t)PL_MX * B.cap, *pmy = pl + (size_t)PL_MY * B.cap;
+    const double *pxx = pl + (size_t)PL_SXX * B.cap, *pxy = pl + (size_t)PL_SXY * B.cap, *pyy = pl + (size_t)PL_SYY * B.cap;
+    const size_t me = (size_t)A.maxEst;
+    double *g = A.gauss + (size_t)b * 6 * me;
+    const unsigned long long below = (1ull << lane) - 1ull;
+    for (int base = 0; base < cnt; base += 64) {
+      const int m = base + lane;
+      bool valid = m < cnt;
+      double w = valid ? pw[m] : 0.0;
+      if (A.logOdds) w = valid ? 1 - 1 / (1 + exp(w)) : 0.0;
+      if (A.holes && w < 0) valid = false;
+      if (valid) card += w;
+      const bool keep = valid && w >= A.wThr;
+      const unsigned long long mask = __ballot(keep);
+      const int pos = n1 + __popcll(mask & below);
+      if (keep && pos < A.maxEst) {
+        g[pos] = pmx[m]; g[me + pos] = pmy[m]; g[2 * me + pos] = pxx[m]; g[3 * me + pos] = pxy[m]; g[4 * me + pos] = pyy[m]; g[5 * me + pos] = w;
+      }
+      n1 += __popcll(mask);
+    }
+    card = wave_sum(card);
+    const double *x = B.pose + (size_t)3 * best;
+    bestW = B.weight[best]; bx = x[0]; by = x[1]; bth = x[2];
+  } else {
+    sx = sy = sc = ss = qnan;
+  }
+  if (lane == 0) {
+    struct rfsgpu_step_estimate &o = A.hdr[b];
+    o.t = t; o.status = n1 > A.maxEst ? 1 : 0; o.best_slot = best; o.n_particles = nLive; o.n_est = n1; o.n_logged = n1 < A.maxEst ? n1 : A.maxEst;
+    o.cardinality = card; o.best_weight = bestW; o.weight_sum = sw;
+    o.best_x = bx; o.best_y = by; o.best_theta = bth;
+    o.mean_x = sx; o.mean_y = sy; o.mean_cos = sc; o.mean_sin = ss;
+  }
+}

@@ -28,6 +28,7 @@
 #include "fastslam_cycle.h"
 #include "motion.h"
 #include "map_metric.h"
+#include "estimate_log.h"
 #include "batch_loop.h"
 #include "batch_sensor.h"
 #include "batch_truth.h"
@@ -279,6 +280,13 @@ struct rfsgpu_filter {
   struct rfsgpu_step_error *dErrLog = nullptr;          // [errLogCap][nF]
   int errLogCap = 0, errLogRows = 0;
   struct rfsgpu_step_error *dErrRow = nullptr;          // [nF]
+  // [estimate] per-step pose / map estimates (estimate_log.h): the device-side log beside dErrLog
+  struct rfsgpu_step_estimate *dEstHdr = nullptr;       // [estLogCap][nF]
+  double *dEstGauss = nullptr;                          // [estLogCap][nF][6][estMax] (nullptr with estMax 0)
+  double *dEstPart = nullptr;                           // [estLogCap][nF][4][estSlots] (nullptr: the log keeps no particles)
+  int estLogCap = 0, estLogRows = 0, estMax = 0, estSlots = 0;
+  bool estRunOn = false;                                // rfsgpu_batch_run_log_estimates: rfsgpu_batch_run_truth_async appends a row per step
+  double estRunThr = 0.0;
   bool groupShard = false;                       // a shard of an rfsgpu_group: the [metric] calls refuse
 };
 
@@ -625,6 +633,7 @@ void rfsgpu_destroy(rfsgpu_filter *f) {
   hipFree(f->dBSensor); hipFree(f->dBSensorLm); hipFree(f->dBSensorPose); hipFree(f->dBSensorCaps); hipFree(f->dBSensorPrev); hipFree(f->dBSensorErrFilter);
   hipFree(f->dTruthCfg); hipFree(f->dTruthProp); hipFree(f->dTruthGt); hipFree(f->dTruthTgt); hipFree(f->dTruthLm); hipFree(f->dTruthSeen); hipFree(f->dTruthCounts);
   hipFree(f->dGtXY); hipFree(f->dGtSeen); hipFree(f->dGtN); hipFree(f->dErrLog); hipFree(f->dErrRow);
+  hipFree(f->dEstHdr); hipFree(f->dEstGauss); hipFree(f->dEstPart);
   if (f->hErr) hipHostFree(f->hErr);
   if (f->hJobCount) hipHostFree(f->hJobCount);
   if (f->hSums) hipHostFree(f->hSums);
@@ -4581,6 +4590,123 @@ int rfsgpu_get_map_estimate(rfsgpu_filter *f, int filter, double w_threshold, in
   return RFSGPU_OK;
 }
 
+// ---- [estimate] per-step pose and map estimates in a device-side log (estimate_log.h) -------------------------------------------------
+// Served where [metric] is served: every call starts with metric_check.
+static inline int estimate_slots(const rfsgpu_filter *f) { return f->batch ? f->nPer : f->N; }
+static void estimate_log_free(rfsgpu_filter *f) {
+  hipFree(f->dEstHdr); hipFree(f->dEstGauss); hipFree(f->dEstPart);
+  f->dEstHdr = nullptr; f->dEstGauss = nullptr; f->dEstPart = nullptr;
+  f->estLogCap = f->estLogRows = f->estMax = f->estSlots = 0;
+}
+// One launch into row `row` of the log: the call's times go into a slot of the pinned staging ring (metric_launch's), which the kernel
+// reads in place.  devIn (rfsgpu_batch_run_truth_async): the times are the first of every four doubles of a truth table row on the device.
+static int estimate_launch(rfsgpu_filter *f, const double *t, double w_threshold, int row, const double *devIn = nullptr) {
+  const int nF = metric_nf(f);
+  hipSetDevice(f->device);
+  const int nPer = estimate_slots(f);
+  if (f->dEstPart && nPer > f->estSlots) {
+    f->err = "step_estimate: the handle holds more particles than the estimate log's particle planes were created for (rfsgpu_estimate_log_create)";
+    return RFSGPU_ERR_INVALID;
+  }
+  double *h = nullptr;
+  int k = 0;
+  if (!devIn) {
+    { const int rc = ring_acquire(f, f->stage, &h, &k); if (rc != RFSGPU_OK) return rc; }
+    for (int b = 0; b < nF; b++) h[b] = t[b];
+  }
+  const size_t at = (size_t)row * nF;
+  EstimateArg A{devIn ? devIn : h, devIn ? 4 : 1, f->dEstHdr + at, f->dEstGauss ? f->dEstGauss + at * 6 * (size_t)f->estMax : nullptr,
+                f->dEstPart ? f->dEstPart + at * 4 * (size_t)f->estSlots : nullptr, w_threshold, nPer, f->estSlots, f->estMax, f->holes ? 1 : 0,
+                metric_log_odds(f) ? 1 : 0};
+  const dim3 grid(nF, 1 + (f->dEstPart ? (nPer + ESTIMATE_PART_SLOTS - 1) / ESTIMATE_PART_SLOTS : 0));
+  if (f->mhBatch) {     // every filter's count is a word of its cycle block, read by the kernel where it runs: nothing waits for it
+    FsCycleState S0;
+    mhb_view(f, f->mhbBlock, 0, S0);
+    estimate_log_kernel<<<grid, 64, 0, f->stream>>>(f->B, f->cur, A, MetricLive{S0.w, FSC_WORDS, FSC_N});
+  } else {
+    estimate_log_kernel<<<grid, 64, 0, f->stream>>>(f->B, f->cur, A);
+  }
+  HIPCHK(hipGetLastError());
+  if (!devIn) HIPCHK(hipEventRecord(f->stage.ev[k], f->stream));
+  return RFSGPU_OK;
+}
+int rfsgpu_estimate_log_create(rfsgpu_filter *f, int log_capacity, int max_est, int log_particles) {
+  CHECK_HANDLE(f);
+  int rc = metric_check(f, "estimate_log_create");
+  if (rc != RFSGPU_OK) return rc;
+  if (log_capacity < 0) return fail(f, RFSGPU_ERR_INVALID, "estimate_log_create: negative capacity");
+  if (max_est < 0 || max_est > f->cap) return fail(f, RFSGPU_ERR_INVALID, "estimate_log_create: max_est must lie in 0 ... gm_capacity");
+  hipSetDevice(f->device);
+  HIPCHK(hipStreamSynchronize(f->stream));
+  estimate_log_free(f);
+  if (log_capacity == 0) return RFSGPU_OK;
+  const size_t cells = (size_t)log_capacity * metric_nf(f);
+  const int slots = estimate_slots(f);
+  hipError_t e = hipMalloc(&f->dEstHdr, cells * sizeof(struct rfsgpu_step_estimate));
+  if (e == hipSuccess && max_est > 0) e = hipMalloc(&f->dEstGauss, cells * 6 * (size_t)max_est * sizeof(double));
+  if (e == hipSuccess && log_particles && slots > 0) e = hipMalloc(&f->dEstPart, cells * 4 * (size_t)slots * sizeof(double));
+  if (e != hipSuccess) {
+    estimate_log_free(f);
+    f->err = std::string("estimate_log_create: hipMalloc: ") + hipGetErrorString(e);
+    return RFSGPU_ERR_HIP;
+  }
+  f->estLogCap = log_capacity;
+  f->estMax = max_est;
+  f->estSlots = f->dEstPart ? slots : 0;
+  return RFSGPU_OK;
+}
+int rfsgpu_estimate_log_reset(rfsgpu_filter *f) {
+  CHECK_HANDLE(f);
+  int rc = metric_check(f, "estimate_log_reset");
+  if (rc != RFSGPU_OK) return rc;
+  f->estLogRows = 0;   // (stream order keeps a row that is still being written ahead of the next one that lands there)
+  return RFSGPU_OK;
+}
+int rfsgpu_step_estimate_async(rfsgpu_filter *f, const double *t, double w_threshold) {
+  if (!f) return RFSGPU_ERR_INVALID;
+  if (!(f->mhBatch && f->mhbMetrics)) {    // (as rfsgpu_step_error_async: a served multi-hypothesis batch keeps its cycles in flight)
+    CHECK_HANDLE(f);
+  }
+  int rc = metric_check(f, "step_estimate_async");
+  if (rc != RFSGPU_OK) return rc;
+  if (!t) return fail(f, RFSGPU_ERR_INVALID, "step_estimate_async: null time array");
+  if (f->estLogRows >= f->estLogCap)
+    return fail(f, RFSGPU_ERR_CAPACITY, f->estLogCap ? "step_estimate_async: the estimate log is full (rfsgpu_estimate_log_read, then rfsgpu_estimate_log_reset)"
+                                                      : "step_estimate_async: no estimate log (rfsgpu_estimate_log_create)");
+  rc = estimate_launch(f, t, w_threshold, f->estLogRows);
+  if (rc == RFSGPU_OK) f->estLogRows++;
+  return rc;
+}
+int rfsgpu_estimate_log_read(rfsgpu_filter *f, int row_from, int max_rows, struct rfsgpu_step_estimate *hdr, double *gauss, double *part, int *n_rows) {
+  CHECK_HANDLE(f);
+  int rc = metric_check(f, "estimate_log_read");
+  if (rc != RFSGPU_OK) return rc;
+  if (max_rows < 0) return fail(f, RFSGPU_ERR_INVALID, "estimate_log_read: negative max_rows");
+  if (row_from < 0 || row_from > f->estLogRows) return fail(f, RFSGPU_ERR_INVALID, "estimate_log_read: row_from outside 0 ... the number of rows in the log");
+  hipSetDevice(f->device);
+  const size_t nF = (size_t)metric_nf(f), at = (size_t)row_from * nF;
+  const size_t cells = (size_t)std::min(max_rows, f->estLogRows - row_from) * nF;
+  if (cells > 0) {
+    if (hdr) HIPCHK(hipMemcpyAsync(hdr, f->dEstHdr + at, cells * sizeof(struct rfsgpu_step_estimate), hipMemcpyDeviceToHost, f->stream));
+    if (gauss && f->dEstGauss)
+      HIPCHK(hipMemcpyAsync(gauss, f->dEstGauss + at * 6 * (size_t)f->estMax, cells * 6 * (size_t)f->estMax * sizeof(double), hipMemcpyDeviceToHost, f->stream));
+    if (part && f->dEstPart)
+      HIPCHK(hipMemcpyAsync(part, f->dEstPart + at * 4 * (size_t)f->estSlots, cells * 4 * (size_t)f->estSlots * sizeof(double), hipMemcpyDeviceToHost, f->stream));
+  }
+  HIPCHK(hipStreamSynchronize(f->stream));
+  if (n_rows) *n_rows = f->estLogRows;
+  return RFSGPU_OK;
+}
+int rfsgpu_batch_run_log_estimates(rfsgpu_filter *f, int on, double w_threshold) {
+  CHECK_HANDLE_HOST(f);
+  int rc = metric_check(f, "batch_run_log_estimates");
+  if (rc != RFSGPU_OK) return rc;
+  if (!f->batch) return fail(f, RFSGPU_ERR_UNSUPPORTED, "batch_run_log_estimates: rfsgpu_batch_run_truth_async serves filter batches only, not an ordinary handle");
+  f->estRunOn = on != 0;
+  f->estRunThr = w_threshold;
+  return RFSGPU_OK;
+}
+
 // ---- [truth] every filter's ground truth drawn on the device, and a run of steps in one call (batch_truth.h) --------------------------
 static const BatchCall BATCH_SET_TRUTH{"batch_set_truth", 0, nullptr, nullptr};
 static const BatchCall BATCH_GENERATE_TRUTH{"batch_generate_truth", 0, nullptr, nullptr};
@@ -4726,6 +4852,14 @@ int rfsgpu_batch_run_truth_async(rfsgpu_filter *f, int k_from, int k_to, int tra
       return RFSGPU_ERR_CAPACITY;
     }
   }
+  if (f->estRunOn) {     // rfsgpu_batch_run_log_estimates: one estimate row per step, beside the error row
+    if ((rc = metric_check(f, "batch_run_truth")) != RFSGPU_OK) return rc;
+    if (f->estLogRows + (k_to - k_from) > f->estLogCap) {
+      f->err = f->estLogCap ? "batch_run_truth: the estimate log has fewer free rows than the run has steps (rfsgpu_estimate_log_read, then rfsgpu_estimate_log_reset)"
+                            : "batch_run_truth: rfsgpu_batch_run_log_estimates is on without an estimate log (rfsgpu_estimate_log_create)";
+      return RFSGPU_ERR_CAPACITY;
+    }
+  }
   for (int k = k_from; k < k_to; k++) {
     const size_t row = (size_t)k * nF;
     const unsigned long long call = (unsigned long long)k;
@@ -4745,6 +4879,10 @@ int rfsgpu_batch_run_truth_async(rfsgpu_filter *f, int k_from, int k_to, int tra
     if (track_errors) {
       if ((rc = metric_launch(f, nullptr, nullptr, w_threshold, cutoff, order, f->dErrLog + (size_t)f->errLogRows * nF, f->dTruthTgt + 4 * row)) != RFSGPU_OK) return rc;
       f->errLogRows++;
+    }
+    if (f->estRunOn) {
+      if ((rc = estimate_launch(f, nullptr, f->estRunThr, f->estLogRows, f->dTruthTgt + 4 * row)) != RFSGPU_OK) return rc;
+      f->estLogRows++;
     }
   }
   return RFSGPU_OK;

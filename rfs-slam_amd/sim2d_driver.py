@@ -126,6 +126,8 @@ def first_seen_times(data, P=C1_SIM):
 
 # the reference's evaluation constants (src/analysis2dSim.cpp:182, :232-233): estimate weight threshold, COLA cutoff and order
 ERROR_W_THRESHOLD, ERROR_CUTOFF, ERROR_ORDER = 0.75, 0.20, 1.0
+# the estimate log's default threshold: every Gaussian of the best particle, as the reference's landmarkEst.dat holds them
+ESTIMATE_W_THRESHOLD = -np.inf
 
 
 def configure(f, P=C1_SIM):
@@ -188,12 +190,16 @@ def configure_fastslam_batch_filter(batch, b, P=C1_FASTSLAM_SIM):
 class Sim2dRun:
     """run() :540-643 over `filters` (all driven through the same realisation); `on_step(k, run)` is called after every update."""
 
-    def __init__(self, filters, data, P=C1_SIM, seed=1, eff_n=None, track_errors=False, device_resample=False):
+    def __init__(self, filters, data, P=C1_SIM, seed=1, eff_n=None, track_errors=False, device_resample=False, track_estimates=False,
+                 estimate_threshold=ESTIMATE_W_THRESHOLD, estimate_max=None, log_particles=False):
         """device_resample: the resample-or-normalise tail of an update runs on the device (rfsgpu_resample_async): the host reads the
         decision and the plan (it keeps the poses) instead of the weights; same realisation, same results.
         track_errors: every filter gets the realisation's ground truth and a device-side error log; each cycle ends with one
         stream-ordered step_error_async (after the resampling, where the reference driver logs its particle set); errors() reads
-        the logs once.  Off (the default) nothing is enqueued."""
+        the logs once.  Off (the default) nothing is enqueued.
+        track_estimates: every filter gets a device-side estimate log ([estimate] in include/rfsgpu.h: estimate_max Gaussians per row,
+        None: gm_capacity; the particle set too with log_particles); each cycle ends with one stream-ordered
+        step_estimate_async(t, estimate_threshold) at the point where the error row is taken; estimates() reads the logs once."""
         self.filters = list(filters)
         self.n = self.filters[0].n
         assert all(f.n == self.n for f in self.filters)
@@ -217,6 +223,11 @@ class Sim2dRun:
             for f in self.filters:
                 f.set_ground_truth(data["landmarks"], fs)
                 f.error_log_create(int(data["K"]))
+        self.track_estimates = bool(track_estimates)
+        self.estimate_threshold = float(estimate_threshold)
+        if self.track_estimates:
+            for f in self.filters:
+                f.estimate_log_create(int(data["K"]), f.gm_capacity if estimate_max is None else int(estimate_max), log_particles)
 
     def _each(self, fn):
         return [fn(f) for f in self.filters]
@@ -226,7 +237,15 @@ class Sim2dRun:
         if self.track_errors:
             t, g = k * self.P["dt"], self.data["gt"][k][None, :]
             self._each(lambda f: f.step_error_async(t, g, ERROR_W_THRESHOLD, ERROR_CUTOFF, ERROR_ORDER))
+        if self.track_estimates:
+            self._each(lambda f: f.step_estimate_async(k * self.P["dt"], self.estimate_threshold))
         return fired
+
+    def estimates(self):
+        """One (hdr [steps, 1], gauss [steps, 1, 6, max_est], part [steps, 1, 4, n] or None) per filter: the estimate rows logged so
+        far (capi.CFilter.estimate_log_read; one read each) -- what write_run_logs takes with b = 0."""
+        assert self.track_estimates, "Sim2dRun(..., track_estimates=True)"
+        return [f.estimate_log_read() for f in self.filters]
 
     def errors(self):
         """One structured array [steps] (capi.STEP_ERROR_DTYPE) per filter: the rows logged so far (one read each)."""
@@ -414,9 +433,12 @@ class Sim2dBatchRun:
     generate()'s: the same model under another generator, as with the device loop."""
 
     def __init__(self, target, datas, Ps, seeds, track_errors=False, device_loop=False, fastslam=False, device_sensor=False, device_truth=False,
-                 kmax=None):
+                 kmax=None, track_estimates=False, estimate_threshold=ESTIMATE_W_THRESHOLD, estimate_max=None, log_particles=False):
         """track_errors: as in Sim2dRun -- each filter's ground truth is uploaded, every cycle ends with one step_error_async (one
-        launch for the whole batch; one per handle otherwise), errors() reads the log(s) once at the end."""
+        launch for the whole batch; one per handle otherwise), errors() reads the log(s) once at the end.
+        track_estimates: as in Sim2dRun -- an estimate log of estimate_max Gaussians per filter and row (None: gm_capacity), with the
+        particle sets when log_particles; every cycle ends with one step_estimate_async where the error row is taken, and the one-call
+        run (device_truth) logs through run_log_estimates; estimates() is the one read."""
         self.device_truth = bool(device_truth)
         if self.device_truth:
             assert datas is None and kmax is not None and isinstance(target, capi.CBatch), "device_truth: a FilterBatch or FastSLAMBatch, datas=None, kmax given"
@@ -469,6 +491,14 @@ class Sim2dBatchRun:
                     self.handles[b].error_log_create(rows)
             if self.batch is not None:
                 self.batch.error_log_create(rows)
+        self.track_estimates = bool(track_estimates)
+        self.estimate_threshold = float(estimate_threshold)
+        if self.track_estimates:
+            rows = int(min(d["K"] for d in self.datas))
+            for f in ([self.batch] if self.batch is not None else self.handles):
+                f.estimate_log_create(rows, f.gm_capacity if estimate_max is None else int(estimate_max), log_particles)
+            if self.device_truth:
+                self.batch.run_log_estimates(True, self.estimate_threshold)
         if self.device_loop:
             assert self.batch is not None, "the device loop needs a FilterBatch"
             self._device_loop_setup(seeds)
@@ -529,6 +559,8 @@ class Sim2dBatchRun:
             self.last_n_z = None            # (on the device: FilterBatch.last_scan reads the sets)
             if self.track_errors:
                 bt.step_error_async(self._t[k], self._gt[k], ERROR_W_THRESHOLD, ERROR_CUTOFF, ERROR_ORDER)
+            if self.track_estimates:
+                bt.step_estimate_async(self._t[k], self.estimate_threshold)
             return None
         if self.fastslam:
             bt.batch_fastslam_cycle_async_packed(True, self._z[k], self._nz[k], normalize=True)
@@ -538,6 +570,8 @@ class Sim2dBatchRun:
         self.last_n_z = self._nz[k]
         if self.track_errors:
             bt.step_error_async(self._t[k], self._gt[k], ERROR_W_THRESHOLD, ERROR_CUTOFF, ERROR_ORDER)
+        if self.track_estimates:
+            bt.step_estimate_async(self._t[k], self.estimate_threshold)
         return None
 
     def resample_counts(self):
@@ -560,6 +594,13 @@ class Sim2dBatchRun:
             else:
                 for b, f in enumerate(self.handles):
                     f.step_error_async(t[b], g[b][None, :], ERROR_W_THRESHOLD, ERROR_CUTOFF, ERROR_ORDER)
+        if self.track_estimates:
+            t = np.array([k * P["dt"] for P in self.Ps])
+            if self.batch is not None:
+                self.batch.step_estimate_async(t, self.estimate_threshold)
+            else:
+                for b, f in enumerate(self.handles):
+                    f.step_estimate_async(t[b], self.estimate_threshold)
         return fired
 
     def errors(self):
@@ -568,6 +609,15 @@ class Sim2dBatchRun:
         if self.batch is not None:
             return self.batch.error_log_read()
         return np.stack([f.error_log_read()[:, 0] for f in self.handles], axis=1)
+
+    def estimates(self):
+        """(hdr [steps, n_filters], gauss [steps, n_filters, 6, max_est], part [steps, n_filters, 4, slots] or None): the estimate
+        rows logged so far (capi.CFilter.estimate_log_read): one read (per handle) -- what write_run_logs takes."""
+        assert self.track_estimates, "Sim2dBatchRun(..., track_estimates=True)"
+        if self.batch is not None:
+            return self.batch.estimate_log_read()
+        each = [f.estimate_log_read() for f in self.handles]
+        return tuple(None if each[0][q] is None else np.concatenate([e[q] for e in each], axis=1) for q in range(3))
 
     def _step(self, k):
         Zs = []
@@ -656,7 +706,8 @@ class Sim2dMHBatchRun:
     is the device's resampling draw of (seeds[b], k).  device_truth=True (implies device_sensor; datas=None, kmax = the steps to
     generate): the ground truth is the device's too (device_truth_datas), and run() without on_step is ONE run_truth_async."""
 
-    def __init__(self, target, datas, Ps, seeds, n=None, device_loop=False, track_errors=False, device_sensor=False, device_truth=False, kmax=None):
+    def __init__(self, target, datas, Ps, seeds, n=None, device_loop=False, track_errors=False, device_sensor=False, device_truth=False, kmax=None,
+                 track_estimates=False, estimate_threshold=ESTIMATE_W_THRESHOLD, estimate_max=None, log_particles=False):
         self.device_truth = bool(device_truth)
         self.device_sensor = bool(device_sensor) or self.device_truth
         if self.device_sensor:
@@ -671,7 +722,9 @@ class Sim2dMHBatchRun:
         self.n = n = int(n if n is not None else (self.batch.n_per_filter if self.batch is not None else self.handles[0].n))
         self.device_loop = bool(device_loop)
         self.track_errors = bool(track_errors)
-        assert self.batch is not None or not (self.device_loop or self.track_errors), "the device loop and the error tracking need an MHFastSLAMBatch"
+        self.track_estimates = bool(track_estimates)
+        self.estimate_threshold = float(estimate_threshold)
+        assert self.batch is not None or not (self.device_loop or self.track_errors or self.track_estimates), "the device loop and the error tracking need an MHFastSLAMBatch"
         K = int(min(d["K"] for d in datas))
         self.rngs = [np.random.default_rng(s) for s in seeds]
         if not self.device_sensor:
@@ -712,6 +765,11 @@ class Sim2dMHBatchRun:
             for b, (d, P) in enumerate(zip(self.datas, self.Ps)):
                 self.batch.set_ground_truth(d["landmarks"], d["first_seen"] if self.device_truth else first_seen_times(d, P), filter=b)
             self.batch.error_log_create(K)
+        if self.track_estimates:    # (served where the metric is: the same switch; the kernel reads each filter's live count on the device)
+            self.batch.serve_metrics(True)
+            self.batch.estimate_log_create(K, self.batch.gm_capacity if estimate_max is None else int(estimate_max), log_particles)
+            if self.device_truth:
+                self.batch.run_log_estimates(True, self.estimate_threshold)
 
     def _moved(self, b, x, k):
         """ParticleFilter::propagate of filter b's live particles on the host (the ground truth for the first 100 steps, :590-593)."""
@@ -747,6 +805,14 @@ class Sim2dMHBatchRun:
                 h.cycle_async(self._z[k, b, :self._nz[k, b]], float(self.u01[k, b]), predict=True)
         if self.track_errors:
             bt.step_error_async(self._t[k], self._gt[k], ERROR_W_THRESHOLD, ERROR_CUTOFF, ERROR_ORDER)
+        if self.track_estimates:
+            bt.step_estimate_async(self._t[k], self.estimate_threshold)
+
+    def estimates(self):
+        """(hdr, gauss, part) as Sim2dBatchRun.estimates(): part [steps, n_filters, 4, max_per_filter], a row's first n_particles
+        entries per plane being the filter's live set."""
+        assert self.track_estimates, "Sim2dMHBatchRun(..., track_estimates=True)"
+        return self.batch.estimate_log_read()
 
     def errors(self):
         """The rows logged so far as one structured array [steps, n_filters] (capi.STEP_ERROR_DTYPE): the one read (it also waits for
@@ -768,6 +834,63 @@ class Sim2dMHBatchRun:
     def synchronize(self):
         for f in ([self.batch] if self.batch is not None else self.handles):
             f.synchronize()
+
+
+def write_run_logs(log_dir, b, estimates, truth, precision=None):
+    """Filter b's log files in the formats of the reference's simulators (src/rbphdslam2dSim.cpp:388-437, :620-638), from the rows of
+    an estimate log: `estimates` = (hdr, gauss, part) as estimates() / capi.CFilter.estimate_log_read return them (part needs
+    log_particles), `truth` a dict with gt [K, 3], odom [K, 3], landmarks [L, 2], dt and optionally first_seen [L] (absent: all -1) --
+    generate()'s dict plus dt, or FilterBatch.get_truth(b)'s.  Writes into log_dir (created if missing)
+        gtPose.dat         `t x y theta`                      one line per step k, t = k dt
+        gtLandmark.dat     `x y t_first_in_range`
+        deadReckoning.dat  `t x y theta`                      pose[0] = gt[0], pose[k] = odometry_step(pose[k - 1], odom[k])
+        particlePose.dat   `t i x y theta w`                  per logged row the filter's n_particles particles, then one blank line
+        landmarkEst.dat    `t i mx my sxx sxy syy w`          per logged row the n_logged Gaussians of the best particle i
+    with i the slot inside the filter.  Numbers are printed with %f as the reference prints them; precision = p prints %.pg instead
+    (17: every double comes back exactly).  tools/analysis2d_sim.py reads the directory."""
+    import os
+    hdr, gauss, part = estimates
+    if part is None:
+        raise ValueError("write_run_logs: particlePose.dat needs the particle planes (estimate_log_create(..., log_particles=True))")
+    os.makedirs(log_dir, exist_ok=True)
+    num = "%f" if precision is None else "%%.%dg" % int(precision)
+    sep = "   "
+    gt, odom = np.asarray(truth["gt"], dtype=np.float64), np.asarray(truth["odom"], dtype=np.float64)
+    lm = np.asarray(truth["landmarks"], dtype=np.float64).reshape(-1, 2)
+    fs = truth.get("first_seen")
+    fs = np.full(len(lm), -1.0) if fs is None else np.asarray(fs, dtype=np.float64)
+    dt = float(truth["dt"])
+    K = gt.shape[0]
+
+    def line(*cols):
+        return sep.join(("%d" % c) if isinstance(c, (int, np.integer)) else (num % c) for c in cols) + "\n"
+
+    with open(os.path.join(log_dir, "gtPose.dat"), "w") as fh:
+        for k in range(K):
+            fh.write(line(k * dt, gt[k, 0], gt[k, 1], gt[k, 2]))
+    with open(os.path.join(log_dir, "gtLandmark.dat"), "w") as fh:
+        for m in range(len(lm)):
+            fh.write(line(lm[m, 0], lm[m, 1], fs[m]))
+    with open(os.path.join(log_dir, "deadReckoning.dat"), "w") as fh:
+        x = gt[0].copy()
+        for k in range(K):
+            if k:
+                x = odometry_step(x, odom[k])
+            fh.write(line(k * dt, x[0], x[1], x[2]))
+    stride = part.shape[3]
+    with open(os.path.join(log_dir, "particlePose.dat"), "w") as fp, open(os.path.join(log_dir, "landmarkEst.dat"), "w") as fl:
+        for r in range(hdr.shape[0]):
+            h = hdr[r, b]
+            t = float(h["t"])
+            P = part[r, b]
+            for i in range(int(h["n_particles"])):
+                fp.write(line(t, i, P[0, i], P[1, i], P[2, i], P[3, i]))
+            fp.write("\n")
+            G = gauss[r, b]
+            i_best = int(h["best_slot"]) - b * stride
+            for m in range(int(h["n_logged"])):
+                fl.write(line(t, i_best, G[0, m], G[1, m], G[2, m], G[3, m], G[4, m], G[5, m]))
+    return log_dir
 
 
 def map_error(f, i, landmarks, w_min=0.5, cutoff=0.5):

@@ -31,6 +31,12 @@ device loop with device-made scans on a host-made ground truth (generate(measure
 the same loop on a device-made ground truth (Sim2dBatchRun(device_truth=True): set_truth + one generate_truth, the landmarks read back
 once for the sensors, and the whole run ONE rfsgpu_batch_run_truth_async).  Setup and run time of each route as with --device-sensor.
 
+--estimates [--log-particles] [--log-dir DIR] (with --device-truth; any of the three kinds): the one-call run with the device-side estimate
+log ([estimate] in include/rfsgpu.h) off, on and -- with --log-particles -- on with the particle planes, side by side (the one read of the log
+timed apart), against the per-step host route to the same data (get_weights + get_poses + get_map_estimate per filter and step).
+--log-dir leaves one directory per filter of the largest batch in the reference's log-file formats (sim2d_driver.write_run_logs):
+    python tools/analysis2d_sim.py DIR/filter_000/
+
 --fastslam: the same table for the FastSLAM half of a comparison sweep (the reference's fastslam2dSim over the same grid): a
 FastSLAMBatch (rfsgpu_batch_fastslam_cycle_async) against FastSLAM handles stepped in turn (predict_map, fastslam_update, normalise,
 resample per handle), host loop / device loop, --errors.  Every line then carries "filter": "fastslam".
@@ -416,6 +422,99 @@ def sensor_sweep(pkg, a, sizes):
     return rows
 
 
+def host_route_estimates(batch, B, thr):
+    """What a caller had to do per step for the same data before the estimate log: the weights and poses, and per filter the best
+    particle's map (rfsgpu_get_map_estimate: a metric launch and the fetch of a whole particle)."""
+    out = [batch.get_weights(), batch.get_poses()]
+    for b in range(B):
+        out.append(batch.get_map_estimate(thr, filter=b))
+    return out
+
+
+def estimates_sweep(pkg, a, sizes):
+    """--estimates (with --device-truth; any of the three kinds): per batch size the one-call run (rfsgpu_batch_run_truth_async) with
+    the estimate log off, on (rfsgpu_batch_run_log_estimates: one rfsgpu_step_estimate row per step, every Gaussian of the best
+    particle) and on with the particle planes, medians of --reps repetitions from the one invocation, the span ending with the
+    stream's synchronisation; the one read of the whole log is timed apart ("estimate_log_read_s_*");
+    and the per-step host route to the same data (get_weights + get_poses + get_map_estimate per filter and step) once.  The variant
+    with particles runs with --log-particles (or --log-dir).  --log-dir DIR:
+    the largest batch's last run with particles leaves DIR/filter_NNN/ per filter (sim2d_driver.write_run_logs, 17 digits), which
+    tools/analysis2d_sim.py analyses."""
+    sim = pkg.sim2d_driver
+    pds = [0.5, 0.6, 0.7, 0.8, 0.9, 0.95, 0.99, 0.85, 0.75, 0.65]
+    clutters = [1e-4, 5e-4, 1e-3, 2e-3, 5e-3, 1e-2, 2e-2, 5e-2, 1e-1]
+    n, stride = a.particles, 0
+    P0 = sim.C1_FASTSLAM_SIM if a.fastslam else sim.C1_SIM
+    if a.mhfastslam:
+        P0, n_xml = mh_params(sim)
+        n = a.particles or n_xml
+        stride = a.max_per_filter or min(2048, 3 * n * P0["max_hypotheses"])
+    Ps = [dict(P0, Pd=pds[b % len(pds)], clutter=clutters[(b // len(pds)) % len(clutters)]) for b in range(max(sizes))]
+    seeds = [100 + b for b in range(max(sizes))]
+    kmax = a.steps + 2
+    thr = sim.ESTIMATE_W_THRESHOLD
+
+    def make(B, estimates, particles):
+        batch = pkg.MHFastSLAMBatch(B, n, stride, gm_capacity=a.capacity) if a.mhfastslam else make_batch(pkg, a, B)
+        kw = dict(device_truth=True, kmax=kmax, track_estimates=estimates, estimate_threshold=thr, log_particles=particles)
+        if a.mhfastslam:
+            run = sim.Sim2dMHBatchRun(batch, None, Ps[:B], seeds[:B], n, **kw)
+        else:
+            run = sim.Sim2dBatchRun(batch, None, Ps[:B], seeds[:B], fastslam=a.fastslam, **kw)
+        run.step(1)                       # warm-up (kernel loads, first allocations)
+        batch.synchronize()
+        return batch, run
+
+    variants = [("off", False, False), ("on", True, False)]
+    if a.log_particles or a.log_dir:      # (particlePose.dat needs the particle planes)
+        variants.append(("on_particles", True, True))
+    rows = []
+    for B in sizes:
+        row = dict(B=B, particles=n, steps=a.steps, loop="device", route="device_truth", reps=max(1, a.reps), max_est=a.capacity,
+                   filter="mhfastslam" if a.mhfastslam else ("fastslam" if a.fastslam else "rbphd"))
+        for name, est, particles in variants:
+            figs, reads = [], []
+            for rep in range(max(1, a.reps)):
+                batch, run = make(B, est, particles)
+                t0 = time.perf_counter()
+                run.run(2, a.steps + 2)            # one call: the loop over steps is the library's
+                batch.synchronize()
+                t1 = time.perf_counter()
+                figs.append(B * a.steps / (t1 - t0))
+                if est:
+                    trace = run.estimates()        # the one read of the whole log (timed apart: it grows with max_est and slots, not with the run)
+                    reads.append(time.perf_counter() - t1)
+                    row["estimate_log_mib_" + name] = sum(x.nbytes for x in trace if x is not None) / 2 ** 20
+                    row["estimate_log_read_s_" + name] = float(np.median(reads))
+                if particles and a.log_dir and B == max(sizes) and rep == max(1, a.reps) - 1:
+                    for b in range(B):
+                        sim.write_run_logs(os.path.join(a.log_dir, "filter_%03d" % b), b, trace, dict(batch.get_truth(b), dt=Ps[b]["dt"]), precision=17)
+                    row["log_dir"] = a.log_dir
+                batch.close()
+            key = "filter_steps_per_s_estimates_" + name
+            row[key], row[key + "_reps"] = float(np.median(figs)), figs
+        # the host route: the per-step form of the same run, stopped after every step for the getters
+        batch, run = make(B, False, False)
+        if a.mhfastslam:
+            batch.serve_metrics(True)
+        t0 = time.perf_counter()
+        for k in range(2, a.steps + 2):
+            run.step(k)
+            host_route_estimates(batch, B, thr)
+        row["filter_steps_per_s_host_route"] = B * a.steps / (time.perf_counter() - t0)
+        batch.close()
+        for name, _, _ in variants[1:]:
+            row[name + "_over_off"] = row["filter_steps_per_s_estimates_" + name] / row["filter_steps_per_s_estimates_off"]
+            row[name + "_over_host_route"] = row["filter_steps_per_s_estimates_" + name] / row["filter_steps_per_s_host_route"]
+        rows.append(row)
+        print(json.dumps(row), flush=True)
+    if a.json:
+        os.makedirs(os.path.dirname(a.json) or ".", exist_ok=True)
+        with open(a.json, "w") as fh:
+            json.dump(rows, fh, indent=1)
+    return rows
+
+
 def make_batch(pkg, a, B):
     return pkg.FastSLAMBatch(B, a.particles, gm_capacity=a.capacity) if a.fastslam else pkg.FilterBatch(B, a.particles, gm_capacity=a.capacity)
 
@@ -437,12 +536,21 @@ def main():
     ap.add_argument("--reps", type=int, default=1, help="timed repetitions of every batch figure")
     ap.add_argument("--mhfastslam", action="store_true", help="multi-hypothesis FastSLAM filters: an MHFastSLAMBatch against handles on the device cycle stepped in turn")
     ap.add_argument("--results", default="", help="--errors: write one line per filter of the largest batch, 'Pd  c  posError  mapError' (the final row's pose_ed and cola)")
+    ap.add_argument("--estimates", action="store_true", help="--device-truth: the one-call run with the device-side estimate log off / on (/ on with particles), and the per-step host route to the same data")
+    ap.add_argument("--log-particles", action="store_true", help="--estimates: also time the log with the particle planes")
+    ap.add_argument("--log-dir", default="", help="--estimates: write the largest batch's run as DIR/filter_NNN/{gtPose,gtLandmark,deadReckoning,particlePose,landmarkEst}.dat (tools/analysis2d_sim.py reads them)")
     ap.add_argument("--max-per-filter", type=int, default=0, help="--mhfastslam: particle slots per filter (default nParticlesMax x hypotheses = 9 x particles, which cannot overflow; at most 2048)")
     a = ap.parse_args()
     a.all_routes = a.device_truth and a.device_sensor      # both given: host-made scans, device-made scans and device-made truth in one line
     if a.device_truth:
         a.device_loop = a.device_sensor = True
     pkg = load_pkg()
+    if a.estimates:
+        if not a.device_truth:
+            ap.error("--estimates times the one-call run: give --device-truth")
+        if not a.mhfastslam:
+            a.particles = a.particles or 200
+        return estimates_sweep(pkg, a, [int(s) for s in a.sizes.split(",")])
     if a.mhfastslam and a.device_sensor:
         return sensor_sweep(pkg, a, [int(s) for s in a.sizes.split(",")])
     if a.mhfastslam:
