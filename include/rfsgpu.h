@@ -42,7 +42,10 @@
  *   [state]    state injection and probes for tests and tools (import / export of mixtures, candidate lists, ids, masks);
  *   [bench]    snapshot / restore, kernel timing statistics, debug counters, test probes: declared only under
  *              RFSGPU_ENABLE_BENCH_API (a maintainer reading this header for the binding never meets them);
- *   [fastslam] FastSLAM / MH-FastSLAM on the same handle, the optional device-side Ackerman propagation, rfsgpu_mat_perm;
+ *   [fastslam] FastSLAM / MH-FastSLAM on the same handle, the optional device-side Ackerman propagation, rfsgpu_mat_perm; the whole
+ *              FastSLAM::update enqueued without a host stop (rfsgpu_fastslam_cycle_async: 2-D model, no candidate lists;
+ *              rfsgpu_fastslam_cycle_full_async: either model, candidate lists, the scan with the call), behind which the
+ *              propagation and static-step calls enqueue without taking the particle count over;
  *   [batch]    many independent 2-D filters in one handle, stepped together in one launch chain;
  *   [metric]   per-step OSPA / COLA map error and pose error computed on the device, kept in a device-side log;
  *   [resample] ParticleFilter::resample for an ordinary handle of any size on the device, without a host stop;
@@ -668,6 +671,39 @@ int rfsgpu_particle_parents(rfsgpu_filter *f, int *parent, int max_n);
  * RFSGPU_FASTSLAM_CYCLE_MAX_PARTICLES (the resampling kernel holds the whole filter in LDS). */
 #define RFSGPU_FASTSLAM_CYCLE_MAX_PARTICLES 2048
 int rfsgpu_fastslam_cycle_async(rfsgpu_filter *f, int predict, const double *z, int n_z, double u01, int n_init);
+/* The same cycle for either model and with landmark candidate lists: the rules above (the counters and the overflow word on the
+ * device, cycles enqueued back to back, rfsgpu_fastslam_last_cycle for the results), and in addition
+ *  - RFSGPU_MODEL_VICTORIAPARK_3D is served, z is then [n_z][3];
+ *  - any landmarkCandidateMeasurementCountThreshold is served: the candidate lists are walked by the new-landmark step, travel with
+ *    the copies of a multiplied particle exactly when the previous cycle resampled (FastSLAM.hpp:551-553), and with every
+ *    resampling copy.  A 65th candidate of a particle, or a map beyond gm_capacity, is reported by the next synchronising call
+ *    (RFSGPU_ERR_UNSUPPORTED / RFSGPU_ERR_CAPACITY), as rfsgpu_fastslam_update reports them;
+ *  - scan [n_scan] is the laser scan of this update (setLaserScan), or NULL to leave the scan as it is.  It goes through the pinned
+ *    staging ring of rfsgpu_set_step_inputs_async without a wait for the device; the clutter density is computed from it on the
+ *    host, as rfsgpu_set_laser_scan computes it, and travels by value with the launches.  The Victoria Park model with no scan ever
+ *    set: RFSGPU_ERR_INVALID;
+ *  - maxNDataAssocHypotheses == 1 associates as rfsgpu_fastslam_update does for one hypothesis (the sparse table and the
+ *    per-component assignment of the single-hypothesis path, no limit of 64 landmarks in range), so the two routes give the same
+ *    bits for every configuration; rfsgpu_fastslam_cycle_async runs the multi-hypothesis pipeline with a limit of one.
+ * RFSGPU_ERR_UNSUPPORTED, state untouched: batch handles, shards of a group, maxNDataAssocHypotheses outside [1, 16],
+ * rfsgpu_max_particles(f) > RFSGPU_FASTSLAM_CYCLE_MAX_PARTICLES.
+ *
+ * While cycles of either call are pending, rfsgpu_propagate_ackerman_async, rfsgpu_propagate_ackerman_run_async,
+ * rfsgpu_static_steps_async and rfsgpu_set_step_inputs_async with x == NULL enqueue behind them without taking the count over:
+ * their kernels are launched at max_particles and read the count and the overflow word on the device (a propagation behind an
+ * abandoned cycle is abandoned with it).  The generator's counter stays (slot, call).  rfsgpu_set_step_inputs_async with poses
+ * still waits: it sizes a host buffer by the count. */
+int rfsgpu_fastslam_cycle_full_async(rfsgpu_filter *f, int predict, const double *z, int n_z, const double *scan, int n_scan, double u01,
+                                     int n_init);
+/* How many cycles with measurements have completed on this handle and how many of them resampled (synchronises): for a host that
+ * enqueues a whole run and reads nothing in between.  Abandoned cycles are not counted.  Either pointer may be NULL. */
+int rfsgpu_fastslam_cycle_counts(rfsgpu_filter *f, int *n_cycles, int *n_resamplings);
+#ifdef RFSGPU_ENABLE_BENCH_API   /* [test]: 1 while the particle count is the device's (cycles are pending); reads nothing, waits for nothing */
+int rfsgpu_fastslam_cycle_pending(rfsgpu_filter *f);
+/* [test]: one slot's weight, mixture size, candidate count and first Gaussian (entry 0 of every plane: gauss [7], or [11] for the
+ * Victoria Park model), read (write == 0) or written for any slot below rfsgpu_max_particles(f), live or not.  Synchronises. */
+int rfsgpu_debug_slot(rfsgpu_filter *f, int slot, int write, double *weight, int *count, int *cand_count, double *gauss);
+#endif /* RFSGPU_ENABLE_BENCH_API */
 /* What the last rfsgpu_fastslam_cycle_async did (synchronises): the count after its update, the count after its resampling, whether
  * that fired, N_eff (0 where the test did not run), parent[k] of the update for the *n_after_update grown slots (what
  * rfsgpu_particle_parents gives after rfsgpu_fastslam_update), plan[k] for the *n_after_resample slots (the slot -- of the grown set

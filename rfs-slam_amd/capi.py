@@ -152,6 +152,7 @@ ABI_SYMBOLS = [
     "default_fastslam_config", "set_fastslam_config", "get_fastslam_config", "fastslam_update",
     "normalize_weights_parts", "create_ex", "n_particles", "max_particles", "resample_apply_n",
     "fastslam_set_resample_occured", "particle_parents", "vp_probe_pd", "fastslam_cycle_async", "fastslam_last_cycle", "fastslam_set_resampling",
+    "fastslam_cycle_full_async", "fastslam_cycle_pending", "fastslam_cycle_counts", "debug_slot",
     "slab_row_bytes", "export_slab_rows", "import_slab_rows", "weights_device_ptr", "step_async", "set_step_inputs_async", "predict_map_async", "set_phase_timing", "static_steps_async", "propagate_ackerman_async", "propagate_ackerman_run_async", "set_partition_mode", "get_partition_mode",
     "set_birth_inheritance", "get_birth_inheritance", "get_particle_ids", "set_particle_ids", "resample_occured", "get_unused_masks", "set_unused_masks", "has_birth_candidates", "predict_map_level", "murty_partition_sums", "partition_likelihoods", "cycle_async", "update_io", "step_async_deferred", "step_async_trailing", "collective_gate", "collective_publish", "collective_probe",
     "group_create", "group_destroy", "group_last_error", "group_n_shards", "group_n_particles", "group_shard", "group_locate",
@@ -318,6 +319,40 @@ class CFilter:
         handle's stream; nothing is read back.  The particle count is the device's until the next call that synchronises."""
         Z = _f64(Z).reshape(-1, self.dz)
         self._call("fastslam_cycle_async", C.c_int(1 if predict else 0), self._ptr(Z), C.c_int(Z.shape[0]), C.c_double(float(u01)), C.c_int(int(n_init)))
+
+    def fastslam_cycle_full_async(self, Z, u01, n_init, predict=False, scan=None):
+        """fastslam_cycle_async for either model and any landmark candidate threshold (rfsgpu_fastslam_cycle_full_async); scan: the
+        laser scan of this update (Victoria Park model), None leaves it as it is."""
+        Z = _f64(Z).reshape(-1, self.dz)
+        sp, ns = None, 0
+        if scan is not None:
+            scan = _f64(scan).reshape(-1)
+            sp, ns = self._ptr(scan), scan.size
+        self._call("fastslam_cycle_full_async", C.c_int(1 if predict else 0), self._ptr(Z), C.c_int(Z.shape[0]), sp, C.c_int(ns),
+                   C.c_double(float(u01)), C.c_int(int(n_init)))
+
+    def fastslam_cycle_counts(self):
+        """(cycles with measurements completed, resamplings among them) of the device-cycle route; synchronises."""
+        a, b = C.c_int(), C.c_int()
+        self._call("fastslam_cycle_counts", C.byref(a), C.byref(b))
+        return a.value, b.value
+
+    def debug_slot(self, slot, values=None):
+        """[test] (weight, count, cand_count, first Gaussian [planes]) of any slot below max_particles; values: write them instead."""
+        npl = 7 if self.dm == 2 else 11
+        w, c, k = C.c_double(), C.c_int(), C.c_int()
+        g = np.zeros(npl)
+        if values is not None:
+            w.value, c.value, k.value = float(values[0]), int(values[1]), int(values[2])
+            g[:] = values[3]
+        self._call("debug_slot", C.c_int(int(slot)), C.c_int(0 if values is None else 1), C.byref(w), C.byref(c), C.byref(k), self._ptr(g))
+        return w.value, c.value, k.value, g
+
+    def fastslam_cycle_pending(self):
+        """Whether the particle count is still the device's (cycles are pending); waits for nothing."""
+        fn = self._fn("fastslam_cycle_pending")
+        fn.restype = C.c_int
+        return bool(fn(self._h))
 
     def fastslam_last_cycle(self):
         """What the last fastslam_cycle_async did (synchronises): dict of n_after_update, n_after_resample, fired, n_eff, parent

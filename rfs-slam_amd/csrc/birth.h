@@ -480,3 +480,22 @@ __global__ __launch_bounds__(WPB * 64) void static_steps_kernel(Buffers B, int c
     }
   }
 }
+// ... behind a pending device cycle (fastslam_cycle.h): launched at the handle's capacity, the count is read on the device.
+template <int D, int WPB>
+__global__ __launch_bounds__(WPB * 64) void static_steps_live_kernel(Buffers B, int cur, StaticRun R, int nCap, LiveCount live) {
+  const int wave = threadIdx.x >> 6;
+  const int lane = threadIdx.x & 63;
+  const int i = __builtin_amdgcn_readfirstlane(blockIdx.x * WPB + wave);
+  if (i >= nCap || live_beyond(live, i)) return;
+  const int cap = B.cap, n = B.count[i];
+  double *slab = B.slab[cur];
+  constexpr int NC = (D == 2) ? 3 : 6;
+  for (int t = 0; t < NC; t++) {
+    double *p = (D == 2) ? plane(slab, cap, i, PL_SXX + t) : plane3(slab, cap, i, P3_SXX + t);
+    for (int m = lane; m < n; m += 64) {
+      double a = p[m];
+      for (int r = 0; r < R.n; r++) a += R.q[r][t];
+      p[m] = a;
+    }
+  }
+}

@@ -545,6 +545,16 @@ __global__ __launch_bounds__(WPB * 64) void fs_associate_update_kernel(Buffers B
   __shared__ __align__(16) unsigned char sPdScratch[WPB][(D == 3) ? ((VP_PD_SCRATCH_BYTES + 15) & ~15) : 16];
   fs_associate_update_body<WPB, D, false>(B, P, F, cur, nZ, arena, smem_raw, sPdScratch[threadIdx.x >> 6], FsBatchArg{});
 }
+// The form of a handle whose particle count is on the device (rfsgpu_fastslam_cycle_full_async with one hypothesis): launched at the
+// handle's capacity, one wavefront per workgroup, so that a workgroup beyond the live count leaves as a whole before it touches
+// memory.  The host passes B.N = max_particles: the body's own bound never cuts a live slot.
+template <int D>
+__global__ __launch_bounds__(64) void fs_associate_update_live_kernel(Buffers B, Params P, FsParams F, int cur, int nZ, unsigned char *arena, LiveCount live) {
+  extern __shared__ __align__(16) unsigned char smem_raw[];
+  __shared__ __align__(16) unsigned char sPdScratch[(D == 3) ? ((VP_PD_SCRATCH_BYTES + 15) & ~15) : 16];
+  if (live_beyond(live, (int)blockIdx.x)) return;     // (workgroup-uniform)
+  fs_associate_update_body<1, D, false>(B, P, F, cur, nZ, arena, smem_raw, sPdScratch, FsBatchArg{});
+}
 // The batch's form (2-D only): launched over all slots of the batch, LDS fs_batch_lds_bytes(cap, WPB).
 template <int WPB>
 __global__ __launch_bounds__(WPB * 64) void fs_associate_update_batch_kernel(Buffers B, int cur, unsigned char *arena, FsBatchArg A) {

@@ -22,6 +22,7 @@ enum FsCycleWord {
   FSC_NGROWN,       // the count after the last update, before its resampling
   FSC_FIRED,        // whether the last cycle resampled
   FSC_DONE,         // cycles with measurements completed so far (the host undoes the slab flips of abandoned ones)
+  FSC_NFIRED,       // ... and how many of them resampled (a host that reads nothing between cycles still learns the number)
   FSC_WORDS = 16
 };
 // One allocation, which a stream-ordered copy takes whole into pinned memory when the host next synchronises: that is how the
@@ -44,10 +45,7 @@ __host__ __device__ inline void fs_cycle_carve(unsigned char *base, int Ncap, Fs
   S.pid = S.plan + Ncap;
   S.ppid = S.pid + Ncap;
 }
-// the copy kernel's LiveCount: its count is the number of copies, and the candidate lists travel when the previous cycle resampled
-struct LiveCopy : LiveCount {
-  const int *copyCand;
-};
+// (LiveCopy, the copy kernel's LiveCount: fastslam_mh.h)
 
 #define FS_CYCLE_THREADS 256
 #define FS_CYCLE_MAX_PARTICLES BATCH_LOOP_MAX_PER_FILTER     // == RFSGPU_FASTSLAM_CYCLE_MAX_PARTICLES (rfsgpu.h)
@@ -82,6 +80,28 @@ __global__ __launch_bounds__(256) void fs_cycle_static_step_kernel(Buffers B, Pa
   const int i = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + wave);
   if (live_beyond(live, i)) return;
   predict_map_particle<64>(B, P, cur, i, lane, false, 0, B.pose, true);
+}
+
+// ... for the Victoria Park model's 3-D landmarks (rfsgpu_fastslam_cycle_full_async): predict_map_general_kernel<3>'s static step
+__global__ __launch_bounds__(256) void fs_cycle_static_step3_kernel(Buffers B, Params P, int cur, LiveCount live) {
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int i = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + wave);
+  if (live_beyond(live, i)) return;
+  const int cap = B.cap, n = B.count[i];
+  double *slab = B.slab[cur];
+  for (int t = 0; t < 6; t++) {
+    double *p = plane3(slab, cap, i, P3_SXX + t);
+    for (int m = lane; m < n; m += 64) p[m] += P.Qlm6[t];
+  }
+}
+
+// The plan of an update with one hypothesis (rfsgpu_fastslam_cycle_full_async, maxNDataAssocHypotheses == 1: the single-hypothesis
+// association of fastslam.h makes no copies): every slot is its own parent and the count stays.
+__global__ __launch_bounds__(FS_CYCLE_THREADS) void fs_cycle_identity_plan_kernel(FsCycleState S, int Ncap) {
+  if (S.w[FSC_OVF] != 0) return;
+  const int n = min(S.w[FSC_N], Ncap);
+  for (int j = threadIdx.x; j < n; j += FS_CYCLE_THREADS) S.slotSrc[j] = j;
+  if (threadIdx.x == 0) { S.w[FSC_NCOPY] = 0; S.w[FSC_NGROWN] = n; }
 }
 
 // The head of a cycle.  nHost / flagHost: the particle count and resampleOccured_ where the host still knows them (no cycle is
@@ -196,6 +216,7 @@ __device__ __forceinline__ void fs_resample_shrink_body(double *weight, const Fs
     S.w[FSC_RENORM_N] = renorm ? n : 0;
     S.w[FSC_N] = nOut;
     S.w[FSC_DONE] += 1;
+    S.w[FSC_NFIRED] += fire;
     sFire = fire; sOut = nOut;
   }
   __syncthreads();

@@ -267,6 +267,14 @@ void fs_mh_associate_kernel(Buffers B, Params Parg, FsParams Farg, int cur, int 
   }
 }
 
+// The copy kernel's LiveCount (the device cycle, fastslam_cycle.h): its count is the number of copies, and the candidate lists travel
+// when the word copyCand points at -- FastSLAM::resampleOccured_ as the previous cycle left it -- is set (:551-553).
+struct LiveCopy : LiveCount {
+  const int *copyCand;
+};
+template <typename... T> struct is_live_copy { static constexpr bool value = false; };
+template <> struct is_live_copy<LiveCopy> { static constexpr bool value = true; };
+
 // One workgroup per NEW slot: ParticleFilter::copyParticle (ParticleFilter.hpp:273-294) of slot src -> slot dst.
 // live: its count is the number of copies.
 template <typename... TLive>
@@ -274,6 +282,7 @@ __global__ __launch_bounds__(256) void fs_mh_copy_kernel(Buffers B, int cur, con
   if constexpr (sizeof...(TLive) == 1) {
     if (live_beyond(pack_first(live...), (int)blockIdx.x)) return;
   }
+  if constexpr (is_live_copy<TLive...>::value) copyCand = __builtin_amdgcn_readfirstlane(*pack_first(live...).copyCand) != 0;
   int d = dstSlot[blockIdx.x], s = srcSlot[blockIdx.x];
   if constexpr (is_mh_batch<TLive...>::value) {    // the lists are per filter, in slots of the filter's own block
     const int nPer = pack_first(live...).nPer, base = ((int)blockIdx.x / nPer) * nPer;

@@ -82,3 +82,24 @@ __global__ __launch_bounds__(256) void propagate_ackerman_run_kernel(double *pos
     ackerman_step_particle(pose, i, A);
   }
 }
+
+// The same two behind a pending device cycle (fastslam_cycle.h), whose particle count the host does not know yet: launched at the
+// handle's capacity with a LiveCount (common.h); nCap bounds the launch's last workgroup.  The generator's counter stays
+// (slot, call): a particle copy draws by the slot it lives in, as it does on the host-count route after the count has come back.
+__global__ __launch_bounds__(256) void propagate_ackerman_live_kernel(double *pose, int nCap, AckermanStep A, LiveCount live) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= nCap || live_beyond(live, i)) return;
+  ackerman_step_particle(pose, i, A);
+}
+
+__global__ __launch_bounds__(256) void propagate_ackerman_run_live_kernel(double *pose, int nCap, AckermanRun R, LiveCount live) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= nCap || live_beyond(live, i)) return;
+  for (int k = 0; k < R.n; k++) {
+    AckermanStep A;
+    A.uv = R.uv[k]; A.ur = R.ur[k]; A.sv = R.sv[k]; A.sr = R.sr[k]; A.dt = R.dt[k];
+    A.h = R.h; A.l = R.l; A.dx = R.dx; A.dy = R.dy;
+    A.seed = R.seed; A.call = R.call0 + (unsigned long long)k;
+    ackerman_step_particle(pose, i, A);
+  }
+}

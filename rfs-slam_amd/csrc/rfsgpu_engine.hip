@@ -143,6 +143,7 @@ struct rfsgpu_filter {
   int mhcStashedRc = 0;               // a pending cycle's error met by a call that cannot return it: returned by the next call that can
   std::vector<char> mhcFlips;         // per pending cycle with measurements: whether it flipped `cur` (its prune ran)
   int mhcDone = 0;                    // FSC_DONE as last read
+  int mhcNFired = 0;                  // FSC_NFIRED as last read
   double fsEffN = -1.0, fsEffNPercent = -1.0;   // rfsgpu_fastslam_set_resampling (negative: n_particles / 4 and 1 / 4 at the first cycle)
   int mhcNGrown = 0, mhcNAfter = 0, mhcFired = 0;   // the last cycle, as resolved
   double mhcNEff = 0.0;
@@ -320,6 +321,13 @@ static int mhc_resolve(rfsgpu_filter *f);
 // pushes its configuration before every cycle does not wait for the cycles in flight
 #define CHECK_HANDLE_HOST(f) \
   if (!(f)) return RFSGPU_ERR_INVALID;
+// ... and the motion and static-step calls start here: behind pending device cycles of a FastSLAM handle (and nothing else pending)
+// they do not take the count over -- `behind` comes back true and the call launches its LiveCount form at the handle's capacity,
+// which reads the count and the overflow word of the cycle block on the device.  Otherwise as CHECK_HANDLE_ENQ.
+#define CHECK_HANDLE_BEHIND_CYCLE(f, behind)                                  \
+  if (!(f)) return RFSGPU_ERR_INVALID;                                        \
+  const bool behind = (f)->mhcPending && !(f)->mhcStashedRc && !(f)->mhbPending && !(f)->rsPending; \
+  if (!behind) { CHECK_HANDLE_ENQ(f); }
 
 static int fail(rfsgpu_filter *f, int code, const char *msg) {
   f->err = msg;
@@ -342,6 +350,7 @@ static int ring_acquire(rfsgpu_filter *f, PinnedRing &R, T **h, int *k_out) {
   *k_out = k;
   return RFSGPU_OK;
 }
+static int push_scan(rfsgpu_filter *f, double *hs, const double *scan, int n_scan);
 // The pose covariance that goes with a push of poses, through hc (pinned, inside the block the caller holds): one shared [9]
 // (cov_stride 0), one per particle [N][9] (cov_stride 9) or none -- then B.poseCov[0 .. 9) gets zeros, once (poseCovZero).  inPacked:
 // the per-particle covariances ride in the step kernel's packed block (its pull form) and no copy command is issued.  The stride is
@@ -2009,7 +2018,7 @@ int rfsgpu_predict_map_async(rfsgpu_filter *f, int add_birth) {
 // rfsgpu_set_lmk_process_noise(Q_k) + rfsgpu_predict_map_async(f, 0).  noises: [n][D*D] row-major, or NULL = the noise that is set
 // now, n times.  Stream-ordered.
 int rfsgpu_static_steps_async(rfsgpu_filter *f, int n, const double *noises) {
-  CHECK_HANDLE_ENQ(f);
+  CHECK_HANDLE_BEHIND_CYCLE(f, behind);
   if (n < 0) return fail(f, RFSGPU_ERR_INVALID, "static_steps: negative count");
   hipSetDevice(f->device);
   const int D = f->D;
@@ -2021,7 +2030,12 @@ int rfsgpu_static_steps_async(rfsgpu_filter *f, int n, const double *noises) {
       if (D == 2) { R.q[r][0] = Q[0]; R.q[r][1] = Q[1]; R.q[r][2] = Q[3]; R.q[r][3] = R.q[r][4] = R.q[r][5] = 0.0; }
       else { R.q[r][0] = Q[0]; R.q[r][1] = Q[1]; R.q[r][2] = Q[2]; R.q[r][3] = Q[4]; R.q[r][4] = Q[5]; R.q[r][5] = Q[8]; }
     }
-    if (D == 3) static_steps_kernel<3, 4><<<(f->N + 3) / 4, 256, 0, f->stream>>>(f->B, f->cur, R);
+    if (behind) {
+      const LiveCount live{f->mhc.w + FSC_N, f->mhc.w + FSC_OVF};
+      if (D == 3) static_steps_live_kernel<3, 4><<<(f->Ncap + 3) / 4, 256, 0, f->stream>>>(f->B, f->cur, R, f->Ncap, live);
+      else static_steps_live_kernel<2, 4><<<(f->Ncap + 3) / 4, 256, 0, f->stream>>>(f->B, f->cur, R, f->Ncap, live);
+    }
+    else if (D == 3) static_steps_kernel<3, 4><<<(f->N + 3) / 4, 256, 0, f->stream>>>(f->B, f->cur, R);
     else static_steps_kernel<2, 4><<<(f->N + 3) / 4, 256, 0, f->stream>>>(f->B, f->cur, R);
     HIPCHK(hipGetLastError());
   }
@@ -2032,7 +2046,7 @@ int rfsgpu_static_steps_async(rfsgpu_filter *f, int n, const double *noises) {
 // steering}, var = their noise variances (null or zeros: noise-free), geom = {h, l, dx, dy}; (seed, call) key the generator.
 int rfsgpu_propagate_ackerman_async(rfsgpu_filter *f, const double *u, const double *var, double dt, const double *geom, unsigned long long seed,
                                     unsigned long long call) {
-  CHECK_HANDLE_ENQ(f);
+  CHECK_HANDLE_BEHIND_CYCLE(f, behind);
   if (!u || !geom || !(dt == dt)) return fail(f, RFSGPU_ERR_INVALID, "propagate_ackerman: bad arguments");
   if (var && (var[0] < 0 || var[1] < 0)) return fail(f, RFSGPU_ERR_INVALID, "propagate_ackerman: negative variance");
   hipSetDevice(f->device);
@@ -2042,7 +2056,8 @@ int rfsgpu_propagate_ackerman_async(rfsgpu_filter *f, const double *u, const dou
   A.dt = dt;
   A.h = geom[0]; A.l = geom[1]; A.dx = geom[2]; A.dy = geom[3];
   A.seed = seed; A.call = call;
-  propagate_ackerman_kernel<<<(f->N + 255) / 256, 256, 0, f->stream>>>(f->B.pose, f->N, A);
+  if (behind) propagate_ackerman_live_kernel<<<(f->Ncap + 255) / 256, 256, 0, f->stream>>>(f->B.pose, f->Ncap, A, LiveCount{f->mhc.w + FSC_N, f->mhc.w + FSC_OVF});
+  else propagate_ackerman_kernel<<<(f->N + 255) / 256, 256, 0, f->stream>>>(f->B.pose, f->N, A);
   HIPCHK(hipGetLastError());
   return RFSGPU_OK;
 }
@@ -2051,7 +2066,7 @@ int rfsgpu_propagate_ackerman_async(rfsgpu_filter *f, const double *u, const dou
 // numbered call0, call0 + 1, ...  Same poses, bit for bit, as n calls of rfsgpu_propagate_ackerman_async.
 int rfsgpu_propagate_ackerman_run_async(rfsgpu_filter *f, int n, const double *u, const double *var, const double *dt, const double *geom,
                                         unsigned long long seed, unsigned long long call0) {
-  CHECK_HANDLE_ENQ(f);
+  CHECK_HANDLE_BEHIND_CYCLE(f, behind);
   if (n < 0 || (n > 0 && (!u || !dt || !geom))) return fail(f, RFSGPU_ERR_INVALID, "propagate_ackerman_run: bad arguments");
   for (int k = 0; k < n; k++)
     if (!(dt[k] == dt[k]) || (var && (var[2 * k] < 0 || var[2 * k + 1] < 0))) return fail(f, RFSGPU_ERR_INVALID, "propagate_ackerman_run: bad interval / negative variance");
@@ -2067,7 +2082,8 @@ int rfsgpu_propagate_ackerman_run_async(rfsgpu_filter *f, int n, const double *u
     }
     R.h = geom[0]; R.l = geom[1]; R.dx = geom[2]; R.dy = geom[3];
     R.seed = seed; R.call0 = call0 + (unsigned long long)k0;
-    propagate_ackerman_run_kernel<<<(f->N + 255) / 256, 256, 0, f->stream>>>(f->B.pose, f->N, R);
+    if (behind) propagate_ackerman_run_live_kernel<<<(f->Ncap + 255) / 256, 256, 0, f->stream>>>(f->B.pose, f->Ncap, R, LiveCount{f->mhc.w + FSC_N, f->mhc.w + FSC_OVF});
+    else propagate_ackerman_run_kernel<<<(f->N + 255) / 256, 256, 0, f->stream>>>(f->B.pose, f->N, R);
     HIPCHK(hipGetLastError());
   }
   return RFSGPU_OK;
@@ -2078,7 +2094,8 @@ int rfsgpu_propagate_ackerman_run_async(rfsgpu_filter *f, int n, const double *u
 // buffers are copied into a pinned staging ring before the call returns; the host never waits for the device (except when all
 // four ring slots are still in flight).  x may be null (poses unchanged), scan may be null (scan unchanged / 2-D model).
 int rfsgpu_set_step_inputs_async(rfsgpu_filter *f, const double *x, const double *cov, int cov_stride, const double *scan, int n_scan) {
-  CHECK_HANDLE_ENQ(f);
+  if (x) { CHECK_HANDLE_ENQ(f); }      // (poses size a host buffer by N)
+  else { CHECK_HANDLE_BEHIND_CYCLE(f, behind); (void)behind; }   // a scan alone goes behind pending cycles: nothing below reads N
   if (cov && cov_stride != 0 && cov_stride != 9) return fail(f, RFSGPU_ERR_INVALID, "set_step_inputs: cov_stride must be 0 or 9");
   if (scan && (f->model != RFSGPU_MODEL_VICTORIAPARK_3D || n_scan < 2 || n_scan > RFSGPU_VP_MAX_SCAN)) return fail(f, RFSGPU_ERR_INVALID, "set_step_inputs: laser scan needs the Victoria Park model and 2..RFSGPU_VP_MAX_SCAN beams");
   if (!x && !scan) return RFSGPU_OK;
@@ -2091,19 +2108,22 @@ int rfsgpu_set_step_inputs_async(rfsgpu_filter *f, const double *x, const double
     { const int rc = push_poses(f, h, f->B.pose, x, cov, cov_stride); if (rc != RFSGPU_OK) return rc; }
     f->P.poseCovStride = cov ? cov_stride : 0;
   }
-  if (scan) {
-    double area = 0;
-    for (int q = 1; q < n_scan; q++) area += scan[q] * scan[q - 1];
-    area += scan[0] * scan[n_scan - 1];
-    area *= sin(acos(-1) / 360) / 2;
-    f->vpClutter = f->vp.expectedClutterNumber / area;
-    double *hs = h + (size_t)f->Ncap * 22;
-    memcpy(hs, scan, (size_t)n_scan * sizeof(double));
-    HIPCHK(hipMemcpyAsync(f->B.scan, hs, (size_t)n_scan * sizeof(double), hipMemcpyHostToDevice, f->stream));
-    f->B.nScan = n_scan;
-    rebuild_params(f);
-  }
+  if (scan) { const int rc = push_scan(f, h + (size_t)f->Ncap * 22, scan, n_scan); if (rc != RFSGPU_OK) return rc; }
   HIPCHK(hipEventRecord(f->stage.ev[k], f->stream));
+  return RFSGPU_OK;
+}
+// setLaserScan through hs, the scan's place in a block of the pinned ring: the FoV area and the clutter density on the host, the raw
+// scan to the device by a stream-ordered copy
+static int push_scan(rfsgpu_filter *f, double *hs, const double *scan, int n_scan) {
+  double area = 0;
+  for (int q = 1; q < n_scan; q++) area += scan[q] * scan[q - 1];
+  area += scan[0] * scan[n_scan - 1];
+  area *= sin(acos(-1) / 360) / 2;
+  f->vpClutter = f->vp.expectedClutterNumber / area;
+  memcpy(hs, scan, (size_t)n_scan * sizeof(double));
+  HIPCHK(hipMemcpyAsync(f->B.scan, hs, (size_t)n_scan * sizeof(double), hipMemcpyHostToDevice, f->stream));
+  f->B.nScan = n_scan;
+  rebuild_params(f);
   return RFSGPU_OK;
 }
 
@@ -2723,6 +2743,7 @@ static int mhc_resolve(rfsgpu_filter *f) {
   fs_cycle_carve(f->hMhcBlock, f->Ncap, H);
   const int done = H.w[FSC_DONE] - f->mhcDone;      // of the pending cycles with measurements, the first `done` ran
   f->mhcDone = H.w[FSC_DONE];
+  f->mhcNFired = H.w[FSC_NFIRED];
   for (size_t k = (size_t)std::max(done, 0); k < f->mhcFlips.size(); k++) f->cur ^= f->mhcFlips[k] ? 1 : 0;
   const bool lastRan = f->mhcFlips.empty() || done >= (int)f->mhcFlips.size();
   f->mhcFlips.clear();
@@ -2870,6 +2891,9 @@ int rfsgpu_fastslam_set_resampling(rfsgpu_filter *f, double eff_n, double eff_n_
   f->fsEffNPercent = eff_n_percent;
   return RFSGPU_OK;
 }
+// One cycle enqueued.  full: rfsgpu_fastslam_cycle_full_async -- either model, any candidate threshold, the scan of this update, and
+// one hypothesis associated as rfsgpu_fastslam_update associates it; without it the launches are rfsgpu_fastslam_cycle_async's.
+static int fastslam_cycle_enqueue(rfsgpu_filter *f, int predict, const double *z, int n_z, const double *scan, int n_scan, double u01, int n_init, bool full);
 int rfsgpu_fastslam_cycle_async(rfsgpu_filter *f, int predict, const double *z, int n_z, double u01, int n_init) {
   if (!f) return RFSGPU_ERR_INVALID;
   if (f->mhcStashedRc || f->rsPending) { const int rc = mhc_resolve(f); if (rc != RFSGPU_OK) return rc; }
@@ -2878,6 +2902,16 @@ int rfsgpu_fastslam_cycle_async(rfsgpu_filter *f, int predict, const double *z, 
   if (f->D != 2) return fail(f, RFSGPU_ERR_UNSUPPORTED, "fastslam_cycle: the Victoria Park model is not served (the 2-D range-bearing model only)");
   if (f->fs.landmarkCandidateMeasurementCountThreshold != 1u)
     return fail(f, RFSGPU_ERR_UNSUPPORTED, "fastslam_cycle: landmarkCandidateMeasurementCountThreshold must be 1 (landmark candidate lists are not served on this route)");
+  return fastslam_cycle_enqueue(f, predict, z, n_z, nullptr, 0, u01, n_init, false);
+}
+int rfsgpu_fastslam_cycle_full_async(rfsgpu_filter *f, int predict, const double *z, int n_z, const double *scan, int n_scan, double u01, int n_init) {
+  if (!f) return RFSGPU_ERR_INVALID;
+  if (f->mhcStashedRc || f->rsPending) { const int rc = mhc_resolve(f); if (rc != RFSGPU_OK) return rc; }
+  REFUSE_ON_BATCH(f, "rfsgpu_fastslam_cycle_full_async");
+  if (f->groupShard) return fail(f, RFSGPU_ERR_UNSUPPORTED, "fastslam_cycle: not available on a shard of an rfsgpu_group (the particle count would be known to one device only)");
+  return fastslam_cycle_enqueue(f, predict, z, n_z, scan, n_scan, u01, n_init, true);
+}
+static int fastslam_cycle_enqueue(rfsgpu_filter *f, int predict, const double *z, int n_z, const double *scan, int n_scan, double u01, int n_init, bool full) {
   if (f->fs.maxNDataAssocHypotheses < 1 || f->fs.maxNDataAssocHypotheses > FSMH_MAX_HYP)
     return fail(f, RFSGPU_ERR_UNSUPPORTED, "fastslam_cycle: maxNDataAssocHypotheses must be in [1, 16]");
   if (f->Ncap > RFSGPU_FASTSLAM_CYCLE_MAX_PARTICLES)
@@ -2886,10 +2920,15 @@ int rfsgpu_fastslam_cycle_async(rfsgpu_filter *f, int predict, const double *z, 
   if (n_z > 0 && !z) return fail(f, RFSGPU_ERR_INVALID, "null measurement buffer");
   if (!(u01 >= 0.0 && u01 < 1.0)) return fail(f, RFSGPU_ERR_INVALID, "fastslam_cycle: u01 must lie in [0, 1)");
   if (n_init < 0) return fail(f, RFSGPU_ERR_INVALID, "fastslam_cycle: negative n_init");
+  if (scan && (f->model != RFSGPU_MODEL_VICTORIAPARK_3D || n_scan < 2 || n_scan > RFSGPU_VP_MAX_SCAN))
+    return fail(f, RFSGPU_ERR_INVALID, "fastslam_cycle: a laser scan needs the Victoria Park model and 2..RFSGPU_VP_MAX_SCAN beams");
+  if (f->D == 3 && !scan && f->B.nScan < 2) return fail(f, RFSGPU_ERR_INVALID, "Victoria Park model: no laser scan has been set (pass one, or rfsgpu_set_laser_scan first)");
   hipSetDevice(f->device);
-  const int Ncap = f->Ncap;
+  const int Ncap = f->Ncap, D = f->D;
+  const bool single = full && f->fs.maxNDataAssocHypotheses == 1;     // (the association of rfsgpu_fastslam_update's single-hypothesis branch)
   const FsMhLayout L = fs_mh_layout();
-  if (!f->mhArena) HIPCHK(hipMalloc(&f->mhArena, (size_t)Ncap * L.total));
+  if (single) { if (!f->fsArena) HIPCHK(hipMalloc(&f->fsArena, (size_t)Ncap * fs_arena_bytes())); }
+  else if (!f->mhArena) HIPCHK(hipMalloc(&f->mhArena, (size_t)Ncap * L.total));
   if (!f->mhcInts) HIPCHK(hipMalloc(&f->mhcInts, (size_t)4 * Ncap * sizeof(int)));
   if (!f->hMhcBlock) HIPCHK(hipHostMalloc(&f->hMhcBlock, fs_cycle_state_bytes(Ncap)));
   if (!f->mhcBlock) {
@@ -2909,9 +2948,17 @@ int rfsgpu_fastslam_cycle_async(rfsgpu_filter *f, int predict, const double *z, 
   f->holes = false;
   f->fastSlamHandle = true;
   f->mhcHave = true;
+  if (scan) {     // through the pinned ring, as rfsgpu_set_step_inputs_async: no wait for the device; the clutter density goes by value in Params
+    double *h = nullptr;
+    int k = 0;
+    { const int rc = ring_acquire(f, f->stage, &h, &k); if (rc != RFSGPU_OK) return rc; }
+    { const int rc = push_scan(f, h + (size_t)Ncap * 22, scan, n_scan); if (rc != RFSGPU_OK) return rc; }
+    HIPCHK(hipEventRecord(f->stage.ev[k], f->stream));
+  }
   const LiveCount live{S.w + FSC_N, S.w + FSC_OVF};
   fs_cycle_begin_kernel<<<1, 64, 0, f->stream>>>(S, f->mhcPending ? -1 : f->N, f->mhcPending ? -1 : (f->fsResampleOccured ? 1 : 0), n_z == 0 ? 1 : 0);
-  if (predict) fs_cycle_static_step_kernel<<<(Ncap + 3) / 4, 256, 0, f->stream>>>(f->B, f->P, f->cur, live);
+  if (predict && D == 3) fs_cycle_static_step3_kernel<<<(Ncap + 3) / 4, 256, 0, f->stream>>>(f->B, f->P, f->cur, live);
+  else if (predict) fs_cycle_static_step_kernel<<<(Ncap + 3) / 4, 256, 0, f->stream>>>(f->B, f->P, f->cur, live);
   HIPCHK(hipGetLastError());
   if (n_z == 0) {    // :399-402: the update is counted, nothing else happens
     f->mhcLastEmpty = true;
@@ -2927,15 +2974,31 @@ int rfsgpu_fastslam_cycle_async(rfsgpu_filter *f, int predict, const double *z, 
   if (rc != RFSGPU_OK) return rc;
   const FsParams F = fs_params(f, n_z);
   int *dSlotHyp = f->mhcInts, *dSlotNH = dSlotHyp + Ncap, *dDst = dSlotNH + Ncap, *dSrc = dDst + Ncap;
-  fs_mh_associate_kernel<2><<<Ncap, 64 * FSMH_WAVES, 0, f->stream>>>(f->B, f->P, F, f->cur, n_z, (int)f->fs.maxNDataAssocHypotheses, f->fs.maxDataAssocLogLikelihoodDiff,
-                                                                     f->mhArena, live);
-  fs_mh_plan_kernel<<<1, FS_CYCLE_THREADS, 0, f->stream>>>(f->mhArena, S, dSlotHyp, dSlotNH, dDst, dSrc, Ncap);
-  LiveCopy lc;
-  lc.n = S.w + FSC_NCOPY; lc.ovf = S.w + FSC_OVF; lc.copyCand = S.w + FSC_RESAMPLED;
-  fs_mh_copy_kernel<<<Ncap, 256, 0, f->stream>>>(f->B, f->cur, dDst, dSrc, 0, f->P.poseCovStride, lc);
-  fs_mh_split_weights_kernel<<<(Ncap + 255) / 256, 256, 0, f->stream>>>(f->B.weight, S.slotSrc, dSlotNH, 0, 0, live);
-  fs_mh_split_weights_kernel<<<(Ncap + 255) / 256, 256, 0, f->stream>>>(f->B.weight, S.slotSrc, dSlotNH, 0, 1, live);
-  fs_mh_apply_kernel<2><<<Ncap, 64, 0, f->stream>>>(f->B, f->P, F, f->cur, n_z, S.slotSrc, dSlotHyp, f->mhArena, live);
+  if (single) {
+    const size_t b1 = (size_t)(3 * RFSGPU_MAX_Z * 8) + fs_lds_bytes_per_wave(f->cap);
+    Buffers Bc = f->B;
+    Bc.N = Ncap;      // (the kernel's bound is its LiveCount)
+    if (D == 2) {
+      if ((rc = set_lds(f, (fs_associate_update_live_kernel<2>), b1)) != RFSGPU_OK) return rc;
+      fs_associate_update_live_kernel<2><<<Ncap, 64, b1, f->stream>>>(Bc, f->P, F, f->cur, n_z, f->fsArena, live);
+    } else {
+      if ((rc = set_lds(f, (fs_associate_update_live_kernel<3>), b1)) != RFSGPU_OK) return rc;
+      fs_associate_update_live_kernel<3><<<Ncap, 64, b1, f->stream>>>(Bc, f->P, F, f->cur, n_z, f->fsArena, live);
+    }
+    fs_cycle_identity_plan_kernel<<<1, FS_CYCLE_THREADS, 0, f->stream>>>(S, Ncap);
+  } else {
+    const int kmax = (int)f->fs.maxNDataAssocHypotheses;
+    if (D == 2) fs_mh_associate_kernel<2><<<Ncap, 64 * FSMH_WAVES, 0, f->stream>>>(f->B, f->P, F, f->cur, n_z, kmax, f->fs.maxDataAssocLogLikelihoodDiff, f->mhArena, live);
+    else fs_mh_associate_kernel<3><<<Ncap, 64 * FSMH_WAVES, 0, f->stream>>>(f->B, f->P, F, f->cur, n_z, kmax, f->fs.maxDataAssocLogLikelihoodDiff, f->mhArena, live);
+    fs_mh_plan_kernel<<<1, FS_CYCLE_THREADS, 0, f->stream>>>(f->mhArena, S, dSlotHyp, dSlotNH, dDst, dSrc, Ncap);
+    LiveCopy lc;
+    lc.n = S.w + FSC_NCOPY; lc.ovf = S.w + FSC_OVF; lc.copyCand = S.w + FSC_RESAMPLED;
+    fs_mh_copy_kernel<<<Ncap, 256, 0, f->stream>>>(f->B, f->cur, dDst, dSrc, 0, f->P.poseCovStride, lc);
+    fs_mh_split_weights_kernel<<<(Ncap + 255) / 256, 256, 0, f->stream>>>(f->B.weight, S.slotSrc, dSlotNH, 0, 0, live);
+    fs_mh_split_weights_kernel<<<(Ncap + 255) / 256, 256, 0, f->stream>>>(f->B.weight, S.slotSrc, dSlotNH, 0, 1, live);
+    if (D == 2) fs_mh_apply_kernel<2><<<Ncap, 64, 0, f->stream>>>(f->B, f->P, F, f->cur, n_z, S.slotSrc, dSlotHyp, f->mhArena, live);
+    else fs_mh_apply_kernel<3><<<Ncap, 64, 0, f->stream>>>(f->B, f->P, F, f->cur, n_z, S.slotSrc, dSlotHyp, f->mhArena, live);
+  }
   HIPCHK(hipGetLastError());
   bool flipped = false;
   if ((unsigned)n_z >= f->fs.pruningMeasurementsThreshold) {   // :611-612
@@ -2948,7 +3011,8 @@ int rfsgpu_fastslam_cycle_async(rfsgpu_filter *f, int predict, const double *z, 
     f->cur ^= 1;
     flipped = true;
   }
-  fs_new_landmarks_kernel<2, false, LiveCount><<<(Ncap + FS_NEWLM_WPB - 1) / FS_NEWLM_WPB, 64 * FS_NEWLM_WPB, 0, f->stream>>>(f->B, f->P, F, f->cur, n_z, live);
+  if (D == 2) fs_new_landmarks_kernel<2, false, LiveCount><<<(Ncap + FS_NEWLM_WPB - 1) / FS_NEWLM_WPB, 64 * FS_NEWLM_WPB, 0, f->stream>>>(f->B, f->P, F, f->cur, n_z, live);
+  else fs_new_landmarks_kernel<3, false, LiveCount><<<(Ncap + FS_NEWLM_WPB - 1) / FS_NEWLM_WPB, 64 * FS_NEWLM_WPB, 0, f->stream>>>(f->B, f->P, F, f->cur, n_z, live);
   // resampleWithMapCopy: the normalisation that ParticleFilter::resample starts with (or, where the gates keep it from running, the
   // one of :743), the decision and the plan, the copies, and the second normalisation of a resample() that returned false
   weight_sums_kernel<<<1, 1024, 0, f->stream>>>(f->B.weight, 0, f->dSums, live);
@@ -2968,6 +3032,32 @@ int rfsgpu_fastslam_cycle_async(rfsgpu_filter *f, int predict, const double *z, 
   f->mhcPending = true;
   return RFSGPU_OK;
 }
+int rfsgpu_fastslam_cycle_counts(rfsgpu_filter *f, int *n_cycles, int *n_resamplings) {
+  CHECK_HANDLE(f);
+  if (!f->mhcHave) return fail(f, RFSGPU_ERR_INVALID, "fastslam_cycle_counts: no device cycle has run on this handle");
+  if (n_cycles) *n_cycles = f->mhcDone;
+  if (n_resamplings) *n_resamplings = f->mhcNFired;
+  return RFSGPU_OK;
+}
+// [test] One slot's weight, mixture size, candidate count and first Gaussian (entry 0 of every plane: gauss [7] or [11]), read or
+// written for ANY slot below max_particles: how a test plants a pattern beyond the live count and finds it again.
+int rfsgpu_debug_slot(rfsgpu_filter *f, int slot, int write, double *weight, int *count, int *cand_count, double *gauss) {
+  CHECK_HANDLE(f);
+  if (slot < 0 || slot >= f->Ncap || !weight || !count || !cand_count || !gauss) return fail(f, RFSGPU_ERR_INVALID, "debug_slot: bad arguments");
+  hipSetDevice(f->device);
+  const hipMemcpyKind kind = write ? hipMemcpyHostToDevice : hipMemcpyDeviceToHost;
+  auto mv = [&](void *dev, void *host, size_t bytes) { return write ? hipMemcpyAsync(dev, host, bytes, kind, f->stream) : hipMemcpyAsync(host, dev, bytes, kind, f->stream); };
+  HIPCHK(mv(f->B.weight + slot, weight, sizeof(double)));
+  HIPCHK(mv(f->B.count + slot, count, sizeof(int)));
+  HIPCHK(mv(f->B.candCount + slot, cand_count, sizeof(int)));
+  for (int pl = 0; pl < f->B.npl; pl++) {     // (written into both slabs: a prune flips them)
+    HIPCHK(mv(f->B.slab[f->cur] + ((size_t)slot * f->B.npl + pl) * (size_t)f->B.cap, gauss + pl, sizeof(double)));
+    if (write) HIPCHK(mv(f->B.slab[f->cur ^ 1] + ((size_t)slot * f->B.npl + pl) * (size_t)f->B.cap, gauss + pl, sizeof(double)));
+  }
+  HIPCHK(hipStreamSynchronize(f->stream));
+  return RFSGPU_OK;
+}
+int rfsgpu_fastslam_cycle_pending(rfsgpu_filter *f) { return (f && f->mhcPending) ? 1 : 0; }
 int rfsgpu_fastslam_last_cycle(rfsgpu_filter *f, int *n_after_update, int *n_after_resample, int *fired, double *n_eff, int *parent, int *plan, int max_n) {
   CHECK_HANDLE(f);
   if (!f->mhcHave) return fail(f, RFSGPU_ERR_INVALID, "fastslam_last_cycle: no rfsgpu_fastslam_cycle_async has run on this handle");

@@ -277,31 +277,43 @@ class FastSLAM(RBPHDFilter):
     handle has room for nParticlesMax * max_hypotheses particles; `parents` (slot -> the particle it was copied from in the
     last update) and `last_resample_plan` let a caller holding poses follow the copies."""
 
-    def __init__(self, n_particles, device_id=0, gm_capacity=512, max_hypotheses=1, n_particles_max=None, device_cycle=False, max_particles=None):
+    def __init__(self, n_particles, device_id=0, gm_capacity=512, max_hypotheses=1, n_particles_max=None, device_cycle=False, max_particles=None,
+                 model=capi.MODEL_RNGBRG_2D):
         n_max = 3 * n_particles if n_particles_max is None else int(n_particles_max)    # FastSLAM.hpp:250
         cap = max(n_particles, n_max) * max(1, int(max_hypotheses)) if max_hypotheses > 1 else None
         if max_particles is not None:       # the handle's particle slots, given outright (the yardstick of one filter of an MHFastSLAMBatch)
             cap = int(max_particles)
-        super().__init__(n_particles, device_id=device_id, gm_capacity=gm_capacity, max_particles=cap)
+        super().__init__(n_particles, device_id=device_id, gm_capacity=gm_capacity, max_particles=cap, model=model)
+        self.model = model
         self.fs_config = self.default_fastslam_config()
         self.fs_config.nParticlesMax = n_max
         self.fs_config.maxNDataAssocHypotheses = max(1, int(max_hypotheses))
         self.parents = np.arange(n_particles, dtype=np.int32)
         self.last_resample_plan = None
         # device_cycle: update_and_resample runs as one rfsgpu_fastslam_cycle_async (copy plan and resampleWithMapCopy on the device,
-        # no host round trip inside the cycle); the handle must hold max_particles <= 2048 and keep no landmark candidate lists
+        # no host round trip inside the cycle); the handle must hold max_particles <= 2048.  The Victoria Park model and landmark
+        # candidate lists (landmarkCandidateMeasurementCountThreshold != 1) go through rfsgpu_fastslam_cycle_full_async.
         self.device_cycle = bool(device_cycle)
         self.last_cycle = None
 
-    def cycle_async(self, Z, u01, predict=False):
-        """One whole FastSLAM::update enqueued, nothing read back (rfsgpu_fastslam_cycle_async): u01 is the draw a resampling would
-        use.  Cycles may follow one another without a synchronisation; sync_cycle() brings parents / last_resample_plan /
-        resampleOccured up to date."""
-        self.apply_config()
-        self.set_fastslam_config(self.fs_config)
-        self.fastslam_set_resampling(self.effNParticles_t, self.effNParticles_t_percent)
+    def uses_full_cycle(self):
+        """Whether device_cycle goes through rfsgpu_fastslam_cycle_full_async: the Victoria Park model, or landmark candidate lists."""
+        return self.model != capi.MODEL_RNGBRG_2D or int(self.fs_config.landmarkCandidateMeasurementCountThreshold) != 1
+
+    def cycle_async(self, Z, u01, predict=False, scan=None, push_config=True):
+        """One whole FastSLAM::update enqueued, nothing read back (rfsgpu_fastslam_cycle_async, or rfsgpu_fastslam_cycle_full_async
+        where uses_full_cycle()): u01 is the draw a resampling would use; scan: this update's laser scan (Victoria Park model).
+        Cycles may follow one another without a synchronisation; sync_cycle() brings parents / last_resample_plan / resampleOccured
+        up to date.  push_config=False: the configuration was pushed by an earlier call and has not changed."""
+        if push_config:
+            self.apply_config()
+            self.set_fastslam_config(self.fs_config)
+            self.fastslam_set_resampling(self.effNParticles_t, self.effNParticles_t_percent)
         Z = np.asarray(Z, dtype=np.float64).reshape(-1, self.dz)
-        self.fastslam_cycle_async(Z, u01, self.n_init, predict)
+        if scan is not None or self.uses_full_cycle():
+            self.fastslam_cycle_full_async(Z, u01, self.n_init, predict, scan=scan)
+        else:
+            self.fastslam_cycle_async(Z, u01, self.n_init, predict)
 
     def sync_cycle(self):
         """The results of the last cycle_async (synchronises)."""

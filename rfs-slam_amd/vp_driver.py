@@ -5,6 +5,17 @@ Mirrors the reference driver's run() (src/rbphdslam_VictoriaPark.cpp:471-628): `
 motion model (src/ProcessModel_Ackerman2D.cpp:47-78) and the input-noise sampling stay on the host like every RNG-bound
 piece of the reference; resampling follows ParticleFilter::resample through engine.systematic_resample_plan.
 The dataset's raw LASER.txt is missing from the reference, so the scan is the synthetic constant-70 m one.
+
+FastSLAM options (filter="fastslam"):
+  max_hypotheses     MH-FastSLAM: an update multiplies particles; `n` is the live count, `n_init` the configured one, and a grown
+                     count above n_particles_max forces the resampling back to n_init (FastSLAM::resampleWithMapCopy).  On the
+                     host-stop route host poses follow particle_parents() and then the resampling plan.
+  device_motion      the poses live on the device: Ackerman propagation under `motion_seed` (csrc/motion.h), every run of messages
+                     up to a lidar message as one propagate_ackerman_run_async + one static_steps_async.
+  device_cycle       every lidar message is one rfsgpu_fastslam_cycle_full_async that carries the scan (implies device_motion);
+                     nothing is read until the end of the run, or until sync().  sync_every_update reads each cycle's results.
+  draw_every_update  one resampling draw per lidar update with measurements, used or not, so that the host-stop route and the
+                     device cycle (which needs the draw before the decision exists) share a realisation.
 """
 import numpy as np
 
@@ -29,7 +40,8 @@ def ackerman_step(x, u_v, u_r, dt, a=ACKERMAN):
 
 class VictoriaParkRun:
     def __init__(self, f, data, params, seed=1, var_uv=0.2, var_ur=0.025, noise_inflation=20.0, added_clutter=3.0, eff_n=None,
-                 filter="rbphd", device_resample=False):
+                 filter="rbphd", device_resample=False, max_hypotheses=1, n_particles_max=None, device_cycle=False, draw_every_update=False,
+                 device_motion=False, motion_seed=1, sync_every_update=False):
         # device_resample: the resample-or-normalise tail of an update as one rfsgpu_resample_async (same realisation and results)
         # filter = "rbphd": src/rbphdslam_VictoriaPark.cpp; "fastslam": src/fastslam_VictoriaPark.cpp (same event loop around
         # FastSLAM::predict / update: no births in predict, rfsgpu_fastslam_update)
@@ -48,9 +60,35 @@ class VictoriaParkRun:
         self.n_meas_since = 0
         self.n_resamples = 0
         self.n_lidar = 0
+        self.n_init = self.n
+        self.hyp = int(max_hypotheses)
+        self.n_max = int(n_particles_max) if n_particles_max is not None else (3 * self.n if self.hyp > 1 else self.n)
+        self.device_cycle = bool(device_cycle)
+        self.device_motion = bool(device_motion) or self.device_cycle
+        self.draw_every_update = bool(draw_every_update) or self.device_cycle
+        self.sync_every_update = bool(sync_every_update)
+        self.motion_seed, self.n_calls = int(motion_seed), 0
+        self.n_grown_max, self.n_forced = self.n, 0
+        self._run = []                    # (u, var, dt) of the predicts not yet enqueued (device_motion)
+        if (self.hyp > 1 or self.device_cycle or self.device_motion) and not self.fastslam:
+            raise ValueError("max_hypotheses, device_cycle and device_motion belong to filter='fastslam'")
+        if self.fastslam and (self.hyp > 1 or self.device_cycle):
+            cfg = f.get_fastslam_config()
+            cfg.maxNDataAssocHypotheses = self.hyp
+            cfg.nParticlesMax = self.n_max
+            cfg.minUpdatesBeforeResample = int(params["min_updates"])
+            cfg.minMeasurementsBeforeResample = int(params["min_measurements"])
+            f.set_fastslam_config(cfg)
+        if self.device_cycle:
+            f.fastslam_set_resampling(self.eff_n, self.eff_n / self.n_init)
+        if self.device_motion:
+            f.set_poses(self.x, None)
 
     def _predict(self, u, dt, stationary, birth):
         f = self.f
+        if self.device_motion:            # queued: the run goes to the device at the next lidar message (or at sync())
+            self._run.append((float(u[0]), float(u[1]), 0.0 if stationary else self.var[0], 0.0 if stationary else self.var[1], float(dt)))
+            return
         f.set_lmk_process_noise(np.diag([5e-4, 5e-4, 1e-4]) * dt * dt)   # varlm* x dt^2 (:497-500)
         f.set_poses(self.x, None)                                          # poses BEFORE propagation: birth uses them
         f.predict_map(False if self.fastslam else birth)
@@ -60,6 +98,58 @@ class VictoriaParkRun:
             uv = u[0] + np.sqrt(self.var[0]) * self.rng.standard_normal(self.n)
             ur = u[1] + np.sqrt(self.var[1]) * self.rng.standard_normal(self.n)
         self.x = ackerman_step(self.x, uv, ur, dt)
+
+    def _flush_run(self):
+        """The queued predicts as one propagation run and one run of static steps (same bits as one call per message)."""
+        if not self._run:
+            return
+        r = np.array(self._run, dtype=np.float64)
+        self._run = []
+        a = ACKERMAN
+        q = np.diag([5e-4, 5e-4, 1e-4])[None, :, :] * (r[:, 4] ** 2)[:, None, None]      # varlm* x dt^2 (:497-500)
+        self.f.static_steps_async(len(r), q)
+        self.f.propagate_ackerman_run_async(r[:, 0:2], r[:, 2:4], r[:, 4], (a["h"], a["l"], a["dx"], a["dy"]), self.motion_seed, self.n_calls)
+        self.n_calls += len(r)
+
+    def sync(self):
+        """Bring the host's view up to date on the device-cycle route (synchronises): the live count and the number of resamplings."""
+        self._flush_run()
+        self.f.synchronize()
+        self.n = self.f.n
+        if self.device_cycle and self.n_lidar:
+            self.n_resamples = self.f.fastslam_cycle_counts()[1]
+        return self
+
+    def _update_fastslam(self, Z):
+        """FastSLAM::update's tail for one lidar message with measurements: the update, then resampleWithMapCopy."""
+        f, P = self.f, self.P
+        u01 = float(self.rng.uniform()) if self.draw_every_update else None
+        draw = (lambda: u01) if self.draw_every_update else (lambda: float(self.rng.uniform()))
+        if self.device_cycle:
+            f.fastslam_cycle_full_async(Z, u01, self.n_init, predict=False, scan=self.scan)
+            if self.sync_every_update:
+                lc = f.fastslam_last_cycle()
+                self.n_grown_max = max(self.n_grown_max, lc["n_after_update"])
+                self.n = lc["n_after_resample"]
+            return
+        f.fastslam_update(Z)
+        if self.hyp > 1:
+            par = f.particle_parents()
+            if not self.device_motion:
+                self.x = self.x[par]
+            self.n = f.n
+            self.n_grown_max = max(self.n_grown_max, self.n)
+        fired, forced = False, self.n > self.n_max
+        if forced or (self.n_updates_since >= P["min_updates"] and self.n_meas_since >= P["min_measurements"]):
+            fired = self._resample(draw, force=forced)
+            self.n_forced += int(forced and fired)
+        if self.hyp > 1:
+            f.fastslam_set_resample_occured(fired)
+        if fired:
+            self.n_updates_since = self.n_meas_since = 0
+        else:
+            s = f.weight_sums()
+            f.normalize_weights(s[0])
 
     def run(self, n_messages=None):
         f, P = self.f, self.P
@@ -88,10 +178,20 @@ class VictoriaParkRun:
                         b = self.rng.uniform() * ((np.rad2deg(P["bmax"]) - np.rad2deg(P["bmin"])) + np.rad2deg(P["bmin"])) * np.pi / 180  # sic (:563)
                         Z.append(np.array([r, b, 1.0]))
                 Z = np.array(Z).reshape(-1, 3)[:60]
-                f.set_laser_scan(self.scan)
-                f.set_poses(self.x, None)
+                self._flush_run()
+                if self.device_cycle:
+                    if not len(Z):        # an update without measurements is only counted (FastSLAM.hpp:399-402)
+                        f.fastslam_cycle_full_async(Z, 0.0, self.n_init, predict=False, scan=self.scan)
+                else:
+                    f.set_laser_scan(self.scan)
+                    if not self.device_motion:
+                        f.set_poses(self.x, None)
                 self.n_updates_since += 1
-                if len(Z):
+                if len(Z) and self.fastslam and (self.device_cycle or self.hyp > 1 or self.draw_every_update or self.device_motion):
+                    self.n_meas_since += len(Z)
+                    self.n_lidar += 1
+                    self._update_fastslam(Z)
+                elif len(Z):
                     self.n_meas_since += len(Z)
                     if self.fastslam:
                         f.fastslam_update(Z)
@@ -109,6 +209,8 @@ class VictoriaParkRun:
                         f.normalize_weights(s[0])
                 birth = True
                 t_km = t_k
+        if self.device_motion:
+            self.sync()
         return self
 
     def _resample_device(self):
@@ -126,16 +228,25 @@ class VictoriaParkRun:
         self.n_resamples += 1
         return True
 
-    def _resample(self):
+    def _resample(self, draw=None, force=False):
+        """ParticleFilter::resample(n_init, force): draw() gives the uniform of the systematic plan (default: the run's stream)."""
         f = self.f
         s = f.weight_sums()
         f.normalize_weights(s[0])
         w = f.get_weights()
-        neff = 1.0 / float(np.sum(w * w))
-        if neff > self.eff_n and neff / self.n > self.eff_n / self.n:
-            return False
-        plan = systematic_resample_plan(w, float(self.rng.uniform()))
-        f.resample_apply(plan)
-        self.x = self.x[plan]
+        if not force:
+            neff = 1.0 / float(np.sum(w * w))
+            if neff > self.eff_n and neff / self.n > self.eff_n / self.n_init:
+                return False
+        u01 = float(self.rng.uniform()) if draw is None else draw()
+        if self.n > self.n_init:          # a grown set comes back to its initial count
+            plan = systematic_resample_plan(w, u01, n_out=self.n_init)
+            f.resample_apply(plan, n_out=self.n_init)
+            self.n = self.n_init
+        else:
+            plan = systematic_resample_plan(w, u01)
+            f.resample_apply(plan)
+        if not self.device_motion:
+            self.x = self.x[plan]
         self.n_resamples += 1
         return True

@@ -54,6 +54,54 @@ def mh_route_times(pkg, device_cycle, n, hyp, steps, reps, quiet=False):
     return out
 
 
+def vp_cycle_run(pkg, route, hyp, n, messages):
+    """Seconds for one run of `messages` messages of the Victoria Park extract through vp_driver.VictoriaParkRun: the values of the
+    reference's fastslam_VictoriaPark.xml / mhfastslam_VictoriaPark.xml (100 particles, candidate threshold 4, 1 or 3 hypotheses),
+    poses propagated on the device on every route.  route: "host" (rfsgpu_fastslam_update + the host's resampleWithMapCopy),
+    "sync" (rfsgpu_fastslam_cycle_full_async, results read after every lidar message) or "queue" (nothing read until the end)."""
+    data = np.load(os.path.join(ROOT, "tests", "golden", "victoria_park_extract.npz"))
+    P = dict(sc.VP_PARAMS)
+    n_max = 3 * n if hyp > 1 else n
+    f = pkg.RBPHDFilter(n, gm_capacity=192, model=pkg.capi.MODEL_VICTORIAPARK_3D, max_particles=n_max * hyp)
+    sc.apply_vp_params(f, P, np.full(361, 70.0))
+    cfg = f.default_fastslam_config()
+    cfg.minLogMeasurementLikelihood = -15.0
+    cfg.mapExistencePruneThreshold = -5.0
+    cfg.landmarkCandidateMeasurementCountThreshold = 4
+    cfg.landmarkCandidateCurrentMeasurementCountThreshold = 0
+    cfg.landmarkCandidateMeasurementCheckThreshold = 5
+    cfg.landmarkCandidateMeasurementSupportDist = 3.0
+    cfg.maxNDataAssocHypotheses = hyp
+    cfg.maxDataAssocLogLikelihoodDiff = 3.0
+    f.set_fastslam_config(cfg)
+    opts = dict(device_motion=True, draw_every_update=True) if route == "host" else dict(device_cycle=True, sync_every_update=route == "sync")
+    f.synchronize()
+    t0 = time.perf_counter()
+    run = pkg.vp_driver.VictoriaParkRun(f, data, P, seed=5, filter="fastslam", max_hypotheses=hyp, n_particles_max=n_max, **opts).run(n_messages=messages)
+    dt = time.perf_counter() - t0
+    out = (dt, run.n_lidar, run.n_resamples, run.n, float(np.asarray(f.gm_sizes()).mean()))
+    f.close()
+    return out
+
+
+if "--vp-cycle" in sys.argv:
+    n, messages, reps = [int(os.environ.get(k, d)) for k, d in (("FS_N", 100), ("FS_MESSAGES", 900), ("FS_REPS", 3))]
+    for hyp in (1, 3):
+        print("Victoria Park extract, %d messages, %d particles, %d hypothes%s, %d repetitions (routes alternate; the first round warms up)" %
+              (messages, n, hyp, "is" if hyp == 1 else "es", reps))
+        times = {"host": [], "sync": [], "queue": []}
+        for rep in range(reps + 1):
+            for route in ("host", "sync", "queue"):
+                dt, nl, nr, nn, size = vp_cycle_run(pkg, route, hyp, n, messages)
+                if rep:
+                    times[route].append(dt)
+                print("  rep %d %-5s: %.4f s/run, %d lidar updates, %d resamplings, final count %d, mean map size %.1f%s" %
+                      (rep, route, dt, nl, nr, nn, size, "" if rep else "  (warm-up)"))
+        med = {k: float(np.median(v)) for k, v in times.items()}
+        print("hyp %d medians: host-stop %.4f s, cycle + sync per update %.4f s (%.2fx), cycle queued %.4f s (%.2fx)" %
+              (hyp, med["host"], med["sync"], med["host"] / med["sync"], med["queue"], med["host"] / med["queue"]))
+    sys.exit(0)
+
 if "--mh-device-cycle" in sys.argv:
     n, hyp, steps, reps = [int(os.environ.get(k, d)) for k, d in (("FS_N", 200), ("FS_HYP", 4), ("FS_STEPS", 100), ("FS_REPS", 3))]
     print("MH-FastSLAM, %d particles, %d hypotheses, %d steps, %d repetitions" % (n, hyp, steps, reps))
