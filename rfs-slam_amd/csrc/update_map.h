@@ -587,15 +587,18 @@ __device__ __forceinline__ void phd_update_map_particle(const Buffers &B, const 
   }
 }
 
-// LDS of the workgroup form below: the single-wave layout + cross-wave scratch.
+// Words of the survivor list's per-measurement bit table (workgroup form): one bit per list position.
+__host__ __device__ inline int update_map_zpos_words(int cap) { return (cap + 31) >> 5; }
+// LDS of the workgroup form below: the single-wave layout + cross-wave scratch + the bit table [words][MAX_Z].
 __host__ __device__ inline size_t update_map_block_lds_bytes(int cap) {
-  return update_map_lds_bytes_per_wave(cap) + 128;
+  return update_map_lds_bytes_per_wave(cap) + 128 + (size_t)update_map_zpos_words(cap) * RFSGPU_MAX_Z * 4;
 }
 
 // The same map update by a workgroup of WPP waves (used inside the fused step kernel, where the particle's workgroup has
 // more than one wave): passes cover WPP*64 landmarks; the survivor list keeps its (m, z) order through a cross-wave
-// offset exchange, wave 0 folds the normalisers in list order (the reference's summation order), phases 2 and 3 are
-// split over all threads.  Bit-identical to phd_update_map_particle.
+// offset exchange, wave 0 folds the normalisers in list order (the reference's summation order) -- once, behind the passes,
+// each lane finding its measurement's list positions in a bit table the emitting lanes fill --, phases 2 and 3 are
+// split over all threads.  Bit-identical to phd_update_map_particle, which walks the list and is the reference for the table.
 template <int WPP>
 __device__ __forceinline__ void phd_update_map_block(const Buffers &B, const Params &P, const int cur, const int nZ, const int i, const int tid,
                                                      const unsigned char *smemZ, unsigned char *wb, const bool phasePrio = false) {
@@ -613,6 +616,9 @@ __device__ __forceinline__ void phd_update_map_block(const Buffers &B, const Par
   int *sTot = reinterpret_cast<int *>(wb + update_map_lds_bytes_per_wave(cap));  // [2][8] survivors per wave of a pass (double-buffered)
   int *sMisc = sTot + 16;                                       // [0] overflow flag [1] landmarks in FOV [2] a new Gaussian has to be dropped
   unsigned *sUsed = reinterpret_cast<unsigned *>(sMisc + 4);    // [2] used-measurement mask (lo, hi)
+  // [words][MAX_Z] bit (pos & 31) of word pos >> 5, column z: list position pos holds a survivor of measurement z (word-major: the
+  // words a particle can reach, those below `room`, are one contiguous block to clear, and lane z's reads of a word are conflict-free)
+  unsigned *sZPos = reinterpret_cast<unsigned *>(wb + update_map_lds_bytes_per_wave(cap) + 128);
 
   const int nM = B.count[i];
   const unsigned long long zmask = (nZ >= 64) ? ~0ull : ((1ull << nZ) - 1ull);
@@ -631,6 +637,11 @@ __device__ __forceinline__ void phd_update_map_block(const Buffers &B, const Par
   PoseReg pr;
   load_pose(B, P, i, pr);
   if (tid < 6) { if (tid < 4) sMisc[tid] = 0; else sUsed[tid - 4] = 0u; }
+  {  // clear the bit table's words below `room` (no bit is set or read beyond); the first barrier of pass 0 stands before the first bit set
+    const int nQuad = (cap - nM > 0) ? ((cap - nM + 31) >> 5) * (RFSGPU_MAX_Z / 4) : 0;
+    uint4 *q = reinterpret_cast<uint4 *>(sZPos);
+    for (int j = tid; j < nQuad; j += NT) q[j] = make_uint4(0u, 0u, 0u, 0u);
+  }
   // the measurement index, once per workgroup: wave 0 bins the bearings, wave 1 the ranges
   if (P.gateIndex) {
     if (wave == 0) gate_index_build_bearing(gTab, sZf, nZ, lane);
@@ -721,38 +732,33 @@ __device__ __forceinline__ void phd_update_map_block(const Buffers &B, const Par
           if (q >= UPDMAP_KEEP) v = pair_value(P, k, pdw, z0, z1);
           sV[pos] = v;
           sMZ[pos] = ((unsigned)m << 8) | (unsigned)z;
+          __hip_atomic_fetch_or(&sZPos[(pos >> 5) * RFSGPU_MAX_Z + z], 1u << (pos & 31), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
           emit_updated(k, mx, my, z0, z1, pMX, pMY, pSXX, pSXY, pSYY, nM + pos);
         } else {
           overflow = true;
         }
       }
     }
-    __syncthreads();
+    // No barrier at the end of a pass: what it writes (sSeg, sV, sMZ, table bits -- every list position and landmark once) is read
+    // only behind the barrier that follows the loop, and sTot alternates between two buffers -- a wave overwrites tot[p & 1] in pass
+    // p + 2, behind the barrier of pass p + 1, which every wave reaches only after its reads of pass p.
     RFS_CUT(4);
-    if (wave == 0) {  // lane z folds this pass's survivors of measurement z into its normaliser, in landmark order
-      const int lo = nSurv, hi = (nSurv + total < room) ? nSurv + total : room;
-      int sIdx = lo;
-      for (; sIdx + 4 <= hi; sIdx += 4) {  // broadcast reads, four in flight; the adds stay in list (= landmark) order
-        const unsigned mz0 = sMZ[sIdx], mz1 = sMZ[sIdx + 1], mz2 = sMZ[sIdx + 2], mz3 = sMZ[sIdx + 3];
-        const double v0 = sV[sIdx], v1 = sV[sIdx + 1], v2 = sV[sIdx + 2], v3 = sV[sIdx + 3];
-        if ((int)(mz0 & 0xffu) == lane) cs += v0;
-        if ((int)(mz1 & 0xffu) == lane) cs += v1;
-        if ((int)(mz2 & 0xffu) == lane) cs += v2;
-        if ((int)(mz3 & 0xffu) == lane) cs += v3;
-      }
-      for (; sIdx < hi; sIdx++) {
-        const unsigned mz = sMZ[sIdx];
-        const double v = sV[sIdx];
-        if ((int)(mz & 0xffu) == lane) cs += v;
-      }
-    }
     nSurv += total;
-    RFS_CUT(5);
   }
   RFS_CUT(6);
   if (__ballot(overflow) != 0ull && lane == 0) atomicOr(&sMisc[0], 1);
   if (lane == 0) atomicAdd(&sMisc[1], nFov);
+  __syncthreads();
+  // lane z of wave 0 folds the survivors of measurement z into its normaliser, once, in list (= landmark) order: its column of the
+  // bit table names their positions, so it reads the handful that are its own instead of walking the whole list
+  if (wave == 0 && lane < nZ) {
+    const int nList = nSurv < room ? nSurv : room;   // (bits exist below this only)
+    const int nWord = (nList + 31) >> 5;
+    for (int w = 0; w < nWord; w++)
+      for (unsigned bits = sZPos[w * RFSGPU_MAX_Z + lane]; bits; bits &= bits - 1) cs += sV[32 * w + __builtin_ctz(bits)];
+  }
   if (wave == 0) sCol[lane] = cs;
+  RFS_CUT(5);   // (behind the store: a cut in front of it leaves the sums dead, and the compiler drops the fold from the cut build)
   __syncthreads();
   if (sMisc[0] != 0 || nSurv > room) {
     if (tid == 0) atomicOr(B.err, ERRBIT_CAPACITY);

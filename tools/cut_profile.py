@@ -13,9 +13,9 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-OUT = os.path.join(ROOT, "tools", "_build")
+OUT = os.path.abspath(os.environ.get("CUT_OUT", os.path.join(ROOT, "tools", "_build")))     # (CUT_OUT: another build's cut libraries, for an A/B)
 CUTS = [(1, "map update, pass 0: KF quantities + Pd"), (2, "  + packed-fp32 gate sweep"), (3, "  + exact gates / likelihood of the candidates"),
-        (4, "  + scan, list write, new means/covariances"), (5, "  + normaliser fold (end of pass 0)"), (6, "map update phase 1 (all passes)"),
+        (4, "  + scan, list write, new means/covariances"), (6, "map update phase 1 (all passes)"), (5, "  + normaliser fold (once, behind the passes)"),
         (7, "map update phase 2"), (8, "map update done"), (10, "weighting: chunk rank sort"), (11, "  + cross-chunk ranks"), (12, "  + permutation out"),
         (13, "  + evaluation points, weight sums"), (14, "  + likelihood table (wave 0 alone; no intensity)"),
         (15, "  + partitions (wave 0 alone; no intensity)"), (16, "weighting done (with the intensity pass)"), (20, "merge: stage"),
@@ -31,7 +31,10 @@ if sys.argv[1] == "--build":
     bm = g.load_package().build_mod
     os.makedirs(OUT, exist_ok=True)
     procs = []
+    only = [int(x) for x in os.environ.get("CUT_ONLY", "").split(",") if x]     # (CUT_ONLY=4,6,5,8: a subset; --run skips the others)
     for k, _ in CUTS:
+        if only and k not in only:
+            continue
         cmd = [bm.hipcc()] + bm.FLAGS + [f"-DRFS_STOP_AT={k}"] + os.environ.get("CUT_FLAGS", "").split() + [os.path.join(bm.CSRC, "rfsgpu_engine.hip"), "-o", lib_of(k)]
         procs.append((k, subprocess.Popen(cmd, stderr=subprocess.DEVNULL)))
     for k, p in procs:
