@@ -49,6 +49,8 @@
  *   [batch]    many independent 2-D filters in one handle, stepped together in one launch chain;
  *   [metric]   per-step OSPA / COLA map error and pose error computed on the device, kept in a device-side log;
  *   [resample] ParticleFilter::resample for an ordinary handle of any size on the device, without a host stop;
+ *   [rbphd-cycle] the whole RBPHDFilter::update -- its counters, its gate, the resampling -- enqueued without a host stop, and the
+ *              birth predict behind it with the inheritance walk made on the device;
  *   [sensor]   the simulator's range-bearing sensor of every filter of a batch (RB-PHD; FastSLAM kinds by a switch) drawn on the device, for batch sweeps;
  *   [truth]    the simulator's trajectory, odometry and landmarks of every filter of a batch drawn on the device, and a run of steps in one call;
  *   [estimate] every filter's pose and map estimate per step (the reference's particlePose.dat / landmarkEst.dat) kept in a device-side log.
@@ -342,7 +344,9 @@ int rfsgpu_cycle_async(rfsgpu_filter *f, int predict, const double *x, const dou
  * inputs, one for the step, no host wait -- src/rbphdslam_VictoriaPark.cpp:555-583):
  *   rfsgpu_set_step_inputs_async  poses (+ covariance; x == NULL leaves them) and, Victoria Park model, the laser scan
  *                                 (MeasurementModel_VictoriaPark::setLaserScan; scan == NULL leaves it) through a pinned ring;
- *   rfsgpu_predict_map_async      rfsgpu_predict_map without the error-word readback.
+ *   rfsgpu_predict_map_async      rfsgpu_predict_map without the error-word readback.  With add_birth != 0 it resolves a pending
+ *                                 rfsgpu_resample_async first (the inheritance walk reads the ids on the host); behind pending
+ *                                 rfsgpu_rbphd_cycle_async cycles it resolves nothing: the walk is made on the device ([rbphd-cycle]).
  * Device-side errors (capacity, ...) of asynchronous calls surface at the next synchronising call (rfsgpu_synchronize,
  * rfsgpu_weight_sums, rfsgpu_get_weights, ...). */
 int rfsgpu_set_step_inputs_async(rfsgpu_filter *f, const double *x, const double *cov, int cov_stride, const double *scan, int n_scan);
@@ -982,13 +986,61 @@ int rfsgpu_get_map_estimate(rfsgpu_filter *f, int filter, double w_threshold, in
  * enqueued before the resampling (RFSGPU_ERR_CAPACITY, ...) is returned by the resolving call, and the resampling's own
  * bookkeeping is still taken over.  While a call that keeps the count is pending, rfsgpu_static_steps_async, rfsgpu_propagate_ackerman_async /
  * _run_async, rfsgpu_set_step_inputs_async, rfsgpu_predict_map_async(f, 0) and the configuration setters enqueue behind it
- * without resolving; every other call, and every call while one with n_out < n_particles is pending, resolves first. */
+ * without resolving; every other call, and every call while one with n_out < n_particles is pending, resolves first.
+ * RFSGPU_ERR_UNSUPPORTED as well on a handle on which rfsgpu_rbphd_cycle_async has run ([rbphd-cycle]: the ids and the gate's
+ * counters are the device's there). */
 int rfsgpu_resample_async(rfsgpu_filter *f, double eff_n, double eff_n_percent, double u01, int n_out, int force, int renormalize);
 /* The last rfsgpu_resample_async (resolves): *fired whether it resampled (the return value of :400), *n_eff its N_eff (0 when
  * forced, :405), *n_after the particle count behind it (:482), plan[k] for those slots: the slot whose particle slot k now holds
  * a copy of (:474), k itself where the particle stayed (case 1, :465) or nothing fired.  Any pointer may be NULL; max_n >= the
  * count when plan is given. */
 int rfsgpu_last_resample(rfsgpu_filter *f, int *fired, double *n_eff, int *n_after, int *plan, int max_n);
+
+/* ---- [rbphd-cycle] the whole RBPHDFilter::update on the device (outside the STABLE CORE) ----------------------------------------------
+ * rfsgpu_resample_async leaves the two gates of RBPHDFilter::update (include/RBPHDFilter.hpp:528-529) and their counters with the
+ * caller, who must therefore read `fired` back after every update.  rfsgpu_rbphd_cycle_async enqueues one whole update (:444-541)
+ * on the handle's stream and waits for nothing:
+ *   1. nUpdatesSinceResample_ is counted on the device (:448); with n_z == 0 the call ends there (:451-452);
+ *   2. nMeasurementsSinceResample_ is counted (:453); the scan (Victoria Park model; NULL leaves it) goes through the pinned ring of
+ *      rfsgpu_set_step_inputs_async, its clutter density computed as rfsgpu_set_laser_scan computes it;
+ *   3. the step: the launches of rfsgpu_cycle_async(f, RFSGPU_CYCLE_NO_PREDICT, NULL, NULL, 0, NULL, z, n_z, 0), z [n_z][2] or [n_z][3];
+ *   4. resampleOccured_ is cleared (:526) and the gate tested on the device against minUpdatesBeforeResample and
+ *      minMeasurementsBeforeResample of the handle's rfsgpu_filter_config.  Closed: the weights are normalised once (:537).  Open:
+ *      ParticleFilter::resample as rfsgpu_resample_async(f, eff_n, eff_n_percent, u01, 0, 0, 1) does it, with the thresholds of
+ *      rfsgpu_rbphd_set_resampling (never set: n_particles / 4 and 1 / 4); where it fires the device zeroes both counters and sets
+ *      resampleOccured_ (:530-535).  The plan, gather and second-normalisation launches are enqueued either way and leave on
+ *      device-side guards behind a closed gate.
+ * The poses are the device's and follow the copies.  The particle count never changes on this route.  Cycles may follow one
+ * another without a resolving call between them.  A weight set that cannot be resampled behaves as under rfsgpu_resample_async:
+ * that cycle's tail touches nothing and the next resolving call returns RFSGPU_ERR_INVALID once.
+ * While cycles are pending, rfsgpu_static_steps_async, rfsgpu_propagate_ackerman_async / _run_async,
+ * rfsgpu_set_step_inputs_async(x == NULL), rfsgpu_set_lmk_process_noise, rfsgpu_set_filter_config, rfsgpu_rbphd_set_resampling and
+ * rfsgpu_predict_map_async enqueue behind them without resolving (rfsgpu_set_kf_config and the model setters resolve).  A call that
+ * returns an error has counted no update and leaves the host route open; a scan it carried may have been installed.  With
+ * n_z == 0 a scan that comes with the call is installed too.  rfsgpu_predict_map_async(f, 1) then makes the inheritance walk of
+ * RBPHDFilter.hpp:1005-1011 on the device, from the ids and the resampleOccured_ the device holds: a levels kernel, the staging
+ * pair and the level-0 births, RFSGPU_RBPHD_WALK_LEVELS (copy, birth) pairs that find nothing to do where the walk is shallower,
+ * and a one-workgroup kernel that finishes any deeper levels -- the same bits as rfsgpu_predict_map after a resolve, at any depth.
+ * Every other call resolves first (one small copy and a wait) and takes over the ids, resampleOccured_ and the device's error
+ * word, as for rfsgpu_resample_async.  Once a cycle has run on a handle, rfsgpu_resample_apply[_n] and rfsgpu_resample_async
+ * return RFSGPU_ERR_UNSUPPORTED on it (the counters are the device's); the host route first and cycles later is allowed.
+ * Both models, every birthGaussianMeasurementCountThreshold, RFSGPU_INHERIT_REFERENCE and _EAGER, any particle count up to
+ * rfsgpu_max_particles.  RFSGPU_ERR_UNSUPPORTED with the state untouched: a filter batch, a shard of an rfsgpu_group,
+ * RFSGPU_INHERIT_EXTERNAL, a handle on which FastSLAM updates have run.  RFSGPU_ERR_INVALID: a NULL handle, u01 outside [0, 1),
+ * n_z beyond RFSGPU_MAX_Z, a Victoria Park handle that has never been given a scan. */
+#define RFSGPU_RBPHD_WALK_LEVELS 4   /* inheritance levels >= 1 with launches of their own; deeper ones are the tail kernel's */
+int rfsgpu_rbphd_set_resampling(rfsgpu_filter *f, double eff_n, double eff_n_percent);
+int rfsgpu_rbphd_cycle_async(rfsgpu_filter *f, const double *z, int n_z, const double *scan, int n_scan, double u01);
+/* Resolving.  Cycles enqueued so far, those that found the gate open, those that resampled, and the deepest inheritance level any
+ * walk on the device has met.  Any pointer may be NULL. */
+int rfsgpu_rbphd_cycle_counts(rfsgpu_filter *f, int *n_cycles, int *n_gate_open, int *n_resamplings, int *max_level);
+/* Resolving.  The last cycle: whether its gate was open, whether it resampled, its N_eff (0 where the test did not run), plan[k]
+ * as rfsgpu_last_resample reports it (identity where nothing fired; max_n >= n_particles when plan is given); *walk_levels the
+ * deepest level of the last walk made on the device.  Any pointer may be NULL. */
+int rfsgpu_rbphd_last_cycle(rfsgpu_filter *f, int *gate_open, int *fired, double *n_eff, int *plan, int max_n, int *walk_levels);
+#ifdef RFSGPU_ENABLE_BENCH_API   /* [test]: 1 while cycles are pending (the ids and resampleOccured_ are the device's); reads nothing, waits for nothing */
+int rfsgpu_rbphd_cycle_pending(rfsgpu_filter *f);
+#endif /* RFSGPU_ENABLE_BENCH_API */
 
 /* ---- [sensor] every filter's scan drawn on the device, for batches of RB-PHD filters (outside the STABLE CORE) --------------------
  * generateMeasurements of the reference's 2-D simulator (src/rbphdslam2dSim.cpp:283-366) for one time step and every filter of a

@@ -166,6 +166,7 @@ ABI_SYMBOLS = [
     "create_batch_mh", "batch_fastslam_mh_cycle_async", "batch_fastslam_last_cycle", "batch_live_counts", "batch_mh_serve_metrics",
     "set_ground_truth", "error_log_create", "error_log_reset", "step_error_async", "error_log_read", "step_error", "get_map_estimate",
     "resample_async", "last_resample", "get_pose_covs",
+    "rbphd_set_resampling", "rbphd_cycle_async", "rbphd_cycle_counts", "rbphd_last_cycle", "rbphd_cycle_pending",
     "batch_set_sensor", "batch_sense_async", "batch_cycle_sensed_async", "batch_resample_sensed_async", "batch_last_scan", "batch_last_cycle_lds",
     "batch_set_truth", "batch_generate_truth", "batch_get_truth", "batch_run_truth_async",
     "batch_fastslam_serve_sensor", "batch_fastslam_cycle_sensed_async", "batch_fastslam_mh_cycle_sensed_async",
@@ -564,6 +565,44 @@ class CFilter:
         plan = np.empty(cap, dtype=np.int32)
         self._call("last_resample", C.byref(fired), C.byref(neff), C.byref(na), self._ptr(plan), C.c_int(cap))
         return {"fired": bool(fired.value), "n_eff": neff.value, "n_after": na.value, "plan": plan[:na.value].copy()}
+
+    # the whole RBPHDFilter::update on the device (rfsgpu.h [rbphd-cycle])
+    def rbphd_set_resampling(self, eff_n, eff_n_percent):
+        """ParticleFilter::resample's two N_eff thresholds for rbphd_cycle_async."""
+        self._call("rbphd_set_resampling", C.c_double(float(eff_n)), C.c_double(float(eff_n_percent)))
+
+    def rbphd_cycle_async(self, Z, u01, scan=None):
+        """One whole RBPHDFilter::update (the counters, the step, the gate, the resample-or-normalise tail) enqueued on the handle's
+        stream; nothing is read back.  u01: the draw a resampling would use; scan: this update's laser scan (Victoria Park model),
+        None leaves it as it is."""
+        Z = _f64(Z).reshape(-1, self.dz)
+        sp, ns = None, 0
+        if scan is not None:
+            scan = _f64(scan).reshape(-1)
+            sp, ns = self._ptr(scan), scan.size
+        self._call("rbphd_cycle_async", self._ptr(Z), C.c_int(Z.shape[0]), sp, C.c_int(ns), C.c_double(float(u01)))
+
+    def rbphd_cycle_counts(self):
+        """dict of n_cycles, n_gate_open, n_resamplings and max_level (the deepest inheritance level a walk on the device has met) of
+        the device-cycle route; resolves."""
+        a, b, c, d = C.c_int(), C.c_int(), C.c_int(), C.c_int()
+        self._call("rbphd_cycle_counts", C.byref(a), C.byref(b), C.byref(c), C.byref(d))
+        return {"n_cycles": a.value, "n_gate_open": b.value, "n_resamplings": c.value, "max_level": d.value}
+
+    def rbphd_last_cycle(self):
+        """What the last rbphd_cycle_async did (resolves): dict of gate_open, fired, n_eff, plan and walk_levels (the deepest level of
+        the last inheritance walk made on the device)."""
+        cap = self.max_particles
+        gate, fired, neff, wl = C.c_int(), C.c_int(), C.c_double(), C.c_int()
+        plan = np.empty(cap, dtype=np.int32)
+        self._call("rbphd_last_cycle", C.byref(gate), C.byref(fired), C.byref(neff), self._ptr(plan), C.c_int(cap), C.byref(wl))
+        return {"gate_open": bool(gate.value), "fired": bool(fired.value), "n_eff": neff.value, "plan": plan[:self.n].copy(), "walk_levels": wl.value}
+
+    def rbphd_cycle_pending(self):
+        """[test] whether cycles are pending (the ids and resampleOccured_ are the device's); waits for nothing."""
+        fn = self._fn("rbphd_cycle_pending")
+        fn.restype = C.c_int
+        return bool(fn(self._h))
 
     # birth-state inheritance after a resampling (rfsgpu.h: RFSGPU_INHERIT_*; include/RBPHDFilter.hpp:1005-1011)
     def set_birth_inheritance(self, mode):

@@ -203,6 +203,221 @@ struct CandLDS {
   }
 };
 
+// The birth step of particle i by one wavefront, candidate c on lane c (candidates + unused measurements <= 64 during the call).
+// nOld: the mixture's size before it.  predict_map_general_kernel runs it for its own particle, birth_walk_tail_kernel
+// (birth_walk.h) for the slots of one inheritance level after the other.
+template <int D>
+__device__ __forceinline__ void birth_step_lanes(const Buffers &B, const Params &P, const int cur, const int i, const int lane, const int nZprev, const int nOld) {
+  const int cap = B.cap;
+  // Candidate c of the particle lives on lane c (at most 64 here): loaded once, kept in registers, stored once.
+  // The reference's walk over the unused measurements and over the list stays serial where its order is observable
+  // (first matching candidate in list order, list order kept by erase, the ++end() wrap); what is per candidate --
+  // the support distance of a measurement to every candidate -- runs across the lanes.
+  int n = nOld;
+  int nc = B.candCount[i];
+  const unsigned nfov = (unsigned)B.nInFov[i];
+  PoseReg pr;
+  load_pose(B, P, i, pr);
+  bool fail = false, listFull = false;
+  int *supG = B.candSup + (size_t)i * RFSGPU_MAX_CANDIDATES, *chkG = B.candChk + (size_t)i * RFSGPU_MAX_CANDIDATES;
+  Cand<D> k;
+  for (int t = 0; t < 3; t++) k.x[t] = 0.0;
+  for (int t = 0; t < 6; t++) k.S[t] = 0.0;
+  int sup = 0, chk = 0;
+  if (lane < nc) { cand_load<D>(B, i, lane, k); sup = supG[lane]; chk = chkG[lane]; }
+  unsigned long long um = (nZprev > 0) ? B.unusedMask[i] : 0ull;
+  while (um) {  // back to front (:1013-1017)
+    const int zi = 63 - __builtin_clzll(um);
+    um &= ~(1ull << zi);
+    const double *z = B.Z + (size_t)D * zi;
+    double d2 = 1.0e300;
+    if (lane < nc) d2 = cand_support_md2<D>(P, pr, k, z);
+    const unsigned long long hit = __ballot(lane < nc && d2 <= P.birthSupportD2);
+    if (hit != 0ull) {                                   // the first candidate in list order that supports it
+      if (lane == __builtin_ctzll(hit)) { cand_correct<D>(P, pr, k, z); sup++; }
+    } else {
+      Cand<D> kn;
+      cand_inverse<D>(P, pr, z, kn);                     // (the same values on every lane)
+      if (P.birthCountThr == 1u || nfov <= P.birthCurThr) {
+        if (n < cap) { if (lane == 0) birth_write<D>(B, P, cur, i, n, kn); n++; }
+        else fail = true;
+      } else if (nc < 64) {   // (always: nc + unused <= 64 on this path)
+        if (lane == nc) { k = kn; sup = 1; chk = 0; }
+        nc++;
+      } else {
+        listFull = true;
+      }
+    }
+  }
+  // promotion / expiry (:1062-1080) with the ++end() wrap
+  int kk = 0;
+  while (kk < nc) {
+    if (lane == kk) chk++;
+    bool atEnd = false;
+    for (;;) {
+      const unsigned supk = (unsigned)__builtin_amdgcn_readlane(sup, kk), chkk = (unsigned)__builtin_amdgcn_readlane(chk, kk);
+      if (!(supk >= P.birthCountThr || chkk > P.birthCheckThr || nfov <= P.birthCurThr)) break;
+      if (supk >= P.birthCountThr || nfov <= P.birthCurThr) {
+        if (n < cap) { if (lane == kk) birth_write<D>(B, P, cur, i, n, k); n++; }
+        else fail = true;
+      }
+      {  // erase(it): the tail moves down one lane, list order kept
+        const int from = (lane >= kk && lane < 63) ? lane + 1 : lane;
+#pragma unroll
+        for (int t = 0; t < 3; t++) k.x[t] = __shfl(k.x[t], from, 64);
+#pragma unroll
+        for (int t = 0; t < 6; t++) k.S[t] = __shfl(k.S[t], from, 64);
+        sup = __shfl(sup, from, 64);
+        chk = __shfl(chk, from, 64);
+      }
+      nc--;
+      if (kk < nc) { if (lane == kk) chk++; }
+      else { atEnd = true; break; }
+    }
+    kk = atEnd ? 0 : kk + 1;
+  }
+  if (lane < nc) { cand_store<D>(B, i, lane, k); supG[lane] = sup; chkG[lane] = chk; }
+  if (lane == 0) {
+    B.unusedMask[i] = 0ull;
+    B.candCount[i] = nc;
+    B.count[i] = n;
+    if (fail) atomicOr(B.err, ERRBIT_CAPACITY);
+    if (listFull) atomicOr(B.err, ERRBIT_BIRTHLIST);
+  }
+
+}
+
+// The same walk on a list staged in LDS (<= RFSGPU_MAX_CANDIDATES), 64 candidates at a time; L: the wave's own image.
+template <int D>
+__device__ __forceinline__ void birth_step_lds(const Buffers &B, const Params &P, const int cur, const int i, const int lane, const int nZprev, CandLDS<D> &L) {
+  const int cap = B.cap;
+  // The particle's candidate list (<= RFSGPU_MAX_CANDIDATES) is staged in LDS in list order.  The reference's walk over
+  // the unused measurements and over the list stays serial where its order is observable (first matching candidate in
+  // list order, list order kept by erase, the ++end() wrap); what is per candidate -- the support distance of a
+  // measurement to every candidate -- runs across the lanes, 64 candidates at a time.  (Until r02 the list lived on the
+  // lanes, one candidate each, which capped it at 64: Victoria Park with artificial clutter and CheckCountThreshold 10
+  // keeps ~60 +- 20 candidates per particle, and about half of all seeds overflowed at 5000 particles.)
+  int n = B.count[i];
+  int nc = B.candCount[i];
+  const unsigned nfov = (unsigned)B.nInFov[i];
+  PoseReg pr;
+  load_pose(B, P, i, pr);
+  bool fail = false, listFull = false;
+  int *supG = B.candSup + (size_t)i * RFSGPU_MAX_CANDIDATES, *chkG = B.candChk + (size_t)i * RFSGPU_MAX_CANDIDATES;
+  for (int c = lane; c < nc; c += 64) {
+    Cand<D> k;
+    for (int t = 0; t < 3; t++) k.x[t] = 0.0;
+    for (int t = 0; t < 6; t++) k.S[t] = 0.0;
+    cand_load<D>(B, i, c, k);
+    L.put(c, k);
+    L.sup[c] = supG[c];
+    L.chk[c] = chkG[c];
+  }
+  wave_sync();
+  unsigned long long um = (nZprev > 0) ? B.unusedMask[i] : 0ull;
+  while (um) {  // back to front (:1013-1017)
+    const int zi = 63 - __builtin_clzll(um);
+    um &= ~(1ull << zi);
+    const double *z = B.Z + (size_t)D * zi;
+    int first = -1;                                       // the first candidate in list order that supports it
+    for (int c0 = 0; c0 < nc && first < 0; c0 += 64) {
+      const int c = c0 + lane;
+      double d2 = 1.0e300;
+      if (c < nc) {
+        Cand<D> k;
+        for (int t = 0; t < 3; t++) k.x[t] = 0.0;
+        for (int t = 0; t < 6; t++) k.S[t] = 0.0;
+        L.get(c, k);
+        d2 = cand_support_md2<D>(P, pr, k, z);
+      }
+      const unsigned long long hit = __ballot(c < nc && d2 <= P.birthSupportD2);
+      if (hit != 0ull) first = c0 + __builtin_ctzll(hit);
+    }
+    if (first >= 0) {
+      if (lane == 0) {
+        Cand<D> k;
+        for (int t = 0; t < 3; t++) k.x[t] = 0.0;
+        for (int t = 0; t < 6; t++) k.S[t] = 0.0;
+        L.get(first, k);
+        cand_correct<D>(P, pr, k, z);
+        L.put(first, k);
+        L.sup[first]++;
+      }
+      wave_sync();
+    } else {
+      Cand<D> kn;
+      cand_inverse<D>(P, pr, z, kn);                     // (the same values on every lane)
+      if (P.birthCountThr == 1u || nfov <= P.birthCurThr) {
+        if (n < cap) { if (lane == 0) birth_write<D>(B, P, cur, i, n, kn); n++; }
+        else fail = true;
+      } else if (nc < RFSGPU_MAX_CANDIDATES) {
+        if (lane == 0) { L.put(nc, kn); L.sup[nc] = 1; L.chk[nc] = 0; }
+        nc++;
+        wave_sync();
+      } else {
+        listFull = true;
+      }
+    }
+  }
+  // promotion / expiry (:1062-1080) with the ++end() wrap
+  int kk = 0;
+  while (kk < nc) {
+    if (lane == 0) L.chk[kk]++;
+    wave_sync();
+    bool atEnd = false;
+    for (;;) {
+      const unsigned supk = (unsigned)L.sup[kk], chkk = (unsigned)L.chk[kk];
+      if (!(supk >= P.birthCountThr || chkk > P.birthCheckThr || nfov <= P.birthCurThr)) break;
+      if (supk >= P.birthCountThr || nfov <= P.birthCurThr) {
+        if (n < cap) {
+          if (lane == 0) {
+            Cand<D> k;
+            for (int t = 0; t < 3; t++) k.x[t] = 0.0;
+            for (int t = 0; t < 6; t++) k.S[t] = 0.0;
+            L.get(kk, k);
+            birth_write<D>(B, P, cur, i, n, k);
+          }
+          n++;
+        } else fail = true;
+      }
+      // erase(it): the tail moves down one place, list order kept (64 entries at a time, ascending: every lane reads its
+      // source before any lane of the same step writes, and a step only writes places the earlier steps have read)
+      for (int c0 = kk; c0 < nc - 1; c0 += 64) {
+        const int c = c0 + lane;
+        const bool mv = c < nc - 1;
+        Cand<D> k;
+        for (int t = 0; t < 3; t++) k.x[t] = 0.0;
+        for (int t = 0; t < 6; t++) k.S[t] = 0.0;
+        int su = 0, ch = 0;
+        if (mv) { L.get(c + 1, k); su = L.sup[c + 1]; ch = L.chk[c + 1]; }
+        wave_sync();
+        if (mv) { L.put(c, k); L.sup[c] = su; L.chk[c] = ch; }
+        wave_sync();
+      }
+      nc--;
+      if (kk < nc) { if (lane == 0) L.chk[kk]++; wave_sync(); }
+      else { atEnd = true; break; }
+    }
+    kk = atEnd ? 0 : kk + 1;
+  }
+  for (int c = lane; c < nc; c += 64) {
+    Cand<D> k;
+    for (int t = 0; t < 3; t++) k.x[t] = 0.0;
+    for (int t = 0; t < 6; t++) k.S[t] = 0.0;
+    L.get(c, k);
+    cand_store<D>(B, i, c, k);
+    supG[c] = L.sup[c];
+    chkG[c] = L.chk[c];
+  }
+  if (lane == 0) {
+    B.unusedMask[i] = 0ull;
+    B.candCount[i] = nc;
+    B.count[i] = n;
+    if (fail) atomicOr(B.err, ERRBIT_CAPACITY);
+    if (listFull) atomicOr(B.err, ERRBIT_BIRTHLIST);
+  }
+}
+
 // Two kernels share the birth step.  predict_map_general_kernel: one wavefront per particle, candidate c on lane c -- the fast form,
 // for every particle whose list stays within the 64 lanes during the call (candidates + unused measurements <= 64: almost all of
 // them); it also does the static step of EVERY particle.  predict_map_long_kernel: the same walk on a list staged in LDS
@@ -220,83 +435,7 @@ __global__ __launch_bounds__(WPB * 64) void predict_map_general_kernel(Buffers B
   // A list that may outgrow the lanes during this call (candidates + unused measurements > 64) is left to predict_map_long_kernel,
   // which the host launches right after this one; the static step below is done here for every particle.
   const bool longList = addBirth && (B.candCount[i] + ((nZprev > 0) ? __popcll(B.unusedMask[i]) : 0) > 64);
-  if (addBirth && !longList) {
-    // Candidate c of the particle lives on lane c (at most 64 here): loaded once, kept in registers, stored once.
-    // The reference's walk over the unused measurements and over the list stays serial where its order is observable
-    // (first matching candidate in list order, list order kept by erase, the ++end() wrap); what is per candidate --
-    // the support distance of a measurement to every candidate -- runs across the lanes.
-    int n = nOld;
-    int nc = B.candCount[i];
-    const unsigned nfov = (unsigned)B.nInFov[i];
-    PoseReg pr;
-    load_pose(B, P, i, pr);
-    bool fail = false, listFull = false;
-    int *supG = B.candSup + (size_t)i * RFSGPU_MAX_CANDIDATES, *chkG = B.candChk + (size_t)i * RFSGPU_MAX_CANDIDATES;
-    Cand<D> k;
-    for (int t = 0; t < 3; t++) k.x[t] = 0.0;
-    for (int t = 0; t < 6; t++) k.S[t] = 0.0;
-    int sup = 0, chk = 0;
-    if (lane < nc) { cand_load<D>(B, i, lane, k); sup = supG[lane]; chk = chkG[lane]; }
-    unsigned long long um = (nZprev > 0) ? B.unusedMask[i] : 0ull;
-    while (um) {  // back to front (:1013-1017)
-      const int zi = 63 - __builtin_clzll(um);
-      um &= ~(1ull << zi);
-      const double *z = B.Z + (size_t)D * zi;
-      double d2 = 1.0e300;
-      if (lane < nc) d2 = cand_support_md2<D>(P, pr, k, z);
-      const unsigned long long hit = __ballot(lane < nc && d2 <= P.birthSupportD2);
-      if (hit != 0ull) {                                   // the first candidate in list order that supports it
-        if (lane == __builtin_ctzll(hit)) { cand_correct<D>(P, pr, k, z); sup++; }
-      } else {
-        Cand<D> kn;
-        cand_inverse<D>(P, pr, z, kn);                     // (the same values on every lane)
-        if (P.birthCountThr == 1u || nfov <= P.birthCurThr) {
-          if (n < cap) { if (lane == 0) birth_write<D>(B, P, cur, i, n, kn); n++; }
-          else fail = true;
-        } else if (nc < 64) {   // (always: nc + unused <= 64 on this path)
-          if (lane == nc) { k = kn; sup = 1; chk = 0; }
-          nc++;
-        } else {
-          listFull = true;
-        }
-      }
-    }
-    // promotion / expiry (:1062-1080) with the ++end() wrap
-    int kk = 0;
-    while (kk < nc) {
-      if (lane == kk) chk++;
-      bool atEnd = false;
-      for (;;) {
-        const unsigned supk = (unsigned)__builtin_amdgcn_readlane(sup, kk), chkk = (unsigned)__builtin_amdgcn_readlane(chk, kk);
-        if (!(supk >= P.birthCountThr || chkk > P.birthCheckThr || nfov <= P.birthCurThr)) break;
-        if (supk >= P.birthCountThr || nfov <= P.birthCurThr) {
-          if (n < cap) { if (lane == kk) birth_write<D>(B, P, cur, i, n, k); n++; }
-          else fail = true;
-        }
-        {  // erase(it): the tail moves down one lane, list order kept
-          const int from = (lane >= kk && lane < 63) ? lane + 1 : lane;
-#pragma unroll
-          for (int t = 0; t < 3; t++) k.x[t] = __shfl(k.x[t], from, 64);
-#pragma unroll
-          for (int t = 0; t < 6; t++) k.S[t] = __shfl(k.S[t], from, 64);
-          sup = __shfl(sup, from, 64);
-          chk = __shfl(chk, from, 64);
-        }
-        nc--;
-        if (kk < nc) { if (lane == kk) chk++; }
-        else { atEnd = true; break; }
-      }
-      kk = atEnd ? 0 : kk + 1;
-    }
-    if (lane < nc) { cand_store<D>(B, i, lane, k); supG[lane] = sup; chkG[lane] = chk; }
-    if (lane == 0) {
-      B.unusedMask[i] = 0ull;
-      B.candCount[i] = nc;
-      B.count[i] = n;
-      if (fail) atomicOr(B.err, ERRBIT_CAPACITY);
-      if (listFull) atomicOr(B.err, ERRBIT_BIRTHLIST);
-    }
-  }
+  if (addBirth && !longList) birth_step_lanes<D>(B, P, cur, i, lane, nZprev, nOld);
   // staticStep on the pre-existing Gaussians
   if (!LV.doStatic) return;
   double *slab = B.slab[cur];
@@ -319,138 +458,9 @@ __global__ __launch_bounds__(WPB * 64) void predict_map_long_kernel(Buffers B, P
   const int i = __builtin_amdgcn_readfirstlane(blockIdx.x * WPB + wave);
   if (i >= B.N) return;
   if (!LV.mine(i)) return;
-  const int cap = B.cap;
-  const int nOld = B.count[i];
   // (only the particles predict_map_general_kernel left alone: candidates + unused measurements > one per lane)
   if (B.candCount[i] + ((nZprev > 0) ? __popcll(B.unusedMask[i]) : 0) <= 64) return;
-  {
-    // The particle's candidate list (<= RFSGPU_MAX_CANDIDATES) is staged in LDS in list order.  The reference's walk over
-    // the unused measurements and over the list stays serial where its order is observable (first matching candidate in
-    // list order, list order kept by erase, the ++end() wrap); what is per candidate -- the support distance of a
-    // measurement to every candidate -- runs across the lanes, 64 candidates at a time.  (Until r02 the list lived on the
-    // lanes, one candidate each, which capped it at 64: Victoria Park with artificial clutter and CheckCountThreshold 10
-    // keeps ~60 +- 20 candidates per particle, and about half of all seeds overflowed at 5000 particles.)
-    CandLDS<D> &L = sCand[wave];
-    int n = nOld;
-    int nc = B.candCount[i];
-    const unsigned nfov = (unsigned)B.nInFov[i];
-    PoseReg pr;
-    load_pose(B, P, i, pr);
-    bool fail = false, listFull = false;
-    int *supG = B.candSup + (size_t)i * RFSGPU_MAX_CANDIDATES, *chkG = B.candChk + (size_t)i * RFSGPU_MAX_CANDIDATES;
-    for (int c = lane; c < nc; c += 64) {
-      Cand<D> k;
-      for (int t = 0; t < 3; t++) k.x[t] = 0.0;
-      for (int t = 0; t < 6; t++) k.S[t] = 0.0;
-      cand_load<D>(B, i, c, k);
-      L.put(c, k);
-      L.sup[c] = supG[c];
-      L.chk[c] = chkG[c];
-    }
-    wave_sync();
-    unsigned long long um = (nZprev > 0) ? B.unusedMask[i] : 0ull;
-    while (um) {  // back to front (:1013-1017)
-      const int zi = 63 - __builtin_clzll(um);
-      um &= ~(1ull << zi);
-      const double *z = B.Z + (size_t)D * zi;
-      int first = -1;                                       // the first candidate in list order that supports it
-      for (int c0 = 0; c0 < nc && first < 0; c0 += 64) {
-        const int c = c0 + lane;
-        double d2 = 1.0e300;
-        if (c < nc) {
-          Cand<D> k;
-          for (int t = 0; t < 3; t++) k.x[t] = 0.0;
-          for (int t = 0; t < 6; t++) k.S[t] = 0.0;
-          L.get(c, k);
-          d2 = cand_support_md2<D>(P, pr, k, z);
-        }
-        const unsigned long long hit = __ballot(c < nc && d2 <= P.birthSupportD2);
-        if (hit != 0ull) first = c0 + __builtin_ctzll(hit);
-      }
-      if (first >= 0) {
-        if (lane == 0) {
-          Cand<D> k;
-          for (int t = 0; t < 3; t++) k.x[t] = 0.0;
-          for (int t = 0; t < 6; t++) k.S[t] = 0.0;
-          L.get(first, k);
-          cand_correct<D>(P, pr, k, z);
-          L.put(first, k);
-          L.sup[first]++;
-        }
-        wave_sync();
-      } else {
-        Cand<D> kn;
-        cand_inverse<D>(P, pr, z, kn);                     // (the same values on every lane)
-        if (P.birthCountThr == 1u || nfov <= P.birthCurThr) {
-          if (n < cap) { if (lane == 0) birth_write<D>(B, P, cur, i, n, kn); n++; }
-          else fail = true;
-        } else if (nc < RFSGPU_MAX_CANDIDATES) {
-          if (lane == 0) { L.put(nc, kn); L.sup[nc] = 1; L.chk[nc] = 0; }
-          nc++;
-          wave_sync();
-        } else {
-          listFull = true;
-        }
-      }
-    }
-    // promotion / expiry (:1062-1080) with the ++end() wrap
-    int kk = 0;
-    while (kk < nc) {
-      if (lane == 0) L.chk[kk]++;
-      wave_sync();
-      bool atEnd = false;
-      for (;;) {
-        const unsigned supk = (unsigned)L.sup[kk], chkk = (unsigned)L.chk[kk];
-        if (!(supk >= P.birthCountThr || chkk > P.birthCheckThr || nfov <= P.birthCurThr)) break;
-        if (supk >= P.birthCountThr || nfov <= P.birthCurThr) {
-          if (n < cap) {
-            if (lane == 0) {
-              Cand<D> k;
-              for (int t = 0; t < 3; t++) k.x[t] = 0.0;
-              for (int t = 0; t < 6; t++) k.S[t] = 0.0;
-              L.get(kk, k);
-              birth_write<D>(B, P, cur, i, n, k);
-            }
-            n++;
-          } else fail = true;
-        }
-        // erase(it): the tail moves down one place, list order kept (64 entries at a time, ascending: every lane reads its
-        // source before any lane of the same step writes, and a step only writes places the earlier steps have read)
-        for (int c0 = kk; c0 < nc - 1; c0 += 64) {
-          const int c = c0 + lane;
-          const bool mv = c < nc - 1;
-          Cand<D> k;
-          for (int t = 0; t < 3; t++) k.x[t] = 0.0;
-          for (int t = 0; t < 6; t++) k.S[t] = 0.0;
-          int su = 0, ch = 0;
-          if (mv) { L.get(c + 1, k); su = L.sup[c + 1]; ch = L.chk[c + 1]; }
-          wave_sync();
-          if (mv) { L.put(c, k); L.sup[c] = su; L.chk[c] = ch; }
-          wave_sync();
-        }
-        nc--;
-        if (kk < nc) { if (lane == 0) L.chk[kk]++; wave_sync(); }
-        else { atEnd = true; break; }
-      }
-      kk = atEnd ? 0 : kk + 1;
-    }
-    for (int c = lane; c < nc; c += 64) {
-      Cand<D> k;
-      for (int t = 0; t < 3; t++) k.x[t] = 0.0;
-      for (int t = 0; t < 6; t++) k.S[t] = 0.0;
-      L.get(c, k);
-      cand_store<D>(B, i, c, k);
-      supG[c] = L.sup[c];
-      chkG[c] = L.chk[c];
-    }
-    if (lane == 0) {
-      B.unusedMask[i] = 0ull;
-      B.candCount[i] = nc;
-      B.count[i] = n;
-      if (fail) atomicOr(B.err, ERRBIT_CAPACITY);
-      if (listFull) atomicOr(B.err, ERRBIT_BIRTHLIST);
-    }
-  }
+  birth_step_lds<D>(B, P, cur, i, lane, nZprev, sCand[wave]);
 }
 
 // StaticProcessModel::staticStep (include/ProcessModel.hpp:195-208), Sigma += Q on every Gaussian, for a RUN of predicts in one

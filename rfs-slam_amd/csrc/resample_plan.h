@@ -20,7 +20,19 @@ enum ResampleWord {
   RSW_RENORM_N,     // the count when the test ran and did not fire and the caller asked for the second normalisation, else 0
   RSW_NO_RENORM,    // != 0: the second normalisation's two launches leave at once
   RSW_N_AFTER,      // the count after the call
-  RSW_WORDS = 16
+  // rfsgpu_rbphd_cycle_async (birth_walk.h): what RBPHDFilter::update keeps between calls, and what the cycles report
+  RCW_UPD,          // nUpdatesSinceResample_
+  RCW_MEAS,         // nMeasurementsSinceResample_
+  RCW_RESAMPLED,    // resampleOccured_
+  RCW_GATE,         // the last cycle: both gates were open (0 for a cycle without measurements)
+  RCW_BADNOW,       // the last cycle: resample_check_kernel's verdict (RSW_BAD also closes the plan kernel behind a closed gate)
+  RCW_BADSEEN,      // a cycle since the last resolving call met weights that cannot be resampled
+  RCW_NCYCLES,      // cycles so far | with an open gate | that resampled
+  RCW_NGATE,
+  RCW_NFIRED,
+  RCW_WALK_MAX,     // the deepest level of the last inheritance walk made on the device
+  RCW_MAXLEVEL,     // the deepest level of any walk so far
+  RSW_WORDS = 24
 };
 // One allocation; the head up to the end of ppid is what the host takes back when it resolves the call.
 // nEff | words | plan | pid | ppid || sidx | sampled | dupl | cum
@@ -101,8 +113,10 @@ __device__ __forceinline__ int rsp_exscan(int v, int *sw, int &total) {
 }
 
 // The weights are normalised (the launches before this one).  One workgroup.  Lane 0 carries N_eff's sum, the running sum of the
-// weights and the sample points across the chunks, each a chain of additions in the reference's order and rounding (no fused
-// multiply-add); every lane searches sample points, and the two compactions -- the copies in sampling order, the un-sampled slots
+// weights and the sample points across the chunks, each a chain in the reference's order.  The running sum and the sample points are
+// plain additions in the reference's rounding; N_eff's sum is NOT: the compiler contracts __dadd_rn(ss, __dmul_rn(v, v)) into one
+// fused multiply-add per particle (v_fmac_f64 in the code object), so it carries one rounding per particle where the reference
+// rounds the square first -- N_eff agrees with the reference's to rounding, not bit for bit; every lane searches sample points, and the two compactions -- the copies in sampling order, the un-sampled slots
 // ascending -- are scans over chunks of RSP_CHUNK slots whose totals carry into the next chunk.  The plan for nOut samples out of n
 // (cases 1-4 of ParticleFilter.hpp:459-478) is fs_resample_shrink_body's: a sampled slot below nOut keeps its particle; every other
 // sample -- a repeat, or a first sample of a slot at or beyond nOut -- is copied, in sampling order, into the un-sampled slots in

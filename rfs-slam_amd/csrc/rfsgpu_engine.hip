@@ -34,6 +34,7 @@
 #include "batch_truth.h"
 #include "fastslam_sensed.h"
 #include "resample_plan.h"
+#include "birth_walk.h"
 
 namespace {
 
@@ -159,6 +160,15 @@ struct rfsgpu_filter {
   int rsFired = 0, rsNAfter = 0;      // the last call, as resolved
   double rsNEff = 0.0;
   std::vector<int> rsPlan;
+  // rfsgpu_rbphd_cycle_async (birth_walk.h): RBPHDFilter::update's counters, gate and resampling on the device, in words of rsBlock
+  bool rcPending = false;             // cycles are enqueued: the ids and resampleOccured are behind the device (the count never changes)
+  bool rcHave = false;                // a cycle has run: the host route of the resampling is closed on this handle
+  bool rcLastEmpty = false;           // the last enqueued cycle had no measurements
+  double rcEffN = -1.0, rcEffNPercent = -1.0;   // rfsgpu_rbphd_set_resampling (negative: n_particles / 4 and 1 / 4)
+  int rcGate = 0, rcFired = 0, rcWalkMax = 0;   // the last cycle and the last walk, as resolved
+  double rcNEff = 0.0;
+  std::vector<int> rcPlan;
+  int rcCounts[4] = {0, 0, 0, 0};     // cycles | with an open gate | that resampled | the deepest inheritance level of a walk
   // birth-state inheritance after a resampling (rfsgpu_set_birth_inheritance; RBPHDFilter.hpp:1005-1011)
   int inheritMode = RFSGPU_INHERIT_REFERENCE;
   std::vector<int> pid, ppid;         // Particle::id_ / idParent_ of the particle in each slot (ParticleFilter.hpp:446-479)
@@ -303,9 +313,10 @@ struct rfsgpu_filter {
 // (a handle whose particle count is still on the device -- rfsgpu_fastslam_cycle_async -- takes it over first: every entry point
 //  that reads or sizes by N starts here)
 static int mhc_resolve(rfsgpu_filter *f);
+static inline bool rc_only_pending(const rfsgpu_filter *f) { return f->rcPending && !f->mhcStashedRc; }   // (never pending next to a FastSLAM cycle or rfsgpu_resample_async)
 #define CHECK_HANDLE(f)                                                       \
   if (!(f)) return RFSGPU_ERR_INVALID;                                        \
-  if ((f)->mhcPending || (f)->mhcStashedRc || (f)->mhbPending || (f)->rsPending) { \
+  if ((f)->mhcPending || (f)->mhcStashedRc || (f)->mhbPending || (f)->rsPending || (f)->rcPending) { \
     const int rcMhc_ = mhc_resolve(f);                                        \
     if (rcMhc_ != RFSGPU_OK) return rcMhc_;                                   \
   }
@@ -313,7 +324,7 @@ static int mhc_resolve(rfsgpu_filter *f);
 // rfsgpu_resample_async that keeps the particle count they enqueue without waiting for it (one that may shrink the set is resolved)
 #define CHECK_HANDLE_ENQ(f)                                                   \
   if (!(f)) return RFSGPU_ERR_INVALID;                                        \
-  if ((f)->mhcPending || (f)->mhcStashedRc || (f)->mhbPending || ((f)->rsPending && (f)->rsShrink)) { \
+  if ((f)->mhcPending || (f)->mhcStashedRc || (f)->mhbPending || ((f)->rsPending && (f)->rsShrink) || (f)->rcPending) { \
     const int rcMhc_ = mhc_resolve(f);                                        \
     if (rcMhc_ != RFSGPU_OK) return rcMhc_;                                   \
   }
@@ -327,7 +338,13 @@ static int mhc_resolve(rfsgpu_filter *f);
 #define CHECK_HANDLE_BEHIND_CYCLE(f, behind)                                  \
   if (!(f)) return RFSGPU_ERR_INVALID;                                        \
   const bool behind = (f)->mhcPending && !(f)->mhcStashedRc && !(f)->mhbPending && !(f)->rsPending; \
-  if (!behind) { CHECK_HANDLE_ENQ(f); }
+  if (!behind && !rc_only_pending(f)) { CHECK_HANDLE_ENQ(f); }
+// ... and the calls that go behind pending rfsgpu_rbphd_cycle_async cycles start here: the particle count is the host's on that route, so
+// what neither reads the ids nor resampleOccured_ (or reads them on the device: rfsgpu_predict_map_async(f, 1)) enqueues as it is.
+// Otherwise as CHECK_HANDLE.
+#define CHECK_HANDLE_BEHIND_RBPHD(f)                                          \
+  if (!(f)) return RFSGPU_ERR_INVALID;                                        \
+  if (!rc_only_pending(f)) { CHECK_HANDLE(f); }
 
 static int fail(rfsgpu_filter *f, int code, const char *msg) {
   f->err = msg;
@@ -823,7 +840,7 @@ int rfsgpu_set_kf_config(rfsgpu_filter *f, const rfsgpu_kf_config *c) {
   return RFSGPU_OK;
 }
 int rfsgpu_set_lmk_process_noise(rfsgpu_filter *f, const double *Q) {
-  CHECK_HANDLE(f);
+  CHECK_HANDLE_BEHIND_RBPHD(f);     // (the noise travels by value with each launch)
   if (!Q) return RFSGPU_ERR_INVALID;
   memcpy(f->Qlm, Q, (size_t)f->D * f->D * sizeof(double));
   rebuild_params(f);
@@ -1903,12 +1920,53 @@ static void ensure_ids(rfsgpu_filter *f) {
   while ((int)f->pid.size() < f->Ncap) { f->pid.push_back((int)f->pid.size()); f->ppid.push_back((int)f->ppid.size()); }
 }
 
+// the level and parent arrays and the staging area of birth_inherit_kernel<0/1>
+static int inherit_buffers(rfsgpu_filter *f) {
+  if (!f->dInhLevel) HIPCHK(hipMalloc(&f->dInhLevel, (size_t)f->Ncap * sizeof(int)));
+  {  // every buffer under its own guard: a failed allocation leaves the others usable and is retried by the next call
+    const size_t nc = (size_t)f->Ncap * RFSGPU_MAX_CANDIDATES;
+    if (!f->dInhParent) HIPCHK(hipMalloc(&f->dInhParent, (size_t)f->Ncap * sizeof(int)));
+    if (!f->inhTmp.unused) HIPCHK(hipMalloc(&f->inhTmp.unused, (size_t)f->Ncap * sizeof(unsigned long long)));
+    if (!f->inhTmp.count) HIPCHK(hipMalloc(&f->inhTmp.count, (size_t)f->Ncap * sizeof(int)));
+    if (!f->inhTmp.sup) HIPCHK(hipMalloc(&f->inhTmp.sup, nc * sizeof(int)));
+    if (!f->inhTmp.chk) HIPCHK(hipMalloc(&f->inhTmp.chk, nc * sizeof(int)));
+    if (!f->inhTmp.mean) HIPCHK(hipMalloc(&f->inhTmp.mean, nc * 3 * sizeof(double)));
+    if (!f->inhTmp.cov) HIPCHK(hipMalloc(&f->inhTmp.cov, nc * 6 * sizeof(double)));
+  }
+  return RFSGPU_OK;
+}
+// The same predict behind pending rfsgpu_rbphd_cycle_async cycles: the ids and resampleOccured_ are the device's, so the levels are
+// computed there (birth_walk.h) and the launches cannot depend on them: the staging pair and level 0 as above, a fixed
+// RFSGPU_RBPHD_WALK_LEVELS of (copy, birth) pairs that find no slot of theirs where the walk is shallower, and one workgroup that
+// finishes whatever lies deeper.  Nothing is read back.
+static int predict_walk_device(rfsgpu_filter *f) {
+  { const int rcb = inherit_buffers(f); if (rcb != RFSGPU_OK) return rcb; }
+  const int N = f->N;
+  const ResampleState &S = f->rs;
+  HIPCHK(hipMemsetAsync(S.w + RCW_WALK_MAX, 0, sizeof(int), f->stream));
+  birth_walk_levels_kernel<<<(N + 255) / 256, 256, 0, f->stream>>>(S, N, 1, f->dInhParent, f->dInhLevel);
+  birth_inherit_kernel<0><<<N, 128, 0, f->stream>>>(f->B, f->inhTmp, f->dInhParent, f->dInhLevel, 0);
+  birth_inherit_kernel<1><<<N, 128, 0, f->stream>>>(f->B, f->inhTmp, f->dInhParent, f->dInhLevel, 0);
+  launch_predict_kernels(f, 1, BirthLevel{f->dInhLevel, 0, 1});
+  for (int L = 1; L <= RFSGPU_RBPHD_WALK_LEVELS; L++) {
+    birth_inherit_kernel<2><<<N, 128, 0, f->stream>>>(f->B, f->inhTmp, f->dInhParent, f->dInhLevel, L);
+    launch_predict_kernels(f, 1, BirthLevel{f->dInhLevel, L, 0});
+  }
+  const int first = RFSGPU_RBPHD_WALK_LEVELS + 1;
+  if (f->D == 3) birth_walk_tail_kernel<3, false><<<1, BIRTH_TAIL_WAVES * 64, 0, f->stream>>>(f->B, f->P, f->cur, f->nZ, S, f->dInhParent, f->dInhLevel, first);
+  else if (f->cfg.birthGaussianMeasurementCountThreshold != 1u) birth_walk_tail_kernel<2, false><<<1, BIRTH_TAIL_WAVES * 64, 0, f->stream>>>(f->B, f->P, f->cur, f->nZ, S, f->dInhParent, f->dInhLevel, first);
+  else birth_walk_tail_kernel<2, true><<<1, BIRTH_TAIL_WAVES * 64, 0, f->stream>>>(f->B, f->P, f->cur, f->nZ, S, f->dInhParent, f->dInhLevel, first);
+  f->candUsed = f->candUsed || f->D == 3 || f->cfg.birthGaussianMeasurementCountThreshold != 1u;
+  return RFSGPU_OK;
+}
+
 // RBPHDFilter::predict's map part.  In the predicts that follow a resampling (resampleOccured_, RFSGPU_INHERIT_REFERENCE) the
 // reference's slot-ordered lazy copy of unused_measurements_ / birthGaussians_ (RBPHDFilter.hpp:1005-1011) precedes each slot's
 // birth step: see birth_inherit_kernel (birth.h) for how the walk is cut into levels.
 static int predict_launch(rfsgpu_filter *f, int add_birth) {
   const BirthLevel all{nullptr, 0, 1};
-  if (!(add_birth && f->resampleOccured && f->inheritMode == RFSGPU_INHERIT_REFERENCE && !f->fastSlamHandle)) {
+  if (add_birth && rc_only_pending(f) && f->inheritMode == RFSGPU_INHERIT_REFERENCE && !f->fastSlamHandle) return predict_walk_device(f);
+  if (!(add_birth && f->resampleOccured && f->inheritMode == RFSGPU_INHERIT_REFERENCE && !f->fastSlamHandle) || rc_only_pending(f)) {
     launch_predict_kernels(f, add_birth, all);
     return RFSGPU_OK;
   }
@@ -1927,17 +1985,7 @@ static int predict_launch(rfsgpu_filter *f, int add_birth) {
     if (f->hInhLevel[i] > maxLevel) maxLevel = f->hInhLevel[i];
   }
   if (!any) { launch_predict_kernels(f, add_birth, all); return RFSGPU_OK; }
-  if (!f->dInhLevel) HIPCHK(hipMalloc(&f->dInhLevel, (size_t)f->Ncap * sizeof(int)));
-  {  // every buffer under its own guard: a failed allocation leaves the others usable and is retried by the next call
-    const size_t nc = (size_t)f->Ncap * RFSGPU_MAX_CANDIDATES;
-    if (!f->dInhParent) HIPCHK(hipMalloc(&f->dInhParent, (size_t)f->Ncap * sizeof(int)));
-    if (!f->inhTmp.unused) HIPCHK(hipMalloc(&f->inhTmp.unused, (size_t)f->Ncap * sizeof(unsigned long long)));
-    if (!f->inhTmp.count) HIPCHK(hipMalloc(&f->inhTmp.count, (size_t)f->Ncap * sizeof(int)));
-    if (!f->inhTmp.sup) HIPCHK(hipMalloc(&f->inhTmp.sup, nc * sizeof(int)));
-    if (!f->inhTmp.chk) HIPCHK(hipMalloc(&f->inhTmp.chk, nc * sizeof(int)));
-    if (!f->inhTmp.mean) HIPCHK(hipMalloc(&f->inhTmp.mean, nc * 3 * sizeof(double)));
-    if (!f->inhTmp.cov) HIPCHK(hipMalloc(&f->inhTmp.cov, nc * 6 * sizeof(double)));
-  }
+  { const int rcb = inherit_buffers(f); if (rcb != RFSGPU_OK) return rcb; }
   // (pageable host vectors: hipMemcpyAsync from them returns after the copy has been staged, so they may be reused at once)
   HIPCHK(hipMemcpyAsync(f->dInhParent, f->hInhParent.data(), (size_t)N * sizeof(int), hipMemcpyHostToDevice, f->stream));
   HIPCHK(hipMemcpyAsync(f->dInhLevel, f->hInhLevel.data(), (size_t)N * sizeof(int), hipMemcpyHostToDevice, f->stream));
@@ -1993,9 +2041,10 @@ int rfsgpu_predict_map(rfsgpu_filter *f, int add_birth) {
 
 // RBPHDFilter::predict's map part without the error-word readback: stream-ordered, errors surface at the next synchronising call.
 int rfsgpu_predict_map_async(rfsgpu_filter *f, int add_birth) {
-  if (add_birth) { CHECK_HANDLE(f); } else { CHECK_HANDLE_ENQ(f); }   // (the births read the ids and resampleOccured)
+  if (f && rc_only_pending(f)) { }                                    // behind pending RB-PHD cycles the births walk the ids on the device (predict_walk_device)
+  else if (add_birth) { CHECK_HANDLE(f); } else { CHECK_HANDLE_ENQ(f); }   // (the births read the ids and resampleOccured)
   REFUSE_ON_BATCH(f, "rfsgpu_predict_map_async");
-  if (add_birth && f->resampleOccured && f->inheritMode == RFSGPU_INHERIT_EXTERNAL && !f->externalAck)
+  if (add_birth && !f->rcPending && f->resampleOccured && f->inheritMode == RFSGPU_INHERIT_EXTERNAL && !f->externalAck)
     return fail(f, RFSGPU_ERR_INVALID, "predict_map with births after a resampling in RFSGPU_INHERIT_EXTERNAL mode, but the host has not applied the "
                 "inheritance rule (rfsgpu_set_unused_masks, rfsgpu_predict_map_level, or rfsgpu_set_birth_inheritance(EXTERNAL) again to acknowledge): "
                 "go through the multi-GPU host's own predict (ShardedRBPHDFilter.predict_map / rfsgpu_group_predict_map)");
@@ -2202,6 +2251,7 @@ int rfsgpu_resample_apply(rfsgpu_filter *f, const int *src_slot) { return f ? rf
 int rfsgpu_resample_apply_n(rfsgpu_filter *f, const int *src_slot, int n_out) {
   CHECK_HANDLE(f);
   REFUSE_ON_BATCH(f, "rfsgpu_resample_apply");
+  if (f->rcHave) return fail(f, RFSGPU_ERR_UNSUPPORTED, "resample_apply: this handle runs rfsgpu_rbphd_cycle_async, which resamples inside the cycle and keeps the ids and the counters of its gate on the device");
   if (!src_slot || n_out < 1 || n_out > f->N) return RFSGPU_ERR_INVALID;
   const int nIn = f->N;
   for (int k = 0; k < n_out; k++) {
@@ -2305,7 +2355,7 @@ int rfsgpu_set_particle_ids(rfsgpu_filter *f, const int *id, const int *parent_i
   return RFSGPU_OK;
 }
 int rfsgpu_resample_occured(const rfsgpu_filter *f) {
-  if (f && f->rsPending) {  // the decision is on the device: take it over; an error goes to the next call that returns a status
+  if (f && (f->rsPending || f->rcPending)) {  // the decision is on the device: take it over; an error goes to the next call that returns a status
     rfsgpu_filter *g = const_cast<rfsgpu_filter *>(f);
     const int rc = mhc_resolve(g);
     if (rc != RFSGPU_OK) g->mhcStashedRc = rc;
@@ -2729,10 +2779,12 @@ int rfsgpu_particle_parents(rfsgpu_filter *f, int *parent, int max_n) {
 // overflow abandoned did not prune, so the slab flips the host made for them are taken back.
 static int mhb_resolve(rfsgpu_filter *f);
 static int rs_resolve(rfsgpu_filter *f);
+static int rc_resolve(rfsgpu_filter *f);
 static int mhc_resolve(rfsgpu_filter *f) {
   if (f->mhbPending) return mhb_resolve(f);     // (a batch of multi-hypothesis filters: its own blocks)
   if (f->mhcStashedRc) { const int rc = f->mhcStashedRc; f->mhcStashedRc = 0; return rc; }   // (f->err still holds its message)
   if (f->rsPending) return rs_resolve(f);       // (rfsgpu_resample_async: never pending next to a cycle)
+  if (f->rcPending) return rc_resolve(f);       // (rfsgpu_rbphd_cycle_async: an RB-PHD handle, no FastSLAM cycle beside it)
   if (!f->mhcPending) return RFSGPU_OK;
   f->mhcPending = false;
   hipSetDevice(f->device);
@@ -2821,24 +2873,19 @@ static int rs_resolve(rfsgpu_filter *f) {
   f->timing.particleResample_cpu += now_ns() - t0;
   return rc;                                // (the bookkeeping above is done either way: the device did resample)
 }
-int rfsgpu_resample_async(rfsgpu_filter *f, double eff_n, double eff_n_percent, double u01, int n_out, int force, int renormalize) {
-  CHECK_HANDLE(f);
-  REFUSE_ON_BATCH(f, "rfsgpu_resample_async (use rfsgpu_batch_resample_async)");
-  if (f->groupShard) return fail(f, RFSGPU_ERR_UNSUPPORTED, "resample_async: not available on a shard of an rfsgpu_group (the resampling is global: rfsgpu_group_resample)");
-  if (f->mhcHave) return fail(f, RFSGPU_ERR_UNSUPPORTED, "resample_async: this handle runs rfsgpu_fastslam_cycle_async, which resamples inside the cycle and keeps the ids in its own block");
-  if (!(u01 >= 0.0 && u01 < 1.0)) return fail(f, RFSGPU_ERR_INVALID, "resample_async: u01 must lie in [0, 1)");
-  if (n_out < 0) return fail(f, RFSGPU_ERR_INVALID, "resample_async: negative n_out");
-  hipSetDevice(f->device);
-  const long long t0 = now_ns();
-  const int N = f->N, Ncap = f->Ncap;
+// The ResampleState block and its pinned landing buffer (allocated on first use).  upload: the ids go up when the host has changed them
+// since the device last held them (the first call, rfsgpu_resample_apply, rfsgpu_set_particle_ids, ...) -- every earlier call has been
+// resolved then, so the pinned buffer's tail is free.
+static int rs_block_ready(rfsgpu_filter *f, bool upload) {
+  const int Ncap = f->Ncap;
   if (!f->hRsBlock) HIPCHK(hipHostMalloc(&f->hRsBlock, resample_state_head_bytes(Ncap) + (size_t)2 * Ncap * sizeof(int)));
   if (!f->rsBlock) {
     HIPCHK(hipMalloc(&f->rsBlock, resample_state_bytes(Ncap)));
     HIPCHK(hipMemsetAsync(f->rsBlock, 0, resample_state_bytes(Ncap), f->stream));
     resample_state_carve(f->rsBlock, Ncap, f->rs);
   }
+  if (!upload) return RFSGPU_OK;
   const ResampleState &S = f->rs;
-  // the ids go up when the host has changed them since the device last held them (the first call, rfsgpu_resample_apply, ...)
   ensure_ids(f);
   bool same = (int)f->rsIdsDev.size() == 2 * Ncap;
   if (same) same = !memcmp(f->rsIdsDev.data(), f->pid.data(), (size_t)Ncap * sizeof(int)) && !memcmp(f->rsIdsDev.data() + Ncap, f->ppid.data(), (size_t)Ncap * sizeof(int));
@@ -2846,10 +2893,25 @@ int rfsgpu_resample_async(rfsgpu_filter *f, double eff_n, double eff_n_percent, 
     f->rsIdsDev.resize((size_t)2 * Ncap);
     memcpy(f->rsIdsDev.data(), f->pid.data(), (size_t)Ncap * sizeof(int));
     memcpy(f->rsIdsDev.data() + Ncap, f->ppid.data(), (size_t)Ncap * sizeof(int));
-    int *up = reinterpret_cast<int *>(f->hRsBlock + resample_state_head_bytes(Ncap));     // (free: every earlier call has been resolved)
+    int *up = reinterpret_cast<int *>(f->hRsBlock + resample_state_head_bytes(Ncap));
     memcpy(up, f->rsIdsDev.data(), (size_t)2 * Ncap * sizeof(int));
     HIPCHK(hipMemcpyAsync(S.pid, up, (size_t)2 * Ncap * sizeof(int), hipMemcpyHostToDevice, f->stream));     // (pid and ppid lie back to back)
   }
+  return RFSGPU_OK;
+}
+int rfsgpu_resample_async(rfsgpu_filter *f, double eff_n, double eff_n_percent, double u01, int n_out, int force, int renormalize) {
+  CHECK_HANDLE(f);
+  REFUSE_ON_BATCH(f, "rfsgpu_resample_async (use rfsgpu_batch_resample_async)");
+  if (f->groupShard) return fail(f, RFSGPU_ERR_UNSUPPORTED, "resample_async: not available on a shard of an rfsgpu_group (the resampling is global: rfsgpu_group_resample)");
+  if (f->mhcHave) return fail(f, RFSGPU_ERR_UNSUPPORTED, "resample_async: this handle runs rfsgpu_fastslam_cycle_async, which resamples inside the cycle and keeps the ids in its own block");
+  if (f->rcHave) return fail(f, RFSGPU_ERR_UNSUPPORTED, "resample_async: this handle runs rfsgpu_rbphd_cycle_async, which resamples inside the cycle and keeps the ids and the counters of its gate on the device");
+  if (!(u01 >= 0.0 && u01 < 1.0)) return fail(f, RFSGPU_ERR_INVALID, "resample_async: u01 must lie in [0, 1)");
+  if (n_out < 0) return fail(f, RFSGPU_ERR_INVALID, "resample_async: negative n_out");
+  hipSetDevice(f->device);
+  const long long t0 = now_ns();
+  const int N = f->N;
+  { const int rcb = rs_block_ready(f, true); if (rcb != RFSGPU_OK) return rcb; }
+  const ResampleState &S = f->rs;
   ResampleArg A;
   A.effN = eff_n; A.effNPercent = eff_n_percent; A.u01 = u01;
   A.n = N; A.nOut = (n_out == 0 || n_out >= N) ? N : n_out;     // ParticleFilter.hpp:417-418
@@ -2883,6 +2945,133 @@ int rfsgpu_last_resample(rfsgpu_filter *f, int *fired, double *n_eff, int *n_aft
   if (plan) for (int k = 0; k < f->rsNAfter; k++) plan[k] = f->rsPlan[k];
   return RFSGPU_OK;
 }
+// ---- [rbphd-cycle] the whole RBPHDFilter::update on the device (birth_walk.h) ------------------------------------------------------
+// What the pending cycles left on the device comes back as rs_resolve brings a resampling back: one copy of the block's head, one
+// wait (through check_device_errors, so an error word raised by an earlier asynchronous call comes out of the resolving call).
+static int rc_resolve(rfsgpu_filter *f) {
+  if (!f->rcPending) return RFSGPU_OK;
+  f->rcPending = false;
+  hipSetDevice(f->device);
+  HIPCHK(hipMemcpyAsync(f->hRsBlock, f->rsBlock, resample_state_head_bytes(f->Ncap), hipMemcpyDeviceToHost, f->stream));
+  const int rc = check_device_errors(f);   // waits for the stream
+  harvest_async(f);
+  ResampleState H;
+  resample_state_carve(f->hRsBlock, f->Ncap, H);
+  const int n = f->N;
+  ensure_ids(f);
+  memcpy(f->pid.data(), H.pid, (size_t)n * sizeof(int));
+  memcpy(f->ppid.data(), H.ppid, (size_t)n * sizeof(int));
+  memcpy(f->rsIdsDev.data(), H.pid, (size_t)n * sizeof(int));
+  memcpy(f->rsIdsDev.data() + f->Ncap, H.ppid, (size_t)n * sizeof(int));
+  f->resampleOccured = H.w[RCW_RESAMPLED] != 0;
+  if (H.w[RCW_NFIRED] != f->rcCounts[2]) { f->externalAck = false; f->mhcIdsDirty = true; }
+  f->rcCounts[0] = H.w[RCW_NCYCLES]; f->rcCounts[1] = H.w[RCW_NGATE]; f->rcCounts[2] = H.w[RCW_NFIRED]; f->rcCounts[3] = H.w[RCW_MAXLEVEL];
+  f->rcWalkMax = H.w[RCW_WALK_MAX];
+  f->rcGate = f->rcLastEmpty ? 0 : H.w[RCW_GATE];
+  f->rcFired = f->rcLastEmpty ? 0 : H.w[RSW_FIRED];
+  f->rcNEff = f->rcLastEmpty ? 0.0 : H.nEff[0];
+  f->rcPlan.resize(n);
+  for (int k = 0; k < n; k++) f->rcPlan[k] = (f->rcLastEmpty || !f->rcFired) ? k : H.plan[k];
+  if (H.w[RCW_BADSEEN] != 0) {
+    HIPCHK(hipMemsetAsync(f->rs.w + RCW_BADSEEN, 0, sizeof(int), f->stream));
+    if (rc == RFSGPU_OK)
+      return fail(f, RFSGPU_ERR_INVALID, "rbphd_cycle: a particle weight was negative or not finite, or the weights did not sum to a positive number, behind an "
+                                         "update; that cycle normalised, moved and reset nothing");
+  }
+  return rc;
+}
+int rfsgpu_rbphd_set_resampling(rfsgpu_filter *f, double eff_n, double eff_n_percent) {
+  CHECK_HANDLE_HOST(f);
+  REFUSE_ON_BATCH(f, "rfsgpu_rbphd_set_resampling (use rfsgpu_batch_set_resampling)");
+  if (!(eff_n >= 0.0) || !(eff_n_percent >= 0.0)) return fail(f, RFSGPU_ERR_INVALID, "rbphd_set_resampling: thresholds must be non-negative");
+  f->rcEffN = eff_n;
+  f->rcEffNPercent = eff_n_percent;
+  return RFSGPU_OK;
+}
+int rfsgpu_rbphd_cycle_async(rfsgpu_filter *f, const double *z, int n_z, const double *scan, int n_scan, double u01) {
+  if (!f) return RFSGPU_ERR_INVALID;
+  if (f->mhcStashedRc || f->rsPending || f->mhcPending || f->mhbPending) { const int rc = mhc_resolve(f); if (rc != RFSGPU_OK) return rc; }
+  REFUSE_ON_BATCH(f, "rfsgpu_rbphd_cycle_async");
+  if (f->groupShard) return fail(f, RFSGPU_ERR_UNSUPPORTED, "rbphd_cycle: not available on a shard of an rfsgpu_group (the resampling is global: rfsgpu_group_resample)");
+  if (f->fastSlamHandle || f->mhcHave) return fail(f, RFSGPU_ERR_UNSUPPORTED, "rbphd_cycle: this handle runs FastSLAM updates (rfsgpu_fastslam_cycle_async is their device cycle)");
+  if (f->inheritMode == RFSGPU_INHERIT_EXTERNAL) return fail(f, RFSGPU_ERR_UNSUPPORTED, "rbphd_cycle: RFSGPU_INHERIT_EXTERNAL leaves the birth lists to a host that must learn of every resampling; the cycle tells nobody");
+  if (!(u01 >= 0.0 && u01 < 1.0)) return fail(f, RFSGPU_ERR_INVALID, "rbphd_cycle: u01 must lie in [0, 1)");
+  if (n_z < 0 || n_z > RFSGPU_MAX_Z) return fail(f, RFSGPU_ERR_INVALID, "at most RFSGPU_MAX_Z measurements per update");
+  if (n_z > 0 && !z) return fail(f, RFSGPU_ERR_INVALID, "null measurement buffer");
+  if (scan && (f->model != RFSGPU_MODEL_VICTORIAPARK_3D || n_scan < 2 || n_scan > RFSGPU_VP_MAX_SCAN))
+    return fail(f, RFSGPU_ERR_INVALID, "rbphd_cycle: a laser scan needs the Victoria Park model and 2..RFSGPU_VP_MAX_SCAN beams");
+  if (n_z > 0 && f->D == 3 && !scan && f->B.nScan < 2) return fail(f, RFSGPU_ERR_INVALID, "Victoria Park model: a laser scan must come with the first update or precede it (rfsgpu_set_laser_scan)");
+  hipSetDevice(f->device);
+  const int N = f->N;
+  { const int rcb = rs_block_ready(f, !f->rcPending); if (rcb != RFSGPU_OK) return rcb; }
+  const ResampleState &S = f->rs;
+  // (the step below clears the host's flag: what the device starts from is taken first)
+  const int resampledInit = f->rcPending ? -1 : (f->resampleOccured ? 1 : 0);
+  // The update is counted, and the handle goes over to the device route, only behind the last host step that can fail: a call that
+  // returns an error has counted nothing (a scan it carried may have been installed, as by rfsgpu_set_step_inputs_async).
+  auto counted = [&]() {
+    rbphd_count_kernel<<<1, 64, 0, f->stream>>>(S, resampledInit, n_z);
+    f->rcPending = true;
+    f->rcHave = true;
+    f->rcLastEmpty = n_z == 0;
+  };
+  if (scan) {     // through the pinned ring, as rfsgpu_set_step_inputs_async: no wait for the device; the clutter density goes by value in Params
+    double *h = nullptr;
+    int k = 0;
+    { const int rc = ring_acquire(f, f->stage, &h, &k); if (rc != RFSGPU_OK) return rc; }
+    { const int rc = push_scan(f, h + (size_t)f->Ncap * 22, scan, n_scan); if (rc != RFSGPU_OK) return rc; }
+    HIPCHK(hipEventRecord(f->stage.ev[k], f->stream));
+  }
+  if (n_z == 0) {                          // :451-452 (the scan, if one came, is installed: setLaserScan precedes the update)
+    counted();
+    HIPCHK(hipGetLastError());
+    return RFSGPU_OK;
+  }
+  { const int rc = cycle_impl(f, RFSGPU_CYCLE_NO_PREDICT, nullptr, nullptr, 0, nullptr, z, n_z, true, 0); if (rc != RFSGPU_OK) return rc; }
+  const long long t0 = now_ns();           // (the step's host time is booked by the step; what follows is the resampling's)
+  counted();
+  // the tail (:526-539): rfsgpu_resample_async's launches with renormalize = 1, the gate in front of the plan
+  ResampleArg A;
+  A.effN = f->rcEffN >= 0.0 ? f->rcEffN : (double)N / 4.0;
+  A.effNPercent = f->rcEffNPercent >= 0.0 ? f->rcEffNPercent : 0.25;
+  A.u01 = u01;
+  A.n = N; A.nOut = N; A.force = 0; A.renorm = 1;
+  const LiveCount first{S.w + RSW_N, S.w + RCW_BADNOW}, moved{S.w + RSW_GATHER_N, S.w + RSW_BAD}, renorm{S.w + RSW_RENORM_N, S.w + RSW_NO_RENORM};
+  weight_sums_kernel<<<1, 1024, 0, f->stream>>>(f->B.weight, N, f->dSums);
+  resample_check_kernel<<<1, RSP_THREADS, 0, f->stream>>>(f->B.weight, N, f->dSums, S);
+  rbphd_gate_kernel<<<1, 64, 0, f->stream>>>(S, (int)std::min<unsigned>(f->cfg.minUpdatesBeforeResample, 0x7fffffffu), (int)std::min<unsigned>(f->cfg.minMeasurementsBeforeResample, 0x7fffffffu));
+  normalize_kernel<<<(N + 255) / 256, 256, 0, f->stream>>>(f->B.weight, 0, 0.0, (const double *)f->dSums, 1, first);
+  resample_plan_kernel<<<1, RSP_THREADS, 0, f->stream>>>(f->B.weight, S, A);
+  resample_gather_kernel<<<N, 256, 0, f->stream>>>(f->B, f->cur, S.plan, f->P.poseCovStride, map_only(f), moved);
+  weight_sums_kernel<<<1, 1024, 0, f->stream>>>(f->B.weight, 0, f->dSums, renorm);
+  normalize_kernel<<<(N + 255) / 256, 256, 0, f->stream>>>(f->B.weight, 0, 0.0, (const double *)f->dSums, 1, renorm);
+  rbphd_fired_kernel<<<1, 64, 0, f->stream>>>(S);
+  HIPCHK(hipGetLastError());
+  const long long dtn = now_ns() - t0;
+  f->timing.particleResample_wall += dtn;
+  f->timing.particleResample_cpu += dtn;
+  return RFSGPU_OK;
+}
+int rfsgpu_rbphd_cycle_counts(rfsgpu_filter *f, int *n_cycles, int *n_gate_open, int *n_resamplings, int *max_level) {
+  CHECK_HANDLE(f);
+  if (n_cycles) *n_cycles = f->rcCounts[0];
+  if (n_gate_open) *n_gate_open = f->rcCounts[1];
+  if (n_resamplings) *n_resamplings = f->rcCounts[2];
+  if (max_level) *max_level = f->rcCounts[3];
+  return RFSGPU_OK;
+}
+int rfsgpu_rbphd_last_cycle(rfsgpu_filter *f, int *gate_open, int *fired, double *n_eff, int *plan, int max_n, int *walk_levels) {
+  CHECK_HANDLE(f);
+  if (!f->rcHave) return fail(f, RFSGPU_ERR_INVALID, "rbphd_last_cycle: no rfsgpu_rbphd_cycle_async has run on this handle");
+  if (plan && max_n < f->N) return fail(f, RFSGPU_ERR_INVALID, "rbphd_last_cycle: max_n is below the particle count");
+  if (gate_open) *gate_open = f->rcGate;
+  if (fired) *fired = f->rcFired;
+  if (n_eff) *n_eff = f->rcNEff;
+  if (walk_levels) *walk_levels = f->rcWalkMax;
+  if (plan) for (int k = 0; k < f->N && k < (int)f->rcPlan.size(); k++) plan[k] = f->rcPlan[k];
+  return RFSGPU_OK;
+}
+int rfsgpu_rbphd_cycle_pending(rfsgpu_filter *f) { return (f && f->rcPending) ? 1 : 0; }
 int rfsgpu_fastslam_set_resampling(rfsgpu_filter *f, double eff_n, double eff_n_percent) {
   CHECK_HANDLE_HOST(f);
   REFUSE_ON_BATCH(f, "rfsgpu_fastslam_set_resampling (use rfsgpu_batch_set_resampling)");

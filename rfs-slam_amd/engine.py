@@ -269,6 +269,26 @@ class RBPHDFilter(capi.CFilter):
         self.last_resample_plan = src
         return True
 
+    # RBPHDFilter::update as one rfsgpu_rbphd_cycle_async: the two counters, the gate and the resampling are the device's.
+    def cycle_on_device(self, Z, u01, scan=None, push_config=True):
+        """One whole update enqueued, nothing read back: u01 is the draw a resampling would use (made whether or not one happens:
+        the decision is the device's), scan this update's laser scan (Victoria Park model).  Cycles, static steps, Ackerman
+        propagations and predict_map_async -- births included -- may follow one another without a synchronisation; sync_cycle()
+        brings resampleOccured and last_resample_plan up to date.  push_config=False: the configuration and the thresholds were
+        pushed by an earlier call and have not changed."""
+        if push_config:
+            self.apply_config()
+            self.rbphd_set_resampling(self.effNParticles_t, self.effNParticles_t_percent)
+        self.rbphd_cycle_async(np.asarray(Z, dtype=np.float64).reshape(-1, self.dz), u01, scan=scan)
+
+    def sync_cycle(self):
+        """The results of the last cycle_on_device (resolves)."""
+        lc = self.rbphd_last_cycle()
+        self.resampleOccured = bool(self.resample_occured())
+        self.last_n_eff = lc["n_eff"]
+        self.last_resample_plan = lc["plan"] if lc["fired"] else None
+        return lc
+
 
 class FastSLAM(RBPHDFilter):
     """rfs::FastSLAM (include/FastSLAM.hpp) for the 2-D range-bearing model on the same engine: the handle's mixtures are

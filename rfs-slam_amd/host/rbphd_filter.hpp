@@ -410,7 +410,8 @@ class RBPHDFilter2d {
   }
   // ParticleFilter::resample(n, forceResample) (ParticleFilter.hpp:399-492).  nOut == 0 or > nParticles_ keeps the count; a
   // smaller nOut draws nOut samples from all particles and shrinks the set (FastSLAM::resampleWithMapCopy).
-  bool resample(unsigned nOut = 0, bool force = false, bool alreadyNormalized = false) {
+  // givenDraw: the uniform of the systematic plan when the caller has drawn it already (one draw per update, used or not).
+  bool resample(unsigned nOut = 0, bool force = false, bool alreadyNormalized = false, const double *givenDraw = nullptr) {
     flushMotion();
     if (!alreadyNormalized) normalizeWeights();
     pullWeights();
@@ -422,7 +423,7 @@ class RBPHDFilter2d {
       if (nEff > effNParticles_t_ && nEff / N > effNParticles_t_percent_) return false;
     }
     const int n = (nOut == 0 || (int)nOut > N) ? N : (int)nOut;
-    const double u01 = drand48();
+    const double u01 = givenDraw ? *givenDraw : drand48();
     unsigned idx = 0;
     const double interval = 1.0 / double(n);
     double sample_point = interval * u01;
@@ -627,6 +628,25 @@ class RBPHDFilterVP : public RBPHDFilter2d {
   void setDeviceMotion(bool on, unsigned long long seed = 0) { pullPoses(); devicePoses_ = on; motionSeed_ = seed; motionCall_ = 0; }
   LmkProcessModel3d *getLmkProcessModel() { return &lmk3_; }
   MeasurementModelVP *getMeasurementModel() { return &measVP_; }
+  // RBPHDFilter::update as one rfsgpu_rbphd_cycle_async (needs setDeviceMotion): the two gate counters, resampleOccured_ and the
+  // resampling are the device's, the scan rides with the call, one drand48() is taken per update with measurements whether or not
+  // it is used, and nothing is read until somebody asks (getParticleWeight, getParticlePose, resampleOccured, resampleCount).
+  // The configuration is pushed when the first call needs it and must not change afterwards (rfsgpu_set_model_victoriapark and
+  // rfsgpu_set_kf_config would wait for the cycles in flight); the landmark noise still goes with every birth predict.
+  void setDeviceCycle(bool on) {
+    if (on && !devicePoses_) throw std::runtime_error("setDeviceCycle: the poses must live on the device (setDeviceMotion)");
+    deviceCycle_ = on;
+  }
+  // The host-stop route of the same realisation: the update without normalisation, then the gate, the normalisation, N_eff in the
+  // arithmetic of resample_plan_kernel (slot order, one fused multiply-add per particle), the plan from this update's one draw
+  // and rfsgpu_resample_apply, or the second normalisation -- every decision on the host, the same kernels in the same order.
+  void setDrawEveryUpdate(bool on) { drawEveryUpdate_ = on; }
+  unsigned cycleResampleCount() {
+    if (!deviceCycle_) return resampleCount();
+    int nr = 0;
+    check(rfsgpu_rbphd_cycle_counts(h_, nullptr, nullptr, &nr, nullptr), "rbphd_cycle_counts");
+    return (unsigned)nr;
+  }
 
   // RBPHDFilter::predict(u, dT, useModelNoise = false, useInputNoise, birthGaussianCheck) (:415-442) with
   // ProcessModel::sample's input-noise branch (include/ProcessModel.hpp:126-150): every particle draws its own input.
@@ -634,7 +654,7 @@ class RBPHDFilterVP : public RBPHDFilter2d {
   void predict(const AckermanInput &u, double dT, bool /*useModelNoise*/, bool useInputNoise, bool birthGaussianCheck) {
     auto now = [] { return std::chrono::steady_clock::now(); };
     auto t0 = now();
-    pushConfigVP();
+    if (deviceCycle_) pushConfigOnce(); else pushConfigVP();
     auto t1 = now();
     // The device reads the poses in two places only: the map update, and the births of the first predict after an update --
     // and those are born at the poses the update just used, which are on the device already (update() pushed them, a
@@ -716,7 +736,22 @@ class RBPHDFilterVP : public RBPHDFilter2d {
     std::vector<Measurement3d> meas;
     meas.swap(Z);
     Z.clear();
+    if (deviceCycle_) {
+      pushConfigOnce();
+      flushMotion();
+      flushStatic();
+      std::vector<double> zc(3 * meas.size() + 3);
+      for (size_t k = 0; k < meas.size(); k++) std::memcpy(&zc[3 * k], meas[k].z, 3 * sizeof(double));
+      const bool scanNow = !meas.empty() && measVP_.scanDirty && !measVP_.scan.empty();
+      const double u01 = meas.empty() ? 0.0 : drand48();
+      check(rfsgpu_rbphd_cycle_async(h_, zc.data(), (int)meas.size(), scanNow ? measVP_.scan.data() : nullptr, scanNow ? (int)measVP_.scan.size() : 0, u01),
+            "rbphd_cycle_async");
+      if (scanNow) measVP_.scanDirty = false;
+      weightsStale_ = true;
+      return;
+    }
     if (meas.empty()) return;  // :450-452
+    if (drawEveryUpdate_) { updateHostStop(meas); return; }
     nMeasurementsSinceResample_ += (unsigned)meas.size();
     pushConfigVP();
     flushMotion();
@@ -760,6 +795,32 @@ class RBPHDFilterVP : public RBPHDFilter2d {
     return resample(0, true, /*alreadyNormalized=*/true);
   }
 
+  // (setDrawEveryUpdate) see there
+  void updateHostStop(const std::vector<Measurement3d> &meas) {
+    nMeasurementsSinceResample_ += (unsigned)meas.size();
+    pushConfigVP();
+    flushMotion();
+    pushInputsAsync();
+    flushStatic();
+    std::vector<double> z(3 * meas.size());
+    for (size_t k = 0; k < meas.size(); k++) std::memcpy(&z[3 * k], meas[k].z, 3 * sizeof(double));
+    const double u01 = drand48();
+    check(rfsgpu_cycle_async(h_, RFSGPU_CYCLE_NO_PREDICT, nullptr, nullptr, 0, nullptr, z.data(), (int)meas.size(), 0), "cycle_async");
+    resampleOccured_ = false;
+    const bool due = nUpdatesSinceResample_ >= (unsigned)config.minUpdatesBeforeResample_ &&
+                     nMeasurementsSinceResample_ >= (unsigned)config.minMeasurementsBeforeResample_;
+    normalizeWeights();
+    if (!due) return;
+    pullWeights();
+    double s2 = 0;
+    for (int i = 0; i < n_; i++) s2 = std::fma(weights_[i], weights_[i], s2);
+    const double nEff = 1.0 / s2;
+    if (nEff > effNParticles_t_ && nEff / n_ > effNParticles_t_percent_) { normalizeWeights(); return; }
+    resampleOccured_ = resample(0, true, /*alreadyNormalized=*/true, &u01);
+    nUpdatesSinceResample_ = 0;
+    nMeasurementsSinceResample_ = 0;
+  }
+
   bool getLandmark(int i, int m, double u[3], double S[9], double &w) {
     flushStatic();
     return rfsgpu_get_landmark(h_, i, m, u, S, &w) == RFSGPU_OK;
@@ -771,6 +832,16 @@ class RBPHDFilterVP : public RBPHDFilter2d {
     if (pendingStatic_.empty()) return;
     check(rfsgpu_static_steps_async(h_, (int)(pendingStatic_.size() / 9), pendingStatic_.data()), "static_steps");
     pendingStatic_.clear();
+  }
+  bool deviceCycle_ = false, drawEveryUpdate_ = false, configPushed_ = false;
+  void pushConfigOnce() {      // (device cycle) afterwards only the landmark noise moves, by a call that waits for nothing
+    if (!configPushed_) {
+      pushConfigVP();
+      check(rfsgpu_rbphd_set_resampling(h_, effNParticles_t_, effNParticles_t_percent_), "rbphd_set_resampling");
+      configPushed_ = true;
+    } else {
+      check(rfsgpu_set_lmk_process_noise(h_, lmk3_.Q), "set_lmk_process_noise");
+    }
   }
   MotionModel_Ackerman2d ackerman_;
   LmkProcessModel3d lmk3_;

@@ -8,7 +8,7 @@
 // the raw scan is the synthetic one SURVEY 8d prescribes: 361 beams at rangeLimitMax.
 //
 //   rbphdslam_vp -c cfg.xml [-d dataDir] [-n nParticles] [-m nMessages] [-e effNParticle] [-s seed] [-o outDir] [--device k] [--host-motion] [--repeat K]
-//                [--no-input-noise] [--no-clutter]
+//                [--no-input-noise] [--no-clutter] [--device-resample | --device-cycle | --draw-every-update]
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -48,7 +48,7 @@ int main(int argc, char **argv) {
   std::string cfgFile, dataDir, outDir;
   int nParticlesOverride = -1, nMsgOverride = -1, seed = 1, device = 0;
   double effNOverride = -1;
-  bool inputNoise = true, clutter = true, deviceMotion = true, deviceResample = false;
+  bool inputNoise = true, clutter = true, deviceMotion = true, deviceResample = false, deviceCycle = false, drawEveryUpdate = false;
   int repeat = 1;
   for (int a = 1; a < argc; a++) {
     std::string s = argv[a];
@@ -67,6 +67,11 @@ int main(int argc, char **argv) {
     // ParticleFilter::resample on the device (rfsgpu_resample_async): update() does not wait, the next predict with births does.  N_eff is
     // added in slot order there, not taken from the step's reduction: the last bits can differ from the host route's (rbphd_filter.hpp)
     else if (s == "--device-resample") deviceResample = true;
+    // the whole update as one rfsgpu_rbphd_cycle_async: counters, gate and resampling on the device, one drand48() per update with
+    // measurements, nothing read until the end of the run (the log files of -o read after every update)
+    else if (s == "--device-cycle") deviceCycle = true;
+    // the host-stop route of that realisation (one draw per update, N_eff added as the device adds it): writes the files of --device-cycle
+    else if (s == "--draw-every-update") drawEveryUpdate = true;
     else if (s == "--host-motion") deviceMotion = false;   // ParticleFilter::propagate on the host (the reference's shape) instead of the device kernel
   }
   Cfg c;
@@ -113,6 +118,9 @@ int main(int argc, char **argv) {
                                               c.d("config.process.AckermanModel.sensorOffset_x", 3.78), c.d("config.process.AckermanModel.sensorOffset_y", 0.50));
   filter.setDeviceMotion(deviceMotion, 0x9E3779B97F4A7C15ull * (unsigned long long)(seed + 1));
   filter.setDeviceResample(deviceResample);
+  if (deviceCycle && (!deviceMotion || deviceResample || drawEveryUpdate)) { std::fprintf(stderr, "--device-cycle goes with device motion and without --device-resample / --draw-every-update\n"); return 2; }
+  if (drawEveryUpdate && deviceResample) { std::fprintf(stderr, "--draw-every-update is the host-stop route: not with --device-resample\n"); return 2; }
+  filter.setDrawEveryUpdate(drawEveryUpdate);
   double R[9] = {0};
   for (int k = 0; k < 3; k++) R[4 * k] = varz[k] * zNoiseInfl;
   filter.getMeasurementModel()->setNoise(R, varza);
@@ -143,6 +151,7 @@ int main(int argc, char **argv) {
   filter.config.gaussianPruningThreshold_ = c.d("config.filter.prune.threshold", filter.config.birthGaussianWeight_);
   filter.setEffectiveParticleCountThreshold(effNOverride > 0 ? effNOverride : c.d("config.filter.resampling.effNParticle", (double)nParticles));
   filter.getMeasurementModel()->setLaserScan(syntheticScan);
+  filter.setDeviceCycle(deviceCycle);     // (behind the configuration: it is pushed once on this route)
 
   FILE *fPose = nullptr, *fLm = nullptr;
   if (!outDir.empty()) {
@@ -202,7 +211,7 @@ int main(int argc, char **argv) {
       filter.getMeasurementModel()->setLaserScan(syntheticScan);
       const bool any = !Z.empty();
       { const auto ta = now(); filter.update(Z); tUpdate += std::chrono::duration<double>(now() - ta).count(); }
-      if (any) { nLidar++; if (!deviceResample) nResample += filter.resampleOccured() ? 1 : 0; }   // (the device route is asked once, at the end: asking waits)
+      if (any) { nLidar++; if (!deviceResample && !deviceCycle) nResample += filter.resampleOccured() ? 1 : 0; }   // (the device route is asked once, at the end: asking waits)
       birthCheck = true;
       if (fPose || fLm) {
         int best = 0;
@@ -224,6 +233,7 @@ int main(int argc, char **argv) {
     t_km = m.t;
   }
   if (deviceResample) nResample = (int)filter.resampleCount();
+  if (deviceCycle) nResample = (int)filter.cycleResampleCount();
   const double wall = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
   if (fPose) std::fclose(fPose);
   if (fLm) std::fclose(fLm);

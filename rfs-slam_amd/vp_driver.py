@@ -16,6 +16,15 @@ FastSLAM options (filter="fastslam"):
                      nothing is read until the end of the run, or until sync().  sync_every_update reads each cycle's results.
   draw_every_update  one resampling draw per lidar update with measurements, used or not, so that the host-stop route and the
                      device cycle (which needs the draw before the decision exists) share a realisation.
+
+The RB-PHD filter (filter="rbphd") takes device_motion, device_cycle, draw_every_update and sync_every_update in the same sense:
+  device_motion      per run of messages the first predict with its births (predict_map_async, at the poses from before the run's
+                     propagation), the rest as one static_steps_async, then one propagate_ackerman_run_async.
+  device_cycle       every lidar message is one rfsgpu_rbphd_cycle_async that carries the scan: the two counters, the gate and the
+                     resampling are the device's, and the birth predict behind it walks the inheritance levels there.
+N_eff: the host-stop route takes 1 / np.sum(w * w); the device adds the squares in slot order with one fused multiply-add per
+particle (csrc/resample_plan.h).  The two agree to rounding, so a run whose N_eff comes within an ulp or so of a threshold could
+decide differently on the two routes; the runs the tests compare do not.
 """
 import numpy as np
 
@@ -60,6 +69,7 @@ class VictoriaParkRun:
         self.n_meas_since = 0
         self.n_resamples = 0
         self.n_lidar = 0
+        self.n_gate_closed = 0            # RB-PHD host-stop route: updates with measurements that found a gate closed
         self.n_init = self.n
         self.hyp = int(max_hypotheses)
         self.n_max = int(n_particles_max) if n_particles_max is not None else (3 * self.n if self.hyp > 1 else self.n)
@@ -70,8 +80,8 @@ class VictoriaParkRun:
         self.motion_seed, self.n_calls = int(motion_seed), 0
         self.n_grown_max, self.n_forced = self.n, 0
         self._run = []                    # (u, var, dt) of the predicts not yet enqueued (device_motion)
-        if (self.hyp > 1 or self.device_cycle or self.device_motion) and not self.fastslam:
-            raise ValueError("max_hypotheses, device_cycle and device_motion belong to filter='fastslam'")
+        if self.hyp > 1 and not self.fastslam:
+            raise ValueError("max_hypotheses belongs to filter='fastslam'")
         if self.fastslam and (self.hyp > 1 or self.device_cycle):
             cfg = f.get_fastslam_config()
             cfg.maxNDataAssocHypotheses = self.hyp
@@ -79,7 +89,15 @@ class VictoriaParkRun:
             cfg.minUpdatesBeforeResample = int(params["min_updates"])
             cfg.minMeasurementsBeforeResample = int(params["min_measurements"])
             f.set_fastslam_config(cfg)
-        if self.device_cycle:
+        if self.device_cycle and not self.fastslam:
+            cfg = f.get_filter_config()
+            cfg.minUpdatesBeforeResample = int(params["min_updates"])
+            cfg.minMeasurementsBeforeResample = int(params["min_measurements"])
+            f.set_filter_config(cfg)
+            if hasattr(f, "config"):
+                f.config = cfg
+            f.rbphd_set_resampling(self.eff_n, self.eff_n / self.n_init)
+        elif self.device_cycle:
             f.fastslam_set_resampling(self.eff_n, self.eff_n / self.n_init)
         if self.device_motion:
             f.set_poses(self.x, None)
@@ -87,7 +105,8 @@ class VictoriaParkRun:
     def _predict(self, u, dt, stationary, birth):
         f = self.f
         if self.device_motion:            # queued: the run goes to the device at the next lidar message (or at sync())
-            self._run.append((float(u[0]), float(u[1]), 0.0 if stationary else self.var[0], 0.0 if stationary else self.var[1], float(dt)))
+            self._run.append((float(u[0]), float(u[1]), 0.0 if stationary else self.var[0], 0.0 if stationary else self.var[1], float(dt),
+                              1.0 if (birth and not self.fastslam) else 0.0))
             return
         f.set_lmk_process_noise(np.diag([5e-4, 5e-4, 1e-4]) * dt * dt)   # varlm* x dt^2 (:497-500)
         f.set_poses(self.x, None)                                          # poses BEFORE propagation: birth uses them
@@ -107,7 +126,13 @@ class VictoriaParkRun:
         self._run = []
         a = ACKERMAN
         q = np.diag([5e-4, 5e-4, 1e-4])[None, :, :] * (r[:, 4] ** 2)[:, None, None]      # varlm* x dt^2 (:497-500)
-        self.f.static_steps_async(len(r), q)
+        if r[0, 5] != 0.0:                # RB-PHD: the run's first predict adds the births, at the poses the last update used
+            self.f.set_lmk_process_noise(q[0])
+            self.f.predict_map_async(True)
+            if len(r) > 1:
+                self.f.static_steps_async(len(r) - 1, q[1:])
+        else:
+            self.f.static_steps_async(len(r), q)
         self.f.propagate_ackerman_run_async(r[:, 0:2], r[:, 2:4], r[:, 4], (a["h"], a["l"], a["dx"], a["dy"]), self.motion_seed, self.n_calls)
         self.n_calls += len(r)
 
@@ -116,7 +141,9 @@ class VictoriaParkRun:
         self._flush_run()
         self.f.synchronize()
         self.n = self.f.n
-        if self.device_cycle and self.n_lidar:
+        if self.device_cycle and not self.fastslam:
+            self.n_resamples = self.f.rbphd_cycle_counts()["n_resamplings"]
+        elif self.device_cycle and self.n_lidar:
             self.n_resamples = self.f.fastslam_cycle_counts()[1]
         return self
 
@@ -179,6 +206,15 @@ class VictoriaParkRun:
                         Z.append(np.array([r, b, 1.0]))
                 Z = np.array(Z).reshape(-1, 3)[:60]
                 self._flush_run()
+                if self.device_cycle and not self.fastslam:     # one call per lidar message: counters, scan, step, gate, tail
+                    u01 = float(self.rng.uniform()) if len(Z) else 0.0
+                    f.rbphd_cycle_async(Z, u01, scan=self.scan)
+                    self.n_lidar += 1 if len(Z) else 0
+                    if self.sync_every_update and len(Z):
+                        f.rbphd_last_cycle()
+                    birth = True
+                    t_km = t_k
+                    continue
                 if self.device_cycle:
                     if not len(Z):        # an update without measurements is only counted (FastSLAM.hpp:399-402)
                         f.fastslam_cycle_full_async(Z, 0.0, self.n_init, predict=False, scan=self.scan)
@@ -199,9 +235,15 @@ class VictoriaParkRun:
                         f.update(Z)
                     self.n_lidar += 1
                     fired, tail_done = False, False
+                    draw = None
+                    if self.draw_every_update:        # taken whether or not it is used: the device cycle's realisation
+                        u01 = float(self.rng.uniform())
+                        draw = lambda: u01
                     if self.n_updates_since >= P["min_updates"] and self.n_meas_since >= P["min_measurements"]:
-                        fired = self._resample_device() if self.device_resample else self._resample()
+                        fired = self._resample_device(draw) if self.device_resample else self._resample(draw)
                         tail_done = self.device_resample
+                    else:
+                        self.n_gate_closed += 1
                     if fired:
                         self.n_updates_since = self.n_meas_since = 0
                     elif not tail_done:
@@ -213,17 +255,22 @@ class VictoriaParkRun:
             self.sync()
         return self
 
-    def _resample_device(self):
-        # the draw is looked at before the decision is known and taken from the stream only when the resampling fired
+    def _resample_device(self, draw=None):
+        # the draw is looked at before the decision is known and taken from the stream only when the resampling fired; with
+        # draw_every_update it is this update's own draw, already taken
         f = self.f
-        state = self.rng.bit_generator.state
-        u01 = float(self.rng.uniform())
-        self.rng.bit_generator.state = state
+        if draw is None:
+            state = self.rng.bit_generator.state
+            u01 = float(self.rng.uniform())
+            self.rng.bit_generator.state = state
+        else:
+            u01 = draw()
         f.resample_async(self.eff_n, self.eff_n / self.n, u01, 0, False, True)
         lr = f.last_resample()
         if not lr["fired"]:
             return False
-        self.rng.uniform()
+        if draw is None:
+            self.rng.uniform()
         self.x = self.x[lr["plan"]]
         self.n_resamples += 1
         return True

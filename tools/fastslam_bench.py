@@ -5,7 +5,11 @@
   python tools/fastslam_bench.py --mh-device-cycle
       MH-FastSLAM cycles per second over one simulator trajectory, timed both ways in this one invocation: the host-planned route
       (rfsgpu_fastslam_update + the numpy resampling of FastSLAM.update_and_resample) and rfsgpu_fastslam_cycle_async
-      (FastSLAM(device_cycle=True)).  FS_N particles (200), FS_HYP hypotheses (4), FS_STEPS steps (100), median of FS_REPS (3)."""
+      (FastSLAM(device_cycle=True)).  FS_N particles (200), FS_HYP hypotheses (4), FS_STEPS steps (100), median of FS_REPS (3).
+  python tools/fastslam_bench.py --vp-cycle [--rbphd]
+      The Victoria Park extract through vp_driver.VictoriaParkRun on three routes that alternate in this one invocation -- the host-stop
+      route, the device cycle read after every lidar message, the device cycle with nothing read until the end -- medians of FS_REPS;
+      FastSLAM with 1 and 3 hypotheses, or with --rbphd the RB-PHD filter (rfsgpu_rbphd_cycle_async).  FS_N particles (100)."""
 import os
 import sys
 import time
@@ -83,6 +87,40 @@ def vp_cycle_run(pkg, route, hyp, n, messages):
     f.close()
     return out
 
+
+def vp_rbphd_run(pkg, route, n, messages):
+    """The same run around the RB-PHD filter (the XML's values, scenarios.VP_PARAMS), poses propagated on the device on every route.
+    route: "host" (the update, then the host's gate and resampling), "sync" (rfsgpu_rbphd_cycle_async, results read after every lidar
+    message) or "queue" (nothing read until the end)."""
+    data = np.load(os.path.join(ROOT, "tests", "golden", "victoria_park_extract.npz"))
+    P = dict(sc.VP_PARAMS)
+    f = pkg.RBPHDFilter(n, gm_capacity=192, model=pkg.capi.MODEL_VICTORIAPARK_3D)
+    sc.apply_vp_params(f, P, np.full(361, 70.0))
+    opts = dict(device_motion=True, draw_every_update=True) if route == "host" else dict(device_cycle=True, sync_every_update=route == "sync")
+    f.synchronize()
+    t0 = time.perf_counter()
+    run = pkg.vp_driver.VictoriaParkRun(f, data, P, seed=5, filter="rbphd", **opts).run(n_messages=messages)
+    dt = time.perf_counter() - t0
+    out = (dt, run.n_lidar, run.n_resamples, run.n, float(np.asarray(f.gm_sizes()).mean()))
+    f.close()
+    return out
+
+
+if "--vp-cycle" in sys.argv and "--rbphd" in sys.argv:
+    n, messages, reps = [int(os.environ.get(k, d)) for k, d in (("FS_N", 100), ("FS_MESSAGES", 900), ("FS_REPS", 3))]
+    print("Victoria Park extract, RB-PHD, %d messages, %d particles, %d repetitions (routes alternate; the first round warms up)" % (messages, n, reps))
+    times = {"host": [], "sync": [], "queue": []}
+    for rep in range(reps + 1):
+        for route in ("host", "sync", "queue"):
+            dt, nl, nr, nn, size = vp_rbphd_run(pkg, route, n, messages)
+            if rep:
+                times[route].append(dt)
+            print("  rep %d %-5s: %.4f s/run, %d lidar updates, %d resamplings, %d particles, mean map size %.1f%s" %
+                  (rep, route, dt, nl, nr, nn, size, "" if rep else "  (warm-up)"))
+    med = {k: float(np.median(v)) for k, v in times.items()}
+    print("rbphd medians: host-stop %.4f s, cycle + sync per update %.4f s (%.2fx), cycle queued %.4f s (%.2fx)" %
+          (med["host"], med["sync"], med["host"] / med["sync"], med["queue"], med["host"] / med["queue"]))
+    sys.exit(0)
 
 if "--vp-cycle" in sys.argv:
     n, messages, reps = [int(os.environ.get(k, d)) for k, d in (("FS_N", 100), ("FS_MESSAGES", 900), ("FS_REPS", 3))]
