@@ -907,7 +907,7 @@ int rfsgpu_murty_seen(rfsgpu_filter *f);
  * A batch of FastSLAM filters (rfsgpu_batch_fastslam_cycle_async) is served: a Gaussian's weight is a log-odds w there, and wherever
  * this section says "weight" of a Gaussian (n_est, cardinality, rfsgpu_get_map_estimate's w) it means 1 - 1 / (1 + exp(w)), the
  * number the reference's fastslam2dSim logs (src/fastslam2dSim.cpp:628) and analysis2dSim thresholds.  Lifting the refusal for an
- * ordinary FastSLAM handle is a later change.
+ * ordinary FastSLAM handle is a later change ([estimate] alone serves one once rfsgpu_handle_serve_estimates is on).
  * A batch of multi-hypothesis FastSLAM filters (rfsgpu_create_batch_mh) returns RFSGPU_ERR_UNSUPPORTED from every call of this section
  * until rfsgpu_batch_mh_serve_metrics(f, 1); from then on it is served as a FastSLAM batch is (log-odds weights), with "the filter's
  * block" read as its LIVE slots -- the first n_b of its max_per_filter, n_b taken from the device where the kernel runs: see
@@ -1220,14 +1220,21 @@ int rfsgpu_batch_run_truth_async(rfsgpu_filter *f, int k_from, int k_to, int tra
  * gets RFSGPU_ERR_UNSUPPORTED from every call below.  The selection of the best particle, the weight of a Gaussian (a FastSLAM kind:
  * 1 - 1 / (1 + exp(log-odds))), the skipping of holes and the summation trees are [metric]'s, so best_slot, cardinality and
  * weight_sum of a row equal those of an rfsgpu_step_error record taken at the same point, bit for bit.
+ * An ordinary handle that [metric] refuses -- the Victoria Park model, a handle that has run rfsgpu_fastslam_update or a FastSLAM
+ * cycle -- is served by the four log calls once rfsgpu_handle_serve_estimates(f, 1) has been called (below).
  * One record per filter and row; every field is 8 bytes wide. */
 struct rfsgpu_step_estimate {
   double t;                 /* the time given with the call                                                                  */
-  long long status;         /* 0 ok; 1: n_est > max_est, the Gaussians are cut to the first max_est in mixture order         */
+  long long status;         /* 0 ok; 1: n_est > max_est, the Gaussians are cut to the first max_est in mixture order; 2 (a served
+                               handle behind rfsgpu_fastslam_cycle_async / _cycle_full_async cycles only): a pending cycle overflowed
+                               max_particles and was abandoned -- nothing of the filter state was read, the other fields are those
+                               of a live count of 0 (n_particles, n_est, n_logged, cardinality 0, best_slot 0, pose and mean fields
+                               NaN); the RFSGPU_ERR_CAPACITY itself comes from the next synchronising call, as always          */
   long long best_slot;      /* global slot of the highest-weight particle: the first slot of the filter's block whose weight is
                                strictly greater than every earlier one, starting from 0 (analysis2dSim.cpp:159-167); slot 0 of the
                                block when no weight is > 0                                                                   */
-  long long n_particles;    /* slots the selection ran over: N, n_per_filter, or the LIVE count of a multi-hypothesis filter  */
+  long long n_particles;    /* slots the selection ran over: N, n_per_filter, or the LIVE count of a multi-hypothesis filter (or
+                               of a served handle behind pending FastSLAM cycles)                                             */
   long long n_est;          /* the best particle's Gaussians with weight >= w_threshold (holes skipped, log-odds converted as in [metric]) */
   long long n_logged;       /* min(n_est, max_est)                                                                           */
   double cardinality;       /* sum of ALL its Gaussians' weights, the fixed tree of map_metric.h                             */
@@ -1239,7 +1246,8 @@ struct rfsgpu_step_estimate {
  * log_particles != 0 keeps the particle set too.  Three arrays on the device, row-major:
  *   hdr   [cap][n_filters]                      one rfsgpu_step_estimate (128 bytes) per filter and row;
  *   gauss [cap][n_filters][6][max_est]          planes mx, my, sxx, sxy, syy, w (48 max_est bytes per filter and row);
- *   part  [cap][n_filters][4][slots]            planes x, y, theta, w; slots = n_particles of an ordinary handle, n_per_filter of a
+ *   part  [cap][n_filters][4][slots]            planes x, y, theta, w; slots = n_particles of an ordinary handle (max_particles once
+ *                                               rfsgpu_handle_serve_estimates is on: a multi-hypothesis set grows), n_per_filter of a
  *                                               batch, max_per_filter of a multi-hypothesis batch (32 slots bytes per filter and row);
  *                                               only the first n_particles entries of each plane of a row are written.
  * _create (re)allocates the log empty (synchronising; capacity 0 frees everything); an allocation that fails: RFSGPU_ERR_HIP and no
@@ -1262,6 +1270,26 @@ int rfsgpu_estimate_log_read(rfsgpu_filter *f, int row_from, int max_rows, struc
  * as many free rows as the run has steps (else RFSGPU_ERR_CAPACITY), and that [metric] serves the handle.  Off (the default) the run
  * enqueues exactly what it enqueues without this section.  RFSGPU_ERR_UNSUPPORTED on a handle that is not a filter batch. */
 int rfsgpu_batch_run_log_estimates(rfsgpu_filter *f, int on, double w_threshold);
+/* The switch of an ORDINARY handle, of either model and either filter class; off at creation, and while it is off every call of this
+ * section behaves as described above, with the same codes and texts.  on != 0 (synchronising; before or after the first
+ * rfsgpu_fastslam_update or cycle): rfsgpu_estimate_log_create, _reset, _read and rfsgpu_step_estimate_async work on the handle with
+ * the signatures and log semantics above; rfsgpu_batch_run_log_estimates and every [metric] call keep refusing as they do.  What a
+ * row means there:
+ *   - the Victoria Park model: the six Gaussian planes are u(0), u(1), S(0,0), S(0,1), S(1,1) and w of the 3-D landmarks -- what the
+ *     reference's Victoria Park drivers print (src/rbphdslam_VictoriaPark.cpp:586-622, src/fastslam_VictoriaPark.cpp:576-611); the
+ *     diameter and its covariances are not logged;
+ *   - a handle on which rfsgpu_fastslam_update or a FastSLAM cycle has run: a Gaussian's weight is 1 - 1 / (1 + exp(w)) of its
+ *     log-odds w, as on a FastSLAM batch (fastslam_VictoriaPark.cpp:609);
+ *   - the part planes have max_particles slots, max_est stays within 0 ... gm_capacity;
+ *   - n_particles is the host's count while nothing of a FastSLAM cycle is pending, and the device's count (the cycle block's word,
+ *     clamped to [0, max_particles], read by the kernel where it runs) behind pending rfsgpu_fastslam_cycle_async / _cycle_full_async
+ *     cycles; no slot at or beyond it is read.  Status 2 (above) where such a cycle overflowed.
+ * rfsgpu_step_estimate_async then enqueues WITHOUT resolving the pending device cycles where only rfsgpu_rbphd_cycle_async cycles
+ * are pending, or only FastSLAM cycles (no stashed error, no rfsgpu_resample_async): a device-cycle run carries its log with it and
+ * reads it once at the end.  In every other pending state it resolves first; _create and _read synchronise.
+ * on == 0: synchronises, frees an existing log and restores the refusals.  RFSGPU_ERR_UNSUPPORTED, naming the reason: a batch of any
+ * kind, a shard of an rfsgpu_group.  RFSGPU_ERR_INVALID: a null handle. */
+int rfsgpu_handle_serve_estimates(rfsgpu_filter *f, int on);
 
 #ifdef __cplusplus
 }

@@ -171,6 +171,7 @@ ABI_SYMBOLS = [
     "batch_set_truth", "batch_generate_truth", "batch_get_truth", "batch_run_truth_async",
     "batch_fastslam_serve_sensor", "batch_fastslam_cycle_sensed_async", "batch_fastslam_mh_cycle_sensed_async",
     "estimate_log_create", "estimate_log_reset", "step_estimate_async", "estimate_log_read", "batch_run_log_estimates",
+    "handle_serve_estimates",
 ]
 
 _dp = np.ctypeslib.ndpointer(dtype=np.float64, flags="C_CONTIGUOUS")
@@ -812,7 +813,18 @@ class CFilter:
     @property
     def n_estimate_slots(self):
         """Slots per particle plane of the estimate log: max_per_filter, n_per_filter, or the particle count of an ordinary handle."""
+        if getattr(self, "_est_served", False):
+            return int(self.max_particles)
         return int(getattr(self, "max_per_filter", getattr(self, "n_per_filter", None) or self.n))
+
+    def handle_serve_estimates(self, on=True):
+        """rfsgpu_handle_serve_estimates (synchronising): the estimate log calls serve this ordinary handle -- the Victoria Park model and
+        FastSLAM handles included -- and step_estimate_async goes behind pending device cycles without resolving them.  Off frees the
+        log and restores the refusals."""
+        self._call("handle_serve_estimates", C.c_int(1 if on else 0))
+        self._est_served = bool(on)
+        if not on:
+            self._est_shape = None
 
     def estimate_log_create(self, log_capacity, max_est, log_particles=False):
         """The device-side estimate log: log_capacity rows, max_est Gaussians kept per filter and row, the particle set too with

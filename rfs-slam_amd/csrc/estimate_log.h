@@ -21,8 +21,14 @@
 // count once (a scalar read), clamps it to [0, stride], and no slot at or beyond it is read -- by either kind of workgroup.  A count of
 // 0 reads nothing of the block at all: best_slot is the block's first slot, n_est and cardinality are 0, pose and mean fields NaN.
 //
+// An EstimateHandle as the trailing argument: an ordinary handle that rfsgpu_handle_serve_estimates serves -- the same code in the same
+// order with the layout as a compile-time parameter, and behind pending FastSLAM cycles the live count and the overflow word of the
+// handle's cycle block read where the kernel runs (status 2 and a count of 0 once a cycle overflowed).  The instantiations without one
+// compile to what they compiled to before it existed.
+//
 // Bounds: a Gaussian is stored at pos < maxEst <= cap (the engine checks max_est against gm_capacity), a particle at s < nLive <=
-// nPer <= slots (the stride the part array was allocated with); nothing else is written but lane 0's header.
+// nPer <= slots (the stride the part array was allocated with; a served handle: s < n_live <= max_particles <= slots); nothing else is
+// written but lane 0's header.
 #pragma once
 
 struct EstimateArg {
@@ -41,12 +47,37 @@ struct EstimateArg {
 
 #define ESTIMATE_PART_SLOTS 256   // slots per particle-plane workgroup
 
+// The trailing argument of an ordinary handle that rfsgpu_handle_serve_estimates serves (one filter, b = 0).  D: the slab layout the
+// Gaussians are read from -- 2: the planes of common.h; 3: the Victoria Park planes of vp.h (Plane3), of which the row keeps u(0), u(1),
+// S(0,0), S(0,1), S(1,1) and w, what the reference's Victoria Park drivers print (the diameter and its covariances are not logged).
+// kBehind: the launch stands behind pending FastSLAM cycles (fastslam_cycle.h) -- n and ovf are the count and the overflow word of
+// the handle's cycle block; otherwise neither is read and the count is the host's, A.nPer.
+template <int D, bool kBehind>
+struct EstimateHandle {
+  const int *n;     // [1] live particle count (FSC_N)
+  const int *ovf;   // [1] != 0: a pending cycle overflowed max_particles and was abandoned (FSC_OVF)
+};
+template <typename... T> struct estimate_traits { static constexpr int D = 2; static constexpr bool handle = false, behind = false; };
+template <int D_, bool kBehind> struct estimate_traits<EstimateHandle<D_, kBehind>> { static constexpr int D = D_; static constexpr bool handle = true, behind = kBehind; };
+
 template <typename... TLive>
 __global__ __launch_bounds__(64) void estimate_log_kernel(Buffers B, int cur, EstimateArg A, TLive... live) {
+  using TR = estimate_traits<TLive...>;
+  constexpr int NPL = TR::D == 3 ? (int)P3_COUNT : (int)PL_COUNT, KW = TR::D == 3 ? (int)P3_W : (int)PL_W;
+  constexpr int KMX = TR::D == 3 ? (int)P3_MX : (int)PL_MX, KMY = TR::D == 3 ? (int)P3_MY : (int)PL_MY;
+  constexpr int KSXX = TR::D == 3 ? (int)P3_SXX : (int)PL_SXX, KSXY = TR::D == 3 ? (int)P3_SXY : (int)PL_SXY, KSYY = TR::D == 3 ? (int)P3_SYY : (int)PL_SYY;
   const int b = blockIdx.x, lane = threadIdx.x;
   const int nPer = A.nPer, lo = b * nPer;
   int nLive = nPer;
-  if constexpr (sizeof...(TLive) == 1) {   // a MetricLive: the filter's count lives on the device (wave-uniform: one scalar read)
+  [[maybe_unused]] int ovf = 0;
+  if constexpr (TR::handle) {              // a served handle: the host's count, or -- behind FastSLAM cycles -- MetricLive's form with b = 0
+    if constexpr (TR::behind) {            // and the overflow word beside it: once set, the host's `cur` is ahead of the device and the
+      const auto &L = pack_first(live...); // row is that of a count of 0 -- nothing of the filter state is read
+      ovf = __builtin_amdgcn_readfirstlane(*L.ovf);
+      nLive = __builtin_amdgcn_readfirstlane(*L.n);
+      nLive = (ovf != 0 || nLive < 0) ? 0 : (nLive > nPer ? nPer : nLive);
+    }
+  } else if constexpr (sizeof...(TLive) == 1) {   // a MetricLive: the filter's count lives on the device (wave-uniform: one scalar read)
     const MetricLive &L = pack_first(live...);
     nLive = __builtin_amdgcn_readfirstlane(L.words[(size_t)b * L.wordStride + L.word]);
     nLive = nLive < 0 ? 0 : (nLive > nPer ? nPer : nLive);
@@ -98,9 +129,9 @@ __global__ __launch_bounds__(64) void estimate_log_kernel(Buffers B, int cur, Es
   if (nLive > 0) {
     int cnt = B.count[best];
     cnt = cnt < 0 ? 0 : (cnt > B.cap ? B.cap : cnt);
-    const double *pl = B.slab[cur] + (size_t)best * PL_COUNT * (size_t)B.cap;
-    const double *pw = pl + (size_t)PL_W * B.cap, *pmx = pl + (size_t)PL_MX * B.cap, *pmy = pl + (size_t)PL_MY * B.cap;
-    const double *pxx = pl + (size_t)PL_SXX * B.cap, *pxy = pl + (size_t)PL_SXY * B.cap, *pyy = pl + (size_t)PL_SYY * B.cap;
+    const double *pl = B.slab[cur] + (size_t)best * NPL * (size_t)B.cap;
+    const double *pw = pl + (size_t)KW * B.cap, *pmx = pl + (size_t)KMX * B.cap, *pmy = pl + (size_t)KMY * B.cap;
+    const double *pxx = pl + (size_t)KSXX * B.cap, *pxy = pl + (size_t)KSXY * B.cap, *pyy = pl + (size_t)KSYY * B.cap;
     const size_t me = (size_t)A.maxEst;
     double *g = A.gauss + (size_t)b * 6 * me;
     const unsigned long long below = (1ull << lane) - 1ull;
@@ -131,5 +162,6 @@ __global__ __launch_bounds__(64) void estimate_log_kernel(Buffers B, int cur, Es
     o.cardinality = card; o.best_weight = bestW; o.weight_sum = sw;
     o.best_x = bx; o.best_y = by; o.best_theta = bth;
     o.mean_x = sx; o.mean_y = sy; o.mean_cos = sc; o.mean_sin = ss;
+    if constexpr (TR::behind) { if (ovf != 0) o.status = 2; }
   }
 }

@@ -298,6 +298,7 @@ struct rfsgpu_filter {
   int estLogCap = 0, estLogRows = 0, estMax = 0, estSlots = 0;
   bool estRunOn = false;                                // rfsgpu_batch_run_log_estimates: rfsgpu_batch_run_truth_async appends a row per step
   double estRunThr = 0.0;
+  bool estServe = false;                                // rfsgpu_handle_serve_estimates: the [estimate] log calls serve this ordinary handle (either model, either filter class)
   bool groupShard = false;                       // a shard of an rfsgpu_group: the [metric] calls refuse
 };
 
@@ -4870,8 +4871,12 @@ int rfsgpu_get_map_estimate(rfsgpu_filter *f, int filter, double w_threshold, in
 }
 
 // ---- [estimate] per-step pose and map estimates in a device-side log (estimate_log.h) -------------------------------------------------
-// Served where [metric] is served: every call starts with metric_check.
-static inline int estimate_slots(const rfsgpu_filter *f) { return f->batch ? f->nPer : f->N; }
+// Served where [metric] is served -- every call starts with metric_check -- and on an ordinary handle whose switch
+// (rfsgpu_handle_serve_estimates) is on: the four log calls start with estimate_check there.
+static inline int estimate_slots(const rfsgpu_filter *f) { return f->batch ? f->nPer : (f->estServe ? f->Ncap : f->N); }
+static int estimate_check(rfsgpu_filter *f, const char *what) { return f->estServe ? RFSGPU_OK : metric_check(f, what); }
+// (a served handle that has run FastSLAM updates or cycles: log-odds weights, as on a FastSLAM batch)
+static inline bool estimate_log_odds(const rfsgpu_filter *f) { return metric_log_odds(f) || (f->estServe && f->fastSlamHandle); }
 static void estimate_log_free(rfsgpu_filter *f) {
   hipFree(f->dEstHdr); hipFree(f->dEstGauss); hipFree(f->dEstPart);
   f->dEstHdr = nullptr; f->dEstGauss = nullptr; f->dEstPart = nullptr;
@@ -4879,10 +4884,12 @@ static void estimate_log_free(rfsgpu_filter *f) {
 }
 // One launch into row `row` of the log: the call's times go into a slot of the pinned staging ring (metric_launch's), which the kernel
 // reads in place.  devIn (rfsgpu_batch_run_truth_async): the times are the first of every four doubles of a truth table row on the device.
-static int estimate_launch(rfsgpu_filter *f, const double *t, double w_threshold, int row, const double *devIn = nullptr) {
+// behind (a served handle with nothing but FastSLAM cycles pending): the count is a word of the handle's cycle block, the launch is sized
+// for max_particles.
+static int estimate_launch(rfsgpu_filter *f, const double *t, double w_threshold, int row, const double *devIn = nullptr, bool behind = false) {
   const int nF = metric_nf(f);
   hipSetDevice(f->device);
-  const int nPer = estimate_slots(f);
+  const int nPer = f->batch ? f->nPer : (behind ? f->Ncap : f->N);
   if (f->dEstPart && nPer > f->estSlots) {
     f->err = "step_estimate: the handle holds more particles than the estimate log's particle planes were created for (rfsgpu_estimate_log_create)";
     return RFSGPU_ERR_INVALID;
@@ -4896,12 +4903,17 @@ static int estimate_launch(rfsgpu_filter *f, const double *t, double w_threshold
   const size_t at = (size_t)row * nF;
   EstimateArg A{devIn ? devIn : h, devIn ? 4 : 1, f->dEstHdr + at, f->dEstGauss ? f->dEstGauss + at * 6 * (size_t)f->estMax : nullptr,
                 f->dEstPart ? f->dEstPart + at * 4 * (size_t)f->estSlots : nullptr, w_threshold, nPer, f->estSlots, f->estMax, f->holes ? 1 : 0,
-                metric_log_odds(f) ? 1 : 0};
+                estimate_log_odds(f) ? 1 : 0};
   const dim3 grid(nF, 1 + (f->dEstPart ? (nPer + ESTIMATE_PART_SLOTS - 1) / ESTIMATE_PART_SLOTS : 0));
   if (f->mhBatch) {     // every filter's count is a word of its cycle block, read by the kernel where it runs: nothing waits for it
     FsCycleState S0;
     mhb_view(f, f->mhbBlock, 0, S0);
     estimate_log_kernel<<<grid, 64, 0, f->stream>>>(f->B, f->cur, A, MetricLive{S0.w, FSC_WORDS, FSC_N});
+  } else if (behind) {  // f->cur counts the flips of the pending cycles; a cycle that did not flip was abandoned by an overflow, and its row reads no slab
+    if (f->D == 3) estimate_log_kernel<<<grid, 64, 0, f->stream>>>(f->B, f->cur, A, EstimateHandle<3, true>{f->mhc.w + FSC_N, f->mhc.w + FSC_OVF});
+    else estimate_log_kernel<<<grid, 64, 0, f->stream>>>(f->B, f->cur, A, EstimateHandle<2, true>{f->mhc.w + FSC_N, f->mhc.w + FSC_OVF});
+  } else if (f->D == 3) {
+    estimate_log_kernel<<<grid, 64, 0, f->stream>>>(f->B, f->cur, A, EstimateHandle<3, false>{nullptr, nullptr});
   } else {
     estimate_log_kernel<<<grid, 64, 0, f->stream>>>(f->B, f->cur, A);
   }
@@ -4909,9 +4921,20 @@ static int estimate_launch(rfsgpu_filter *f, const double *t, double w_threshold
   if (!devIn) HIPCHK(hipEventRecord(f->stage.ev[k], f->stream));
   return RFSGPU_OK;
 }
+// The switch of an ordinary handle: off at creation, so the refusals the section was published with stand until a caller asks.
+int rfsgpu_handle_serve_estimates(rfsgpu_filter *f, int on) {
+  CHECK_HANDLE(f);
+  if (f->batch) return fail(f, RFSGPU_ERR_UNSUPPORTED, "handle_serve_estimates: a filter batch is served by [estimate] as [metric] serves it (a multi-hypothesis batch: rfsgpu_batch_mh_serve_metrics); the switch is for ordinary handles");
+  if (f->groupShard) return fail(f, RFSGPU_ERR_UNSUPPORTED, "handle_serve_estimates: not available on a shard of an rfsgpu_group (the highest-weight particle and the sums would be those of one shard only)");
+  hipSetDevice(f->device);
+  HIPCHK(hipStreamSynchronize(f->stream));
+  if (!on) estimate_log_free(f);
+  f->estServe = on != 0;
+  return RFSGPU_OK;
+}
 int rfsgpu_estimate_log_create(rfsgpu_filter *f, int log_capacity, int max_est, int log_particles) {
   CHECK_HANDLE(f);
-  int rc = metric_check(f, "estimate_log_create");
+  int rc = estimate_check(f, "estimate_log_create");
   if (rc != RFSGPU_OK) return rc;
   if (log_capacity < 0) return fail(f, RFSGPU_ERR_INVALID, "estimate_log_create: negative capacity");
   if (max_est < 0 || max_est > f->cap) return fail(f, RFSGPU_ERR_INVALID, "estimate_log_create: max_est must lie in 0 ... gm_capacity");
@@ -4936,29 +4959,35 @@ int rfsgpu_estimate_log_create(rfsgpu_filter *f, int log_capacity, int max_est, 
 }
 int rfsgpu_estimate_log_reset(rfsgpu_filter *f) {
   CHECK_HANDLE(f);
-  int rc = metric_check(f, "estimate_log_reset");
+  int rc = estimate_check(f, "estimate_log_reset");
   if (rc != RFSGPU_OK) return rc;
   f->estLogRows = 0;   // (stream order keeps a row that is still being written ahead of the next one that lands there)
   return RFSGPU_OK;
 }
 int rfsgpu_step_estimate_async(rfsgpu_filter *f, const double *t, double w_threshold) {
   if (!f) return RFSGPU_ERR_INVALID;
-  if (!(f->mhBatch && f->mhbMetrics)) {    // (as rfsgpu_step_error_async: a served multi-hypothesis batch keeps its cycles in flight)
+  // A served handle keeps its device cycles in flight: behind rfsgpu_rbphd_cycle_async cycles the count is the host's and the kernel
+  // reads the state at its point of the stream; behind FastSLAM cycles (nothing stashed, no resampling call pending) it reads the
+  // count on the device too.  A pending error is the next synchronising call's to report.
+  const bool behind = f->estServe && f->mhcPending && !f->mhcStashedRc && !f->mhbPending && !f->rsPending;
+  if (f->estServe) {
+    if (!behind && !rc_only_pending(f)) { CHECK_HANDLE(f); }
+  } else if (!(f->mhBatch && f->mhbMetrics)) {    // (as rfsgpu_step_error_async: a served multi-hypothesis batch keeps its cycles in flight)
     CHECK_HANDLE(f);
   }
-  int rc = metric_check(f, "step_estimate_async");
+  int rc = estimate_check(f, "step_estimate_async");
   if (rc != RFSGPU_OK) return rc;
   if (!t) return fail(f, RFSGPU_ERR_INVALID, "step_estimate_async: null time array");
   if (f->estLogRows >= f->estLogCap)
     return fail(f, RFSGPU_ERR_CAPACITY, f->estLogCap ? "step_estimate_async: the estimate log is full (rfsgpu_estimate_log_read, then rfsgpu_estimate_log_reset)"
                                                       : "step_estimate_async: no estimate log (rfsgpu_estimate_log_create)");
-  rc = estimate_launch(f, t, w_threshold, f->estLogRows);
+  rc = estimate_launch(f, t, w_threshold, f->estLogRows, nullptr, behind);
   if (rc == RFSGPU_OK) f->estLogRows++;
   return rc;
 }
 int rfsgpu_estimate_log_read(rfsgpu_filter *f, int row_from, int max_rows, struct rfsgpu_step_estimate *hdr, double *gauss, double *part, int *n_rows) {
   CHECK_HANDLE(f);
-  int rc = metric_check(f, "estimate_log_read");
+  int rc = estimate_check(f, "estimate_log_read");
   if (rc != RFSGPU_OK) return rc;
   if (max_rows < 0) return fail(f, RFSGPU_ERR_INVALID, "estimate_log_read: negative max_rows");
   if (row_from < 0 || row_from > f->estLogRows) return fail(f, RFSGPU_ERR_INVALID, "estimate_log_read: row_from outside 0 ... the number of rows in the log");

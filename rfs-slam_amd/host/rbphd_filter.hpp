@@ -259,7 +259,33 @@ class RBPHDFilter2d {
     return e;
   }
 
+  // What the reference's drivers write after every update (particlePose.dat, landmarkEst.dat), kept on the device instead: the handle's
+  // estimate log (rfsgpu.h [estimate], switched on for an ordinary handle of either model by rfsgpu_handle_serve_estimates).
+  // estimateLogCreate: `rows` rows of up to gm_capacity Gaussians each, the particle set too; logEstimate appends one row behind whatever
+  // is enqueued -- a pending device cycle stays pending; estimateLogRead is the one read at the end: hdr [rows], gauss [rows][6][maxEst],
+  // part [rows][4][slots], and returns the number of rows.
+  void estimateLogCreate(int rows, int maxEst, bool particles = true) {
+    if (g_) throw std::runtime_error("estimateLogCreate: not available on a filter sharded over several devices");
+    check(rfsgpu_handle_serve_estimates(h_, 1), "handle_serve_estimates");
+    check(rfsgpu_estimate_log_create(h_, rows, maxEst, particles ? 1 : 0), "estimate_log_create");
+    estMax_ = maxEst;
+    estSlots_ = particles ? rfsgpu_max_particles(h_) : 0;
+  }
+  void logEstimate(double t, double wThreshold) { check(rfsgpu_step_estimate_async(h_, &t, wThreshold), "step_estimate_async"); }
+  int estimateLogMaxEst() const { return estMax_; }
+  int estimateLogSlots() const { return estSlots_; }
+  int estimateLogRead(std::vector<struct rfsgpu_step_estimate> &hdr, std::vector<double> &gauss, std::vector<double> &part) {
+    int rows = 0;
+    check(rfsgpu_estimate_log_read(h_, 0, 0, nullptr, nullptr, nullptr, &rows), "estimate_log_read");
+    hdr.assign((size_t)rows, rfsgpu_step_estimate{});
+    gauss.assign((size_t)rows * 6 * (size_t)estMax_, 0.0);
+    part.assign((size_t)rows * 4 * (size_t)estSlots_, 0.0);
+    check(rfsgpu_estimate_log_read(h_, 0, rows, hdr.data(), estMax_ ? gauss.data() : nullptr, estSlots_ ? part.data() : nullptr, &rows), "estimate_log_read");
+    return rows;
+  }
+
  protected:
+  int estMax_ = 0, estSlots_ = 0;
   rfsgpu_filter *h_ = nullptr;
   rfsgpu_group *g_ = nullptr;   // set: the particle set is sharded over several devices
   int n_, nInit_;

@@ -8,7 +8,7 @@
 // the raw scan is the synthetic one SURVEY 8d prescribes: 361 beams at rangeLimitMax.
 //
 //   rbphdslam_vp -c cfg.xml [-d dataDir] [-n nParticles] [-m nMessages] [-e effNParticle] [-s seed] [-o outDir] [--device k] [--host-motion] [--repeat K]
-//                [--no-input-noise] [--no-clutter] [--device-resample | --device-cycle | --draw-every-update]
+//                [--no-input-noise] [--no-clutter] [--device-resample | --device-cycle | --draw-every-update] [--device-log]
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -49,6 +49,7 @@ int main(int argc, char **argv) {
   int nParticlesOverride = -1, nMsgOverride = -1, seed = 1, device = 0;
   double effNOverride = -1;
   bool inputNoise = true, clutter = true, deviceMotion = true, deviceResample = false, deviceCycle = false, drawEveryUpdate = false;
+  bool deviceLog = false;
   int repeat = 1;
   for (int a = 1; a < argc; a++) {
     std::string s = argv[a];
@@ -72,6 +73,10 @@ int main(int argc, char **argv) {
     else if (s == "--device-cycle") deviceCycle = true;
     // the host-stop route of that realisation (one draw per update, N_eff added as the device adds it): writes the files of --device-cycle
     else if (s == "--draw-every-update") drawEveryUpdate = true;
+    // with --device-cycle and -o: the rows of the two log files are kept in the handle's estimate log on the device, appended behind every
+    // update without resolving the cycles in flight, and the files are written from ONE read at the end -- the same bytes as the
+    // per-update getter route (the default), which waits for every update
+    else if (s == "--device-log") deviceLog = true;
     else if (s == "--host-motion") deviceMotion = false;   // ParticleFilter::propagate on the host (the reference's shape) instead of the device kernel
   }
   Cfg c;
@@ -159,6 +164,13 @@ int main(int argc, char **argv) {
     fPose = std::fopen((outDir + "particlePose.dat").c_str(), "w");
     fLm = std::fopen((outDir + "landmarkEst.dat").c_str(), "w");
   }
+  if (deviceLog && (!deviceCycle || (pass == 0 && outDir.empty()))) { std::fprintf(stderr, "--device-log goes with --device-cycle and -o\n"); return 2; }
+  const bool logOnDevice = deviceLog && (fPose || fLm);
+  if (logOnDevice) {     // one row per lidar message of the run, counted before the loop
+    int rows = 0;
+    for (int k = 0; k < nMsg; k++) rows += msgs[k].type == 3 ? 1 : 0;
+    filter.estimateLogCreate(rows, 192, true);
+  }
 
   // ---------------- run (:440-660) ----------------
   std::mt19937 rng((unsigned)seed);
@@ -213,7 +225,9 @@ int main(int argc, char **argv) {
       { const auto ta = now(); filter.update(Z); tUpdate += std::chrono::duration<double>(now() - ta).count(); }
       if (any) { nLidar++; if (!deviceResample && !deviceCycle) nResample += filter.resampleOccured() ? 1 : 0; }   // (the device route is asked once, at the end: asking waits)
       birthCheck = true;
-      if (fPose || fLm) {
+      if (logOnDevice) {
+        filter.logEstimate(m.t, -INFINITY);     // (every Gaussian of the best particle, as getGMSize / getLandmark give them)
+      } else if (fPose || fLm) {
         int best = 0;
         double bw = 0;
         for (int i = 0; i < filter.getParticleCount(); i++) {
@@ -234,7 +248,27 @@ int main(int argc, char **argv) {
   }
   if (deviceResample) nResample = (int)filter.resampleCount();
   if (deviceCycle) nResample = (int)filter.cycleResampleCount();
+  double tLogRead = 0;
+  if (logOnDevice) {     // the one read: the rows in the order they were appended, printed as the getter route prints them
+    const auto ta = now();
+    std::vector<struct rfsgpu_step_estimate> hdr;
+    std::vector<double> gauss, part;
+    const int rows = filter.estimateLogRead(hdr, gauss, part);
+    tLogRead = std::chrono::duration<double>(now() - ta).count();
+    const size_t me = (size_t)filter.estimateLogMaxEst(), sl = (size_t)filter.estimateLogSlots();
+    for (int r = 0; r < rows; r++) {
+      const struct rfsgpu_step_estimate &h = hdr[r];
+      const double *pp = part.data() + (size_t)r * 4 * sl, *gg = gauss.data() + (size_t)r * 6 * me;
+      if (fPose)
+        for (long long i = 0; i < h.n_particles; i++)
+          std::fprintf(fPose, "%10.3f%5d%10.3f%10.3f%10.3f%10.3f\n", h.t, (int)i, pp[i], pp[sl + i], pp[2 * sl + i], pp[3 * sl + i]);
+      if (fLm)
+        for (long long g = 0; g < h.n_logged; g++)
+          std::fprintf(fLm, "%10.3f%5d%10.3f%10.3f%10.3f%10.3f%10.3f%10.3f\n", h.t, (int)h.best_slot, gg[g], gg[me + g], gg[2 * me + g], gg[3 * me + g], gg[4 * me + g], gg[5 * me + g]);
+    }
+  }
   const double wall = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+  if (logOnDevice) std::printf("device log: read and printed once at the end, the read took %.4f s\n", tLogRead);
   if (fPose) std::fclose(fPose);
   if (fLm) std::fclose(fLm);
 

@@ -22,6 +22,13 @@ The RB-PHD filter (filter="rbphd") takes device_motion, device_cycle, draw_every
                      propagation), the rest as one static_steps_async, then one propagate_ackerman_run_async.
   device_cycle       every lidar message is one rfsgpu_rbphd_cycle_async that carries the scan: the two counters, the gate and the
                      resampling are the device's, and the birth predict behind it walks the inheritance levels there.
+Logging (either filter, every route):
+  log_estimates      the reference's particlePose.dat / landmarkEst.dat content is kept on the device (rfsgpu.h [estimate], switched on
+                     for the handle by rfsgpu_handle_serve_estimates): one row taken before the loop at the first message's time (the
+                     reference's initial block of poses), then one row behind every lidar update with the message's time.  On the
+                     device-cycle route the rows go behind the pending cycles and nothing is read; estimates() is the one read at the
+                     end and write_vp_logs prints the two files from it.  log_particles: keep the particle set (particlePose.dat);
+                     log_w_threshold: the least weight of a logged Gaussian (-inf: every one, what landmarkEst.dat holds).
 N_eff: the host-stop route takes 1 / np.sum(w * w); the device adds the squares in slot order with one fused multiply-add per
 particle (csrc/resample_plan.h).  The two agree to rounding, so a run whose N_eff comes within an ulp or so of a threshold could
 decide differently on the two routes; the runs the tests compare do not.
@@ -50,7 +57,8 @@ def ackerman_step(x, u_v, u_r, dt, a=ACKERMAN):
 class VictoriaParkRun:
     def __init__(self, f, data, params, seed=1, var_uv=0.2, var_ur=0.025, noise_inflation=20.0, added_clutter=3.0, eff_n=None,
                  filter="rbphd", device_resample=False, max_hypotheses=1, n_particles_max=None, device_cycle=False, draw_every_update=False,
-                 device_motion=False, motion_seed=1, sync_every_update=False):
+                 device_motion=False, motion_seed=1, sync_every_update=False, log_estimates=False, log_particles=True,
+                 log_w_threshold=-np.inf):
         # device_resample: the resample-or-normalise tail of an update as one rfsgpu_resample_async (same realisation and results)
         # filter = "rbphd": src/rbphdslam_VictoriaPark.cpp; "fastslam": src/fastslam_VictoriaPark.cpp (same event loop around
         # FastSLAM::predict / update: no births in predict, rfsgpu_fastslam_update)
@@ -101,6 +109,18 @@ class VictoriaParkRun:
             f.fastslam_set_resampling(self.eff_n, self.eff_n / self.n_init)
         if self.device_motion:
             f.set_poses(self.x, None)
+        self.log_estimates, self.log_particles, self.log_w_threshold = bool(log_estimates), bool(log_particles), float(log_w_threshold)
+        if self.log_estimates:
+            f.handle_serve_estimates(True)
+
+    def _log_row(self, t):
+        """One row of the estimate log behind whatever is enqueued (a pending device cycle stays pending)."""
+        if self.log_estimates:
+            self.f.step_estimate_async(t, self.log_w_threshold)
+
+    def estimates(self):
+        """(hdr, gauss, part) of the run's rows, as estimate_log_read returns them: the one read at the end."""
+        return self.f.estimate_log_read()
 
     def _predict(self, u, dt, stationary, birth):
         f = self.f
@@ -182,6 +202,12 @@ class VictoriaParkRun:
         f, P = self.f, self.P
         t_km, u_km, stationary, birth, z_idx = 0.0, np.zeros(2), True, True, 0
         msgs = self.mgr if n_messages is None else self.mgr[:n_messages]
+        if self.log_estimates:            # a row before the loop and one per lidar message, counted here
+            f.estimate_log_create(1 + int(sum(1 for m in msgs if m[1] == 3)), f.gm_capacity, self.log_particles)
+            if not self.device_motion:
+                f.set_poses(self.x, None)
+            if len(msgs):
+                self._log_row(float(msgs[0][0]))
         for t_k, typ, idx in msgs:
             idx = int(idx) - 1
             dt = t_k - t_km
@@ -212,6 +238,7 @@ class VictoriaParkRun:
                     self.n_lidar += 1 if len(Z) else 0
                     if self.sync_every_update and len(Z):
                         f.rbphd_last_cycle()
+                    self._log_row(t_k)
                     birth = True
                     t_km = t_k
                     continue
@@ -249,6 +276,7 @@ class VictoriaParkRun:
                     elif not tail_done:
                         s = f.weight_sums()
                         f.normalize_weights(s[0])
+                self._log_row(t_k)
                 birth = True
                 t_km = t_k
         if self.device_motion:
@@ -297,3 +325,29 @@ class VictoriaParkRun:
             self.x = self.x[plan]
         self.n_resamples += 1
         return True
+
+
+def write_vp_logs(log_dir, estimates):
+    """particlePose.dat and landmarkEst.dat in the reference's Victoria Park format (std::fixed, precision 3, widths 10 / 5 / 10 ...:
+    src/rbphdslam_VictoriaPark.cpp:427-440, :586-622) from (hdr, gauss, part) as VictoriaParkRun.estimates() returns them: per row
+    the row's n_particles particles (a log without particles: none), then its n_logged Gaussians under the best slot's index.
+    Returns the two paths."""
+    import os
+    hdr, gauss, part = estimates
+    poses, lms = [], []
+    for r in range(hdr.shape[0]):
+        h = hdr[r, 0]
+        t = float(h["t"])
+        if part is not None:
+            p = part[r, 0]
+            for i in range(int(h["n_particles"])):
+                poses.append("%10.3f%5d%10.3f%10.3f%10.3f%10.3f\n" % (t, i, p[0, i], p[1, i], p[2, i], p[3, i]))
+        g, best = gauss[r, 0], int(h["best_slot"])
+        for m in range(int(h["n_logged"])):
+            lms.append("%10.3f%5d%10.3f%10.3f%10.3f%10.3f%10.3f%10.3f\n" % (t, best, g[0, m], g[1, m], g[2, m], g[3, m], g[4, m], g[5, m]))
+    os.makedirs(log_dir, exist_ok=True)
+    paths = os.path.join(log_dir, "particlePose.dat"), os.path.join(log_dir, "landmarkEst.dat")
+    for path, lines in zip(paths, (poses, lms)):
+        with open(path, "w") as fh:
+            fh.writelines(lines)
+    return paths

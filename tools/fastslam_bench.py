@@ -9,7 +9,11 @@
   python tools/fastslam_bench.py --vp-cycle [--rbphd]
       The Victoria Park extract through vp_driver.VictoriaParkRun on three routes that alternate in this one invocation -- the host-stop
       route, the device cycle read after every lidar message, the device cycle with nothing read until the end -- medians of FS_REPS;
-      FastSLAM with 1 and 3 hypotheses, or with --rbphd the RB-PHD filter (rfsgpu_rbphd_cycle_async).  FS_N particles (100)."""
+      FastSLAM with 1 and 3 hypotheses, or with --rbphd the RB-PHD filter (rfsgpu_rbphd_cycle_async).  FS_N particles (100).
+  python tools/fastslam_bench.py --vp-cycle --log [--rbphd]
+      The logging column: the device cycle with nothing read until the end, the same with the device-side estimate log (one row
+      behind every lidar update, vp_driver's log_estimates; the one read at the end is timed apart), and the same with the per-update
+      getter route (weights, poses and the best particle's map read after every lidar update, which resolves the pending cycle)."""
 import os
 import sys
 import time
@@ -58,7 +62,38 @@ def mh_route_times(pkg, device_cycle, n, hyp, steps, reps, quiet=False):
     return out
 
 
-def vp_cycle_run(pkg, route, hyp, n, messages):
+class GetterLogRun(pkg.vp_driver.VictoriaParkRun):
+    """The per-update getter route of a logged run: after every lidar update the weights, the poses and the map of the highest-weight
+    particle come to the host, as the C++ driver's -o route reads them."""
+    rows = None
+
+    def _log_row(self, t):
+        if self.rows is None:
+            self.rows = []
+        w, x = self.f.get_weights(), self.f.get_poses()
+        best = int(np.argmax(w)) if (w > 0).any() else 0
+        self.rows.append((t, x, w, best, self.f.export_gm(best)))
+
+
+def log_setup(pkg, log, opts):
+    """The run class and options of a logged run: log None, "device" (the device-side estimate log) or "getter"."""
+    if log == "device":
+        opts["log_estimates"] = True
+    return GetterLogRun if log == "getter" else pkg.vp_driver.VictoriaParkRun
+
+
+def log_read(run, log):
+    """Seconds of the one read at the end of a run with the device log (0 on the other routes)."""
+    if log != "device":
+        return 0.0
+    t0 = time.perf_counter()
+    hdr = run.estimates()[0]
+    dt = time.perf_counter() - t0
+    assert hdr.shape[0] > run.n_lidar and (hdr["status"] == 0).all()
+    return dt
+
+
+def vp_cycle_run(pkg, route, hyp, n, messages, log=None):
     """Seconds for one run of `messages` messages of the Victoria Park extract through vp_driver.VictoriaParkRun: the values of the
     reference's fastslam_VictoriaPark.xml / mhfastslam_VictoriaPark.xml (100 particles, candidate threshold 4, 1 or 3 hypotheses),
     poses propagated on the device on every route.  route: "host" (rfsgpu_fastslam_update + the host's resampleWithMapCopy),
@@ -78,17 +113,18 @@ def vp_cycle_run(pkg, route, hyp, n, messages):
     cfg.maxNDataAssocHypotheses = hyp
     cfg.maxDataAssocLogLikelihoodDiff = 3.0
     f.set_fastslam_config(cfg)
-    opts = dict(device_motion=True, draw_every_update=True) if route == "host" else dict(device_cycle=True, sync_every_update=route == "sync")
+    opts = dict(device_motion=True, draw_every_update=True) if route == "host" else dict(device_cycle=True, sync_every_update=route == "sync")      # ("queue", and "log" of the logging column: nothing read)
+    cls = log_setup(pkg, log, opts)
     f.synchronize()
     t0 = time.perf_counter()
-    run = pkg.vp_driver.VictoriaParkRun(f, data, P, seed=5, filter="fastslam", max_hypotheses=hyp, n_particles_max=n_max, **opts).run(n_messages=messages)
+    run = cls(f, data, P, seed=5, filter="fastslam", max_hypotheses=hyp, n_particles_max=n_max, **opts).run(n_messages=messages)
     dt = time.perf_counter() - t0
-    out = (dt, run.n_lidar, run.n_resamples, run.n, float(np.asarray(f.gm_sizes()).mean()))
+    out = (dt, run.n_lidar, run.n_resamples, run.n, float(np.asarray(f.gm_sizes()).mean())) + ((log_read(run, log),) if log is not None or route == "log" else ())
     f.close()
     return out
 
 
-def vp_rbphd_run(pkg, route, n, messages):
+def vp_rbphd_run(pkg, route, n, messages, log=None):
     """The same run around the RB-PHD filter (the XML's values, scenarios.VP_PARAMS), poses propagated on the device on every route.
     route: "host" (the update, then the host's gate and resampling), "sync" (rfsgpu_rbphd_cycle_async, results read after every lidar
     message) or "queue" (nothing read until the end)."""
@@ -96,15 +132,38 @@ def vp_rbphd_run(pkg, route, n, messages):
     P = dict(sc.VP_PARAMS)
     f = pkg.RBPHDFilter(n, gm_capacity=192, model=pkg.capi.MODEL_VICTORIAPARK_3D)
     sc.apply_vp_params(f, P, np.full(361, 70.0))
-    opts = dict(device_motion=True, draw_every_update=True) if route == "host" else dict(device_cycle=True, sync_every_update=route == "sync")
+    opts = dict(device_motion=True, draw_every_update=True) if route == "host" else dict(device_cycle=True, sync_every_update=route == "sync")      # ("queue", and "log" of the logging column: nothing read)
+    cls = log_setup(pkg, log, opts)
     f.synchronize()
     t0 = time.perf_counter()
-    run = pkg.vp_driver.VictoriaParkRun(f, data, P, seed=5, filter="rbphd", **opts).run(n_messages=messages)
+    run = cls(f, data, P, seed=5, filter="rbphd", **opts).run(n_messages=messages)
     dt = time.perf_counter() - t0
-    out = (dt, run.n_lidar, run.n_resamples, run.n, float(np.asarray(f.gm_sizes()).mean()))
+    out = (dt, run.n_lidar, run.n_resamples, run.n, float(np.asarray(f.gm_sizes()).mean())) + ((log_read(run, log),) if log is not None or route == "log" else ())
     f.close()
     return out
 
+
+if "--vp-cycle" in sys.argv and "--log" in sys.argv:
+    n, messages, reps = [int(os.environ.get(k, d)) for k, d in (("FS_N", 100), ("FS_MESSAGES", 900), ("FS_REPS", 3))]
+    kinds = [("rbphd", 1)] if "--rbphd" in sys.argv else [("fastslam", h) for h in ([int(os.environ["FS_HYP"])] if "FS_HYP" in os.environ else [1, 3])]
+    for kind, hyp in kinds:
+        print("Victoria Park extract, %s, %d hypothes%s, %d messages, %d particles, %d repetitions (the logging routes alternate; the first round warms up)" %
+              (kind, hyp, "is" if hyp == 1 else "es", messages, n, reps))
+        times = {None: [], "device": [], "getter": []}
+        reads = []
+        for rep in range(reps + 1):
+            for log in (None, "device", "getter"):
+                r = vp_rbphd_run(pkg, "log", n, messages, log=log) if kind == "rbphd" else vp_cycle_run(pkg, "log", hyp, n, messages, log=log)
+                if rep:
+                    times[log].append(r[0])
+                    if log == "device":
+                        reads.append(r[5])
+                print("  rep %d %-7s: %.4f s/run%s, %d lidar updates, %d resamplings, final count %d%s" %
+                      (rep, log or "no log", r[0], " + %.4f s for the one read" % r[5] if log == "device" else "", r[1], r[2], r[3], "" if rep else "  (warm-up)"))
+        med = {k: float(np.median(v)) for k, v in times.items()}
+        print("%s hyp %d medians: device cycle %.4f s, with the device log %.4f s (%.3fx) + %.4f s read at the end, with per-update getters %.4f s (%.3fx)" %
+              (kind, hyp, med[None], med["device"], med["device"] / med[None], float(np.median(reads)), med["getter"], med["getter"] / med[None]))
+    sys.exit(0)
 
 if "--vp-cycle" in sys.argv and "--rbphd" in sys.argv:
     n, messages, reps = [int(os.environ.get(k, d)) for k, d in (("FS_N", 100), ("FS_MESSAGES", 900), ("FS_REPS", 3))]
