@@ -726,10 +726,11 @@ int rfsgpu_fastslam_set_resampling(rfsgpu_filter *f, double eff_n, double eff_n_
  * rfsgpu_gm_size(s), rfsgpu_get_landmark, rfsgpu_export_gm, rfsgpu_get_unused, particle ids).  Each filter has its own configuration,
  * measurement set, weights, normalisation, resampling and resampleOccured_; each equals a separate handle given the same inputs.
  * The whole-handle setters (rfsgpu_set_filter_config, _set_model_rngbrg, _set_kf_config, _set_lmk_process_noise) set every filter.
- * Not on a batch handle (RFSGPU_ERR_UNSUPPORTED, with a rfsgpu_last_error message): the Victoria Park model and
- * rfsgpu_set_laser_scan, the single-handle FastSLAM calls (rfsgpu_set_fastslam_config, rfsgpu_fastslam_update: a batch of FastSLAM
- * filters has rfsgpu_batch_set_fastslam_config / rfsgpu_batch_fastslam_cycle_async below), multi-hypothesis FastSLAM and landmark
- * candidate lists (count threshold != 1), rfsgpu_update* and the phase calls, rfsgpu_step_async*, rfsgpu_cycle_async, rfsgpu_predict_map*,
+ * Not on a batch handle (RFSGPU_ERR_UNSUPPORTED, with a rfsgpu_last_error message): the Victoria Park model, rfsgpu_set_laser_scan
+ * and rfsgpu_import_birth_candidates on a 2-D batch (a batch of Victoria Park filters has them: see below), the single-handle
+ * FastSLAM calls (rfsgpu_set_fastslam_config, rfsgpu_fastslam_update: a batch of FastSLAM filters has
+ * rfsgpu_batch_set_fastslam_config / rfsgpu_batch_fastslam_cycle_async below), multi-hypothesis FastSLAM and landmark candidate
+ * lists (count threshold != 1), rfsgpu_update* and the phase calls, rfsgpu_step_async*, rfsgpu_cycle_async, rfsgpu_predict_map*,
  * the collective calls, rfsgpu_resample_apply[_n], rfsgpu_weight_sums[_async], rfsgpu_normalize_weights[_parts] (one total for all
  * filters: rfsgpu_batch_weight_sums and the cycle's normalize instead), rfsgpu_import_birth_candidates, birth inheritance modes other
  * than RFSGPU_INHERIT_REFERENCE, and configurations with birthGaussianMeasurementCountThreshold != 1 (the births are immediate).
@@ -749,6 +750,38 @@ int rfsgpu_batch_configure(rfsgpu_filter *f, int filter, const rfsgpu_filter_con
  * weights are summed and divided as asked).  normalize != 0: each filter's weights are divided by their own sum. */
 int rfsgpu_batch_cycle_async(rfsgpu_filter *f, int predict, const double *x, const double *x_cov, int cov_stride,
                              const double *z, const int *n_z, int normalize);
+/* -- a batch of Victoria Park RB-PHD filters: rfsgpu_create_batch with RFSGPU_MODEL_VICTORIAPARK_3D (rfsgpu_create_batch_mh still
+ * refuses the model).  Each filter equals a separate Victoria Park handle given the same inputs: its own rfsgpu_filter_config with
+ * ANY birth thresholds (the birth-candidate lists are per slot, as on a handle), its own rfsgpu_vp_config, Kalman thresholds,
+ * landmark noise, measurement set and count per cycle.  All filters see the same dataset: the laser scan is the handle's
+ * (rfsgpu_set_laser_scan, rfsgpu_set_step_inputs_async, or the cycle call's scan) and each filter's clutter density is derived from
+ * it with the filter's own expectedClutterNumber, by rfsgpu_set_laser_scan's rule.  rfsgpu_set_lmk_process_noise sets every
+ * filter's Q (and nothing else of its configuration); rfsgpu_set_model_victoriapark sets every filter's model;
+ * rfsgpu_static_steps_async serves the batch as it serves a handle.  The host-stop route only: rfsgpu_batch_weight_sums,
+ * rfsgpu_batch_resample_apply (pose and mixture move; the birth state follows lazily in the next birth predicts of a filter that
+ * resampled, level by level as on a handle, until its next update with measurements) and rfsgpu_batch_resample_occured work as on a
+ * 2-D batch, and so do the per-slot getters and setters, rfsgpu_export / _import_birth_candidates and rfsgpu_get / _set_unused_masks
+ * included.  RFSGPU_ERR_UNSUPPORTED on such a batch, with a message and the state untouched: rfsgpu_batch_cycle_async, the FastSLAM
+ * and multi-hypothesis batch calls, the device loop (rfsgpu_batch_set_motion_odometry, _set_resampling, _propagate_async,
+ * _resample_async), [sensor], [truth], [metric], [estimate] and rfsgpu_rbphd_cycle_async.  rfsgpu_batch_configure on such a batch,
+ * and rfsgpu_batch_configure_vp on a 2-D batch, return RFSGPU_ERR_INVALID.  rfsgpu_last_error names the lowest filter that exceeded
+ * gm_capacity, and for a full candidate list (RFSGPU_MAX_CANDIDATES) the lowest filter with a slot whose list, with the unused
+ * measurements that could join it, stood beyond the limit in a birth predict that reported one: the filter at fault where one
+ * filter is near the limit; where several are, possibly a lower one that stayed just inside it.
+ *
+ * Filter `filter`'s configuration; a NULL pointer leaves that part as it is.  lmk_Q: the 3x3 landmark process noise, row-major. */
+int rfsgpu_batch_configure_vp(rfsgpu_filter *f, int filter, const rfsgpu_filter_config *cfg, const rfsgpu_vp_config *model,
+                              const rfsgpu_kf_config *kf, const double *lmk_Q);
+/* rfsgpu_cycle_async for every filter of a Victoria Park batch at once.  predict, x, x_cov, cov_stride, normalize: as
+ * rfsgpu_batch_cycle_async.  z: [n_filters][RFSGPU_MAX_Z][3], n_z: [n_filters]; a filter with n_z == 0 is not updated (its predict
+ * part runs, its weights are summed and divided as asked).  scan, n_scan: the laser scan that goes with the sets (2 ...
+ * RFSGPU_VP_MAX_SCAN beams), or NULL: the scan the handle holds; a batch that has never been given one: RFSGPU_ERR_INVALID.
+ * Stream-ordered, nothing is read back.  On a 2-D, FastSLAM or multi-hypothesis batch: RFSGPU_ERR_UNSUPPORTED.  A call in which
+ * every n_z is 0 is its predict part and the sums, with no step launch (a driver's birth predict at the head of a run of messages).
+ * rfsgpu_last_step_variant after it: {1, 0, particles per workgroup of the step kernel (2, or 1 where two do not fit in LDS; 0: no
+ * step launch), 1 (0: no step launch)}. */
+int rfsgpu_batch_vp_cycle_async(rfsgpu_filter *f, int predict, const double *x, const double *x_cov, int cov_stride,
+                                const double *z, const int *n_z, const double *scan, int n_scan, int normalize);
 /* {sum w, sum w^2} of each filter's current weights: out [n_filters][2].  Synchronising. */
 int rfsgpu_batch_weight_sums(rfsgpu_filter *f, double *out);
 /* Resample the filters with resampled[b] != 0: slot k takes slot src_slot[k] (global slots; a source lies in k's own block and keeps

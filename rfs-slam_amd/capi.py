@@ -172,6 +172,7 @@ ABI_SYMBOLS = [
     "batch_fastslam_serve_sensor", "batch_fastslam_cycle_sensed_async", "batch_fastslam_mh_cycle_sensed_async",
     "estimate_log_create", "estimate_log_reset", "step_estimate_async", "estimate_log_read", "batch_run_log_estimates",
     "handle_serve_estimates",
+    "batch_configure_vp", "batch_vp_cycle_async",
 ]
 
 _dp = np.ctypeslib.ndpointer(dtype=np.float64, flags="C_CONTIGUOUS")
@@ -884,20 +885,25 @@ class CBatch(CFilter):
     """A filter batch behind the C ABI ([batch] in include/rfsgpu.h): n_filters independent 2-D filters of n_per_filter particles in one
     handle, filter b in the global slots [b * n_per_filter, (b + 1) * n_per_filter).  Every per-slot method of CFilter works on it."""
 
+    MODELS = (MODEL_RNGBRG_2D,)      # what this class steps (CVPBatch: the Victoria Park model)
+
     def __init__(self, lib, prefix, n_filters, n_per_filter, model=MODEL_RNGBRG_2D, device_id=0, gm_capacity=512):
         self._lib, self._p = lib, prefix
         self.model = model
         self.device_id = device_id
-        self.dm = self.dz = 2
+        self.dm = self.dz = 3 if model == MODEL_VICTORIAPARK_3D else 2
         self._borrowed = False
         self._h = C.c_void_p()
+        if model not in self.MODELS:
+            raise EngineError(ERR_UNSUPPORTED, "create_batch: this class steps 2-D range-bearing filters; a batch of Victoria Park filters is a CVPBatch "
+                                               "(engine.VPFilterBatch), whose cycle is rfsgpu_batch_vp_cycle_async" if model == MODEL_VICTORIAPARK_3D
+                              else "create_batch: this class steps Victoria Park filters only")
         fn = self._fn("create_batch")
         fn.restype = C.c_int
         rc = fn(C.byref(self._h), C.c_int(model), C.c_int(int(n_filters)), C.c_int(int(n_per_filter)), C.c_int(device_id), C.c_int(gm_capacity))
         if rc != OK:
             self._h = C.c_void_p()
-            raise EngineError(rc, "create_batch failed: " + ("the Victoria Park model has no batch form" if rc == ERR_UNSUPPORTED and model == MODEL_VICTORIAPARK_3D
-                                                             else "no gfx950 device / bad arguments"))
+            raise EngineError(rc, "create_batch failed: no gfx950 device / bad arguments")
         self.n_filters = int(n_filters)
         self.n_per_filter = int(n_per_filter)
         self.gm_capacity = int(gm_capacity)
@@ -1142,6 +1148,71 @@ class CBatch(CFilter):
         fn = self._fn("n_filters")
         fn.restype = C.c_int
         return int(fn(self._h))
+
+
+def vp_config(R, Slb, pd_table, expected_clutter, rmax, rmin, bmax, bmin, buffer_pd):
+    """A VPConfig from the arguments of CFilter.set_model_victoriapark."""
+    m = VPConfig()
+    R = _f64(R, (9,))
+    for k in range(9):
+        m.R[k] = R[k]
+    m.Slb = Slb
+    pd_table = list(pd_table)
+    assert len(pd_table) <= VP_MAX_PD
+    for k, v in enumerate(pd_table):
+        m.PdTable[k] = v
+    m.nPd = len(pd_table)
+    m.expectedClutterNumber = expected_clutter
+    m.rangeLimMax, m.rangeLimMin, m.bearingLimitMax, m.bearingLimitMin, m.bufferZonePd = rmax, rmin, bmax, bmin, buffer_pd
+    return m
+
+
+class CVPBatch(CBatch):
+    """A batch of Victoria Park RB-PHD filters behind the C ABI (rfsgpu_create_batch with the Victoria Park model,
+    rfsgpu_batch_configure_vp, rfsgpu_batch_vp_cycle_async): filter b in the global slots [b * n_per_filter, (b + 1) * n_per_filter), one
+    laser scan for the handle, everything else per filter.  The per-slot methods of CFilter, set_laser_scan, set_lmk_process_noise,
+    static_steps_async, batch_weight_sums, batch_resample_apply and batch_resample_occured work on it; the 2-D batch calls refuse."""
+
+    MODELS = (MODEL_VICTORIAPARK_3D,)
+
+    def __init__(self, lib, prefix, n_filters, n_per_filter, device_id=0, gm_capacity=512):
+        super().__init__(lib, prefix, n_filters, n_per_filter, model=MODEL_VICTORIAPARK_3D, device_id=device_id, gm_capacity=gm_capacity)
+
+    def batch_configure_vp(self, b, cfg=None, model=None, kf=None, Q=None):
+        """Filter b's configuration: cfg a FilterConfig (any birth thresholds); model a VPConfig (vp_config) or the tuple of its
+        arguments; kf = (range_thr, bearing_thr); Q the 3x3 landmark process noise.  What is None stays."""
+        m = model if (model is None or isinstance(model, VPConfig)) else vp_config(*model)
+        k = None if kf is None else KFConfig(*kf)
+        q = None if Q is None else _f64(Q, (9,))
+        self._call("batch_configure_vp", C.c_int(int(b)), C.c_void_p(None) if cfg is None else C.byref(cfg), C.c_void_p(None) if m is None else C.byref(m),
+                   C.c_void_p(None) if k is None else C.byref(k), C.c_void_p(None) if q is None else self._ptr(q))
+
+    def batch_vp_cycle_async(self, predict, Zs, poses=None, pose_cov=None, scan=None, normalize=True):
+        """rfsgpu_batch_vp_cycle_async: Zs = one measurement array per filter ([n_z, 3], possibly empty); predict None / False / True as
+        rfsgpu_cycle_async; scan: the laser scan that goes with the sets (None: the one the handle holds)."""
+        assert len(Zs) == self.n_filters
+        z = np.zeros((self.n_filters, MAX_Z, 3))
+        nz = np.zeros(self.n_filters, dtype=np.int32)
+        for b, Z in enumerate(Zs):
+            Z = _f64(Z).reshape(-1, 3) if np.size(Z) else np.zeros((0, 3))
+            nz[b] = Z.shape[0]
+            z[b, : min(Z.shape[0], MAX_Z)] = Z[:MAX_Z]
+        self.batch_vp_cycle_async_packed(predict, z, nz, poses=poses, pose_cov=pose_cov, scan=scan, normalize=normalize)
+
+    def batch_vp_cycle_async_packed(self, predict, z, nz, poses=None, pose_cov=None, scan=None, normalize=True):
+        """The same with the sets already in the call's layout (z [n_filters, MAX_Z, 3] float64, nz [n_filters] int32, C-contiguous)."""
+        assert z.dtype == np.float64 and nz.dtype == np.int32 and z.shape == (self.n_filters, MAX_Z, 3) and z.flags.c_contiguous and nz.flags.c_contiguous
+        x = None if poses is None else _f64(poses, (self.n, 3))
+        stride = 0
+        cv = None
+        if pose_cov is not None:
+            cv = _f64(pose_cov)
+            assert cv.size in (9, 9 * self.n)
+            stride = 0 if cv.size == 9 else 9
+        s = None if scan is None else _f64(scan).reshape(-1)
+        self._call("batch_vp_cycle_async", C.c_int(-1 if predict is None else (1 if predict else 0)), C.c_void_p(None) if x is None else self._ptr(x),
+                   C.c_void_p(None) if cv is None else self._ptr(cv), C.c_int(stride), self._ptr(z), self._ptr(nz),
+                   C.c_void_p(None) if s is None else self._ptr(s), C.c_int(0 if s is None else s.size), C.c_int(1 if normalize else 0))
 
 
 class CBatchMH(CBatch):

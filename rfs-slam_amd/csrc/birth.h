@@ -423,12 +423,38 @@ __device__ __forceinline__ void birth_step_lds(const Buffers &B, const Params &P
 // them); it also does the static step of EVERY particle.  predict_map_long_kernel: the same walk on a list staged in LDS
 // (<= RFSGPU_MAX_CANDIDATES), 64 candidates at a time, for the particles the first kernel left alone.  (r02: the LDS form alone,
 // for everybody, made a birth predict of the Victoria Park run 103 us where the lane form takes 47: 20 KB of LDS per wave.)
+// predict_map_general_kernel's work for particle i as a function, for the batch form in vp_batch.h, which takes P, nZprev and B.Z from its
+// filter's tables (the kernel below keeps its own copy of the text)
+template <int D>
+__device__ __forceinline__ void predict_map_general_particle(const Buffers &B, const Params &P, const int cur, int addBirth, const int nZprev, const BirthLevel &LV,
+                                                             const int i, const int lane) {
+  const int cap = B.cap;
+  const int nOld = B.count[i];
+  addBirth = addBirth && LV.mine(i);
+  // A list that may outgrow the lanes during this call (candidates + unused measurements > 64) is left to predict_map_long_kernel,
+  // which the host launches right after this one; the static step below is done here for every particle.
+  const bool longList = addBirth && (B.candCount[i] + ((nZprev > 0) ? __popcll(B.unusedMask[i]) : 0) > 64);
+  if (addBirth && !longList) birth_step_lanes<D>(B, P, cur, i, lane, nZprev, nOld);
+  // staticStep on the pre-existing Gaussians
+  if (!LV.doStatic) return;
+  double *slab = B.slab[cur];
+  if (D == 2) {
+    double *pSXX = plane(slab, cap, i, PL_SXX), *pSXY = plane(slab, cap, i, PL_SXY), *pSYY = plane(slab, cap, i, PL_SYY);
+    for (int m = lane; m < nOld; m += 64) { pSXX[m] += P.Qlm[0]; pSXY[m] += P.Qlm[1]; pSYY[m] += P.Qlm[2]; }
+  } else {
+    for (int t = 0; t < 6; t++) {
+      double *p = plane3(slab, cap, i, P3_SXX + t);
+      for (int m = lane; m < nOld; m += 64) p[m] += P.Qlm6[t];
+    }
+  }
+}
 template <int D, int WPB>
 __global__ __launch_bounds__(WPB * 64) void predict_map_general_kernel(Buffers B, Params P, int cur, int addBirth, int nZprev, BirthLevel LV) {
   const int wave = threadIdx.x >> 6;
   const int lane = threadIdx.x & 63;
   const int i = __builtin_amdgcn_readfirstlane(blockIdx.x * WPB + wave);
   if (i >= B.N) return;
+  // (the text of predict_map_general_particle, kept in the kernel as it was written: through the function the <3, 4> instantiation took one VGPR more)
   const int cap = B.cap;
   const int nOld = B.count[i];
   addBirth = addBirth && LV.mine(i);

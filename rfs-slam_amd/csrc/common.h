@@ -80,10 +80,10 @@ struct BatchFilter {
 struct BatchArg {
   const BatchFilter *filt;   // [nF]
   const Params *params;      // [nF]
-  const double *z;           // this cycle's sets, packed (2 doubles per measurement)
-  double *zPrev;             // [nF][RFSGPU_MAX_Z * 2] each filter's last non-empty set: the next predict's births (written by the post kernel)
+  const double *z;           // this cycle's sets, packed (2 doubles per measurement; 3 in a batch of Victoria Park filters)
+  double *zPrev;             // [nF][RFSGPU_MAX_Z * 2 (* 3)] each filter's last non-empty set: the next predict's births (written by the post kernel)
   double *sums;              // [nF][2] {sum w, sum w^2} per filter (post kernel)
-  int *errFilter;            // [1] lowest filter seen at gm_capacity with the capacity bit up (INT_MAX: none)
+  int *errFilter;            // [2] lowest filter seen at gm_capacity with the capacity bit up | (vp_batch.h) with a full candidate list and that bit up (INT_MAX: none)
   int nF, nPer;
 };
 

@@ -1271,7 +1271,8 @@ __device__ __forceinline__ void batch_post_tail(double *weight, const BatchArg &
 
 // BATCH: the post kernel of a batch cycle -- the measurement sets written back per filter, the sums / division per filter; the Murty
 // jobs themselves need nothing per filter (they carry global particle indices).  ZArg and dZ / nZdoubles are then unused.
-template <int W, int WAVES_PER_EU, bool BATCH = false>
+// ZD: doubles per measurement of a batch's sets (2; 3 for a batch of Victoria Park filters, whose tables are [nF][RFSGPU_MAX_Z * 3]).
+template <int W, int WAVES_PER_EU, bool BATCH = false, int ZD = 2>
 __global__ __launch_bounds__(64 * W) __attribute__((amdgpu_waves_per_eu(WAVES_PER_EU > 0 ? WAVES_PER_EU : 1, WAVES_PER_EU > 0 ? WAVES_PER_EU : 8)))
 void murty_jobs_kernel(MurtyQueue Q, MurtyScratch MS, int *err, double *weight, int N, double *sums,
                                                                          int normalize, typename std::conditional<BATCH, BatchArg, ZArg>::type zarg, double *dZ, int nZdoubles, int *hostSeen, int ordered, StepOut SO,
@@ -1279,9 +1280,9 @@ void murty_jobs_kernel(MurtyQueue Q, MurtyScratch MS, int *err, double *weight, 
   // (a fused step carries the measurement set in its kernel arguments; the device copy the next predict reads is written here)
   if constexpr (BATCH) {
     for (int b = blockIdx.x; b < zarg.nF; b += gridDim.x) {     // (block-uniform)
-      const int n2 = 2 * zarg.filt[b].nZ;
+      const int n2 = ZD * zarg.filt[b].nZ;     // (a filter without an update this cycle keeps its previous set: nothing is written)
       const double *zs = zarg.z + zarg.filt[b].zOff;
-      for (int t = threadIdx.x; t < n2; t += blockDim.x) zarg.zPrev[(size_t)b * (RFSGPU_MAX_Z * 2) + t] = zs[t];
+      for (int t = threadIdx.x; t < n2; t += blockDim.x) zarg.zPrev[(size_t)b * (RFSGPU_MAX_Z * ZD) + t] = zs[t];
     }
   } else {
     if (blockIdx.x == 0 && dZ)
@@ -1498,7 +1499,9 @@ static inline int murty_launch(MurtyQueue &Q, MurtyScratch &MS, Buffers &B, hipS
                                                                                                       za ? *za : none, za ? B.Z : nullptr, nZdoubles, hostSeen, ordered, SO, sord);
   return hipGetLastError() == hipSuccess ? 0 : 1;
 }
-// The post launch of a batch cycle (rfsgpu_batch_cycle_async): murty_launch's choice of instance, the BATCH kernel.
+// The post launch of a batch cycle (rfsgpu_batch_cycle_async): murty_launch's choice of instance, the BATCH kernel.  ZD: doubles per
+// measurement of the batch's sets (3: rfsgpu_batch_vp_cycle_async).
+template <int ZD = 2>
 static inline int murty_launch_batch(MurtyQueue &Q, MurtyScratch &MS, Buffers &B, hipStream_t stream, const BatchArg &A, int normalize, int *hostSeen,
                                      const StepOrderArg &SOrd) {
   int blocks = std::min(MURTY_JOB_BLOCKS, Q.maxJobs);
@@ -1508,10 +1511,10 @@ static inline int murty_launch_batch(MurtyQueue &Q, MurtyScratch &MS, Buffers &B
   const StepOut none{nullptr, nullptr, 0, nullptr, nullptr, 0, 0};
   if (ordered) murty_order_kernel<<<1, 1024, 0, stream>>>(Q);
   if (hostSeen && *hostSeen == 0)
-    murty_jobs_kernel<MURTY_LIGHT_WAVES, 0, true><<<blocks, 64 * MURTY_LIGHT_WAVES, 0, stream>>>(Q, MS, B.err, B.weight, B.N, A.sums, normalize, A, nullptr, 0,
+    murty_jobs_kernel<MURTY_LIGHT_WAVES, 0, true, ZD><<<blocks, 64 * MURTY_LIGHT_WAVES, 0, stream>>>(Q, MS, B.err, B.weight, B.N, A.sums, normalize, A, nullptr, 0,
                                                                                                hostSeen, ordered, none, sord);
   else
-    murty_jobs_kernel<MURTY_JOB_WAVES, MURTY_WAVES_PER_EU, true><<<blocks, 64 * MURTY_JOB_WAVES, 0, stream>>>(Q, MS, B.err, B.weight, B.N, A.sums, normalize, A,
+    murty_jobs_kernel<MURTY_JOB_WAVES, MURTY_WAVES_PER_EU, true, ZD><<<blocks, 64 * MURTY_JOB_WAVES, 0, stream>>>(Q, MS, B.err, B.weight, B.N, A.sums, normalize, A,
                                                                                                             nullptr, 0, hostSeen, ordered, none, sord);
   return hipGetLastError() == hipSuccess ? 0 : 1;
 }

@@ -35,6 +35,7 @@
 #include "fastslam_sensed.h"
 #include "resample_plan.h"
 #include "birth_walk.h"
+#include "vp_batch.h"
 
 namespace {
 
@@ -209,16 +210,18 @@ struct rfsgpu_filter {
   std::vector<rfsgpu_rngbrg_config> bRb;
   std::vector<rfsgpu_kf_config> bKf;
   std::vector<double> bQ;             // [nF][9]
+  std::vector<rfsgpu_vp_config> bVp;  // a batch of Victoria Park filters: each filter's model ...
+  std::vector<double> bVpClutter;     // ... and its clutter density, expectedClutterNumber / FoV area of the scan that was current when it was last derived
   std::vector<int> bNZ;               // measurements of each filter's last update (its next births)
   std::vector<char> bResampled;       // RBPHDFilter::resampleOccured_ per filter
   bool bParamsDirty = true;           // the device Params table is behind the host configuration
   int bHandleWide[3] = {-1, -1, -1};  // the handle-wide Params fields the table was built with (pose covariance stride, partition mode, dense intensity)
   BatchFilter *dBFilt = nullptr;      // [nF]
   Params *dBParams = nullptr;         // [nF]
-  double *dBZ = nullptr;              // [nF][RFSGPU_MAX_Z * 2] this cycle's sets, packed
-  double *dBZPrev = nullptr;          // [nF][RFSGPU_MAX_Z * 2]
+  double *dBZ = nullptr;              // [nF][RFSGPU_MAX_Z * D] this cycle's sets, packed
+  double *dBZPrev = nullptr;          // [nF][RFSGPU_MAX_Z * D]
   double *dBSums = nullptr;           // [nF][2]
-  int *dBErrFilter = nullptr;         // [1] BatchArg::errFilter
+  int *dBErrFilter = nullptr;         // [2] BatchArg::errFilter
   unsigned long long *dBMaskTmp = nullptr;   // [N] birth inheritance: the masks before the walk
   int *dBInhSrc = nullptr;            // [N]
   PinnedRing bStage;                  // ring of the per-cycle tables (batch_push_tables)
@@ -417,12 +420,17 @@ __global__ __launch_bounds__(64) void partition_tables_kernel(const double *L, c
 }
 
 static void batch_set_all(rfsgpu_filter *f);
+static void batch_scan_clutter(rfsgpu_filter *f, double area);
 #define REFUSE_ON_BATCH(f, what)                                                                                                   \
   if ((f)->batch) return fail(f, RFSGPU_ERR_UNSUPPORTED, what " is not available on a filter batch (rfsgpu_create_batch): use the rfsgpu_batch_* calls")
 
 // (the calls that assume that every filter of a batch fills its block)
 #define REFUSE_ON_MH_BATCH(f, what)                                                                                                 \
   if ((f)->mhBatch) return fail(f, RFSGPU_ERR_UNSUPPORTED, what " is not available on a batch of multi-hypothesis FastSLAM filters (rfsgpu_create_batch_mh): it assumes that every filter fills its block")
+
+// (what a batch of Victoria Park filters does not have yet: its cycle is rfsgpu_batch_vp_cycle_async on the host-stop route)
+#define REFUSE_ON_VP_BATCH(f, what)                                                                                                  \
+  if ((f)->batch && (f)->D == 3) return fail(f, RFSGPU_ERR_UNSUPPORTED, what " is not available on a batch of Victoria Park filters (rfsgpu_create_batch with RFSGPU_MODEL_VICTORIAPARK_3D): it steps by rfsgpu_batch_vp_cycle_async, with propagation, gate and resampling on the host")
 
 static std::string batch_error_note(rfsgpu_filter *f, int e);
 static void rebuild_params(rfsgpu_filter *f) {
@@ -786,19 +794,23 @@ int rfsgpu_set_model_rngbrg(rfsgpu_filter *f, const rfsgpu_rngbrg_config *c) {
 }
 int rfsgpu_set_model_victoriapark(rfsgpu_filter *f, const rfsgpu_vp_config *c) {
   CHECK_HANDLE(f);
-  REFUSE_ON_BATCH(f, "the Victoria Park model");
+  if (f->batch && f->D != 3) { REFUSE_ON_BATCH(f, "the Victoria Park model"); }
   if (!c) return RFSGPU_ERR_INVALID;
   if (f->model != RFSGPU_MODEL_VICTORIAPARK_3D) return fail(f, RFSGPU_ERR_INVALID, "set_model_victoriapark on a handle created for another model");
   if (c->nPd < 1 || c->nPd > RFSGPU_VP_MAX_PD) return fail(f, RFSGPU_ERR_INVALID, "Pd table size out of range");
   f->vp = *c;
   rebuild_params(f);
+  if (f->batch) {     // (a whole-handle setter sets every filter, as on a 2-D batch; the densities stay until the next scan, as on a handle)
+    for (int b = 0; b < f->nF; b++) f->bVp[b] = *c;
+    f->bParamsDirty = true;
+  }
   return RFSGPU_OK;
 }
 // MeasurementModel_VictoriaPark::setLaserScan (src/MeasurementModel_VictoriaPark.cpp:267-281): the FoV area / clutter
 // intensity are a 361-term host sum; the raw scan goes to the device for the occlusion-based Pd.
 int rfsgpu_set_laser_scan(rfsgpu_filter *f, const double *scan, int n) {
   CHECK_HANDLE(f);
-  REFUSE_ON_BATCH(f, "rfsgpu_set_laser_scan");
+  if (f->batch && f->D != 3) { REFUSE_ON_BATCH(f, "rfsgpu_set_laser_scan"); }
   if (f->model != RFSGPU_MODEL_VICTORIAPARK_3D) return fail(f, RFSGPU_ERR_INVALID, "set_laser_scan needs the Victoria Park model");
   if (!scan || n < 2 || n > RFSGPU_VP_MAX_SCAN) return fail(f, RFSGPU_ERR_INVALID, "laser scan size out of range");
   double area = 0;
@@ -806,6 +818,7 @@ int rfsgpu_set_laser_scan(rfsgpu_filter *f, const double *scan, int n) {
   area += scan[0] * scan[n - 1];
   area *= sin(acos(-1) / 360) / 2;
   f->vpClutter = f->vp.expectedClutterNumber / area;
+  if (f->batch) batch_scan_clutter(f, area);     // (one scan for the handle, each filter's density from its own expectedClutterNumber)
   hipSetDevice(f->device);
   HIPCHK(hipMemcpyAsync(f->B.scan, scan, (size_t)n * sizeof(double), hipMemcpyHostToDevice, f->stream));
   HIPCHK(hipStreamSynchronize(f->stream));
@@ -845,7 +858,10 @@ int rfsgpu_set_lmk_process_noise(rfsgpu_filter *f, const double *Q) {
   if (!Q) return RFSGPU_ERR_INVALID;
   memcpy(f->Qlm, Q, (size_t)f->D * f->D * sizeof(double));
   rebuild_params(f);
-  if (f->batch) batch_set_all(f);
+  if (f->batch && f->D == 3) {      // a batch of Victoria Park filters: every filter's Q, and nothing else of its configuration
+    for (int b = 0; b < f->nF; b++) memcpy(&f->bQ[(size_t)9 * b], Q, 9 * sizeof(double));
+    f->bParamsDirty = true;
+  } else if (f->batch) batch_set_all(f);
   return RFSGPU_OK;
 }
 
@@ -1043,7 +1059,7 @@ int rfsgpu_export_birth_candidates(rfsgpu_filter *f, int slot, int max_n, int *n
 }
 int rfsgpu_import_birth_candidates(rfsgpu_filter *f, int slot, int n, const double *mean, const double *cov, const int *n_support, const int *n_checks) {
   CHECK_HANDLE(f);
-  REFUSE_ON_BATCH(f, "rfsgpu_import_birth_candidates");
+  if (f->batch && f->D != 3) { REFUSE_ON_BATCH(f, "rfsgpu_import_birth_candidates"); }
   if (slot < 0 || slot >= f->N || n < 0 || n > RFSGPU_MAX_CANDIDATES) return fail(f, RFSGPU_ERR_INVALID, "import_birth_candidates: bad arguments");
   hipSetDevice(f->device);
   if (n > 0) f->candUsed = true;
@@ -2170,6 +2186,7 @@ static int push_scan(rfsgpu_filter *f, double *hs, const double *scan, int n_sca
   area += scan[0] * scan[n_scan - 1];
   area *= sin(acos(-1) / 360) / 2;
   f->vpClutter = f->vp.expectedClutterNumber / area;
+  if (f->batch) batch_scan_clutter(f, area);
   memcpy(hs, scan, (size_t)n_scan * sizeof(double));
   HIPCHK(hipMemcpyAsync(f->B.scan, hs, (size_t)n_scan * sizeof(double), hipMemcpyHostToDevice, f->stream));
   f->B.nScan = n_scan;
@@ -3369,6 +3386,13 @@ static std::string batch_error_note(rfsgpu_filter *f, int e) {
       hipMemcpy(f->dBErrFilter, &none, sizeof(int), hipMemcpyHostToDevice);
     add(b >= 0 && b < f->nF ? "gm_capacity exceeded in filter " + std::to_string(b) : std::string("gm_capacity exceeded, filter not identified"));
   }
+  if ((e & ERRBIT_BIRTHLIST) && f->D == 3) {     // (vp_batch.h: the second word of errFilter)
+    int b = INT_MAX;
+    const int none = INT_MAX;
+    if (hipMemcpy(&b, f->dBErrFilter + 1, sizeof(int), hipMemcpyDeviceToHost) == hipSuccess)
+      hipMemcpy(f->dBErrFilter + 1, &none, sizeof(int), hipMemcpyHostToDevice);
+    add(b >= 0 && b < f->nF ? "candidate list full in filter " + std::to_string(b) : std::string("candidate list full, filter not identified"));
+  }
   if (e & ERRBIT_EVALPTS) {
     int b = -1;
     for (int q = 0; q < f->nF && b < 0; q++) {
@@ -3394,6 +3418,12 @@ static void batch_set_all(rfsgpu_filter *f) {
   }
   f->bParamsDirty = true;
 }
+// setLaserScan for every filter of a Victoria Park batch: the density rfsgpu_set_laser_scan derives on a handle, from the filter's own
+// expectedClutterNumber as it is configured now (a later rfsgpu_batch_configure_vp leaves it until the next scan, as the handle's setter does)
+static void batch_scan_clutter(rfsgpu_filter *f, double area) {
+  for (int b = 0; b < f->nF; b++) f->bVpClutter[b] = f->bVp[b].expectedClutterNumber / area;
+  f->bParamsDirty = true;
+}
 // Params of filter b: the handle's own rule (rebuild_params) on the filter's configuration; the handle-wide fields (pose covariance
 // stride, partition mode, dense intensity) are the handle's.
 static Params batch_params(rfsgpu_filter *f, int b) {
@@ -3403,17 +3433,21 @@ static Params batch_params(rfsgpu_filter *f, int b) {
   double Q[9];
   memcpy(Q, f->Qlm, sizeof Q);
   const Params keep = f->P;
+  const rfsgpu_vp_config vp = f->vp;
+  const double vpClutter = f->vpClutter;
   f->cfg = f->bCfg[b]; f->rb = f->bRb[b]; f->kf = f->bKf[b];
+  if (f->D == 3) { f->vp = f->bVp[b]; f->vpClutter = f->bVpClutter[b]; }
   memcpy(f->Qlm, &f->bQ[(size_t)9 * b], sizeof Q);
   rebuild_params(f);
   const Params out = f->P;
   f->cfg = cfg; f->rb = rb; f->kf = kf;
+  f->vp = vp; f->vpClutter = vpClutter;
   memcpy(f->Qlm, Q, sizeof Q);
   f->P = keep;
   return out;
 }
 static size_t batch_stage_bytes(const rfsgpu_filter *f) {
-  return (size_t)f->nF * (std::max(sizeof(MhBatchFilter), std::max(sizeof(BatchFilter), sizeof(FsBatchFilter))) + sizeof(Params) + RFSGPU_MAX_Z * 2 * sizeof(double) + sizeof(int)) + (size_t)f->N * sizeof(int);
+  return (size_t)f->nF * (std::max(sizeof(MhBatchFilter), std::max(sizeof(BatchFilter), sizeof(FsBatchFilter))) + sizeof(Params) + RFSGPU_MAX_Z * (size_t)f->D * sizeof(double) + sizeof(int)) + (size_t)f->N * sizeof(int);
 }
 // The handle-wide Params fields of a cycle (both kinds of batch): the pose covariance stride the call's x / x_cov ask for, and whatever
 // else of f->P every filter's record repeats; the table is rewritten when one of them has changed.
@@ -3476,19 +3510,20 @@ static int batch_push_tables(rfsgpu_filter *f, Rec *dRec, const double *z, const
     f->bParamsDirty = false;
   }
   int zOff = 0;
+  const int zd = f->D;     // doubles per measurement (3: a batch of Victoria Park filters)
   for (int b = 0; b < nF; b++) {
     Rec &T = hf[b];
     memset(&T, 0, sizeof T);
     T.nZ = n_z[b];
     T.zOff = zOff;
     fill(T, b);
-    if (n_z[b] > 0) memcpy(hz + zOff, z + (size_t)b * RFSGPU_MAX_Z * 2, (size_t)n_z[b] * 2 * sizeof(double));
-    zOff += 2 * n_z[b];
+    if (n_z[b] > 0) memcpy(hz + zOff, z + (size_t)b * RFSGPU_MAX_Z * zd, (size_t)n_z[b] * zd * sizeof(double));
+    zOff += zd * n_z[b];
   }
   HIPCHK(hipMemcpyAsync(dRec, hf, (size_t)nF * sizeof(Rec), hipMemcpyHostToDevice, f->stream));
   if (zOff) HIPCHK(hipMemcpyAsync(f->dBZ, hz, (size_t)zOff * sizeof(double), hipMemcpyHostToDevice, f->stream));
   if (extra) {
-    void *he = hz + (size_t)nF * RFSGPU_MAX_Z * 2;
+    void *he = hz + (size_t)nF * RFSGPU_MAX_Z * zd;
     memcpy(he, extra, extraBytes);
     HIPCHK(hipMemcpyAsync(dExtra, he, extraBytes, hipMemcpyHostToDevice, f->stream));
   }
@@ -3564,14 +3599,16 @@ static int batch_push_poses(rfsgpu_filter *f, const double *x, const double *x_c
 int rfsgpu_create_batch(rfsgpu_filter **out, int model, int n_filters, int n_per_filter, int device_id, int gm_capacity) {
   if (!out) return RFSGPU_ERR_INVALID;
   *out = nullptr;
-  if (model == RFSGPU_MODEL_VICTORIAPARK_3D) return RFSGPU_ERR_UNSUPPORTED;    // (2-D range-bearing filters only)
-  if (model != RFSGPU_MODEL_RNGBRG_2D || n_filters < 1 || n_per_filter < 1 || (long long)n_filters * n_per_filter > (1 << 24)) return RFSGPU_ERR_INVALID;
+  if ((model != RFSGPU_MODEL_RNGBRG_2D && model != RFSGPU_MODEL_VICTORIAPARK_3D) || n_filters < 1 || n_per_filter < 1 || (long long)n_filters * n_per_filter > (1 << 24)) return RFSGPU_ERR_INVALID;
   rfsgpu_filter *f = nullptr;
   int rc = rfsgpu_create(&f, model, n_filters * n_per_filter, device_id, gm_capacity);
   if (rc != RFSGPU_OK) return rc;
   f->batch = true;
   f->nF = n_filters;
   f->nPer = n_per_filter;
+  const size_t zd = (size_t)f->D;     // doubles per measurement in the sets' tables
+  if (f->D == 3) f->bKind = 1;        // (a batch of Victoria Park filters steps RB-PHD filters: rfsgpu_batch_vp_cycle_async)
+  f->bVp.assign(n_filters, f->vp); f->bVpClutter.assign(n_filters, 0.0);
   f->bCfg.resize(n_filters); f->bRb.resize(n_filters); f->bKf.resize(n_filters); f->bQ.assign((size_t)9 * n_filters, 0.0);
   f->bNZ.assign(n_filters, 0);
   f->bResampled.assign(n_filters, 0);
@@ -3586,14 +3623,14 @@ int rfsgpu_create_batch(rfsgpu_filter **out, int model, int n_filters, int n_per
   ok &= hipMalloc(&f->dBFilt, (size_t)n_filters * sizeof(BatchFilter)) == hipSuccess;
   ok &= hipMalloc(&f->dBParams, (size_t)n_filters * sizeof(Params)) == hipSuccess;
   ok &= hipMalloc(&f->dFsFilt, (size_t)n_filters * sizeof(FsBatchFilter)) == hipSuccess;
-  ok &= hipMalloc(&f->dBZ, (size_t)n_filters * RFSGPU_MAX_Z * 2 * sizeof(double)) == hipSuccess;
-  ok &= hipMalloc(&f->dBZPrev, (size_t)n_filters * RFSGPU_MAX_Z * 2 * sizeof(double)) == hipSuccess;
+  ok &= hipMalloc(&f->dBZ, (size_t)n_filters * RFSGPU_MAX_Z * zd * sizeof(double)) == hipSuccess;
+  ok &= hipMalloc(&f->dBZPrev, (size_t)n_filters * RFSGPU_MAX_Z * zd * sizeof(double)) == hipSuccess;
   ok &= hipMalloc(&f->dBSums, (size_t)n_filters * 2 * sizeof(double)) == hipSuccess;
-  ok &= hipMalloc(&f->dBErrFilter, sizeof(int)) == hipSuccess;
-  if (ok) { const int none = INT_MAX; ok &= hipMemcpy(f->dBErrFilter, &none, sizeof(int), hipMemcpyHostToDevice) == hipSuccess; }
+  ok &= hipMalloc(&f->dBErrFilter, 2 * sizeof(int)) == hipSuccess;
+  if (ok) { const int none[2] = {INT_MAX, INT_MAX}; ok &= hipMemcpy(f->dBErrFilter, none, sizeof none, hipMemcpyHostToDevice) == hipSuccess; }
   ok &= hipMalloc(&f->dBMaskTmp, (size_t)f->Ncap * sizeof(unsigned long long)) == hipSuccess;
   ok &= hipMalloc(&f->dBInhSrc, (size_t)f->Ncap * sizeof(int)) == hipSuccess;
-  if (ok) ok &= hipMemset(f->dBZPrev, 0, (size_t)n_filters * RFSGPU_MAX_Z * 2 * sizeof(double)) == hipSuccess;
+  if (ok) ok &= hipMemset(f->dBZPrev, 0, (size_t)n_filters * RFSGPU_MAX_Z * zd * sizeof(double)) == hipSuccess;
   if (ok) ok &= hipMemset(f->dBSums, 0, (size_t)n_filters * 2 * sizeof(double)) == hipSuccess;
   // the device loop's tables (batch_loop.h)
   f->bMotionSet.assign(n_filters, 0); f->bResSet.assign(n_filters, 0);
@@ -3641,12 +3678,30 @@ int rfsgpu_batch_configure(rfsgpu_filter *f, int filter, const rfsgpu_filter_con
   int rc = batch_check(f, filter);
   if (rc != RFSGPU_OK) return rc;
   if (filter < 0) return fail(f, RFSGPU_ERR_INVALID, "batch_configure: filter index out of range");
+  if (f->model != RFSGPU_MODEL_RNGBRG_2D) return fail(f, RFSGPU_ERR_INVALID, "batch_configure on a batch created for another model (rfsgpu_batch_configure_vp)");
   if (cfg && cfg->birthGaussianMeasurementCountThreshold != 1u)
     return fail(f, RFSGPU_ERR_UNSUPPORTED, "batch_configure: a filter batch takes immediate births only (birthGaussianMeasurementCountThreshold 1)");
   if (cfg) f->bCfg[filter] = *cfg;
   if (model) f->bRb[filter] = *model;
   if (kf) f->bKf[filter] = *kf;
   if (lmk_Q) memcpy(&f->bQ[(size_t)9 * filter], lmk_Q, 4 * sizeof(double));
+  f->bParamsDirty = true;
+  return RFSGPU_OK;
+}
+// The same for a filter of a Victoria Park batch: every birth threshold is allowed (the candidate lists are per slot, as on a handle).
+// lmk_Q: 3x3, row-major.  The filter's clutter density stays what the last scan made it until the next one, as rfsgpu_set_model_victoriapark leaves it on a handle.
+int rfsgpu_batch_configure_vp(rfsgpu_filter *f, int filter, const rfsgpu_filter_config *cfg, const rfsgpu_vp_config *model, const rfsgpu_kf_config *kf,
+                              const double *lmk_Q) {
+  CHECK_HANDLE(f);
+  int rc = batch_check(f, filter);
+  if (rc != RFSGPU_OK) return rc;
+  if (filter < 0) return fail(f, RFSGPU_ERR_INVALID, "batch_configure_vp: filter index out of range");
+  if (f->model != RFSGPU_MODEL_VICTORIAPARK_3D) return fail(f, RFSGPU_ERR_INVALID, "batch_configure_vp on a batch created for another model (rfsgpu_batch_configure)");
+  if (model && (model->nPd < 1 || model->nPd > RFSGPU_VP_MAX_PD)) return fail(f, RFSGPU_ERR_INVALID, "batch_configure_vp: Pd table size out of range");
+  if (cfg) f->bCfg[filter] = *cfg;
+  if (model) f->bVp[filter] = *model;
+  if (kf) f->bKf[filter] = *kf;
+  if (lmk_Q) memcpy(&f->bQ[(size_t)9 * filter], lmk_Q, 9 * sizeof(double));
   f->bParamsDirty = true;
   return RFSGPU_OK;
 }
@@ -3659,6 +3714,7 @@ int rfsgpu_batch_cycle_async(rfsgpu_filter *f, int predict, const double *x, con
   int rc = batch_check(f, -1);
   if (rc != RFSGPU_OK) return rc;
   REFUSE_ON_MH_BATCH(f, "rfsgpu_batch_cycle_async");
+  REFUSE_ON_VP_BATCH(f, "rfsgpu_batch_cycle_async");
   if ((rc = batch_check_call(f, BATCH_CYCLE, predict, x_cov, cov_stride, n_z)) != RFSGPU_OK) return rc;
   for (int b = 0; b < f->nF; b++) {
     if ((rc = batch_check_filter(f, BATCH_CYCLE, b, z, n_z)) != RFSGPU_OK) return rc;
@@ -3791,6 +3847,144 @@ static int batch_cycle_core(rfsgpu_filter *f, int predict, const double *x, cons
   f->timing.mapUpdate_cpu += now_ns() - t0;
   return RFSGPU_OK;
 }
+// ---- a batch of Victoria Park RB-PHD filters (vp_batch.h): rfsgpu_cycle_async of every filter's own handle in one launch chain --
+// the per-cycle tables -> [inheritance walk +] births + static step (the BATCH forms of the general birth kernels) -> the host's
+// poses and scan by copy command -> the BATCH form of the Victoria Park step -> the batch post kernel (sets kept per filter, Murty
+// jobs, per-filter sums / division).  Nothing is read back.
+static const BatchCall BATCH_VP_CYCLE{"batch_vp_cycle", -1, "RFSGPU_CYCLE_NO_PREDICT (-1), 0 (static step only) or 1 (births + static step)", "null measurement counts"};
+static void launch_predict_kernels_vp_batch(rfsgpu_filter *f, int add_birth, const BirthLevel &LV, const BatchArg &A) {
+  predict_map_general_batch_kernel<3, 4><<<(f->N + 3) / 4, 256, 0, f->stream>>>(f->B, f->cur, add_birth ? 1 : 0, LV, A);
+  if (add_birth) predict_map_long_batch_kernel<3, 2><<<(f->N + 1) / 2, 128, 0, f->stream>>>(f->B, f->cur, LV, A);   // (lists longer than a wavefront; the others exit at once)
+}
+static int batch_vp_cycle_core(rfsgpu_filter *f, int predict, const double *x, const double *x_cov, int cov_stride, const double *z, const int *n_z, const double *scan,
+                               int n_scan, int normalize) {
+  const int nF = f->nF, nPer = f->nPer, N = f->N;
+  int rc = RFSGPU_OK, nZmax = 0, ecMax = 1;
+  for (int b = 0; b < nF; b++) { nZmax = std::max(nZmax, n_z[b]); ecMax = std::max(ecMax, batch_eval_cap(f, b)); }
+  hipSetDevice(f->device);
+  long long t0 = now_ns();
+  batch_handle_wide(f, x, x_cov, cov_stride);
+  // the call's scan: every filter's clutter density on the host (it travels in the Params table), the beams by copy command below
+  if (scan) {
+    double area = 0;
+    for (int q = 1; q < n_scan; q++) area += scan[q] * scan[q - 1];
+    area += scan[0] * scan[n_scan - 1];
+    area *= sin(acos(-1) / 360) / 2;
+    f->vpClutter = f->vp.expectedClutterNumber / area;
+    batch_scan_clutter(f, area);
+  }
+  // The reference's lazy copy of the per-slot birth state (RBPHDFilter.hpp:1005-1011) for the filters that have resampled since their
+  // last update with measurements: predict_launch's parent and level tables, built across the batch.  A parent lies inside its filter's
+  // block; a filter whose flag is clear keeps every slot its own parent, whatever idParent_ an older resampling left it.
+  ensure_ids(f);
+  bool walk = false;
+  int maxLevel = 0;
+  if (predict == 1) {
+    f->hInhParent.resize(N);
+    f->hInhLevel.resize(N);
+    for (int b = 0; b < nF; b++) {
+      const int lo = b * nPer, hi = lo + nPer;
+      for (int i = lo; i < hi; i++) {
+        int p = f->bResampled[b] ? f->ppid[i] : i;
+        if (p < lo || p >= hi) p = i;
+        f->hInhParent[i] = p;
+        f->hInhLevel[i] = (p >= i) ? 0 : f->hInhLevel[p] + 1;
+        walk |= p != i;
+        maxLevel = std::max(maxLevel, f->hInhLevel[i]);
+      }
+    }
+  }
+  rc = batch_push_tables(f, f->dBFilt, z, n_z, nullptr, 0, nullptr, [&](BatchFilter &F, int b) {
+    F.nZprev = f->bNZ[b];
+    F.evalCap = batch_eval_cap(f, b);
+    F.useW = f->bCfg[b].useClusterProcess ? 0 : 1;
+  });
+  if (rc != RFSGPU_OK) return rc;
+  const BatchArg A{f->dBFilt, f->dBParams, f->dBZ, f->dBZPrev, f->dBSums, f->dBErrFilter, nF, nPer};
+  if (predict >= 0) {
+    const BirthLevel all{nullptr, 0, 1};
+    if (!walk) {
+      launch_predict_kernels_vp_batch(f, predict, all, A);
+    } else {
+      if ((rc = inherit_buffers(f)) != RFSGPU_OK) return rc;
+      // (pageable host vectors: hipMemcpyAsync from them returns after the copy has been staged, so they may be reused at once)
+      HIPCHK(hipMemcpyAsync(f->dInhParent, f->hInhParent.data(), (size_t)N * sizeof(int), hipMemcpyHostToDevice, f->stream));
+      HIPCHK(hipMemcpyAsync(f->dInhLevel, f->hInhLevel.data(), (size_t)N * sizeof(int), hipMemcpyHostToDevice, f->stream));
+      birth_inherit_kernel<0><<<N, 128, 0, f->stream>>>(f->B, f->inhTmp, f->dInhParent, f->dInhLevel, 0);
+      birth_inherit_kernel<1><<<N, 128, 0, f->stream>>>(f->B, f->inhTmp, f->dInhParent, f->dInhLevel, 0);
+      launch_predict_kernels_vp_batch(f, 1, BirthLevel{f->dInhLevel, 0, 1}, A);
+      for (int L = 1; L <= maxLevel; L++) {     // (the deepest chain over all filters)
+        birth_inherit_kernel<2><<<N, 128, 0, f->stream>>>(f->B, f->inhTmp, f->dInhParent, f->dInhLevel, L);
+        launch_predict_kernels_vp_batch(f, 1, BirthLevel{f->dInhLevel, L, 0}, A);
+      }
+    }
+    HIPCHK(hipGetLastError());
+    f->candUsed = true;
+  }
+  // the host's new poses / covariances and the scan, behind the births (which happen at the poses the last update used)
+  if (x || scan) {
+    double *h = nullptr;
+    int ks = 0;
+    if ((rc = ring_acquire(f, f->stage, &h, &ks)) != RFSGPU_OK) return rc;
+    if (x) {
+      f->bBirthAlt = false;
+      if ((rc = push_poses(f, h, f->B.pose, x, x_cov, cov_stride)) != RFSGPU_OK) return rc;
+    }
+    if (scan) {
+      double *hs = h + (size_t)f->Ncap * 22;
+      memcpy(hs, scan, (size_t)n_scan * sizeof(double));
+      HIPCHK(hipMemcpyAsync(f->B.scan, hs, (size_t)n_scan * sizeof(double), hipMemcpyHostToDevice, f->stream));
+      f->B.nScan = n_scan;
+    }
+    HIPCHK(hipEventRecord(f->stage.ev[ks], f->stream));
+  }
+  // two particles per workgroup where two waves' areas fit beside the scan (the handle's rule and its 64 KiB bound), else one
+  const size_t scanB = vp_batch_scan_lds_bytes(f->B.nScan), stride = vp_batch_lds_stride(f->cap, ecMax, nZmax);
+  const int wpb = scanB + 2 * stride <= (size_t)64 * 1024 ? 2 : 1;
+  const size_t lds = scanB + (size_t)wpb * stride;
+  f->lastStepVariant[0] = 1; f->lastStepVariant[1] = 0; f->lastStepVariant[2] = wpb; f->lastStepVariant[3] = 1;
+  f->bLastCycleLds = (long long)lds;
+  if ((rc = vp_order_buffers(f)) != RFSGPU_OK) return rc;
+  // A cycle in which no filter has measurements is its predict and the sums (what rfsgpu_cycle_async does for an empty set): no step
+  // launch, the mixtures stay in their slab.  The drivers use it for the birth predict at the head of a run of input messages.
+  const bool anyUpdate = nZmax > 0;
+  const int *vpOrd = f->vpOrderMode ? f->vpOrder : nullptr;
+  const bool sortCosts = anyUpdate && f->vpOrderMode == 2;
+  const StepOrderArg sord{sortCosts ? f->vpCost : nullptr, f->vpOrder, N, f->vpCost + f->Ncap, f->vpParity};
+  if (sortCosts) f->vpParity ^= 1;
+  if (!anyUpdate) {
+    f->lastStepVariant[2] = 0; f->lastStepVariant[3] = 0;
+  } else if (wpb == 2) {
+    if ((rc = set_lds(f, vp_step_fused_batch_kernel<2>, lds)) != RFSGPU_OK) return rc;
+    vp_step_fused_batch_kernel<2><<<(N + 1) / 2, 128, lds, f->stream>>>(f->B, f->cur, f->Q, A, nZmax, ecMax, f->vpCost, vpOrd);
+  } else {
+    if ((rc = set_lds(f, vp_step_fused_batch_kernel<1>, lds)) != RFSGPU_OK) return rc;
+    vp_step_fused_batch_kernel<1><<<N, 64, lds, f->stream>>>(f->B, f->cur, f->Q, A, nZmax, ecMax, f->vpCost, vpOrd);
+  }
+  HIPCHK(hipGetLastError());
+  if (murty_launch_batch<3>(f->Q, f->MS, f->B, f->stream, A, normalize, f->hJobCount, sord) != 0) return fail(f, RFSGPU_ERR_HIP, "batch post kernel launch failed");
+  if (anyUpdate) f->cur ^= 1;   // (filters without an update had their mixture moved to the new slab by the step kernel)
+  for (int b = 0; b < nF; b++)
+    if (n_z[b] > 0) { f->bNZ[b] = n_z[b]; f->bResampled[b] = 0; }
+  f->holes = false;
+  f->timing.mapUpdate_cpu += now_ns() - t0;
+  return RFSGPU_OK;
+}
+int rfsgpu_batch_vp_cycle_async(rfsgpu_filter *f, int predict, const double *x, const double *x_cov, int cov_stride, const double *z, const int *n_z,
+                                const double *scan, int n_scan, int normalize) {
+  CHECK_HANDLE(f);
+  int rc = batch_check(f, -1);
+  if (rc != RFSGPU_OK) return rc;
+  if (f->D != 3)
+    return fail(f, RFSGPU_ERR_UNSUPPORTED, "batch_vp_cycle: this batch steps 2-D filters (rfsgpu_batch_cycle_async, rfsgpu_batch_fastslam_cycle_async or rfsgpu_batch_fastslam_mh_cycle_async): the Victoria Park cycle needs a batch created with RFSGPU_MODEL_VICTORIAPARK_3D");
+  if ((rc = batch_check_call(f, BATCH_VP_CYCLE, predict, x_cov, cov_stride, n_z)) != RFSGPU_OK) return rc;
+  for (int b = 0; b < f->nF; b++)
+    if ((rc = batch_check_filter(f, BATCH_VP_CYCLE, b, z, n_z)) != RFSGPU_OK) return rc;
+  if (scan && (n_scan < 2 || n_scan > RFSGPU_VP_MAX_SCAN)) return batch_fail(f, BATCH_VP_CYCLE, "laser scan size out of range (2 ... RFSGPU_VP_MAX_SCAN beams)");
+  if (!scan && f->B.nScan < 2) return batch_fail(f, BATCH_VP_CYCLE, "the batch has not been given a laser scan (rfsgpu_set_laser_scan, or this call's scan)");
+  return batch_vp_cycle_core(f, predict, x, x_cov, cov_stride, z, n_z, scan, n_scan, normalize);
+}
+
 // ---- a batch of FastSLAM filters: FastSLAM::predict's map part + the single-hypothesis FastSLAM::update (include/FastSLAM.hpp:376-383,
 // :387-706) of every filter in one launch chain -- [predict] -> associate + Kalman update + weights -> prune -> new landmarks -> per-filter
 // sums / division.  Nothing synchronises: errors reach the host through the shared error word, as with rfsgpu_batch_cycle_async.
@@ -3798,6 +3992,7 @@ int rfsgpu_batch_set_fastslam_config(rfsgpu_filter *f, int filter, const rfsgpu_
   CHECK_HANDLE(f);
   int rc = batch_check(f, filter);
   if (rc != RFSGPU_OK) return rc;
+  REFUSE_ON_VP_BATCH(f, "rfsgpu_batch_set_fastslam_config");
   if (!cfg) return fail(f, RFSGPU_ERR_INVALID, "batch_set_fastslam_config: null configuration");
   const std::string who = filter < 0 ? std::string("every filter") : "filter " + std::to_string(filter);
   if (f->mhBatch) {
@@ -3825,6 +4020,7 @@ int rfsgpu_batch_fastslam_cycle_async(rfsgpu_filter *f, int predict, const doubl
   CHECK_HANDLE(f);
   int rc = batch_check(f, -1);
   if (rc != RFSGPU_OK) return rc;
+  REFUSE_ON_VP_BATCH(f, "rfsgpu_batch_fastslam_cycle_async");
   REFUSE_ON_MH_BATCH(f, "rfsgpu_batch_fastslam_cycle_async");
   if ((rc = batch_check_call(f, BATCH_FS_CYCLE, predict, x_cov, cov_stride, n_z)) != RFSGPU_OK) return rc;
   const int nF = f->nF;
@@ -4215,6 +4411,7 @@ int rfsgpu_batch_set_motion_odometry(rfsgpu_filter *f, int filter, const double 
   CHECK_HANDLE(f);
   int rc = batch_check(f, filter);
   if (rc != RFSGPU_OK) return rc;
+  REFUSE_ON_VP_BATCH(f, "rfsgpu_batch_set_motion_odometry");
   if (!var || !(var[0] >= 0.0) || !(var[1] >= 0.0) || !(var[2] >= 0.0)) return fail(f, RFSGPU_ERR_INVALID, "batch_set_motion_odometry: var is three variances >= 0");
   for (int b = (filter < 0 ? 0 : filter); b < (filter < 0 ? f->nF : filter + 1); b++) {
     BatchMotion &M = f->bMotion[b];
@@ -4229,6 +4426,7 @@ int rfsgpu_batch_set_resampling(rfsgpu_filter *f, int filter, double eff_n, doub
   CHECK_HANDLE(f);
   int rc = batch_check(f, filter);
   if (rc != RFSGPU_OK) return rc;
+  REFUSE_ON_VP_BATCH(f, "rfsgpu_batch_set_resampling");
   for (int b = (filter < 0 ? 0 : filter); b < (filter < 0 ? f->nF : filter + 1); b++) {
     f->bEffN[2 * (size_t)b] = eff_n; f->bEffN[2 * (size_t)b + 1] = eff_n_percent;
     f->bResSet[b] = 1;
@@ -4252,6 +4450,7 @@ int rfsgpu_batch_propagate_async(rfsgpu_filter *f, const double *u, const double
   CHECK_HANDLE(f);
   int rc = batch_check(f, -1);
   if (rc != RFSGPU_OK) return rc;
+  REFUSE_ON_VP_BATCH(f, "rfsgpu_batch_propagate_async");
   if (!u) return fail(f, RFSGPU_ERR_INVALID, "batch_propagate: null odometry input");
   const int nF = f->nF;
   for (int b = 0; b < nF; b++) {
@@ -4301,6 +4500,7 @@ int rfsgpu_batch_resample_async(rfsgpu_filter *f, const int *n_z, unsigned long 
   CHECK_HANDLE(f);
   int rc = batch_check(f, -1);
   if (rc != RFSGPU_OK) return rc;
+  REFUSE_ON_VP_BATCH(f, "rfsgpu_batch_resample_async");
   REFUSE_ON_MH_BATCH(f, "rfsgpu_batch_resample_async");
   if ((rc = batch_check_call(f, BATCH_RESAMPLE, 0, nullptr, 0, n_z)) != RFSGPU_OK) return rc;
   if (f->bSensed)
@@ -4369,6 +4569,7 @@ int rfsgpu_batch_last_resample(rfsgpu_filter *f, unsigned char *fired, int *src_
   CHECK_HANDLE(f);
   int rc = batch_check(f, -1);
   if (rc != RFSGPU_OK) return rc;
+  REFUSE_ON_VP_BATCH(f, "rfsgpu_batch_last_resample");
   REFUSE_ON_MH_BATCH(f, "rfsgpu_batch_last_resample");
   hipSetDevice(f->device);
   if (!f->bDevRoute) {     // no rfsgpu_batch_resample_async yet: nothing fired
@@ -4400,6 +4601,7 @@ int rfsgpu_batch_resample_counts(rfsgpu_filter *f, long long *out) {
   CHECK_HANDLE(f);
   int rc = batch_check(f, -1);
   if (rc != RFSGPU_OK) return rc;
+  REFUSE_ON_VP_BATCH(f, "rfsgpu_batch_resample_counts");
   REFUSE_ON_MH_BATCH(f, "rfsgpu_batch_resample_counts");
   if (!out) return fail(f, RFSGPU_ERR_INVALID, "batch_resample_counts: null output");
   hipSetDevice(f->device);
@@ -4419,6 +4621,10 @@ static const BatchCall BATCH_LAST_SCAN{"batch_last_scan", 0, nullptr, nullptr};
 // draw), which the sensed cycle of their kind derives on the device (fastslam_sensed.h); the switch is off at creation, so the refusals
 // the section was published with stand until a caller asks.
 static int sensor_check(rfsgpu_filter *f, const BatchCall &C) {
+  if (f->batch && f->D == 3) {
+    f->err = std::string(C.who) + ": the device sensor is a 2-D range-bearing sensor: it does not serve a batch of Victoria Park filters";
+    return RFSGPU_ERR_UNSUPPORTED;
+  }
   const bool served = f->batch && f->bServeSensor;
   const char *why = !f->batch ? (f->groupShard ? "a shard of an rfsgpu_group" : "an ordinary handle")
                               : (served ? nullptr : (f->mhBatch ? "a batch of multi-hypothesis FastSLAM filters (rfsgpu_create_batch_mh)" : (f->bKind == 2 ? "a batch of FastSLAM filters" : nullptr)));
@@ -5021,6 +5227,10 @@ static const BatchCall BATCH_GENERATE_TRUTH{"batch_generate_truth", 0, nullptr, 
 static const BatchCall BATCH_GET_TRUTH{"batch_get_truth", 0, nullptr, nullptr};
 static const BatchCall BATCH_RUN_TRUTH{"batch_run_truth", 0, nullptr, nullptr};
 static int truth_check(rfsgpu_filter *f, const BatchCall &C) {
+  if (f->batch && f->D == 3) {
+    f->err = std::string(C.who) + ": the device truth draws 2-D odometry runs: it does not serve a batch of Victoria Park filters";
+    return RFSGPU_ERR_UNSUPPORTED;
+  }
   if (f->batch) return RFSGPU_OK;
   f->err = std::string(C.who) + ": the device truth serves filter batches only, not " + (f->groupShard ? "a shard of an rfsgpu_group" : "an ordinary handle");
   return RFSGPU_ERR_UNSUPPORTED;

@@ -562,6 +562,36 @@ class FilterBatch(capi.CBatch):
         return fired, plan
 
 
+class VPFilterBatch(capi.CVPBatch):
+    """n_filters independent Victoria Park RB-PHD filters stepped together (rfsgpu_create_batch with the Victoria Park model,
+    rfsgpu_batch_vp_cycle_async): per cycle the births and the static step, the fused Victoria Park step and the post launch, one chain
+    for all filters.  Filter b owns the global slots [b * n_per_filter, (b + 1) * n_per_filter) and has its own configuration (any
+    birth thresholds: the candidate lists are per slot), model, measurement set, weights, normalisation and resampling; the laser scan
+    is the batch's.  Each filter equals a separate Victoria Park RBPHDFilter given the same inputs."""
+
+    def __init__(self, n_filters, n_per_filter, device_id=0, gm_capacity=512):
+        super().__init__(load_library(), "rfsgpu_", n_filters, n_per_filter, device_id=device_id, gm_capacity=gm_capacity)
+        self.configs = [self.default_filter_config() for _ in range(n_filters)]
+        self.nUpdatesSinceResample = np.zeros(n_filters, dtype=np.int64)
+        self.nMeasurementsSinceResample = np.zeros(n_filters, dtype=np.int64)
+
+    def configure(self, b, cfg=None, model=None, kf=None, Q=None):
+        """Filter b's configuration (see CVPBatch.batch_configure_vp); cfg also becomes self.configs[b] (the resampling thresholds)."""
+        if cfg is not None:
+            self.configs[b] = cfg
+        self.batch_configure_vp(b, cfg=cfg, model=model, kf=kf, Q=Q)
+
+    def cycle_async(self, predict, Zs, poses=None, pose_cov=None, scan=None, normalize=True):
+        """One predict + update cycle of every filter (rfsgpu_batch_vp_cycle_async)."""
+        self.batch_vp_cycle_async(predict, Zs, poses=poses, pose_cov=pose_cov, scan=scan, normalize=normalize)
+
+    last_step_variant = RBPHDFilter.last_step_variant      # after a cycle: (1, 0, particles per workgroup of the step kernel, 1)
+    step_launch_order = RBPHDFilter.step_launch_order      # the step's launch order, across the whole batch
+    _gate_config = FilterBatch._gate_config
+    weight_sums_per_filter = FilterBatch.weight_sums_per_filter
+    update_and_resample = FilterBatch.update_and_resample
+
+
 class FastSLAMBatch(FilterBatch):
     """n_filters independent 2-D single-hypothesis FastSLAM filters stepped together (rfsgpu_batch_fastslam_cycle_async): per cycle the
     static landmark step, the association / Kalman update / weights, the existence prune, the new landmarks and each filter's

@@ -205,7 +205,26 @@ def make_vp_scenario(n_particles, n_landmarks, n_z, seed=4242, scan="const", par
                 particle_w=np.ones(n_particles), params=P, gt=gt, scan=np.asarray(scan, dtype=np.float64), model="vp")
 
 
+def apply_vp_batch_params(batch, b, P):
+    """Filter b of a VPFilterBatch gets what apply_vp_params gives a handle (the scan is the batch's: set_laser_scan or the cycle call)."""
+    cfg = vp_filter_config(batch, P)
+    batch.configure(b, cfg, model=(P["R"], P["Slb"], P["pd_table"], P["expected_clutter"], P["rmax"], P["rmin"], P["bmax"], P["bmin"], P["buffer_pd"]),
+                    kf=(P["kf_range"], P["kf_bearing"]), Q=P["Q_lm"])
+
+
 def apply_vp_params(f, P, scan):
+    cfg = vp_filter_config(f, P)
+    f.set_filter_config(cfg)
+    if hasattr(f, "config"):
+        f.config = cfg
+    f.set_model_victoriapark(P["R"], P["Slb"], P["pd_table"], P["expected_clutter"], P["rmax"], P["rmin"], P["bmax"], P["bmin"], P["buffer_pd"])
+    f.set_kf_config(P["kf_range"], P["kf_bearing"])
+    f.set_lmk_process_noise(P["Q_lm"])
+    f.set_laser_scan(scan)
+
+
+def vp_filter_config(f, P):
+    """The FilterConfig of a Victoria Park parameter set (VP_PARAMS' keys)."""
     cfg = f.default_filter_config()
     cfg.birthGaussianWeight = P["birth_w"]
     cfg.birthGaussianMeasurementCountThreshold = P["birth_count_thr"]
@@ -222,10 +241,4 @@ def apply_vp_params(f, P, scan):
     cfg.useClusterProcess = P["use_cluster"]
     cfg.minUpdatesBeforeResample = P["min_updates"]
     cfg.minMeasurementsBeforeResample = P["min_measurements"]
-    f.set_filter_config(cfg)
-    if hasattr(f, "config"):
-        f.config = cfg
-    f.set_model_victoriapark(P["R"], P["Slb"], P["pd_table"], P["expected_clutter"], P["rmax"], P["rmin"], P["bmax"], P["bmin"], P["buffer_pd"])
-    f.set_kf_config(P["kf_range"], P["kf_bearing"])
-    f.set_lmk_process_noise(P["Q_lm"])
-    f.set_laser_scan(scan)
+    return cfg

@@ -327,6 +327,167 @@ class VictoriaParkRun:
         return True
 
 
+class VictoriaParkBatchRun:
+    """VictoriaParkRun's loop (the RB-PHD filter on the host-stop route) for B filters in lock-step over one dataset: the sweep of
+    cfg/rbphdslam_VictoriaPark_artificialClutter.xml -- the same messages under different input-noise, clutter and resampling
+    realisations and different parameter sets.  target: a VPFilterBatch, or a list of B plain Victoria Park handles, which then take
+    the same realisations in turn (the comparison route of the tests and of tools/vp_bench.py).
+
+    Every filter has its own generator (seeds[b]) for its input noise, artificial clutter and resampling draws, taken in
+    VictoriaParkRun's order; the Ackerman propagation is one vectorised step over all slots on the host.  The device work of a run of
+    messages is issued at its lidar message: the run's first predict with its births (at the poses the last update used; a cycle call
+    without measurement sets, or predict_map_async on a handle), the other predicts as one static_steps_async, then one cycle call with
+    the sets, the new poses and the scan; a lidar message that follows another directly is one cycle call.  Then each filter's gate and
+    N_eff decision on the host and one resample_apply for the filters that fire.  keep_history: (n_z, fired, plans) per lidar message.
+    One difference from VictoriaParkRun, on both routes alike: the cycle call's normalize flag is the whole batch's, so a filter whose
+    set is empty at a lidar message has its (already normalised) weights divided by their sum once more, where VictoriaParkRun leaves
+    them alone (RBPHDFilter.hpp:451-452); the batch is held to the handles stepped through this class, not to VictoriaParkRun."""
+
+    def __init__(self, target, data, params_per_filter, seeds, var_uv=0.2, var_ur=0.025, noise_inflation=20.0, added_clutter=3.0, eff_n=None,
+                 keep_history=False):
+        self.batch = None if isinstance(target, (list, tuple)) else target
+        self.handles = list(target) if self.batch is None else None
+        self.nF = len(params_per_filter)
+        self.n = self.batch.n_per_filter if self.batch is not None else self.handles[0].n
+        assert len(seeds) == self.nF and (self.batch.n_filters if self.batch is not None else len(self.handles)) == self.nF
+        self.Ps = list(params_per_filter)
+        self.mgr, self.inputs, self.meas = data["manager"], data["inputs"], data["measurements"]
+        self.rngs = [np.random.default_rng(s) for s in seeds]
+        self.x = np.zeros((self.nF * self.n, 3))
+        self.sd = np.sqrt(np.array([var_uv, var_ur]) * noise_inflation)
+        self.added_clutter = np.broadcast_to(np.asarray(added_clutter, dtype=np.float64), (self.nF,)).copy()
+        self.eff_n = np.broadcast_to(np.asarray(self.n / 2.0 if eff_n is None else eff_n, dtype=np.float64), (self.nF,)).copy()
+        self.scan = np.full(361, 70.0)
+        if self.batch is not None:
+            self.batch.set_laser_scan(self.scan)      # (a cycle call needs one, the run's first birth predict included)
+        self.n_updates_since = np.zeros(self.nF, dtype=np.int64)
+        self.n_meas_since = np.zeros(self.nF, dtype=np.int64)
+        self.n_resamples = np.zeros(self.nF, dtype=np.int64)
+        self.n_lidar = 0
+        self.history = [] if keep_history else None
+        self._dts = []                    # the intervals of the predicts not yet issued (the first of a run adds the births)
+
+    def _block(self, b):
+        return slice(b * self.n, (b + 1) * self.n)
+
+    def _predict(self, u, dt, stationary):
+        self._dts.append(float(dt))
+        N = self.nF * self.n
+        if stationary:
+            uv, ur = np.full(N, u[0]), np.full(N, u[1])
+        else:                             # predict(u, dt, false, true): each filter's noise from its own generator, uv then ur
+            uv, ur = np.empty(N), np.empty(N)
+            for b, rng in enumerate(self.rngs):
+                uv[self._block(b)] = u[0] + self.sd[0] * rng.standard_normal(self.n)
+                ur[self._block(b)] = u[1] + self.sd[1] * rng.standard_normal(self.n)
+        self.x = ackerman_step(self.x, uv, ur, dt)
+
+    def _clutter(self, b):
+        P, rng, out = self.Ps[b], self.rngs[b], []
+        if self.added_clutter[b] > 0:
+            for _ in range(rng.poisson(self.added_clutter[b])):
+                r = rng.uniform() * (P["rmax"] - P["rmin"]) + P["rmin"]
+                a = rng.uniform() * ((np.rad2deg(P["bmax"]) - np.rad2deg(P["bmin"])) + np.rad2deg(P["bmin"])) * np.pi / 180  # sic (:563)
+                out.append(np.array([r, a, 1.0]))
+        return out
+
+    def _cycle(self, Zs):
+        """The queued predicts and this lidar message's update on the device."""
+        q = np.diag([5e-4, 5e-4, 1e-4])[None, :, :] * (np.array(self._dts) ** 2)[:, None, None]      # varlm* x dt^2 (:497-500)
+        self._dts = []
+        one = len(q) == 1 and Zs is not None      # (Zs None: the predicts behind the last lidar message, no update)
+        if self.batch is not None:
+            f = self.batch
+            f.set_lmk_process_noise(q[0])
+            if not one:
+                f.cycle_async(True, [np.zeros((0, 3))] * self.nF, normalize=False)
+                if len(q) > 1:
+                    f.static_steps_async(len(q) - 1, q[1:])
+            if Zs is not None:
+                f.cycle_async(True if one else None, Zs, poses=self.x, scan=self.scan, normalize=True)
+            return
+        for b, f in enumerate(self.handles):
+            f.set_lmk_process_noise(q[0])
+            if not one:
+                f.predict_map_async(True)
+                if len(q) > 1:
+                    f.static_steps_async(len(q) - 1, q[1:])
+            if Zs is not None:
+                f.set_step_inputs_async(scan=self.scan)      # (through the pinned ring: no stop behind the predicts just enqueued)
+                f.cycle_async(True if one else None, Zs[b], poses=self.x[self._block(b)], normalize=True)
+
+    def _resample(self, n_z):
+        """RBPHDFilter::update's tail per filter: counters, the two gates, N_eff, the systematic plan with the filter's own draw.  A batch
+        makes it itself (update_and_resample, from the configurations it was given: params_per_filter's); the handles' is made here."""
+        if self.batch is not None:
+            fired, glob = self.batch.update_and_resample(n_z, lambda b: float(self.rngs[b].uniform()), self.eff_n)
+            plans = [glob[self._block(b)] - b * self.n for b in range(self.nF)]
+            self.n_updates_since[:] = self.batch.nUpdatesSinceResample
+            self.n_meas_since[:] = self.batch.nMeasurementsSinceResample
+            for b in np.nonzero(fired)[0]:
+                self.x[self._block(b)] = self.x[self._block(b)][plans[b]]
+            self.n_resamples += fired
+            return fired, plans
+        w = np.concatenate([f.get_weights() for f in self.handles])
+        fired = np.zeros(self.nF, dtype=bool)
+        plans = [np.arange(self.n) for _ in range(self.nF)]
+        for b in range(self.nF):
+            self.n_updates_since[b] += 1
+            if n_z[b] == 0:
+                continue
+            self.n_meas_since[b] += int(n_z[b])
+            P = self.Ps[b]
+            if self.n_updates_since[b] < P["min_updates"] or self.n_meas_since[b] < P["min_measurements"]:
+                continue
+            wb = w[self._block(b)]
+            neff = 1.0 / float(np.sum(wb * wb))
+            if neff > self.eff_n[b] and neff / self.n > self.eff_n[b] / self.n:
+                continue
+            plans[b] = systematic_resample_plan(wb, float(self.rngs[b].uniform()))
+            fired[b] = True
+            self.n_updates_since[b] = self.n_meas_since[b] = 0
+        for b in np.nonzero(fired)[0]:
+            self.handles[b].resample_apply(plans[b])
+            self.x[self._block(b)] = self.x[self._block(b)][plans[b]]
+        self.n_resamples += fired
+        return fired, plans
+
+    def run(self, n_messages=None):
+        t_km, u_km, stationary, z_idx = 0.0, np.zeros(2), True, 0
+        msgs = self.mgr if n_messages is None else self.mgr[:n_messages]
+        for t_k, typ, idx in msgs:
+            idx = int(idx) - 1
+            dt = t_k - t_km
+            if typ == 2:          # Input
+                self._predict(u_km, dt, stationary)
+                u_km = self.inputs[idx, 1:3].copy()
+                if u_km[0] != 0:
+                    stationary = False
+                t_km = t_k
+            elif typ == 3:        # Lidar
+                self._predict(u_km, dt, stationary)
+                Z = []
+                while z_idx < len(self.meas) and abs(self.meas[z_idx, 0] - t_k) < 1e-9:
+                    Z.append(self.meas[z_idx, 1:4])
+                    z_idx += 1
+                Zs = [np.array(Z + self._clutter(b)).reshape(-1, 3)[:60] for b in range(self.nF)]
+                n_z = np.array([len(z) for z in Zs])
+                self._cycle(Zs)
+                self.n_lidar += 1
+                fired, plans = self._resample(n_z)
+                if self.history is not None:
+                    self.history.append((n_z, fired, plans))
+                t_km = t_k
+        if self._dts:
+            self._cycle(None)
+        self.synchronize()
+        return self
+
+    def synchronize(self):
+        for f in ([self.batch] if self.batch is not None else self.handles):
+            f.synchronize()
+
+
 def write_vp_logs(log_dir, estimates):
     """particlePose.dat and landmarkEst.dat in the reference's Victoria Park format (std::fixed, precision 3, widths 10 / 5 / 10 ...:
     src/rbphdslam_VictoriaPark.cpp:427-440, :586-622) from (hdr, gauss, part) as VictoriaParkRun.estimates() returns them: per row

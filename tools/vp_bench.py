@@ -1,6 +1,11 @@
 #!/usr/bin/env python3
 """Victoria Park (configs[3]) update rate -- not the headline metric (bench.py), a measurement for DESIGN.md.
-5000 particles, Victoria-Park-shaped maps (40 landmarks, 12 measurements per update); state re-seeded every step."""
+5000 particles, Victoria-Park-shaped maps (40 landmarks, 12 measurements per update); state re-seeded every step.
+  python tools/vp_bench.py --batch B [--reps 3] [--particles 100] [--messages 900] [--capacity 384] [--only batch|handles]
+      A sweep of B Victoria Park RB-PHD filters over the dataset extract (tests/golden/victoria_park_extract.npz, artificial clutter
+      on): the filter batch (VPFilterBatch, rfsgpu_batch_vp_cycle_async) against the same B filters as plain handles stepped in turn,
+      both through vp_driver.VictoriaParkBatchRun with the same realisations, alternating in this one invocation.  One line per
+      repetition and route, then one JSON line: medians in seconds per sweep, runs (filters) per second, and the ratio."""
 import os
 import sys
 import time
@@ -12,6 +17,78 @@ pkg = load_package()
 if os.environ.get("RFS_LIB"):
     pkg.engine.LIB = os.environ["RFS_LIB"]      # a tools/variant_bench.py --build variant
 sc = pkg.scenarios
+
+
+def batch_sweep(nF):
+    """Per filter: parameter set (Pd table / expected clutter of the sweep), seed, artificial-clutter rate."""
+    Ps, seeds, clutter = [], [], []
+    for b in range(nF):
+        P = dict(sc.VP_PARAMS)
+        P["expected_clutter"] = [6.0, 3.0, 9.0, 12.0][b % 4]
+        P["pd_table"] = [[0.0, 0.05, 0.35, 0.76, 0.89, 0.90], [0.0, 0.1, 0.5, 0.8, 0.95], [0.0, 0.03, 0.3, 0.7, 0.85, 0.88]][b % 3]
+        Ps.append(P)
+        seeds.append(100 + b)
+        clutter.append([3.0, 1.0, 5.0, 2.0][(b // 4) % 4])
+    return Ps, seeds, clutter
+
+
+def batch_one_run(route, nF, n, data, messages, cap):
+    Ps, seeds, clutter = batch_sweep(nF)
+    if route == "batch":
+        target = pkg.VPFilterBatch(nF, n, gm_capacity=cap)
+        for b in range(nF):
+            sc.apply_vp_batch_params(target, b, Ps[b])
+        target.synchronize()
+        owned = [target]
+    else:
+        target = [pkg.RBPHDFilter(n, gm_capacity=cap, model=pkg.capi.MODEL_VICTORIAPARK_3D) for _ in range(nF)]
+        for b, h in enumerate(target):
+            sc.apply_vp_params(h, Ps[b], np.full(361, 70.0))
+            h.synchronize()
+        owned = target
+    t0 = time.perf_counter()
+    r = pkg.vp_driver.VictoriaParkBatchRun(target, data, Ps, seeds, added_clutter=clutter).run(n_messages=messages)
+    dt = time.perf_counter() - t0
+    info = (int(r.n_lidar), int(r.n_resamples.sum()), float(np.mean(np.concatenate([h.gm_sizes() for h in owned]))))
+    for h in owned:
+        h.close()
+    return dt, info
+
+
+def batch_main():
+    import argparse
+    import json
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batch", type=int, required=True)
+    ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--particles", type=int, default=100)
+    ap.add_argument("--messages", type=int, default=900)
+    ap.add_argument("--only", choices=["batch", "handles"], default=None)
+    ap.add_argument("--capacity", type=int, default=384)      # (192 is transiently short under the heaviest clutter of the sweep)
+    a = ap.parse_args()
+    data = np.load(os.path.join(ROOT, "tests", "golden", "victoria_park_extract.npz"))
+    routes = [a.only] if a.only else ["handles", "batch"]
+    times = {r: [] for r in routes}
+    for rep in range(a.reps + 1):                     # (the first repetition warms up: code objects, allocations)
+        for route in routes:
+            dt, info = batch_one_run(route, a.batch, a.particles, data, a.messages, a.capacity)
+            if rep:
+                times[route].append(dt)
+            print("  %-7s rep %d%s: %.4f s for %d filters (%d lidar updates, %d resamplings, mean map size %.1f)" %
+                  ((route, rep, "" if rep else " (warm-up)", dt, a.batch) + info), flush=True)
+    out = dict(tool="vp_bench", filters=a.batch, particles=a.particles, messages=a.messages, reps=a.reps)
+    for r in routes:
+        med = float(np.median(times[r]))
+        out[r + "_s"] = med
+        out[r + "_runs_per_s"] = a.batch / med
+    if len(routes) == 2:
+        out["batch_over_handles"] = out["batch_runs_per_s"] / out["handles_runs_per_s"]
+    print(json.dumps(out))
+
+
+if "--batch" in sys.argv:
+    batch_main()
+    sys.exit(0)
 N, NM, NZ = [int(os.environ.get(k, d)) for k, d in (("VP_N", 5000), ("VP_NM", 40), ("VP_NZ", 12))]
 scen = sc.make_vp_scenario(N, NM, NZ, seed=4321, scan="ragged")
 f = pkg.RBPHDFilter(N, gm_capacity=int(os.environ.get("VP_CAP", 192)), model=pkg.capi.MODEL_VICTORIAPARK_3D)
