@@ -757,13 +757,15 @@ int rfsgpu_batch_cycle_async(rfsgpu_filter *f, int predict, const double *x, con
  * (rfsgpu_set_laser_scan, rfsgpu_set_step_inputs_async, or the cycle call's scan) and each filter's clutter density is derived from
  * it with the filter's own expectedClutterNumber, by rfsgpu_set_laser_scan's rule.  rfsgpu_set_lmk_process_noise sets every
  * filter's Q (and nothing else of its configuration); rfsgpu_set_model_victoriapark sets every filter's model;
- * rfsgpu_static_steps_async serves the batch as it serves a handle.  The host-stop route only: rfsgpu_batch_weight_sums,
+ * rfsgpu_static_steps_async serves the batch as it serves a handle.  The host-stop route: rfsgpu_batch_weight_sums,
  * rfsgpu_batch_resample_apply (pose and mixture move; the birth state follows lazily in the next birth predicts of a filter that
  * resampled, level by level as on a handle, until its next update with measurements) and rfsgpu_batch_resample_occured work as on a
  * 2-D batch, and so do the per-slot getters and setters, rfsgpu_export / _import_birth_candidates and rfsgpu_get / _set_unused_masks
- * included.  RFSGPU_ERR_UNSUPPORTED on such a batch, with a message and the state untouched: rfsgpu_batch_cycle_async, the FastSLAM
- * and multi-hypothesis batch calls, the device loop (rfsgpu_batch_set_motion_odometry, _set_resampling, _propagate_async,
- * _resample_async), [sensor], [truth], [metric], [estimate] and rfsgpu_rbphd_cycle_async.  rfsgpu_batch_configure on such a batch,
+ * included.  The device route, on which nothing is read back between the messages of a run: rfsgpu_batch_vp_set_motion,
+ * _vp_set_resampling, _vp_propagate_run_async, _vp_resample_async, _vp_last_resample and _vp_loop_counts, below the 2-D device loop.
+ * RFSGPU_ERR_UNSUPPORTED on such a batch, with a message and the state untouched: rfsgpu_batch_cycle_async, the FastSLAM
+ * and multi-hypothesis batch calls, the 2-D device loop (rfsgpu_batch_set_motion_odometry, _set_resampling, _propagate_async,
+ * _resample_async, _last_resample, _resample_counts), [sensor], [truth], [metric], [estimate] and rfsgpu_rbphd_cycle_async.  rfsgpu_batch_configure on such a batch,
  * and rfsgpu_batch_configure_vp on a 2-D batch, return RFSGPU_ERR_INVALID.  rfsgpu_last_error names the lowest filter that exceeded
  * gm_capacity, and for a full candidate list (RFSGPU_MAX_CANDIDATES) the lowest filter with a slot whose list, with the unused
  * measurements that could join it, stood beyond the limit in a birth predict that reported one: the filter at fault where one
@@ -832,6 +834,47 @@ int rfsgpu_batch_last_resample(rfsgpu_filter *f, unsigned char *fired, int *src_
 int rfsgpu_batch_get_pose_covs(rfsgpu_filter *f, double *out);
 /* Resamplings of each filter by rfsgpu_batch_resample_async so far: out [n_filters].  Synchronising. */
 int rfsgpu_batch_resample_counts(rfsgpu_filter *f, long long *out);
+/* -- the device route of a batch of Victoria Park filters: ParticleFilter::propagate with MotionModel_Ackerman2d::step for a run of
+ * odometry messages, the resampling tail of RBPHDFilter::update, and the birth predict's inheritance walk from the ids the device
+ * holds.  With them a run of messages is birth cycle -> rfsgpu_static_steps_async -> propagate_run -> update cycle (x = NULL) ->
+ * resample, and the host waits for nothing.  Each filter equals the host-stop route of the same batch bit for bit, given the same
+ * poses and draws.  On a 2-D batch, a shard or an ordinary handle every call of the section returns RFSGPU_ERR_UNSUPPORTED with the
+ * state untouched.
+ *
+ * Filter `filter`'s (-1: every filter's) input noise N(0, diag(var)) on (speed, steering), the vehicle geometry {h, l, dx, dy}
+ * (l != 0) and its 64-bit Philox key (propagation and resampling draws). */
+int rfsgpu_batch_vp_set_motion(rfsgpu_filter *f, int filter, const double var[2], const double geom[4], unsigned long long seed);
+/* The two thresholds of ParticleFilter::resample of filter `filter` (-1: every filter): the rule stated for
+ * rfsgpu_batch_set_resampling; the gates are those of the filter's rfsgpu_filter_config. */
+int rfsgpu_batch_vp_set_resampling(rfsgpu_filter *f, int filter, double eff_n, double eff_n_percent);
+/* n consecutive odometry messages: u [n][2] = {speed, steering}, dt [n], noisy [n] (NULL: every step is noisy).  The inputs are the
+ * dataset's, shared by all filters; every slot takes the steps one after the other in ONE launch.  Slot i of filter b draws what a
+ * handle draws for particle i under rfsgpu_propagate_ackerman_run_async(seed = key_b, call0): counter (i within the filter, 0,
+ * call low word, call high word) with call = call0 + step, Box-Muller as there (rad cos ang on the speed, rad sin ang on the
+ * steering); no draw is made for a step with noisy[k] == 0 (a driver's stationary predicts) or with both variances 0.  The run is
+ * copied into a block of the batch's pinned ring before the call returns: n <= RFSGPU_BATCH_VP_RUN_MAX, beyond it
+ * RFSGPU_ERR_INVALID with the state untouched (split the run; the calls continue at call0 + n).  The propagation is IN PLACE and
+ * stream-ordered: the caller issues it behind the birth predict of the run (rfsgpu_batch_vp_cycle_async with predict = 1), which must
+ * still see the poses of the last update, and in front of the update cycle, which then passes x = NULL.  The pose covariances are
+ * left as they are.  A filter without rfsgpu_batch_vp_set_motion: RFSGPU_ERR_INVALID, naming it. */
+#define RFSGPU_BATCH_VP_RUN_MAX 16
+int rfsgpu_batch_vp_propagate_run_async(rfsgpu_filter *f, int n, const double *u, const unsigned char *noisy, const double *dt, unsigned long long call0);
+/* rfsgpu_batch_resample_async for such a batch, after an rfsgpu_batch_vp_cycle_async with normalize != 0: counters, both gates,
+ * N_eff, the systematic plan with the draw of (key_b, call), ids, gather, weights 1, resampleOccured_, counters back to 0.
+ * n_per_filter <= RFSGPU_BATCH_RESAMPLE_MAX_PER_FILTER, beyond it RFSGPU_ERR_UNSUPPORTED; a filter without
+ * rfsgpu_batch_vp_set_resampling or _vp_set_motion: RFSGPU_ERR_INVALID, naming it.  From the first call on the handle is on the device
+ * route: the particle ids, resampleOccured_ and the counters live on the device (rfsgpu_get_particle_ids / _set_particle_ids and
+ * rfsgpu_batch_resample_occured read / write them there, synchronising), rfsgpu_batch_resample_apply is refused with
+ * RFSGPU_ERR_UNSUPPORTED, and a birth predict computes its inheritance levels on the device: the staging pair and the level-0
+ * births, RFSGPU_RBPHD_WALK_LEVELS (copy, birth) pairs that find nothing to do where the walk is shallower, and one workgroup per
+ * filter for deeper chains.  A filter's resampleOccured_ falls in the cycle that updates it (n_z > 0).  Host-stop route first,
+ * device route later is allowed (the host's ids and flags move to the device). */
+int rfsgpu_batch_vp_resample_async(rfsgpu_filter *f, const int *n_z, unsigned long long call);
+/* The last rfsgpu_batch_vp_resample_async, as rfsgpu_batch_last_resample reports it; any output may be NULL.  Synchronising. */
+int rfsgpu_batch_vp_last_resample(rfsgpu_filter *f, unsigned char *fired, int *src_slot, double *n_eff);
+/* resamplings [n_filters]: each filter's resamplings by rfsgpu_batch_vp_resample_async so far; max_level: the deepest inheritance
+ * level any walk on the device has met.  Either may be NULL.  Synchronising. */
+int rfsgpu_batch_vp_loop_counts(rfsgpu_filter *f, long long *resamplings, int *max_level);
 /* -- a batch of FastSLAM filters: every filter is a 2-D single-hypothesis rfs::FastSLAM (include/FastSLAM.hpp) with its own
  * configuration, measurement set, weights, resampling and seed; each equals a separate handle driven through
  * rfsgpu_predict_map(add_birth = 0) / rfsgpu_fastslam_update given the same inputs.  A batch is of ONE kind: the first of

@@ -173,6 +173,7 @@ ABI_SYMBOLS = [
     "estimate_log_create", "estimate_log_reset", "step_estimate_async", "estimate_log_read", "batch_run_log_estimates",
     "handle_serve_estimates",
     "batch_configure_vp", "batch_vp_cycle_async",
+    "batch_vp_set_motion", "batch_vp_set_resampling", "batch_vp_propagate_run_async", "batch_vp_resample_async", "batch_vp_last_resample", "batch_vp_loop_counts",
 ]
 
 _dp = np.ctypeslib.ndpointer(dtype=np.float64, flags="C_CONTIGUOUS")
@@ -1213,6 +1214,46 @@ class CVPBatch(CBatch):
         self._call("batch_vp_cycle_async", C.c_int(-1 if predict is None else (1 if predict else 0)), C.c_void_p(None) if x is None else self._ptr(x),
                    C.c_void_p(None) if cv is None else self._ptr(cv), C.c_int(stride), self._ptr(z), self._ptr(nz),
                    C.c_void_p(None) if s is None else self._ptr(s), C.c_int(0 if s is None else s.size), C.c_int(1 if normalize else 0))
+
+    # -- the device route ([batch] in include/rfsgpu.h: a run of messages without a stop on the host) --------------------------
+    def batch_vp_set_motion(self, b, var, geom, seed):
+        """rfsgpu_batch_vp_set_motion: filter b's (None: every filter's) input-noise variances (speed, steering), the vehicle geometry
+        (h, l, dx, dy) and its Philox key."""
+        v, g = _f64(var, (2,)), _f64(geom, (4,))
+        self._call("batch_vp_set_motion", C.c_int(-1 if b is None else int(b)), self._ptr(v), self._ptr(g), C.c_ulonglong(int(seed) & 0xFFFFFFFFFFFFFFFF))
+
+    def batch_vp_set_resampling(self, b, eff_n, eff_n_percent):
+        """rfsgpu_batch_vp_set_resampling: ParticleFilter::resample's two thresholds for filter b (None: every filter)."""
+        self._call("batch_vp_set_resampling", C.c_int(-1 if b is None else int(b)), C.c_double(float(eff_n)), C.c_double(float(eff_n_percent)))
+
+    def batch_vp_propagate_run_async(self, u, dt, call0, noisy=None):
+        """rfsgpu_batch_vp_propagate_run_async: u [n, 2], dt [n], noisy [n] bool (None: every step is noisy); calls call0, call0 + 1, ..."""
+        u = _f64(u).reshape(-1, 2)
+        dt = _f64(dt).reshape(-1)
+        assert u.shape[0] == dt.shape[0]
+        ny = None if noisy is None else np.ascontiguousarray(noisy, dtype=np.uint8).reshape(dt.shape[0])
+        self._call("batch_vp_propagate_run_async", C.c_int(dt.shape[0]), self._ptr(u), C.c_void_p(None) if ny is None else self._ptr(ny), self._ptr(dt),
+                   C.c_ulonglong(int(call0)))
+
+    def batch_vp_resample_async(self, n_z, call):
+        """rfsgpu_batch_vp_resample_async: n_z [n_filters] the cycle's measurement counts."""
+        nz = np.ascontiguousarray(n_z, dtype=np.int32).reshape(self.n_filters)
+        self._call("batch_vp_resample_async", self._ptr(nz), C.c_ulonglong(int(call)))
+
+    def batch_vp_last_resample(self):
+        """(fired [n_filters] bool, plan [N] global source slots, n_eff [n_filters]) of the last batch_vp_resample_async (synchronising)."""
+        fired = np.zeros(self.n_filters, dtype=np.uint8)
+        plan = np.zeros(self.n, dtype=np.int32)
+        neff = np.zeros(self.n_filters)
+        self._call("batch_vp_last_resample", self._ptr(fired), self._ptr(plan), self._ptr(neff))
+        return fired.astype(bool), plan, neff
+
+    def batch_vp_loop_counts(self):
+        """(resamplings [n_filters], the deepest inheritance level any walk on the device has met) (synchronising)."""
+        out = np.zeros(self.n_filters, dtype=np.int64)
+        lv = C.c_int(0)
+        self._call("batch_vp_loop_counts", self._ptr(out), C.byref(lv))
+        return out, int(lv.value)
 
 
 class CBatchMH(CBatch):

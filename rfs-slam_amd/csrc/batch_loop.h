@@ -81,6 +81,14 @@ __global__ __launch_bounds__(256) void batch_propagate_kernel(const double *pose
   c[0] = v0; c[1] = 0.0; c[2] = 0.0; c[3] = 0.0; c[4] = v1; c[5] = 0.0; c[6] = 0.0; c[7] = 0.0; c[8] = v2;
 }
 
+// s + w * w with the product rounded before it is added.  (__dmul_rn and __dadd_rn are plain operators in this toolchain's headers:
+// under the build's contraction mode the pair became one v_fmac_f64, and N_eff differed from the stated sum in its last bit.)
+__device__ __forceinline__ double batch_add_square(double s, double w) {
+#pragma clang fp contract(off)
+  const double p = w * w;
+  return s + p;
+}
+
 #define BATCH_LOOP_THREADS 256
 #define BATCH_LOOP_MAX_PER_FILTER 2048     // == RFSGPU_BATCH_RESAMPLE_MAX_PER_FILTER (rfsgpu.h); the LDS arrays below
 
@@ -127,7 +135,7 @@ __global__ __launch_bounds__(BATCH_LOOP_THREADS) void batch_resample_kernel(doub
       nm += I.nZ;
       if (nu >= I.minUpdates && nm >= I.minMeasurements) {
         double ss = 0.0;
-        for (int j = 0; j < n; j++) ss = __dadd_rn(ss, __dmul_rn(cum[j], cum[j]));   // (no fused multiply-add: the reference's rounding)
+        for (int j = 0; j < n; j++) ss = batch_add_square(ss, cum[j]);   // (no fused multiply-add: the reference's rounding)
         neff = 1.0 / ss;
         fire = !(neff > I.effN && neff / (double)n > I.effNPercent);
       }

@@ -36,6 +36,7 @@
 #include "resample_plan.h"
 #include "birth_walk.h"
 #include "vp_batch.h"
+#include "vp_batch_loop.h"
 
 namespace {
 
@@ -237,6 +238,11 @@ struct rfsgpu_filter {
   BatchResIn *dBResIn = nullptr;               // [nF]
   BatchLoopState BL{};
   PinnedRing bLoop;                            // ring of the loop calls' per-filter inputs, a block per call (eight blocks: propagate + resample, four cycles; with a sense call three per cycle, 2 2/3 cycles)
+  // the device route of a batch of Victoria Park filters (vp_batch_loop.h)
+  std::vector<VpBatchMotion> bVpMotion;        // [nF] rfsgpu_batch_vp_set_motion
+  VpBatchMotion *dBVpMotion = nullptr;         // [nF]
+  VpBatchRun *dBVpRun = nullptr;               // [1] the run of the last rfsgpu_batch_vp_propagate_run_async
+  int *dBVpWalk = nullptr;                     // [VBW_FILTER + nF] the walk's words
   // the sensor of a batch (batch_sensor.h): every filter's scan drawn on the device
   std::vector<char> bSensorSet;                // rfsgpu_batch_set_sensor has been called for the filter
   std::vector<int> bSensorMaxNz;               // [nF] its max_nz
@@ -665,6 +671,7 @@ void rfsgpu_destroy(rfsgpu_filter *f) {
   hipFree(f->dMhFilt); hipFree(f->mhbBlock); if (f->hMhbBlock) hipHostFree(f->hMhbBlock);
   hipFree(f->dBMotion); hipFree(f->dBPropIn); hipFree(f->dBResIn); hipFree(f->BL.counters); hipFree(f->BL.nResamples); hipFree(f->BL.resampled);
   hipFree(f->BL.fired); hipFree(f->BL.nEff); hipFree(f->BL.plan); hipFree(f->BL.pid); hipFree(f->BL.ppid);
+  hipFree(f->dBVpMotion); hipFree(f->dBVpRun); hipFree(f->dBVpWalk);
   hipFree(f->dBSensor); hipFree(f->dBSensorLm); hipFree(f->dBSensorPose); hipFree(f->dBSensorCaps); hipFree(f->dBSensorPrev); hipFree(f->dBSensorErrFilter);
   hipFree(f->dTruthCfg); hipFree(f->dTruthProp); hipFree(f->dTruthGt); hipFree(f->dTruthTgt); hipFree(f->dTruthLm); hipFree(f->dTruthSeen); hipFree(f->dTruthCounts);
   hipFree(f->dGtXY); hipFree(f->dGtSeen); hipFree(f->dGtN); hipFree(f->dErrLog); hipFree(f->dErrRow);
@@ -3582,6 +3589,7 @@ static int batch_mh_cycle_core(rfsgpu_filter *f, int predict, const double *x, c
 static int batch_push_motion(rfsgpu_filter *f);
 static int batch_resample_core(rfsgpu_filter *f, const BatchCall &C, const int *n_z, unsigned long long call, bool stageIn = true);
 static int batch_enter_dev_route(rfsgpu_filter *f);
+static int batch_last_resample_core(rfsgpu_filter *f, unsigned char *fired, int *src_slot, double *n_eff);
 static int batch_propagate_core(rfsgpu_filter *f, const double *u, const double *pin_pose, const unsigned char *pin, const BatchPropIn *devRow, unsigned long long call);
 static int batch_sense_core(rfsgpu_filter *f, const double *gt_pose, const double *devPose, unsigned long long call);
 extern "C" {
@@ -3617,6 +3625,7 @@ int rfsgpu_create_batch(rfsgpu_filter **out, int model, int n_filters, int n_per
   f->bParamsHost.resize(n_filters);
   f->bStage.bytes = batch_stage_bytes(f);
   f->bLoop.bytes = (size_t)n_filters * std::max(sizeof(BatchMotion), std::max(sizeof(BatchPropIn), sizeof(BatchResIn)));
+  if (f->D == 3) f->bLoop.bytes = std::max(f->bLoop.bytes, std::max((size_t)n_filters * sizeof(VpBatchMotion), sizeof(VpBatchRun)));
   f->bLoop.depth = 8;
   batch_set_all(f);
   bool ok = true;
@@ -3652,6 +3661,14 @@ int rfsgpu_create_batch(rfsgpu_filter **out, int model, int n_filters, int n_per
   if (ok) ok &= hipMemset(f->BL.resampled, 0, (size_t)n_filters * sizeof(int)) == hipSuccess;
   if (ok) ok &= hipMemset(f->BL.fired, 0, (size_t)n_filters * sizeof(int)) == hipSuccess;
   if (ok) ok &= hipMemset(f->BL.nEff, 0, (size_t)n_filters * sizeof(double)) == hipSuccess;
+  if (f->D == 3) {     // the device route of a Victoria Park batch (vp_batch_loop.h)
+    f->bVpMotion.assign(n_filters, VpBatchMotion{});
+    ok &= hipMalloc(&f->dBVpMotion, (size_t)n_filters * sizeof(VpBatchMotion)) == hipSuccess;
+    ok &= hipMalloc(&f->dBVpRun, sizeof(VpBatchRun)) == hipSuccess;
+    ok &= hipMalloc(&f->dBVpWalk, (size_t)(VBW_FILTER + n_filters) * sizeof(int)) == hipSuccess;
+    if (ok) ok &= hipMemset(f->dBVpRun, 0, sizeof(VpBatchRun)) == hipSuccess;
+    if (ok) ok &= hipMemset(f->dBVpWalk, 0, (size_t)(VBW_FILTER + n_filters) * sizeof(int)) == hipSuccess;
+  }
   // the sensor's tables (batch_sensor.h)
   f->bSensorSet.assign(n_filters, 0);
   f->bSensorMaxNz.assign(n_filters, 0);
@@ -3876,10 +3893,13 @@ static int batch_vp_cycle_core(rfsgpu_filter *f, int predict, const double *x, c
   // The reference's lazy copy of the per-slot birth state (RBPHDFilter.hpp:1005-1011) for the filters that have resampled since their
   // last update with measurements: predict_launch's parent and level tables, built across the batch.  A parent lies inside its filter's
   // block; a filter whose flag is clear keeps every slot its own parent, whatever idParent_ an older resampling left it.
-  ensure_ids(f);
+  // On the device route (rfsgpu_batch_vp_resample_async has run) the ids and the flags are the device's: the tables are computed
+  // there (vp_batch_loop.h) and the launches cannot depend on them -- predict_walk_device's chain, across the batch.
+  const bool devWalk = f->bDevRoute;
+  if (!devWalk) ensure_ids(f);
   bool walk = false;
   int maxLevel = 0;
-  if (predict == 1) {
+  if (predict == 1 && !devWalk) {
     f->hInhParent.resize(N);
     f->hInhLevel.resize(N);
     for (int b = 0; b < nF; b++) {
@@ -3903,7 +3923,21 @@ static int batch_vp_cycle_core(rfsgpu_filter *f, int predict, const double *x, c
   const BatchArg A{f->dBFilt, f->dBParams, f->dBZ, f->dBZPrev, f->dBSums, f->dBErrFilter, nF, nPer};
   if (predict >= 0) {
     const BirthLevel all{nullptr, 0, 1};
-    if (!walk) {
+    if (devWalk && predict == 1) {
+      // the levels from the device's ids, the staging pair and level 0, a fixed RFSGPU_RBPHD_WALK_LEVELS of (copy, birth) pairs that
+      // find no slot of theirs where the walk is shallower, and one workgroup per filter for whatever lies deeper
+      if ((rc = inherit_buffers(f)) != RFSGPU_OK) return rc;
+      vp_batch_walk_levels_kernel<<<(N + 255) / 256, 256, 0, f->stream>>>(f->BL.ppid, f->BL.resampled, N, nPer, RFSGPU_RBPHD_WALK_LEVELS, f->dInhParent, f->dInhLevel,
+                                                                          f->dBVpWalk);
+      birth_inherit_kernel<0><<<N, 128, 0, f->stream>>>(f->B, f->inhTmp, f->dInhParent, f->dInhLevel, 0);
+      birth_inherit_kernel<1><<<N, 128, 0, f->stream>>>(f->B, f->inhTmp, f->dInhParent, f->dInhLevel, 0);
+      launch_predict_kernels_vp_batch(f, 1, BirthLevel{f->dInhLevel, 0, 1}, A);
+      for (int L = 1; L <= RFSGPU_RBPHD_WALK_LEVELS; L++) {
+        birth_inherit_kernel<2><<<N, 128, 0, f->stream>>>(f->B, f->inhTmp, f->dInhParent, f->dInhLevel, L);
+        launch_predict_kernels_vp_batch(f, 1, BirthLevel{f->dInhLevel, L, 0}, A);
+      }
+      vp_batch_walk_tail_kernel<3><<<nF, BIRTH_TAIL_WAVES * 64, 0, f->stream>>>(f->B, f->cur, A, f->dInhParent, f->dInhLevel, RFSGPU_RBPHD_WALK_LEVELS + 1, f->dBVpWalk);
+    } else if (!walk) {
       launch_predict_kernels_vp_batch(f, predict, all, A);
     } else {
       if ((rc = inherit_buffers(f)) != RFSGPU_OK) return rc;
@@ -3963,6 +3997,10 @@ static int batch_vp_cycle_core(rfsgpu_filter *f, int predict, const double *x, c
   }
   HIPCHK(hipGetLastError());
   if (murty_launch_batch<3>(f->Q, f->MS, f->B, f->stream, A, normalize, f->hJobCount, sord) != 0) return fail(f, RFSGPU_ERR_HIP, "batch post kernel launch failed");
+  if (devWalk && anyUpdate) {     // resampleOccured_ of the filters this cycle updates falls on the device, behind the walk's read
+    vp_batch_clear_flags_kernel<<<(nF + 255) / 256, 256, 0, f->stream>>>(f->BL.resampled, f->dBFilt, nF);
+    HIPCHK(hipGetLastError());
+  }
   if (anyUpdate) f->cur ^= 1;   // (filters without an update had their mixture moved to the new slab by the step kernel)
   for (int b = 0; b < nF; b++)
     if (n_z[b] > 0) { f->bNZ[b] = n_z[b]; f->bResampled[b] = 0; }
@@ -4330,7 +4368,7 @@ int rfsgpu_batch_resample_apply(rfsgpu_filter *f, const int *src_slot, const uns
   REFUSE_ON_MH_BATCH(f, "rfsgpu_batch_resample_apply");
   if (!src_slot || !resampled) return fail(f, RFSGPU_ERR_INVALID, "batch_resample_apply: null argument");
   if (f->bDevRoute)
-    return fail(f, RFSGPU_ERR_UNSUPPORTED, "batch_resample_apply: this batch resamples on the device (rfsgpu_batch_resample_async has run): the particle ids, resampleOccured_ "
+    return fail(f, RFSGPU_ERR_UNSUPPORTED, "batch_resample_apply: this batch resamples on the device (rfsgpu_batch_resample_async or rfsgpu_batch_vp_resample_async has run): the particle ids, resampleOccured_ "
                                            "and the resampling counters live there, and the two routes do not mix on one handle");
   const int nF = f->nF, nPer = f->nPer;
   bool any = false;
@@ -4443,6 +4481,12 @@ static int batch_push_motion(rfsgpu_filter *f) {
   memcpy(h, f->bMotion.data(), (size_t)f->nF * sizeof(BatchMotion));
   HIPCHK(hipMemcpyAsync(f->dBMotion, h, (size_t)f->nF * sizeof(BatchMotion), hipMemcpyHostToDevice, f->stream));
   HIPCHK(hipEventRecord(f->bLoop.ev[k], f->stream));
+  if (f->D == 3) {     // a batch of Victoria Park filters: the Ackerman table beside it (rfsgpu_batch_vp_set_motion), a block of its own
+    if ((rc = ring_acquire(f, f->bLoop, &h, &k)) != RFSGPU_OK) return rc;
+    memcpy(h, f->bVpMotion.data(), (size_t)f->nF * sizeof(VpBatchMotion));
+    HIPCHK(hipMemcpyAsync(f->dBVpMotion, h, (size_t)f->nF * sizeof(VpBatchMotion), hipMemcpyHostToDevice, f->stream));
+    HIPCHK(hipEventRecord(f->bLoop.ev[k], f->stream));
+  }
   f->bMotionDirty = false;
   return RFSGPU_OK;
 }
@@ -4534,6 +4578,8 @@ static int batch_resample_core(rfsgpu_filter *f, const BatchCall &C, const int *
   }
   for (int b = 0; b < nF; b++) {
     if (n_z && (rc = batch_check_filter(f, C, b, nullptr, n_z)) != RFSGPU_OK) return rc;
+    if ((!f->bMotionSet[b] || !f->bResSet[b]) && f->D == 3)
+      return batch_fail(f, C, "filter " + std::to_string(b) + (f->bResSet[b] ? " has no Philox key (rfsgpu_batch_vp_set_motion)" : " has no resampling thresholds (rfsgpu_batch_vp_set_resampling)"));
     if (!f->bMotionSet[b] || !f->bResSet[b])
       return batch_fail(f, C, "filter " + std::to_string(b) + (f->bResSet[b] ? " has no Philox key (rfsgpu_batch_set_motion_odometry)" : " has no resampling thresholds (rfsgpu_batch_set_resampling)"));
   }
@@ -4571,6 +4617,10 @@ int rfsgpu_batch_last_resample(rfsgpu_filter *f, unsigned char *fired, int *src_
   if (rc != RFSGPU_OK) return rc;
   REFUSE_ON_VP_BATCH(f, "rfsgpu_batch_last_resample");
   REFUSE_ON_MH_BATCH(f, "rfsgpu_batch_last_resample");
+  return batch_last_resample_core(f, fired, src_slot, n_eff);
+}
+// (the arguments have been checked: rfsgpu_batch_last_resample, rfsgpu_batch_vp_last_resample)
+static int batch_last_resample_core(rfsgpu_filter *f, unsigned char *fired, int *src_slot, double *n_eff) {
   hipSetDevice(f->device);
   if (!f->bDevRoute) {     // no rfsgpu_batch_resample_async yet: nothing fired
     for (int b = 0; b < f->nF; b++) { if (fired) fired[b] = 0; if (n_eff) n_eff[b] = 0.0; }
@@ -4607,6 +4657,110 @@ int rfsgpu_batch_resample_counts(rfsgpu_filter *f, long long *out) {
   hipSetDevice(f->device);
   HIPCHK(hipMemcpyAsync(out, f->BL.nResamples, (size_t)f->nF * sizeof(long long), hipMemcpyDeviceToHost, f->stream));
   HIPCHK(hipStreamSynchronize(f->stream));
+  return RFSGPU_OK;
+}
+
+// ---- the device route of a batch of Victoria Park filters (vp_batch_loop.h): Ackerman propagation of a run of odometry messages and
+// the resampling tail as stream-ordered launches; the birth predict's inheritance walk behind them is batch_vp_cycle_core's ----------
+static const BatchCall BATCH_VP_RESAMPLE{"batch_vp_resample", 0, nullptr, "null measurement counts"};
+static_assert(RFSGPU_BATCH_VP_RUN_MAX == ACKERMAN_RUN_MAX, "a run of a batch is what a handle's run launch takes (VpBatchRun, motion.h)");
+// What the section serves, else RFSGPU_ERR_UNSUPPORTED with the state untouched
+static int vp_loop_check(rfsgpu_filter *f, const char *who, int filter) {
+  if (!f->batch || f->D != 3) {
+    f->err = std::string(who) + ": the call serves a batch of Victoria Park filters (rfsgpu_create_batch with RFSGPU_MODEL_VICTORIAPARK_3D), not " +
+             (f->batch ? "a 2-D batch (its device loop is rfsgpu_batch_set_motion_odometry, _set_resampling, _propagate_async, _resample_async)"
+                       : (f->groupShard ? "a shard of an rfsgpu_group" : "an ordinary handle (rfsgpu_propagate_ackerman_run_async, rfsgpu_rbphd_cycle_async)"));
+    return RFSGPU_ERR_UNSUPPORTED;
+  }
+  if (filter < -1 || filter >= f->nF) { f->err = std::string(who) + ": filter index out of range"; return RFSGPU_ERR_INVALID; }
+  return RFSGPU_OK;
+}
+int rfsgpu_batch_vp_set_motion(rfsgpu_filter *f, int filter, const double *var, const double *geom, unsigned long long seed) {
+  CHECK_HANDLE(f);
+  int rc = vp_loop_check(f, "batch_vp_set_motion", filter);
+  if (rc != RFSGPU_OK) return rc;
+  if (!var || !(var[0] >= 0.0) || !(var[1] >= 0.0)) return fail(f, RFSGPU_ERR_INVALID, "batch_vp_set_motion: var is two variances >= 0 (speed, steering)");
+  if (!geom || !(geom[0] == geom[0]) || !(geom[1] == geom[1]) || !(geom[2] == geom[2]) || !(geom[3] == geom[3]) || geom[1] == 0.0)
+    return fail(f, RFSGPU_ERR_INVALID, "batch_vp_set_motion: geom is {h, l, dx, dy} with l != 0");
+  for (int b = (filter < 0 ? 0 : filter); b < (filter < 0 ? f->nF : filter + 1); b++) {
+    VpBatchMotion &M = f->bVpMotion[b];
+    M.sv = std::sqrt(var[0]); M.sr = std::sqrt(var[1]);
+    M.h = geom[0]; M.l = geom[1]; M.dx = geom[2]; M.dy = geom[3];
+    M.seed = seed;
+    f->bMotion[b].seed = seed;     // (batch_resample_kernel takes the resampling draw's key from this table)
+    f->bMotionSet[b] = 1;
+  }
+  f->bMotionDirty = true;
+  return RFSGPU_OK;
+}
+int rfsgpu_batch_vp_set_resampling(rfsgpu_filter *f, int filter, double eff_n, double eff_n_percent) {
+  CHECK_HANDLE(f);
+  int rc = vp_loop_check(f, "batch_vp_set_resampling", filter);
+  if (rc != RFSGPU_OK) return rc;
+  for (int b = (filter < 0 ? 0 : filter); b < (filter < 0 ? f->nF : filter + 1); b++) {
+    f->bEffN[2 * (size_t)b] = eff_n; f->bEffN[2 * (size_t)b + 1] = eff_n_percent;
+    f->bResSet[b] = 1;
+  }
+  return RFSGPU_OK;
+}
+int rfsgpu_batch_vp_propagate_run_async(rfsgpu_filter *f, int n, const double *u, const unsigned char *noisy, const double *dt, unsigned long long call0) {
+  CHECK_HANDLE(f);
+  int rc = vp_loop_check(f, "batch_vp_propagate_run", -1);
+  if (rc != RFSGPU_OK) return rc;
+  if (n < 0 || (n > 0 && (!u || !dt))) return fail(f, RFSGPU_ERR_INVALID, "batch_vp_propagate_run: bad arguments");
+  if (n > RFSGPU_BATCH_VP_RUN_MAX)
+    return fail(f, RFSGPU_ERR_INVALID, "batch_vp_propagate_run: more than RFSGPU_BATCH_VP_RUN_MAX steps in one call (the run travels through one block of the pinned ring): split it");
+  for (int k = 0; k < n; k++)
+    if (!(dt[k] == dt[k])) return fail(f, RFSGPU_ERR_INVALID, "batch_vp_propagate_run: bad interval");
+  for (int b = 0; b < f->nF; b++)
+    if (!f->bMotionSet[b]) {
+      f->err = "batch_vp_propagate_run: filter " + std::to_string(b) + " has no motion parameters (rfsgpu_batch_vp_set_motion)";
+      return RFSGPU_ERR_INVALID;
+    }
+  if (n == 0) return RFSGPU_OK;
+  hipSetDevice(f->device);
+  if ((rc = batch_push_motion(f)) != RFSGPU_OK) return rc;
+  unsigned char *h = nullptr;
+  int k = 0;
+  if ((rc = ring_acquire(f, f->bLoop, &h, &k)) != RFSGPU_OK) return rc;
+  VpBatchRun *R = reinterpret_cast<VpBatchRun *>(h);
+  memset(R, 0, sizeof *R);
+  R->n = n;
+  R->call0 = call0;
+  for (int r = 0; r < n; r++) {
+    R->uv[r] = u[2 * r]; R->ur[r] = u[2 * r + 1]; R->dt[r] = dt[r];
+    R->noisy[r] = (!noisy || noisy[r]) ? 1 : 0;
+  }
+  HIPCHK(hipMemcpyAsync(f->dBVpRun, R, sizeof *R, hipMemcpyHostToDevice, f->stream));
+  HIPCHK(hipEventRecord(f->bLoop.ev[k], f->stream));
+  // in place: the caller orders the call behind the birth predict, which must still see the poses of the last update
+  vp_batch_propagate_run_kernel<<<(f->N + 255) / 256, 256, 0, f->stream>>>(f->B.pose, f->N, f->nPer, f->dBVpMotion, f->dBVpRun);
+  HIPCHK(hipGetLastError());
+  return RFSGPU_OK;
+}
+int rfsgpu_batch_vp_resample_async(rfsgpu_filter *f, const int *n_z, unsigned long long call) {
+  CHECK_HANDLE(f);
+  int rc = vp_loop_check(f, "batch_vp_resample", -1);
+  if (rc != RFSGPU_OK) return rc;
+  if ((rc = batch_check_call(f, BATCH_VP_RESAMPLE, 0, nullptr, 0, n_z)) != RFSGPU_OK) return rc;
+  return batch_resample_core(f, BATCH_VP_RESAMPLE, n_z, call);
+}
+int rfsgpu_batch_vp_last_resample(rfsgpu_filter *f, unsigned char *fired, int *src_slot, double *n_eff) {
+  CHECK_HANDLE(f);
+  int rc = vp_loop_check(f, "batch_vp_last_resample", -1);
+  if (rc != RFSGPU_OK) return rc;
+  return batch_last_resample_core(f, fired, src_slot, n_eff);
+}
+int rfsgpu_batch_vp_loop_counts(rfsgpu_filter *f, long long *resamplings, int *max_level) {
+  CHECK_HANDLE(f);
+  int rc = vp_loop_check(f, "batch_vp_loop_counts", -1);
+  if (rc != RFSGPU_OK) return rc;
+  hipSetDevice(f->device);
+  int w[2] = {0, 0};
+  if (resamplings) HIPCHK(hipMemcpyAsync(resamplings, f->BL.nResamples, (size_t)f->nF * sizeof(long long), hipMemcpyDeviceToHost, f->stream));
+  if (max_level) HIPCHK(hipMemcpyAsync(w, f->dBVpWalk, sizeof w, hipMemcpyDeviceToHost, f->stream));
+  HIPCHK(hipStreamSynchronize(f->stream));
+  if (max_level) *max_level = std::max(w[VBW_MAXEVER], w[VBW_LAST]);
   return RFSGPU_OK;
 }
 

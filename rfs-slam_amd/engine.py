@@ -585,6 +585,33 @@ class VPFilterBatch(capi.CVPBatch):
         """One predict + update cycle of every filter (rfsgpu_batch_vp_cycle_async)."""
         self.batch_vp_cycle_async(predict, Zs, poses=poses, pose_cov=pose_cov, scan=scan, normalize=normalize)
 
+    # -- the device route: a run of messages without a stop on the host (the 2-D device loop's names, on the batch's own calls) --
+    def set_motion(self, b, var, geom, seed):
+        """Filter b's (None: every filter's) input-noise variances (speed, steering), vehicle geometry (h, l, dx, dy) and Philox key."""
+        self.batch_vp_set_motion(b, var, geom, seed)
+
+    def set_resampling(self, b, eff_n, eff_n_percent):
+        """ParticleFilter::resample's two thresholds for filter b (None: every filter); the gates are self.configs[b]'s."""
+        self.batch_vp_set_resampling(b, eff_n, eff_n_percent)
+
+    def propagate_run_async(self, u, dt, call0, noisy=None):
+        """A run of odometry messages for every slot in one launch, in place (rfsgpu_batch_vp_propagate_run_async): behind the run's
+        birth cycle, in front of its update cycle, which then passes poses=None."""
+        self.batch_vp_propagate_run_async(u, dt, call0, noisy=noisy)
+
+    def resample_async(self, n_z, call):
+        """The tail of RBPHDFilter::update for every filter on the device (rfsgpu_batch_vp_resample_async); from the first call on
+        the ids, resampleOccured_ and the counters are the device's, and update_and_resample (the host-stop route) is refused."""
+        self.batch_vp_resample_async(n_z, call)
+
+    def last_resample(self):
+        """(fired, plan in global slots, n_eff) of the last resample_async (synchronising)."""
+        return self.batch_vp_last_resample()
+
+    def loop_counts(self):
+        """(resamplings per filter, deepest inheritance level any device walk has met) (synchronising)."""
+        return self.batch_vp_loop_counts()
+
     last_step_variant = RBPHDFilter.last_step_variant      # after a cycle: (1, 0, particles per workgroup of the step kernel, 1)
     step_launch_order = RBPHDFilter.step_launch_order      # the step's launch order, across the whole batch
     _gate_config = FilterBatch._gate_config

@@ -38,6 +38,20 @@ import numpy as np
 from .engine import systematic_resample_plan
 
 ACKERMAN = dict(h=0.76, l=2.83, dx=3.78, dy=0.50)   # cfg/rbphdslam_VictoriaPark*.xml <AckermanModel>
+VP_BATCH_RUN_MAX = 16                                # RFSGPU_BATCH_VP_RUN_MAX (include/rfsgpu.h): steps of one propagate_run_async
+
+
+def philox_resample_draw(seed, call):
+    """The resampling draw a batch's device route takes for (filter key, call): 53 bits of Philox4x32-10 block (0, 2, call low word,
+    call high word) under the key, over 2^53 -- in [0, 1) (csrc/batch_loop.h, batch_resample_draw)."""
+    m = 0xFFFFFFFF
+    c = [0, 2, int(call) & m, (int(call) >> 32) & m]
+    k0, k1 = int(seed) & m, (int(seed) >> 32) & m
+    for _ in range(10):
+        p0, p1 = 0xD2511F53 * c[0], 0xCD9E8D57 * c[2]
+        c = [(p1 >> 32) ^ c[1] ^ k0, p1 & m, (p0 >> 32) ^ c[3] ^ k1, p0 & m]
+        k0, k1 = (k0 + 0x9E3779B9) & m, (k1 + 0xBB67AE85) & m
+    return float(((c[0] << 32) | c[1]) >> 11) * (1.0 / 9007199254740992.0)
 
 
 def ackerman_step(x, u_v, u_r, dt, a=ACKERMAN):
@@ -341,10 +355,20 @@ class VictoriaParkBatchRun:
     N_eff decision on the host and one resample_apply for the filters that fire.  keep_history: (n_z, fired, plans) per lidar message.
     One difference from VictoriaParkRun, on both routes alike: the cycle call's normalize flag is the whole batch's, so a filter whose
     set is empty at a lidar message has its (already normalised) weights divided by their sum once more, where VictoriaParkRun leaves
-    them alone (RBPHDFilter.hpp:451-452); the batch is held to the handles stepped through this class, not to VictoriaParkRun."""
+    them alone (RBPHDFilter.hpp:451-452); the batch is held to the handles stepped through this class, not to VictoriaParkRun.
+
+    device_loop: the run is enqueued and nothing is read until synchronize().  The artificial clutter and the measurement sets are
+    still drawn on the host from seeds[b] (they depend on no device state); the poses live on the device.  Per run of messages a
+    batch gets the birth cycle (no sets, at the poses the last update used), static_steps_async, one propagate_run_async (noisy = not
+    stationary, calls numbered by message index), the update cycle with poses=None and resample_async(n_z, call = lidar index): the
+    gates, N_eff, plan, ids and the next birth predict's inheritance walk are the device's.  keep_history reads last_resample per lidar
+    message, which synchronises there.  A list of handles takes the same realisations: propagate_ackerman_run_async under the same key
+    and the same calls, and the host-side decision with the draw the device would take (philox_resample_draw) and the squares added in
+    slot order.  The noise and resampling realisations are Philox's under seeds[b], not numpy's: the same model, another generator
+    (as for the 2-D batch loop), so a device_loop run is compared with a device_loop run.  The normalise-flag difference above stays."""
 
     def __init__(self, target, data, params_per_filter, seeds, var_uv=0.2, var_ur=0.025, noise_inflation=20.0, added_clutter=3.0, eff_n=None,
-                 keep_history=False):
+                 keep_history=False, device_loop=False):
         self.batch = None if isinstance(target, (list, tuple)) else target
         self.handles = list(target) if self.batch is None else None
         self.nF = len(params_per_filter)
@@ -366,12 +390,31 @@ class VictoriaParkBatchRun:
         self.n_lidar = 0
         self.history = [] if keep_history else None
         self._dts = []                    # the intervals of the predicts not yet issued (the first of a run adds the births)
+        self.device_loop = bool(device_loop)
+        self.seeds = [int(s) for s in seeds]
+        self.var = np.array([var_uv, var_ur]) * noise_inflation
+        self._run = []                    # device_loop: (uv, ur, noisy) of the predicts not yet issued
+        self._n_calls = 0                 # ... and the message index of the first of them: the propagation's call number
+        if self.device_loop:
+            a = ACKERMAN
+            self._geom = (a["h"], a["l"], a["dx"], a["dy"])
+            if self.batch is not None:
+                for b in range(self.nF):
+                    self.batch.set_motion(b, self.var, self._geom, self.seeds[b])
+                    self.batch.set_resampling(b, self.eff_n[b], self.eff_n[b] / self.n)
+                self.batch.set_poses(self.x, None)
+            else:
+                for b, f in enumerate(self.handles):
+                    f.set_poses(self.x[self._block(b)], None)
 
     def _block(self, b):
         return slice(b * self.n, (b + 1) * self.n)
 
     def _predict(self, u, dt, stationary):
         self._dts.append(float(dt))
+        if self.device_loop:              # queued: the run goes to the device at the next lidar message
+            self._run.append((float(u[0]), float(u[1]), 0.0 if stationary else 1.0))
+            return
         N = self.nF * self.n
         if stationary:
             uv, ur = np.full(N, u[0]), np.full(N, u[1])
@@ -394,7 +437,10 @@ class VictoriaParkBatchRun:
     def _cycle(self, Zs):
         """The queued predicts and this lidar message's update on the device."""
         q = np.diag([5e-4, 5e-4, 1e-4])[None, :, :] * (np.array(self._dts) ** 2)[:, None, None]      # varlm* x dt^2 (:497-500)
+        dts = np.array(self._dts, dtype=np.float64)
         self._dts = []
+        if self.device_loop:
+            return self._cycle_device(q, dts, Zs)
         one = len(q) == 1 and Zs is not None      # (Zs None: the predicts behind the last lidar message, no update)
         if self.batch is not None:
             f = self.batch
@@ -415,6 +461,67 @@ class VictoriaParkBatchRun:
             if Zs is not None:
                 f.set_step_inputs_async(scan=self.scan)      # (through the pinned ring: no stop behind the predicts just enqueued)
                 f.cycle_async(True if one else None, Zs[b], poses=self.x[self._block(b)], normalize=True)
+
+    def _cycle_device(self, q, dts, Zs):
+        """device_loop: the queued predicts and this lidar message's update, with the propagation between the births (which see the
+        poses of the last update) and the update.  Nothing is read."""
+        r = np.array(self._run, dtype=np.float64).reshape(-1, 3)
+        self._run = []
+        call0 = self._n_calls
+        self._n_calls += len(r)
+        if self.batch is not None:
+            f = self.batch
+            f.set_lmk_process_noise(q[0])
+            f.cycle_async(True, [np.zeros((0, 3))] * self.nF, normalize=False)
+            if len(q) > 1:
+                f.static_steps_async(len(q) - 1, q[1:])
+            for k0 in range(0, len(r), VP_BATCH_RUN_MAX):
+                k1 = min(len(r), k0 + VP_BATCH_RUN_MAX)
+                f.propagate_run_async(r[k0:k1, 0:2], dts[k0:k1], call0 + k0, noisy=r[k0:k1, 2] != 0)
+            if Zs is not None:
+                f.cycle_async(None, Zs, poses=None, scan=self.scan, normalize=True)
+            return
+        var = r[:, 2:3] * self.var[None, :]
+        for b, f in enumerate(self.handles):
+            f.set_lmk_process_noise(q[0])
+            f.predict_map_async(True)
+            if len(q) > 1:
+                f.static_steps_async(len(q) - 1, q[1:])
+            f.propagate_ackerman_run_async(r[:, 0:2], var, dts, self._geom, self.seeds[b], call0)
+            if Zs is not None:
+                f.set_step_inputs_async(scan=self.scan)
+                f.cycle_async(None, Zs[b], poses=None, normalize=True)
+
+    def _resample_device(self, n_z):
+        """device_loop: a batch resamples on the device (nothing is read unless the history is kept); the handles' decision is made
+        here by the rule the device states -- squares added in slot order, the draw of (seeds[b], lidar index)."""
+        call = self.n_lidar - 1
+        if self.batch is not None:
+            self.batch.resample_async(n_z, call)
+            if self.history is None:
+                return None, None
+            fired, glob, _ = self.batch.last_resample()
+            return fired, [glob[self._block(b)] - b * self.n for b in range(self.nF)]
+        fired = np.zeros(self.nF, dtype=bool)
+        plans = [np.arange(self.n) for _ in range(self.nF)]
+        for b, f in enumerate(self.handles):
+            self.n_updates_since[b] += 1
+            if n_z[b] == 0:
+                continue
+            self.n_meas_since[b] += int(n_z[b])
+            P = self.Ps[b]
+            if self.n_updates_since[b] < P["min_updates"] or self.n_meas_since[b] < P["min_measurements"]:
+                continue
+            wb = f.get_weights()
+            neff = 1.0 / float(np.cumsum(wb * wb)[-1])
+            if neff > self.eff_n[b] and neff / self.n > self.eff_n[b] / self.n:
+                continue
+            plans[b] = systematic_resample_plan(wb, philox_resample_draw(self.seeds[b], call))
+            fired[b] = True
+            self.n_updates_since[b] = self.n_meas_since[b] = 0
+            f.resample_apply(plans[b])
+        self.n_resamples += fired
+        return fired, plans
 
     def _resample(self, n_z):
         """RBPHDFilter::update's tail per filter: counters, the two gates, N_eff, the systematic plan with the filter's own draw.  A batch
@@ -474,7 +581,7 @@ class VictoriaParkBatchRun:
                 n_z = np.array([len(z) for z in Zs])
                 self._cycle(Zs)
                 self.n_lidar += 1
-                fired, plans = self._resample(n_z)
+                fired, plans = self._resample_device(n_z) if self.device_loop else self._resample(n_z)
                 if self.history is not None:
                     self.history.append((n_z, fired, plans))
                 t_km = t_k
@@ -486,6 +593,12 @@ class VictoriaParkBatchRun:
     def synchronize(self):
         for f in ([self.batch] if self.batch is not None else self.handles):
             f.synchronize()
+        if self.device_loop:              # the poses (and a batch's counts) are the device's: the one read at the end
+            if self.batch is not None:
+                self.x = self.batch.get_poses()
+                self.n_resamples = self.batch.loop_counts()[0]
+            else:
+                self.x = np.concatenate([f.get_poses() for f in self.handles], 0)
 
 
 def write_vp_logs(log_dir, estimates):

@@ -1,11 +1,15 @@
 #!/usr/bin/env python3
 """Victoria Park (configs[3]) update rate -- not the headline metric (bench.py), a measurement for DESIGN.md.
 5000 particles, Victoria-Park-shaped maps (40 landmarks, 12 measurements per update); state re-seeded every step.
-  python tools/vp_bench.py --batch B [--reps 3] [--particles 100] [--messages 900] [--capacity 384] [--only batch|handles]
+  python tools/vp_bench.py --batch B [--reps 3] [--particles 100] [--messages 900] [--capacity 384] [--only batch|handles|batch_dev]
       A sweep of B Victoria Park RB-PHD filters over the dataset extract (tests/golden/victoria_park_extract.npz, artificial clutter
       on): the filter batch (VPFilterBatch, rfsgpu_batch_vp_cycle_async) against the same B filters as plain handles stepped in turn,
       both through vp_driver.VictoriaParkBatchRun with the same realisations, alternating in this one invocation.  One line per
-      repetition and route, then one JSON line: medians in seconds per sweep, runs (filters) per second, and the ratio."""
+      repetition and route, then one JSON line: medians in seconds per sweep, runs (filters) per second, and the ratio.
+  python tools/vp_bench.py --batch B --device-loop [...]
+      Three routes, alternating: the host-stop batch, the device-loop batch (VictoriaParkBatchRun(device_loop=True): propagation, the
+      resampling tail and the inheritance walk on the device, nothing read until the end) and the handles in turn under the device
+      loop's realisations.  The JSON line adds batch_dev_s, batch_dev_runs_per_s, batch_dev_over_batch and batch_dev_over_handles."""
 import os
 import sys
 import time
@@ -32,9 +36,9 @@ def batch_sweep(nF):
     return Ps, seeds, clutter
 
 
-def batch_one_run(route, nF, n, data, messages, cap):
+def batch_one_run(route, nF, n, data, messages, cap, device_loop=False):
     Ps, seeds, clutter = batch_sweep(nF)
-    if route == "batch":
+    if route in ("batch", "batch_dev"):
         target = pkg.VPFilterBatch(nF, n, gm_capacity=cap)
         for b in range(nF):
             sc.apply_vp_batch_params(target, b, Ps[b])
@@ -47,7 +51,8 @@ def batch_one_run(route, nF, n, data, messages, cap):
             h.synchronize()
         owned = target
     t0 = time.perf_counter()
-    r = pkg.vp_driver.VictoriaParkBatchRun(target, data, Ps, seeds, added_clutter=clutter).run(n_messages=messages)
+    dev = route == "batch_dev" or (route == "handles" and device_loop)
+    r = pkg.vp_driver.VictoriaParkBatchRun(target, data, Ps, seeds, added_clutter=clutter, device_loop=dev).run(n_messages=messages)
     dt = time.perf_counter() - t0
     info = (int(r.n_lidar), int(r.n_resamples.sum()), float(np.mean(np.concatenate([h.gm_sizes() for h in owned]))))
     for h in owned:
@@ -63,26 +68,32 @@ def batch_main():
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--particles", type=int, default=100)
     ap.add_argument("--messages", type=int, default=900)
-    ap.add_argument("--only", choices=["batch", "handles"], default=None)
+    ap.add_argument("--only", choices=["batch", "handles", "batch_dev"], default=None)
     ap.add_argument("--capacity", type=int, default=384)      # (192 is transiently short under the heaviest clutter of the sweep)
+    ap.add_argument("--device-loop", action="store_true")
     a = ap.parse_args()
     data = np.load(os.path.join(ROOT, "tests", "golden", "victoria_park_extract.npz"))
-    routes = [a.only] if a.only else ["handles", "batch"]
+    routes = [a.only] if a.only else (["handles", "batch", "batch_dev"] if a.device_loop else ["handles", "batch"])
     times = {r: [] for r in routes}
     for rep in range(a.reps + 1):                     # (the first repetition warms up: code objects, allocations)
         for route in routes:
-            dt, info = batch_one_run(route, a.batch, a.particles, data, a.messages, a.capacity)
+            dt, info = batch_one_run(route, a.batch, a.particles, data, a.messages, a.capacity, a.device_loop)
             if rep:
                 times[route].append(dt)
-            print("  %-7s rep %d%s: %.4f s for %d filters (%d lidar updates, %d resamplings, mean map size %.1f)" %
+            print("  %-9s rep %d%s: %.4f s for %d filters (%d lidar updates, %d resamplings, mean map size %.1f)" %
                   ((route, rep, "" if rep else " (warm-up)", dt, a.batch) + info), flush=True)
-    out = dict(tool="vp_bench", filters=a.batch, particles=a.particles, messages=a.messages, reps=a.reps)
+    out = dict(tool="vp_bench", filters=a.batch, particles=a.particles, messages=a.messages, reps=a.reps, device_loop=bool(a.device_loop))
     for r in routes:
         med = float(np.median(times[r]))
         out[r + "_s"] = med
+        out[r + "_spread_s"] = float(np.max(times[r]) - np.min(times[r]))
         out[r + "_runs_per_s"] = a.batch / med
-    if len(routes) == 2:
+    if "batch" in routes and "handles" in routes:
         out["batch_over_handles"] = out["batch_runs_per_s"] / out["handles_runs_per_s"]
+    if "batch_dev" in routes and "batch" in routes:
+        out["batch_dev_over_batch"] = out["batch_dev_runs_per_s"] / out["batch_runs_per_s"]
+    if "batch_dev" in routes and "handles" in routes:
+        out["batch_dev_over_handles"] = out["batch_dev_runs_per_s"] / out["handles_runs_per_s"]
     print(json.dumps(out))
 
 
