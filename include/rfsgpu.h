@@ -765,7 +765,9 @@ int rfsgpu_batch_cycle_async(rfsgpu_filter *f, int predict, const double *x, con
  * _vp_set_resampling, _vp_propagate_run_async, _vp_resample_async, _vp_last_resample and _vp_loop_counts, below the 2-D device loop.
  * RFSGPU_ERR_UNSUPPORTED on such a batch, with a message and the state untouched: rfsgpu_batch_cycle_async, the FastSLAM
  * and multi-hypothesis batch calls, the 2-D device loop (rfsgpu_batch_set_motion_odometry, _set_resampling, _propagate_async,
- * _resample_async, _last_resample, _resample_counts), [sensor], [truth], [metric], [estimate] and rfsgpu_rbphd_cycle_async.  rfsgpu_batch_configure on such a batch,
+ * _resample_async, _last_resample, _resample_counts), [sensor], [truth], [metric] and rfsgpu_rbphd_cycle_async -- fifteen standing
+ * refusals -- and, until rfsgpu_batch_vp_serve_estimates(f, 1) switches it on for the batch, [estimate] (with the switch on, the four
+ * log calls of that section serve the batch on both routes; rfsgpu_batch_run_log_estimates stays refused).  rfsgpu_batch_configure on such a batch,
  * and rfsgpu_batch_configure_vp on a 2-D batch, return RFSGPU_ERR_INVALID.  rfsgpu_last_error names the lowest filter that exceeded
  * gm_capacity, and for a full candidate list (RFSGPU_MAX_CANDIDATES) the lowest filter with a slot whose list, with the unused
  * measurements that could join it, stood beyond the limit in a birth predict that reported one: the filter at fault where one
@@ -1297,7 +1299,8 @@ int rfsgpu_batch_run_truth_async(rfsgpu_filter *f, int k_from, int k_to, int tra
  * 1 - 1 / (1 + exp(log-odds))), the skipping of holes and the summation trees are [metric]'s, so best_slot, cardinality and
  * weight_sum of a row equal those of an rfsgpu_step_error record taken at the same point, bit for bit.
  * An ordinary handle that [metric] refuses -- the Victoria Park model, a handle that has run rfsgpu_fastslam_update or a FastSLAM
- * cycle -- is served by the four log calls once rfsgpu_handle_serve_estimates(f, 1) has been called (below).
+ * cycle -- is served by the four log calls once rfsgpu_handle_serve_estimates(f, 1) has been called (below), and a batch of Victoria
+ * Park filters once rfsgpu_batch_vp_serve_estimates(f, 1) has been called (below it).
  * One record per filter and row; every field is 8 bytes wide. */
 struct rfsgpu_step_estimate {
   double t;                 /* the time given with the call                                                                  */
@@ -1366,6 +1369,23 @@ int rfsgpu_batch_run_log_estimates(rfsgpu_filter *f, int on, double w_threshold)
  * on == 0: synchronises, frees an existing log and restores the refusals.  RFSGPU_ERR_UNSUPPORTED, naming the reason: a batch of any
  * kind, a shard of an rfsgpu_group.  RFSGPU_ERR_INVALID: a null handle. */
 int rfsgpu_handle_serve_estimates(rfsgpu_filter *f, int on);
+/* The switch of a BATCH OF VICTORIA PARK FILTERS (rfsgpu_create_batch with RFSGPU_MODEL_VICTORIAPARK_3D); off at creation, and while it
+ * is off every call of this section refuses such a batch as described above, with the same codes and texts.  on != 0 (synchronising):
+ * rfsgpu_estimate_log_create, _reset, _read and rfsgpu_step_estimate_async serve the batch with the signatures and log semantics above:
+ * hdr [cap][n_filters], gauss [cap][n_filters][6][max_est] with 0 <= max_est <= gm_capacity, part [cap][n_filters][4][n_per_filter],
+ * t [n_filters].  A filter's row is the row of a Victoria Park handle that rfsgpu_handle_serve_estimates serves, from the same code in
+ * the same order, so it carries the bits such a handle holding the same state produces: the six planes are u(0), u(1), S(0,0), S(0,1),
+ * S(1,1) and w of the best particle's 3-D landmarks (no diameter), weights are plain weights, best_slot is a GLOBAL slot (filter b's
+ * lies in [b n_per_filter, (b + 1) n_per_filter)), n_particles is n_per_filter, status is 0 or 1.
+ * rfsgpu_step_estimate_async is stream-ordered on both routes of such a batch and waits for nothing: it reads weights, poses, counts
+ * and the current slab where it stands in the stream and changes nothing; on the device route it neither resolves anything nor takes
+ * the ids, flags or counters over (a row enqueued behind rfsgpu_batch_vp_resample_async sees the gathered state).  A full log, or no
+ * log: RFSGPU_ERR_CAPACITY, nothing is enqueued.  rfsgpu_batch_run_log_estimates, every [metric] call and
+ * rfsgpu_handle_serve_estimates keep refusing the batch as they do.
+ * on == 0: synchronises, frees an existing log and restores the refusals.  RFSGPU_ERR_UNSUPPORTED with the state untouched, naming
+ * the call that serves it: a 2-D, FastSLAM or multi-hypothesis batch, an ordinary handle, a shard of an rfsgpu_group.
+ * RFSGPU_ERR_INVALID: a null handle. */
+int rfsgpu_batch_vp_serve_estimates(rfsgpu_filter *f, int on);
 
 #ifdef __cplusplus
 }

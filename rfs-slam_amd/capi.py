@@ -171,7 +171,7 @@ ABI_SYMBOLS = [
     "batch_set_truth", "batch_generate_truth", "batch_get_truth", "batch_run_truth_async",
     "batch_fastslam_serve_sensor", "batch_fastslam_cycle_sensed_async", "batch_fastslam_mh_cycle_sensed_async",
     "estimate_log_create", "estimate_log_reset", "step_estimate_async", "estimate_log_read", "batch_run_log_estimates",
-    "handle_serve_estimates",
+    "handle_serve_estimates", "batch_vp_serve_estimates",
     "batch_configure_vp", "batch_vp_cycle_async",
     "batch_vp_set_motion", "batch_vp_set_resampling", "batch_vp_propagate_run_async", "batch_vp_resample_async", "batch_vp_last_resample", "batch_vp_loop_counts",
 ]
@@ -814,7 +814,8 @@ class CFilter:
     # -- [estimate] per-step pose and map estimates in a device-side log (rfsgpu_step_estimate*, csrc/estimate_log.h) ------------
     @property
     def n_estimate_slots(self):
-        """Slots per particle plane of the estimate log: max_per_filter, n_per_filter, or the particle count of an ordinary handle."""
+        """Slots per particle plane of the estimate log: max_per_filter, n_per_filter (a Victoria Park batch included), or the particle
+        count of an ordinary handle."""
         if getattr(self, "_est_served", False):
             return int(self.max_particles)
         return int(getattr(self, "max_per_filter", getattr(self, "n_per_filter", None) or self.n))
@@ -1254,6 +1255,14 @@ class CVPBatch(CBatch):
         lv = C.c_int(0)
         self._call("batch_vp_loop_counts", self._ptr(out), C.byref(lv))
         return out, int(lv.value)
+
+    def serve_estimates(self, on=True):
+        """rfsgpu_batch_vp_serve_estimates (synchronising): estimate_log_create / _reset / _read and step_estimate_async serve this batch on
+        both routes -- one row per call and filter, a Victoria Park handle's row with best_slot a global slot; step_estimate_async waits
+        for nothing.  Off frees the log and restores the refusals."""
+        self._call("batch_vp_serve_estimates", C.c_int(1 if on else 0))
+        if not on:
+            self._est_shape = None
 
 
 class CBatchMH(CBatch):

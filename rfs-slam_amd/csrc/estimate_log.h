@@ -26,6 +26,10 @@
 // handle's cycle block read where the kernel runs (status 2 and a count of 0 once a cycle overflowed).  The instantiations without one
 // compile to what they compiled to before it existed.
 //
+// An EstimateBatch<3> as the trailing argument: a batch of Victoria Park filters that rfsgpu_batch_vp_serve_estimates serves -- the 3-D
+// layout of the handle form with the batch's b = blockIdx.x and lo = b * nPer, the count the host's n_per_filter.  Code and order are
+// those of the handle form, so a filter's row carries the bits a served handle holding the same state produces.
+//
 // Bounds: a Gaussian is stored at pos < maxEst <= cap (the engine checks max_est against gm_capacity), a particle at s < nLive <=
 // nPer <= slots (the stride the part array was allocated with; a served handle: s < n_live <= max_particles <= slots); nothing else is
 // written but lane 0's header.
@@ -57,8 +61,13 @@ struct EstimateHandle {
   const int *n;     // [1] live particle count (FSC_N)
   const int *ovf;   // [1] != 0: a pending cycle overflowed max_particles and was abandoned (FSC_OVF)
 };
-template <typename... T> struct estimate_traits { static constexpr int D = 2; static constexpr bool handle = false, behind = false; };
-template <int D_, bool kBehind> struct estimate_traits<EstimateHandle<D_, kBehind>> { static constexpr int D = D_; static constexpr bool handle = true, behind = kBehind; };
+// The trailing tag of a filter batch whose slabs have the layout D (3: a batch of Victoria Park filters): every filter fills its block,
+// nothing is read through it.
+template <int D>
+struct EstimateBatch {};
+template <typename... T> struct estimate_traits { static constexpr int D = 2; static constexpr bool handle = false, behind = false, live = sizeof...(T) == 1; };
+template <int D_, bool kBehind> struct estimate_traits<EstimateHandle<D_, kBehind>> { static constexpr int D = D_; static constexpr bool handle = true, behind = kBehind, live = false; };
+template <int D_> struct estimate_traits<EstimateBatch<D_>> { static constexpr int D = D_; static constexpr bool handle = false, behind = false, live = false; };
 
 template <typename... TLive>
 __global__ __launch_bounds__(64) void estimate_log_kernel(Buffers B, int cur, EstimateArg A, TLive... live) {
@@ -77,7 +86,7 @@ __global__ __launch_bounds__(64) void estimate_log_kernel(Buffers B, int cur, Es
       nLive = __builtin_amdgcn_readfirstlane(*L.n);
       nLive = (ovf != 0 || nLive < 0) ? 0 : (nLive > nPer ? nPer : nLive);
     }
-  } else if constexpr (sizeof...(TLive) == 1) {   // a MetricLive: the filter's count lives on the device (wave-uniform: one scalar read)
+  } else if constexpr (TR::live) {   // a MetricLive: the filter's count lives on the device (wave-uniform: one scalar read)
     const MetricLive &L = pack_first(live...);
     nLive = __builtin_amdgcn_readfirstlane(L.words[(size_t)b * L.wordStride + L.word]);
     nLive = nLive < 0 ? 0 : (nLive > nPer ? nPer : nLive);

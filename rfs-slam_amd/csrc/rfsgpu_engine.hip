@@ -308,6 +308,7 @@ struct rfsgpu_filter {
   bool estRunOn = false;                                // rfsgpu_batch_run_log_estimates: rfsgpu_batch_run_truth_async appends a row per step
   double estRunThr = 0.0;
   bool estServe = false;                                // rfsgpu_handle_serve_estimates: the [estimate] log calls serve this ordinary handle (either model, either filter class)
+  bool estServeVpBatch = false;                         // rfsgpu_batch_vp_serve_estimates: the [estimate] log calls serve this batch of Victoria Park filters
   bool groupShard = false;                       // a shard of an rfsgpu_group: the [metric] calls refuse
 };
 
@@ -5232,9 +5233,10 @@ int rfsgpu_get_map_estimate(rfsgpu_filter *f, int filter, double w_threshold, in
 
 // ---- [estimate] per-step pose and map estimates in a device-side log (estimate_log.h) -------------------------------------------------
 // Served where [metric] is served -- every call starts with metric_check -- and on an ordinary handle whose switch
-// (rfsgpu_handle_serve_estimates) is on: the four log calls start with estimate_check there.
+// (rfsgpu_handle_serve_estimates) is on, and on a batch of Victoria Park filters whose switch (rfsgpu_batch_vp_serve_estimates) is on:
+// the four log calls start with estimate_check there.
 static inline int estimate_slots(const rfsgpu_filter *f) { return f->batch ? f->nPer : (f->estServe ? f->Ncap : f->N); }
-static int estimate_check(rfsgpu_filter *f, const char *what) { return f->estServe ? RFSGPU_OK : metric_check(f, what); }
+static int estimate_check(rfsgpu_filter *f, const char *what) { return (f->estServe || f->estServeVpBatch) ? RFSGPU_OK : metric_check(f, what); }
 // (a served handle that has run FastSLAM updates or cycles: log-odds weights, as on a FastSLAM batch)
 static inline bool estimate_log_odds(const rfsgpu_filter *f) { return metric_log_odds(f) || (f->estServe && f->fastSlamHandle); }
 static void estimate_log_free(rfsgpu_filter *f) {
@@ -5272,6 +5274,8 @@ static int estimate_launch(rfsgpu_filter *f, const double *t, double w_threshold
   } else if (behind) {  // f->cur counts the flips of the pending cycles; a cycle that did not flip was abandoned by an overflow, and its row reads no slab
     if (f->D == 3) estimate_log_kernel<<<grid, 64, 0, f->stream>>>(f->B, f->cur, A, EstimateHandle<3, true>{f->mhc.w + FSC_N, f->mhc.w + FSC_OVF});
     else estimate_log_kernel<<<grid, 64, 0, f->stream>>>(f->B, f->cur, A, EstimateHandle<2, true>{f->mhc.w + FSC_N, f->mhc.w + FSC_OVF});
+  } else if (f->batch && f->D == 3) {     // a served batch of Victoria Park filters: every filter fills its block, on both routes
+    estimate_log_kernel<<<grid, 64, 0, f->stream>>>(f->B, f->cur, A, EstimateBatch<3>{});
   } else if (f->D == 3) {
     estimate_log_kernel<<<grid, 64, 0, f->stream>>>(f->B, f->cur, A, EstimateHandle<3, false>{nullptr, nullptr});
   } else {
@@ -5290,6 +5294,26 @@ int rfsgpu_handle_serve_estimates(rfsgpu_filter *f, int on) {
   HIPCHK(hipStreamSynchronize(f->stream));
   if (!on) estimate_log_free(f);
   f->estServe = on != 0;
+  return RFSGPU_OK;
+}
+// The switch of a batch of Victoria Park filters: off at creation, so the batch's refusals of the section stand until a caller asks.
+// Nothing of such a batch is ever pending on the host's side (the device route keeps its ids, flags and counters on the device and
+// the host never sizes by them), so rfsgpu_step_estimate_async enqueues as it stands on both routes.
+int rfsgpu_batch_vp_serve_estimates(rfsgpu_filter *f, int on) {
+  CHECK_HANDLE_HOST(f);
+  if (!f->batch || f->D != 3 || f->mhBatch) {
+    f->err = std::string("batch_vp_serve_estimates: the switch is for a batch of Victoria Park filters (rfsgpu_create_batch with RFSGPU_MODEL_VICTORIAPARK_3D), not ") +
+             (f->batch ? (f->mhBatch ? "a batch of multi-hypothesis FastSLAM filters ([estimate] serves it once rfsgpu_batch_mh_serve_metrics is on)"
+                                     : (f->bKind == 2 ? "a batch of FastSLAM filters ([estimate] serves it as it is: rfsgpu_estimate_log_create)"
+                                                      : "a 2-D batch ([estimate] serves it as it is: rfsgpu_estimate_log_create)"))
+                       : (f->groupShard ? "a shard of an rfsgpu_group (no call of [estimate] serves one: rfsgpu_group_get_poses, rfsgpu_group_get_weights and rfsgpu_group_get_landmark read its state)"
+                                        : "an ordinary handle (rfsgpu_handle_serve_estimates)"));
+    return RFSGPU_ERR_UNSUPPORTED;
+  }
+  hipSetDevice(f->device);
+  HIPCHK(hipStreamSynchronize(f->stream));
+  if (!on) estimate_log_free(f);
+  f->estServeVpBatch = on != 0;
   return RFSGPU_OK;
 }
 int rfsgpu_estimate_log_create(rfsgpu_filter *f, int log_capacity, int max_est, int log_particles) {

@@ -567,7 +567,8 @@ class VPFilterBatch(capi.CVPBatch):
     rfsgpu_batch_vp_cycle_async): per cycle the births and the static step, the fused Victoria Park step and the post launch, one chain
     for all filters.  Filter b owns the global slots [b * n_per_filter, (b + 1) * n_per_filter) and has its own configuration (any
     birth thresholds: the candidate lists are per slot), model, measurement set, weights, normalisation and resampling; the laser scan
-    is the batch's.  Each filter equals a separate Victoria Park RBPHDFilter given the same inputs."""
+    is the batch's.  Each filter equals a separate Victoria Park RBPHDFilter given the same inputs.  serve_estimates(True) opens the
+    device-side estimate log to the batch (estimate_log_create / step_estimate_async / estimate_log_read: one row per call and filter)."""
 
     def __init__(self, n_filters, n_per_filter, device_id=0, gm_capacity=512):
         super().__init__(load_library(), "rfsgpu_", n_filters, n_per_filter, device_id=device_id, gm_capacity=gm_capacity)

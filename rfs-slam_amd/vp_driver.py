@@ -365,10 +365,16 @@ class VictoriaParkBatchRun:
     message, which synchronises there.  A list of handles takes the same realisations: propagate_ackerman_run_async under the same key
     and the same calls, and the host-side decision with the draw the device would take (philox_resample_draw) and the squares added in
     slot order.  The noise and resampling realisations are Philox's under seeds[b], not numpy's: the same model, another generator
-    (as for the 2-D batch loop), so a device_loop run is compared with a device_loop run.  The normalise-flag difference above stays."""
+    (as for the 2-D batch loop), so a device_loop run is compared with a device_loop run.  The normalise-flag difference above stays.
+
+    log_estimates: VictoriaParkRun's log for every filter, on both routes and both kinds of target -- one row before the loop at the
+    first message's time (the poses set on the device), then one row per lidar message behind that message's resampling step.  A batch
+    goes through rfsgpu_batch_vp_serve_estimates with the time repeated per filter, a list of handles through handle_serve_estimates
+    per handle.  run() creates the log (1 + number of lidar messages rows, log_max_est Gaussians per row: None = gm_capacity); with
+    device_loop the rows go behind the enqueued work and nothing is read; estimates() is the one read."""
 
     def __init__(self, target, data, params_per_filter, seeds, var_uv=0.2, var_ur=0.025, noise_inflation=20.0, added_clutter=3.0, eff_n=None,
-                 keep_history=False, device_loop=False):
+                 keep_history=False, device_loop=False, log_estimates=False, log_particles=True, log_w_threshold=-np.inf, log_max_est=None):
         self.batch = None if isinstance(target, (list, tuple)) else target
         self.handles = list(target) if self.batch is None else None
         self.nF = len(params_per_filter)
@@ -406,6 +412,32 @@ class VictoriaParkBatchRun:
             else:
                 for b, f in enumerate(self.handles):
                     f.set_poses(self.x[self._block(b)], None)
+        self.log_estimates, self.log_particles, self.log_w_threshold = bool(log_estimates), bool(log_particles), float(log_w_threshold)
+        self.log_max_est = None if log_max_est is None else int(log_max_est)
+        if self.log_estimates:
+            if self.batch is not None:
+                self.batch.serve_estimates(True)
+            else:
+                for f in self.handles:
+                    f.handle_serve_estimates(True)
+
+    def _targets(self):
+        return [self.batch] if self.batch is not None else self.handles
+
+    def _log_row(self, t):
+        """One row of every filter's estimate log behind whatever is enqueued (a batch: the time repeated per filter)."""
+        if self.log_estimates:
+            for f in self._targets():
+                f.step_estimate_async(float(t), self.log_w_threshold)
+
+    def estimates(self):
+        """(hdr, gauss, part) with the filter axis ([rows, n_filters, ...]): the one read at the end.  A batch's best_slot is a global
+        slot; a list of handles is stacked onto the same axes with best_slot as each handle reports it (a slot of its own)."""
+        if self.batch is not None:
+            return self.batch.estimate_log_read()
+        logs = [f.estimate_log_read() for f in self.handles]
+        part = None if logs[0][2] is None else np.concatenate([l[2] for l in logs], axis=1)
+        return np.concatenate([l[0] for l in logs], axis=1), np.concatenate([l[1] for l in logs], axis=1), part
 
     def _block(self, b):
         return slice(b * self.n, (b + 1) * self.n)
@@ -562,6 +594,18 @@ class VictoriaParkBatchRun:
     def run(self, n_messages=None):
         t_km, u_km, stationary, z_idx = 0.0, np.zeros(2), True, 0
         msgs = self.mgr if n_messages is None else self.mgr[:n_messages]
+        if self.log_estimates:            # a row before the loop and one per lidar message, counted here
+            rows = 1 + int(sum(1 for m in msgs if m[1] == 3))
+            for f in self._targets():
+                f.estimate_log_create(rows, f.gm_capacity if self.log_max_est is None else self.log_max_est, self.log_particles)
+            if not self.device_loop:      # (device_loop: the constructor has set the poses on the device)
+                if self.batch is not None:
+                    self.batch.set_poses(self.x, None)
+                else:
+                    for b, f in enumerate(self.handles):
+                        f.set_poses(self.x[self._block(b)], None)
+            if len(msgs):
+                self._log_row(msgs[0][0])
         for t_k, typ, idx in msgs:
             idx = int(idx) - 1
             dt = t_k - t_km
@@ -584,6 +628,7 @@ class VictoriaParkBatchRun:
                 fired, plans = self._resample_device(n_z) if self.device_loop else self._resample(n_z)
                 if self.history is not None:
                     self.history.append((n_z, fired, plans))
+                self._log_row(t_k)
                 t_km = t_k
         if self._dts:
             self._cycle(None)
@@ -601,22 +646,28 @@ class VictoriaParkBatchRun:
                 self.x = np.concatenate([f.get_poses() for f in self.handles], 0)
 
 
-def write_vp_logs(log_dir, estimates):
+def write_vp_logs(log_dir, estimates, filter=0):
     """particlePose.dat and landmarkEst.dat in the reference's Victoria Park format (std::fixed, precision 3, widths 10 / 5 / 10 ...:
     src/rbphdslam_VictoriaPark.cpp:427-440, :586-622) from (hdr, gauss, part) as VictoriaParkRun.estimates() returns them: per row
     the row's n_particles particles (a log without particles: none), then its n_logged Gaussians under the best slot's index.
+    The lines are "%10.3f%5d" + 4 * "%10.3f" (time, particle, x, y, theta, weight) and "%10.3f%5d" + 6 * "%10.3f" (time, best slot,
+    the six planes).  filter: which filter of a log with a filter axis (VictoriaParkBatchRun.estimates()); its best slot is printed
+    relative to the filter's block of n_particles slots, so a batch's file equals the file of the same filter run as a handle.
     Returns the two paths."""
     import os
     hdr, gauss, part = estimates
+    b = int(filter)
     poses, lms = [], []
     for r in range(hdr.shape[0]):
-        h = hdr[r, 0]
+        h = hdr[r, b]
         t = float(h["t"])
         if part is not None:
-            p = part[r, 0]
+            p = part[r, b]
             for i in range(int(h["n_particles"])):
                 poses.append("%10.3f%5d%10.3f%10.3f%10.3f%10.3f\n" % (t, i, p[0, i], p[1, i], p[2, i], p[3, i]))
-        g, best = gauss[r, 0], int(h["best_slot"])
+        g, best = gauss[r, b], int(h["best_slot"])
+        if b:                     # (a global slot of a batch: within the filter's block; a handle's own slot stays what it is)
+            best %= max(int(h["n_particles"]), 1)
         for m in range(int(h["n_logged"])):
             lms.append("%10.3f%5d%10.3f%10.3f%10.3f%10.3f%10.3f%10.3f\n" % (t, best, g[0, m], g[1, m], g[2, m], g[3, m], g[4, m], g[5, m]))
     os.makedirs(log_dir, exist_ok=True)
@@ -625,3 +676,9 @@ def write_vp_logs(log_dir, estimates):
         with open(path, "w") as fh:
             fh.writelines(lines)
     return paths
+
+
+def write_vp_batch_logs(root, estimates):
+    """write_vp_logs for every filter of (hdr, gauss, part) with a filter axis, into root/filter_%03d/.  Returns the list of path pairs."""
+    import os
+    return [write_vp_logs(os.path.join(root, "filter_%03d" % b), estimates, filter=b) for b in range(estimates[0].shape[1])]

@@ -9,7 +9,14 @@
   python tools/vp_bench.py --batch B --device-loop [...]
       Three routes, alternating: the host-stop batch, the device-loop batch (VictoriaParkBatchRun(device_loop=True): propagation, the
       resampling tail and the inheritance walk on the device, nothing read until the end) and the handles in turn under the device
-      loop's realisations.  The JSON line adds batch_dev_s, batch_dev_runs_per_s, batch_dev_over_batch and batch_dev_over_handles."""
+      loop's realisations.  The JSON line adds batch_dev_s, batch_dev_runs_per_s, batch_dev_over_batch and batch_dev_over_handles.
+  python tools/vp_bench.py --batch B --device-loop --log [--log-dir DIR] [--no-log-particles] [...]
+      What recording the sweep's per-update estimates costs.  Three routes of the device-loop batch, alternating: unlogged; logged on
+      the device (VictoriaParkBatchRun(log_estimates=True): rfsgpu_batch_vp_serve_estimates, one row per lidar message behind its
+      resampling step, nothing read until the end -- the one read, estimates(), is timed apart as log_read_s); and the per-update
+      getter route (get_weights + get_poses + the best slot's map per filter and lidar message, each of which synchronises).  The
+      JSON line holds the medians, the log's size in MiB and the ratios.  --log-dir: the last logged repetition's files
+      (write_vp_batch_logs: DIR/filter_%03d/particlePose.dat and landmarkEst.dat), written outside the timed part."""
 import os
 import sys
 import time
@@ -60,6 +67,86 @@ def batch_one_run(route, nF, n, data, messages, cap, device_loop=False):
     return dt, info
 
 
+def log_one_run(route, nF, n, data, messages, cap, particles=True, log_dir=None):
+    """One device-loop sweep of the batch: route 'plain' (no log), 'logged' (the device-side log) or 'getters' (the per-update getters).
+    Returns (seconds of the run, seconds of the one read or 0, info, log bytes)."""
+    drv = pkg.vp_driver
+    Ps, seeds, clutter = batch_sweep(nF)
+    batch = pkg.VPFilterBatch(nF, n, gm_capacity=cap)
+    for b in range(nF):
+        sc.apply_vp_batch_params(batch, b, Ps[b])
+    batch.synchronize()
+    kept = []
+
+    class GetterRun(drv.VictoriaParkBatchRun):
+        """What a sweep without the device-side log has to do per lidar message to keep the two files' content."""
+
+        def _log_row(self, t):
+            w, x = batch.get_weights(), batch.get_poses()
+            best = [b * n + int(np.argmax(w[b * n:(b + 1) * n])) for b in range(nF)]
+            kept.append((t, w, x, [batch.export_gm(s) for s in best]))
+
+    cls = GetterRun if route == "getters" else drv.VictoriaParkBatchRun
+    t0 = time.perf_counter()
+    r = cls(batch, data, Ps, seeds, added_clutter=clutter, device_loop=True, log_estimates=(route == "logged"), log_particles=particles).run(n_messages=messages)
+    dt = time.perf_counter() - t0
+    t_read, nbytes = 0.0, 0
+    if route == "logged":
+        t1 = time.perf_counter()
+        est = r.estimates()
+        t_read = time.perf_counter() - t1
+        nbytes = sum(a.nbytes for a in est if a is not None)
+        if log_dir:
+            drv.write_vp_batch_logs(log_dir, est)
+    info = (int(r.n_lidar), int(np.sum(r.n_resamples)), float(np.mean(batch.gm_sizes())))
+    batch.close()
+    return dt, t_read, info, nbytes
+
+
+def log_main():
+    import argparse
+    import json
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batch", type=int, required=True)
+    ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--particles", type=int, default=100)
+    ap.add_argument("--messages", type=int, default=900)
+    ap.add_argument("--capacity", type=int, default=384)
+    ap.add_argument("--device-loop", action="store_true", required=True)
+    ap.add_argument("--log", action="store_true")
+    ap.add_argument("--log-dir", default=None)
+    ap.add_argument("--no-log-particles", action="store_true")
+    ap.add_argument("--only", choices=["plain", "logged", "getters"], default=None)
+    a = ap.parse_args()
+    data = np.load(os.path.join(ROOT, "tests", "golden", "victoria_park_extract.npz"))
+    routes = [a.only] if a.only else ["plain", "logged", "getters"]
+    times, reads, nbytes = {r: [] for r in routes}, [], 0
+    for rep in range(a.reps + 1):                     # (the first repetition warms up: code objects, allocations)
+        for route in routes:
+            dt, t_read, info, nb = log_one_run(route, a.batch, a.particles, data, a.messages, a.capacity, not a.no_log_particles,
+                                               a.log_dir if rep == a.reps else None)
+            if rep:
+                times[route].append(dt)
+                if route == "logged":
+                    reads.append(t_read)
+            nbytes = max(nbytes, nb)
+            print("  %-8s rep %d%s: %.4f s%s for %d filters (%d lidar updates, %d resamplings, mean map size %.1f)" %
+                  ((route, rep, "" if rep else " (warm-up)", dt, (" + %.4f s read" % t_read) if route == "logged" else "", a.batch) + info), flush=True)
+    out = dict(tool="vp_bench", mode="log", filters=a.batch, particles=a.particles, messages=a.messages, reps=a.reps, log_particles=not a.no_log_particles)
+    for r in routes:
+        out[r + "_s"] = float(np.median(times[r]))
+        out[r + "_spread_s"] = float(np.max(times[r]) - np.min(times[r]))
+    if "logged" in routes:
+        out["log_read_s"] = float(np.median(reads))
+        out["logged_with_read_s"] = out["logged_s"] + out["log_read_s"]
+        out["log_mib"] = nbytes / 2.0 ** 20
+    if "logged" in routes and "plain" in routes:
+        out["logged_with_read_over_plain"] = out["logged_with_read_s"] / out["plain_s"]
+    if "logged" in routes and "getters" in routes:
+        out["getters_over_logged_with_read"] = out["getters_s"] / out["logged_with_read_s"]
+    print(json.dumps(out))
+
+
 def batch_main():
     import argparse
     import json
@@ -98,7 +185,7 @@ def batch_main():
 
 
 if "--batch" in sys.argv:
-    batch_main()
+    log_main() if "--log" in sys.argv else batch_main()
     sys.exit(0)
 N, NM, NZ = [int(os.environ.get(k, d)) for k, d in (("VP_N", 5000), ("VP_NM", 40), ("VP_NZ", 12))]
 scen = sc.make_vp_scenario(N, NM, NZ, seed=4321, scan="ragged")
