@@ -767,7 +767,8 @@ int rfsgpu_batch_cycle_async(rfsgpu_filter *f, int predict, const double *x, con
  * and multi-hypothesis batch calls, the 2-D device loop (rfsgpu_batch_set_motion_odometry, _set_resampling, _propagate_async,
  * _resample_async, _last_resample, _resample_counts), [sensor], [truth], [metric] and rfsgpu_rbphd_cycle_async -- fifteen standing
  * refusals -- and, until rfsgpu_batch_vp_serve_estimates(f, 1) switches it on for the batch, [estimate] (with the switch on, the four
- * log calls of that section serve the batch on both routes; rfsgpu_batch_run_log_estimates stays refused).  rfsgpu_batch_configure on such a batch,
+ * log calls of that section serve the batch on both routes; rfsgpu_batch_run_log_estimates stays refused).  rfsgpu_batch_vp_serve_fastslam(f, 1), below the cycle call, makes such a batch step
+ * FastSLAM filters instead; until then the FastSLAM calls stay refused as listed.  rfsgpu_batch_configure on such a batch,
  * and rfsgpu_batch_configure_vp on a 2-D batch, return RFSGPU_ERR_INVALID.  rfsgpu_last_error names the lowest filter that exceeded
  * gm_capacity, and for a full candidate list (RFSGPU_MAX_CANDIDATES) the lowest filter with a slot whose list, with the unused
  * measurements that could join it, stood beyond the limit in a birth predict that reported one: the filter at fault where one
@@ -786,6 +787,38 @@ int rfsgpu_batch_configure_vp(rfsgpu_filter *f, int filter, const rfsgpu_filter_
  * step launch), 1 (0: no step launch)}. */
 int rfsgpu_batch_vp_cycle_async(rfsgpu_filter *f, int predict, const double *x, const double *x_cov, int cov_stride,
                                 const double *z, const int *n_z, const double *scan, int n_scan, int normalize);
+/* -- a batch of Victoria Park FastSLAM filters (single hypothesis): the switch that makes a batch created with
+ * RFSGPU_MODEL_VICTORIAPARK_3D step FastSLAM filters instead of RB-PHD filters.  Off at creation, like
+ * rfsgpu_batch_vp_serve_estimates and rfsgpu_batch_mh_serve_metrics: with the switch off every refusal above stands.
+ * on != 0: the batch is a FastSLAM batch from here on.  rfsgpu_batch_set_fastslam_config serves it, per filter or -1, with
+ * landmarkCandidateMeasurementCountThreshold free (the lists live one candidate per lane: at most 64 per particle, a fuller list
+ * raises the candidate-list error as on a handle; a 2-D batch keeps refusing thresholds other than 1) and maxNDataAssocHypotheses
+ * != 1 still refused, naming the filter.  Its cycle is rfsgpu_batch_vp_fastslam_cycle_async; rfsgpu_batch_vp_cycle_async refuses.
+ * Each filter equals a separate Victoria Park handle stepped by rfsgpu_predict_map(f, 0) / rfsgpu_fastslam_update on the same
+ * inputs, bit for bit.  The host-stop route (rfsgpu_batch_weight_sums, rfsgpu_batch_resample_apply, rfsgpu_batch_resample_occured)
+ * and the device route (rfsgpu_batch_vp_set_motion, _vp_set_resampling, _vp_propagate_run_async, _vp_resample_async,
+ * _vp_last_resample, _vp_loop_counts) and rfsgpu_static_steps_async serve it.  Both resampling routes move the landmark candidate
+ * lists, the unused mask and the in-view count with the particle, as rfsgpu_resample_apply does on a FastSLAM handle; the two gates
+ * of rfsgpu_batch_vp_resample_async are the FastSLAM configuration's minUpdatesBeforeResample / minMeasurementsBeforeResample, as on
+ * a 2-D FastSLAM batch; no birth predict and no inheritance walk is launched.  Still refused on such a batch: [sensor], [truth],
+ * [metric], [estimate] (rfsgpu_batch_vp_serve_estimates included), the 2-D device loop, rfsgpu_batch_fastslam_cycle_async and the
+ * RB-PHD and multi-hypothesis batch calls.
+ * RFSGPU_ERR_UNSUPPORTED with a message and the state untouched: not a batch of Victoria Park filters; on != 0 after
+ * rfsgpu_batch_vp_cycle_async has run, or while rfsgpu_batch_vp_serve_estimates is on (a batch is of one kind); on == 0 after
+ * rfsgpu_batch_vp_fastslam_cycle_async has run.  RFSGPU_ERR_INVALID: a null handle. */
+int rfsgpu_batch_vp_serve_fastslam(rfsgpu_filter *f, int on);
+/* FastSLAM::predict's map part + the single-hypothesis FastSLAM::update for every filter of such a batch at once.  Semantics are
+ * those of rfsgpu_batch_fastslam_cycle_async: predict 0 / 1 runs the static step with each filter's own Q (also for a filter with
+ * n_z == 0), RFSGPU_CYCLE_NO_PREDICT runs none; a filter with n_z == 0 is neither updated nor normalised; the prune runs only from
+ * the filter's pruningMeasurementsThreshold.  z: [n_filters][RFSGPU_MAX_Z][3], n_z: [n_filters]; scan, n_scan: as
+ * rfsgpu_batch_vp_cycle_async (NULL: the scan the batch holds).  A filter's clutter term is its own expectedClutterNumber / n_z, the
+ * handle's expression.  Stream-ordered, nothing is read back: errors arrive through the shared error word, with the lowest filter
+ * that exceeded gm_capacity named.  RFSGPU_ERR_INVALID: the argument errors of the other batch cycles.  RFSGPU_ERR_UNSUPPORTED with
+ * the state untouched: any other kind of handle, a batch of Victoria Park filters whose switch is off included.
+ * rfsgpu_last_step_variant after it: {2, 0, particles per workgroup of the associate kernel (2, or 1 where two do not fit in LDS),
+ * 1}; rfsgpu_batch_last_cycle_lds: the bytes of LDS of a workgroup of that kernel. */
+int rfsgpu_batch_vp_fastslam_cycle_async(rfsgpu_filter *f, int predict, const double *x, const double *x_cov, int cov_stride,
+                                         const double *z, const int *n_z, const double *scan, int n_scan, int normalize);
 /* {sum w, sum w^2} of each filter's current weights: out [n_filters][2].  Synchronising. */
 int rfsgpu_batch_weight_sums(rfsgpu_filter *f, double *out);
 /* Resample the filters with resampled[b] != 0: slot k takes slot src_slot[k] (global slots; a source lies in k's own block and keeps

@@ -174,6 +174,7 @@ ABI_SYMBOLS = [
     "handle_serve_estimates", "batch_vp_serve_estimates",
     "batch_configure_vp", "batch_vp_cycle_async",
     "batch_vp_set_motion", "batch_vp_set_resampling", "batch_vp_propagate_run_async", "batch_vp_resample_async", "batch_vp_last_resample", "batch_vp_loop_counts",
+    "batch_vp_serve_fastslam", "batch_vp_fastslam_cycle_async",
 ]
 
 _dp = np.ctypeslib.ndpointer(dtype=np.float64, flags="C_CONTIGUOUS")
@@ -1189,7 +1190,7 @@ class CVPBatch(CBatch):
         self._call("batch_configure_vp", C.c_int(int(b)), C.c_void_p(None) if cfg is None else C.byref(cfg), C.c_void_p(None) if m is None else C.byref(m),
                    C.c_void_p(None) if k is None else C.byref(k), C.c_void_p(None) if q is None else self._ptr(q))
 
-    def batch_vp_cycle_async(self, predict, Zs, poses=None, pose_cov=None, scan=None, normalize=True):
+    def batch_vp_cycle_async(self, predict, Zs, poses=None, pose_cov=None, scan=None, normalize=True, name="batch_vp_cycle_async"):
         """rfsgpu_batch_vp_cycle_async: Zs = one measurement array per filter ([n_z, 3], possibly empty); predict None / False / True as
         rfsgpu_cycle_async; scan: the laser scan that goes with the sets (None: the one the handle holds)."""
         assert len(Zs) == self.n_filters
@@ -1199,10 +1200,25 @@ class CVPBatch(CBatch):
             Z = _f64(Z).reshape(-1, 3) if np.size(Z) else np.zeros((0, 3))
             nz[b] = Z.shape[0]
             z[b, : min(Z.shape[0], MAX_Z)] = Z[:MAX_Z]
-        self.batch_vp_cycle_async_packed(predict, z, nz, poses=poses, pose_cov=pose_cov, scan=scan, normalize=normalize)
+        self.batch_vp_cycle_async_packed(predict, z, nz, poses=poses, pose_cov=pose_cov, scan=scan, normalize=normalize, name=name)
 
-    def batch_vp_cycle_async_packed(self, predict, z, nz, poses=None, pose_cov=None, scan=None, normalize=True):
-        """The same with the sets already in the call's layout (z [n_filters, MAX_Z, 3] float64, nz [n_filters] int32, C-contiguous)."""
+    # -- a batch of Victoria Park FastSLAM filters (rfsgpu_batch_vp_serve_fastslam) ---------------------------------------------
+    def batch_vp_serve_fastslam(self, on=True):
+        """rfsgpu_batch_vp_serve_fastslam: the batch steps single-hypothesis FastSLAM filters from here on (batch_set_fastslam_config,
+        batch_vp_fastslam_cycle_async); refused once a cycle of the other kind has run."""
+        self._call("batch_vp_serve_fastslam", C.c_int(1 if on else 0))
+
+    def batch_vp_fastslam_cycle_async(self, predict, Zs, poses=None, pose_cov=None, scan=None, normalize=True):
+        """rfsgpu_batch_vp_fastslam_cycle_async: the arguments of batch_vp_cycle_async; predict None (RFSGPU_CYCLE_NO_PREDICT) or
+        False / True (the static landmark step with each filter's own Q; FastSLAM has no births)."""
+        self.batch_vp_cycle_async(predict, Zs, poses=poses, pose_cov=pose_cov, scan=scan, normalize=normalize, name="batch_vp_fastslam_cycle_async")
+
+    def batch_vp_fastslam_cycle_async_packed(self, predict, z, nz, poses=None, pose_cov=None, scan=None, normalize=True):
+        self.batch_vp_cycle_async_packed(predict, z, nz, poses=poses, pose_cov=pose_cov, scan=scan, normalize=normalize, name="batch_vp_fastslam_cycle_async")
+
+    def batch_vp_cycle_async_packed(self, predict, z, nz, poses=None, pose_cov=None, scan=None, normalize=True, name="batch_vp_cycle_async"):
+        """The same with the sets already in the call's layout (z [n_filters, MAX_Z, 3] float64, nz [n_filters] int32, C-contiguous).
+        name: the cycle call (rfsgpu_batch_vp_fastslam_cycle_async has the same argument list)."""
         assert z.dtype == np.float64 and nz.dtype == np.int32 and z.shape == (self.n_filters, MAX_Z, 3) and z.flags.c_contiguous and nz.flags.c_contiguous
         x = None if poses is None else _f64(poses, (self.n, 3))
         stride = 0
@@ -1212,7 +1228,7 @@ class CVPBatch(CBatch):
             assert cv.size in (9, 9 * self.n)
             stride = 0 if cv.size == 9 else 9
         s = None if scan is None else _f64(scan).reshape(-1)
-        self._call("batch_vp_cycle_async", C.c_int(-1 if predict is None else (1 if predict else 0)), C.c_void_p(None) if x is None else self._ptr(x),
+        self._call(name, C.c_int(-1 if predict is None else (1 if predict else 0)), C.c_void_p(None) if x is None else self._ptr(x),
                    C.c_void_p(None) if cv is None else self._ptr(cv), C.c_int(stride), self._ptr(z), self._ptr(nz),
                    C.c_void_p(None) if s is None else self._ptr(s), C.c_int(0 if s is None else s.size), C.c_int(1 if normalize else 0))
 

@@ -48,7 +48,7 @@ struct FsBatchFilter {
 struct FsBatchArg {
   const FsBatchFilter *filt;   // [nF]
   const Params *params;        // [nF]
-  const double *z;             // this cycle's sets, packed (2 doubles per measurement)
+  const double *z;             // this cycle's sets, packed (2 doubles per measurement; 3 on a batch of Victoria Park filters)
   int *errFilter;              // [1] lowest filter that ran out of gm_capacity (INT_MAX: none)
   int nPer;
   int predict;                 // FastSLAM::predict's static landmark step runs at the head of the associate kernel
@@ -262,8 +262,9 @@ __device__ __forceinline__ double fs_existence_step(const FsParams &F, double w,
 
 // LDS of the BATCH form: the single filter's layout, then one measurement set per wave (two waves of a workgroup may belong to
 // different filters)
-__host__ __device__ inline size_t fs_batch_lds_bytes(int cap, int wpb) {
-  return (size_t)(3 * RFSGPU_MAX_Z * 8) + (size_t)wpb * fs_lds_bytes_per_wave(cap) + (size_t)wpb * (2 * RFSGPU_MAX_Z * 8);
+// (D doubles per measurement: 2 range-bearing, 3 Victoria Park)
+__host__ __device__ inline size_t fs_batch_lds_bytes(int cap, int wpb, int D) {
+  return (size_t)(3 * RFSGPU_MAX_Z * 8) + (size_t)wpb * fs_lds_bytes_per_wave(cap) + (size_t)wpb * ((size_t)D * RFSGPU_MAX_Z * 8);
 }
 // The kernel's body, shared by the single filter's kernel and the batch's: BATCH reads the wave's filter from the tables of A (Parg,
 // Farg and nZarg are ignored), runs the static landmark step of FastSLAM::predict at its head when asked, and stops there for a
@@ -289,9 +290,19 @@ __device__ __forceinline__ void fs_associate_update_body(const Buffers &B, const
     nZ = __builtin_amdgcn_readfirstlane(A.filt[bf].nZ);
     // FastSLAM::predict (:376-383): Sigma += Q on every landmark, no births; also for a filter whose scan is empty.  The lane that
     // adds Q to an entry is the lane that reads it below (entry m belongs to lane m & 63 in both loops).
-    if (A.predict) predict_map_particle<64>(B, P, cur, i, lane, false, 0, B.pose, true);
+    if (A.predict) {
+      if constexpr (D == 2) {
+        predict_map_particle<64>(B, P, cur, i, lane, false, 0, B.pose, true);
+      } else {   // the static step of predict_map_general_kernel<3, .> (birth.h): plane by plane, entry m on lane m & 63
+        const int nOld = B.count[i];
+        for (int t = 0; t < 6; t++) {
+          double *p = plane3(B.slab[cur], cap, i, P3_SXX + t);
+          for (int m = lane; m < nOld; m += 64) p[m] += P.Qlm6[t];
+        }
+      }
+    }
     if (nZ == 0) return;
-    sZ = reinterpret_cast<double *>(smem_raw + 3 * RFSGPU_MAX_Z * 8 + (size_t)WPB * fs_lds_bytes_per_wave(cap)) + (size_t)wave * (2 * RFSGPU_MAX_Z);
+    sZ = reinterpret_cast<double *>(smem_raw + 3 * RFSGPU_MAX_Z * 8 + (size_t)WPB * fs_lds_bytes_per_wave(cap)) + (size_t)wave * (D * RFSGPU_MAX_Z);
     const double *zs = A.z + A.filt[bf].zOff;
     for (int t = lane; t < D * nZ; t += 64) sZ[t] = zs[t];
     wave_sync();
@@ -555,12 +566,15 @@ __global__ __launch_bounds__(64) void fs_associate_update_live_kernel(Buffers B,
   if (live_beyond(live, (int)blockIdx.x)) return;     // (workgroup-uniform)
   fs_associate_update_body<1, D, false>(B, P, F, cur, nZ, arena, smem_raw, sPdScratch, FsBatchArg{});
 }
-// The batch's form (2-D only): launched over all slots of the batch, LDS fs_batch_lds_bytes(cap, WPB).
-template <int WPB>
+// The batch's form: launched over all slots of the batch, LDS fs_batch_lds_bytes(cap, WPB, D).  D == 3 (a batch of Victoria Park
+// filters): every wave has its own Pd scratch, its filter's Pd table, clutter and noise come from A.params[filter], the laser scan is
+// the one the handle holds (B.scan: the filters share the vehicle's scan).  Waves of one workgroup may belong to different filters:
+// nothing staged per workgroup depends on the filter, and the body has no workgroup barrier behind a wave's early exit.
+template <int WPB, int D>
 __global__ __launch_bounds__(WPB * 64) void fs_associate_update_batch_kernel(Buffers B, int cur, unsigned char *arena, FsBatchArg A) {
   extern __shared__ __align__(16) unsigned char smem_raw[];
-  __shared__ __align__(16) unsigned char sPdScratch[WPB][16];
-  fs_associate_update_body<WPB, 2, true>(B, A.params[0], A.filt[0].F, cur, 0, arena, smem_raw, sPdScratch[threadIdx.x >> 6], A);
+  __shared__ __align__(16) unsigned char sPdScratch[WPB][(D == 3) ? ((VP_PD_SCRATCH_BYTES + 15) & ~15) : 16];
+  fs_associate_update_body<WPB, D, true>(B, A.params[0], A.filt[0].F, cur, 0, arena, smem_raw, sPdScratch[threadIdx.x >> 6], A);
 }
 // Each filter's weights after its update: {sum w, sum w^2} and the division by the sum, in the order of rfsgpu_batch_weight_sums and of
 // the RB-PHD batch's post kernel (step_post_tail).  A filter without measurements keeps its weights (no normalisation, :402-403).

@@ -274,6 +274,8 @@ struct rfsgpu_filter {
   // a batch of FastSLAM filters (rfsgpu_batch_fastslam_cycle_async; fastslam.h FsBatchArg)
   int bKind = 0;                               // what the batch steps: 0 not decided yet, 1 RB-PHD filters, 2 FastSLAM filters (the first cycle call decides), 3 multi-hypothesis FastSLAM filters (rfsgpu_create_batch_mh decides)
   std::vector<rfsgpu_fastslam_config> bFs;     // [nF]
+  bool bVpFastSlam = false;                    // rfsgpu_batch_vp_serve_fastslam: this batch of Victoria Park filters steps FastSLAM filters (bKind 2)
+  bool bVpRbphdRan = false, bVpFsRan = false;  // a cycle of either kind has run on a batch of Victoria Park filters: the switch no longer moves
   std::vector<Params> bParamsHost;             // [nF] the device Params table as last written (each filter's pfa comes from its own model)
   FsBatchFilter *dFsFilt = nullptr;            // [nF]
   // a batch of multi-hypothesis FastSLAM filters (rfsgpu_create_batch_mh; fastslam_cycle.h): nPer is the stride max_per_filter, every
@@ -1941,6 +1943,8 @@ static void launch_predict_kernels(rfsgpu_filter *f, int add_birth, const BirthL
 // what a resampling copy / a migration row carries: pose + mixture only (RBPHDFilter: the per-slot birth state is copied
 // lazily by the next predict, or by the host), or the birth bookkeeping as well (RFSGPU_INHERIT_EAGER, and FastSLAM handles)
 static int map_only(const rfsgpu_filter *f) { return (f->inheritMode != RFSGPU_INHERIT_EAGER && !f->fastSlamHandle) ? 1 : 0; }
+// ... of a batch: the lists travel where the batch keeps landmark candidates (Victoria Park FastSLAM filters, as on a FastSLAM handle)
+static int batch_map_only(const rfsgpu_filter *f) { return f->bVpFastSlam ? 0 : 1; }
 static void ensure_ids(rfsgpu_filter *f) {
   while ((int)f->pid.size() < f->Ncap) { f->pid.push_back((int)f->pid.size()); f->ppid.push_back((int)f->ppid.size()); }
 }
@@ -3584,7 +3588,8 @@ static int batch_sensed_records(rfsgpu_filter *f, Rec *dRec, unsigned long long 
   return RFSGPU_OK;
 }
 static int batch_cycle_core(rfsgpu_filter *f, int predict, const double *x, const double *x_cov, int cov_stride, const double *z, const int *n_z, int normalize);
-static int batch_fs_cycle_core(rfsgpu_filter *f, int predict, const double *x, const double *x_cov, int cov_stride, const double *z, const int *n_z, int normalize);
+static int batch_fs_cycle_core(rfsgpu_filter *f, int predict, const double *x, const double *x_cov, int cov_stride, const double *z, const int *n_z, int normalize,
+                               const double *scan = nullptr, int n_scan = 0);
 static int batch_mh_cycle_core(rfsgpu_filter *f, int predict, const double *x, const double *x_cov, int cov_stride, const double *z, const int *n_z, const double *u01,
                                unsigned long long call);
 static int batch_push_motion(rfsgpu_filter *f);
@@ -4021,6 +4026,9 @@ int rfsgpu_batch_vp_cycle_async(rfsgpu_filter *f, int predict, const double *x, 
     if ((rc = batch_check_filter(f, BATCH_VP_CYCLE, b, z, n_z)) != RFSGPU_OK) return rc;
   if (scan && (n_scan < 2 || n_scan > RFSGPU_VP_MAX_SCAN)) return batch_fail(f, BATCH_VP_CYCLE, "laser scan size out of range (2 ... RFSGPU_VP_MAX_SCAN beams)");
   if (!scan && f->B.nScan < 2) return batch_fail(f, BATCH_VP_CYCLE, "the batch has not been given a laser scan (rfsgpu_set_laser_scan, or this call's scan)");
+  if (f->bVpFastSlam)
+    return fail(f, RFSGPU_ERR_UNSUPPORTED, "batch_vp_cycle: this batch steps FastSLAM filters (rfsgpu_batch_vp_serve_fastslam is on; its cycle is rfsgpu_batch_vp_fastslam_cycle_async): a batch is of one kind");
+  f->bVpRbphdRan = true;
   return batch_vp_cycle_core(f, predict, x, x_cov, cov_stride, z, n_z, scan, n_scan, normalize);
 }
 
@@ -4031,7 +4039,7 @@ int rfsgpu_batch_set_fastslam_config(rfsgpu_filter *f, int filter, const rfsgpu_
   CHECK_HANDLE(f);
   int rc = batch_check(f, filter);
   if (rc != RFSGPU_OK) return rc;
-  REFUSE_ON_VP_BATCH(f, "rfsgpu_batch_set_fastslam_config");
+  if (!f->bVpFastSlam) { REFUSE_ON_VP_BATCH(f, "rfsgpu_batch_set_fastslam_config"); }     // (rfsgpu_batch_vp_serve_fastslam switches it on)
   if (!cfg) return fail(f, RFSGPU_ERR_INVALID, "batch_set_fastslam_config: null configuration");
   const std::string who = filter < 0 ? std::string("every filter") : "filter " + std::to_string(filter);
   if (f->mhBatch) {
@@ -4043,7 +4051,8 @@ int rfsgpu_batch_set_fastslam_config(rfsgpu_filter *f, int filter, const rfsgpu_
     f->err = "batch_set_fastslam_config: " + who + ": maxNDataAssocHypotheses must be 1 on a filter batch (the multi-hypothesis update grows the particle set)";
     return RFSGPU_ERR_UNSUPPORTED;
   }
-  if (cfg->landmarkCandidateMeasurementCountThreshold != 1u) {
+  // (a batch of Victoria Park FastSLAM filters keeps candidate lists: both of its resampling routes move them with the particle)
+  if (cfg->landmarkCandidateMeasurementCountThreshold != 1u && !f->bVpFastSlam) {
     f->err = "batch_set_fastslam_config: " + who + ": landmarkCandidateMeasurementCountThreshold must be 1 on a filter batch (landmark candidate lists would have to travel with a resampling)";
     return RFSGPU_ERR_UNSUPPORTED;
   }
@@ -4072,44 +4081,120 @@ int rfsgpu_batch_fastslam_cycle_async(rfsgpu_filter *f, int predict, const doubl
   f->bKind = 2;
   return batch_fs_cycle_core(f, predict, x, x_cov, cov_stride, z, n_z, normalize);
 }
+// ---- ... of Victoria Park filters: the switch that makes a batch created with RFSGPU_MODEL_VICTORIAPARK_3D a batch of FastSLAM filters,
+// and its cycle (the D = 3 forms of the chain above; the scan as in rfsgpu_batch_vp_cycle_async).  Off at creation, so every refusal such
+// a batch was published with stands until a caller asks.
+static const BatchCall BATCH_VP_FS_CYCLE{"batch_vp_fastslam_cycle", -1, "RFSGPU_CYCLE_NO_PREDICT (-1), or 0 / 1 (the static landmark step; FastSLAM has no births)", "null measurement counts"};
+int rfsgpu_batch_vp_serve_fastslam(rfsgpu_filter *f, int on) {
+  CHECK_HANDLE(f);
+  if (!f->batch || f->D != 3 || f->mhBatch) {
+    f->err = std::string("batch_vp_serve_fastslam: the switch is for a batch of Victoria Park filters (rfsgpu_create_batch with RFSGPU_MODEL_VICTORIAPARK_3D), not ") +
+             (f->batch ? (f->mhBatch ? "a batch of multi-hypothesis FastSLAM filters (rfsgpu_create_batch_mh)" : "a 2-D batch (rfsgpu_batch_set_fastslam_config makes it a FastSLAM batch)")
+                       : (f->groupShard ? "a shard of an rfsgpu_group" : "an ordinary handle (rfsgpu_set_fastslam_config, rfsgpu_fastslam_update)"));
+    return RFSGPU_ERR_UNSUPPORTED;
+  }
+  if (on && f->bVpRbphdRan)
+    return fail(f, RFSGPU_ERR_UNSUPPORTED, "batch_vp_serve_fastslam: this batch steps RB-PHD filters (rfsgpu_batch_vp_cycle_async has run): a batch is of one kind");
+  if (on && f->estServeVpBatch)
+    return fail(f, RFSGPU_ERR_UNSUPPORTED, "batch_vp_serve_fastslam: this batch serves the [estimate] log of RB-PHD filters (rfsgpu_batch_vp_serve_estimates is on): switch that off first");
+  if (!on && f->bVpFsRan)
+    return fail(f, RFSGPU_ERR_UNSUPPORTED, "batch_vp_serve_fastslam: this batch steps FastSLAM filters (rfsgpu_batch_vp_fastslam_cycle_async has run): a batch is of one kind");
+  f->bVpFastSlam = on != 0;
+  f->bKind = on ? 2 : 1;     // (2: the device route's gates are the FastSLAM configuration's, batch_resample_core)
+  return RFSGPU_OK;
+}
+int rfsgpu_batch_vp_fastslam_cycle_async(rfsgpu_filter *f, int predict, const double *x, const double *x_cov, int cov_stride, const double *z, const int *n_z,
+                                         const double *scan, int n_scan, int normalize) {
+  CHECK_HANDLE(f);
+  if (!f->batch || f->D != 3 || !f->bVpFastSlam) {
+    f->err = std::string("batch_vp_fastslam_cycle: the call serves a batch of Victoria Park FastSLAM filters (rfsgpu_create_batch with RFSGPU_MODEL_VICTORIAPARK_3D, then rfsgpu_batch_vp_serve_fastslam), not ") +
+             (f->batch ? (f->D == 3 ? "a batch of Victoria Park filters whose switch is off (it steps RB-PHD filters: rfsgpu_batch_vp_cycle_async)"
+                                    : (f->mhBatch ? "a batch of multi-hypothesis FastSLAM filters (rfsgpu_batch_fastslam_mh_cycle_async)" : "a 2-D batch (rfsgpu_batch_fastslam_cycle_async)"))
+                       : (f->groupShard ? "a shard of an rfsgpu_group" : "an ordinary handle (rfsgpu_fastslam_update)"));
+    return RFSGPU_ERR_UNSUPPORTED;
+  }
+  int rc = RFSGPU_OK;
+  if ((rc = batch_check_call(f, BATCH_VP_FS_CYCLE, predict, x_cov, cov_stride, n_z)) != RFSGPU_OK) return rc;
+  for (int b = 0; b < f->nF; b++)
+    if ((rc = batch_check_filter(f, BATCH_VP_FS_CYCLE, b, z, n_z)) != RFSGPU_OK) return rc;
+  if (scan && (n_scan < 2 || n_scan > RFSGPU_VP_MAX_SCAN)) return batch_fail(f, BATCH_VP_FS_CYCLE, "laser scan size out of range (2 ... RFSGPU_VP_MAX_SCAN beams)");
+  if (!scan && f->B.nScan < 2) return batch_fail(f, BATCH_VP_FS_CYCLE, "the batch has not been given a laser scan (rfsgpu_set_laser_scan, or this call's scan)");
+  f->bVpFsRan = true;
+  return batch_fs_cycle_core(f, predict, x, x_cov, cov_stride, z, n_z, normalize, scan, n_scan);
+}
 // The cycle behind rfsgpu_batch_fastslam_cycle_async (n_z given: the host's sets and records go to the device first) and
 // rfsgpu_batch_fastslam_cycle_sensed_async (n_z null: the sets are where the last rfsgpu_batch_sense_async left them, the records are
 // made from that call's on the device).  The arguments have been checked.
-static int batch_fs_cycle_core(rfsgpu_filter *f, int predict, const double *x, const double *x_cov, int cov_stride, const double *z, const int *n_z, int normalize) {
+// A batch of Victoria Park filters (rfsgpu_batch_vp_fastslam_cycle_async; never sensed): the D = 3 forms of the same chain; scan, when
+// given, becomes the scan the batch holds, as in batch_vp_cycle_core.
+static int batch_fs_cycle_core(rfsgpu_filter *f, int predict, const double *x, const double *x_cov, int cov_stride, const double *z, const int *n_z, int normalize,
+                               const double *scan, int n_scan) {
   const bool sensed = n_z == nullptr;
-  const int nF = f->nF;
+  const int nF = f->nF, D = f->D;
   int rc = RFSGPU_OK;
   hipSetDevice(f->device);
   long long t0 = now_ns();
   if (!f->fsArena) HIPCHK(hipMalloc(&f->fsArena, (size_t)f->Ncap * fs_arena_bytes()));   // the Hungarian scratch of every slot of the batch, once
   batch_handle_wide(f, x, x_cov, cov_stride);
+  if (scan) {     // every filter's clutter density on the host (it travels in the Params table), the beams by copy command below
+    double area = 0;
+    for (int q = 1; q < n_scan; q++) area += scan[q] * scan[q - 1];
+    area += scan[0] * scan[n_scan - 1];
+    area *= sin(acos(-1) / 360) / 2;
+    f->vpClutter = f->vp.expectedClutterNumber / area;
+    batch_scan_clutter(f, area);
+  }
   if (sensed) rc = batch_sensed_records(f, f->dFsFilt, 0ull, [&](FsBatchFilter &T, int b) {
     T.F = fs_params_of(f->bFs[b], f->bParamsHost[b], 2, 1);
     T.pruneT = f->bFs[b].mapExistencePruneThreshold;
   });
   else rc = batch_push_tables(f, f->dFsFilt, z, n_z, nullptr, 0, nullptr, [&](FsBatchFilter &T, int b) {
-    T.F = fs_params_of(f->bFs[b], f->bParamsHost[b], 2, n_z[b]);
+    T.F = fs_params_of(f->bFs[b], f->bParamsHost[b], D, n_z[b]);
     T.pruneT = f->bFs[b].mapExistencePruneThreshold;
     T.prune = ((unsigned)n_z[b] >= f->bFs[b].pruningMeasurementsThreshold) ? 1 : 0;
   });
   if (rc != RFSGPU_OK) return rc;
-  if (x && (rc = batch_push_poses(f, x, x_cov, cov_stride)) != RFSGPU_OK) return rc;
+  if (scan) {     // the host's new poses and the scan through one block of the staging ring (batch_vp_cycle_core's layout)
+    double *h = nullptr;
+    int ks = 0;
+    if ((rc = ring_acquire(f, f->stage, &h, &ks)) != RFSGPU_OK) return rc;
+    if (x && (rc = push_poses(f, h, f->B.pose, x, x_cov, cov_stride)) != RFSGPU_OK) return rc;
+    double *hs = h + (size_t)f->Ncap * 22;
+    memcpy(hs, scan, (size_t)n_scan * sizeof(double));
+    HIPCHK(hipMemcpyAsync(f->B.scan, hs, (size_t)n_scan * sizeof(double), hipMemcpyHostToDevice, f->stream));
+    f->B.nScan = n_scan;
+    HIPCHK(hipEventRecord(f->stage.ev[ks], f->stream));
+  } else if (x && (rc = batch_push_poses(f, x, x_cov, cov_stride)) != RFSGPU_OK) return rc;
   f->bBirthAlt = false;      // (no births here: the poses from before a propagation are not needed)
   FsBatchArg A{f->dFsFilt, f->dBParams, f->dBZ, f->dBErrFilter, f->nPer, predict >= 0 ? 1 : 0};
-  const size_t b2 = fs_batch_lds_bytes(f->cap, 2), b1 = fs_batch_lds_bytes(f->cap, 1);
-  if (b2 <= 64 * 1024) {      // (the single handle's rule)
-    if ((rc = set_lds(f, (fs_associate_update_batch_kernel<2>), b2)) != RFSGPU_OK) return rc;
-    fs_associate_update_batch_kernel<2><<<(f->N + 1) / 2, 128, b2, f->stream>>>(f->B, f->cur, f->fsArena, A);
+  const size_t b2 = fs_batch_lds_bytes(f->cap, 2, D), b1 = fs_batch_lds_bytes(f->cap, 1, D);
+  if (D == 3) {
+    // two particles per workgroup where both waves' areas and Pd scratch fit the same 64 KiB, else one
+    const size_t pdB = (VP_PD_SCRATCH_BYTES + 15) & ~(size_t)15;
+    const int wpb = b2 + 2 * pdB <= 64 * 1024 ? 2 : 1;
+    f->lastStepVariant[0] = 2; f->lastStepVariant[1] = 0; f->lastStepVariant[2] = wpb; f->lastStepVariant[3] = 1;
+    f->bLastCycleLds = (long long)(wpb == 2 ? b2 + 2 * pdB : b1 + pdB);
+    if (wpb == 2) {
+      if ((rc = set_lds(f, (fs_associate_update_batch_kernel<2, 3>), b2)) != RFSGPU_OK) return rc;
+      fs_associate_update_batch_kernel<2, 3><<<(f->N + 1) / 2, 128, b2, f->stream>>>(f->B, f->cur, f->fsArena, A);
+    } else {
+      if ((rc = set_lds(f, (fs_associate_update_batch_kernel<1, 3>), b1)) != RFSGPU_OK) return rc;
+      fs_associate_update_batch_kernel<1, 3><<<f->N, 64, b1, f->stream>>>(f->B, f->cur, f->fsArena, A);
+    }
+  } else if (b2 <= 64 * 1024) {      // (the single handle's rule)
+    if ((rc = set_lds(f, (fs_associate_update_batch_kernel<2, 2>), b2)) != RFSGPU_OK) return rc;
+    fs_associate_update_batch_kernel<2, 2><<<(f->N + 1) / 2, 128, b2, f->stream>>>(f->B, f->cur, f->fsArena, A);
   } else {
-    if ((rc = set_lds(f, (fs_associate_update_batch_kernel<1>), b1)) != RFSGPU_OK) return rc;
-    fs_associate_update_batch_kernel<1><<<f->N, 64, b1, f->stream>>>(f->B, f->cur, f->fsArena, A);
+    if ((rc = set_lds(f, (fs_associate_update_batch_kernel<1, 2>), b1)) != RFSGPU_OK) return rc;
+    fs_associate_update_batch_kernel<1, 2><<<f->N, 64, b1, f->stream>>>(f->B, f->cur, f->fsArena, A);
   }
   HIPCHK(hipGetLastError());
   const size_t pb = gm_prune_lds_bytes_per_wave(f->cap);
   if ((rc = set_lds(f, (gm_prune_kernel<4, false, true, FsBatchArg>), 4 * pb)) != RFSGPU_OK) return rc;
   gm_prune_kernel<4, false, true, FsBatchArg><<<(f->N + 3) / 4, 256, 4 * pb, f->stream>>>(f->B, f->P, f->cur, f->cur ^ 1, A);
   f->cur ^= 1;     // (filters that do not prune this cycle had their mixtures moved to the new slab)
-  fs_new_landmarks_kernel<2, true, FsBatchArg><<<(f->N + FS_NEWLM_WPB - 1) / FS_NEWLM_WPB, 64 * FS_NEWLM_WPB, 0, f->stream>>>(f->B, f->P, FsParams{}, f->cur, 0, A);
+  if (D == 3) fs_new_landmarks_kernel<3, true, FsBatchArg><<<(f->N + FS_NEWLM_WPB - 1) / FS_NEWLM_WPB, 64 * FS_NEWLM_WPB, 0, f->stream>>>(f->B, f->P, FsParams{}, f->cur, 0, A);
+  else fs_new_landmarks_kernel<2, true, FsBatchArg><<<(f->N + FS_NEWLM_WPB - 1) / FS_NEWLM_WPB, 64 * FS_NEWLM_WPB, 0, f->stream>>>(f->B, f->P, FsParams{}, f->cur, 0, A);
   fs_batch_post_kernel<<<nF, 256, 0, f->stream>>>(f->B.weight, A, f->dBSums, normalize, f->bDevRoute ? f->BL.resampled : nullptr);
   HIPCHK(hipGetLastError());
   if (!sensed)
@@ -4410,7 +4495,7 @@ int rfsgpu_batch_resample_apply(rfsgpu_filter *f, const int *src_slot, const uns
     }
     if (resampled[b]) f->bResampled[b] = 1;
   }
-  resample_gather_kernel<<<f->N, 256, 0, f->stream>>>(f->B, f->cur, hsrc, f->P.poseCovStride, 1);
+  resample_gather_kernel<<<f->N, 256, 0, f->stream>>>(f->B, f->cur, hsrc, f->P.poseCovStride, batch_map_only(f));
   batch_reset_weights_kernel<<<(f->N + 255) / 256, 256, 0, f->stream>>>(f->B.weight, f->N, nPer, hflag);
   HIPCHK(hipGetLastError());
   HIPCHK(hipEventRecord(f->stage.ev[ks], f->stream));
@@ -4605,7 +4690,7 @@ static int batch_resample_core(rfsgpu_filter *f, const BatchCall &C, const int *
     HIPCHK(hipEventRecord(f->bLoop.ev[k], f->stream));
   }
   batch_resample_kernel<<<nF, BATCH_LOOP_THREADS, 0, f->stream>>>(f->B.weight, f->BL, f->dBMotion, f->dBResIn, f->nPer, call, n_z ? nullptr : f->dBFilt);
-  resample_gather_kernel<<<f->N, 256, 0, f->stream>>>(f->B, f->cur, f->BL.plan, f->P.poseCovStride, 1);
+  resample_gather_kernel<<<f->N, 256, 0, f->stream>>>(f->B, f->cur, f->BL.plan, f->P.poseCovStride, batch_map_only(f));
   HIPCHK(hipGetLastError());
   const long long dtn = now_ns() - t0;
   f->timing.particleResample_wall += dtn;
@@ -4791,6 +4876,7 @@ static int sensor_check(rfsgpu_filter *f, const BatchCall &C) {
 // The switch of a FastSLAM or multi-hypothesis batch: off at creation (rfsgpu_batch_mh_serve_metrics is the precedent).
 int rfsgpu_batch_fastslam_serve_sensor(rfsgpu_filter *f, int on) {
   CHECK_HANDLE(f);
+  if (f->batch && f->D == 3) return fail(f, RFSGPU_ERR_UNSUPPORTED, "batch_fastslam_serve_sensor: the device sensor is a 2-D range-bearing sensor: it does not serve a batch of Victoria Park filters");
   const char *why = !f->batch ? (f->groupShard ? "a shard of an rfsgpu_group" : "an ordinary handle")
                               : (f->mhBatch || f->bKind == 2 ? nullptr : (f->bKind == 1 ? "a batch of RB-PHD filters (the [sensor] calls serve it as it is)"
                                                                                          : "a batch whose kind is not decided yet (rfsgpu_batch_set_fastslam_config decides it)"));
@@ -5310,6 +5396,8 @@ int rfsgpu_batch_vp_serve_estimates(rfsgpu_filter *f, int on) {
                                         : "an ordinary handle (rfsgpu_handle_serve_estimates)"));
     return RFSGPU_ERR_UNSUPPORTED;
   }
+  if (f->bVpFastSlam)
+    return fail(f, RFSGPU_ERR_UNSUPPORTED, "batch_vp_serve_estimates: this batch steps FastSLAM filters (rfsgpu_batch_vp_serve_fastslam): the [estimate] log does not serve it");
   hipSetDevice(f->device);
   HIPCHK(hipStreamSynchronize(f->stream));
   if (!on) estimate_log_free(f);

@@ -620,6 +620,34 @@ class VPFilterBatch(capi.CVPBatch):
     update_and_resample = FilterBatch.update_and_resample
 
 
+class VPFastSLAMBatch(VPFilterBatch):
+    """n_filters independent Victoria Park single-hypothesis FastSLAM filters stepped together (rfsgpu_batch_vp_serve_fastslam,
+    rfsgpu_batch_vp_fastslam_cycle_async): per cycle the static landmark step, the association / Kalman update / weights, the existence
+    prune, the new landmarks and candidates and each filter's normalisation, one launch chain for all filters.  Each filter equals a
+    separate Victoria Park FastSLAM handle given the same inputs; landmark candidate lists of any count threshold are kept, and both
+    resampling routes (update_and_resample; resample_async) move them with the particle.  The model / Kalman filter / landmark noise
+    of a filter come through configure(b, None, model=..., ...), the FastSLAM configuration through configure_fastslam(b, fs_cfg),
+    whose two gates also decide the resampling."""
+
+    def __init__(self, n_filters, n_per_filter, device_id=0, gm_capacity=512):
+        super().__init__(n_filters, n_per_filter, device_id=device_id, gm_capacity=gm_capacity)
+        self.batch_vp_serve_fastslam(True)
+        self.fs_configs = [self.default_fastslam_config() for _ in range(n_filters)]
+
+    def configure_fastslam(self, b, fs_cfg):
+        """Filter b's (None: every filter's) FastSlamConfig (rfsgpu_batch_set_fastslam_config; refused for more than one hypothesis)."""
+        self.batch_set_fastslam_config(b, fs_cfg)
+        for q in (range(self.n_filters) if b is None else [b]):
+            self.fs_configs[q] = fs_cfg
+
+    def cycle_async(self, predict, Zs, poses=None, pose_cov=None, scan=None, normalize=True):
+        """One predict (static landmark step; None: none) + FastSLAM update cycle of every filter."""
+        self.batch_vp_fastslam_cycle_async(predict, Zs, poses=poses, pose_cov=pose_cov, scan=scan, normalize=normalize)
+
+    def _gate_config(self, b):
+        return self.fs_configs[b]
+
+
 class FastSLAMBatch(FilterBatch):
     """n_filters independent 2-D single-hypothesis FastSLAM filters stepped together (rfsgpu_batch_fastslam_cycle_async): per cycle the
     static landmark step, the association / Kalman update / weights, the existence prune, the new landmarks and each filter's

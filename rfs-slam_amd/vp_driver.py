@@ -357,6 +357,13 @@ class VictoriaParkBatchRun:
     set is empty at a lidar message has its (already normalised) weights divided by their sum once more, where VictoriaParkRun leaves
     them alone (RBPHDFilter.hpp:451-452); the batch is held to the handles stepped through this class, not to VictoriaParkRun.
 
+    filter="fastslam": the loop of VictoriaParkRun(filter="fastslam") per filter -- the FastSLAM half of the sweep
+    (cfg/fastslam_VictoriaPark_artificialClutter.xml).  target: a VPFastSLAMBatch, or a list of Victoria Park FastSLAM handles.  No
+    births: every predict of a run is a static step with the dt^2-scaled landmark noise (one static_steps_async), the update cycle
+    runs with predict = None.  A filter whose set is empty is only counted (FastSLAM.hpp:399-402), on both kinds of target.  The
+    gates are params_per_filter's min_updates / min_measurements, which the constructor writes into a batch's FastSLAM
+    configurations; both resampling routes move the landmark candidate lists with the particle.  Not with log_estimates.
+
     device_loop: the run is enqueued and nothing is read until synchronize().  The artificial clutter and the measurement sets are
     still drawn on the host from seeds[b] (they depend on no device state); the poses live on the device.  Per run of messages a
     batch gets the birth cycle (no sets, at the poses the last update used), static_steps_async, one propagate_run_async (noisy = not
@@ -374,7 +381,13 @@ class VictoriaParkBatchRun:
     device_loop the rows go behind the enqueued work and nothing is read; estimates() is the one read."""
 
     def __init__(self, target, data, params_per_filter, seeds, var_uv=0.2, var_ur=0.025, noise_inflation=20.0, added_clutter=3.0, eff_n=None,
-                 keep_history=False, device_loop=False, log_estimates=False, log_particles=True, log_w_threshold=-np.inf, log_max_est=None):
+                 keep_history=False, device_loop=False, log_estimates=False, log_particles=True, log_w_threshold=-np.inf, log_max_est=None,
+                 filter="rbphd"):
+        if filter not in ("rbphd", "fastslam"):
+            raise ValueError("filter is 'rbphd' or 'fastslam'")
+        self.fastslam = filter == "fastslam"
+        if self.fastslam and log_estimates:
+            raise ValueError("the estimate log does not serve a batch of Victoria Park FastSLAM filters")
         self.batch = None if isinstance(target, (list, tuple)) else target
         self.handles = list(target) if self.batch is None else None
         self.nF = len(params_per_filter)
@@ -397,6 +410,12 @@ class VictoriaParkBatchRun:
         self.history = [] if keep_history else None
         self._dts = []                    # the intervals of the predicts not yet issued (the first of a run adds the births)
         self.device_loop = bool(device_loop)
+        if self.fastslam and self.batch is not None:      # the batch's gates (update_and_resample, resample_async) are its FastSLAM configurations'
+            for b in range(self.nF):
+                cfg = self.batch.fs_configs[b]
+                cfg.minUpdatesBeforeResample = int(self.Ps[b]["min_updates"])
+                cfg.minMeasurementsBeforeResample = int(self.Ps[b]["min_measurements"])
+                self.batch.configure_fastslam(b, cfg)
         self.seeds = [int(s) for s in seeds]
         self.var = np.array([var_uv, var_ur]) * noise_inflation
         self._run = []                    # device_loop: (uv, ur, noisy) of the predicts not yet issued
@@ -473,6 +492,12 @@ class VictoriaParkBatchRun:
         self._dts = []
         if self.device_loop:
             return self._cycle_device(q, dts, Zs)
+        if self.fastslam:
+            for f in self._targets():
+                f.static_steps_async(len(q), q)
+            if Zs is not None:
+                self._update_fastslam(Zs, self.x)
+            return
         one = len(q) == 1 and Zs is not None      # (Zs None: the predicts behind the last lidar message, no update)
         if self.batch is not None:
             f = self.batch
@@ -501,6 +526,19 @@ class VictoriaParkBatchRun:
         self._run = []
         call0 = self._n_calls
         self._n_calls += len(r)
+        if self.fastslam:
+            var = r[:, 2:3] * self.var[None, :]
+            for b, f in enumerate(self._targets()):
+                f.static_steps_async(len(q), q)
+                if self.batch is None:
+                    f.propagate_ackerman_run_async(r[:, 0:2], var, dts, self._geom, self.seeds[b], call0)
+                    continue
+                for k0 in range(0, len(r), VP_BATCH_RUN_MAX):
+                    k1 = min(len(r), k0 + VP_BATCH_RUN_MAX)
+                    f.propagate_run_async(r[k0:k1, 0:2], dts[k0:k1], call0 + k0, noisy=r[k0:k1, 2] != 0)
+            if Zs is not None:
+                self._update_fastslam(Zs, None)
+            return
         if self.batch is not None:
             f = self.batch
             f.set_lmk_process_noise(q[0])
@@ -523,6 +561,22 @@ class VictoriaParkBatchRun:
             if Zs is not None:
                 f.set_step_inputs_async(scan=self.scan)
                 f.cycle_async(None, Zs[b], poses=None, normalize=True)
+
+    def _update_fastslam(self, Zs, x):
+        """This lidar message's FastSLAM update of every filter (x None: the poses are the device's) and the normalisation of the
+        filters that had measurements: one batch cycle, or rfsgpu_fastslam_update and the division per handle."""
+        if self.batch is not None:
+            self.batch.cycle_async(None, Zs, poses=x, scan=self.scan, normalize=True)
+            return
+        for b, f in enumerate(self.handles):
+            if not len(Zs[b]):
+                continue
+            f.set_laser_scan(self.scan)
+            if x is not None:
+                f.set_poses(x[self._block(b)], None)
+            f.fastslam_update(Zs[b])
+            s = f.weight_sums()
+            f.normalize_weights(s[0])
 
     def _resample_device(self, n_z):
         """device_loop: a batch resamples on the device (nothing is read unless the history is kept); the handles' decision is made

@@ -6,6 +6,9 @@
       on): the filter batch (VPFilterBatch, rfsgpu_batch_vp_cycle_async) against the same B filters as plain handles stepped in turn,
       both through vp_driver.VictoriaParkBatchRun with the same realisations, alternating in this one invocation.  One line per
       repetition and route, then one JSON line: medians in seconds per sweep, runs (filters) per second, and the ratio.
+  python tools/vp_bench.py --batch B --fastslam [--device-loop] [...]
+      The FastSLAM half of the sweep: a VPFastSLAMBatch (rfsgpu_batch_vp_fastslam_cycle_async) against B FastSLAM handles stepped in
+      turn, through VictoriaParkBatchRun(filter="fastslam"); the routes and the JSON fields of the RB-PHD forms.
   python tools/vp_bench.py --batch B --device-loop [...]
       Three routes, alternating: the host-stop batch, the device-loop batch (VictoriaParkBatchRun(device_loop=True): propagation, the
       resampling tail and the inheritance walk on the device, nothing read until the end) and the handles in turn under the device
@@ -43,23 +46,40 @@ def batch_sweep(nF):
     return Ps, seeds, clutter
 
 
-def batch_one_run(route, nF, n, data, messages, cap, device_loop=False):
+def fastslam_sweep_config(f, P):
+    """The FastSLAM half of the sweep (cfg/fastslam_VictoriaPark_artificialClutter.xml): candidate lists with a count threshold of 4."""
+    cfg = f.default_fastslam_config()
+    cfg.landmarkCandidateMeasurementCountThreshold = 4
+    cfg.landmarkCandidateMeasurementCheckThreshold = 6
+    cfg.landmarkCandidateCurrentMeasurementCountThreshold = 0
+    cfg.landmarkCandidateMeasurementSupportDist = 3.0
+    cfg.minUpdatesBeforeResample = int(P["min_updates"])
+    cfg.minMeasurementsBeforeResample = int(P["min_measurements"])
+    return cfg
+
+
+def batch_one_run(route, nF, n, data, messages, cap, device_loop=False, fastslam=False):
     Ps, seeds, clutter = batch_sweep(nF)
     if route in ("batch", "batch_dev"):
-        target = pkg.VPFilterBatch(nF, n, gm_capacity=cap)
+        target = (pkg.VPFastSLAMBatch if fastslam else pkg.VPFilterBatch)(nF, n, gm_capacity=cap)
         for b in range(nF):
             sc.apply_vp_batch_params(target, b, Ps[b])
+            if fastslam:
+                target.configure_fastslam(b, fastslam_sweep_config(target, Ps[b]))
         target.synchronize()
         owned = [target]
     else:
-        target = [pkg.RBPHDFilter(n, gm_capacity=cap, model=pkg.capi.MODEL_VICTORIAPARK_3D) for _ in range(nF)]
+        target = [(pkg.FastSLAM if fastslam else pkg.RBPHDFilter)(n, gm_capacity=cap, model=pkg.capi.MODEL_VICTORIAPARK_3D) for _ in range(nF)]
         for b, h in enumerate(target):
             sc.apply_vp_params(h, Ps[b], np.full(361, 70.0))
+            if fastslam:
+                h.set_fastslam_config(fastslam_sweep_config(h, Ps[b]))
             h.synchronize()
         owned = target
     t0 = time.perf_counter()
     dev = route == "batch_dev" or (route == "handles" and device_loop)
-    r = pkg.vp_driver.VictoriaParkBatchRun(target, data, Ps, seeds, added_clutter=clutter, device_loop=dev).run(n_messages=messages)
+    r = pkg.vp_driver.VictoriaParkBatchRun(target, data, Ps, seeds, added_clutter=clutter, device_loop=dev,
+                                           filter="fastslam" if fastslam else "rbphd").run(n_messages=messages)
     dt = time.perf_counter() - t0
     info = (int(r.n_lidar), int(r.n_resamples.sum()), float(np.mean(np.concatenate([h.gm_sizes() for h in owned]))))
     for h in owned:
@@ -158,18 +178,21 @@ def batch_main():
     ap.add_argument("--only", choices=["batch", "handles", "batch_dev"], default=None)
     ap.add_argument("--capacity", type=int, default=384)      # (192 is transiently short under the heaviest clutter of the sweep)
     ap.add_argument("--device-loop", action="store_true")
+    ap.add_argument("--fastslam", action="store_true")
     a = ap.parse_args()
     data = np.load(os.path.join(ROOT, "tests", "golden", "victoria_park_extract.npz"))
     routes = [a.only] if a.only else (["handles", "batch", "batch_dev"] if a.device_loop else ["handles", "batch"])
     times = {r: [] for r in routes}
     for rep in range(a.reps + 1):                     # (the first repetition warms up: code objects, allocations)
         for route in routes:
-            dt, info = batch_one_run(route, a.batch, a.particles, data, a.messages, a.capacity, a.device_loop)
+            dt, info = batch_one_run(route, a.batch, a.particles, data, a.messages, a.capacity, a.device_loop, a.fastslam)
             if rep:
                 times[route].append(dt)
             print("  %-9s rep %d%s: %.4f s for %d filters (%d lidar updates, %d resamplings, mean map size %.1f)" %
                   ((route, rep, "" if rep else " (warm-up)", dt, a.batch) + info), flush=True)
     out = dict(tool="vp_bench", filters=a.batch, particles=a.particles, messages=a.messages, reps=a.reps, device_loop=bool(a.device_loop))
+    if a.fastslam:
+        out["filter"] = "fastslam"
     for r in routes:
         med = float(np.median(times[r]))
         out[r + "_s"] = med
