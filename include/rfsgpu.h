@@ -1002,6 +1002,43 @@ int rfsgpu_batch_live_counts(rfsgpu_filter *f, int *out);
  *     weights 1: slot 0 of the block is the best), is evaluated like any other.
  * Everything else that is refused on such a batch stays refused (rfsgpu_batch_weight_sums, the resampling calls). */
 int rfsgpu_batch_mh_serve_metrics(rfsgpu_filter *f, int on);
+/* -- a batch of Victoria Park multi-hypothesis FastSLAM filters (outside the STABLE CORE): n_filters independent rfs::FastSLAM filters
+ * on the Victoria Park models, each with maxNDataAssocHypotheses in [2, 16].  The layout is rfsgpu_create_batch_mh's: filter b owns the
+ * global slots [b * max_per_filter, (b + 1) * max_per_filter), its first n_b are live, n_b is a word on the device.  Filter b equals a
+ * Victoria Park handle made by rfsgpu_create_ex(max_particles = max_per_filter) and stepped by rfsgpu_static_steps_async /
+ * rfsgpu_propagate_ackerman_run_async / rfsgpu_fastslam_cycle_full_async(predict = 0, n_init = n_per_filter) on the same poses, sets,
+ * scan and draws: mixtures, counts, candidate lists, unused masks, in-view counts, poses, ids, parents, plans, live counts and the
+ * fired / forced decisions bit for bit; weights and N_eff to rounding (the batch sums in its own tree).  The argument errors are those
+ * of rfsgpu_create_batch_mh (which keeps refusing the Victoria Park model); nParticlesMax defaults to 3 * n_per_filter.
+ *
+ * Configuration: rfsgpu_batch_configure_vp, rfsgpu_set_model_victoriapark, rfsgpu_set_lmk_process_noise and rfsgpu_set_laser_scan as on
+ * a batch of Victoria Park filters (one scan for the handle; each filter's clutter term comes from its own expectedClutterNumber);
+ * rfsgpu_batch_set_fastslam_config with maxNDataAssocHypotheses 2 ... 16 and ANY landmarkCandidateMeasurementCountThreshold -- one
+ * hypothesis is refused, naming the filter: single-hypothesis filters belong to rfsgpu_batch_vp_serve_fastslam (a handle associates one
+ * hypothesis by the sparse single-hypothesis kernel, whose bits Murty's search with a limit of one does not reproduce);
+ * rfsgpu_batch_set_resampling for the N_eff thresholds (unset: n_per_filter / 4 and 0.25).
+ *
+ * Also served: rfsgpu_batch_fastslam_last_cycle and rfsgpu_batch_live_counts; rfsgpu_batch_vp_set_motion and
+ * rfsgpu_batch_vp_propagate_run_async (every slot of every block moves; a slot's draw is keyed by its index within the filter, so a live
+ * slot draws what its handle's particle draws); rfsgpu_static_steps_async (the live slots).  The last two enqueue behind pending cycles
+ * without waiting, and skip a filter whose overflow word is up, as a handle abandons them behind an abandoned cycle.
+ *
+ * Refused with RFSGPU_ERR_UNSUPPORTED and a message, state untouched: rfsgpu_batch_cycle_async, rfsgpu_batch_vp_cycle_async,
+ * rfsgpu_batch_fastslam_cycle_async, rfsgpu_batch_vp_fastslam_cycle_async, rfsgpu_batch_fastslam_mh_cycle_async;
+ * rfsgpu_batch_vp_resample_async / _vp_last_resample / _vp_set_resampling / _vp_loop_counts, rfsgpu_batch_resample_async /
+ * _resample_apply / _last_resample / _resample_counts, rfsgpu_batch_weight_sums; the [sensor], [truth], [metric] and [estimate] calls;
+ * rfsgpu_batch_vp_serve_fastslam, rfsgpu_batch_vp_serve_estimates and rfsgpu_batch_mh_serve_metrics; rfsgpu_batch_set_motion_odometry,
+ * rfsgpu_batch_propagate_async (the 2-D device loop). */
+int rfsgpu_create_batch_vp_mh(rfsgpu_filter **out, int n_filters, int n_per_filter, int max_per_filter, int device_id, int gm_capacity);
+/* One whole FastSLAM::update of every filter of such a batch as one launch chain; nothing is read back.  Counts, per-filter overflow,
+ * the u01 range check (naming the filter) and x == NULL are rfsgpu_batch_fastslam_mh_cycle_async's; z is [n_filters][RFSGPU_MAX_Z][3];
+ * scan / n_scan follow rfsgpu_batch_vp_cycle_async (NULL: the scan the batch holds; none held: RFSGPU_ERR_INVALID).  A particle's
+ * copies take its landmark candidate lists exactly when THAT FILTER's previous cycle resampled (FastSLAM.hpp:551-553); the resampling
+ * gather moves the lists, the unused mask and the in-view count with the particle.  A 65th candidate, a map beyond gm_capacity or a
+ * Murty table beyond 64 reaches the host through the shared error word at the next synchronising call; rfsgpu_last_error names the
+ * lowest filter for gm_capacity and for the candidate list.  Any other kind of handle: RFSGPU_ERR_UNSUPPORTED, state untouched. */
+int rfsgpu_batch_vp_fastslam_mh_cycle_async(rfsgpu_filter *f, int predict, const double *x, const double *x_cov, int cov_stride,
+                                            const double *z, const int *n_z, const double *scan, int n_scan, const double *u01);
 #ifdef RFSGPU_ENABLE_BENCH_API
 /* [test] 1 once a step of this handle (batch or not) has queued Murty-200 partitions, else 0.  Synchronising. */
 int rfsgpu_murty_seen(rfsgpu_filter *f);

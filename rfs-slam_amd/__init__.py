@@ -15,4 +15,4 @@ from . import scenarios  # noqa: F401
 from . import sharded  # noqa: F401
 from . import vp_driver  # noqa: F401
 from . import sim2d_driver  # noqa: F401
-from .engine import FastSLAM, FastSLAMBatch, FilterBatch, FilterGroup, MHFastSLAMBatch, RBPHDFilter, VPFastSLAMBatch, VPFilterBatch, load_library, mat_perm  # noqa: F401
+from .engine import FastSLAM, FastSLAMBatch, FilterBatch, FilterGroup, MHFastSLAMBatch, RBPHDFilter, VPFastSLAMBatch, VPFilterBatch, VPMHFastSLAMBatch, load_library, mat_perm  # noqa: F401

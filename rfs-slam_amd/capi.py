@@ -175,6 +175,7 @@ ABI_SYMBOLS = [
     "batch_configure_vp", "batch_vp_cycle_async",
     "batch_vp_set_motion", "batch_vp_set_resampling", "batch_vp_propagate_run_async", "batch_vp_resample_async", "batch_vp_last_resample", "batch_vp_loop_counts",
     "batch_vp_serve_fastslam", "batch_vp_fastslam_cycle_async",
+    "create_batch_vp_mh", "batch_vp_fastslam_mh_cycle_async",
 ]
 
 _dp = np.ctypeslib.ndpointer(dtype=np.float64, flags="C_CONTIGUOUS")
@@ -1364,6 +1365,52 @@ class CBatchMH(CBatch):
         step_error, get_map_estimate) serve this batch, each filter's record over its live slots as the device counts them where the
         kernel runs; on=False: they refuse again."""
         self._call("batch_mh_serve_metrics", C.c_int(1 if on else 0))
+
+
+class CBatchVPMH(CBatchMH, CVPBatch):
+    """A batch of Victoria Park multi-hypothesis FastSLAM filters behind the C ABI (rfsgpu_create_batch_vp_mh): CBatchMH's layout and
+    read-backs (block, batch_fastslam_last_cycle, batch_live_counts), CVPBatch's configuration, scan, motion and run propagation.  Its
+    cycle is batch_vp_fastslam_mh_cycle_async; every other cycle, the resampling calls and the serve_* switches refuse."""
+
+    def __init__(self, lib, prefix, n_filters, n_per_filter, max_per_filter, device_id=0, gm_capacity=512):
+        self._lib, self._p = lib, prefix
+        self.model = MODEL_VICTORIAPARK_3D
+        self.device_id = device_id
+        self.dm = self.dz = 3
+        self._borrowed = False
+        self._h = C.c_void_p()
+        fn = self._fn("create_batch_vp_mh")
+        fn.restype = C.c_int
+        rc = fn(C.byref(self._h), C.c_int(int(n_filters)), C.c_int(int(n_per_filter)), C.c_int(int(max_per_filter)), C.c_int(device_id), C.c_int(gm_capacity))
+        if rc != OK:
+            self._h = C.c_void_p()
+            raise EngineError(rc, "create_batch_vp_mh failed: " + ("max_per_filter beyond 2048 (one workgroup resamples a filter)" if rc == ERR_UNSUPPORTED
+                                                                   else "no gfx950 device / bad arguments (max_per_filter < n_per_filter?)"))
+        self.n_filters = int(n_filters)
+        self.n_per_filter = int(n_per_filter)
+        self.gm_capacity = int(gm_capacity)
+        self.max_per_filter = int(max_per_filter)
+
+    def batch_vp_fastslam_mh_cycle_async(self, predict, Zs, u01, poses=None, pose_cov=None, scan=None):
+        """rfsgpu_batch_vp_fastslam_mh_cycle_async: Zs one measurement array per filter ([n_z, 3], possibly empty), u01 [n_filters] the
+        draws in [0, 1); scan: the laser scan that goes with the sets (None: the one the handle holds)."""
+        assert len(Zs) == self.n_filters
+        z = np.zeros((self.n_filters, MAX_Z, 3))
+        nz = np.zeros(self.n_filters, dtype=np.int32)
+        for b, Z in enumerate(Zs):
+            Z = _f64(Z).reshape(-1, 3) if np.size(Z) else np.zeros((0, 3))
+            nz[b] = Z.shape[0]
+            z[b, : min(Z.shape[0], MAX_Z)] = Z[:MAX_Z]
+        self.batch_vp_fastslam_mh_cycle_async_packed(predict, z, nz, u01, poses=poses, pose_cov=pose_cov, scan=scan)
+
+    def batch_vp_fastslam_mh_cycle_async_packed(self, predict, z, nz, u01, poses=None, pose_cov=None, scan=None):
+        """The same with the sets already in the call's layout (z [n_filters, MAX_Z, 3] float64, nz [n_filters] int32, C-contiguous)."""
+        assert z.dtype == np.float64 and nz.dtype == np.int32 and z.shape == (self.n_filters, MAX_Z, 3) and z.flags.c_contiguous and nz.flags.c_contiguous
+        u = _f64(u01, (self.n_filters,))
+        px, pc, stride, keep = self._pose_args(poses, pose_cov)
+        s = None if scan is None else _f64(scan).reshape(-1)
+        self._call("batch_vp_fastslam_mh_cycle_async", C.c_int(1 if predict else 0), px, pc, stride, self._ptr(z), self._ptr(nz),
+                   C.c_void_p(None) if s is None else self._ptr(s), C.c_int(0 if s is None else s.size), self._ptr(u))
 
 
 def mat_perm(lib, prefix, A, device_id=0):

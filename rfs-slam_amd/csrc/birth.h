@@ -516,6 +516,31 @@ __global__ __launch_bounds__(WPB * 64) void static_steps_kernel(Buffers B, int c
     }
   }
 }
+// ... on a batch of multi-hypothesis filters whose counts are on the device (rfsgpu_create_batch_vp_mh): a wave beyond its filter's
+// count leaves, and so does every wave of a filter whose overflow word is up (its cycle and what follows it are abandoned, as on a
+// handle).  words: filter 0's cycle words, wordStride ints per filter; nWord / ovfWord: the count's and the overflow word's index.
+// Waves of one workgroup may belong to different filters: no workgroup barrier.
+template <int D, int WPB>
+__global__ __launch_bounds__(WPB * 64) void static_steps_guard_kernel(Buffers B, int cur, StaticRun R, int nPer, const int *words, int wordStride, int nWord, int ovfWord) {
+  const int wave = threadIdx.x >> 6;
+  const int lane = threadIdx.x & 63;
+  const int i = __builtin_amdgcn_readfirstlane(blockIdx.x * WPB + wave);
+  if (i >= B.N) return;
+  const int bf = i / nPer;
+  const int *w = words + (size_t)bf * wordStride;
+  if (__builtin_amdgcn_readfirstlane(w[ovfWord]) != 0 || i - bf * nPer >= __builtin_amdgcn_readfirstlane(w[nWord])) return;
+  const int cap = B.cap, n = B.count[i];
+  double *slab = B.slab[cur];
+  constexpr int NC = (D == 2) ? 3 : 6;
+  for (int t = 0; t < NC; t++) {
+    double *p = (D == 2) ? plane(slab, cap, i, PL_SXX + t) : plane3(slab, cap, i, P3_SXX + t);
+    for (int m = lane; m < n; m += 64) {
+      double a = p[m];
+      for (int r = 0; r < R.n; r++) a += R.q[r][t];
+      p[m] = a;
+    }
+  }
+}
 // ... behind a pending device cycle (fastslam_cycle.h): launched at the handle's capacity, the count is read on the device.
 template <int D, int WPB>
 __global__ __launch_bounds__(WPB * 64) void static_steps_live_kernel(Buffers B, int cur, StaticRun R, int nCap, LiveCount live) {

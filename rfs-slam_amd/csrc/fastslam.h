@@ -722,6 +722,9 @@ __global__ __launch_bounds__(64 * FS_NEWLM_WPB) void fs_new_landmarks_kernel(Buf
       atomicOr(B.err, ERRBIT_CAPACITY);
       if constexpr (BATCH) atomicMin(batch_first_arg(batchArg...).errFilter, bf);
     }
-    if (listFull) atomicOr(B.err, ERRBIT_BIRTHLIST);
+    if (listFull) {
+      atomicOr(B.err, ERRBIT_BIRTHLIST);
+      if constexpr (D == 3 && is_mh_batch<TBatch...>::value) atomicMin(batch_first_arg(batchArg...).errFilter + 1, bf);   // (the second word names the lowest filter)
+    }
   }
 }

@@ -305,6 +305,21 @@ __global__ __launch_bounds__(256) void fs_cycle_static_step_batch_kernel(Buffers
   if (mhb_ovf(A, bf) || mhb_beyond_count(A, i)) return;
   predict_map_particle<64>(B, A.params[bf], cur, i, lane, false, 0, B.pose, true);
 }
+// ... of a batch of Victoria Park filters: fs_cycle_static_step3_kernel's additions with the slot's own filter's Q
+__global__ __launch_bounds__(256) void fs_cycle_static_step3_batch_kernel(Buffers B, int cur, MhBatchArg A) {
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int i = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + wave);
+  if (i >= B.N) return;
+  const int bf = __builtin_amdgcn_readfirstlane(i / A.nPer);
+  if (mhb_ovf(A, bf) || mhb_beyond_count(A, i)) return;
+  const Params &P = A.params[bf];
+  const int cap = B.cap, n = B.count[i];
+  double *slab = B.slab[cur];
+  for (int t = 0; t < 6; t++) {
+    double *p = plane3(slab, cap, i, P3_SXX + t);
+    for (int m = lane; m < n; m += 64) p[m] += P.Qlm6[t];
+  }
+}
 __global__ __launch_bounds__(FS_CYCLE_THREADS) void fs_mh_plan_batch_kernel(const unsigned char *arena, unsigned char *state, int *slotHyp, int *slotNH, int *copyDst,
                                                                             int *copySrc, MhBatchArg A) {
   const int b = blockIdx.x, base = b * A.nPer;

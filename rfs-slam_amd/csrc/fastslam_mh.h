@@ -274,6 +274,14 @@ struct LiveCopy : LiveCount {
 };
 template <typename... T> struct is_live_copy { static constexpr bool value = false; };
 template <> struct is_live_copy<LiveCopy> { static constexpr bool value = true; };
+// ... and of a batch of Victoria Park multi-hypothesis filters (rfsgpu_batch_vp_fastslam_mh_cycle_async): candWord names the word of
+// the destination slot's own filter that holds its resampleOccured_, so the lists travel per filter.
+struct MhBatchCopy : MhBatchArg {
+  int candWord;
+};
+template <> struct is_mh_batch<MhBatchCopy> { static constexpr bool value = true; };
+template <typename... T> struct is_mh_batch_copy { static constexpr bool value = false; };
+template <> struct is_mh_batch_copy<MhBatchCopy> { static constexpr bool value = true; };
 
 // One workgroup per NEW slot: ParticleFilter::copyParticle (ParticleFilter.hpp:273-294) of slot src -> slot dst.
 // live: its count is the number of copies.
@@ -283,6 +291,10 @@ __global__ __launch_bounds__(256) void fs_mh_copy_kernel(Buffers B, int cur, con
     if (live_beyond(pack_first(live...), (int)blockIdx.x)) return;
   }
   if constexpr (is_live_copy<TLive...>::value) copyCand = __builtin_amdgcn_readfirstlane(*pack_first(live...).copyCand) != 0;
+  if constexpr (is_mh_batch_copy<TLive...>::value) {     // (workgroup-uniform: the workgroup's slot names its filter)
+    const MhBatchCopy &A = pack_first(live...);
+    copyCand = __builtin_amdgcn_readfirstlane(A.words[(size_t)((int)blockIdx.x / A.nPer) * A.wordStride + A.candWord]) != 0;
+  }
   int d = dstSlot[blockIdx.x], s = srcSlot[blockIdx.x];
   if constexpr (is_mh_batch<TLive...>::value) {    // the lists are per filter, in slots of the filter's own block
     const int nPer = pack_first(live...).nPer, base = ((int)blockIdx.x / nPer) * nPer;

@@ -281,6 +281,7 @@ struct rfsgpu_filter {
   // a batch of multi-hypothesis FastSLAM filters (rfsgpu_create_batch_mh; fastslam_cycle.h): nPer is the stride max_per_filter, every
   // filter has its own cycle block on the device and its live count is a word of it
   bool mhBatch = false;
+  bool vpMh = false;                           // ... of Victoria Park filters (rfsgpu_create_batch_vp_mh; its cycle is rfsgpu_batch_vp_fastslam_mh_cycle_async)
   int nInitPer = 0;                            // n_per_filter: the count a filter starts with and a resampling brings it back to
   unsigned char *mhbBlock = nullptr;           // device: nF cycle blocks of fs_cycle_state_bytes(nPer) bytes
   unsigned char *hMhbBlock = nullptr;          // pinned: where they land when the host next synchronises
@@ -2096,6 +2097,23 @@ int rfsgpu_predict_map_async(rfsgpu_filter *f, int add_birth) {
 // rfsgpu_set_lmk_process_noise(Q_k) + rfsgpu_predict_map_async(f, 0).  noises: [n][D*D] row-major, or NULL = the noise that is set
 // now, n times.  Stream-ordered.
 int rfsgpu_static_steps_async(rfsgpu_filter *f, int n, const double *noises) {
+  if (f && f->vpMh) {     // a batch of Victoria Park multi-hypothesis filters: behind its cycles, the counts and overflow words read on the device
+    if (n < 0) return fail(f, RFSGPU_ERR_INVALID, "static_steps: negative count");
+    hipSetDevice(f->device);
+    FsCycleState S0;
+    mhb_state(f->mhbBlock, f->nF, f->nPer, 0, S0);
+    for (int k0 = 0; k0 < n; k0 += STATIC_RUN_MAX) {
+      StaticRun R;
+      R.n = std::min(STATIC_RUN_MAX, n - k0);
+      for (int r = 0; r < R.n; r++) {
+        const double *Q = noises ? noises + (size_t)(k0 + r) * 9 : f->Qlm;
+        R.q[r][0] = Q[0]; R.q[r][1] = Q[1]; R.q[r][2] = Q[2]; R.q[r][3] = Q[4]; R.q[r][4] = Q[5]; R.q[r][5] = Q[8];
+      }
+      static_steps_guard_kernel<3, 4><<<(f->N + 3) / 4, 256, 0, f->stream>>>(f->B, f->cur, R, f->nPer, S0.w, FSC_WORDS, FSC_N, FSC_OVF);
+      HIPCHK(hipGetLastError());
+    }
+    return RFSGPU_OK;
+  }
   CHECK_HANDLE_BEHIND_CYCLE(f, behind);
   if (n < 0) return fail(f, RFSGPU_ERR_INVALID, "static_steps: negative count");
   hipSetDevice(f->device);
@@ -3591,7 +3609,7 @@ static int batch_cycle_core(rfsgpu_filter *f, int predict, const double *x, cons
 static int batch_fs_cycle_core(rfsgpu_filter *f, int predict, const double *x, const double *x_cov, int cov_stride, const double *z, const int *n_z, int normalize,
                                const double *scan = nullptr, int n_scan = 0);
 static int batch_mh_cycle_core(rfsgpu_filter *f, int predict, const double *x, const double *x_cov, int cov_stride, const double *z, const int *n_z, const double *u01,
-                               unsigned long long call);
+                               unsigned long long call, const double *scan = nullptr, int n_scan = 0);
 static int batch_push_motion(rfsgpu_filter *f);
 static int batch_resample_core(rfsgpu_filter *f, const BatchCall &C, const int *n_z, unsigned long long call, bool stageIn = true);
 static int batch_enter_dev_route(rfsgpu_filter *f);
@@ -4021,6 +4039,7 @@ int rfsgpu_batch_vp_cycle_async(rfsgpu_filter *f, int predict, const double *x, 
   if (rc != RFSGPU_OK) return rc;
   if (f->D != 3)
     return fail(f, RFSGPU_ERR_UNSUPPORTED, "batch_vp_cycle: this batch steps 2-D filters (rfsgpu_batch_cycle_async, rfsgpu_batch_fastslam_cycle_async or rfsgpu_batch_fastslam_mh_cycle_async): the Victoria Park cycle needs a batch created with RFSGPU_MODEL_VICTORIAPARK_3D");
+  if (f->vpMh) return fail(f, RFSGPU_ERR_UNSUPPORTED, "batch_vp_cycle: this is the RB-PHD cycle; a batch of Victoria Park multi-hypothesis FastSLAM filters (rfsgpu_create_batch_vp_mh) takes rfsgpu_batch_vp_fastslam_mh_cycle_async");
   if ((rc = batch_check_call(f, BATCH_VP_CYCLE, predict, x_cov, cov_stride, n_z)) != RFSGPU_OK) return rc;
   for (int b = 0; b < f->nF; b++)
     if ((rc = batch_check_filter(f, BATCH_VP_CYCLE, b, z, n_z)) != RFSGPU_OK) return rc;
@@ -4039,10 +4058,16 @@ int rfsgpu_batch_set_fastslam_config(rfsgpu_filter *f, int filter, const rfsgpu_
   CHECK_HANDLE(f);
   int rc = batch_check(f, filter);
   if (rc != RFSGPU_OK) return rc;
-  if (!f->bVpFastSlam) { REFUSE_ON_VP_BATCH(f, "rfsgpu_batch_set_fastslam_config"); }     // (rfsgpu_batch_vp_serve_fastslam switches it on)
+  if (!f->bVpFastSlam && !f->vpMh) { REFUSE_ON_VP_BATCH(f, "rfsgpu_batch_set_fastslam_config"); }     // (rfsgpu_batch_vp_serve_fastslam switches it on; rfsgpu_create_batch_vp_mh has it from creation)
   if (!cfg) return fail(f, RFSGPU_ERR_INVALID, "batch_set_fastslam_config: null configuration");
   const std::string who = filter < 0 ? std::string("every filter") : "filter " + std::to_string(filter);
-  if (f->mhBatch) {
+  if (f->vpMh) {     // (one hypothesis is the sparse single-hypothesis association on a handle, whose bits Murty with a limit of one does not give)
+    if (cfg->maxNDataAssocHypotheses < 2u || cfg->maxNDataAssocHypotheses > (unsigned)FSMH_MAX_HYP) {
+      f->err = "batch_set_fastslam_config: " + who + ": maxNDataAssocHypotheses must be in [2, 16] on a batch of Victoria Park multi-hypothesis filters (rfsgpu_create_batch_vp_mh); "
+               "single-hypothesis filters belong to a batch with rfsgpu_batch_vp_serve_fastslam";
+      return RFSGPU_ERR_UNSUPPORTED;
+    }
+  } else if (f->mhBatch) {
     if (cfg->maxNDataAssocHypotheses < 1u || cfg->maxNDataAssocHypotheses > (unsigned)FSMH_MAX_HYP) {
       f->err = "batch_set_fastslam_config: " + who + ": maxNDataAssocHypotheses must be in [1, 16]";
       return RFSGPU_ERR_UNSUPPORTED;
@@ -4052,7 +4077,7 @@ int rfsgpu_batch_set_fastslam_config(rfsgpu_filter *f, int filter, const rfsgpu_
     return RFSGPU_ERR_UNSUPPORTED;
   }
   // (a batch of Victoria Park FastSLAM filters keeps candidate lists: both of its resampling routes move them with the particle)
-  if (cfg->landmarkCandidateMeasurementCountThreshold != 1u && !f->bVpFastSlam) {
+  if (cfg->landmarkCandidateMeasurementCountThreshold != 1u && !f->bVpFastSlam && !f->vpMh) {
     f->err = "batch_set_fastslam_config: " + who + ": landmarkCandidateMeasurementCountThreshold must be 1 on a filter batch (landmark candidate lists would have to travel with a resampling)";
     return RFSGPU_ERR_UNSUPPORTED;
   }
@@ -4108,7 +4133,8 @@ int rfsgpu_batch_vp_fastslam_cycle_async(rfsgpu_filter *f, int predict, const do
   CHECK_HANDLE(f);
   if (!f->batch || f->D != 3 || !f->bVpFastSlam) {
     f->err = std::string("batch_vp_fastslam_cycle: the call serves a batch of Victoria Park FastSLAM filters (rfsgpu_create_batch with RFSGPU_MODEL_VICTORIAPARK_3D, then rfsgpu_batch_vp_serve_fastslam), not ") +
-             (f->batch ? (f->D == 3 ? "a batch of Victoria Park filters whose switch is off (it steps RB-PHD filters: rfsgpu_batch_vp_cycle_async)"
+             (f->batch ? (f->D == 3 ? (f->vpMh ? "a batch of Victoria Park multi-hypothesis FastSLAM filters (rfsgpu_create_batch_vp_mh): its cycle is rfsgpu_batch_vp_fastslam_mh_cycle_async"
+                                               : "a batch of Victoria Park filters whose switch is off (it steps RB-PHD filters: rfsgpu_batch_vp_cycle_async)")
                                     : (f->mhBatch ? "a batch of multi-hypothesis FastSLAM filters (rfsgpu_batch_fastslam_mh_cycle_async)" : "a 2-D batch (rfsgpu_batch_fastslam_cycle_async)"))
                        : (f->groupShard ? "a shard of an rfsgpu_group" : "an ordinary handle (rfsgpu_fastslam_update)"));
     return RFSGPU_ERR_UNSUPPORTED;
@@ -4212,16 +4238,28 @@ static int batch_fs_cycle_core(rfsgpu_filter *f, int predict, const double *x, c
 // first n_b are live; n_b, the overflow word, the counters, the plans and the ids are in the filter's own cycle block on the device.
 static inline size_t mhb_bytes(const rfsgpu_filter *f) { return mhb_state_bytes(f->nF, f->nPer); }
 static void mhb_view(const rfsgpu_filter *f, unsigned char *base, int b, FsCycleState &S) { mhb_state(base, f->nF, f->nPer, b, S); }
+static int create_batch_mh_of(rfsgpu_filter **out, int model, int n_filters, int n_per_filter, int max_per_filter, int device_id, int gm_capacity);
 int rfsgpu_create_batch_mh(rfsgpu_filter **out, int model, int n_filters, int n_per_filter, int max_per_filter, int device_id, int gm_capacity) {
   if (!out) return RFSGPU_ERR_INVALID;
   *out = nullptr;
-  if (model == RFSGPU_MODEL_VICTORIAPARK_3D) return RFSGPU_ERR_UNSUPPORTED;    // (2-D range-bearing filters only)
-  if (model != RFSGPU_MODEL_RNGBRG_2D || n_filters < 1 || n_per_filter < 1 || max_per_filter < n_per_filter) return RFSGPU_ERR_INVALID;
+  if (model == RFSGPU_MODEL_VICTORIAPARK_3D) return RFSGPU_ERR_UNSUPPORTED;    // (2-D range-bearing filters only; rfsgpu_create_batch_vp_mh)
+  if (model != RFSGPU_MODEL_RNGBRG_2D) return RFSGPU_ERR_INVALID;
+  return create_batch_mh_of(out, model, n_filters, n_per_filter, max_per_filter, device_id, gm_capacity);
+}
+// ... of Victoria Park filters: a kind of its own from creation (rfsgpu_batch_vp_fastslam_mh_cycle_async steps it)
+int rfsgpu_create_batch_vp_mh(rfsgpu_filter **out, int n_filters, int n_per_filter, int max_per_filter, int device_id, int gm_capacity) {
+  if (!out) return RFSGPU_ERR_INVALID;
+  *out = nullptr;
+  return create_batch_mh_of(out, RFSGPU_MODEL_VICTORIAPARK_3D, n_filters, n_per_filter, max_per_filter, device_id, gm_capacity);
+}
+static int create_batch_mh_of(rfsgpu_filter **out, int model, int n_filters, int n_per_filter, int max_per_filter, int device_id, int gm_capacity) {
+  if (n_filters < 1 || n_per_filter < 1 || max_per_filter < n_per_filter) return RFSGPU_ERR_INVALID;
   if (max_per_filter > RFSGPU_FASTSLAM_CYCLE_MAX_PARTICLES) return RFSGPU_ERR_UNSUPPORTED;   // (the resampling workgroup holds one filter in LDS)
   rfsgpu_filter *f = nullptr;
   int rc = rfsgpu_create_batch(&f, model, n_filters, max_per_filter, device_id, gm_capacity);
   if (rc != RFSGPU_OK) return rc;
   f->mhBatch = true;
+  f->vpMh = model == RFSGPU_MODEL_VICTORIAPARK_3D;
   f->bKind = 3;
   f->nInitPer = n_per_filter;
   f->mhbLastNZ.assign(n_filters, 0);
@@ -4290,6 +4328,7 @@ int rfsgpu_batch_fastslam_mh_cycle_async(rfsgpu_filter *f, int predict, const do
   int rc = batch_check(f, -1);
   if (rc != RFSGPU_OK) return rc;
   if (!f->mhBatch) return fail(f, RFSGPU_ERR_UNSUPPORTED, "batch_fastslam_mh_cycle: not a batch of multi-hypothesis FastSLAM filters (rfsgpu_create_batch_mh)");
+  if (f->vpMh) return fail(f, RFSGPU_ERR_UNSUPPORTED, "batch_fastslam_mh_cycle: this is the 2-D cycle; a batch of Victoria Park multi-hypothesis filters (rfsgpu_create_batch_vp_mh) takes rfsgpu_batch_vp_fastslam_mh_cycle_async");
   if ((rc = batch_check_call(f, BATCH_MH_CYCLE, predict, x_cov, cov_stride, u01 ? n_z : nullptr)) != RFSGPU_OK) return rc;
   const int nF = f->nF;
   for (int b = 0; b < nF; b++) {
@@ -4303,13 +4342,49 @@ int rfsgpu_batch_fastslam_mh_cycle_async(rfsgpu_filter *f, int predict, const do
     return fail(f, RFSGPU_ERR_UNSUPPORTED, "batch_fastslam_mh_cycle: this batch has run a sensed cycle (rfsgpu_batch_fastslam_mh_cycle_sensed_async): its measurement counts live on the device, the host-fed cycle no longer knows them");
   return batch_mh_cycle_core(f, predict, x, x_cov, cov_stride, z, n_z, u01, 0ull);
 }
+// ... of Victoria Park filters (rfsgpu_create_batch_vp_mh): z [n_filters][RFSGPU_MAX_Z][3]; the scan as in rfsgpu_batch_vp_cycle_async.
+static const BatchCall BATCH_VP_MH_CYCLE{"batch_vp_fastslam_mh_cycle", 0, "0 or 1 (the static landmark step; FastSLAM has no births)", "null measurement counts or draws"};
+int rfsgpu_batch_vp_fastslam_mh_cycle_async(rfsgpu_filter *f, int predict, const double *x, const double *x_cov, int cov_stride, const double *z, const int *n_z,
+                                            const double *scan, int n_scan, const double *u01) {
+  if (!f) return RFSGPU_ERR_INVALID;
+  if (!f->vpMh) {
+    if (f->mhcPending || f->mhcStashedRc || f->mhbPending || f->rsPending || f->rcPending) { const int rcp = mhc_resolve(f); if (rcp != RFSGPU_OK) return rcp; }
+    f->err = std::string("batch_vp_fastslam_mh_cycle: the call serves a batch of Victoria Park multi-hypothesis FastSLAM filters (rfsgpu_create_batch_vp_mh), not ") +
+             (f->batch ? (f->mhBatch ? "a 2-D batch of multi-hypothesis FastSLAM filters (rfsgpu_batch_fastslam_mh_cycle_async)"
+                                     : (f->D == 3 ? (f->bVpFastSlam ? "a batch of Victoria Park FastSLAM filters (rfsgpu_batch_vp_fastslam_cycle_async)"
+                                                                    : "a batch of Victoria Park RB-PHD filters (rfsgpu_batch_vp_cycle_async)")
+                                                  : "a 2-D batch (rfsgpu_batch_cycle_async, rfsgpu_batch_fastslam_cycle_async)"))
+                       : (f->groupShard ? "a shard of an rfsgpu_group" : "an ordinary handle (rfsgpu_fastslam_cycle_full_async)"));
+    return RFSGPU_ERR_UNSUPPORTED;
+  }
+  int rc = RFSGPU_OK;
+  if ((rc = batch_check_call(f, BATCH_VP_MH_CYCLE, predict, x_cov, cov_stride, u01 ? n_z : nullptr)) != RFSGPU_OK) return rc;
+  const int nF = f->nF;
+  for (int b = 0; b < nF; b++) {
+    if ((rc = batch_check_filter(f, BATCH_VP_MH_CYCLE, b, z, n_z)) != RFSGPU_OK) return rc;
+    if (!(u01[b] >= 0.0 && u01[b] < 1.0)) {
+      f->err = "batch_vp_fastslam_mh_cycle: filter " + std::to_string(b) + ": u01 must lie in [0, 1)";
+      return RFSGPU_ERR_INVALID;
+    }
+    if (f->bFs[b].maxNDataAssocHypotheses < 2u || f->bFs[b].maxNDataAssocHypotheses > (unsigned)FSMH_MAX_HYP) {
+      f->err = "batch_vp_fastslam_mh_cycle: filter " + std::to_string(b) + ": maxNDataAssocHypotheses must be in [2, 16] (rfsgpu_batch_set_fastslam_config)";
+      return RFSGPU_ERR_UNSUPPORTED;
+    }
+  }
+  if (scan && (n_scan < 2 || n_scan > RFSGPU_VP_MAX_SCAN)) return batch_fail(f, BATCH_VP_MH_CYCLE, "laser scan size out of range (2 ... RFSGPU_VP_MAX_SCAN beams)");
+  if (!scan && f->B.nScan < 2) return batch_fail(f, BATCH_VP_MH_CYCLE, "the batch has not been given a laser scan (rfsgpu_set_laser_scan, or this call's scan)");
+  return batch_mh_cycle_core(f, predict, x, x_cov, cov_stride, z, n_z, u01, 0ull, scan, n_scan);
+}
 // The cycle behind rfsgpu_batch_fastslam_mh_cycle_async (n_z, u01 given: the host's sets and records go to the device first) and
 // rfsgpu_batch_fastslam_mh_cycle_sensed_async (n_z null: the sets are where the last rfsgpu_batch_sense_async left them, the records are
 // made from that call's on the device, each filter's draw is the resampling draw of (its motion key, call)).  The arguments have been checked.
+// A batch of Victoria Park filters (rfsgpu_batch_vp_fastslam_mh_cycle_async; never sensed): the D = 3 forms of the same chain, the
+// candidate lists travelling with the copies of a filter whose previous cycle resampled and with every resampling; scan, when given,
+// becomes the scan the batch holds, as in batch_fs_cycle_core.
 static int batch_mh_cycle_core(rfsgpu_filter *f, int predict, const double *x, const double *x_cov, int cov_stride, const double *z, const int *n_z, const double *u01,
-                               unsigned long long call) {
+                               unsigned long long call, const double *scan, int n_scan) {
   const bool sensed = n_z == nullptr;
-  const int nF = f->nF, N = f->N, stride = f->nPer;
+  const int nF = f->nF, N = f->N, stride = f->nPer, D = f->D;
   int rc = RFSGPU_OK;
   hipSetDevice(f->device);
   long long t0 = now_ns();
@@ -4317,10 +4392,18 @@ static int batch_mh_cycle_core(rfsgpu_filter *f, int predict, const double *x, c
   if (!f->mhArena) HIPCHK(hipMalloc(&f->mhArena, (size_t)N * L.total));          // every slot's table / Murty arena / assignments, once
   if (!f->mhcInts) HIPCHK(hipMalloc(&f->mhcInts, (size_t)4 * N * sizeof(int)));
   batch_handle_wide(f, x, x_cov, cov_stride);
+  if (scan) {     // every filter's clutter density on the host (it travels in the Params table), the beams by copy command below
+    double area = 0;
+    for (int q = 1; q < n_scan; q++) area += scan[q] * scan[q - 1];
+    area += scan[0] * scan[n_scan - 1];
+    area *= sin(acos(-1) / 360) / 2;
+    f->vpClutter = f->vp.expectedClutterNumber / area;
+    batch_scan_clutter(f, area);
+  }
   // (the record's static part: one filler for both routes; nz 1 where the device derives pfa)
   auto fillStatic = [&](MhBatchFilter &T, int b, int nz) {
     const rfsgpu_fastslam_config &c = f->bFs[b];
-    T.F = fs_params_of(c, f->bParamsHost[b], 2, nz);
+    T.F = fs_params_of(c, f->bParamsHost[b], D, nz);
     T.pruneT = c.mapExistencePruneThreshold;
     T.kmax = (int)c.maxNDataAssocHypotheses;
     T.maxDiff = c.maxDataAssocLogLikelihoodDiff;
@@ -4342,7 +4425,17 @@ static int batch_mh_cycle_core(rfsgpu_filter *f, int predict, const double *x, c
     });
   }
   if (rc != RFSGPU_OK) return rc;
-  if (x && (rc = batch_push_poses(f, x, x_cov, cov_stride)) != RFSGPU_OK) return rc;     // (every slot of every block)
+  if (scan) {     // the host's new poses and the scan through one block of the staging ring (batch_vp_cycle_core's layout)
+    double *h = nullptr;
+    int ks = 0;
+    if ((rc = ring_acquire(f, f->stage, &h, &ks)) != RFSGPU_OK) return rc;
+    if (x && (rc = push_poses(f, h, f->B.pose, x, x_cov, cov_stride)) != RFSGPU_OK) return rc;
+    double *hs = h + (size_t)f->Ncap * 22;
+    memcpy(hs, scan, (size_t)n_scan * sizeof(double));
+    HIPCHK(hipMemcpyAsync(f->B.scan, hs, (size_t)n_scan * sizeof(double), hipMemcpyHostToDevice, f->stream));
+    f->B.nScan = n_scan;
+    HIPCHK(hipEventRecord(f->stage.ev[ks], f->stream));
+  } else if (x && (rc = batch_push_poses(f, x, x_cov, cov_stride)) != RFSGPU_OK) return rc;     // (every slot of every block)
   f->bBirthAlt = false;
   FsCycleState S0;      // filter 0's view: its slot arrays are the batch's, [N] each, holding slots local to each filter's block
   mhb_view(f, f->mhbBlock, 0, S0);
@@ -4352,13 +4445,21 @@ static int batch_mh_cycle_core(rfsgpu_filter *f, int predict, const double *x, c
   Arenorm.word = FSC_RENORM_N;
   int *dSlotHyp = f->mhcInts, *dSlotNH = dSlotHyp + N, *dDst = dSlotNH + N, *dSrc = dDst + N;
   fs_cycle_begin_batch_kernel<<<(nF + 63) / 64, 64, 0, f->stream>>>(f->mhbBlock, A, nF);
-  if (predict) fs_cycle_static_step_batch_kernel<<<(N + 3) / 4, 256, 0, f->stream>>>(f->B, f->cur, A);
-  fs_mh_associate_kernel<2><<<N, 64 * FSMH_WAVES, 0, f->stream>>>(f->B, f->P, FsParams{}, f->cur, 0, 0, 0.0, f->mhArena, A);
+  if (predict && D == 3) fs_cycle_static_step3_batch_kernel<<<(N + 3) / 4, 256, 0, f->stream>>>(f->B, f->cur, A);
+  else if (predict) fs_cycle_static_step_batch_kernel<<<(N + 3) / 4, 256, 0, f->stream>>>(f->B, f->cur, A);
+  if (D == 3) fs_mh_associate_kernel<3><<<N, 64 * FSMH_WAVES, 0, f->stream>>>(f->B, f->P, FsParams{}, f->cur, 0, 0, 0.0, f->mhArena, A);
+  else fs_mh_associate_kernel<2><<<N, 64 * FSMH_WAVES, 0, f->stream>>>(f->B, f->P, FsParams{}, f->cur, 0, 0, 0.0, f->mhArena, A);
   fs_mh_plan_batch_kernel<<<nF, FS_CYCLE_THREADS, 0, f->stream>>>(f->mhArena, f->mhbBlock, dSlotHyp, dSlotNH, dDst, dSrc, A);
-  fs_mh_copy_kernel<<<N, 256, 0, f->stream>>>(f->B, f->cur, dDst, dSrc, 0, f->P.poseCovStride, Acopy);
+  if (D == 3) {     // the lists travel with the copies of a filter whose resampleOccured_ is up, read where the kernel runs (:551-553)
+    MhBatchCopy Ac;
+    static_cast<MhBatchArg &>(Ac) = Acopy;
+    Ac.candWord = FSC_RESAMPLED;
+    fs_mh_copy_kernel<<<N, 256, 0, f->stream>>>(f->B, f->cur, dDst, dSrc, 0, f->P.poseCovStride, Ac);
+  } else fs_mh_copy_kernel<<<N, 256, 0, f->stream>>>(f->B, f->cur, dDst, dSrc, 0, f->P.poseCovStride, Acopy);
   fs_mh_split_weights_kernel<<<(N + 255) / 256, 256, 0, f->stream>>>(f->B.weight, S0.slotSrc, dSlotNH, N, 0, A);
   fs_mh_split_weights_kernel<<<(N + 255) / 256, 256, 0, f->stream>>>(f->B.weight, S0.slotSrc, dSlotNH, N, 1, A);
-  fs_mh_apply_kernel<2><<<N, 64, 0, f->stream>>>(f->B, f->P, FsParams{}, f->cur, 0, S0.slotSrc, dSlotHyp, f->mhArena, A);
+  if (D == 3) fs_mh_apply_kernel<3><<<N, 64, 0, f->stream>>>(f->B, f->P, FsParams{}, f->cur, 0, S0.slotSrc, dSlotHyp, f->mhArena, A);
+  else fs_mh_apply_kernel<2><<<N, 64, 0, f->stream>>>(f->B, f->P, FsParams{}, f->cur, 0, S0.slotSrc, dSlotHyp, f->mhArena, A);
   HIPCHK(hipGetLastError());
   // the prune of the filters that prune this cycle (:611-612); the others' mixtures -- no measurements, below their
   // pruningMeasurementsThreshold, overflowed -- move unchanged to the other slab, because the batch flips `cur` as one
@@ -4366,13 +4467,14 @@ static int batch_mh_cycle_core(rfsgpu_filter *f, int predict, const double *x, c
   if ((rc = set_lds(f, (gm_prune_kernel<4, false, true, MhBatchArg>), 4 * pb)) != RFSGPU_OK) return rc;
   gm_prune_kernel<4, false, true, MhBatchArg><<<(N + 3) / 4, 256, 4 * pb, f->stream>>>(f->B, f->P, f->cur, f->cur ^ 1, A);
   f->cur ^= 1;
-  fs_new_landmarks_kernel<2, true, MhBatchArg><<<(N + FS_NEWLM_WPB - 1) / FS_NEWLM_WPB, 64 * FS_NEWLM_WPB, 0, f->stream>>>(f->B, f->P, FsParams{}, f->cur, 0, A);
+  if (D == 3) fs_new_landmarks_kernel<3, true, MhBatchArg><<<(N + FS_NEWLM_WPB - 1) / FS_NEWLM_WPB, 64 * FS_NEWLM_WPB, 0, f->stream>>>(f->B, f->P, FsParams{}, f->cur, 0, A);
+  else fs_new_landmarks_kernel<2, true, MhBatchArg><<<(N + FS_NEWLM_WPB - 1) / FS_NEWLM_WPB, 64 * FS_NEWLM_WPB, 0, f->stream>>>(f->B, f->P, FsParams{}, f->cur, 0, A);
   // resampleWithMapCopy per filter, as rfsgpu_fastslam_cycle_async: normalisation, decision and plan, copies, and the second
   // normalisation of a resample() that returned false
   mhb_weight_sums_kernel<<<nF, 1024, 0, f->stream>>>(f->B.weight, f->dBSums, A);
   mhb_normalize_kernel<<<(N + 255) / 256, 256, 0, f->stream>>>(f->B.weight, N, f->dBSums, A);
   fs_resample_shrink_batch_kernel<<<nF, FS_CYCLE_THREADS, 0, f->stream>>>(f->B.weight, f->mhbBlock, A);
-  resample_gather_kernel<<<N, 256, 0, f->stream>>>(f->B, f->cur, S0.plan, f->P.poseCovStride, 0, A);
+  resample_gather_kernel<<<N, 256, 0, f->stream>>>(f->B, f->cur, S0.plan, f->P.poseCovStride, 0, A);     // (mapOnly 0: lists, mask and in-view count move with the particle)
   mhb_weight_sums_kernel<<<nF, 1024, 0, f->stream>>>(f->B.weight, f->dBSums, Arenorm);
   mhb_normalize_kernel<<<(N + 255) / 256, 256, 0, f->stream>>>(f->B.weight, N, f->dBSums, Arenorm);
   HIPCHK(hipGetLastError());
@@ -4550,7 +4652,7 @@ int rfsgpu_batch_set_resampling(rfsgpu_filter *f, int filter, double eff_n, doub
   CHECK_HANDLE(f);
   int rc = batch_check(f, filter);
   if (rc != RFSGPU_OK) return rc;
-  REFUSE_ON_VP_BATCH(f, "rfsgpu_batch_set_resampling");
+  if (!f->vpMh) { REFUSE_ON_VP_BATCH(f, "rfsgpu_batch_set_resampling"); }     // (the thresholds of the resampling inside its cycle, as on a 2-D multi-hypothesis batch)
   for (int b = (filter < 0 ? 0 : filter); b < (filter < 0 ? f->nF : filter + 1); b++) {
     f->bEffN[2 * (size_t)b] = eff_n; f->bEffN[2 * (size_t)b + 1] = eff_n_percent;
     f->bResSet[b] = 1;
@@ -4783,6 +4885,7 @@ int rfsgpu_batch_vp_set_resampling(rfsgpu_filter *f, int filter, double eff_n, d
   CHECK_HANDLE(f);
   int rc = vp_loop_check(f, "batch_vp_set_resampling", filter);
   if (rc != RFSGPU_OK) return rc;
+  if (f->vpMh) return fail(f, RFSGPU_ERR_UNSUPPORTED, "batch_vp_set_resampling: not available on a batch of Victoria Park multi-hypothesis FastSLAM filters (rfsgpu_create_batch_vp_mh): its resampling runs inside rfsgpu_batch_vp_fastslam_mh_cycle_async (thresholds: rfsgpu_batch_set_resampling; outcome: rfsgpu_batch_fastslam_last_cycle)");
   for (int b = (filter < 0 ? 0 : filter); b < (filter < 0 ? f->nF : filter + 1); b++) {
     f->bEffN[2 * (size_t)b] = eff_n; f->bEffN[2 * (size_t)b + 1] = eff_n_percent;
     f->bResSet[b] = 1;
@@ -4790,7 +4893,8 @@ int rfsgpu_batch_vp_set_resampling(rfsgpu_filter *f, int filter, double eff_n, d
   return RFSGPU_OK;
 }
 int rfsgpu_batch_vp_propagate_run_async(rfsgpu_filter *f, int n, const double *u, const unsigned char *noisy, const double *dt, unsigned long long call0) {
-  CHECK_HANDLE(f);
+  if (!f) return RFSGPU_ERR_INVALID;
+  if (!f->vpMh) { CHECK_HANDLE(f); }     // (a batch of multi-hypothesis filters: behind its cycles, nothing is read back)
   int rc = vp_loop_check(f, "batch_vp_propagate_run", -1);
   if (rc != RFSGPU_OK) return rc;
   if (n < 0 || (n > 0 && (!u || !dt))) return fail(f, RFSGPU_ERR_INVALID, "batch_vp_propagate_run: bad arguments");
@@ -4820,7 +4924,11 @@ int rfsgpu_batch_vp_propagate_run_async(rfsgpu_filter *f, int n, const double *u
   HIPCHK(hipMemcpyAsync(f->dBVpRun, R, sizeof *R, hipMemcpyHostToDevice, f->stream));
   HIPCHK(hipEventRecord(f->bLoop.ev[k], f->stream));
   // in place: the caller orders the call behind the birth predict, which must still see the poses of the last update
-  vp_batch_propagate_run_kernel<<<(f->N + 255) / 256, 256, 0, f->stream>>>(f->B.pose, f->N, f->nPer, f->dBVpMotion, f->dBVpRun);
+  if (f->vpMh) {     // (a filter whose overflow word is up stays where its abandoned cycle found it)
+    FsCycleState S0;
+    mhb_state(f->mhbBlock, f->nF, f->nPer, 0, S0);
+    vp_batch_propagate_run_guard_kernel<<<(f->N + 255) / 256, 256, 0, f->stream>>>(f->B.pose, f->N, f->nPer, f->dBVpMotion, f->dBVpRun, S0.w, FSC_WORDS, FSC_OVF);
+  } else vp_batch_propagate_run_kernel<<<(f->N + 255) / 256, 256, 0, f->stream>>>(f->B.pose, f->N, f->nPer, f->dBVpMotion, f->dBVpRun);
   HIPCHK(hipGetLastError());
   return RFSGPU_OK;
 }
@@ -4828,6 +4936,7 @@ int rfsgpu_batch_vp_resample_async(rfsgpu_filter *f, const int *n_z, unsigned lo
   CHECK_HANDLE(f);
   int rc = vp_loop_check(f, "batch_vp_resample", -1);
   if (rc != RFSGPU_OK) return rc;
+  if (f->vpMh) return fail(f, RFSGPU_ERR_UNSUPPORTED, "batch_vp_resample: not available on a batch of Victoria Park multi-hypothesis FastSLAM filters (rfsgpu_create_batch_vp_mh): its resampling runs inside rfsgpu_batch_vp_fastslam_mh_cycle_async (thresholds: rfsgpu_batch_set_resampling; outcome: rfsgpu_batch_fastslam_last_cycle)");
   if ((rc = batch_check_call(f, BATCH_VP_RESAMPLE, 0, nullptr, 0, n_z)) != RFSGPU_OK) return rc;
   return batch_resample_core(f, BATCH_VP_RESAMPLE, n_z, call);
 }
@@ -4835,12 +4944,14 @@ int rfsgpu_batch_vp_last_resample(rfsgpu_filter *f, unsigned char *fired, int *s
   CHECK_HANDLE(f);
   int rc = vp_loop_check(f, "batch_vp_last_resample", -1);
   if (rc != RFSGPU_OK) return rc;
+  if (f->vpMh) return fail(f, RFSGPU_ERR_UNSUPPORTED, "batch_vp_last_resample: not available on a batch of Victoria Park multi-hypothesis FastSLAM filters (rfsgpu_create_batch_vp_mh): its resampling runs inside rfsgpu_batch_vp_fastslam_mh_cycle_async (thresholds: rfsgpu_batch_set_resampling; outcome: rfsgpu_batch_fastslam_last_cycle)");
   return batch_last_resample_core(f, fired, src_slot, n_eff);
 }
 int rfsgpu_batch_vp_loop_counts(rfsgpu_filter *f, long long *resamplings, int *max_level) {
   CHECK_HANDLE(f);
   int rc = vp_loop_check(f, "batch_vp_loop_counts", -1);
   if (rc != RFSGPU_OK) return rc;
+  if (f->vpMh) return fail(f, RFSGPU_ERR_UNSUPPORTED, "batch_vp_loop_counts: not available on a batch of Victoria Park multi-hypothesis FastSLAM filters (rfsgpu_create_batch_vp_mh): its resampling runs inside rfsgpu_batch_vp_fastslam_mh_cycle_async (thresholds: rfsgpu_batch_set_resampling; outcome: rfsgpu_batch_fastslam_last_cycle)");
   hipSetDevice(f->device);
   int w[2] = {0, 0};
   if (resamplings) HIPCHK(hipMemcpyAsync(resamplings, f->BL.nResamples, (size_t)f->nF * sizeof(long long), hipMemcpyDeviceToHost, f->stream));
@@ -5189,6 +5300,7 @@ static int metric_row(rfsgpu_filter *f) {
 int rfsgpu_batch_mh_serve_metrics(rfsgpu_filter *f, int on) {
   CHECK_HANDLE(f);
   if (!f->mhBatch) return fail(f, RFSGPU_ERR_UNSUPPORTED, "batch_mh_serve_metrics: not a batch of multi-hypothesis FastSLAM filters (rfsgpu_create_batch_mh)");
+  if (f->vpMh) return fail(f, RFSGPU_ERR_UNSUPPORTED, "batch_mh_serve_metrics: the device-side map / pose error is 2-D: it does not serve a batch of Victoria Park multi-hypothesis FastSLAM filters (rfsgpu_create_batch_vp_mh)");
   hipSetDevice(f->device);
   HIPCHK(hipStreamSynchronize(f->stream));
   f->mhbMetrics = on != 0;

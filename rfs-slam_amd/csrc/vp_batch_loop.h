@@ -39,9 +39,7 @@ struct VpBatchRun {         // one call's run of odometry messages, through the 
 // One thread per global slot; every slot takes the run's steps one after the other, in place.  The filter's block of the pose array
 // is handed to ackerman_step_particle with the slot's index INSIDE the block: the counter of its draw and the address of its pose
 // are then what a handle of nPer particles has for particle i.
-__global__ __launch_bounds__(256) void vp_batch_propagate_run_kernel(double *pose, int N, int nPer, const VpBatchMotion *mot, const VpBatchRun *run) {
-  const int k = blockIdx.x * blockDim.x + threadIdx.x;
-  if (k >= N) return;
+__device__ __forceinline__ void vp_batch_propagate_run_slot(double *pose, int k, int nPer, const VpBatchMotion *mot, const VpBatchRun *run) {
   const int b = k / nPer, i = k - b * nPer;
   const VpBatchMotion M = mot[b];
   double *blk = pose + 3 * (size_t)b * nPer;
@@ -56,6 +54,22 @@ __global__ __launch_bounds__(256) void vp_batch_propagate_run_kernel(double *pos
     A.seed = M.seed; A.call = call0 + (unsigned long long)r;
     ackerman_step_particle(blk, i, A);
   }
+}
+__global__ __launch_bounds__(256) void vp_batch_propagate_run_kernel(double *pose, int N, int nPer, const VpBatchMotion *mot, const VpBatchRun *run) {
+  const int k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= N) return;
+  vp_batch_propagate_run_slot(pose, k, nPer, mot, run);
+}
+// ... of a batch of multi-hypothesis filters (rfsgpu_create_batch_vp_mh): every slot of every block moves, live or not (a slot beyond
+// its filter's count is overwritten by the copy that makes it live), except those of a filter whose overflow word is up -- it has
+// abandoned its cycle and what is enqueued behind it, as a handle's LiveCount forms do.  words: filter 0's cycle words, wordStride
+// ints per filter, ovfWord the overflow word's index (FsCycleState, fastslam_cycle.h).
+__global__ __launch_bounds__(256) void vp_batch_propagate_run_guard_kernel(double *pose, int N, int nPer, const VpBatchMotion *mot, const VpBatchRun *run,
+                                                                           const int *words, int wordStride, int ovfWord) {
+  const int k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= N) return;
+  if (words[(size_t)(k / nPer) * wordStride + ovfWord] != 0) return;
+  vp_batch_propagate_run_slot(pose, k, nPer, mot, run);
 }
 
 // The words of a batch's walk: walk[VBW_MAXEVER] the deepest level any walk has met (folded by the tail), walk[VBW_LAST] the batch's

@@ -721,3 +721,53 @@ class MHFastSLAMBatch(capi.CBatchMH):
     def live_counts(self):
         """The live particle count of every filter (synchronises)."""
         return self.batch_live_counts()
+
+
+class VPMHFastSLAMBatch(capi.CBatchVPMH):
+    """n_filters independent Victoria Park multi-hypothesis FastSLAM filters stepped together (rfsgpu_create_batch_vp_mh,
+    rfsgpu_batch_vp_fastslam_mh_cycle_async): per cycle one launch chain runs every filter's whole FastSLAM::update on the Victoria Park
+    models with each filter's live particle count on the device; landmark candidate lists of any count threshold are kept and travel
+    with the copies of a filter whose previous cycle resampled and with every resampling.  Filter b owns max_per_filter global slots
+    (block(b)) and equals a Victoria Park FastSLAM handle with max_particles = max_per_filter stepped by fastslam_cycle_full_async on
+    the same inputs.  configure(b, None, model=..., kf=..., Q=...) as on a VPFilterBatch; configure_fastslam(b, fs_cfg) with 2 ... 16
+    hypotheses; set_resampling for the N_eff thresholds; set_motion / propagate_run_async / static_steps_async between the cycles."""
+
+    def __init__(self, n_filters, n_per_filter, max_per_filter=None, device_id=0, gm_capacity=512, max_hypotheses=3):
+        # (the default stride: MHFastSLAMBatch's -- a set at nParticlesMax is not forced back and can multiply once more)
+        m = min(2048, 3 * int(n_per_filter) * max(1, int(max_hypotheses))) if max_per_filter is None else int(max_per_filter)
+        super().__init__(load_library(), "rfsgpu_", n_filters, n_per_filter, m, device_id=device_id, gm_capacity=gm_capacity)
+        self.fs_configs = [self.default_fastslam_config() for _ in range(n_filters)]
+        for c in self.fs_configs:
+            c.nParticlesMax = 3 * int(n_per_filter)          # FastSLAM.hpp:250
+            c.maxNDataAssocHypotheses = max(2, int(max_hypotheses))
+
+    def configure(self, b, cfg=None, model=None, kf=None, Q=None):
+        """Filter b's model / Kalman filter / landmark noise (see CVPBatch.batch_configure_vp)."""
+        self.batch_configure_vp(b, cfg=cfg, model=model, kf=kf, Q=Q)
+
+    def configure_fastslam(self, b, fs_cfg):
+        """Filter b's (None: every filter's) FastSlamConfig: maxNDataAssocHypotheses 2 ... 16 (1 is refused, naming the filter), any
+        landmark-candidate count threshold."""
+        self.batch_set_fastslam_config(b, fs_cfg)
+        for q in (range(self.n_filters) if b is None else [b]):
+            self.fs_configs[q] = fs_cfg
+
+    def set_motion(self, b, var, geom, seed):
+        """Filter b's (None: every filter's) input-noise variances (speed, steering), vehicle geometry (h, l, dx, dy) and Philox key."""
+        self.batch_vp_set_motion(b, var, geom, seed)
+
+    def propagate_run_async(self, u, dt, call0, noisy=None):
+        """A run of odometry messages for every slot of every block in one launch, behind the cycles in flight."""
+        self.batch_vp_propagate_run_async(u, dt, call0, noisy=noisy)
+
+    def cycle_async(self, predict, Zs, u01, poses=None, pose_cov=None, scan=None):
+        """One whole FastSLAM::update of every filter, enqueued; nothing is read back.  u01 [n_filters]: the draws a resampling would use."""
+        self.batch_vp_fastslam_mh_cycle_async(predict, Zs, u01, poses=poses, pose_cov=pose_cov, scan=scan)
+
+    def last_cycle(self):
+        """What the last cycle did, per filter (synchronises): see CBatchMH.batch_fastslam_last_cycle."""
+        return self.batch_fastslam_last_cycle()
+
+    def live_counts(self):
+        """The live particle count of every filter (synchronises)."""
+        return self.batch_live_counts()

@@ -364,6 +364,16 @@ class VictoriaParkBatchRun:
     gates are params_per_filter's min_updates / min_measurements, which the constructor writes into a batch's FastSLAM
     configurations; both resampling routes move the landmark candidate lists with the particle.  Not with log_estimates.
 
+    filter="mhfastslam": the multi-hypothesis third of the sweep (cfg/mhfastslam_VictoriaPark_artificialClutter.xml), on the device route
+    only (device_loop=False and log_estimates=True raise ValueError).  target: a VPMHFastSLAMBatch, or a list of Victoria Park FastSLAM
+    handles created with max_particles and device_cycle=True, which take the same realisations through fastslam_cycle_full_async.  Per
+    run of messages: static_steps_async, the run propagation, then one cycle (predict off, poses=None, the scan) whose resampling is
+    inside it.  Per filter and lidar message with measurements one u01 is drawn from rngs[b], behind that message's clutter draws, on
+    both kinds of target -- VictoriaParkRun's draw_every_update -- so the streams stay aligned.  The gates are params_per_filter's
+    min_updates / min_measurements and the N_eff thresholds eff_n, which the constructor writes into the batch or the handles.
+    Nothing is read until synchronize(); keep_history reads batch_fastslam_last_cycle (fastslam_last_cycle per handle) per lidar
+    message: (n_z, fired, plans in slots of the filter), and grown gets the counts after that message's update.
+
     device_loop: the run is enqueued and nothing is read until synchronize().  The artificial clutter and the measurement sets are
     still drawn on the host from seeds[b] (they depend on no device state); the poses live on the device.  Per run of messages a
     batch gets the birth cycle (no sets, at the poses the last update used), static_steps_async, one propagate_run_async (noisy = not
@@ -383,9 +393,14 @@ class VictoriaParkBatchRun:
     def __init__(self, target, data, params_per_filter, seeds, var_uv=0.2, var_ur=0.025, noise_inflation=20.0, added_clutter=3.0, eff_n=None,
                  keep_history=False, device_loop=False, log_estimates=False, log_particles=True, log_w_threshold=-np.inf, log_max_est=None,
                  filter="rbphd"):
-        if filter not in ("rbphd", "fastslam"):
-            raise ValueError("filter is 'rbphd' or 'fastslam'")
+        if filter not in ("rbphd", "fastslam", "mhfastslam"):
+            raise ValueError("filter is 'rbphd', 'fastslam' or 'mhfastslam'")
         self.fastslam = filter == "fastslam"
+        self.mh = filter == "mhfastslam"
+        if self.mh and not device_loop:
+            raise ValueError("a batch of Victoria Park multi-hypothesis FastSLAM filters runs on the device route only (device_loop=True)")
+        if self.mh and log_estimates:
+            raise ValueError("the estimate log does not serve a batch of Victoria Park multi-hypothesis FastSLAM filters")
         if self.fastslam and log_estimates:
             raise ValueError("the estimate log does not serve a batch of Victoria Park FastSLAM filters")
         self.batch = None if isinstance(target, (list, tuple)) else target
@@ -396,7 +411,7 @@ class VictoriaParkBatchRun:
         self.Ps = list(params_per_filter)
         self.mgr, self.inputs, self.meas = data["manager"], data["inputs"], data["measurements"]
         self.rngs = [np.random.default_rng(s) for s in seeds]
-        self.x = np.zeros((self.nF * self.n, 3))
+        self.x = np.zeros(((self.batch.n if self.mh and self.batch is not None else self.nF * self.n), 3))     # (mh: every slot of every block)
         self.sd = np.sqrt(np.array([var_uv, var_ur]) * noise_inflation)
         self.added_clutter = np.broadcast_to(np.asarray(added_clutter, dtype=np.float64), (self.nF,)).copy()
         self.eff_n = np.broadcast_to(np.asarray(self.n / 2.0 if eff_n is None else eff_n, dtype=np.float64), (self.nF,)).copy()
@@ -408,6 +423,7 @@ class VictoriaParkBatchRun:
         self.n_resamples = np.zeros(self.nF, dtype=np.int64)
         self.n_lidar = 0
         self.history = [] if keep_history else None
+        self.grown = []                   # mhfastslam with keep_history: every filter's count after each lidar message's update
         self._dts = []                    # the intervals of the predicts not yet issued (the first of a run adds the births)
         self.device_loop = bool(device_loop)
         if self.fastslam and self.batch is not None:      # the batch's gates (update_and_resample, resample_async) are its FastSLAM configurations'
@@ -416,6 +432,17 @@ class VictoriaParkBatchRun:
                 cfg.minUpdatesBeforeResample = int(self.Ps[b]["min_updates"])
                 cfg.minMeasurementsBeforeResample = int(self.Ps[b]["min_measurements"])
                 self.batch.configure_fastslam(b, cfg)
+        if self.mh:                       # the gates and N_eff thresholds of the resampling inside the cycle
+            for b in range(self.nF):
+                cfg = self.batch.fs_configs[b] if self.batch is not None else self.handles[b].fs_config
+                cfg.minUpdatesBeforeResample = int(self.Ps[b]["min_updates"])
+                cfg.minMeasurementsBeforeResample = int(self.Ps[b]["min_measurements"])
+                if self.batch is not None:
+                    self.batch.configure_fastslam(b, cfg)
+                else:
+                    f = self.handles[b]
+                    f.set_fastslam_config(cfg)
+                    f.effNParticles_t, f.effNParticles_t_percent = float(self.eff_n[b]), float(self.eff_n[b] / self.n)
         self.seeds = [int(s) for s in seeds]
         self.var = np.array([var_uv, var_ur]) * noise_inflation
         self._run = []                    # device_loop: (uv, ur, noisy) of the predicts not yet issued
@@ -430,7 +457,7 @@ class VictoriaParkBatchRun:
                 self.batch.set_poses(self.x, None)
             else:
                 for b, f in enumerate(self.handles):
-                    f.set_poses(self.x[self._block(b)], None)
+                    f.set_poses(self.x[self._block(b)] if not self.mh else np.zeros((f.n, 3)), None)
         self.log_estimates, self.log_particles, self.log_w_threshold = bool(log_estimates), bool(log_particles), float(log_w_threshold)
         self.log_max_est = None if log_max_est is None else int(log_max_est)
         if self.log_estimates:
@@ -526,7 +553,7 @@ class VictoriaParkBatchRun:
         self._run = []
         call0 = self._n_calls
         self._n_calls += len(r)
-        if self.fastslam:
+        if self.fastslam or self.mh:
             var = r[:, 2:3] * self.var[None, :]
             for b, f in enumerate(self._targets()):
                 f.static_steps_async(len(q), q)
@@ -536,7 +563,14 @@ class VictoriaParkBatchRun:
                 for k0 in range(0, len(r), VP_BATCH_RUN_MAX):
                     k1 = min(len(r), k0 + VP_BATCH_RUN_MAX)
                     f.propagate_run_async(r[k0:k1, 0:2], dts[k0:k1], call0 + k0, noisy=r[k0:k1, 2] != 0)
-            if Zs is not None:
+            if Zs is not None and self.mh:
+                u01 = np.array([float(self.rngs[b].uniform()) if len(Zs[b]) else 0.5 for b in range(self.nF)])
+                if self.batch is not None:
+                    self.batch.cycle_async(False, Zs, u01, poses=None, scan=self.scan)
+                else:
+                    for b, f in enumerate(self.handles):
+                        f.cycle_async(Zs[b], u01[b], predict=False, scan=self.scan, push_config=self.n_lidar == 0)
+            elif Zs is not None:
                 self._update_fastslam(Zs, None)
             return
         if self.batch is not None:
@@ -582,6 +616,16 @@ class VictoriaParkBatchRun:
         """device_loop: a batch resamples on the device (nothing is read unless the history is kept); the handles' decision is made
         here by the rule the device states -- squares added in slot order, the draw of (seeds[b], lidar index)."""
         call = self.n_lidar - 1
+        if self.mh:                       # (the resampling ran inside the cycle; the history is the one read)
+            if self.history is None:
+                return None, None
+            if self.batch is not None:
+                lc = self.batch.last_cycle()
+                self.grown.append(lc["n_after_update"].copy())
+                return lc["fired"].copy(), [lc["plan"][b, :lc["n_after_resample"][b]].copy() for b in range(self.nF)]
+            lcs = [f.fastslam_last_cycle() for f in self.handles]
+            self.grown.append(np.array([l["n_after_update"] for l in lcs], dtype=np.int32))
+            return np.array([l["fired"] for l in lcs]), [l["plan"] for l in lcs]
         if self.batch is not None:
             self.batch.resample_async(n_z, call)
             if self.history is None:
@@ -695,7 +739,8 @@ class VictoriaParkBatchRun:
         if self.device_loop:              # the poses (and a batch's counts) are the device's: the one read at the end
             if self.batch is not None:
                 self.x = self.batch.get_poses()
-                self.n_resamples = self.batch.loop_counts()[0]
+                if not self.mh:
+                    self.n_resamples = self.batch.loop_counts()[0]
             else:
                 self.x = np.concatenate([f.get_poses() for f in self.handles], 0)
 

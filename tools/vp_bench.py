@@ -9,6 +9,11 @@
   python tools/vp_bench.py --batch B --fastslam [--device-loop] [...]
       The FastSLAM half of the sweep: a VPFastSLAMBatch (rfsgpu_batch_vp_fastslam_cycle_async) against B FastSLAM handles stepped in
       turn, through VictoriaParkBatchRun(filter="fastslam"); the routes and the JSON fields of the RB-PHD forms.
+  python tools/vp_bench.py --batch B --mhfastslam --device-loop [...]
+      The multi-hypothesis third of the sweep (cfg/mhfastslam_VictoriaPark_artificialClutter.xml: 3 hypotheses, window 3.0, candidate
+      count threshold 4, minTimesteps 2, minMeasurements 15): a VPMHFastSLAMBatch (rfsgpu_batch_vp_fastslam_mh_cycle_async) against B
+      FastSLAM handles on rfsgpu_fastslam_cycle_full_async stepped in turn, through VictoriaParkBatchRun(filter="mhfastslam"), which
+      has the device route only: the routes are handles and batch_dev.
   python tools/vp_bench.py --batch B --device-loop [...]
       Three routes, alternating: the host-stop batch, the device-loop batch (VictoriaParkBatchRun(device_loop=True): propagation, the
       resampling tail and the inheritance walk on the device, nothing read until the end) and the handles in turn under the device
@@ -56,6 +61,53 @@ def fastslam_sweep_config(f, P):
     cfg.minUpdatesBeforeResample = int(P["min_updates"])
     cfg.minMeasurementsBeforeResample = int(P["min_measurements"])
     return cfg
+
+
+MH_HYPOTHESES = 3
+
+
+def mh_sweep_config(cfg, P, n):
+    """The multi-hypothesis third of the sweep: fastslam_sweep_config's lists, three hypotheses inside a window of 3.0."""
+    cfg.maxNDataAssocHypotheses = MH_HYPOTHESES
+    cfg.maxDataAssocLogLikelihoodDiff = 3.0
+    cfg.nParticlesMax = 3 * n
+    cfg.landmarkCandidateMeasurementCountThreshold = 4
+    cfg.landmarkCandidateMeasurementCheckThreshold = 6
+    cfg.landmarkCandidateCurrentMeasurementCountThreshold = 0
+    cfg.landmarkCandidateMeasurementSupportDist = 3.0
+    return cfg
+
+
+def mh_one_run(route, nF, n, data, messages, cap):
+    Ps, seeds, clutter = batch_sweep(nF)
+    for P in Ps:
+        P["min_updates"], P["min_measurements"] = 2, 15
+    if route == "batch_dev":
+        target = pkg.VPMHFastSLAMBatch(nF, n, gm_capacity=cap, max_hypotheses=MH_HYPOTHESES)
+        for b in range(nF):
+            sc.apply_vp_batch_params(target, b, Ps[b])
+            target.configure_fastslam(b, mh_sweep_config(target.fs_configs[b], Ps[b], n))
+        target.synchronize()
+        owned = [target]
+        live = lambda: [np.asarray(target.gm_sizes())[target.block(b, c)] for b, c in enumerate(target.live_counts())]
+    else:
+        stride = min(2048, 3 * n * MH_HYPOTHESES)
+        target = [pkg.FastSLAM(n, gm_capacity=cap, max_hypotheses=MH_HYPOTHESES, device_cycle=True, max_particles=stride,
+                               model=pkg.capi.MODEL_VICTORIAPARK_3D) for _ in range(nF)]
+        for b, h in enumerate(target):
+            sc.apply_vp_params(h, Ps[b], np.full(361, 70.0))
+            h.config = h.get_filter_config()
+            mh_sweep_config(h.fs_config, Ps[b], n)
+            h.synchronize()
+        owned = target
+        live = lambda: [h.gm_sizes() for h in target]
+    t0 = time.perf_counter()
+    r = pkg.vp_driver.VictoriaParkBatchRun(target, data, Ps, seeds, added_clutter=clutter, device_loop=True, filter="mhfastslam").run(n_messages=messages)
+    dt = time.perf_counter() - t0
+    info = (int(r.n_lidar), -1, float(np.mean(np.concatenate(live()))))      # (the resamplings are counted on the device and not read)
+    for h in owned:
+        h.close()
+    return dt, info
 
 
 def batch_one_run(route, nF, n, data, messages, cap, device_loop=False, fastslam=False):
@@ -179,20 +231,26 @@ def batch_main():
     ap.add_argument("--capacity", type=int, default=384)      # (192 is transiently short under the heaviest clutter of the sweep)
     ap.add_argument("--device-loop", action="store_true")
     ap.add_argument("--fastslam", action="store_true")
+    ap.add_argument("--mhfastslam", action="store_true")
     a = ap.parse_args()
+    if a.mhfastslam and not a.device_loop:
+        ap.error("--mhfastslam runs on the device route only: add --device-loop")
     data = np.load(os.path.join(ROOT, "tests", "golden", "victoria_park_extract.npz"))
-    routes = [a.only] if a.only else (["handles", "batch", "batch_dev"] if a.device_loop else ["handles", "batch"])
+    routes = [a.only] if a.only else (["handles", "batch_dev"] if a.mhfastslam else (["handles", "batch", "batch_dev"] if a.device_loop else ["handles", "batch"]))
     times = {r: [] for r in routes}
     for rep in range(a.reps + 1):                     # (the first repetition warms up: code objects, allocations)
         for route in routes:
-            dt, info = batch_one_run(route, a.batch, a.particles, data, a.messages, a.capacity, a.device_loop, a.fastslam)
+            if a.mhfastslam:
+                dt, info = mh_one_run(route, a.batch, a.particles, data, a.messages, a.capacity)
+            else:
+                dt, info = batch_one_run(route, a.batch, a.particles, data, a.messages, a.capacity, a.device_loop, a.fastslam)
             if rep:
                 times[route].append(dt)
             print("  %-9s rep %d%s: %.4f s for %d filters (%d lidar updates, %d resamplings, mean map size %.1f)" %
                   ((route, rep, "" if rep else " (warm-up)", dt, a.batch) + info), flush=True)
     out = dict(tool="vp_bench", filters=a.batch, particles=a.particles, messages=a.messages, reps=a.reps, device_loop=bool(a.device_loop))
-    if a.fastslam:
-        out["filter"] = "fastslam"
+    if a.fastslam or a.mhfastslam:
+        out["filter"] = "mhfastslam" if a.mhfastslam else "fastslam"
     for r in routes:
         med = float(np.median(times[r]))
         out[r + "_s"] = med
