@@ -37,6 +37,7 @@
 #include "birth_walk.h"
 #include "vp_batch.h"
 #include "vp_batch_loop.h"
+#include "scan_fov.h"
 
 namespace {
 
@@ -54,6 +55,11 @@ struct PinnedRing {
   int depth = 4, next = 0;   // blocks in use (4 or 8), cursor
   size_t bytes = 0;          // of one block (set where the handle is created)
 };
+
+// What a filter batch steps.  A 2-D batch is created undecided and its first cycle call (or rfsgpu_batch_set_fastslam_config) decides
+// for good; a Victoria Park batch is created stepping RB-PHD filters and rfsgpu_batch_vp_serve_fastslam moves it until a cycle has
+// run; rfsgpu_create_batch_mh / _vp_mh create the multi-hypothesis kinds.
+enum BatchSteps { STEPS_UNDECIDED = 0, STEPS_RBPHD, STEPS_FASTSLAM, STEPS_MH };
 
 }  // namespace
 
@@ -272,16 +278,13 @@ struct rfsgpu_filter {
   double *dTruthSeen = nullptr;                // [nF][SENSOR_MAX_LANDMARKS]
   int *dTruthCounts = nullptr;                 // [nF][2]
   // a batch of FastSLAM filters (rfsgpu_batch_fastslam_cycle_async; fastslam.h FsBatchArg)
-  int bKind = 0;                               // what the batch steps: 0 not decided yet, 1 RB-PHD filters, 2 FastSLAM filters (the first cycle call decides), 3 multi-hypothesis FastSLAM filters (rfsgpu_create_batch_mh decides)
+  BatchSteps bSteps = STEPS_UNDECIDED;         // what the batch steps; with D (the model) and bStepsLocked, all there is to its kind: the predicates and transitions below the struct
+  bool bStepsLocked = false;                   // bSteps no longer moves
   std::vector<rfsgpu_fastslam_config> bFs;     // [nF]
-  bool bVpFastSlam = false;                    // rfsgpu_batch_vp_serve_fastslam: this batch of Victoria Park filters steps FastSLAM filters (bKind 2)
-  bool bVpRbphdRan = false, bVpFsRan = false;  // a cycle of either kind has run on a batch of Victoria Park filters: the switch no longer moves
   std::vector<Params> bParamsHost;             // [nF] the device Params table as last written (each filter's pfa comes from its own model)
   FsBatchFilter *dFsFilt = nullptr;            // [nF]
   // a batch of multi-hypothesis FastSLAM filters (rfsgpu_create_batch_mh; fastslam_cycle.h): nPer is the stride max_per_filter, every
   // filter has its own cycle block on the device and its live count is a word of it
-  bool mhBatch = false;
-  bool vpMh = false;                           // ... of Victoria Park filters (rfsgpu_create_batch_vp_mh; its cycle is rfsgpu_batch_vp_fastslam_mh_cycle_async)
   int nInitPer = 0;                            // n_per_filter: the count a filter starts with and a resampling brings it back to
   unsigned char *mhbBlock = nullptr;           // device: nF cycle blocks of fs_cycle_state_bytes(nPer) bytes
   unsigned char *hMhbBlock = nullptr;          // pinned: where they land when the host next synchronises
@@ -314,6 +317,49 @@ struct rfsgpu_filter {
   bool estServeVpBatch = false;                         // rfsgpu_batch_vp_serve_estimates: the [estimate] log calls serve this batch of Victoria Park filters
   bool groupShard = false;                       // a shard of an rfsgpu_group: the [metric] calls refuse
 };
+
+// ---- the kind of a filter batch: bSteps, bStepsLocked and D (the model).  What the code asks of it ...
+static inline bool batch_is_vp(const rfsgpu_filter *f) { return f->batch && f->D == 3; }     // a batch of Victoria Park filters, whatever it steps
+static inline bool batch_is_mh(const rfsgpu_filter *f) { return f->bSteps == STEPS_MH; }      // multi-hypothesis filters, either model: a filter's live count is a word of its cycle block
+static inline bool batch_fills_blocks(const rfsgpu_filter *f) { return !batch_is_mh(f); }     // every filter fills its block
+static inline bool batch_is_vp_fastslam(const rfsgpu_filter *f) { return batch_is_vp(f) && f->bSteps == STEPS_FASTSLAM; }
+static inline bool batch_is_vp_mh(const rfsgpu_filter *f) { return batch_is_vp(f) && batch_is_mh(f); }
+// (resample_gather_kernel's mapOnly: the candidate lists, the mask and the in-view count travel with the particle only on a batch of
+//  Victoria Park FastSLAM filters -- a 2-D FastSLAM batch keeps no lists)
+static inline int batch_map_only(const rfsgpu_filter *f) { return batch_is_vp_fastslam(f) ? 0 : 1; }
+static inline bool batch_log_odds(const rfsgpu_filter *f) { return f->bSteps == STEPS_FASTSLAM || f->bSteps == STEPS_MH; }
+// ... and how it moves.  rfsgpu_create_batch: a Victoria Park batch steps RB-PHD filters until its switch says otherwise
+static inline void batch_born(rfsgpu_filter *f) { f->bSteps = f->D == 3 ? STEPS_RBPHD : STEPS_UNDECIDED; }
+// A 2-D batch's first cycle call, or rfsgpu_batch_set_fastslam_config: decides an undecided batch for good and moves no other (the
+// caller has refused a batch of another kind under its own wording)
+static inline void batch_decide(rfsgpu_filter *f, BatchSteps s) {
+  if (f->bSteps == STEPS_UNDECIDED) { f->bSteps = s; f->bStepsLocked = true; }
+}
+// rfsgpu_batch_vp_serve_fastslam moves a Victoria Park batch between RB-PHD and FastSLAM filters until a cycle of either kind has run
+static inline bool batch_vp_may_step(const rfsgpu_filter *f, BatchSteps s) { return !f->bStepsLocked || f->bSteps == s; }
+static inline void batch_vp_cycle_ran(rfsgpu_filter *f) { f->bStepsLocked = true; }
+// rfsgpu_create_batch_mh, rfsgpu_create_batch_vp_mh: a kind of its own from creation
+static inline void batch_born_mh(rfsgpu_filter *f) { f->bSteps = STEPS_MH; f->bStepsLocked = true; }
+// What a handle is and the cycle call that serves it: the tail of every "..., not <this>" and "not available on <this>" refusal
+static const char *handle_kind_text(const rfsgpu_filter *f) {
+  if (!f->batch)
+    return f->groupShard ? "a shard of an rfsgpu_group (the rfsgpu_group_* calls step it)"
+                         : "an ordinary handle (rfsgpu_cycle_async or rfsgpu_rbphd_cycle_async; with rfsgpu_set_fastslam_config, rfsgpu_fastslam_update or rfsgpu_fastslam_cycle_full_async)";
+  if (f->D == 3) {
+    if (f->bSteps == STEPS_MH) return "a batch of Victoria Park multi-hypothesis FastSLAM filters (rfsgpu_create_batch_vp_mh; its cycle is rfsgpu_batch_vp_fastslam_mh_cycle_async)";
+    if (f->bSteps == STEPS_FASTSLAM)
+      return "a batch of Victoria Park FastSLAM filters (rfsgpu_create_batch with RFSGPU_MODEL_VICTORIAPARK_3D, rfsgpu_batch_vp_serve_fastslam on; its cycle is rfsgpu_batch_vp_fastslam_cycle_async)";
+    return "a batch of Victoria Park RB-PHD filters (rfsgpu_create_batch with RFSGPU_MODEL_VICTORIAPARK_3D; its cycle is rfsgpu_batch_vp_cycle_async)";
+  }
+  switch (f->bSteps) {
+    case STEPS_MH: return "a 2-D batch of multi-hypothesis FastSLAM filters (rfsgpu_create_batch_mh; its cycle is rfsgpu_batch_fastslam_mh_cycle_async)";
+    case STEPS_FASTSLAM: return "a 2-D batch of FastSLAM filters (rfsgpu_create_batch, then rfsgpu_batch_set_fastslam_config; its cycle is rfsgpu_batch_fastslam_cycle_async)";
+    case STEPS_RBPHD: return "a 2-D batch of RB-PHD filters (rfsgpu_create_batch; its cycle is rfsgpu_batch_cycle_async)";
+    default: break;
+  }
+  return "a 2-D batch whose kind is not decided yet (rfsgpu_create_batch; rfsgpu_batch_cycle_async makes it a batch of RB-PHD filters, rfsgpu_batch_set_fastslam_config or "
+         "rfsgpu_batch_fastslam_cycle_async a batch of FastSLAM filters)";
+}
 
 #define HIPCHK(call)                                                                       \
   do {                                                                                     \
@@ -364,6 +410,19 @@ static int fail(rfsgpu_filter *f, int code, const char *msg) {
   f->err = msg;
   return code;
 }
+// "<what> is not available on <what this handle is>: <why>", for the calls that a kind of batch does not have
+static int refuse_on_kind(rfsgpu_filter *f, const char *what, const char *why) {
+  f->err = std::string(what) + " is not available on " + handle_kind_text(f) + ": " + why;
+  return RFSGPU_ERR_UNSUPPORTED;
+}
+// "<who>: <what the call serves>, not <what this handle is>[<hint>]", for the calls that belong to one kind of handle
+static int refuse_not(rfsgpu_filter *f, const char *head, const char *hint = "") {
+  f->err = std::string(head) + ", not " + handle_kind_text(f) + hint;
+  return RFSGPU_ERR_UNSUPPORTED;
+}
+static const char ON_BATCH[] = "a filter batch takes the rfsgpu_batch_* calls";
+static const char ON_MH_BATCH[] = "the call assumes that every filter fills its block";     // (!batch_fills_blocks)
+static const char ON_VP_BATCH[] = "a batch of Victoria Park filters is configured, stepped and resampled by the rfsgpu_batch_vp_* calls";
 
 // The next block of a pinned ring (created on first use): waits until whatever was enqueued from it one turn of the ring ago is done.
 // The caller writes into *h, enqueues its host-to-device copies (or the kernels that read the block in place) on the stream and
@@ -430,65 +489,69 @@ __global__ __launch_bounds__(64) void partition_tables_kernel(const double *L, c
 }
 
 static void batch_set_all(rfsgpu_filter *f);
-static void batch_scan_clutter(rfsgpu_filter *f, double area);
-#define REFUSE_ON_BATCH(f, what)                                                                                                   \
-  if ((f)->batch) return fail(f, RFSGPU_ERR_UNSUPPORTED, what " is not available on a filter batch (rfsgpu_create_batch): use the rfsgpu_batch_* calls")
-
-// (the calls that assume that every filter of a batch fills its block)
-#define REFUSE_ON_MH_BATCH(f, what)                                                                                                 \
-  if ((f)->mhBatch) return fail(f, RFSGPU_ERR_UNSUPPORTED, what " is not available on a batch of multi-hypothesis FastSLAM filters (rfsgpu_create_batch_mh): it assumes that every filter fills its block")
-
-// (what a batch of Victoria Park filters does not have yet: its cycle is rfsgpu_batch_vp_cycle_async on the host-stop route)
-#define REFUSE_ON_VP_BATCH(f, what)                                                                                                  \
-  if ((f)->batch && (f)->D == 3) return fail(f, RFSGPU_ERR_UNSUPPORTED, what " is not available on a batch of Victoria Park filters (rfsgpu_create_batch with RFSGPU_MODEL_VICTORIAPARK_3D): it steps by rfsgpu_batch_vp_cycle_async, with propagation, gate and resampling on the host")
-
 static std::string batch_error_note(rfsgpu_filter *f, int e);
-static void rebuild_params(rfsgpu_filter *f) {
-  Params &P = f->P;
-  P.denseIntensity = f->denseIntensity ? 1 : 0;
-  P.gateIndex = f->gateIndex ? 1 : 0;
-  for (int k = 0; k < 4; k++) P.R[k] = f->rb.R[k];
-  P.Pd = f->rb.probabilityOfDetection;
-  P.clutter = f->rb.uniformClutterIntensity;
-  P.rmax = f->rb.rangeLimMax;
-  P.rmin = f->rb.rangeLimMin;
-  P.rbuf = f->rb.rangeLimBuffer;
+// The Params of one filter from its configuration: a function of its arguments.  The fields it does not set (poseCovStride,
+// exactPartitions, ...) stay what P holds.  Q: the landmark process noise, D x D row-major.
+static void rebuild_params(Params &P, const rfsgpu_filter_config &cfg, const rfsgpu_rngbrg_config &rb, const rfsgpu_kf_config &kf, const double *Qlm,
+                           const rfsgpu_vp_config &vp, double vpClutter, int D, bool denseIntensity, bool gateIndex) {
+  P.denseIntensity = denseIntensity ? 1 : 0;
+  P.gateIndex = gateIndex ? 1 : 0;
+  for (int k = 0; k < 4; k++) P.R[k] = rb.R[k];
+  P.Pd = rb.probabilityOfDetection;
+  P.clutter = rb.uniformClutterIntensity;
+  P.rmax = rb.rangeLimMax;
+  P.rmin = rb.rangeLimMin;
+  P.rbuf = rb.rangeLimBuffer;
   P.rmaxIn = P.rmax - P.rbuf; P.rmaxOut = P.rmax + P.rbuf; P.rminIn = P.rmin + P.rbuf; P.rminOut = P.rmin - P.rbuf;
-  P.kfRange = f->kf.rangeInnovationThreshold;
-  P.kfBearing = f->kf.bearingInnovationThreshold;
-  P.birthW = f->cfg.birthGaussianWeight;
-  P.newGaussMd2 = f->cfg.newGaussianCreateInnovMDThreshold * f->cfg.newGaussianCreateInnovMDThreshold;
-  P.evalMinW = f->cfg.importanceWeightingEvalPointGuassianWeight;
-  P.weightingMd2 = f->cfg.importanceWeightingMeasurementLikelihoodMDThreshold * f->cfg.importanceWeightingMeasurementLikelihoodMDThreshold;
-  P.mergeT2 = f->cfg.gaussianMergingThreshold * f->cfg.gaussianMergingThreshold;
-  P.mergeInfl = f->cfg.gaussianMergingCovarianceInflationFactor;
-  P.pruneT = f->cfg.gaussianPruningThreshold;
-  if (f->D == 2) {
-    P.Qlm[0] = f->Qlm[0];
-    P.Qlm[1] = f->Qlm[1];
-    P.Qlm[2] = f->Qlm[3];
+  P.kfRange = kf.rangeInnovationThreshold;
+  P.kfBearing = kf.bearingInnovationThreshold;
+  P.birthW = cfg.birthGaussianWeight;
+  P.newGaussMd2 = cfg.newGaussianCreateInnovMDThreshold * cfg.newGaussianCreateInnovMDThreshold;
+  P.evalMinW = cfg.importanceWeightingEvalPointGuassianWeight;
+  P.weightingMd2 = cfg.importanceWeightingMeasurementLikelihoodMDThreshold * cfg.importanceWeightingMeasurementLikelihoodMDThreshold;
+  P.mergeT2 = cfg.gaussianMergingThreshold * cfg.gaussianMergingThreshold;
+  P.mergeInfl = cfg.gaussianMergingCovarianceInflationFactor;
+  P.pruneT = cfg.gaussianPruningThreshold;
+  if (D == 2) {
+    P.Qlm[0] = Qlm[0];
+    P.Qlm[1] = Qlm[1];
+    P.Qlm[2] = Qlm[3];
     P.twoPiPowD = pow(2 * acos(-1), 2);
   } else {
-    P.Qlm6[0] = f->Qlm[0]; P.Qlm6[1] = f->Qlm[1]; P.Qlm6[2] = f->Qlm[2];
-    P.Qlm6[3] = f->Qlm[4]; P.Qlm6[4] = f->Qlm[5]; P.Qlm6[5] = f->Qlm[8];
+    P.Qlm6[0] = Qlm[0]; P.Qlm6[1] = Qlm[1]; P.Qlm6[2] = Qlm[2];
+    P.Qlm6[3] = Qlm[4]; P.Qlm6[4] = Qlm[5]; P.Qlm6[5] = Qlm[8];
     P.twoPiPowD = pow(2 * acos(-1), 3);
-    for (int k = 0; k < 9; k++) P.R9[k] = f->vp.R[k];
-    P.R[0] = f->vp.R[0]; P.R[1] = f->vp.R[1]; P.R[2] = f->vp.R[3]; P.R[3] = f->vp.R[4];  // 2x2 range-bearing block
-    P.Slb = f->vp.Slb;
-    for (int k = 0; k < RFSGPU_VP_MAX_PD; k++) P.PdTable[k] = f->vp.PdTable[k];
-    P.nPd = f->vp.nPd;
-    P.vpClutter = f->vpClutter;
-    P.vpExpClutter = f->vp.expectedClutterNumber;
-    P.rmax = f->vp.rangeLimMax; P.rmin = f->vp.rangeLimMin;
-    P.bmax = f->vp.bearingLimitMax; P.bmin = f->vp.bearingLimitMin;
-    P.bufferPd = f->vp.bufferZonePd;
+    for (int k = 0; k < 9; k++) P.R9[k] = vp.R[k];
+    P.R[0] = vp.R[0]; P.R[1] = vp.R[1]; P.R[2] = vp.R[3]; P.R[3] = vp.R[4];  // 2x2 range-bearing block
+    P.Slb = vp.Slb;
+    for (int k = 0; k < RFSGPU_VP_MAX_PD; k++) P.PdTable[k] = vp.PdTable[k];
+    P.nPd = vp.nPd;
+    P.vpClutter = vpClutter;
+    P.vpExpClutter = vp.expectedClutterNumber;
+    P.rmax = vp.rangeLimMax; P.rmin = vp.rangeLimMin;
+    P.bmax = vp.bearingLimitMax; P.bmin = vp.bearingLimitMin;
+    P.bufferPd = vp.bufferZonePd;
   }
-  P.birthCheckThr = f->cfg.birthGaussianMeasurementCheckThreshold;
-  P.birthSupportD2 = f->cfg.birthGaussianMeasurementSupportDist * f->cfg.birthGaussianMeasurementSupportDist;
-  P.evalCount = f->cfg.importanceWeightingEvalPointCount;
-  P.useCluster = f->cfg.useClusterProcess ? 1 : 0;
-  P.birthCountThr = f->cfg.birthGaussianMeasurementCountThreshold;
-  P.birthCurThr = f->cfg.birthGaussianCurrentMeasurementCountThreshold;
+  P.birthCheckThr = cfg.birthGaussianMeasurementCheckThreshold;
+  P.birthSupportD2 = cfg.birthGaussianMeasurementSupportDist * cfg.birthGaussianMeasurementSupportDist;
+  P.evalCount = cfg.importanceWeightingEvalPointCount;
+  P.useCluster = cfg.useClusterProcess ? 1 : 0;
+  P.birthCountThr = cfg.birthGaussianMeasurementCountThreshold;
+  P.birthCurThr = cfg.birthGaussianCurrentMeasurementCountThreshold;
+}
+// ... of a handle, from its own members
+static void rebuild_params(rfsgpu_filter *f) {
+  rebuild_params(f->P, f->cfg, f->rb, f->kf, f->Qlm, f->vp, f->vpClutter, f->D, f->denseIntensity, f->gateIndex);
+}
+// setLaserScan's clutter density, expectedClutterNumber over the scan's field-of-view area: the handle's and, on a batch of Victoria
+// Park filters, every filter's from its own expectedClutterNumber as it is configured now (a later rfsgpu_batch_configure_vp leaves
+// it until the next scan, as the handle's setter does).  One scan for the handle; a batch's densities travel in its Params table.
+static void scan_clutter(rfsgpu_filter *f, const double *scan, int n) {
+  const double area = scan_fov_area(scan, n);
+  f->vpClutter = f->vp.expectedClutterNumber / area;
+  if (!f->batch) return;
+  for (int b = 0; b < f->nF; b++) f->bVpClutter[b] = f->bVp[b].expectedClutterNumber / area;
+  f->bParamsDirty = true;
 }
 
 static int check_device_errors(rfsgpu_filter *f) {
@@ -745,7 +808,7 @@ int rfsgpu_murty_partition_sums(rfsgpu_filter *f, const double *mats, const int 
 int rfsgpu_partition_likelihoods(rfsgpu_filter *f, const double *L, const double *pd, const int *nE, const int *nZ, int n_tables, double clutter,
                                  double *out) {
   CHECK_HANDLE(f);
-  REFUSE_ON_BATCH(f, "rfsgpu_partition_likelihoods");
+  if (f->batch) return refuse_on_kind(f, "rfsgpu_partition_likelihoods", ON_BATCH);
   if (!L || !pd || !nE || !nZ || !out || n_tables < 1 || n_tables > f->N) return fail(f, RFSGPU_ERR_INVALID, "partition_likelihoods: bad arguments");
   std::vector<int> dims((size_t)n_tables * 4);
   size_t offL = 0, offPd = 0;
@@ -805,7 +868,7 @@ int rfsgpu_set_model_rngbrg(rfsgpu_filter *f, const rfsgpu_rngbrg_config *c) {
 }
 int rfsgpu_set_model_victoriapark(rfsgpu_filter *f, const rfsgpu_vp_config *c) {
   CHECK_HANDLE(f);
-  if (f->batch && f->D != 3) { REFUSE_ON_BATCH(f, "the Victoria Park model"); }
+  if (f->batch && !batch_is_vp(f)) return refuse_on_kind(f, "the Victoria Park model", ON_BATCH);
   if (!c) return RFSGPU_ERR_INVALID;
   if (f->model != RFSGPU_MODEL_VICTORIAPARK_3D) return fail(f, RFSGPU_ERR_INVALID, "set_model_victoriapark on a handle created for another model");
   if (c->nPd < 1 || c->nPd > RFSGPU_VP_MAX_PD) return fail(f, RFSGPU_ERR_INVALID, "Pd table size out of range");
@@ -821,15 +884,10 @@ int rfsgpu_set_model_victoriapark(rfsgpu_filter *f, const rfsgpu_vp_config *c) {
 // intensity are a 361-term host sum; the raw scan goes to the device for the occlusion-based Pd.
 int rfsgpu_set_laser_scan(rfsgpu_filter *f, const double *scan, int n) {
   CHECK_HANDLE(f);
-  if (f->batch && f->D != 3) { REFUSE_ON_BATCH(f, "rfsgpu_set_laser_scan"); }
+  if (f->batch && !batch_is_vp(f)) return refuse_on_kind(f, "rfsgpu_set_laser_scan", ON_BATCH);
   if (f->model != RFSGPU_MODEL_VICTORIAPARK_3D) return fail(f, RFSGPU_ERR_INVALID, "set_laser_scan needs the Victoria Park model");
   if (!scan || n < 2 || n > RFSGPU_VP_MAX_SCAN) return fail(f, RFSGPU_ERR_INVALID, "laser scan size out of range");
-  double area = 0;
-  for (int k = 1; k < n; k++) area += scan[k] * scan[k - 1];
-  area += scan[0] * scan[n - 1];
-  area *= sin(acos(-1) / 360) / 2;
-  f->vpClutter = f->vp.expectedClutterNumber / area;
-  if (f->batch) batch_scan_clutter(f, area);     // (one scan for the handle, each filter's density from its own expectedClutterNumber)
+  scan_clutter(f, scan, n);
   hipSetDevice(f->device);
   HIPCHK(hipMemcpyAsync(f->B.scan, scan, (size_t)n * sizeof(double), hipMemcpyHostToDevice, f->stream));
   HIPCHK(hipStreamSynchronize(f->stream));
@@ -1070,7 +1128,7 @@ int rfsgpu_export_birth_candidates(rfsgpu_filter *f, int slot, int max_n, int *n
 }
 int rfsgpu_import_birth_candidates(rfsgpu_filter *f, int slot, int n, const double *mean, const double *cov, const int *n_support, const int *n_checks) {
   CHECK_HANDLE(f);
-  if (f->batch && f->D != 3) { REFUSE_ON_BATCH(f, "rfsgpu_import_birth_candidates"); }
+  if (f->batch && !batch_is_vp(f)) return refuse_on_kind(f, "rfsgpu_import_birth_candidates", ON_BATCH);
   if (slot < 0 || slot >= f->N || n < 0 || n > RFSGPU_MAX_CANDIDATES) return fail(f, RFSGPU_ERR_INVALID, "import_birth_candidates: bad arguments");
   hipSetDevice(f->device);
   if (n > 0) f->candUsed = true;
@@ -1246,7 +1304,7 @@ static int stage_measurements(rfsgpu_filter *f, const double *z, int n_z) {
 
 int rfsgpu_update_map(rfsgpu_filter *f, const double *z, int n_z) {
   CHECK_HANDLE(f);
-  REFUSE_ON_BATCH(f, "rfsgpu_update_map");
+  if (f->batch) return refuse_on_kind(f, "rfsgpu_update_map", ON_BATCH);
   long long t0 = now_ns();
   int rc = stage_measurements(f, z, n_z);
   if (rc != RFSGPU_OK) return rc;
@@ -1261,7 +1319,7 @@ int rfsgpu_update_map(rfsgpu_filter *f, const double *z, int n_z) {
 }
 int rfsgpu_importance_weighting(rfsgpu_filter *f) {
   CHECK_HANDLE(f);
-  REFUSE_ON_BATCH(f, "rfsgpu_importance_weighting");
+  if (f->batch) return refuse_on_kind(f, "rfsgpu_importance_weighting", ON_BATCH);
   long long t0 = now_ns();
   hipSetDevice(f->device);
   HIPCHK(hipEventRecord(f->ev[EV_UM1], f->stream));
@@ -1275,7 +1333,7 @@ int rfsgpu_importance_weighting(rfsgpu_filter *f) {
 }
 int rfsgpu_merge(rfsgpu_filter *f) {
   CHECK_HANDLE(f);
-  REFUSE_ON_BATCH(f, "rfsgpu_merge");
+  if (f->batch) return refuse_on_kind(f, "rfsgpu_merge", ON_BATCH);
   f->holes = true;
   long long t0 = now_ns();
   hipSetDevice(f->device);
@@ -1290,7 +1348,7 @@ int rfsgpu_merge(rfsgpu_filter *f) {
 }
 int rfsgpu_prune(rfsgpu_filter *f) {
   CHECK_HANDLE(f);
-  REFUSE_ON_BATCH(f, "rfsgpu_prune");
+  if (f->batch) return refuse_on_kind(f, "rfsgpu_prune", ON_BATCH);
   f->holes = false;
   long long t0 = now_ns();
   hipSetDevice(f->device);
@@ -1342,7 +1400,7 @@ static int update_async_impl(rfsgpu_filter *f, const double *z, int n_z, bool wi
                              hipEvent_t waitBeforePost = nullptr);
 int rfsgpu_update(rfsgpu_filter *f, const double *z, int n_z) {
   CHECK_HANDLE(f);
-  REFUSE_ON_BATCH(f, "rfsgpu_update");
+  if (f->batch) return refuse_on_kind(f, "rfsgpu_update", ON_BATCH);
   f->holes = false;
   if (n_z == 0) return RFSGPU_OK;  // :450-452
   // 2-D model: ONE fused launch (+ the post kernel) unless the caller asked for phase-resolved timing (rfsgpu_set_phase_timing):
@@ -1582,12 +1640,12 @@ static int update_async_impl(rfsgpu_filter *f, const double *z, int n_z, bool wi
 }
 int rfsgpu_update_async(rfsgpu_filter *f, const double *z, int n_z) {
   CHECK_HANDLE(f);
-  REFUSE_ON_BATCH(f, "rfsgpu_update_async");
+  if (f->batch) return refuse_on_kind(f, "rfsgpu_update_async", ON_BATCH);
   return update_async_impl(f, z, n_z, false, 0);
 }
 int rfsgpu_step_async(rfsgpu_filter *f, const double *z, int n_z, int normalize) {
   CHECK_HANDLE(f);
-  REFUSE_ON_BATCH(f, "rfsgpu_step_async");
+  if (f->batch) return refuse_on_kind(f, "rfsgpu_step_async", ON_BATCH);
   if (n_z == 0) {  // no update (:450-452), but the weights are still summed / normalised as the caller asked
     int rc = rfsgpu_weight_sums_async(f);
     if (rc != RFSGPU_OK) return rc;
@@ -1603,7 +1661,7 @@ int rfsgpu_step_async(rfsgpu_filter *f, const double *z, int n_z, int normalize)
 // and the post kernel: the collective of step k runs beside the step kernel of step k + 1 instead of in front of it.
 int rfsgpu_step_async_deferred(rfsgpu_filter *f, const double *z, int n_z, const void *prev_total_dev, void *wait_event) {
   CHECK_HANDLE(f);
-  REFUSE_ON_BATCH(f, "rfsgpu_step_async_deferred");
+  if (f->batch) return refuse_on_kind(f, "rfsgpu_step_async_deferred", ON_BATCH);
   hipSetDevice(f->device);
   if (n_z == 0 || !f->fuseSteps || f->phaseTiming) {        // no fused step: the same arithmetic with the stand-alone kernels, in stream order
     if (wait_event) HIPCHK(hipStreamWaitEvent(f->stream, (hipEvent_t)wait_event, 0));
@@ -1622,7 +1680,7 @@ int rfsgpu_step_async_deferred(rfsgpu_filter *f, const double *z, int n_z, const
 // before it divides by total_dev).  have_prev == 0: the first step of a run (or the first after a flush): nothing to divide by.
 int rfsgpu_step_async_trailing(rfsgpu_filter *f, const double *z, int n_z, const void *total_dev, int have_prev) {
   CHECK_HANDLE(f);
-  REFUSE_ON_BATCH(f, "rfsgpu_step_async_trailing");
+  if (f->batch) return refuse_on_kind(f, "rfsgpu_step_async_trailing", ON_BATCH);
   hipSetDevice(f->device);
   if (!total_dev) return fail(f, RFSGPU_ERR_INVALID, "step_async_trailing: null total buffer");
   const int k = ++f->collStep;
@@ -1644,7 +1702,7 @@ int rfsgpu_step_async_trailing(rfsgpu_filter *f, const double *z, int n_z, const
 // rfsgpu_step_async_trailing call has written this shard's sums.
 int rfsgpu_collective_gate(rfsgpu_filter *f, void *hip_stream) {
   CHECK_HANDLE(f);
-  REFUSE_ON_BATCH(f, "rfsgpu_collective_gate");
+  if (f->batch) return refuse_on_kind(f, "rfsgpu_collective_gate", ON_BATCH);
   hipSetDevice(f->device);
   coll_gate_kernel<<<1, 64, 0, (hipStream_t)hip_stream>>>(f->dCollSeq, f->collStep, f->B.err);
   HIPCHK(hipGetLastError());
@@ -1653,7 +1711,7 @@ int rfsgpu_collective_gate(rfsgpu_filter *f, void *hip_stream) {
 // [multi] on the same stream, behind the collective: the total of the last step is in place.
 int rfsgpu_collective_publish(rfsgpu_filter *f, void *hip_stream) {
   CHECK_HANDLE(f);
-  REFUSE_ON_BATCH(f, "rfsgpu_collective_publish");
+  if (f->batch) return refuse_on_kind(f, "rfsgpu_collective_publish", ON_BATCH);
   hipSetDevice(f->device);
   coll_publish_kernel<<<1, 1, 0, (hipStream_t)hip_stream>>>(f->dCollSeq + 1, f->collStep);   // word [1]: "the total of step k is in place"
   HIPCHK(hipGetLastError());
@@ -1669,7 +1727,7 @@ int rfsgpu_collective_publish(rfsgpu_filter *f, void *hip_stream) {
 // a spinning kernel for that long -- past the bound the probe must answer 0 and the hosts must take the event form.
 int rfsgpu_collective_probe(rfsgpu_filter *f, void *hip_stream, int *side_by_side) {
   CHECK_HANDLE(f);
-  REFUSE_ON_BATCH(f, "rfsgpu_collective_probe");
+  if (f->batch) return refuse_on_kind(f, "rfsgpu_collective_probe", ON_BATCH);
   if (!side_by_side) return fail(f, RFSGPU_ERR_INVALID, "collective_probe: null result pointer");
   hipSetDevice(f->device);
   const int k = ++f->collProbeSeq;
@@ -1828,7 +1886,7 @@ static int cycle_impl(rfsgpu_filter *f, int predict, const double *x, const doub
 int rfsgpu_cycle_async(rfsgpu_filter *f, int predict, const double *x, const double *x_cov, int cov_stride, const double *w_in, const double *z, int n_z,
                        int normalize) {
   CHECK_HANDLE(f);
-  REFUSE_ON_BATCH(f, "rfsgpu_cycle_async");
+  if (f->batch) return refuse_on_kind(f, "rfsgpu_cycle_async", ON_BATCH);
   return cycle_impl(f, predict, x, x_cov, cov_stride, w_in, z, n_z, true, normalize);
 }
 // The synchronous form for a host that stands where RBPHDFilter::update stands (:444-541): everything the update consumes goes in,
@@ -1892,7 +1950,7 @@ static int update_io_end(rfsgpu_filter *f, double *w_out) {
 int rfsgpu_update_io(rfsgpu_filter *f, int predict, const double *x, const double *x_cov, int cov_stride, const double *w_in, const double *z, int n_z,
                      double *w_out) {
   CHECK_HANDLE(f);
-  REFUSE_ON_BATCH(f, "rfsgpu_update_io");
+  if (f->batch) return refuse_on_kind(f, "rfsgpu_update_io", ON_BATCH);
   long long t0 = now_ns();
   int rc = update_io_begin(f, predict, x, x_cov, cov_stride, w_in, z, n_z, w_out != nullptr);
   if (rc != RFSGPU_OK) return rc;
@@ -1945,7 +2003,6 @@ static void launch_predict_kernels(rfsgpu_filter *f, int add_birth, const BirthL
 // lazily by the next predict, or by the host), or the birth bookkeeping as well (RFSGPU_INHERIT_EAGER, and FastSLAM handles)
 static int map_only(const rfsgpu_filter *f) { return (f->inheritMode != RFSGPU_INHERIT_EAGER && !f->fastSlamHandle) ? 1 : 0; }
 // ... of a batch: the lists travel where the batch keeps landmark candidates (Victoria Park FastSLAM filters, as on a FastSLAM handle)
-static int batch_map_only(const rfsgpu_filter *f) { return f->bVpFastSlam ? 0 : 1; }
 static void ensure_ids(rfsgpu_filter *f) {
   while ((int)f->pid.size() < f->Ncap) { f->pid.push_back((int)f->pid.size()); f->ppid.push_back((int)f->ppid.size()); }
 }
@@ -2033,7 +2090,7 @@ static int predict_launch(rfsgpu_filter *f, int add_birth) {
 // One level of the level-ordered birth step, for hosts that move the per-slot birth lists between shards themselves (rfsgpu.h).
 int rfsgpu_predict_map_level(rfsgpu_filter *f, int add_birth, const int *level_of_slot, int level, int do_static) {
   CHECK_HANDLE(f);
-  REFUSE_ON_BATCH(f, "rfsgpu_predict_map_level");
+  if (f->batch) return refuse_on_kind(f, "rfsgpu_predict_map_level", ON_BATCH);
   if (!level_of_slot) return fail(f, RFSGPU_ERR_INVALID, "predict_map_level: null level array");
   f->externalAck = true;
   hipSetDevice(f->device);
@@ -2052,7 +2109,7 @@ int rfsgpu_predict_map_level(rfsgpu_filter *f, int add_birth, const int *level_o
 
 int rfsgpu_predict_map(rfsgpu_filter *f, int add_birth) {
   CHECK_HANDLE(f);
-  REFUSE_ON_BATCH(f, "rfsgpu_predict_map");
+  if (f->batch) return refuse_on_kind(f, "rfsgpu_predict_map", ON_BATCH);
   if (add_birth && f->resampleOccured && f->inheritMode == RFSGPU_INHERIT_EXTERNAL && !f->externalAck)
     return fail(f, RFSGPU_ERR_INVALID, "predict_map with births after a resampling in RFSGPU_INHERIT_EXTERNAL mode, but the host has not applied the "
                 "inheritance rule (rfsgpu_set_unused_masks, rfsgpu_predict_map_level, or rfsgpu_set_birth_inheritance(EXTERNAL) again to acknowledge): "
@@ -2073,7 +2130,7 @@ int rfsgpu_predict_map(rfsgpu_filter *f, int add_birth) {
 int rfsgpu_predict_map_async(rfsgpu_filter *f, int add_birth) {
   if (f && rc_only_pending(f)) { }                                    // behind pending RB-PHD cycles the births walk the ids on the device (predict_walk_device)
   else if (add_birth) { CHECK_HANDLE(f); } else { CHECK_HANDLE_ENQ(f); }   // (the births read the ids and resampleOccured)
-  REFUSE_ON_BATCH(f, "rfsgpu_predict_map_async");
+  if (f->batch) return refuse_on_kind(f, "rfsgpu_predict_map_async", ON_BATCH);
   if (add_birth && !f->rcPending && f->resampleOccured && f->inheritMode == RFSGPU_INHERIT_EXTERNAL && !f->externalAck)
     return fail(f, RFSGPU_ERR_INVALID, "predict_map with births after a resampling in RFSGPU_INHERIT_EXTERNAL mode, but the host has not applied the "
                 "inheritance rule (rfsgpu_set_unused_masks, rfsgpu_predict_map_level, or rfsgpu_set_birth_inheritance(EXTERNAL) again to acknowledge): "
@@ -2097,7 +2154,7 @@ int rfsgpu_predict_map_async(rfsgpu_filter *f, int add_birth) {
 // rfsgpu_set_lmk_process_noise(Q_k) + rfsgpu_predict_map_async(f, 0).  noises: [n][D*D] row-major, or NULL = the noise that is set
 // now, n times.  Stream-ordered.
 int rfsgpu_static_steps_async(rfsgpu_filter *f, int n, const double *noises) {
-  if (f && f->vpMh) {     // a batch of Victoria Park multi-hypothesis filters: behind its cycles, the counts and overflow words read on the device
+  if (f && batch_is_vp_mh(f)) {     // a batch of Victoria Park multi-hypothesis filters: behind its cycles, the counts and overflow words read on the device
     if (n < 0) return fail(f, RFSGPU_ERR_INVALID, "static_steps: negative count");
     hipSetDevice(f->device);
     FsCycleState S0;
@@ -2211,12 +2268,7 @@ int rfsgpu_set_step_inputs_async(rfsgpu_filter *f, const double *x, const double
 // setLaserScan through hs, the scan's place in a block of the pinned ring: the FoV area and the clutter density on the host, the raw
 // scan to the device by a stream-ordered copy
 static int push_scan(rfsgpu_filter *f, double *hs, const double *scan, int n_scan) {
-  double area = 0;
-  for (int q = 1; q < n_scan; q++) area += scan[q] * scan[q - 1];
-  area += scan[0] * scan[n_scan - 1];
-  area *= sin(acos(-1) / 360) / 2;
-  f->vpClutter = f->vp.expectedClutterNumber / area;
-  if (f->batch) batch_scan_clutter(f, area);
+  scan_clutter(f, scan, n_scan);
   memcpy(hs, scan, (size_t)n_scan * sizeof(double));
   HIPCHK(hipMemcpyAsync(f->B.scan, hs, (size_t)n_scan * sizeof(double), hipMemcpyHostToDevice, f->stream));
   f->B.nScan = n_scan;
@@ -2250,7 +2302,7 @@ int rfsgpu_landmarks_in_fov(rfsgpu_filter *f, int slot, int *n_out) {
 
 int rfsgpu_weight_sums_async(rfsgpu_filter *f) {
   CHECK_HANDLE(f);
-  REFUSE_ON_BATCH(f, "rfsgpu_weight_sums_async");
+  if (f->batch) return refuse_on_kind(f, "rfsgpu_weight_sums_async", ON_BATCH);
   hipSetDevice(f->device);
   weight_sums_kernel<<<1, 1024, 0, f->stream>>>(f->B.weight, f->N, f->dSums);
   HIPCHK(hipGetLastError());
@@ -2259,7 +2311,7 @@ int rfsgpu_weight_sums_async(rfsgpu_filter *f) {
 void *rfsgpu_weight_sums_device_ptr(rfsgpu_filter *f) { return f ? (void *)f->dSums : nullptr; }
 int rfsgpu_weight_sums(rfsgpu_filter *f, double *out) {
   CHECK_HANDLE(f);
-  REFUSE_ON_BATCH(f, "rfsgpu_weight_sums (use rfsgpu_batch_weight_sums)");
+  if (f->batch) return refuse_on_kind(f, "rfsgpu_weight_sums (use rfsgpu_batch_weight_sums)", ON_BATCH);
   int rc = rfsgpu_weight_sums_async(f);
   if (rc != RFSGPU_OK) return rc;
   HIPCHK(hipMemcpyAsync(f->hSums, f->dSums, 2 * sizeof(double), hipMemcpyDeviceToHost, f->stream));
@@ -2271,7 +2323,7 @@ int rfsgpu_weight_sums(rfsgpu_filter *f, double *out) {
 int rfsgpu_normalize_weights(rfsgpu_filter *f, double sum, const void *sum_dev) { return rfsgpu_normalize_weights_parts(f, sum, sum_dev, 1); }
 int rfsgpu_normalize_weights_parts(rfsgpu_filter *f, double sum, const void *sum_dev, int n_parts) {
   CHECK_HANDLE(f);
-  REFUSE_ON_BATCH(f, "rfsgpu_normalize_weights");
+  if (f->batch) return refuse_on_kind(f, "rfsgpu_normalize_weights", ON_BATCH);
   if (n_parts < 1) return RFSGPU_ERR_INVALID;
   hipSetDevice(f->device);
   long long t0 = now_ns();
@@ -2298,7 +2350,7 @@ int rfsgpu_max_particles(const rfsgpu_filter *f) { return f ? f->Ncap : -1; }
 int rfsgpu_resample_apply(rfsgpu_filter *f, const int *src_slot) { return f ? rfsgpu_resample_apply_n(f, src_slot, f->N) : RFSGPU_ERR_INVALID; }
 int rfsgpu_resample_apply_n(rfsgpu_filter *f, const int *src_slot, int n_out) {
   CHECK_HANDLE(f);
-  REFUSE_ON_BATCH(f, "rfsgpu_resample_apply");
+  if (f->batch) return refuse_on_kind(f, "rfsgpu_resample_apply", ON_BATCH);
   if (f->rcHave) return fail(f, RFSGPU_ERR_UNSUPPORTED, "resample_apply: this handle runs rfsgpu_rbphd_cycle_async, which resamples inside the cycle and keeps the ids and the counters of its gate on the device");
   if (!src_slot || n_out < 1 || n_out > f->N) return RFSGPU_ERR_INVALID;
   const int nIn = f->N;
@@ -2386,7 +2438,7 @@ int rfsgpu_set_particle_ids(rfsgpu_filter *f, const int *id, const int *parent_i
   }
   for (int k = 0; k < f->N; k++) { if (id) f->pid[k] = id[k]; if (parent_id) f->ppid[k] = parent_id[k]; }
   f->mhcIdsDirty = true;
-  if (f->mhBatch) {      // (the ids live in the filters' cycle state on the device)
+  if (batch_is_mh(f)) {      // (the ids live in the filters' cycle state on the device)
     FsCycleState S0;
     mhb_state(f->mhbBlock, f->nF, f->nPer, 0, S0);
     hipSetDevice(f->device);
@@ -2413,7 +2465,7 @@ int rfsgpu_resample_occured(const rfsgpu_filter *f) {
 // every particle's pose covariance as the update reads it: [n_particles][9] row-major (one shared matrix is repeated)
 int rfsgpu_get_pose_covs(rfsgpu_filter *f, double *cov) {
   CHECK_HANDLE(f);
-  REFUSE_ON_BATCH(f, "rfsgpu_get_pose_covs (use rfsgpu_batch_get_pose_covs)");
+  if (f->batch) return refuse_on_kind(f, "rfsgpu_get_pose_covs (use rfsgpu_batch_get_pose_covs)", ON_BATCH);
   if (!cov) return RFSGPU_ERR_INVALID;
   hipSetDevice(f->device);
   const bool per = f->P.poseCovStride == 9;
@@ -2696,7 +2748,7 @@ void rfsgpu_default_fastslam_config(rfsgpu_fastslam_config *c) {  // constructor
 }
 int rfsgpu_set_fastslam_config(rfsgpu_filter *f, const rfsgpu_fastslam_config *cfg) {
   CHECK_HANDLE_HOST(f);
-  REFUSE_ON_BATCH(f, "FastSLAM");
+  if (f->batch) return refuse_on_kind(f, "FastSLAM", ON_BATCH);
   if (!cfg) return RFSGPU_ERR_INVALID;
   f->fs = *cfg;
   return RFSGPU_OK;
@@ -2949,7 +3001,7 @@ static int rs_block_ready(rfsgpu_filter *f, bool upload) {
 }
 int rfsgpu_resample_async(rfsgpu_filter *f, double eff_n, double eff_n_percent, double u01, int n_out, int force, int renormalize) {
   CHECK_HANDLE(f);
-  REFUSE_ON_BATCH(f, "rfsgpu_resample_async (use rfsgpu_batch_resample_async)");
+  if (f->batch) return refuse_on_kind(f, "rfsgpu_resample_async (use rfsgpu_batch_resample_async)", ON_BATCH);
   if (f->groupShard) return fail(f, RFSGPU_ERR_UNSUPPORTED, "resample_async: not available on a shard of an rfsgpu_group (the resampling is global: rfsgpu_group_resample)");
   if (f->mhcHave) return fail(f, RFSGPU_ERR_UNSUPPORTED, "resample_async: this handle runs rfsgpu_fastslam_cycle_async, which resamples inside the cycle and keeps the ids in its own block");
   if (f->rcHave) return fail(f, RFSGPU_ERR_UNSUPPORTED, "resample_async: this handle runs rfsgpu_rbphd_cycle_async, which resamples inside the cycle and keeps the ids and the counters of its gate on the device");
@@ -3030,7 +3082,7 @@ static int rc_resolve(rfsgpu_filter *f) {
 }
 int rfsgpu_rbphd_set_resampling(rfsgpu_filter *f, double eff_n, double eff_n_percent) {
   CHECK_HANDLE_HOST(f);
-  REFUSE_ON_BATCH(f, "rfsgpu_rbphd_set_resampling (use rfsgpu_batch_set_resampling)");
+  if (f->batch) return refuse_on_kind(f, "rfsgpu_rbphd_set_resampling (use rfsgpu_batch_set_resampling)", ON_BATCH);
   if (!(eff_n >= 0.0) || !(eff_n_percent >= 0.0)) return fail(f, RFSGPU_ERR_INVALID, "rbphd_set_resampling: thresholds must be non-negative");
   f->rcEffN = eff_n;
   f->rcEffNPercent = eff_n_percent;
@@ -3039,7 +3091,7 @@ int rfsgpu_rbphd_set_resampling(rfsgpu_filter *f, double eff_n, double eff_n_per
 int rfsgpu_rbphd_cycle_async(rfsgpu_filter *f, const double *z, int n_z, const double *scan, int n_scan, double u01) {
   if (!f) return RFSGPU_ERR_INVALID;
   if (f->mhcStashedRc || f->rsPending || f->mhcPending || f->mhbPending) { const int rc = mhc_resolve(f); if (rc != RFSGPU_OK) return rc; }
-  REFUSE_ON_BATCH(f, "rfsgpu_rbphd_cycle_async");
+  if (f->batch) return refuse_on_kind(f, "rfsgpu_rbphd_cycle_async", ON_BATCH);
   if (f->groupShard) return fail(f, RFSGPU_ERR_UNSUPPORTED, "rbphd_cycle: not available on a shard of an rfsgpu_group (the resampling is global: rfsgpu_group_resample)");
   if (f->fastSlamHandle || f->mhcHave) return fail(f, RFSGPU_ERR_UNSUPPORTED, "rbphd_cycle: this handle runs FastSLAM updates (rfsgpu_fastslam_cycle_async is their device cycle)");
   if (f->inheritMode == RFSGPU_INHERIT_EXTERNAL) return fail(f, RFSGPU_ERR_UNSUPPORTED, "rbphd_cycle: RFSGPU_INHERIT_EXTERNAL leaves the birth lists to a host that must learn of every resampling; the cycle tells nobody");
@@ -3122,7 +3174,7 @@ int rfsgpu_rbphd_last_cycle(rfsgpu_filter *f, int *gate_open, int *fired, double
 int rfsgpu_rbphd_cycle_pending(rfsgpu_filter *f) { return (f && f->rcPending) ? 1 : 0; }
 int rfsgpu_fastslam_set_resampling(rfsgpu_filter *f, double eff_n, double eff_n_percent) {
   CHECK_HANDLE_HOST(f);
-  REFUSE_ON_BATCH(f, "rfsgpu_fastslam_set_resampling (use rfsgpu_batch_set_resampling)");
+  if (f->batch) return refuse_on_kind(f, "rfsgpu_fastslam_set_resampling (use rfsgpu_batch_set_resampling)", ON_BATCH);
   if (!(eff_n >= 0.0) || !(eff_n_percent >= 0.0)) return fail(f, RFSGPU_ERR_INVALID, "fastslam_set_resampling: thresholds must be non-negative");
   f->fsEffN = eff_n;
   f->fsEffNPercent = eff_n_percent;
@@ -3134,7 +3186,7 @@ static int fastslam_cycle_enqueue(rfsgpu_filter *f, int predict, const double *z
 int rfsgpu_fastslam_cycle_async(rfsgpu_filter *f, int predict, const double *z, int n_z, double u01, int n_init) {
   if (!f) return RFSGPU_ERR_INVALID;
   if (f->mhcStashedRc || f->rsPending) { const int rc = mhc_resolve(f); if (rc != RFSGPU_OK) return rc; }
-  REFUSE_ON_BATCH(f, "rfsgpu_fastslam_cycle_async");
+  if (f->batch) return refuse_on_kind(f, "rfsgpu_fastslam_cycle_async", ON_BATCH);
   if (f->groupShard) return fail(f, RFSGPU_ERR_UNSUPPORTED, "fastslam_cycle: not available on a shard of an rfsgpu_group (the particle count would be known to one device only)");
   if (f->D != 2) return fail(f, RFSGPU_ERR_UNSUPPORTED, "fastslam_cycle: the Victoria Park model is not served (the 2-D range-bearing model only)");
   if (f->fs.landmarkCandidateMeasurementCountThreshold != 1u)
@@ -3144,7 +3196,7 @@ int rfsgpu_fastslam_cycle_async(rfsgpu_filter *f, int predict, const double *z, 
 int rfsgpu_fastslam_cycle_full_async(rfsgpu_filter *f, int predict, const double *z, int n_z, const double *scan, int n_scan, double u01, int n_init) {
   if (!f) return RFSGPU_ERR_INVALID;
   if (f->mhcStashedRc || f->rsPending) { const int rc = mhc_resolve(f); if (rc != RFSGPU_OK) return rc; }
-  REFUSE_ON_BATCH(f, "rfsgpu_fastslam_cycle_full_async");
+  if (f->batch) return refuse_on_kind(f, "rfsgpu_fastslam_cycle_full_async", ON_BATCH);
   if (f->groupShard) return fail(f, RFSGPU_ERR_UNSUPPORTED, "fastslam_cycle: not available on a shard of an rfsgpu_group (the particle count would be known to one device only)");
   return fastslam_cycle_enqueue(f, predict, z, n_z, scan, n_scan, u01, n_init, true);
 }
@@ -3309,7 +3361,7 @@ int rfsgpu_fastslam_last_cycle(rfsgpu_filter *f, int *n_after_update, int *n_aft
 }
 int rfsgpu_fastslam_update(rfsgpu_filter *f, const double *z, int n_z) {
   CHECK_HANDLE(f);
-  REFUSE_ON_BATCH(f, "FastSLAM");
+  if (f->batch) return refuse_on_kind(f, "FastSLAM", ON_BATCH);
   f->holes = false;
   f->fastSlamHandle = true;
   if (n_z == 0) return RFSGPU_OK;  // :401-402
@@ -3448,33 +3500,13 @@ static void batch_set_all(rfsgpu_filter *f) {
   }
   f->bParamsDirty = true;
 }
-// setLaserScan for every filter of a Victoria Park batch: the density rfsgpu_set_laser_scan derives on a handle, from the filter's own
-// expectedClutterNumber as it is configured now (a later rfsgpu_batch_configure_vp leaves it until the next scan, as the handle's setter does)
-static void batch_scan_clutter(rfsgpu_filter *f, double area) {
-  for (int b = 0; b < f->nF; b++) f->bVpClutter[b] = f->bVp[b].expectedClutterNumber / area;
-  f->bParamsDirty = true;
-}
 // Params of filter b: the handle's own rule (rebuild_params) on the filter's configuration; the handle-wide fields (pose covariance
 // stride, partition mode, dense intensity) are the handle's.
-static Params batch_params(rfsgpu_filter *f, int b) {
-  const rfsgpu_filter_config cfg = f->cfg;
-  const rfsgpu_rngbrg_config rb = f->rb;
-  const rfsgpu_kf_config kf = f->kf;
-  double Q[9];
-  memcpy(Q, f->Qlm, sizeof Q);
-  const Params keep = f->P;
-  const rfsgpu_vp_config vp = f->vp;
-  const double vpClutter = f->vpClutter;
-  f->cfg = f->bCfg[b]; f->rb = f->bRb[b]; f->kf = f->bKf[b];
-  if (f->D == 3) { f->vp = f->bVp[b]; f->vpClutter = f->bVpClutter[b]; }
-  memcpy(f->Qlm, &f->bQ[(size_t)9 * b], sizeof Q);
-  rebuild_params(f);
-  const Params out = f->P;
-  f->cfg = cfg; f->rb = rb; f->kf = kf;
-  f->vp = vp; f->vpClutter = vpClutter;
-  memcpy(f->Qlm, Q, sizeof Q);
-  f->P = keep;
-  return out;
+static Params batch_params(const rfsgpu_filter *f, int b) {
+  Params P = f->P;
+  rebuild_params(P, f->bCfg[b], f->bRb[b], f->bKf[b], &f->bQ[(size_t)9 * b], f->D == 3 ? f->bVp[b] : f->vp, f->D == 3 ? f->bVpClutter[b] : f->vpClutter, f->D,
+                 f->denseIntensity, f->gateIndex);
+  return P;
 }
 static size_t batch_stage_bytes(const rfsgpu_filter *f) {
   return (size_t)f->nF * (std::max(sizeof(MhBatchFilter), std::max(sizeof(BatchFilter), sizeof(FsBatchFilter))) + sizeof(Params) + RFSGPU_MAX_Z * (size_t)f->D * sizeof(double) + sizeof(int)) + (size_t)f->N * sizeof(int);
@@ -3601,7 +3633,7 @@ static int batch_sensed_records(rfsgpu_filter *f, Rec *dRec, unsigned long long 
     f->bFsTmplHost.swap(now);
   }
   fs_sensed_records_kernel<Rec><<<(nF + 63) / 64, 64, 0, f->stream>>>(reinterpret_cast<const Tmpl *>(f->dFsTmpl), f->dBFilt, dRec, f->dBMotion, nF, call,
-                                                                      f->mhBatch ? f->dFsLastNZ : nullptr);
+                                                                      batch_is_mh(f) ? f->dFsLastNZ : nullptr);
   HIPCHK(hipGetLastError());
   return RFSGPU_OK;
 }
@@ -3627,6 +3659,52 @@ static int batch_push_poses(rfsgpu_filter *f, const double *x, const double *x_c
   HIPCHK(hipEventRecord(f->stage.ev[ks], f->stream));
   return RFSGPU_OK;
 }
+// ... and, on a batch of Victoria Park filters, the call's scan with them: poses (when given) and scan through one block of the
+// staging ring, the scan at h + Ncap * 22 (rfsgpu_set_step_inputs_async's layout); it becomes the scan the batch holds.  No scan:
+// batch_push_poses, when there are poses.
+static int batch_push_poses_scan(rfsgpu_filter *f, const double *x, const double *x_cov, int cov_stride, const double *scan, int n_scan) {
+  if (!scan) return x ? batch_push_poses(f, x, x_cov, cov_stride) : RFSGPU_OK;
+  double *h = nullptr;
+  int ks = 0;
+  int rc = ring_acquire(f, f->stage, &h, &ks);
+  if (rc != RFSGPU_OK) return rc;
+  if (x && (rc = push_poses(f, h, f->B.pose, x, x_cov, cov_stride)) != RFSGPU_OK) return rc;
+  double *hs = h + (size_t)f->Ncap * 22;
+  memcpy(hs, scan, (size_t)n_scan * sizeof(double));
+  HIPCHK(hipMemcpyAsync(f->B.scan, hs, (size_t)n_scan * sizeof(double), hipMemcpyHostToDevice, f->stream));
+  f->B.nScan = n_scan;
+  HIPCHK(hipEventRecord(f->stage.ev[ks], f->stream));
+  return RFSGPU_OK;
+}
+// Whether the call's scan or the one the batch holds can serve a Victoria Park cycle, under the call's own prefix
+static int batch_check_scan(rfsgpu_filter *f, const BatchCall &C, const double *scan, int n_scan) {
+  if (scan && (n_scan < 2 || n_scan > RFSGPU_VP_MAX_SCAN)) return batch_fail(f, C, "laser scan size out of range (2 ... RFSGPU_VP_MAX_SCAN beams)");
+  if (!scan && f->B.nScan < 2) return batch_fail(f, C, "the batch has not been given a laser scan (rfsgpu_set_laser_scan, or this call's scan)");
+  return RFSGPU_OK;
+}
+// The draws of a multi-hypothesis cycle call, one per filter
+static int batch_check_u01(rfsgpu_filter *f, const BatchCall &C, int b, const double *u01) {
+  if (u01[b] >= 0.0 && u01[b] < 1.0) return RFSGPU_OK;
+  return batch_fail(f, C, "filter " + std::to_string(b) + ": u01 must lie in [0, 1)");
+}
+// The host's bookkeeping at the end of a cycle core, the launches enqueued.  n_z null: a sensed cycle, whose counts stay on the device.
+// flipCur: the chain wrote the other slab and has not flipped `cur` itself (the Victoria Park RB-PHD cycle: only with an update).
+// mh: a multi-hypothesis cycle -- the counts are kept for rfsgpu_batch_fastslam_last_cycle as well, resampleOccured_ is the device's
+// (mhb_resolve) and, the resampling being inside the cycle, no sensed resampling may follow.
+static void batch_cycle_done(rfsgpu_filter *f, const int *n_z, bool flipCur, bool mh, long long t0) {
+  const bool sensed = n_z == nullptr;
+  if (flipCur) f->cur ^= 1;   // (filters without an update had their mixture moved to the new slab by the step kernel)
+  if (!sensed)
+    for (int b = 0; b < f->nF; b++) {
+      if (mh) f->mhbLastNZ[b] = n_z[b];
+      if (n_z[b] > 0) { f->bNZ[b] = n_z[b]; if (!mh) f->bResampled[b] = 0; }
+    }
+  f->bSenseFresh = false;     // (either kind of cycle: the next sensed cycle needs a sense call of its own)
+  f->bSensedTail = sensed && !mh;
+  if (!sensed) f->bScanHeld = false;     // (the host's sets lie over the sensor's)
+  f->holes = false;
+  f->timing.mapUpdate_cpu += now_ns() - t0;
+}
 
 int rfsgpu_create_batch(rfsgpu_filter **out, int model, int n_filters, int n_per_filter, int device_id, int gm_capacity) {
   if (!out) return RFSGPU_ERR_INVALID;
@@ -3639,7 +3717,7 @@ int rfsgpu_create_batch(rfsgpu_filter **out, int model, int n_filters, int n_per
   f->nF = n_filters;
   f->nPer = n_per_filter;
   const size_t zd = (size_t)f->D;     // doubles per measurement in the sets' tables
-  if (f->D == 3) f->bKind = 1;        // (a batch of Victoria Park filters steps RB-PHD filters: rfsgpu_batch_vp_cycle_async)
+  batch_born(f);
   f->bVp.assign(n_filters, f->vp); f->bVpClutter.assign(n_filters, 0.0);
   f->bCfg.resize(n_filters); f->bRb.resize(n_filters); f->bKf.resize(n_filters); f->bQ.assign((size_t)9 * n_filters, 0.0);
   f->bNZ.assign(n_filters, 0);
@@ -3754,19 +3832,19 @@ int rfsgpu_batch_cycle_async(rfsgpu_filter *f, int predict, const double *x, con
   CHECK_HANDLE(f);
   int rc = batch_check(f, -1);
   if (rc != RFSGPU_OK) return rc;
-  REFUSE_ON_MH_BATCH(f, "rfsgpu_batch_cycle_async");
-  REFUSE_ON_VP_BATCH(f, "rfsgpu_batch_cycle_async");
+  if (!batch_fills_blocks(f)) return refuse_on_kind(f, "rfsgpu_batch_cycle_async", ON_MH_BATCH);
+  if (batch_is_vp(f)) return refuse_on_kind(f, "rfsgpu_batch_cycle_async", ON_VP_BATCH);
   if ((rc = batch_check_call(f, BATCH_CYCLE, predict, x_cov, cov_stride, n_z)) != RFSGPU_OK) return rc;
   for (int b = 0; b < f->nF; b++) {
     if ((rc = batch_check_filter(f, BATCH_CYCLE, b, z, n_z)) != RFSGPU_OK) return rc;
     if (f->bCfg[b].birthGaussianMeasurementCountThreshold != 1u)
       return fail(f, RFSGPU_ERR_UNSUPPORTED, "batch_cycle: a filter batch takes immediate births only (birthGaussianMeasurementCountThreshold 1)");
   }
-  if (f->bKind == 2)
+  if (f->bSteps == STEPS_FASTSLAM)
     return fail(f, RFSGPU_ERR_UNSUPPORTED, "batch_cycle: this batch steps FastSLAM filters (rfsgpu_batch_set_fastslam_config or rfsgpu_batch_fastslam_cycle_async has run): a batch is of one kind");
   if (f->bSensed)
     return fail(f, RFSGPU_ERR_UNSUPPORTED, "batch_cycle: this batch has run a sensed cycle (rfsgpu_batch_cycle_sensed_async): the count of each filter's last update lives on the device, the host-fed cycle no longer knows it");
-  f->bKind = 1;
+  batch_decide(f, STEPS_RBPHD);
   return batch_cycle_core(f, predict, x, x_cov, cov_stride, z, n_z, normalize);
 }
 // eval_cap() of filter b's configuration, as its BatchFilter record carries it
@@ -3877,15 +3955,7 @@ static int batch_cycle_core(rfsgpu_filter *f, int predict, const double *x, cons
   if (sortCosts) f->vpParity ^= 1;
   if (murty_launch_batch(f->Q, f->MS, f->B, f->stream, A, normalize, f->hJobCount, sord) != 0) return fail(f, RFSGPU_ERR_HIP, "batch post kernel launch failed");
   if (ks >= 0) HIPCHK(hipEventRecord(f->stage.ev[ks], f->stream));   // the pinned input slot is free once the step kernel has read it
-  f->cur ^= 1;   // (filters without an update had their mixture moved to the new slab by the step kernel)
-  if (!sensed)
-    for (int b = 0; b < nF; b++)
-      if (n_z[b] > 0) { f->bNZ[b] = n_z[b]; f->bResampled[b] = 0; }
-  f->bSenseFresh = false;     // (either kind of cycle: the next sensed cycle needs a sense call of its own)
-  f->bSensedTail = sensed;
-  if (!sensed) f->bScanHeld = false;
-  f->holes = false;
-  f->timing.mapUpdate_cpu += now_ns() - t0;
+  batch_cycle_done(f, n_z, true, false, t0);
   return RFSGPU_OK;
 }
 // ---- a batch of Victoria Park RB-PHD filters (vp_batch.h): rfsgpu_cycle_async of every filter's own handle in one launch chain --
@@ -3906,14 +3976,7 @@ static int batch_vp_cycle_core(rfsgpu_filter *f, int predict, const double *x, c
   long long t0 = now_ns();
   batch_handle_wide(f, x, x_cov, cov_stride);
   // the call's scan: every filter's clutter density on the host (it travels in the Params table), the beams by copy command below
-  if (scan) {
-    double area = 0;
-    for (int q = 1; q < n_scan; q++) area += scan[q] * scan[q - 1];
-    area += scan[0] * scan[n_scan - 1];
-    area *= sin(acos(-1) / 360) / 2;
-    f->vpClutter = f->vp.expectedClutterNumber / area;
-    batch_scan_clutter(f, area);
-  }
+  if (scan) scan_clutter(f, scan, n_scan);     // every filter's clutter density on the host (it travels in the Params table); the beams by copy command below
   // The reference's lazy copy of the per-slot birth state (RBPHDFilter.hpp:1005-1011) for the filters that have resampled since their
   // last update with measurements: predict_launch's parent and level tables, built across the batch.  A parent lies inside its filter's
   // block; a filter whose flag is clear keeps every slot its own parent, whatever idParent_ an older resampling left it.
@@ -3980,22 +4043,8 @@ static int batch_vp_cycle_core(rfsgpu_filter *f, int predict, const double *x, c
     f->candUsed = true;
   }
   // the host's new poses / covariances and the scan, behind the births (which happen at the poses the last update used)
-  if (x || scan) {
-    double *h = nullptr;
-    int ks = 0;
-    if ((rc = ring_acquire(f, f->stage, &h, &ks)) != RFSGPU_OK) return rc;
-    if (x) {
-      f->bBirthAlt = false;
-      if ((rc = push_poses(f, h, f->B.pose, x, x_cov, cov_stride)) != RFSGPU_OK) return rc;
-    }
-    if (scan) {
-      double *hs = h + (size_t)f->Ncap * 22;
-      memcpy(hs, scan, (size_t)n_scan * sizeof(double));
-      HIPCHK(hipMemcpyAsync(f->B.scan, hs, (size_t)n_scan * sizeof(double), hipMemcpyHostToDevice, f->stream));
-      f->B.nScan = n_scan;
-    }
-    HIPCHK(hipEventRecord(f->stage.ev[ks], f->stream));
-  }
+  if (x) f->bBirthAlt = false;
+  if ((rc = batch_push_poses_scan(f, x, x_cov, cov_stride, scan, n_scan)) != RFSGPU_OK) return rc;
   // two particles per workgroup where two waves' areas fit beside the scan (the handle's rule and its 64 KiB bound), else one
   const size_t scanB = vp_batch_scan_lds_bytes(f->B.nScan), stride = vp_batch_lds_stride(f->cap, ecMax, nZmax);
   const int wpb = scanB + 2 * stride <= (size_t)64 * 1024 ? 2 : 1;
@@ -4025,11 +4074,7 @@ static int batch_vp_cycle_core(rfsgpu_filter *f, int predict, const double *x, c
     vp_batch_clear_flags_kernel<<<(nF + 255) / 256, 256, 0, f->stream>>>(f->BL.resampled, f->dBFilt, nF);
     HIPCHK(hipGetLastError());
   }
-  if (anyUpdate) f->cur ^= 1;   // (filters without an update had their mixture moved to the new slab by the step kernel)
-  for (int b = 0; b < nF; b++)
-    if (n_z[b] > 0) { f->bNZ[b] = n_z[b]; f->bResampled[b] = 0; }
-  f->holes = false;
-  f->timing.mapUpdate_cpu += now_ns() - t0;
+  batch_cycle_done(f, n_z, anyUpdate, false, t0);     // (never sensed: the device sensor does not serve the Victoria Park model, and its flags stay down)
   return RFSGPU_OK;
 }
 int rfsgpu_batch_vp_cycle_async(rfsgpu_filter *f, int predict, const double *x, const double *x_cov, int cov_stride, const double *z, const int *n_z,
@@ -4039,15 +4084,14 @@ int rfsgpu_batch_vp_cycle_async(rfsgpu_filter *f, int predict, const double *x, 
   if (rc != RFSGPU_OK) return rc;
   if (f->D != 3)
     return fail(f, RFSGPU_ERR_UNSUPPORTED, "batch_vp_cycle: this batch steps 2-D filters (rfsgpu_batch_cycle_async, rfsgpu_batch_fastslam_cycle_async or rfsgpu_batch_fastslam_mh_cycle_async): the Victoria Park cycle needs a batch created with RFSGPU_MODEL_VICTORIAPARK_3D");
-  if (f->vpMh) return fail(f, RFSGPU_ERR_UNSUPPORTED, "batch_vp_cycle: this is the RB-PHD cycle; a batch of Victoria Park multi-hypothesis FastSLAM filters (rfsgpu_create_batch_vp_mh) takes rfsgpu_batch_vp_fastslam_mh_cycle_async");
+  if (batch_is_mh(f)) return fail(f, RFSGPU_ERR_UNSUPPORTED, "batch_vp_cycle: this is the RB-PHD cycle; a batch of Victoria Park multi-hypothesis FastSLAM filters (rfsgpu_create_batch_vp_mh) takes rfsgpu_batch_vp_fastslam_mh_cycle_async");
   if ((rc = batch_check_call(f, BATCH_VP_CYCLE, predict, x_cov, cov_stride, n_z)) != RFSGPU_OK) return rc;
   for (int b = 0; b < f->nF; b++)
     if ((rc = batch_check_filter(f, BATCH_VP_CYCLE, b, z, n_z)) != RFSGPU_OK) return rc;
-  if (scan && (n_scan < 2 || n_scan > RFSGPU_VP_MAX_SCAN)) return batch_fail(f, BATCH_VP_CYCLE, "laser scan size out of range (2 ... RFSGPU_VP_MAX_SCAN beams)");
-  if (!scan && f->B.nScan < 2) return batch_fail(f, BATCH_VP_CYCLE, "the batch has not been given a laser scan (rfsgpu_set_laser_scan, or this call's scan)");
-  if (f->bVpFastSlam)
+  if ((rc = batch_check_scan(f, BATCH_VP_CYCLE, scan, n_scan)) != RFSGPU_OK) return rc;
+  if (f->bSteps == STEPS_FASTSLAM)
     return fail(f, RFSGPU_ERR_UNSUPPORTED, "batch_vp_cycle: this batch steps FastSLAM filters (rfsgpu_batch_vp_serve_fastslam is on; its cycle is rfsgpu_batch_vp_fastslam_cycle_async): a batch is of one kind");
-  f->bVpRbphdRan = true;
+  batch_vp_cycle_ran(f);
   return batch_vp_cycle_core(f, predict, x, x_cov, cov_stride, z, n_z, scan, n_scan, normalize);
 }
 
@@ -4058,16 +4102,16 @@ int rfsgpu_batch_set_fastslam_config(rfsgpu_filter *f, int filter, const rfsgpu_
   CHECK_HANDLE(f);
   int rc = batch_check(f, filter);
   if (rc != RFSGPU_OK) return rc;
-  if (!f->bVpFastSlam && !f->vpMh) { REFUSE_ON_VP_BATCH(f, "rfsgpu_batch_set_fastslam_config"); }     // (rfsgpu_batch_vp_serve_fastslam switches it on; rfsgpu_create_batch_vp_mh has it from creation)
+  if (batch_is_vp(f) && f->bSteps == STEPS_RBPHD) return refuse_on_kind(f, "rfsgpu_batch_set_fastslam_config", ON_VP_BATCH);     // (rfsgpu_batch_vp_serve_fastslam switches it on; rfsgpu_create_batch_vp_mh has it from creation)
   if (!cfg) return fail(f, RFSGPU_ERR_INVALID, "batch_set_fastslam_config: null configuration");
   const std::string who = filter < 0 ? std::string("every filter") : "filter " + std::to_string(filter);
-  if (f->vpMh) {     // (one hypothesis is the sparse single-hypothesis association on a handle, whose bits Murty with a limit of one does not give)
+  if (batch_is_vp_mh(f)) {     // (one hypothesis is the sparse single-hypothesis association on a handle, whose bits Murty with a limit of one does not give)
     if (cfg->maxNDataAssocHypotheses < 2u || cfg->maxNDataAssocHypotheses > (unsigned)FSMH_MAX_HYP) {
       f->err = "batch_set_fastslam_config: " + who + ": maxNDataAssocHypotheses must be in [2, 16] on a batch of Victoria Park multi-hypothesis filters (rfsgpu_create_batch_vp_mh); "
                "single-hypothesis filters belong to a batch with rfsgpu_batch_vp_serve_fastslam";
       return RFSGPU_ERR_UNSUPPORTED;
     }
-  } else if (f->mhBatch) {
+  } else if (batch_is_mh(f)) {
     if (cfg->maxNDataAssocHypotheses < 1u || cfg->maxNDataAssocHypotheses > (unsigned)FSMH_MAX_HYP) {
       f->err = "batch_set_fastslam_config: " + who + ": maxNDataAssocHypotheses must be in [1, 16]";
       return RFSGPU_ERR_UNSUPPORTED;
@@ -4077,15 +4121,14 @@ int rfsgpu_batch_set_fastslam_config(rfsgpu_filter *f, int filter, const rfsgpu_
     return RFSGPU_ERR_UNSUPPORTED;
   }
   // (a batch of Victoria Park FastSLAM filters keeps candidate lists: both of its resampling routes move them with the particle)
-  if (cfg->landmarkCandidateMeasurementCountThreshold != 1u && !f->bVpFastSlam && !f->vpMh) {
+  if (cfg->landmarkCandidateMeasurementCountThreshold != 1u && !batch_is_vp(f)) {
     f->err = "batch_set_fastslam_config: " + who + ": landmarkCandidateMeasurementCountThreshold must be 1 on a filter batch (landmark candidate lists would have to travel with a resampling)";
     return RFSGPU_ERR_UNSUPPORTED;
   }
-  if (f->bKind == 1)
+  if (f->bSteps == STEPS_RBPHD)
     return fail(f, RFSGPU_ERR_UNSUPPORTED, "batch_set_fastslam_config: this batch steps RB-PHD filters (rfsgpu_batch_cycle_async has run): a batch is of one kind");
   for (int b = (filter < 0 ? 0 : filter); b < (filter < 0 ? f->nF : filter + 1); b++) f->bFs[b] = *cfg;
-  if (f->mhBatch) return RFSGPU_OK;     // (its kind was decided at creation)
-  f->bKind = 2;      // a FastSLAM batch from here on: the [metric] calls read the Gaussians' weights as log-odds
+  batch_decide(f, STEPS_FASTSLAM);      // an undecided batch is a FastSLAM batch from here on: the [metric] calls read the Gaussians' weights as log-odds
   return RFSGPU_OK;
 }
 int rfsgpu_batch_fastslam_cycle_async(rfsgpu_filter *f, int predict, const double *x, const double *x_cov, int cov_stride, const double *z, const int *n_z,
@@ -4093,17 +4136,17 @@ int rfsgpu_batch_fastslam_cycle_async(rfsgpu_filter *f, int predict, const doubl
   CHECK_HANDLE(f);
   int rc = batch_check(f, -1);
   if (rc != RFSGPU_OK) return rc;
-  REFUSE_ON_VP_BATCH(f, "rfsgpu_batch_fastslam_cycle_async");
-  REFUSE_ON_MH_BATCH(f, "rfsgpu_batch_fastslam_cycle_async");
+  if (batch_is_vp(f)) return refuse_on_kind(f, "rfsgpu_batch_fastslam_cycle_async", ON_VP_BATCH);
+  if (!batch_fills_blocks(f)) return refuse_on_kind(f, "rfsgpu_batch_fastslam_cycle_async", ON_MH_BATCH);
   if ((rc = batch_check_call(f, BATCH_FS_CYCLE, predict, x_cov, cov_stride, n_z)) != RFSGPU_OK) return rc;
   const int nF = f->nF;
   for (int b = 0; b < nF; b++)
     if ((rc = batch_check_filter(f, BATCH_FS_CYCLE, b, z, n_z)) != RFSGPU_OK) return rc;
-  if (f->bKind == 1)
+  if (f->bSteps == STEPS_RBPHD)
     return fail(f, RFSGPU_ERR_UNSUPPORTED, "batch_fastslam_cycle: this batch steps RB-PHD filters (rfsgpu_batch_cycle_async has run): a batch is of one kind");
   if (f->bSensed)
     return fail(f, RFSGPU_ERR_UNSUPPORTED, "batch_fastslam_cycle: this batch has run a sensed cycle (rfsgpu_batch_fastslam_cycle_sensed_async): its measurement counts live on the device, the host-fed cycle no longer knows them");
-  f->bKind = 2;
+  batch_decide(f, STEPS_FASTSLAM);
   return batch_fs_cycle_core(f, predict, x, x_cov, cov_stride, z, n_z, normalize);
 }
 // ---- ... of Victoria Park filters: the switch that makes a batch created with RFSGPU_MODEL_VICTORIAPARK_3D a batch of FastSLAM filters,
@@ -4112,40 +4155,29 @@ int rfsgpu_batch_fastslam_cycle_async(rfsgpu_filter *f, int predict, const doubl
 static const BatchCall BATCH_VP_FS_CYCLE{"batch_vp_fastslam_cycle", -1, "RFSGPU_CYCLE_NO_PREDICT (-1), or 0 / 1 (the static landmark step; FastSLAM has no births)", "null measurement counts"};
 int rfsgpu_batch_vp_serve_fastslam(rfsgpu_filter *f, int on) {
   CHECK_HANDLE(f);
-  if (!f->batch || f->D != 3 || f->mhBatch) {
-    f->err = std::string("batch_vp_serve_fastslam: the switch is for a batch of Victoria Park filters (rfsgpu_create_batch with RFSGPU_MODEL_VICTORIAPARK_3D), not ") +
-             (f->batch ? (f->mhBatch ? "a batch of multi-hypothesis FastSLAM filters (rfsgpu_create_batch_mh)" : "a 2-D batch (rfsgpu_batch_set_fastslam_config makes it a FastSLAM batch)")
-                       : (f->groupShard ? "a shard of an rfsgpu_group" : "an ordinary handle (rfsgpu_set_fastslam_config, rfsgpu_fastslam_update)"));
-    return RFSGPU_ERR_UNSUPPORTED;
-  }
-  if (on && f->bVpRbphdRan)
+  if (!batch_is_vp(f) || batch_is_mh(f))
+    return refuse_not(f, "batch_vp_serve_fastslam: the switch is for a batch of Victoria Park filters (rfsgpu_create_batch with RFSGPU_MODEL_VICTORIAPARK_3D)");
+  const BatchSteps want = on ? STEPS_FASTSLAM : STEPS_RBPHD;
+  if (on && !batch_vp_may_step(f, want))
     return fail(f, RFSGPU_ERR_UNSUPPORTED, "batch_vp_serve_fastslam: this batch steps RB-PHD filters (rfsgpu_batch_vp_cycle_async has run): a batch is of one kind");
   if (on && f->estServeVpBatch)
     return fail(f, RFSGPU_ERR_UNSUPPORTED, "batch_vp_serve_fastslam: this batch serves the [estimate] log of RB-PHD filters (rfsgpu_batch_vp_serve_estimates is on): switch that off first");
-  if (!on && f->bVpFsRan)
+  if (!on && !batch_vp_may_step(f, want))
     return fail(f, RFSGPU_ERR_UNSUPPORTED, "batch_vp_serve_fastslam: this batch steps FastSLAM filters (rfsgpu_batch_vp_fastslam_cycle_async has run): a batch is of one kind");
-  f->bVpFastSlam = on != 0;
-  f->bKind = on ? 2 : 1;     // (2: the device route's gates are the FastSLAM configuration's, batch_resample_core)
+  f->bSteps = want;     // (FastSLAM: the device route's gates are the FastSLAM configuration's, batch_resample_core)
   return RFSGPU_OK;
 }
 int rfsgpu_batch_vp_fastslam_cycle_async(rfsgpu_filter *f, int predict, const double *x, const double *x_cov, int cov_stride, const double *z, const int *n_z,
                                          const double *scan, int n_scan, int normalize) {
   CHECK_HANDLE(f);
-  if (!f->batch || f->D != 3 || !f->bVpFastSlam) {
-    f->err = std::string("batch_vp_fastslam_cycle: the call serves a batch of Victoria Park FastSLAM filters (rfsgpu_create_batch with RFSGPU_MODEL_VICTORIAPARK_3D, then rfsgpu_batch_vp_serve_fastslam), not ") +
-             (f->batch ? (f->D == 3 ? (f->vpMh ? "a batch of Victoria Park multi-hypothesis FastSLAM filters (rfsgpu_create_batch_vp_mh): its cycle is rfsgpu_batch_vp_fastslam_mh_cycle_async"
-                                               : "a batch of Victoria Park filters whose switch is off (it steps RB-PHD filters: rfsgpu_batch_vp_cycle_async)")
-                                    : (f->mhBatch ? "a batch of multi-hypothesis FastSLAM filters (rfsgpu_batch_fastslam_mh_cycle_async)" : "a 2-D batch (rfsgpu_batch_fastslam_cycle_async)"))
-                       : (f->groupShard ? "a shard of an rfsgpu_group" : "an ordinary handle (rfsgpu_fastslam_update)"));
-    return RFSGPU_ERR_UNSUPPORTED;
-  }
+  if (!batch_is_vp_fastslam(f))
+    return refuse_not(f, "batch_vp_fastslam_cycle: the call serves a batch of Victoria Park FastSLAM filters (rfsgpu_create_batch with RFSGPU_MODEL_VICTORIAPARK_3D, then rfsgpu_batch_vp_serve_fastslam)");
   int rc = RFSGPU_OK;
   if ((rc = batch_check_call(f, BATCH_VP_FS_CYCLE, predict, x_cov, cov_stride, n_z)) != RFSGPU_OK) return rc;
   for (int b = 0; b < f->nF; b++)
     if ((rc = batch_check_filter(f, BATCH_VP_FS_CYCLE, b, z, n_z)) != RFSGPU_OK) return rc;
-  if (scan && (n_scan < 2 || n_scan > RFSGPU_VP_MAX_SCAN)) return batch_fail(f, BATCH_VP_FS_CYCLE, "laser scan size out of range (2 ... RFSGPU_VP_MAX_SCAN beams)");
-  if (!scan && f->B.nScan < 2) return batch_fail(f, BATCH_VP_FS_CYCLE, "the batch has not been given a laser scan (rfsgpu_set_laser_scan, or this call's scan)");
-  f->bVpFsRan = true;
+  if ((rc = batch_check_scan(f, BATCH_VP_FS_CYCLE, scan, n_scan)) != RFSGPU_OK) return rc;
+  batch_vp_cycle_ran(f);
   return batch_fs_cycle_core(f, predict, x, x_cov, cov_stride, z, n_z, normalize, scan, n_scan);
 }
 // The cycle behind rfsgpu_batch_fastslam_cycle_async (n_z given: the host's sets and records go to the device first) and
@@ -4162,14 +4194,7 @@ static int batch_fs_cycle_core(rfsgpu_filter *f, int predict, const double *x, c
   long long t0 = now_ns();
   if (!f->fsArena) HIPCHK(hipMalloc(&f->fsArena, (size_t)f->Ncap * fs_arena_bytes()));   // the Hungarian scratch of every slot of the batch, once
   batch_handle_wide(f, x, x_cov, cov_stride);
-  if (scan) {     // every filter's clutter density on the host (it travels in the Params table), the beams by copy command below
-    double area = 0;
-    for (int q = 1; q < n_scan; q++) area += scan[q] * scan[q - 1];
-    area += scan[0] * scan[n_scan - 1];
-    area *= sin(acos(-1) / 360) / 2;
-    f->vpClutter = f->vp.expectedClutterNumber / area;
-    batch_scan_clutter(f, area);
-  }
+  if (scan) scan_clutter(f, scan, n_scan);     // every filter's clutter density on the host (it travels in the Params table); the beams by copy command below
   if (sensed) rc = batch_sensed_records(f, f->dFsFilt, 0ull, [&](FsBatchFilter &T, int b) {
     T.F = fs_params_of(f->bFs[b], f->bParamsHost[b], 2, 1);
     T.pruneT = f->bFs[b].mapExistencePruneThreshold;
@@ -4180,17 +4205,7 @@ static int batch_fs_cycle_core(rfsgpu_filter *f, int predict, const double *x, c
     T.prune = ((unsigned)n_z[b] >= f->bFs[b].pruningMeasurementsThreshold) ? 1 : 0;
   });
   if (rc != RFSGPU_OK) return rc;
-  if (scan) {     // the host's new poses and the scan through one block of the staging ring (batch_vp_cycle_core's layout)
-    double *h = nullptr;
-    int ks = 0;
-    if ((rc = ring_acquire(f, f->stage, &h, &ks)) != RFSGPU_OK) return rc;
-    if (x && (rc = push_poses(f, h, f->B.pose, x, x_cov, cov_stride)) != RFSGPU_OK) return rc;
-    double *hs = h + (size_t)f->Ncap * 22;
-    memcpy(hs, scan, (size_t)n_scan * sizeof(double));
-    HIPCHK(hipMemcpyAsync(f->B.scan, hs, (size_t)n_scan * sizeof(double), hipMemcpyHostToDevice, f->stream));
-    f->B.nScan = n_scan;
-    HIPCHK(hipEventRecord(f->stage.ev[ks], f->stream));
-  } else if (x && (rc = batch_push_poses(f, x, x_cov, cov_stride)) != RFSGPU_OK) return rc;
+  if ((rc = batch_push_poses_scan(f, x, x_cov, cov_stride, scan, n_scan)) != RFSGPU_OK) return rc;
   f->bBirthAlt = false;      // (no births here: the poses from before a propagation are not needed)
   FsBatchArg A{f->dFsFilt, f->dBParams, f->dBZ, f->dBErrFilter, f->nPer, predict >= 0 ? 1 : 0};
   const size_t b2 = fs_batch_lds_bytes(f->cap, 2, D), b1 = fs_batch_lds_bytes(f->cap, 1, D);
@@ -4223,14 +4238,7 @@ static int batch_fs_cycle_core(rfsgpu_filter *f, int predict, const double *x, c
   else fs_new_landmarks_kernel<2, true, FsBatchArg><<<(f->N + FS_NEWLM_WPB - 1) / FS_NEWLM_WPB, 64 * FS_NEWLM_WPB, 0, f->stream>>>(f->B, f->P, FsParams{}, f->cur, 0, A);
   fs_batch_post_kernel<<<nF, 256, 0, f->stream>>>(f->B.weight, A, f->dBSums, normalize, f->bDevRoute ? f->BL.resampled : nullptr);
   HIPCHK(hipGetLastError());
-  if (!sensed)
-    for (int b = 0; b < nF; b++)
-      if (n_z[b] > 0) { f->bNZ[b] = n_z[b]; f->bResampled[b] = 0; }
-  f->bSenseFresh = false;     // (either kind of cycle: the next sensed cycle needs a sense call of its own)
-  f->bSensedTail = sensed;
-  if (!sensed) f->bScanHeld = false;     // (the host's sets lie over the sensor's)
-  f->holes = false;
-  f->timing.mapUpdate_cpu += now_ns() - t0;
+  batch_cycle_done(f, n_z, false, false, t0);     // (`cur` was flipped behind the prune)
   return RFSGPU_OK;
 }
 // ---- a batch of multi-hypothesis FastSLAM filters (fastslam_cycle.h, the kernels at its end) -------------------------------------
@@ -4258,9 +4266,7 @@ static int create_batch_mh_of(rfsgpu_filter **out, int model, int n_filters, int
   rfsgpu_filter *f = nullptr;
   int rc = rfsgpu_create_batch(&f, model, n_filters, max_per_filter, device_id, gm_capacity);
   if (rc != RFSGPU_OK) return rc;
-  f->mhBatch = true;
-  f->vpMh = model == RFSGPU_MODEL_VICTORIAPARK_3D;
-  f->bKind = 3;
+  batch_born_mh(f);
   f->nInitPer = n_per_filter;
   f->mhbLastNZ.assign(n_filters, 0);
   for (auto &c : f->bFs) c.nParticlesMax = 3 * n_per_filter;      // FastSLAM.hpp:250
@@ -4327,16 +4333,13 @@ int rfsgpu_batch_fastslam_mh_cycle_async(rfsgpu_filter *f, int predict, const do
   if (!f) return RFSGPU_ERR_INVALID;
   int rc = batch_check(f, -1);
   if (rc != RFSGPU_OK) return rc;
-  if (!f->mhBatch) return fail(f, RFSGPU_ERR_UNSUPPORTED, "batch_fastslam_mh_cycle: not a batch of multi-hypothesis FastSLAM filters (rfsgpu_create_batch_mh)");
-  if (f->vpMh) return fail(f, RFSGPU_ERR_UNSUPPORTED, "batch_fastslam_mh_cycle: this is the 2-D cycle; a batch of Victoria Park multi-hypothesis filters (rfsgpu_create_batch_vp_mh) takes rfsgpu_batch_vp_fastslam_mh_cycle_async");
+  if (!batch_is_mh(f)) return fail(f, RFSGPU_ERR_UNSUPPORTED, "batch_fastslam_mh_cycle: not a batch of multi-hypothesis FastSLAM filters (rfsgpu_create_batch_mh)");
+  if (batch_is_vp(f)) return fail(f, RFSGPU_ERR_UNSUPPORTED, "batch_fastslam_mh_cycle: this is the 2-D cycle; a batch of Victoria Park multi-hypothesis filters (rfsgpu_create_batch_vp_mh) takes rfsgpu_batch_vp_fastslam_mh_cycle_async");
   if ((rc = batch_check_call(f, BATCH_MH_CYCLE, predict, x_cov, cov_stride, u01 ? n_z : nullptr)) != RFSGPU_OK) return rc;
   const int nF = f->nF;
   for (int b = 0; b < nF; b++) {
     if ((rc = batch_check_filter(f, BATCH_MH_CYCLE, b, z, n_z)) != RFSGPU_OK) return rc;
-    if (!(u01[b] >= 0.0 && u01[b] < 1.0)) {
-      f->err = "batch_fastslam_mh_cycle: filter " + std::to_string(b) + ": u01 must lie in [0, 1)";
-      return RFSGPU_ERR_INVALID;
-    }
+    if ((rc = batch_check_u01(f, BATCH_MH_CYCLE, b, u01)) != RFSGPU_OK) return rc;
   }
   if (f->bSensed)
     return fail(f, RFSGPU_ERR_UNSUPPORTED, "batch_fastslam_mh_cycle: this batch has run a sensed cycle (rfsgpu_batch_fastslam_mh_cycle_sensed_async): its measurement counts live on the device, the host-fed cycle no longer knows them");
@@ -4347,32 +4350,22 @@ static const BatchCall BATCH_VP_MH_CYCLE{"batch_vp_fastslam_mh_cycle", 0, "0 or 
 int rfsgpu_batch_vp_fastslam_mh_cycle_async(rfsgpu_filter *f, int predict, const double *x, const double *x_cov, int cov_stride, const double *z, const int *n_z,
                                             const double *scan, int n_scan, const double *u01) {
   if (!f) return RFSGPU_ERR_INVALID;
-  if (!f->vpMh) {
+  if (!batch_is_vp_mh(f)) {
     if (f->mhcPending || f->mhcStashedRc || f->mhbPending || f->rsPending || f->rcPending) { const int rcp = mhc_resolve(f); if (rcp != RFSGPU_OK) return rcp; }
-    f->err = std::string("batch_vp_fastslam_mh_cycle: the call serves a batch of Victoria Park multi-hypothesis FastSLAM filters (rfsgpu_create_batch_vp_mh), not ") +
-             (f->batch ? (f->mhBatch ? "a 2-D batch of multi-hypothesis FastSLAM filters (rfsgpu_batch_fastslam_mh_cycle_async)"
-                                     : (f->D == 3 ? (f->bVpFastSlam ? "a batch of Victoria Park FastSLAM filters (rfsgpu_batch_vp_fastslam_cycle_async)"
-                                                                    : "a batch of Victoria Park RB-PHD filters (rfsgpu_batch_vp_cycle_async)")
-                                                  : "a 2-D batch (rfsgpu_batch_cycle_async, rfsgpu_batch_fastslam_cycle_async)"))
-                       : (f->groupShard ? "a shard of an rfsgpu_group" : "an ordinary handle (rfsgpu_fastslam_cycle_full_async)"));
-    return RFSGPU_ERR_UNSUPPORTED;
+    return refuse_not(f, "batch_vp_fastslam_mh_cycle: the call serves a batch of Victoria Park multi-hypothesis FastSLAM filters (rfsgpu_create_batch_vp_mh)");
   }
   int rc = RFSGPU_OK;
   if ((rc = batch_check_call(f, BATCH_VP_MH_CYCLE, predict, x_cov, cov_stride, u01 ? n_z : nullptr)) != RFSGPU_OK) return rc;
   const int nF = f->nF;
   for (int b = 0; b < nF; b++) {
     if ((rc = batch_check_filter(f, BATCH_VP_MH_CYCLE, b, z, n_z)) != RFSGPU_OK) return rc;
-    if (!(u01[b] >= 0.0 && u01[b] < 1.0)) {
-      f->err = "batch_vp_fastslam_mh_cycle: filter " + std::to_string(b) + ": u01 must lie in [0, 1)";
-      return RFSGPU_ERR_INVALID;
-    }
+    if ((rc = batch_check_u01(f, BATCH_VP_MH_CYCLE, b, u01)) != RFSGPU_OK) return rc;
     if (f->bFs[b].maxNDataAssocHypotheses < 2u || f->bFs[b].maxNDataAssocHypotheses > (unsigned)FSMH_MAX_HYP) {
       f->err = "batch_vp_fastslam_mh_cycle: filter " + std::to_string(b) + ": maxNDataAssocHypotheses must be in [2, 16] (rfsgpu_batch_set_fastslam_config)";
       return RFSGPU_ERR_UNSUPPORTED;
     }
   }
-  if (scan && (n_scan < 2 || n_scan > RFSGPU_VP_MAX_SCAN)) return batch_fail(f, BATCH_VP_MH_CYCLE, "laser scan size out of range (2 ... RFSGPU_VP_MAX_SCAN beams)");
-  if (!scan && f->B.nScan < 2) return batch_fail(f, BATCH_VP_MH_CYCLE, "the batch has not been given a laser scan (rfsgpu_set_laser_scan, or this call's scan)");
+  if ((rc = batch_check_scan(f, BATCH_VP_MH_CYCLE, scan, n_scan)) != RFSGPU_OK) return rc;
   return batch_mh_cycle_core(f, predict, x, x_cov, cov_stride, z, n_z, u01, 0ull, scan, n_scan);
 }
 // The cycle behind rfsgpu_batch_fastslam_mh_cycle_async (n_z, u01 given: the host's sets and records go to the device first) and
@@ -4392,14 +4385,7 @@ static int batch_mh_cycle_core(rfsgpu_filter *f, int predict, const double *x, c
   if (!f->mhArena) HIPCHK(hipMalloc(&f->mhArena, (size_t)N * L.total));          // every slot's table / Murty arena / assignments, once
   if (!f->mhcInts) HIPCHK(hipMalloc(&f->mhcInts, (size_t)4 * N * sizeof(int)));
   batch_handle_wide(f, x, x_cov, cov_stride);
-  if (scan) {     // every filter's clutter density on the host (it travels in the Params table), the beams by copy command below
-    double area = 0;
-    for (int q = 1; q < n_scan; q++) area += scan[q] * scan[q - 1];
-    area += scan[0] * scan[n_scan - 1];
-    area *= sin(acos(-1) / 360) / 2;
-    f->vpClutter = f->vp.expectedClutterNumber / area;
-    batch_scan_clutter(f, area);
-  }
+  if (scan) scan_clutter(f, scan, n_scan);     // every filter's clutter density on the host (it travels in the Params table); the beams by copy command below
   // (the record's static part: one filler for both routes; nz 1 where the device derives pfa)
   auto fillStatic = [&](MhBatchFilter &T, int b, int nz) {
     const rfsgpu_fastslam_config &c = f->bFs[b];
@@ -4425,17 +4411,7 @@ static int batch_mh_cycle_core(rfsgpu_filter *f, int predict, const double *x, c
     });
   }
   if (rc != RFSGPU_OK) return rc;
-  if (scan) {     // the host's new poses and the scan through one block of the staging ring (batch_vp_cycle_core's layout)
-    double *h = nullptr;
-    int ks = 0;
-    if ((rc = ring_acquire(f, f->stage, &h, &ks)) != RFSGPU_OK) return rc;
-    if (x && (rc = push_poses(f, h, f->B.pose, x, x_cov, cov_stride)) != RFSGPU_OK) return rc;
-    double *hs = h + (size_t)f->Ncap * 22;
-    memcpy(hs, scan, (size_t)n_scan * sizeof(double));
-    HIPCHK(hipMemcpyAsync(f->B.scan, hs, (size_t)n_scan * sizeof(double), hipMemcpyHostToDevice, f->stream));
-    f->B.nScan = n_scan;
-    HIPCHK(hipEventRecord(f->stage.ev[ks], f->stream));
-  } else if (x && (rc = batch_push_poses(f, x, x_cov, cov_stride)) != RFSGPU_OK) return rc;     // (every slot of every block)
+  if ((rc = batch_push_poses_scan(f, x, x_cov, cov_stride, scan, n_scan)) != RFSGPU_OK) return rc;     // (every slot of every block)
   f->bBirthAlt = false;
   FsCycleState S0;      // filter 0's view: its slot arrays are the batch's, [N] each, holding slots local to each filter's block
   mhb_view(f, f->mhbBlock, 0, S0);
@@ -4478,19 +4454,10 @@ static int batch_mh_cycle_core(rfsgpu_filter *f, int predict, const double *x, c
   mhb_weight_sums_kernel<<<nF, 1024, 0, f->stream>>>(f->B.weight, f->dBSums, Arenorm);
   mhb_normalize_kernel<<<(N + 255) / 256, 256, 0, f->stream>>>(f->B.weight, N, f->dBSums, Arenorm);
   HIPCHK(hipGetLastError());
-  if (!sensed)      // (a sensed cycle: mhb_resolve takes the counts from the records on the device)
-    for (int b = 0; b < nF; b++) {
-      f->mhbLastNZ[b] = n_z[b];
-      if (n_z[b] > 0) f->bNZ[b] = n_z[b];
-    }
-  f->bSenseFresh = false;     // (either kind of cycle: the next sensed cycle needs a sense call of its own)
-  f->bSensedTail = false;     // (the resampling is inside the cycle)
-  if (!sensed) f->bScanHeld = false;     // (the host's sets lie over the sensor's)
-  f->holes = false;
-  f->mhbLastSensed = sensed;
+  f->mhbLastSensed = sensed;      // (a sensed cycle: mhb_resolve takes the counts from the records on the device)
   f->mhbPending = true;
   f->mhbHave = true;
-  f->timing.mapUpdate_cpu += now_ns() - t0;
+  batch_cycle_done(f, n_z, false, true, t0);     // (`cur` was flipped behind the prune)
   return RFSGPU_OK;
 }
 // The last cycle of every filter (synchronising).  Per-filter arrays [n_filters]; parent and plan [n_filters * max_per_filter] in slots
@@ -4500,7 +4467,7 @@ int rfsgpu_batch_fastslam_last_cycle(rfsgpu_filter *f, int *n_after_update, int 
   CHECK_HANDLE(f);
   int rc = batch_check(f, -1);
   if (rc != RFSGPU_OK) return rc;
-  if (!f->mhBatch) return fail(f, RFSGPU_ERR_UNSUPPORTED, "batch_fastslam_last_cycle: not a batch of multi-hypothesis FastSLAM filters (rfsgpu_create_batch_mh)");
+  if (!batch_is_mh(f)) return fail(f, RFSGPU_ERR_UNSUPPORTED, "batch_fastslam_last_cycle: not a batch of multi-hypothesis FastSLAM filters (rfsgpu_create_batch_mh)");
   if (!f->mhbHave) return fail(f, RFSGPU_ERR_INVALID, "batch_fastslam_last_cycle: no rfsgpu_batch_fastslam_mh_cycle_async has run on this handle");
   const int stride = f->nPer;
   for (int b = 0; b < f->nF; b++) {
@@ -4524,7 +4491,7 @@ int rfsgpu_batch_live_counts(rfsgpu_filter *f, int *out) {
   CHECK_HANDLE(f);
   int rc = batch_check(f, -1);
   if (rc != RFSGPU_OK) return rc;
-  if (!f->mhBatch) return fail(f, RFSGPU_ERR_UNSUPPORTED, "batch_live_counts: not a batch of multi-hypothesis FastSLAM filters (rfsgpu_create_batch_mh)");
+  if (!batch_is_mh(f)) return fail(f, RFSGPU_ERR_UNSUPPORTED, "batch_live_counts: not a batch of multi-hypothesis FastSLAM filters (rfsgpu_create_batch_mh)");
   if (!out) return fail(f, RFSGPU_ERR_INVALID, "batch_live_counts: null output");
   for (int b = 0; b < f->nF; b++) {
     FsCycleState H;
@@ -4538,7 +4505,7 @@ int rfsgpu_batch_weight_sums(rfsgpu_filter *f, double *out) {
   CHECK_HANDLE(f);
   int rc = batch_check(f, -1);
   if (rc != RFSGPU_OK) return rc;
-  REFUSE_ON_MH_BATCH(f, "rfsgpu_batch_weight_sums");
+  if (!batch_fills_blocks(f)) return refuse_on_kind(f, "rfsgpu_batch_weight_sums", ON_MH_BATCH);
   if (!out) return fail(f, RFSGPU_ERR_INVALID, "batch_weight_sums: null output");
   hipSetDevice(f->device);
   batch_weight_sums_kernel<<<f->nF, 256, 0, f->stream>>>(f->B.weight, f->nPer, f->dBSums);
@@ -4553,7 +4520,7 @@ int rfsgpu_batch_resample_apply(rfsgpu_filter *f, const int *src_slot, const uns
   CHECK_HANDLE(f);
   int rc = batch_check(f, -1);
   if (rc != RFSGPU_OK) return rc;
-  REFUSE_ON_MH_BATCH(f, "rfsgpu_batch_resample_apply");
+  if (!batch_fills_blocks(f)) return refuse_on_kind(f, "rfsgpu_batch_resample_apply", ON_MH_BATCH);
   if (!src_slot || !resampled) return fail(f, RFSGPU_ERR_INVALID, "batch_resample_apply: null argument");
   if (f->bDevRoute)
     return fail(f, RFSGPU_ERR_UNSUPPORTED, "batch_resample_apply: this batch resamples on the device (rfsgpu_batch_resample_async or rfsgpu_batch_vp_resample_async has run): the particle ids, resampleOccured_ "
@@ -4637,7 +4604,7 @@ int rfsgpu_batch_set_motion_odometry(rfsgpu_filter *f, int filter, const double 
   CHECK_HANDLE(f);
   int rc = batch_check(f, filter);
   if (rc != RFSGPU_OK) return rc;
-  REFUSE_ON_VP_BATCH(f, "rfsgpu_batch_set_motion_odometry");
+  if (batch_is_vp(f)) return refuse_on_kind(f, "rfsgpu_batch_set_motion_odometry", ON_VP_BATCH);
   if (!var || !(var[0] >= 0.0) || !(var[1] >= 0.0) || !(var[2] >= 0.0)) return fail(f, RFSGPU_ERR_INVALID, "batch_set_motion_odometry: var is three variances >= 0");
   for (int b = (filter < 0 ? 0 : filter); b < (filter < 0 ? f->nF : filter + 1); b++) {
     BatchMotion &M = f->bMotion[b];
@@ -4652,7 +4619,7 @@ int rfsgpu_batch_set_resampling(rfsgpu_filter *f, int filter, double eff_n, doub
   CHECK_HANDLE(f);
   int rc = batch_check(f, filter);
   if (rc != RFSGPU_OK) return rc;
-  if (!f->vpMh) { REFUSE_ON_VP_BATCH(f, "rfsgpu_batch_set_resampling"); }     // (the thresholds of the resampling inside its cycle, as on a 2-D multi-hypothesis batch)
+  if (batch_is_vp(f) && !batch_is_mh(f)) return refuse_on_kind(f, "rfsgpu_batch_set_resampling", ON_VP_BATCH);     // (the thresholds of the resampling inside its cycle, as on a 2-D multi-hypothesis batch)
   for (int b = (filter < 0 ? 0 : filter); b < (filter < 0 ? f->nF : filter + 1); b++) {
     f->bEffN[2 * (size_t)b] = eff_n; f->bEffN[2 * (size_t)b + 1] = eff_n_percent;
     f->bResSet[b] = 1;
@@ -4682,7 +4649,7 @@ int rfsgpu_batch_propagate_async(rfsgpu_filter *f, const double *u, const double
   CHECK_HANDLE(f);
   int rc = batch_check(f, -1);
   if (rc != RFSGPU_OK) return rc;
-  REFUSE_ON_VP_BATCH(f, "rfsgpu_batch_propagate_async");
+  if (batch_is_vp(f)) return refuse_on_kind(f, "rfsgpu_batch_propagate_async", ON_VP_BATCH);
   if (!u) return fail(f, RFSGPU_ERR_INVALID, "batch_propagate: null odometry input");
   const int nF = f->nF;
   for (int b = 0; b < nF; b++) {
@@ -4732,8 +4699,8 @@ int rfsgpu_batch_resample_async(rfsgpu_filter *f, const int *n_z, unsigned long 
   CHECK_HANDLE(f);
   int rc = batch_check(f, -1);
   if (rc != RFSGPU_OK) return rc;
-  REFUSE_ON_VP_BATCH(f, "rfsgpu_batch_resample_async");
-  REFUSE_ON_MH_BATCH(f, "rfsgpu_batch_resample_async");
+  if (batch_is_vp(f)) return refuse_on_kind(f, "rfsgpu_batch_resample_async", ON_VP_BATCH);
+  if (!batch_fills_blocks(f)) return refuse_on_kind(f, "rfsgpu_batch_resample_async", ON_MH_BATCH);
   if ((rc = batch_check_call(f, BATCH_RESAMPLE, 0, nullptr, 0, n_z)) != RFSGPU_OK) return rc;
   if (f->bSensed)
     return fail(f, RFSGPU_ERR_UNSUPPORTED, "batch_resample: this batch has run a sensed cycle (rfsgpu_batch_cycle_sensed_async or rfsgpu_batch_fastslam_cycle_sensed_async): its measurement counts live on the device (rfsgpu_batch_resample_sensed_async)");
@@ -4784,7 +4751,7 @@ static int batch_resample_core(rfsgpu_filter *f, const BatchCall &C, const int *
       BatchResIn &I = hi[b];
       I.effN = f->bEffN[2 * (size_t)b]; I.effNPercent = f->bEffN[2 * (size_t)b + 1];
       I.nZ = n_z ? n_z[b] : 0;
-      if (f->bKind == 2) { I.minUpdates = (int)f->bFs[b].minUpdatesBeforeResample; I.minMeasurements = (int)f->bFs[b].minMeasurementsBeforeResample; }   // (a FastSLAM batch: FastSLAM.hpp:729-733)
+      if (f->bSteps == STEPS_FASTSLAM) { I.minUpdates = (int)f->bFs[b].minUpdatesBeforeResample; I.minMeasurements = (int)f->bFs[b].minMeasurementsBeforeResample; }   // (a FastSLAM batch: FastSLAM.hpp:729-733)
       else { I.minUpdates = f->bCfg[b].minUpdatesBeforeResample; I.minMeasurements = f->bCfg[b].minMeasurementsBeforeResample; }
       I.pad = 0;
     }
@@ -4803,8 +4770,8 @@ int rfsgpu_batch_last_resample(rfsgpu_filter *f, unsigned char *fired, int *src_
   CHECK_HANDLE(f);
   int rc = batch_check(f, -1);
   if (rc != RFSGPU_OK) return rc;
-  REFUSE_ON_VP_BATCH(f, "rfsgpu_batch_last_resample");
-  REFUSE_ON_MH_BATCH(f, "rfsgpu_batch_last_resample");
+  if (batch_is_vp(f)) return refuse_on_kind(f, "rfsgpu_batch_last_resample", ON_VP_BATCH);
+  if (!batch_fills_blocks(f)) return refuse_on_kind(f, "rfsgpu_batch_last_resample", ON_MH_BATCH);
   return batch_last_resample_core(f, fired, src_slot, n_eff);
 }
 // (the arguments have been checked: rfsgpu_batch_last_resample, rfsgpu_batch_vp_last_resample)
@@ -4839,8 +4806,8 @@ int rfsgpu_batch_resample_counts(rfsgpu_filter *f, long long *out) {
   CHECK_HANDLE(f);
   int rc = batch_check(f, -1);
   if (rc != RFSGPU_OK) return rc;
-  REFUSE_ON_VP_BATCH(f, "rfsgpu_batch_resample_counts");
-  REFUSE_ON_MH_BATCH(f, "rfsgpu_batch_resample_counts");
+  if (batch_is_vp(f)) return refuse_on_kind(f, "rfsgpu_batch_resample_counts", ON_VP_BATCH);
+  if (!batch_fills_blocks(f)) return refuse_on_kind(f, "rfsgpu_batch_resample_counts", ON_MH_BATCH);
   if (!out) return fail(f, RFSGPU_ERR_INVALID, "batch_resample_counts: null output");
   hipSetDevice(f->device);
   HIPCHK(hipMemcpyAsync(out, f->BL.nResamples, (size_t)f->nF * sizeof(long long), hipMemcpyDeviceToHost, f->stream));
@@ -4853,7 +4820,8 @@ int rfsgpu_batch_resample_counts(rfsgpu_filter *f, long long *out) {
 static const BatchCall BATCH_VP_RESAMPLE{"batch_vp_resample", 0, nullptr, "null measurement counts"};
 static_assert(RFSGPU_BATCH_VP_RUN_MAX == ACKERMAN_RUN_MAX, "a run of a batch is what a handle's run launch takes (VpBatchRun, motion.h)");
 // What the section serves, else RFSGPU_ERR_UNSUPPORTED with the state untouched
-static int vp_loop_check(rfsgpu_filter *f, const char *who, int filter) {
+// resampling: a call of the resampling tail, which a batch of multi-hypothesis filters runs inside its cycle
+static int vp_loop_check(rfsgpu_filter *f, const char *who, int filter, bool resampling = false) {
   if (!f->batch || f->D != 3) {
     f->err = std::string(who) + ": the call serves a batch of Victoria Park filters (rfsgpu_create_batch with RFSGPU_MODEL_VICTORIAPARK_3D), not " +
              (f->batch ? "a 2-D batch (its device loop is rfsgpu_batch_set_motion_odometry, _set_resampling, _propagate_async, _resample_async)"
@@ -4861,6 +4829,10 @@ static int vp_loop_check(rfsgpu_filter *f, const char *who, int filter) {
     return RFSGPU_ERR_UNSUPPORTED;
   }
   if (filter < -1 || filter >= f->nF) { f->err = std::string(who) + ": filter index out of range"; return RFSGPU_ERR_INVALID; }
+  if (resampling && batch_is_mh(f)) {
+    f->err = std::string(who) + ": not available on " + handle_kind_text(f) + ": its resampling runs inside that cycle (thresholds: rfsgpu_batch_set_resampling; outcome: rfsgpu_batch_fastslam_last_cycle)";
+    return RFSGPU_ERR_UNSUPPORTED;
+  }
   return RFSGPU_OK;
 }
 int rfsgpu_batch_vp_set_motion(rfsgpu_filter *f, int filter, const double *var, const double *geom, unsigned long long seed) {
@@ -4883,9 +4855,8 @@ int rfsgpu_batch_vp_set_motion(rfsgpu_filter *f, int filter, const double *var, 
 }
 int rfsgpu_batch_vp_set_resampling(rfsgpu_filter *f, int filter, double eff_n, double eff_n_percent) {
   CHECK_HANDLE(f);
-  int rc = vp_loop_check(f, "batch_vp_set_resampling", filter);
+  int rc = vp_loop_check(f, "batch_vp_set_resampling", filter, true);
   if (rc != RFSGPU_OK) return rc;
-  if (f->vpMh) return fail(f, RFSGPU_ERR_UNSUPPORTED, "batch_vp_set_resampling: not available on a batch of Victoria Park multi-hypothesis FastSLAM filters (rfsgpu_create_batch_vp_mh): its resampling runs inside rfsgpu_batch_vp_fastslam_mh_cycle_async (thresholds: rfsgpu_batch_set_resampling; outcome: rfsgpu_batch_fastslam_last_cycle)");
   for (int b = (filter < 0 ? 0 : filter); b < (filter < 0 ? f->nF : filter + 1); b++) {
     f->bEffN[2 * (size_t)b] = eff_n; f->bEffN[2 * (size_t)b + 1] = eff_n_percent;
     f->bResSet[b] = 1;
@@ -4894,7 +4865,7 @@ int rfsgpu_batch_vp_set_resampling(rfsgpu_filter *f, int filter, double eff_n, d
 }
 int rfsgpu_batch_vp_propagate_run_async(rfsgpu_filter *f, int n, const double *u, const unsigned char *noisy, const double *dt, unsigned long long call0) {
   if (!f) return RFSGPU_ERR_INVALID;
-  if (!f->vpMh) { CHECK_HANDLE(f); }     // (a batch of multi-hypothesis filters: behind its cycles, nothing is read back)
+  if (!batch_is_vp_mh(f)) { CHECK_HANDLE(f); }     // (a batch of multi-hypothesis filters: behind its cycles, nothing is read back)
   int rc = vp_loop_check(f, "batch_vp_propagate_run", -1);
   if (rc != RFSGPU_OK) return rc;
   if (n < 0 || (n > 0 && (!u || !dt))) return fail(f, RFSGPU_ERR_INVALID, "batch_vp_propagate_run: bad arguments");
@@ -4924,7 +4895,7 @@ int rfsgpu_batch_vp_propagate_run_async(rfsgpu_filter *f, int n, const double *u
   HIPCHK(hipMemcpyAsync(f->dBVpRun, R, sizeof *R, hipMemcpyHostToDevice, f->stream));
   HIPCHK(hipEventRecord(f->bLoop.ev[k], f->stream));
   // in place: the caller orders the call behind the birth predict, which must still see the poses of the last update
-  if (f->vpMh) {     // (a filter whose overflow word is up stays where its abandoned cycle found it)
+  if (batch_is_mh(f)) {     // (a filter whose overflow word is up stays where its abandoned cycle found it)
     FsCycleState S0;
     mhb_state(f->mhbBlock, f->nF, f->nPer, 0, S0);
     vp_batch_propagate_run_guard_kernel<<<(f->N + 255) / 256, 256, 0, f->stream>>>(f->B.pose, f->N, f->nPer, f->dBVpMotion, f->dBVpRun, S0.w, FSC_WORDS, FSC_OVF);
@@ -4934,24 +4905,21 @@ int rfsgpu_batch_vp_propagate_run_async(rfsgpu_filter *f, int n, const double *u
 }
 int rfsgpu_batch_vp_resample_async(rfsgpu_filter *f, const int *n_z, unsigned long long call) {
   CHECK_HANDLE(f);
-  int rc = vp_loop_check(f, "batch_vp_resample", -1);
+  int rc = vp_loop_check(f, "batch_vp_resample", -1, true);
   if (rc != RFSGPU_OK) return rc;
-  if (f->vpMh) return fail(f, RFSGPU_ERR_UNSUPPORTED, "batch_vp_resample: not available on a batch of Victoria Park multi-hypothesis FastSLAM filters (rfsgpu_create_batch_vp_mh): its resampling runs inside rfsgpu_batch_vp_fastslam_mh_cycle_async (thresholds: rfsgpu_batch_set_resampling; outcome: rfsgpu_batch_fastslam_last_cycle)");
   if ((rc = batch_check_call(f, BATCH_VP_RESAMPLE, 0, nullptr, 0, n_z)) != RFSGPU_OK) return rc;
   return batch_resample_core(f, BATCH_VP_RESAMPLE, n_z, call);
 }
 int rfsgpu_batch_vp_last_resample(rfsgpu_filter *f, unsigned char *fired, int *src_slot, double *n_eff) {
   CHECK_HANDLE(f);
-  int rc = vp_loop_check(f, "batch_vp_last_resample", -1);
+  int rc = vp_loop_check(f, "batch_vp_last_resample", -1, true);
   if (rc != RFSGPU_OK) return rc;
-  if (f->vpMh) return fail(f, RFSGPU_ERR_UNSUPPORTED, "batch_vp_last_resample: not available on a batch of Victoria Park multi-hypothesis FastSLAM filters (rfsgpu_create_batch_vp_mh): its resampling runs inside rfsgpu_batch_vp_fastslam_mh_cycle_async (thresholds: rfsgpu_batch_set_resampling; outcome: rfsgpu_batch_fastslam_last_cycle)");
   return batch_last_resample_core(f, fired, src_slot, n_eff);
 }
 int rfsgpu_batch_vp_loop_counts(rfsgpu_filter *f, long long *resamplings, int *max_level) {
   CHECK_HANDLE(f);
-  int rc = vp_loop_check(f, "batch_vp_loop_counts", -1);
+  int rc = vp_loop_check(f, "batch_vp_loop_counts", -1, true);
   if (rc != RFSGPU_OK) return rc;
-  if (f->vpMh) return fail(f, RFSGPU_ERR_UNSUPPORTED, "batch_vp_loop_counts: not available on a batch of Victoria Park multi-hypothesis FastSLAM filters (rfsgpu_create_batch_vp_mh): its resampling runs inside rfsgpu_batch_vp_fastslam_mh_cycle_async (thresholds: rfsgpu_batch_set_resampling; outcome: rfsgpu_batch_fastslam_last_cycle)");
   hipSetDevice(f->device);
   int w[2] = {0, 0};
   if (resamplings) HIPCHK(hipMemcpyAsync(resamplings, f->BL.nResamples, (size_t)f->nF * sizeof(long long), hipMemcpyDeviceToHost, f->stream));
@@ -4972,37 +4940,31 @@ static const BatchCall BATCH_LAST_SCAN{"batch_last_scan", 0, nullptr, nullptr};
 // draw), which the sensed cycle of their kind derives on the device (fastslam_sensed.h); the switch is off at creation, so the refusals
 // the section was published with stand until a caller asks.
 static int sensor_check(rfsgpu_filter *f, const BatchCall &C) {
-  if (f->batch && f->D == 3) {
+  if (batch_is_vp(f)) {
     f->err = std::string(C.who) + ": the device sensor is a 2-D range-bearing sensor: it does not serve a batch of Victoria Park filters";
     return RFSGPU_ERR_UNSUPPORTED;
   }
-  const bool served = f->batch && f->bServeSensor;
-  const char *why = !f->batch ? (f->groupShard ? "a shard of an rfsgpu_group" : "an ordinary handle")
-                              : (served ? nullptr : (f->mhBatch ? "a batch of multi-hypothesis FastSLAM filters (rfsgpu_create_batch_mh)" : (f->bKind == 2 ? "a batch of FastSLAM filters" : nullptr)));
-  if (!why) return RFSGPU_OK;
-  f->err = std::string(C.who) + ": the device sensor serves batches of RB-PHD filters (rfsgpu_create_batch, rfsgpu_batch_cycle_async) only, not " + why;
+  // (a batch that has not decided serves as the RB-PHD batch its first sensed cycle makes it)
+  if (f->batch && (f->bServeSensor || !batch_log_odds(f))) return RFSGPU_OK;
+  f->err = std::string(C.who) + ": the device sensor serves batches of RB-PHD filters (rfsgpu_create_batch, rfsgpu_batch_cycle_async) only, not " + handle_kind_text(f);
   if (f->batch) f->err += " (rfsgpu_batch_fastslam_serve_sensor switches the section on for it)";
   return RFSGPU_ERR_UNSUPPORTED;
 }
 // The switch of a FastSLAM or multi-hypothesis batch: off at creation (rfsgpu_batch_mh_serve_metrics is the precedent).
 int rfsgpu_batch_fastslam_serve_sensor(rfsgpu_filter *f, int on) {
   CHECK_HANDLE(f);
-  if (f->batch && f->D == 3) return fail(f, RFSGPU_ERR_UNSUPPORTED, "batch_fastslam_serve_sensor: the device sensor is a 2-D range-bearing sensor: it does not serve a batch of Victoria Park filters");
-  const char *why = !f->batch ? (f->groupShard ? "a shard of an rfsgpu_group" : "an ordinary handle")
-                              : (f->mhBatch || f->bKind == 2 ? nullptr : (f->bKind == 1 ? "a batch of RB-PHD filters (the [sensor] calls serve it as it is)"
-                                                                                         : "a batch whose kind is not decided yet (rfsgpu_batch_set_fastslam_config decides it)"));
-  if (why) {
-    f->err = std::string("batch_fastslam_serve_sensor: the switch is for batches of FastSLAM or multi-hypothesis FastSLAM filters, not ") + why;
-    return RFSGPU_ERR_UNSUPPORTED;
-  }
+  if (batch_is_vp(f)) return fail(f, RFSGPU_ERR_UNSUPPORTED, "batch_fastslam_serve_sensor: the device sensor is a 2-D range-bearing sensor: it does not serve a batch of Victoria Park filters");
+  if (!f->batch || !batch_log_odds(f))
+    return refuse_not(f, "batch_fastslam_serve_sensor: the switch is for batches of FastSLAM or multi-hypothesis FastSLAM filters",
+                      f->bSteps == STEPS_RBPHD ? ": the [sensor] calls serve it as it is" : "");
   if (!on && f->bSensed)
     return fail(f, RFSGPU_ERR_INVALID, "batch_fastslam_serve_sensor: a sensed cycle has run on this handle: its measurement counts live on the device, the host-fed calls could not take over");
   hipSetDevice(f->device);
   HIPCHK(hipStreamSynchronize(f->stream));
   if (on && !f->dFsTmpl)
     HIPCHK(hipMalloc(&f->dFsTmpl, (size_t)f->nF * std::max(sizeof(FsSensedTemplate<FsBatchFilter>), sizeof(FsSensedTemplate<MhBatchFilter>))));
-  if (on && f->mhBatch && !f->dFsLastNZ) HIPCHK(hipMalloc(&f->dFsLastNZ, (size_t)f->nF * sizeof(int)));
-  if (on && f->mhBatch && !f->hFsLastNZ) HIPCHK(hipHostMalloc(&f->hFsLastNZ, (size_t)f->nF * sizeof(int)));
+  if (on && batch_is_mh(f) && !f->dFsLastNZ) HIPCHK(hipMalloc(&f->dFsLastNZ, (size_t)f->nF * sizeof(int)));
+  if (on && batch_is_mh(f) && !f->hFsLastNZ) HIPCHK(hipHostMalloc(&f->hFsLastNZ, (size_t)f->nF * sizeof(int)));
   f->bServeSensor = on != 0;
   if (!on) f->bSenseFresh = false;
   return RFSGPU_OK;
@@ -5138,8 +5100,8 @@ int rfsgpu_batch_cycle_sensed_async(rfsgpu_filter *f, int predict, const double 
   const BatchCall &C = BATCH_CYCLE_SENSED;
   int rc = sensor_check(f, C);
   if (rc != RFSGPU_OK) return rc;
-  if (f->mhBatch) return fail(f, RFSGPU_ERR_UNSUPPORTED, "batch_cycle_sensed: this is the RB-PHD cycle; a batch of multi-hypothesis FastSLAM filters (rfsgpu_create_batch_mh) takes rfsgpu_batch_fastslam_mh_cycle_sensed_async");
-  if (f->bKind == 2) return fail(f, RFSGPU_ERR_UNSUPPORTED, "batch_cycle_sensed: this is the RB-PHD cycle; a batch of FastSLAM filters takes rfsgpu_batch_fastslam_cycle_sensed_async");
+  if (batch_is_mh(f)) return fail(f, RFSGPU_ERR_UNSUPPORTED, "batch_cycle_sensed: this is the RB-PHD cycle; a batch of multi-hypothesis FastSLAM filters (rfsgpu_create_batch_mh) takes rfsgpu_batch_fastslam_mh_cycle_sensed_async");
+  if (f->bSteps == STEPS_FASTSLAM) return fail(f, RFSGPU_ERR_UNSUPPORTED, "batch_cycle_sensed: this is the RB-PHD cycle; a batch of FastSLAM filters takes rfsgpu_batch_fastslam_cycle_sensed_async");
   if ((rc = batch_check_call(f, C, predict, x_cov, cov_stride, nullptr)) != RFSGPU_OK) return rc;
   for (int b = 0; b < f->nF; b++) {
     if (!f->bSensorSet[b]) return batch_fail(f, C, "filter " + std::to_string(b) + " has no sensor (rfsgpu_batch_set_sensor)");
@@ -5163,7 +5125,7 @@ int rfsgpu_batch_cycle_sensed_async(rfsgpu_filter *f, int predict, const double 
   // rfsgpu_batch_resample_async does too: it moves the ids, it refuses nothing, and it stays if the cycle below fails.)
   if ((rc = batch_enter_dev_route(f)) != RFSGPU_OK) return rc;
   if ((rc = batch_cycle_core(f, predict, x, x_cov, cov_stride, nullptr, nullptr, normalize)) != RFSGPU_OK) return rc;
-  f->bKind = 1;
+  batch_decide(f, STEPS_RBPHD);
   f->bSensed = true;     // (only now: a cycle that failed leaves the host-fed calls open)
   return RFSGPU_OK;
 }
@@ -5187,9 +5149,9 @@ int rfsgpu_batch_fastslam_cycle_sensed_async(rfsgpu_filter *f, int predict, cons
   const BatchCall &C = BATCH_FS_CYCLE_SENSED;
   int rc = sensor_check(f, C);
   if (rc != RFSGPU_OK) return rc;
-  if (f->mhBatch) return fail(f, RFSGPU_ERR_UNSUPPORTED, "batch_fastslam_cycle_sensed: a batch of multi-hypothesis FastSLAM filters (rfsgpu_create_batch_mh) takes rfsgpu_batch_fastslam_mh_cycle_sensed_async");
-  if (f->bKind != 2)
-    return fail(f, RFSGPU_ERR_UNSUPPORTED, f->bKind == 1 ? "batch_fastslam_cycle_sensed: this batch steps RB-PHD filters (rfsgpu_batch_cycle_async has run): it takes rfsgpu_batch_cycle_sensed_async"
+  if (batch_is_mh(f)) return fail(f, RFSGPU_ERR_UNSUPPORTED, "batch_fastslam_cycle_sensed: a batch of multi-hypothesis FastSLAM filters (rfsgpu_create_batch_mh) takes rfsgpu_batch_fastslam_mh_cycle_sensed_async");
+  if (f->bSteps != STEPS_FASTSLAM)
+    return fail(f, RFSGPU_ERR_UNSUPPORTED, f->bSteps == STEPS_RBPHD ? "batch_fastslam_cycle_sensed: this batch steps RB-PHD filters (rfsgpu_batch_cycle_async has run): it takes rfsgpu_batch_cycle_sensed_async"
                                                          : "batch_fastslam_cycle_sensed: not a batch of FastSLAM filters yet (rfsgpu_batch_set_fastslam_config, then rfsgpu_batch_fastslam_serve_sensor)");
   if ((rc = fs_sensed_check(f, C, predict, x_cov, cov_stride, false)) != RFSGPU_OK) return rc;
   hipSetDevice(f->device);
@@ -5204,8 +5166,8 @@ int rfsgpu_batch_fastslam_mh_cycle_sensed_async(rfsgpu_filter *f, int predict, c
   const BatchCall &C = BATCH_MH_CYCLE_SENSED;
   int rc = sensor_check(f, C);
   if (rc != RFSGPU_OK) return rc;
-  if (!f->mhBatch)
-    return fail(f, RFSGPU_ERR_UNSUPPORTED, f->bKind == 2 ? "batch_fastslam_mh_cycle_sensed: not a batch of multi-hypothesis FastSLAM filters (rfsgpu_create_batch_mh): a batch of FastSLAM filters takes rfsgpu_batch_fastslam_cycle_sensed_async"
+  if (!batch_is_mh(f))
+    return fail(f, RFSGPU_ERR_UNSUPPORTED, f->bSteps == STEPS_FASTSLAM ? "batch_fastslam_mh_cycle_sensed: not a batch of multi-hypothesis FastSLAM filters (rfsgpu_create_batch_mh): a batch of FastSLAM filters takes rfsgpu_batch_fastslam_cycle_sensed_async"
                                                          : "batch_fastslam_mh_cycle_sensed: not a batch of multi-hypothesis FastSLAM filters (rfsgpu_create_batch_mh): an RB-PHD batch takes rfsgpu_batch_cycle_sensed_async");
   if ((rc = fs_sensed_check(f, C, predict, x_cov, cov_stride, true)) != RFSGPU_OK) return rc;
   if ((rc = batch_mh_cycle_core(f, predict, x, x_cov, cov_stride, nullptr, nullptr, nullptr, call)) != RFSGPU_OK) return rc;
@@ -5217,7 +5179,7 @@ int rfsgpu_batch_resample_sensed_async(rfsgpu_filter *f, unsigned long long call
   const BatchCall &C = BATCH_RESAMPLE_SENSED;
   int rc = sensor_check(f, C);
   if (rc != RFSGPU_OK) return rc;
-  REFUSE_ON_MH_BATCH(f, "rfsgpu_batch_resample_sensed_async (a multi-hypothesis cycle resamples inside the cycle)");
+  if (!batch_fills_blocks(f)) return refuse_on_kind(f, "rfsgpu_batch_resample_sensed_async (a multi-hypothesis cycle resamples inside the cycle)", ON_MH_BATCH);
   if (!f->bSensedTail) return batch_fail(f, C, "no rfsgpu_batch_cycle_sensed_async has run since the last rfsgpu_batch_sense_async: the records on the device are not those of a finished cycle");
   return batch_resample_core(f, C, nullptr, call);
 }
@@ -5251,14 +5213,14 @@ int rfsgpu_batch_last_cycle_lds(rfsgpu_filter *f, long long *bytes) {
 
 // ---- [metric] per-step map error and pose error (map_metric.h) ------------------------------------------------------------------------
 static int metric_check(rfsgpu_filter *f, const char *what) {
-  const char *why = f->D != 2 ? "the Victoria Park model" : (f->fastSlamHandle ? "a FastSLAM handle" : (f->groupShard ? "a shard of an rfsgpu_group" : ((f->mhBatch && !f->mhbMetrics) ? "a batch of multi-hypothesis FastSLAM filters (rfsgpu_create_batch_mh: the step-error kernel assumes that every filter fills its block; rfsgpu_batch_mh_serve_metrics switches its live-count form on)" : nullptr)));
-  if (!why) return RFSGPU_OK;
-  f->err = std::string(what) + ": the device-side map / pose error serves ordinary 2-D RB-PHD handles and filter batches (RB-PHD or FastSLAM) only, not " + why;
+  const bool mhOff = batch_is_mh(f) && !f->mhbMetrics;     // (the step-error kernel assumes that every filter fills its block, until the switch turns its live-count form on)
+  if (f->D == 2 && !f->fastSlamHandle && !f->groupShard && !mhOff) return RFSGPU_OK;
+  f->err = std::string(what) + ": the device-side map / pose error serves ordinary 2-D RB-PHD handles and filter batches (RB-PHD or FastSLAM) only, not " +
+           (f->D != 2 ? "the Victoria Park model" : (f->fastSlamHandle ? "a FastSLAM handle" : handle_kind_text(f)));
+  if (f->D == 2 && !f->fastSlamHandle && mhOff) f->err += ": rfsgpu_batch_mh_serve_metrics switches the live-count form of the step-error kernel on";
   return RFSGPU_ERR_UNSUPPORTED;
 }
 static inline int metric_nf(const rfsgpu_filter *f) { return f->batch ? f->nF : 1; }
-// (FastSLAM filters, single- or multi-hypothesis: a Gaussian's weight is the log-odds of existence)
-static inline bool metric_log_odds(const rfsgpu_filter *f) { return f->bKind == 2 || f->bKind == 3; }
 // One launch into `row` ([nF] records): the call's t / gt_pose go into a slot of the pinned staging ring, which the kernel reads in place.
 // devIn (rfsgpu_batch_run_truth_async): the call's {t, pose} block is a row of the truth tables on the device instead, with a pose.
 static int metric_launch(rfsgpu_filter *f, const double *t, const double *gt_pose, double w_threshold, double cutoff, double order, struct rfsgpu_step_error *row,
@@ -5274,8 +5236,8 @@ static int metric_launch(rfsgpu_filter *f, const double *t, const double *gt_pos
       for (int q = 0; q < 3; q++) h[4 * b + 1 + q] = gt_pose ? gt_pose[3 * b + q] : 0.0;
     }
   }
-  MetricArg A{devIn ? devIn : h, f->dGtXY, f->dGtSeen, f->dGtN, row, w_threshold, cutoff, order, f->batch ? f->nPer : f->N, (gt_pose || devIn) ? 1 : 0, f->holes ? 1 : 0, metric_log_odds(f) ? 1 : 0};
-  if (f->mhBatch) {     // every filter's count is a word of its cycle block, read by the kernel where it runs: nothing waits for it
+  MetricArg A{devIn ? devIn : h, f->dGtXY, f->dGtSeen, f->dGtN, row, w_threshold, cutoff, order, f->batch ? f->nPer : f->N, (gt_pose || devIn) ? 1 : 0, f->holes ? 1 : 0, batch_log_odds(f) ? 1 : 0};
+  if (batch_is_mh(f)) {     // every filter's count is a word of its cycle block, read by the kernel where it runs: nothing waits for it
     FsCycleState S0;
     mhb_view(f, f->mhbBlock, 0, S0);
     map_metric_kernel<<<nF, 64, 0, f->stream>>>(f->B, f->cur, A, MetricLive{S0.w, FSC_WORDS, FSC_N});
@@ -5299,8 +5261,8 @@ static int metric_row(rfsgpu_filter *f) {
 // The switch of a multi-hypothesis batch: off at creation, so the refusals it was published with stand until a caller asks.
 int rfsgpu_batch_mh_serve_metrics(rfsgpu_filter *f, int on) {
   CHECK_HANDLE(f);
-  if (!f->mhBatch) return fail(f, RFSGPU_ERR_UNSUPPORTED, "batch_mh_serve_metrics: not a batch of multi-hypothesis FastSLAM filters (rfsgpu_create_batch_mh)");
-  if (f->vpMh) return fail(f, RFSGPU_ERR_UNSUPPORTED, "batch_mh_serve_metrics: the device-side map / pose error is 2-D: it does not serve a batch of Victoria Park multi-hypothesis FastSLAM filters (rfsgpu_create_batch_vp_mh)");
+  if (!batch_is_mh(f)) return fail(f, RFSGPU_ERR_UNSUPPORTED, "batch_mh_serve_metrics: not a batch of multi-hypothesis FastSLAM filters (rfsgpu_create_batch_mh)");
+  if (batch_is_vp(f)) return fail(f, RFSGPU_ERR_UNSUPPORTED, "batch_mh_serve_metrics: the device-side map / pose error is 2-D: it does not serve a batch of Victoria Park multi-hypothesis FastSLAM filters (rfsgpu_create_batch_vp_mh)");
   hipSetDevice(f->device);
   HIPCHK(hipStreamSynchronize(f->stream));
   f->mhbMetrics = on != 0;
@@ -5360,7 +5322,7 @@ int rfsgpu_error_log_reset(rfsgpu_filter *f) {
 }
 int rfsgpu_step_error_async(rfsgpu_filter *f, const double *t, const double *gt_pose, double w_threshold, double cutoff, double order) {
   if (!f) return RFSGPU_ERR_INVALID;
-  if (!(f->mhBatch && f->mhbMetrics)) {    // (a served multi-hypothesis batch: the kernel reads the counts on the device, so cycles in
+  if (!(batch_is_mh(f) && f->mhbMetrics)) {    // (a served multi-hypothesis batch: the kernel reads the counts on the device, so cycles in
     CHECK_HANDLE(f);                       //  flight stay in flight and a pending overflow is the next synchronising call's to report)
   }
   int rc = metric_check(f, "step_error_async");
@@ -5416,7 +5378,7 @@ int rfsgpu_get_map_estimate(rfsgpu_filter *f, int filter, double w_threshold, in
   int k = 0;
   for (int m = 0; m < cnt; m++) {
     double wm = pl[m];
-    if (metric_log_odds(f)) wm = 1 - 1 / (1 + exp(wm));     // a FastSLAM batch: the existence probability of the log-odds (fastslam2dSim.cpp:628)
+    if (batch_log_odds(f)) wm = 1 - 1 / (1 + exp(wm));     // a FastSLAM batch: the existence probability of the log-odds (fastslam2dSim.cpp:628)
     if ((f->holes && wm < 0) || !(wm >= w_threshold)) continue;
     if (k < max_n) {
       if (w) w[k] = wm;
@@ -5436,7 +5398,7 @@ int rfsgpu_get_map_estimate(rfsgpu_filter *f, int filter, double w_threshold, in
 static inline int estimate_slots(const rfsgpu_filter *f) { return f->batch ? f->nPer : (f->estServe ? f->Ncap : f->N); }
 static int estimate_check(rfsgpu_filter *f, const char *what) { return (f->estServe || f->estServeVpBatch) ? RFSGPU_OK : metric_check(f, what); }
 // (a served handle that has run FastSLAM updates or cycles: log-odds weights, as on a FastSLAM batch)
-static inline bool estimate_log_odds(const rfsgpu_filter *f) { return metric_log_odds(f) || (f->estServe && f->fastSlamHandle); }
+static inline bool estimate_log_odds(const rfsgpu_filter *f) { return batch_log_odds(f) || (f->estServe && f->fastSlamHandle); }
 static void estimate_log_free(rfsgpu_filter *f) {
   hipFree(f->dEstHdr); hipFree(f->dEstGauss); hipFree(f->dEstPart);
   f->dEstHdr = nullptr; f->dEstGauss = nullptr; f->dEstPart = nullptr;
@@ -5465,7 +5427,7 @@ static int estimate_launch(rfsgpu_filter *f, const double *t, double w_threshold
                 f->dEstPart ? f->dEstPart + at * 4 * (size_t)f->estSlots : nullptr, w_threshold, nPer, f->estSlots, f->estMax, f->holes ? 1 : 0,
                 estimate_log_odds(f) ? 1 : 0};
   const dim3 grid(nF, 1 + (f->dEstPart ? (nPer + ESTIMATE_PART_SLOTS - 1) / ESTIMATE_PART_SLOTS : 0));
-  if (f->mhBatch) {     // every filter's count is a word of its cycle block, read by the kernel where it runs: nothing waits for it
+  if (batch_is_mh(f)) {     // every filter's count is a word of its cycle block, read by the kernel where it runs: nothing waits for it
     FsCycleState S0;
     mhb_view(f, f->mhbBlock, 0, S0);
     estimate_log_kernel<<<grid, 64, 0, f->stream>>>(f->B, f->cur, A, MetricLive{S0.w, FSC_WORDS, FSC_N});
@@ -5499,16 +5461,13 @@ int rfsgpu_handle_serve_estimates(rfsgpu_filter *f, int on) {
 // the host never sizes by them), so rfsgpu_step_estimate_async enqueues as it stands on both routes.
 int rfsgpu_batch_vp_serve_estimates(rfsgpu_filter *f, int on) {
   CHECK_HANDLE_HOST(f);
-  if (!f->batch || f->D != 3 || f->mhBatch) {
-    f->err = std::string("batch_vp_serve_estimates: the switch is for a batch of Victoria Park filters (rfsgpu_create_batch with RFSGPU_MODEL_VICTORIAPARK_3D), not ") +
-             (f->batch ? (f->mhBatch ? "a batch of multi-hypothesis FastSLAM filters ([estimate] serves it once rfsgpu_batch_mh_serve_metrics is on)"
-                                     : (f->bKind == 2 ? "a batch of FastSLAM filters ([estimate] serves it as it is: rfsgpu_estimate_log_create)"
-                                                      : "a 2-D batch ([estimate] serves it as it is: rfsgpu_estimate_log_create)"))
-                       : (f->groupShard ? "a shard of an rfsgpu_group (no call of [estimate] serves one: rfsgpu_group_get_poses, rfsgpu_group_get_weights and rfsgpu_group_get_landmark read its state)"
-                                        : "an ordinary handle (rfsgpu_handle_serve_estimates)"));
-    return RFSGPU_ERR_UNSUPPORTED;
-  }
-  if (f->bVpFastSlam)
+  if (!batch_is_vp(f) || batch_is_mh(f))     // (the hint: what serves [estimate] on that handle instead)
+    return refuse_not(f, "batch_vp_serve_estimates: the switch is for a batch of Victoria Park filters (rfsgpu_create_batch with RFSGPU_MODEL_VICTORIAPARK_3D)",
+                      !f->batch ? (f->groupShard ? ": no call of [estimate] serves a shard (rfsgpu_group_get_poses, rfsgpu_group_get_weights and rfsgpu_group_get_landmark read its state)"
+                                                 : ": rfsgpu_handle_serve_estimates is its switch")
+                                : (batch_is_vp(f) ? ": [estimate] does not serve it"
+                                                  : (batch_is_mh(f) ? ": [estimate] serves it once rfsgpu_batch_mh_serve_metrics is on" : ": [estimate] serves it as it is (rfsgpu_estimate_log_create)")));
+  if (f->bSteps == STEPS_FASTSLAM)
     return fail(f, RFSGPU_ERR_UNSUPPORTED, "batch_vp_serve_estimates: this batch steps FastSLAM filters (rfsgpu_batch_vp_serve_fastslam): the [estimate] log does not serve it");
   hipSetDevice(f->device);
   HIPCHK(hipStreamSynchronize(f->stream));
@@ -5556,7 +5515,7 @@ int rfsgpu_step_estimate_async(rfsgpu_filter *f, const double *t, double w_thres
   const bool behind = f->estServe && f->mhcPending && !f->mhcStashedRc && !f->mhbPending && !f->rsPending;
   if (f->estServe) {
     if (!behind && !rc_only_pending(f)) { CHECK_HANDLE(f); }
-  } else if (!(f->mhBatch && f->mhbMetrics)) {    // (as rfsgpu_step_error_async: a served multi-hypothesis batch keeps its cycles in flight)
+  } else if (!(batch_is_mh(f) && f->mhbMetrics)) {    // (as rfsgpu_step_error_async: a served multi-hypothesis batch keeps its cycles in flight)
     CHECK_HANDLE(f);
   }
   int rc = estimate_check(f, "step_estimate_async");
@@ -5723,17 +5682,17 @@ int rfsgpu_batch_run_truth_async(rfsgpu_filter *f, int k_from, int k_to, int tra
   // everything the per-step calls would refuse, before the first of them enqueues anything
   // (the kind: a FastSLAM or multi-hypothesis batch gets here with its switch on only, sensor_check above; a multi-hypothesis cycle
   //  resamples inside the cycle, by thresholds that have defaults, and only RB-PHD filters have births)
-  const int kind = f->mhBatch ? 3 : (f->bKind == 2 ? 2 : 1);
+  const BatchSteps kind = f->bSteps == STEPS_UNDECIDED ? STEPS_RBPHD : f->bSteps;     // (an undecided batch: its first sensed cycle makes it an RB-PHD batch)
   for (int b = 0; b < nF; b++) {
     if (!f->bSensorSet[b]) return batch_fail(f, C, "filter " + std::to_string(b) + " has no sensor (rfsgpu_batch_set_sensor)");
     if (!f->bMotionSet[b]) return batch_fail(f, C, "filter " + std::to_string(b) + " has no motion parameters (rfsgpu_batch_set_motion_odometry)");
-    if (kind != 3 && !f->bResSet[b]) return batch_fail(f, C, "filter " + std::to_string(b) + " has no resampling thresholds (rfsgpu_batch_set_resampling)");
-    if (kind == 1 && f->bCfg[b].birthGaussianMeasurementCountThreshold != 1u) {
+    if (kind != STEPS_MH && !f->bResSet[b]) return batch_fail(f, C, "filter " + std::to_string(b) + " has no resampling thresholds (rfsgpu_batch_set_resampling)");
+    if (kind == STEPS_RBPHD && f->bCfg[b].birthGaussianMeasurementCountThreshold != 1u) {
       f->err = "batch_run_truth: a filter batch takes immediate births only (birthGaussianMeasurementCountThreshold 1)";
       return RFSGPU_ERR_UNSUPPORTED;
     }
   }
-  if (kind != 3 && f->nPer > RFSGPU_BATCH_RESAMPLE_MAX_PER_FILTER) {
+  if (kind != STEPS_MH && f->nPer > RFSGPU_BATCH_RESAMPLE_MAX_PER_FILTER) {
     f->err = "batch_run_truth: more than RFSGPU_BATCH_RESAMPLE_MAX_PER_FILTER particles per filter (one workgroup resamples a filter)";
     return RFSGPU_ERR_UNSUPPORTED;
   }
@@ -5761,9 +5720,9 @@ int rfsgpu_batch_run_truth_async(rfsgpu_filter *f, int k_from, int k_to, int tra
     const unsigned long long call = (unsigned long long)k;
     if ((rc = batch_propagate_core(f, nullptr, nullptr, nullptr, f->dTruthProp + row, call)) != RFSGPU_OK) return rc;
     if ((rc = batch_sense_core(f, nullptr, f->dTruthGt + 3 * row, call)) != RFSGPU_OK) return rc;
-    if (kind == 1) {
+    if (kind == STEPS_RBPHD) {
       if ((rc = rfsgpu_batch_cycle_sensed_async(f, 1, nullptr, nullptr, 0, 1)) != RFSGPU_OK) return rc;
-    } else if (kind == 2) {
+    } else if (kind == STEPS_FASTSLAM) {
       if ((rc = batch_enter_dev_route(f)) != RFSGPU_OK) return rc;     // (as rfsgpu_batch_fastslam_cycle_sensed_async; once per handle)
       if ((rc = batch_fs_cycle_core(f, 1, nullptr, nullptr, 0, nullptr, nullptr, 1)) != RFSGPU_OK) return rc;
       f->bSensed = true;
@@ -5771,7 +5730,7 @@ int rfsgpu_batch_run_truth_async(rfsgpu_filter *f, int k_from, int k_to, int tra
       if ((rc = batch_mh_cycle_core(f, 1, nullptr, nullptr, 0, nullptr, nullptr, nullptr, call)) != RFSGPU_OK) return rc;
       f->bSensed = true;
     }
-    if (kind != 3 && (rc = batch_resample_core(f, BATCH_RESAMPLE_SENSED, nullptr, call, k == k_from)) != RFSGPU_OK) return rc;
+    if (kind != STEPS_MH && (rc = batch_resample_core(f, BATCH_RESAMPLE_SENSED, nullptr, call, k == k_from)) != RFSGPU_OK) return rc;
     if (track_errors) {
       if ((rc = metric_launch(f, nullptr, nullptr, w_threshold, cutoff, order, f->dErrLog + (size_t)f->errLogRows * nF, f->dTruthTgt + 4 * row)) != RFSGPU_OK) return rc;
       f->errLogRows++;
